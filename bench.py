@@ -26,6 +26,11 @@ launch latency.  The interval is the UNION of the rollout kernel and the table r
 first start to last end; `refresh_us` = the helper's own duration, 0 when the launch needed none -- the pass at the head of a launch is
 part of the rollout kernel itself since round 3).  `roofline` = the K timed steps exactly as the driver asked for them (few steps
 right after a reset: launch prologue and drain are not amortised); `steady_state` = a 400-step launch run after the timed region.
+`ms_per_step` = `value`'s wall clock over the K timed steps, per step.
+
+--dump-outputs DIR writes the headline leg's outputs of its last timed step -- what a caller of that path receives: obs.npy (in the
+chosen layout and dtype), reward.npy, done.npy (as float32) -- once the timed region is over.  Inputs are seeded (synthetic trace,
+action tape, noise), so the same arguments give the same inputs on every run and two builds can be compared file by file.
 """
 import argparse
 import json
@@ -39,6 +44,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s measured copy peak
+DUMP_BYTES = 60 << 20       # --dump-outputs: cap on the array bytes written over all ranks (with the .npy headers: < 64 MB)
 
 
 def algorithmic_bytes_per_env_step(obs_dim, out_bytes, path):
@@ -164,7 +170,12 @@ def main():
                     help="BASELINE.json configs[4]'s per-rank leg: business scenarios 1, 2, 3 mixed inside the batch (global env e -> scenario e %% 3), one operation level")
     ap.add_argument("--no-boundary-leg", dest="boundary_leg", action="store_false",
                     help="skip the episode_boundary leg (a window that contains the episode end + the finished-episode all-gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its last timed step to DIR/<name>.npy (obs, reward, done; float32 / "
+                         "float64, at most 64 MB in all: beyond that a fixed sample of envs, listed in env_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)                     # no launcher: this process becomes the launcher (and never touches a GPU)
@@ -217,8 +228,23 @@ def main():
     first_ptr, stride = ptg_dist.episode_plan(n_total, world, rank)
     STEADY_T = 400
 
-    def measure(path, launch, layout, out_dtype, steady):
-        """W warm-up steps, then exactly K timed steps of `path`.  Returns a dict: wall seconds, per-launch kernel times, ..."""
+    def last_step_outputs(obs, rew, done, feature_major, budget):
+        """{name: host array} of one vector step's outputs as the caller got them (obs [N, F], or [F, N] feature-major; rew [N];
+        done [N] as float32).  Over `budget` bytes: a fixed sample of envs (seed 0, ascending env indices, saved as env_index)."""
+        n = rew.shape[0]
+        per_env = obs.element_size() * (obs.numel() // n) + rew.element_size() + 4
+        out = {}
+        if n * per_env > budget:
+            idx = np.sort(np.random.default_rng(0).choice(n, budget // (per_env + 8), replace=False))
+            it = torch.from_numpy(idx).to(rew.device)
+            obs, rew, done = obs.index_select(1 if feature_major else 0, it), rew.index_select(0, it), done.index_select(0, it)
+            out["env_index"] = idx.astype(np.float64)
+        out.update(obs=obs.cpu().numpy(), reward=rew.cpu().numpy(), done=done.cpu().numpy().astype(np.float32))
+        return out
+
+    def measure(path, launch, layout, out_dtype, steady, dump=False):
+        """W warm-up steps, then exactly K timed steps of `path`.  Returns a dict: wall seconds, per-launch kernel times, ...
+        dump: also the outputs of the last timed step on the host (res["dump"]), copied before anything else runs on the handle."""
         torch.cuda.empty_cache()                              # each leg starts from a fresh allocator state (no recycled multi-GB blocks)
         eng = HipEngine(spec.consts, spec.tables, spec.markets, n, device=local_rank, out_dtype=out_dtype, obs_layout=layout, obs_pitch="auto")
         F = eng.obs_dim
@@ -320,6 +346,10 @@ def main():
         if multi:
             dist.barrier()
         eng.sync()
+        dumped = None
+        if dump:                                   # before the eager re-run / steady-state launches below overwrite these buffers
+            last = (bufs[0][K - 1], bufs[1][K - 1], bufs[2][K - 1]) if path == "rollout" else (eng.obs, eng.rew, eng.done)
+            dumped = last_step_outputs(*last, layout == "feature", DUMP_BYTES // world)
         span_ms = ev0.elapsed_time(ev1) if graph is not None else 0.0      # stream events around the replayed graph (host launch latency included)
         launch_us = kernel_us = helper_us = None
         if graph is None:
@@ -335,7 +365,8 @@ def main():
             eng.profile(False)
         res = {"pitch": eng.pitch if layout == "feature" else None, "elapsed": elapsed, "span_ms": span_ms, "launch_us": launch_us, "kernel_us": kernel_us, "helper_us": helper_us, "n_launch": n_launch,
                "n_fin": len(r_all), "F": F, "steady": None, "rerun": graph is not None, "boundary": boundary, "steps_to_episode_end": s_end,
-               "elapsed_rank": elapsed, "device_us_rank": float(np.sum(launch_us)) if launch_us is not None else span_ms * 1e3}
+               "elapsed_rank": elapsed, "device_us_rank": float(np.sum(launch_us)) if launch_us is not None else span_ms * 1e3,
+               "dump": dumped}
         if extra:                                             # steady state: two more 400-step launches, the second one counted
             eng.profile(True)
             for q in range(2):
@@ -404,8 +435,8 @@ def main():
         per = ent["bytes_per_step"] * steps_per_launch if path == "rollout" else ent["bytes_per_launch"]
         return per, tj.get("source")
 
-    def leg(path, layout, dtype, steady=False):
-        res = measure(path, args.launch, layout, dtype, steady)
+    def leg(path, layout, dtype, steady=False, dump=False):
+        res = measure(path, args.launch, layout, dtype, steady, dump)
         ob = 4 if dtype == "float32" else 8
         roof = roofline(path, res, ob, K)
         roof["traffic"], src = traffic(path, layout, dtype, roof["steps_per_launch"])
@@ -489,8 +520,9 @@ def main():
     order = os.environ.get("PTG_BENCH_ORDER", "head_first")          # experiment knob: "head_last" runs the other legs before the headline leg
     if os.environ.get("PTG_BENCH_WAKE"):
         wake()
+    dump = args.dump_outputs is not None
     if order == "head_first":
-        head, res = leg(args.path, args.obs_layout, args.out_dtype, steady=args.steady and n <= 131072)     # (400-step buffers: 3.7 GB per 65 536 envs)
+        head, res = leg(args.path, args.obs_layout, args.out_dtype, steady=args.steady and n <= 131072, dump=dump)     # (400-step buffers: 3.7 GB per 65 536 envs)
     also = {}
     if args.also:
         other = "rollout" if args.path == "step" else "step"
@@ -500,7 +532,12 @@ def main():
         if args.out_dtype == "float32":                   # the reference's declared dtype (env/ptg_gym_env.py:166-202): float64 observations / rewards
             also["rollout_" + args.obs_layout + "_float64"] = leg("rollout", args.obs_layout, "float64")[0]
     if order != "head_first":
-        head, res = leg(args.path, args.obs_layout, args.out_dtype, steady=args.steady and n <= 131072)
+        head, res = leg(args.path, args.obs_layout, args.out_dtype, steady=args.steady and n <= 131072, dump=dump)
+    if dump:                                                  # every rank its own files (suffix _rank<r> when there are several)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = f"_rank{rank}" if world > 1 else ""
+        for name, a in res["dump"].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}{tag}.npy"), a)
 
     boundary = None
     if args.boundary_leg:
