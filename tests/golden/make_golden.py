@@ -249,6 +249,41 @@ def main():
         pt, ft = set(out["ints"][..., 6].reshape(-1).tolist()), set(out["ints"][..., 7].reshape(-1).tolist())
         assert pt >= {5, 8, 9, 10, 11, 12} and ft >= {6, 7, 13, 14, 15, 16}, (pt, ft)
         s.close()
+
+    # ---------------- cells added later: each with its own generator, so the files above regenerate byte for byte ----------------
+    print("real / BS2 / OP2 / val split, eval mode, one whole validation episode")
+    s = rd.RefSetup(dict(scenario=2, operation="OP2"))
+    t_end = int(s.pre.eps_sim_steps_val) - 6              # step index of the termination (8 634), then 10 post-reset steps
+    n_val = t_end + 1 + 10
+    out = save_traj("real_bs2_op2_mod_disc_evalval_full", s, "real_bs2_OP2", "val", "eval",
+                    sticky_tape(np.random.default_rng(2001), n_val, 1), 605,
+                    note="the whole validation episode: its last steps read gas / EUA day D with D + 2 == n_days")
+    assert np.nonzero(out["done"][:, 0])[0].tolist() == [t_end], np.nonzero(out["done"][:, 0])[0]
+    s.close()
+
+    print("real / BS3 / OP2 / raw features")
+    s = rd.RefSetup(dict(scenario=3, operation="OP2"))
+    save_traj("real_bs3_op2_raw_disc_train", s, "real_bs3_OP2", "train", "train",
+              np.random.default_rng(2002).integers(0, 5, (600, 2)), 3655, dict(raw_modified="raw"),
+              note="BS3 gas / EUA are 0: the normalised raw features are negative constants")
+    s.close()
+
+    print("real / BS1 / OP1 / continuous actions")
+    s = rd.RefSetup(dict(scenario=1, operation="OP1"))
+    g = np.random.default_rng(2003)
+    save_traj("real_bs1_op1_mod_cont_train", s, "real_bs1_OP1", "train", "train",
+              to_continuous(g, sticky_tape(g, 700, 2)), 468, dict(action_type="continuous"))
+    s.close()
+
+    print("synthetic / BS1 / OP1 / sim_step 60, raw features, continuous actions")
+    s = rd.RefSetup(dict(scenario=1, operation="OP1", eps_len_d=1, sim_step=60), synthetic_market=sm, train_steps=200000)
+    g = np.random.default_rng(2004)
+    out = save_traj("synth_bs1_op1_raw_cont_s60_toggle", s, "synth_bs1_OP1", "train", "train",
+                    to_continuous(g, toggler_tape(g, 2600, 2)), 44, dict(raw_modified="raw", action_type="continuous"),
+                    note="sim_step=60 toggler decoded from continuous actions, raw features: every ladder rung")
+    pt, ft = set(out["ints"][..., 6].reshape(-1).tolist()), set(out["ints"][..., 7].reshape(-1).tolist())
+    assert pt >= {5, 8, 9, 10, 11, 12} and ft >= {6, 7, 13, 14, 15, 16}, (pt, ft)
+    s.close()
     print("done")
 
 

@@ -1,4 +1,5 @@
 """Shared fixture loading for the parity tests (test infrastructure; may import the oracle)."""
+import atexit
 import glob
 import json
 import os
@@ -15,6 +16,39 @@ TRAJ_CASES = sorted(os.path.basename(p)[5:-4] for p in glob.glob(os.path.join(GO
 PREP_CASES = sorted(os.path.basename(p)[5:-4] for p in glob.glob(os.path.join(GOLD, "prep_*.npz")))
 
 _cache = {}
+
+# the reward contract: float64 outputs share the reference's operand order (a few ulp); float32 outputs are one rounding of the
+# float64 value (2^-24 relative), so rtol 2e-7 with a floor far below the smallest nonzero reward of the fixtures (3.1e-6);
+# an exact zero of the reference stays exactly zero in both
+RTOL64, ATOL64 = 1e-11, 1e-13
+RTOL32, ATOL32 = 2e-7, 1e-9
+
+
+def assert_rewards(got, ref, out_dtype, err_msg=""):
+    """Rewards of a HIP path against a float64 reference under the contract above.  With PTG_REWARD_ERR_LOG=<file>, the largest
+    relative error over the nonzero reference rewards of each test is written to <file> when the process exits."""
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    assert out_dtype in ("float32", "float64"), out_dtype
+    rtol, atol = (RTOL64, ATOL64) if out_dtype == "float64" else (RTOL32, ATOL32)
+    np.testing.assert_allclose(got, ref, rtol=rtol, atol=atol, err_msg=err_msg)
+    z = ref == 0.0
+    assert np.all(got[z] == 0.0), f"{err_msg}: nonzero reward where the reference has exactly 0.0: {got[z][got[z] != 0.0][:8]}"
+    if os.environ.get("PTG_REWARD_ERR_LOG") and (~z).any():
+        rel = float(np.max(np.abs(got[~z] - ref[~z]) / np.abs(ref[~z])))
+        key = (os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0], out_dtype)
+        if not _reward_err:
+            atexit.register(_write_reward_err)
+        _reward_err[key] = max(rel, _reward_err.get(key, 0.0))
+
+
+_reward_err = {}
+
+
+def _write_reward_err():
+    with open(os.environ["PTG_REWARD_ERR_LOG"], "a") as f:
+        for (test, dt), rel in sorted(_reward_err.items()):
+            f.write(f"{test}\t{dt}\t{rel:.3e}\n")
 
 
 def load_npz(path):

@@ -41,7 +41,7 @@ def test_trajectory_vs_reference_golden(case, out_dtype, layout):
         eng.sync()
         obs, rew, done = eng.rows(obs).cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy()
         assert np.array_equal(done, tr["done"][t]), f"done differs at step {t}"
-        np.testing.assert_allclose(rew, tr["f64s"][t, :, 0], rtol=rtol, atol=atol, err_msg=f"reward, step {t}")
+        H.assert_rewards(rew, tr["f64s"][t, :, 0], out_dtype, err_msg=f"reward, step {t}")
         ret_acc += tr["f64s"][t, :, 0]
         final = eng.rows(eng.final_obs).cpu().numpy()
         any_done = bool(done.any())
@@ -239,7 +239,7 @@ def test_full_size_properties_n65536():
         a64.sync(); a32.sync()
         o64n, o32n = o64.cpu().numpy(), a32.rows(o32).cpu().numpy()
         np.testing.assert_allclose(o32n, o64n, rtol=RTOL32, atol=ATOL32)
-        np.testing.assert_allclose(r32.cpu().numpy(), r64.cpu().numpy(), rtol=RTOL32, atol=1e-6)
+        H.assert_rewards(r32.cpu().numpy(), r64.cpu().numpy(), "float32", err_msg=f"reward step {t}")
         assert np.array_equal(b32.rows(ro[t]).cpu().numpy(), o32n[perm])           # (1) + (2)
         assert np.array_equal(rr[t].cpu().numpy(), r32.cpu().numpy()[perm])
         assert np.array_equal(o32n[: n // 2], np.broadcast_to(o32n[0], (n // 2, o32n.shape[1])))   # (4)
@@ -318,7 +318,7 @@ def test_full_size_properties_n262144_bs3():
         a64.sync(); a32.sync()
         assert np.array_equal(ro[t].cpu().numpy(), o32.cpu().numpy()) and np.array_equal(rr[t].cpu().numpy(), r32.cpu().numpy())
         np.testing.assert_allclose(o32.cpu().numpy(), o64.cpu().numpy(), rtol=RTOL32, atol=ATOL32)
-        np.testing.assert_allclose(r32.cpu().numpy(), r64.cpu().numpy(), rtol=RTOL32, atol=1e-6)
+        H.assert_rewards(r32.cpu().numpy(), r64.cpu().numpy(), "float32", err_msg=f"reward step {t}")
     for f in INT_FIELDS:
         assert np.array_equal(a32.get_state(f), a64.get_state(f)) and np.array_equal(b32.get_state(f), a32.get_state(f)), f
     assert int(rd.sum()) == 0
@@ -415,7 +415,7 @@ def test_differential_vs_oracle_other_step_sizes(sim_step, action_type, raw_modi
         eng.sync()
         o_ref, r_ref, d_ref, _, _ = ora.step(acts)
         np.testing.assert_allclose(eng.rows(o).cpu().numpy(), o_ref, rtol=rtol, atol=atol, err_msg=f"obs step {t}")
-        np.testing.assert_allclose(r.cpu().numpy(), r_ref, rtol=rtol, atol=max(atol, 1e-6 if out_dtype == "float32" else 0), err_msg=f"reward step {t}")
+        H.assert_rewards(r.cpu().numpy(), r_ref, out_dtype, err_msg=f"reward step {t}")
         assert np.array_equal(d.cpu().numpy(), d_ref)
     ints, f64s = ora.state()
     for col, name in [(0, "meth_state"), (1, "i"), (2, "j"), (3, "hot_cold"), (4, "standby_tid"), (5, "startup_tid"),
@@ -593,14 +593,18 @@ def test_sb3_flat_layout_equals_flattened_dict_observation(raw_modified, out_dty
     assert torch.equal(ff, flat(fr))                      # terminal observations in the flat layout
 
 
+INFO_CASES = [c for c in H.TRAJ_CASES if "infos" in np.load(f"{H.GOLD}/traj_{c}.npz").files]
+
+
 @pytest.mark.gpu
-def test_rollout_info_stream_equals_reference_infos():
+@pytest.mark.parametrize("case", INFO_CASES)
+def test_rollout_info_stream_equals_reference_infos(case):
     """§8(f) rank 4: the 24 `_get_info` fields of every step recorded on the device ([T][N][24]) == the info dicts of the
     unmodified reference (golden fixture), and the `stats` table Postprocessing.test_performance builds from them
-    (src/rl_utils.py:528-565: key order of stats_names, Meth_Action as its index, zero rows at terminated steps)."""
+    (src/rl_utils.py:528-565: key order of stats_names, Meth_Action as its index, zero rows at terminated steps), for every env
+    of every eval-mode fixture.  real_bs2_op2_mod_disc_evalval_full terminates, so its table has a zero row."""
     from rl_ptg_amd.vec_env import stats_table, INFO_KEYS
     from rl_ptg_amd.config import STATS_NAMES
-    case = next(c for c in H.TRAJ_CASES if "infos" in H.load_traj(c)[0])
     tr, eng = H.make_engine(case, "float64", obs_layout="row")
     eng.reset()
     obs, rew, done, info = eng.rollout_info(tr["actions"])
@@ -609,14 +613,68 @@ def test_rollout_info_stream_equals_reference_infos():
     assert tuple(info.shape) == (K, n, 24) and len(INFO_KEYS) == len(STATS_NAMES) == 24
     np.testing.assert_allclose(info.cpu().numpy(), tr["infos"], rtol=RTOL64, atol=ATOL64)
     assert np.array_equal(done.cpu().numpy(), tr["done"])
-    np.testing.assert_allclose(rew.cpu().numpy(), tr["f64s"][:, :, 0], rtol=RTOL64, atol=ATOL64)
-    tab = stats_table(info[:, 0], done[:, 0])
-    assert list(tab) == list(STATS_NAMES)
-    exp = tr["infos"][:, 0].copy()
-    exp[tr["done"][:, 0].astype(bool)] = 0.0
-    for m, nme in enumerate(STATS_NAMES):
-        np.testing.assert_allclose(tab[nme], exp[:, m], rtol=RTOL64, atol=ATOL64)
+    H.assert_rewards(rew.cpu().numpy(), tr["f64s"][:, :, 0], "float64")
+    for e in range(n):
+        tab = stats_table(info[:, e], done[:, e])
+        assert list(tab) == list(STATS_NAMES)
+        exp = tr["infos"][:, e].copy()
+        exp[tr["done"][:, e].astype(bool)] = 0.0
+        for m, nme in enumerate(STATS_NAMES):
+            np.testing.assert_allclose(tab[nme], exp[:, m], rtol=RTOL64, atol=ATOL64)
+        for t in np.nonzero(tr["done"][:, e])[0]:
+            assert all(float(tab[nme][t]) == 0.0 for nme in STATS_NAMES)
+    if case.endswith("_full"):
+        assert int(tr["done"].sum()) == 1
     eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route,out_dtype", [("rollout", "float32"), ("rollout", "float64"), ("step", "float32"), ("generic", "float64")])
+def test_whole_validation_episode_ends_at_the_series_end(route, out_dtype):
+    """The reference's validation episode run to its real end (eval mode, no episode plan: 8 640 - 6 steps).  Its last steps read
+    gas / EUA day D with D + 2 == n_days, the exact boundary of the kernels' range check: no PtgError may be raised there, done
+    is set at step 8 634 and nowhere else, and the env restarts at act_ep_d == 0.  route: the fused rollout (hot kernel up to the
+    terminating step), per-step launches, or the generic kernels alone (PTG_NO_HOT_KERNELS)."""
+    import os
+    case = "real_bs2_op2_mod_disc_evalval_full"
+    tr, consts, _, market = H.load_traj(case)
+    K = tr["actions"].shape[0]
+    t_end = consts["eps_sim_steps"] - 6
+    assert t_end == 8634 and np.nonzero(tr["done"][:, 0])[0].tolist() == [t_end] and K == t_end + 11
+    assert (t_end + 1) * consts["sim_step"] // 86400 + 2 == len(market["gas"]) == len(market["eua"])
+    assert market["eps_ind"] is None and tr["post_reset_int"][0, 11] == 0
+    if route == "generic":
+        os.environ["PTG_NO_HOT_KERNELS"] = "1"
+    try:
+        _, eng = H.make_engine(case, out_dtype)
+        eng.reset()
+        if route == "step":
+            rew = np.zeros(K)
+            for t in range(K):
+                o, r, d = eng.step(tr["actions"][t])
+                eng.sync()                                       # raises PtgError if the range flag was set on this step
+                rew[t] = float(r.cpu()[0])
+                assert bool(d.cpu()[0]) == (t == t_end), t
+                if t == t_end:
+                    assert np.array_equal(_ints(eng)[0], tr["post_reset_int"][0]) and eng.get_state("act_ep_d")[0] == 0
+        else:
+            parts = []
+            for t0 in range(0, K, 2000):                         # the last chunk holds the terminating step
+                o, r, d = eng.rollout(tr["actions"][t0:t0 + 2000])
+                eng.sync()
+                parts.append((r.cpu().numpy()[:, 0], d.cpu().numpy()[:, 0]))
+            rew = np.concatenate([p[0] for p in parts])
+            done = np.concatenate([p[1] for p in parts])
+            assert np.nonzero(done)[0].tolist() == [t_end]
+        H.assert_rewards(rew, tr["f64s"][:, 0, 0], out_dtype)
+        ints = _ints(eng)
+        assert np.array_equal(ints[0], tr["ints"][K - 1, 0]) and ints[0, 11] == 0     # 10 steps into the next episode, from day 0
+        r, l, ids = eng.finished_episodes()
+        assert l.tolist() == [t_end + 1] and ids.tolist() == [0]
+        assert abs(r[0] - tr["f64s"][:t_end + 1, 0, 0].sum()) <= 1e-9 * np.abs(tr["f64s"][:t_end + 1, 0, 0]).sum()
+        eng.close()
+    finally:
+        os.environ.pop("PTG_NO_HOT_KERNELS", None)
 
 
 @pytest.mark.gpu

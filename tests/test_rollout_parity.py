@@ -39,7 +39,7 @@ def test_rollout_vs_reference_golden(case, out_dtype, layout):
     eng.sync()
     obs, rew, done = eng.rows(obs).cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy()
     assert np.array_equal(done, tr["done"])
-    np.testing.assert_allclose(rew, tr["f64s"][:, :, 0], rtol=rtol, atol=atol)
+    H.assert_rewards(rew, tr["f64s"][:, :, 0], out_dtype)
     want = tr["obs"].copy()                                   # [K, n, F] canonical; finished envs show the post-reset observation
     for q, (t, e) in enumerate(tr["post_reset_at"].tolist()):
         want[t, e] = tr["post_reset_obs"][q]
@@ -112,14 +112,14 @@ def test_config2_hot_kernels_vs_oracle_n4096(out_dtype, layout):
         o, r, d = eng.step(acts[t])
         eng.sync()
         np.testing.assert_allclose(eng.rows(o).cpu().numpy(), refs[t][0], rtol=rtol, atol=atol, err_msg=f"step {t}")
-        np.testing.assert_allclose(r.cpu().numpy(), refs[t][1], rtol=rtol, atol=max(atol, 1e-6 if out_dtype == "float32" else 0))
+        H.assert_rewards(r.cpu().numpy(), refs[t][1], out_dtype, err_msg=f"reward step {t}")
         assert np.array_equal(d.cpu().numpy(), refs[t][2])
     o, r, d = eng.rollout(acts[K1:])
     eng.sync()
     o, r = eng.rows(o).cpu().numpy(), r.cpu().numpy()
     for t in range(K2):
         np.testing.assert_allclose(o[t], refs[K1 + t][0], rtol=rtol, atol=atol, err_msg=f"fused step {t}")
-        np.testing.assert_allclose(r[t], refs[K1 + t][1], rtol=rtol, atol=max(atol, 1e-6 if out_dtype == "float32" else 0))
+        H.assert_rewards(r[t], refs[K1 + t][1], out_dtype, err_msg=f"reward fused step {t}")
     ints, f64s = ora.state()
     for col, name in enumerate(INT_FIELDS):
         assert np.array_equal(eng.get_state(name), ints[:, col]), name
@@ -174,7 +174,7 @@ def test_full_size_slice_vs_oracle(n, scenario, operation, noise, out_dtype):
     for t in range(K):
         o_ref, r_ref, d_ref, _, _ = ora.step(a_host[t])
         np.testing.assert_allclose(o[t], o_ref, rtol=rtol, atol=atol, err_msg=f"step {t}")
-        np.testing.assert_allclose(r[t], r_ref, rtol=rtol, atol=max(atol, 1e-6 if out_dtype == "float32" else 0))
+        H.assert_rewards(r[t], r_ref, out_dtype, err_msg=f"reward step {t}")
     ints, f64s = ora.state()
     for col, name in enumerate(INT_FIELDS):
         assert np.array_equal(eng.get_state(name)[lo:lo + m], ints[:, col]), name
@@ -209,7 +209,6 @@ def test_real_training_set_every_env_its_own_episode_vs_oracle(scenario, operati
     ora = H.po.OracleVecEnv(consts, spec.tables, dict(m, eps_ind=spec.eps_ind), n, ep_index0=0)
     ora.set_noise_tape(tape)
     rtol, atol = (RTOL64, ATOL64) if out_dtype == "float64" else (RTOL32, ATOL32)
-    ratol = max(atol, 1e-6 if out_dtype == "float32" else 0)
     o_ref, _ = ora.reset()
     np.testing.assert_allclose(eng.rows(eng.reset()).cpu().numpy(), o_ref, rtol=rtol, atol=atol)
     assert len(np.unique(eng.get_state("act_ep_d"))) > 30          # the envs really are spread over the episodes
@@ -228,7 +227,7 @@ def test_real_training_set_every_env_its_own_episode_vs_oracle(scenario, operati
         eng.sync()
         o_ref, r_ref, d_ref, _, _ = ora.step(a)
         np.testing.assert_allclose(eng.rows(o).cpu().numpy(), o_ref, rtol=rtol, atol=atol, err_msg=f"obs step {t}")
-        np.testing.assert_allclose(r.cpu().numpy(), r_ref, rtol=rtol, atol=ratol, err_msg=f"reward step {t}")
+        H.assert_rewards(r.cpu().numpy(), r_ref, out_dtype, err_msg=f"reward step {t}")
     acts = np.stack([acts_at(K1 + t) for t in range(K2)])
     obs, rew, done = eng.rollout(acts)
     eng.sync()
@@ -236,7 +235,7 @@ def test_real_training_set_every_env_its_own_episode_vs_oracle(scenario, operati
     for t in range(K2):
         o_ref, r_ref, d_ref, _, _ = ora.step(acts[t])
         np.testing.assert_allclose(eng.rows(obs[t]).numpy(), o_ref, rtol=rtol, atol=atol, err_msg=f"obs fused step {t}")
-        np.testing.assert_allclose(rew[t], r_ref, rtol=rtol, atol=ratol, err_msg=f"reward fused step {t}")
+        H.assert_rewards(rew[t], r_ref, out_dtype, err_msg=f"reward fused step {t}")
     ints, f64s = ora.state()
     got = _ints(eng)
     assert np.array_equal(got[:, :10], ints[:, :10]) and np.array_equal(got[:, 11], ints[:, 11])

@@ -45,7 +45,7 @@ def test_vec_env_matches_reference_stack(case):
         obs, rew, done, infos = env.step(a.reshape(n, 1) if kw["action_type"] == "continuous" else a)
         assert rew.dtype == np.float32 and done.dtype == bool and len(infos) == n
         assert np.array_equal(done, tr["done"][t].astype(bool))
-        np.testing.assert_allclose(rew, tr["f64s"][t, :, 0].astype(np.float32), rtol=1e-6, atol=1e-6)
+        H.assert_rewards(rew, tr["f64s"][t, :, 0], "float32", err_msg=f"reward step {t}")
         ret += tr["f64s"][t, :, 0]
         flat = _flat(obs, order)
         for e in range(n):
@@ -99,7 +99,7 @@ def test_single_env_adapter_eval_mode():
         obs, r, term, trunc, info = env.step(int(tr["actions"][t, 0]))
         assert trunc is False and term is False and isinstance(r, float)
         np.testing.assert_allclose(_flat({k: np.asarray([v]) for k, v in obs.items()}, order)[0], tr["obs"][t, 0], rtol=RTOL, atol=ATOL)
-        assert abs(r - tr["f64s"][t, 0, 0]) <= 1e-6 * max(1.0, abs(tr["f64s"][t, 0, 0]))
+        H.assert_rewards([r], tr["f64s"][t, :1, 0], "float32", err_msg=f"reward step {t}")
         assert info["step"] == t and abs(info["cum_reward"] - tr["f64s"][t, 0, 1]) < 1e-8
         tot += r
     env.close()
