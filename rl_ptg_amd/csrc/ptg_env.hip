@@ -816,11 +816,7 @@ typedef double vd2 __attribute__((ext_vector_type(2)));
 template <typename T>
 __device__ __forceinline__ void st_off(void* base, unsigned byte_off, T v)
 {
-#ifdef PTG_PLAIN_STORES
-    *(T*)((char*)base + byte_off) = v;
-#else
     __builtin_nontemporal_store(v, (T*)((char*)base + byte_off));
-#endif
 }
 
 enum { LAD_T1_START_P_F = 0, LAD_T2_START_F_P, LAD_T_P_F, LAD_T_F_P, LAD_T1_P_F_P, LAD_T2_P_F_P, LAD_T3_P_F_P, LAD_T34_P_F_P,
@@ -1428,7 +1424,7 @@ __device__ __forceinline__ void pc_load_market(const HotParams& P, unsigned hb4,
 // reset (or under a policy that drives every env alike) the envs walk through the tables as a front, every step gathers lines
 // nobody has touched since the output stream (9.8 MB per step at 65 536 envs) flushed them from the Infinity Cache, and each
 // of those misses goes to DRAM underneath a saturated write stream: measured 2.5 us per step instead of 1.5 for the first
-// ~270 steps after a reset (tools/fresh20.py, tools/phase_pmc.sh: same instruction counts, read latency + 40 %, TCP pending-line
+// ~270 steps after a reset (profiles/r02_fresh20.txt, profiles/r02_phase_pmc.txt: same instruction counts, read latency + 40 %, TCP pending-line
 // stalls + 50 %; touching the tables right before a launch removes it).  k_refresh runs BESIDE k_rollout_pc, on a stream of its
 // own (one 64-lane workgroup per CU, no LDS, a handful of registers: it fits next to the rollout's workgroup): it re-reads its
 // 1 / gridDim share of the records and keys `passes` times, one pass per `period` ticks of the 100 MHz clock.  The loads are
@@ -1449,19 +1445,17 @@ __device__ __forceinline__ void refresh_rows(const void* __restrict__ recs, cons
     }
 }
 
-// Pass p (p = p0 .. passes - 1) starts p periods after the kernel did.  p0 = 1: the launch's head pass is done by the rollout kernel
-// itself, in its prologue (k_rollout_pc, `refresh_rec`), and this kernel -- forked from the rollout's stream right before it, so it
-// starts when the rollout does -- only adds the rolling passes of a long launch over a batch that is still a front.
+// The rolling passes of a long launch over a batch that is still a front.  Pass 0, the head pass, is done by the rollout kernel
+// itself, in its prologue (k_rollout_pc, `refresh_rec`); this kernel -- forked from the rollout's stream right before it, so it
+// starts when the rollout does -- runs passes 1 .. passes - 1, pass p starting p periods after the kernel did.
 __global__ void __launch_bounds__(64)
-k_refresh(const void* __restrict__ recf, const unsigned short* __restrict__ rkey, int n_rec, int p0, int passes, unsigned period)
+k_refresh(const void* __restrict__ recf, const unsigned short* __restrict__ rkey, int n_rec, int passes, unsigned period)
 {
     uv4 sink = {0u, 0u, 0u, 0u};
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (int p = p0; p < passes; p++) {
-        if (p > 0) {                                        // pace (the clock only runs forward)
-            const unsigned long long target = t0 + (unsigned long long)p * period;
-            while (__builtin_amdgcn_s_memrealtime() < target) __builtin_amdgcn_s_sleep(64);
-        }
+    for (int p = 1; p < passes; p++) {
+        const unsigned long long target = t0 + (unsigned long long)p * period;      // pace (the clock only runs forward)
+        while (__builtin_amdgcn_s_memrealtime() < target) __builtin_amdgcn_s_sleep(64);
         refresh_rows(recf, rkey, (unsigned)n_rec, blockIdx.x, gridDim.x, 0u, 1u, threadIdx.x, sink);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1699,9 +1693,6 @@ k_rollout_pc(const HotParams P, const void* __restrict__ actions, int actk, int 
     // hand-off barrier: only the LDS traffic has to be complete.  __syncthreads() would also drain vmcnt -- the consumers'
     // stores and the gathers just issued -- once per step, which serialises exactly what this kernel overlaps
     auto handoff = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-#ifdef PTG_ABLATE_KEYLAG      // TIMING-ONLY ablation (wrong results): the state machine consumes the key gathered TWO steps ago (two registers used in
-    unsigned tkB = 0;         // turn), so the newest gather is never on the loop-carried chain: the upper bound of what any key run-ahead / speculation
-#endif                        // scheme could gain for chain-bound shapes (small batches, SPLIT rows); tools/r03_keylag.sh
     Ladder G;                                               // producers: the ladder thresholds, in registers for the whole launch
     int code_nx = 0;                                        // producers: the NEXT step's action byte, read one step ahead of its use --
     if (producer) { load_ladder(L, G); code_nx = s_act[lx]; }      // its address depends on nothing, its LDS latency need not sit on the chain
@@ -1723,7 +1714,7 @@ k_rollout_pc(const HotParams P, const void* __restrict__ actions, int actk, int 
         slot[it & 1].w[lx] = (unsigned)ridx | ((R.flags & 7u) << 24) | (changed ? (1u << 27) : 0u) |
                              (((R.flags >> 12) & 7u) << 28) | (((R.flags >> 3) & 1u) << 31);       // + action, hot / cold: the info rows' fields
     };
-    auto produce = [&](const int it) { produce_(it, tk); };
+    auto produce = [&](const int it) { produce_(it, tk); };      // (one lambda capturing tk compiles the float32 kernels differently: vmcnt waits move)
     auto request = [&](const int t, rec_t& rec, unsigned& w) {                    // consumer: record gather of step t
         w = slot[t & 1].w[lx];
         rec = ld_off<rec_t>(rec_table(P, (const rec_t*)nullptr), (w & 0xFFFFFFu) * 64u);
@@ -1820,15 +1811,7 @@ k_rollout_pc(const HotParams P, const void* __restrict__ actions, int actk, int 
     // made it drain the whole queue at the top of every consumer iteration).
     if (producer) {
         if (NOISE == NOISE_TAPE) z_next = P.tape[(size_t)((unsigned)R.nctr % (unsigned)P.tape_len) * P.N + e];
-#ifdef PTG_ABLATE_KEYLAG
-        {
-            int it = 0;
-            for (; it + 1 < T; it += 2) { produce_(it, tk); handoff(); produce_(it + 1, tkB); handoff(); }
-            if (it < T) { produce_(it, tk); handoff(); }
-        }
-#else
         for (int it = 0; it < T; it++) { produce(it); handoff(); if (it == 0) PTG_STAMP(4); if (it == 1) PTG_STAMP(5); }
-#endif
         PTG_STAMP(6);
         handoff();
     } else {
@@ -2067,12 +2050,9 @@ struct ptg_env {
     int* d_eps_ind = nullptr;
     // experiment knobs, read from the environment ONCE in ptg_create (PTG_NO_HOT_KERNELS, PTG_NO_LDS_LUT, PTG_NO_REFRESH, PTG_REFRESH_ALWAYS, PTG_PC_CHUNK, PTG_BLOCK)
     bool knob_no_hot = false, knob_no_lds_lut = false, knob_no_refresh = false, knob_refresh_always = false;
-    bool knob_capture_fork = false;      // PTG_REFRESH_CAPTURE_FORK: capture k_refresh as a forked branch of the graph (measured slower: the branches replay serially)
-    int knob_refresh_mode = 0;   // PTG_REFRESH_MODE: 0 head pass in the rollout's prologue + forked rolling passes (default), 1 "legacy" (round 2:
-                                 // k_refresh enqueued ahead of the rollout, unordered), 2 "head" (no rolling passes)
     int front_horizon = 0;       // steps after a synchronised reset during which the table refresher keeps rolling (k_refresh)
     hipStream_t ref_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;      // the refresher's stream is forked from / joined to the caller's (also under capture)
+    hipEvent_t ev_fork = nullptr;        // the refresher's stream is forked from the caller's
     double unrefreshed_bytes = 1e18;      // written by this handle's kernels since the tables were last re-read (first launch: refresh)
     int n_cu = 256;
     std::vector<const void*> attr_done;   // kernels whose dynamic-LDS limit has been raised on this handle's device
@@ -2453,41 +2433,29 @@ PcPlan pc_plan(const ptg_env* h)
 //                 the tables as a front (the first front_horizon steps of an episode; PTG_REFRESH_ALWAYS: a policy that keeps the envs
 //                 in lock-step) and only in launches long enough to need one: k_refresh on a stream FORKED from `st` (event on `st`
 //                 before the rollout launch -> the refresher starts when the rollout does, whatever else `st` was busy with).
-//                 NOT while `st` is being captured: the fork / join captures fine (a parallel branch of the graph), but the runtime
+//                 NOT while `st` is being captured: forked and joined, k_refresh captures fine (a parallel branch of the graph), but the runtime
 //                 replays the two branches one after the other -- 150 steps from reset took 420 us as a graph against 253 us eager
 //                 (tests/test_batch_edges.py, round 3) -- so a captured launch keeps the head pass only (+ 8 % on the first ~250 steps
-//                 after a reset, profiles/r03_refresh_ab.txt).  PTG_REFRESH_CAPTURE_FORK=1 brings the captured branch back.
-struct RefreshPlan { int head_rec = 0; bool forked = false; };
-
-RefreshPlan launch_refresher(ptg_env* h, hipStream_t st, int m, int tn, int k0)
+//                 after a reset, profiles/r03_refresh_ab.txt).
+int launch_refresher(ptg_env* h, hipStream_t st, int m, int tn, int k0)
 {
-    RefreshPlan rp;
+    int head_rec = 0;
     const int osz = h->cfg.out_dtype == PTG_OUT_F64 ? 8 : 4;
     const double step_bytes = (double)m * (h->F * osz + osz + 1), launch_bytes = step_bytes * tn;
-    if (h->knob_no_refresh) return rp;
-    const bool legacy = h->knob_refresh_mode == 1;
+    if (h->knob_no_refresh) return head_rec;
     const double pass_steps = std::max(8.0, 192e6 / step_bytes);
-    const bool roll = (h->knob_refresh_always || k0 < h->front_horizon) && h->knob_refresh_mode != 2;
-    int passes;                                             // k_refresh's pass count (pass 0 = the head pass, only "legacy" runs it there)
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    const bool may_roll = roll && !(capturing && !h->knob_capture_fork);
-    if (legacy) passes = roll ? std::max(1, (int)std::ceil(tn / pass_steps)) : 1;
-    else {
-        const bool head = h->unrefreshed_bytes + launch_bytes >= 64e6;
-        if (head) { rp.head_rec = (int)h->rec_total; h->unrefreshed_bytes = 0.0; }
-        passes = (may_roll && tn > 4) ? 1 + (int)((tn - 4) / pass_steps) : 1;      // a pass with fewer than 4 steps left to serve is not issued
-        h->unrefreshed_bytes += launch_bytes - (passes - 1) * pass_steps * step_bytes;
-    }
-    if (!h->ref_stream || (!legacy && passes < 2)) return rp;
-    if (capturing && (legacy || !h->knob_capture_fork)) return rp;
-    if (!legacy) {                                          // fork
-        if (!h->ev_fork || hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->ref_stream, h->ev_fork, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            return rp;
-        }
-        rp.forked = capturing;
+    const bool roll = (h->knob_refresh_always || k0 < h->front_horizon) && cs == hipStreamCaptureStatusNone;
+    const bool head = h->unrefreshed_bytes + launch_bytes >= 64e6;
+    if (head) { head_rec = (int)h->rec_total; h->unrefreshed_bytes = 0.0; }
+    // k_refresh's pass count (pass 0 = the head pass, done by the rollout kernel); a pass with fewer than 4 steps left to serve is not issued
+    const int passes = (roll && tn > 4) ? 1 + (int)((tn - 4) / pass_steps) : 1;
+    h->unrefreshed_bytes += launch_bytes - (passes - 1) * pass_steps * step_bytes;
+    if (!h->ref_stream || passes < 2) return head_rec;
+    if (!h->ev_fork || hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->ref_stream, h->ev_fork, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return head_rec;
     }
     const double step_us = std::max(0.9, step_bytes / 6.2e6);                 // the rollout's pace: its output stream at ~6.2 TB/s, >= the producers' chain
     const unsigned period = (unsigned)std::min(4.0e6, pass_steps * step_us * 100.0);      // ticks of the 100 MHz clock; <= 40 ms
@@ -2495,20 +2463,14 @@ RefreshPlan launch_refresher(ptg_env* h, hipStream_t st, int m, int tn, int k0)
     const int grid = (int)std::min<long long>(h->n_cu, (n16 + 63) / 64);
     const void* recs = osz == 8 ? (const void*)h->P.rec : (const void*)h->P.recf;
     hipEvent_t h0 = nullptr, h1 = nullptr;
-    if (h->profiling && !capturing && prof_events(h, h0, h1)) {
+    if (h->profiling && prof_events(h, h0, h1)) {          // (never under capture: a captured launch has no rolling passes)
         g_helper0 = h0; g_helper1 = h1;
         hipExtLaunchKernelGGL(k_refresh, dim3(grid), dim3(64), 0, h->ref_stream, h0, h1, 0, recs, (const unsigned short*)h->d_rkey, (int)h->rec_total,
-                              legacy ? 0 : 1, passes, period);
+                              passes, period);
     } else
         hipLaunchKernelGGL(k_refresh, dim3(grid), dim3(64), 0, h->ref_stream, recs, (const unsigned short*)h->d_rkey, (int)h->rec_total,
-                           legacy ? 0 : 1, passes, period);
-    return rp;
-}
-
-void join_refresher(ptg_env* h, hipStream_t st, const RefreshPlan& rp)
-{
-    if (!rp.forked) return;                                 // eager: k_refresh ends by itself, nothing waits for it
-    if (hipEventRecord(h->ev_join, h->ref_stream) != hipSuccess || hipStreamWaitEvent(st, h->ev_join, 0) != hipSuccess) (void)hipGetLastError();
+                           passes, period);
+    return head_rec;      // k_refresh ends by itself: nothing waits for it
 }
 
 // attach the helper's events (if one was just launched) to the profile record of the launch it runs beside
@@ -2545,8 +2507,7 @@ void launch_rollout_hot(ptg_env* h, hipStream_t st, const void* actions, int kin
             const int m = std::min(chunk, h->n - e0);
             const dim3 grid(grid_for(m, np)), block(bs_all);
             const bool full = m % np == 0;
-            const RefreshPlan rp = launch_refresher(h, st, m, tn, k0);
-            const int rr = rp.head_rec;
+            const int rr = launch_refresher(h, st, m, tn, k0);
 #define PTG_PC2(LL, FULL)                                                                                             \
     do {                                                                                                              \
         auto kfn = k_rollout_pc<LAY, MOD, NOISE, LL, FULL, OUT>;                                                      \
@@ -2572,7 +2533,6 @@ void launch_rollout_hot(ptg_env* h, hipStream_t st, const void* actions, int kin
             }
             if (!launched) { if (ll) PTG_PC(true); else PTG_PC(false); }
             if (g_helper0) { h->prof_free.push_back({g_helper0, g_helper1}); g_helper0 = g_helper1 = nullptr; }      // (a helper nobody's record took: back to the pool)
-            join_refresher(h, st, rp);
 #undef PTG_PC
 #undef PTG_PC2
         }
@@ -2714,7 +2674,6 @@ void ptg_destroy(ptg_env* env)
     (void)hipDeviceSynchronize();                           // nothing of this handle (incl. the refresher's stream) is in flight any more
     if (env->ref_stream) (void)hipStreamDestroy(env->ref_stream);
     if (env->ev_fork) (void)hipEventDestroy(env->ev_fork);
-    if (env->ev_join) (void)hipEventDestroy(env->ev_join);
     if (env->ev_tail) (void)hipEventDestroy(env->ev_tail);
     for (void* p : env->allocs) (void)hipFree(p);
     if (env->d_tape) (void)hipFree(env->d_tape);
@@ -2753,8 +2712,6 @@ int ptg_create(const ptg_config* cfg, const ptg_tables* tables, const ptg_market
     h->cfg = *cfg; h->n = n_envs; h->device = device_id; h->n_sets = n_sets;
     h->knob_no_hot = getenv("PTG_NO_HOT_KERNELS") != nullptr; h->knob_no_lds_lut = getenv("PTG_NO_LDS_LUT") != nullptr;
     h->knob_no_refresh = getenv("PTG_NO_REFRESH") != nullptr; h->knob_refresh_always = getenv("PTG_REFRESH_ALWAYS") != nullptr;
-    h->knob_capture_fork = getenv("PTG_REFRESH_CAPTURE_FORK") != nullptr;
-    if (const char* v = getenv("PTG_REFRESH_MODE")) h->knob_refresh_mode = !strcmp(v, "legacy") ? 1 : !strcmp(v, "head") ? 2 : 0;
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) h->n_cu = prop.multiProcessorCount;
@@ -2918,9 +2875,9 @@ int ptg_create(const ptg_config* cfg, const ptg_tables* tables, const ptg_market
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         if (hipStreamCreateWithPriority(&h->ref_stream, hipStreamNonBlocking, hi) != hipSuccess) { h->ref_stream = nullptr; (void)hipGetLastError(); }
-        if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
-            if (h->ref_stream) { (void)hipStreamDestroy(h->ref_stream); h->ref_stream = nullptr; }     // no fork / join events: no rolling passes
+            if (h->ref_stream) { (void)hipStreamDestroy(h->ref_stream); h->ref_stream = nullptr; }     // no fork event: no rolling passes
         }
     }
     if (hipDeviceSynchronize() != hipSuccess) { set_err(h, PTG_E_HIP, "device synchronize failed after init"); return fail(PTG_E_HIP); }

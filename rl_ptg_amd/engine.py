@@ -89,9 +89,8 @@ class HipEngine:
         self.obs_dim = self._L.ptg_obs_dim(h)
         osz = 8 if out_dtype == "float64" else 4
         if obs_pitch == "auto":
-            import os
-            pad = int(os.environ.get("PTG_FM_PAD_BYTES", "1024"))         # (experiments: tools/r03_pitch2.sh -> profiles/r03_fm_pitch.txt)
-            obs_pitch = self.n + pad // osz if (self.feature_major and osz == 8 and pad and (self.n * osz) % 65536 == 0) else None
+            pad = 1024                                                    # bytes (profiles/r03_fm_pitch.txt)
+            obs_pitch = self.n + pad // osz if (self.feature_major and osz == 8 and (self.n * osz) % 65536 == 0) else None
         self.pitch = self.n if obs_pitch is None else int(obs_pitch)
         if self.pitch != self.n:
             if not self.feature_major:

@@ -1,5 +1,5 @@
 // HBM probe for the rollout kernels' traffic shape: what does MI355X sustain for write-only streams, compared with reads?
-// Build: hipcc --offload-arch=gfx950 -O3 -o gpurun_out/hbm_probe tools/hbm_probe.hip      Run: gpurun_out/hbm_probe
+// Build: mkdir -p tools/bin && hipcc --offload-arch=gfx950 -O3 -o tools/bin/hbm_probe tools/hbm_probe.hip      Run: tools/bin/hbm_probe
 // Every kernel moves the same number of bytes as one rollout launch of T steps over N envs with F+2 output planes
 // ([T][F][N] float32 obs, [T][N] float32 rewards, [T][N] bytes) unless stated otherwise.
 #include <hip/hip_runtime.h>

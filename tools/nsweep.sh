@@ -1,11 +1,15 @@
 #!/bin/bash
-# usage (GPU box): tools/nsweep.sh > gpurun_out/nsweep.txt   -- bench.py over batch sizes / layouts / dtypes, one line each
-one() { timeout -k 10 400 python bench.py --no-cpu-baseline --no-boundary-leg "$@" > gpurun_out/bench_sweep.log 2>&1; python - "$@" <<'PY'
+# usage: tools/nsweep.sh > build/nsweep.txt   -- bench.py over batch sizes / layouts / dtypes, one line each; stops at the first
+# bench run that fails, times out or prints no result line
+cd "$(dirname "$0")/.." && mkdir -p build || exit 1
+one() {
+  timeout -k 10 400 python bench.py --no-cpu-baseline --no-boundary-leg "$@" > build/bench_sweep.log 2>&1 || { s=$?; echo "$* FAILED (exit $s)"; exit $s; }
+  python - "$@" <<'PY' || exit 1
 import json, sys
 try:
-    d = json.loads([l for l in open('gpurun_out/bench_sweep.log') if l.startswith('{')][-1])
+    d = json.loads([l for l in open('build/bench_sweep.log') if l.startswith('{')][-1])
 except Exception as e:
-    print(' '.join(sys.argv[1:]), 'FAILED'); sys.exit(0)
+    print(' '.join(sys.argv[1:]), 'FAILED: no result line'); sys.exit(1)
 r = d['roofline']
 msg = '%-58s %-8s dev us/step %8.3f  %7.0f GB/s frac %.3f  wall env-steps/s %.3e' % (' '.join(sys.argv[1:]), 'rollout' if 'rollout' in d['config']['path'] else 'step', r['avg_launch_us'] * r['launches_timed'] / d['steps'], r['achieved'], r['frac'], d['value'])
 s = d.get('steady_state')

@@ -31,7 +31,7 @@ def short(name):
 
 
 def newest(pattern):
-    """files of the most recent profiler run only (gpurun merges its output directory: an older run's <pid>_*.csv may still lie beside the new one)"""
+    """files of the most recent profiler run only (an older run's <pid>_*.csv may still lie beside the new one)"""
     fs = glob.glob(pattern, recursive=True)
     if not fs:
         return []
@@ -41,7 +41,7 @@ def newest(pattern):
 
 
 rows = []
-for f in newest(f"gpurun_out/prof_{tag}_trace/**/*kernel_stats.csv"):
+for f in newest(f"build/prof_{tag}_trace/**/*kernel_stats.csv"):
     for r in csv.DictReader(open(f)):
         rows.append(r)
 with open(f"profiles/{tag}_kernel_stats.csv", "w", newline="") as out:
@@ -53,7 +53,7 @@ with open(f"profiles/{tag}_kernel_stats.csv", "w", newline="") as out:
 
 trace = defaultdict(list)
 meta = {}
-for f in newest(f"gpurun_out/prof_{tag}_trace/**/*kernel_trace.csv"):
+for f in newest(f"build/prof_{tag}_trace/**/*kernel_trace.csv"):
     for r in csv.DictReader(open(f)):
         k = short(r["Kernel_Name"])
         trace[k].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
@@ -61,7 +61,7 @@ for f in newest(f"gpurun_out/prof_{tag}_trace/**/*kernel_trace.csv"):
 
 pmc = defaultdict(lambda: defaultdict(list))          # kernel -> counter -> [(dispatch id, value)]
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    for f in newest(f"gpurun_out/prof_{tag}_{c}/**/*counter_collection.csv"):
+    for f in newest(f"build/prof_{tag}_{c}/**/*counter_collection.csv"):
         for r in csv.DictReader(open(f)):
             pmc[short(r["Kernel_Name"])][r["Counter_Name"]].append((int(r["Dispatch_Id"]), float(r["Counter_Value"])))
 
@@ -109,11 +109,11 @@ if hk in trace and len(trace[hk]) > NW:
                  (" (the head pass is inside the rollout kernel; rolling passes only in launches long enough to need one)" if not inside else ""))
 # the bench line of the PROFILED run: its own event-based figures for the same launches
 try:
-    line = [l for l in open(f"gpurun_out/prof_{tag}_trace.log") if l.startswith("{")][-1]
+    line = [l for l in open(f"build/prof_{tag}_trace.log") if l.startswith("{")][-1]
     bj = json.loads(line)
     legs = [("headline (row-major float32)", bj["roofline"])] + [(k, v["roofline"]) for k, v in bj.get("also", {}).items()]
     lines += ["", "bench.py's own figures in this same profiled run (HIP events attached to the launches).  Two things to know when comparing: (i) with the",
-              "profiler attached the event pair reads 4-7 us MORE than the dispatch duration above (tools/tsweep.py under rocprofv3: 10.5-15.9 vs 6.5-7.2 us at",
+              "profiler attached the event pair reads 4-7 us MORE than the dispatch duration above (profiles/r02_tsweep.txt, under rocprofv3: 10.5-15.9 vs 6.5-7.2 us at",
               "T = 1, 37-40 vs 33-37 at T = 20), without it the events match these dispatch durations (6.3-6.6 us at T = 1, 33-35 at T = 20); (ii) the whole",
               "profiled process runs 8-10 % slower than an un-profiled one (steady state 1.60-1.65 vs 1.47-1.53 us per step; MI355X_MICROARCH.md, DVFS",
               "give-back item 2: never compare a profiled arm with an un-profiled one).  The un-profiled driver-argument run is profiles/r03_bench_driver_args.json."]
@@ -123,7 +123,7 @@ try:
     if "steady_state" in bj:
         lines.append(f"* steady_state: {bj['steady_state']['us_per_step']:.3f} us per step, frac = {bj['steady_state']['frac']:.3f}")
 except Exception as e:
-    lines += ["", f"(no bench line found in gpurun_out/prof_{tag}_trace.log: {e})"]
+    lines += ["", f"(no bench line found in build/prof_{tag}_trace.log: {e})"]
 traffic = {"source": f"profiles/{tag}_summary.md"}
 lines += ["", "| kernel | dispatch | FETCH_SIZE KiB (raw) | read bytes (x2 corrected) | WRITE_SIZE KiB | HBM bytes | per step / launch |", "|---|---|---|---|---|---|---|"]
 for k in sorted(pmc):

@@ -1,7 +1,9 @@
-"""Phases of one fused-rollout launch from in-kernel 100 MHz stamps (diagnostic build -DPTG_STAMPS, loaded through PTG_LIB_PATH):
-python tools/stamps.py [T].  Stamps per workgroup, wave 0 (producer) / first consumer wave: 0 kernel entry, 1 actions staged,
-2 LDS staging issued, 3 past the barrier, 4 first hand-off (producer: step 0 produced; consumer: step 0 requested), 5 second step
-(consumer: first finish issued), 6 loop done (producer: before the last barrier), 7 end (consumer: all stores retired)."""
+"""Phases of one fused-rollout launch from in-kernel 100 MHz stamps: python tools/stamps.py [T].  Needs the diagnostic build, in ONE
+translation unit (g_stamps is per translation unit): hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DPTG_STAMPS
+-shared -o tools/libptg_stamps.so rl_ptg_amd/csrc/ptg_env.hip, loaded through PTG_LIB_PATH=tools/libptg_stamps.so.
+Stamps per workgroup, wave 0 (producer) / first consumer wave: 0 kernel entry, 1 actions staged, 2 LDS staging issued, 3 past the
+barrier, 4 first hand-off (producer: step 0 produced; consumer: step 0 requested), 5 second step (consumer: first finish issued),
+6 loop done (producer: before the last barrier), 7 end (consumer: all stores retired)."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
