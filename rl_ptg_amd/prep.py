@@ -5,7 +5,7 @@ Restates (vectorised, same float64 operand order, checked bit-for-bit against te
   * calculate_optimum: potential reward / load identifier / T-OPT          src/rl_opt.py:26-152
   * define_episodes + rand_eps_ind                                          src/rl_utils.py:283-335
   * dict_env_kwargs: the env's input contract                               src/rl_utils.py:337-405
-The 13-wide `e_r_b` and 2-wide `g_e` tensors of preprocessing_array (:243-281) are NOT materialised: the kernels
+The price_ahead-wide `e_r_b` and 2-wide `g_e` tensors of preprocessing_array (:243-281) are NOT materialised: the kernels
 read the 1-D series (e_r_b[c, i, t] == series_c[t + i]).  `EnvSpec.from_dict_input` also accepts a reference-made
 kwargs dict (with e_r_b / g_e) and folds it back, so the reference's own Preprocessing output drops in unchanged.
 """
@@ -230,6 +230,10 @@ class EnvSpec:
         tables = {k: np.ascontiguousarray(kw[k], dtype=np.float64) for k in TABLE_KEYS}
         if "el_series" in kw:
             ser = {k: np.asarray(kw[f"{k}_series"], dtype=np.float64) for k in ("el", "pot_rew", "part_full", "gas", "eua")}
+            # the reference's e_r_b has n_hours - P columns, so its env can index hours 0 .. n_hours - 2 only, whatever P is
+            # (src/rl_utils.py:250-263): drop the last hour, which is exactly what folding e_r_b back gives
+            for k in ("el", "pot_rew", "part_full"):
+                ser[k] = ser[k][:len(ser[k]) - 1]
         else:
             e_r_b, g_e = kw["e_r_b"], kw["g_e"]
             ser = dict(el=_fold(e_r_b[0]), pot_rew=_fold(e_r_b[1]), part_full=_fold(e_r_b[2]), gas=_fold(g_e[0]), eua=_fold(g_e[1]))
@@ -248,12 +252,12 @@ class EnvSpec:
 
 
 def synthetic_spec(scenario=2, operation="OP2", eps_len_d=32, raw_modified="mod", action_type="discrete",
-                   train_or_eval="train", sim_step=600, seed_train=3654, train_steps=1500000, state_change_penalty=0.0):
+                   train_or_eval="train", sim_step=600, seed_train=3654, train_steps=1500000, state_change_penalty=0.0, price_ahead=13):
     """The BASELINE.json workload: synthetic 38-day trace (32-day episodes), real process tables."""
     from .synthetic import synthetic_market
     from .tables import load_op_tables
     cfg = EnvConfig(scenario=scenario, operation=operation, eps_len_d=eps_len_d, raw_modified=raw_modified,
-                    sim_step=sim_step, state_change_penalty=state_change_penalty)
+                    sim_step=sim_step, state_change_penalty=state_change_penalty, price_ahead=price_ahead)
     prices = {}
     for split, (days, seed) in dict(train=(38, 20250614), val=(9, 20250615), test=(9, 20250616)).items():
         el, gas, eua = synthetic_market(days, seed)

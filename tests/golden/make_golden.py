@@ -15,6 +15,7 @@ Files written
   units_<op>.npz             _get_index for every distinct T_cat x 6 destination tables
 """
 import json
+import math
 import os
 import sys
 
@@ -130,14 +131,14 @@ def save_prep(name, setup, extra_meta):
     print(f"  prep_{name}.npz  n_eps={pre.n_eps} eps_ind={len(pre.eps_ind)} r_level={pre.r_level[0]:.8f}")
 
 
-def save_traj(case, setup, prep_name, split, train_or_eval, actions, seed, kw_over=None, note=""):
+def save_traj(case, setup, prep_name, split, train_or_eval, actions, seed, kw_over=None, note="", extra_meta=None):
     kw = dict(setup.kwargs(split))
     kw.update(kw_over or {})
     out = rd.run_vector(kw, actions, seed=seed, train_or_eval=train_or_eval)
     consts, _, market = po.split_reference_kwargs(kw, train_or_eval)
     meta = dict(case=case, prep=prep_name, split=split, train_or_eval=train_or_eval, n_envs=int(actions.shape[1]),
                 seed=int(seed), ep_index0=0, consts=jsonable(consts), operation=setup.EnvConfig.operation,
-                int_cols=rd.INT_COLS, f64_cols=rd.F64_COLS, info_keys=rd.INFO_KEYS, note=note)
+                int_cols=rd.INT_COLS, f64_cols=rd.F64_COLS, info_keys=rd.INFO_KEYS, note=note, **(extra_meta or {}))
     arrs = dict(actions=out["actions"], ints=out["ints"].astype(np.int32), f64s=out["f64s"], obs=out["obs"],
                 done=out["done"], noise=out["noise"], noise_len=out["noise_len"], n_noise=out["n_noise"].astype(np.int32),
                 reset_obs=out["reset_obs"], reset_int=out["reset_int"].astype(np.int32), reset_info=out["reset_info"],
@@ -284,7 +285,87 @@ def main():
     pt, ft = set(out["ints"][..., 6].reshape(-1).tolist()), set(out["ints"][..., 7].reshape(-1).tolist())
     assert pt >= {5, 8, 9, 10, 11, 12} and ft >= {6, 7, 13, 14, 15, 16}, (pt, ft)
     s.close()
+
+    # ---------------- price_ahead other than 13 (config/config_env.yaml:26): observation widths, e_r_b windows, T-OPT ----------------
+    print("synthetic / BS2 / OP2 / price_ahead 6, 2-day episodes")
+    s = rd.RefSetup(dict(scenario=2, operation="OP2", eps_len_d=2, price_ahead=6), synthetic_market=sm, train_steps=20000)
+    save_prep("synth_bs2_OP2_pa6", s, dict(market="synth", eps_len_d=2, sim_step=600, price_ahead=6, t_opt=ref_t_opt(s)))
+    g = np.random.default_rng(2005)
+    out = save_traj("synth_bs2_op2_pa6_mod_disc_term", s, "synth_bs2_OP2_pa6", "train", "train", sticky_tape(g, 900, 5, 1 / 5.0), 3656,
+                    note="price_ahead=6, eps_len_d=2 (283-step episodes): several terminations")
+    assert out["done"].sum() >= 10
+    s.close()
+
+    print("real / BS1 / OP1 / price_ahead 24, raw features, continuous actions")
+    s = rd.RefSetup(dict(scenario=1, operation="OP1", price_ahead=24))
+    save_prep("real_bs1_OP1_pa24", s, dict(market="real", eps_len_d=37, sim_step=600, price_ahead=24, t_opt=ref_t_opt(s)))
+    g = np.random.default_rng(2006)
+    save_traj("real_bs1_op1_pa24_raw_cont_train", s, "real_bs1_OP1_pa24", "train", "train",
+              to_continuous(g, sticky_tape(g, 700, 2, 1 / 6.0)), 469, dict(raw_modified="raw", action_type="continuous"),
+              note="price_ahead=24, raw features, continuous actions with decode edge cases")
+    s.close()
+
+    print("real / BS3 / OP2 / price_ahead 1, raw features")
+    s = rd.RefSetup(dict(scenario=3, operation="OP2", price_ahead=1))
+    save_prep("real_bs3_OP2_pa1", s, dict(market="real", eps_len_d=37, sim_step=600, price_ahead=1, t_opt=ref_t_opt(s)))
+    save_traj("real_bs3_op2_pa1_raw_disc_train", s, "real_bs3_OP2_pa1", "train", "train",
+              np.random.default_rng(2007).integers(0, 5, (600, 3)), 3657, dict(raw_modified="raw"),
+              note="price_ahead=1: the smallest window")
+    s.close()
+
+    print("real / BS2 / OP2 / price_ahead 25, val split, eval mode, one whole validation episode")
+    s = rd.RefSetup(dict(scenario=2, operation="OP2", price_ahead=25))
+    save_prep("real_bs2_OP2_pa25", s, dict(market="real", eps_len_d=37, sim_step=600, price_ahead=25, t_opt=ref_t_opt(s)))
+    t_end = int(s.pre.eps_sim_steps_val) - 6
+    n_val = t_end + 1 + 10
+    out = save_traj("real_bs2_op2_pa25_mod_disc_evalval_full", s, "real_bs2_OP2_pa25", "val", "eval",
+                    sticky_tape(np.random.default_rng(2008), n_val, 1), 606,
+                    note="price_ahead=25, the whole validation episode: its last steps read the last hour the reference exposes")
+    assert np.nonzero(out["done"][:, 0])[0].tolist() == [t_end], np.nonzero(out["done"][:, 0])[0]
+
+    print("real / BS2 / OP2 / price_ahead 25, test split, eval mode: the reference raises before the episode ends")
+    kw = s.kwargs("test")
+    acts = sticky_tape(np.random.default_rng(2009), int(s.pre.eps_sim_steps_test), 1)
+    t_fail, h_fail = ref_failing_step(kw, acts, 607, "eval")
+    save_traj("real_bs2_op2_pa25_mod_disc_evaltest_end", s, "real_bs2_OP2_pa25", "test", "eval", acts[:t_fail], 607,
+              note="price_ahead=25, whole test split: the reference raises IndexError on step fail_step (hour fail_h), "
+                   "which is not part of the trajectory", extra_meta=dict(fail_step=t_fail, fail_h=h_fail, fail_action=int(acts[t_fail, 0])))
+    s.close()
     print("done")
+
+
+def ref_t_opt(setup):
+    """T-OPT of each split as the reference prints it, unrounded: Meth_cum_reward_stats[-price_ahead] of its own calculate_optimum
+    (src/rl_opt.py:145-147), which reads config_env.yaml relative to the working directory"""
+    import src.rl_opt as rl_opt
+    P = setup.EnvConfig.price_ahead
+    cwd = os.getcwd()
+    os.chdir(setup.wd)
+    try:
+        with rd._quiet():
+            return {sp: float(rl_opt.calculate_optimum(setup.price[f"el_price_{sp}"], setup.price[f"gas_price_{sp}"],
+                                                       setup.price[f"eua_price_{sp}"], sp, setup.EnvConfig.stats_names)
+                              ["Meth_cum_reward_stats"][-P]) for sp in ("train", "val", "test")}
+    finally:
+        os.chdir(cwd)
+
+
+def ref_failing_step(kw, actions, seed, train_or_eval):
+    """Step one reference env (env 0 of run_vector: same seed, same actions) until it raises IndexError -> (step index, the hour
+    index act_ep_h + h_step it asked e_r_b for, env/ptg_gym_env.py:442-446)."""
+    ptg = rd._import_reference()["ptg"]
+    ptg.ep_index = 0
+    env = ptg.PTGEnv(kw, train_or_eval)
+    env.reset(seed=seed)
+    for t in range(actions.shape[0]):
+        h = int(env.act_ep_h + math.floor((env.k + 1) * env.time_step_size_sim / 3600))
+        try:
+            env.step(int(actions[t, 0]))
+        except IndexError as ex:
+            print(f"  reference raised at step {t} (h = {h}): {ex}")
+            assert h == np.asarray(kw["e_r_b"]).shape[2], (h, np.asarray(kw["e_r_b"]).shape)
+            return t, h
+    raise AssertionError("the reference finished without an IndexError")
 
 
 if __name__ == "__main__":

@@ -71,15 +71,22 @@ def load_prep(name):
 
 
 def load_traj(case):
-    """-> (traj dict, consts, tables, market) with market series taken from the referenced prep fixture."""
+    """-> (traj dict, consts, tables, market) with market series taken from the referenced prep fixture, the hourly ones cut to the
+    hours the reference env can index (what EnvSpec.from_dict_input makes of them)."""
     tr = load_npz(os.path.join(GOLD, f"traj_{case}.npz"))
     meta = tr["meta"]
+    market = dict(_full_series(meta), eps_ind=tr["eps_ind"] if len(tr["eps_ind"]) else None)
+    for k in ("el", "pot_rew", "part_full"):          # e_r_b covers all hours but the last, whatever P is
+        market[k] = market[k][:-1]
+    return tr, dict(meta["consts"]), load_tables(meta["operation"]), market
+
+
+def _full_series(meta):
+    """the split's whole series as Preprocessing makes them (what dict_env_kwargs passes as *_series)"""
     prep = load_prep(meta["prep"])
     sp = meta["split"]
-    market = dict(el=prep[f"el_{sp}"], pot_rew=prep[f"pot_rew_{sp}"], part_full=prep[f"part_full_{sp}"].astype(np.float64),
-                  gas=prep[f"gas_{sp}"], eua=prep[f"eua_{sp}"],
-                  eps_ind=tr["eps_ind"] if len(tr["eps_ind"]) else None)
-    return tr, dict(meta["consts"]), load_tables(meta["operation"]), market
+    return dict(el=prep[f"el_{sp}"], pot_rew=prep[f"pot_rew_{sp}"], part_full=prep[f"part_full_{sp}"].astype(np.float64),
+                gas=prep[f"gas_{sp}"], eua=prep[f"eua_{sp}"])
 
 
 def make_oracle(case):
@@ -117,8 +124,7 @@ def kwargs_from_fixture(case):
               action_type="continuous" if consts["action_type"] else "discrete",
               reward_level=np.array([consts["r_0"]]), parallel="Singleprocessing", n_eps_loops=0,
               eps_ind=None if market["eps_ind"] is None else market["eps_ind"].astype(int),
-              el_series=market["el"], pot_rew_series=market["pot_rew"], part_full_series=market["part_full"],
-              gas_series=market["gas"], eua_series=market["eua"])
+              **{f"{k}_series": v for k, v in _full_series(tr["meta"]).items()})
     kw.update({f"ptg_{k}": i for i, k in enumerate(["standby", "cooldown", "startup", "partial_load", "full_load"])})
     kw.update(tables)
     return tr, kw

@@ -45,11 +45,16 @@ def test_sb3_flat_features_order_and_one_hot():
     assert raw.shape == (3, 31)
 
 
-def test_env_spec_validation_and_merge():
+def test_env_spec_validation_merge_and_series_lengths():
     spec, pre = synthetic_spec(scenario=2, operation="OP2", eps_len_d=32)
     assert spec.consts["raw_modified"] == 1 and spec.consts["action_type"] == 0 and spec.consts["eps_sim_steps"] == 4608
     assert spec.eps_ind is not None and len(spec.eps_ind) == 3250 and not spec.eps_ind.any()
-    assert len(spec.markets[0]["el"]) == 38 * 24 and len(spec.markets[0]["gas"]) == 38
+    # hourly series: the 38 * 24 - 1 hours the reference's e_r_b covers (38 * 24 - P columns of width P), as folding e_r_b gives;
+    # daily: all 38 days
+    folded = EnvSpec.from_dict_input({k: v for k, v in pre.dict_env_kwargs("train", materialize=True).items() if not k.endswith("_series")})
+    for k in ("el", "pot_rew", "part_full"):
+        assert len(spec.markets[0][k]) == 38 * 24 - 1 == len(folded.markets[0][k]), k
+    assert len(spec.markets[0]["gas"]) == 38 == len(folded.markets[0]["gas"])
     kw = pre.dict_env_kwargs("val")
     assert kw["eps_ind"] is None and kw["state_change_penalty"] == 0.0            # validation envs: offset 0, no penalty (:381-385)
     bad = dict(pre.dict_env_kwargs("train"), raw_modified="both")
@@ -105,24 +110,33 @@ def test_sb3_flat_oracle_known_answers():
     assert sorted(k for k, _ in fo.reference_keys("mod"))[5] == "METH_STATUS"
 
 
-def test_split_layout_columns_agree_with_the_flat_oracle():
-    """rl_ptg_amd.policy_split's column tables against oracle/sb3_flat_oracle.py: the 14 env columns of a split row land where the
-    flattened observation has them, and the market windows where the oracle puts Pot_Reward / Part_Full (Elec / Gas / EUA)."""
+@pytest.mark.parametrize("P", [13, 1, 6, 24, 64])
+def test_split_layout_columns_agree_with_the_flat_oracle(P):
+    """rl_ptg_amd.policy_split's column tables against oracle/sb3_flat_oracle.py at price_ahead P: the 14 env columns of a split row
+    land where the flattened observation has them, and the market windows where the oracle puts Pot_Reward / Part_Full (Elec / Gas /
+    EUA).  At P = 13 the tables are also the module's FLAT_MOD / FLAT_RAW."""
     import os, sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
     import sb3_flat_oracle as fo
-    from rl_ptg_amd.policy_split import FLAT_MOD, FLAT_RAW, SPLIT_ENV, env_columns, flat_rows_from_split
+    from rl_ptg_amd.policy_split import FLAT_MOD, FLAT_RAW, SPLIT_ENV, env_columns, flat_columns, flat_rows_from_split
     for rm, table in (("mod", FLAT_MOD), ("raw", FLAT_RAW)):
-        keys = dict(fo.reference_keys(rm))
+        keys = dict(fo.reference_keys(rm, P))
         off, c = {}, 0
         for k in sorted(keys):
             off[k] = c
             c += 6 if k == "METH_STATUS" else keys[k]
-        assert off == table
-        assert env_columns(rm) == [off["METH_STATUS"] + j for j in range(6)] + [off[k] for k in SPLIT_ENV]
+        assert flat_columns(rm, P) == (off, c) and c == (2 * P + 14 if rm == "mod" else P + 18)
+        if P == 13:
+            assert off == table
+        assert env_columns(rm, P) == [off["METH_STATUS"] + j for j in range(6)] + [off[k] for k in SPLIT_ENV]
     # a hand-built split row + series -> the flat row the oracle builds from the canonical row
-    fa, fb = np.arange(100, 160, dtype=np.float32), np.arange(200, 260, dtype=np.float32)
-    canon = np.concatenate([fa[7:20], fb[7:20], [3], [0.31, 0.32, 0.33, 0.34, 0.35, 0.36, 0.37, 0.38]]).astype(np.float64)
-    split = np.array([[0, 0, 0, 1, 0, 0, 0.31, 0.32, 0.33, 0.34, 0.35, 0.36, 0.37, 0.38, 7, 0]], dtype=np.float32)
-    got = flat_rows_from_split(split, {"featA": fa[None], "featB": fb[None], "gas_n": np.zeros((1, 4), np.float32), "eua_n": np.zeros((1, 4), np.float32)}, "mod")
-    assert np.array_equal(got, fo.flatten_rows(canon[None], "mod"))
+    fa, fb = np.arange(100, 200, dtype=np.float32), np.arange(200, 300, dtype=np.float32)
+    g, u = np.arange(300, 310, dtype=np.float32), np.arange(400, 410, dtype=np.float32)
+    series = {"featA": fa[None], "featB": fb[None], "gas_n": g[None], "eua_n": u[None]}
+    tail = [0.31, 0.32, 0.33, 0.34, 0.35, 0.36, 0.37, 0.38]
+    split = np.array([[0, 0, 0, 1, 0, 0] + tail + [7, 4]], dtype=np.float32)
+    canon = {"mod": np.concatenate([fa[7:7 + P], fb[7:7 + P], [3], tail]),
+             "raw": np.concatenate([fa[7:7 + P], g[4:6], u[4:6], [3], tail])}
+    for rm in ("mod", "raw"):
+        got = flat_rows_from_split(split, series, rm, price_ahead=P)
+        assert np.array_equal(got, fo.flatten_rows(canon[rm][None].astype(np.float64), rm, P)), rm

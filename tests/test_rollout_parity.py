@@ -34,6 +34,7 @@ def test_rollout_vs_reference_golden(case, out_dtype, layout):
     rtol, atol = (RTOL64, ATOL64) if out_dtype == "float64" else (RTOL32, ATOL32)
     K, n = tr["actions"].shape
     mode = "mod" if tr["meta"]["consts"]["raw_modified"] else "raw"
+    P = tr["meta"]["consts"]["price_ahead"]
     eng.reset()
     obs, rew, done = eng.rollout(tr["actions"])
     eng.sync()
@@ -44,12 +45,12 @@ def test_rollout_vs_reference_golden(case, out_dtype, layout):
     for q, (t, e) in enumerate(tr["post_reset_at"].tolist()):
         want[t, e] = tr["post_reset_obs"][q]
     if layout == "sb3_flat":
-        want = flat_oracle.flatten_rows(want.reshape(K * n, -1), mode).reshape(K, n, -1)
+        want = flat_oracle.flatten_rows(want.reshape(K * n, -1), mode, P).reshape(K, n, -1)
         assert obs.shape == want.shape
     np.testing.assert_allclose(obs, want, rtol=rtol, atol=atol)
     if layout == "sb3_flat":                                  # the one-hot block is exact
-        c0 = sorted(k for k, _ in flat_oracle.reference_keys(mode))
-        off = sum(dict(flat_oracle.reference_keys(mode))[k] for k in c0[:c0.index("METH_STATUS")])
+        c0 = sorted(k for k, _ in flat_oracle.reference_keys(mode, P))
+        off = sum(dict(flat_oracle.reference_keys(mode, P))[k] for k in c0[:c0.index("METH_STATUS")])
         assert np.array_equal(obs[:, :, off:off + 6], want[:, :, off:off + 6])
     # final state: the reference's last step (envs that finished on the last step are checked through post_reset_int)
     last_done = tr["done"][K - 1].astype(bool)
