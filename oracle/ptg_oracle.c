@@ -681,5 +681,41 @@ int ptgo_get_state(const ptgo_env* h, int64_t* ints, double* f64s)
     return 0;
 }
 
+/* Writes the attributes a reference env holds between two step() calls, in the column order of ptgo_get_state.
+ * The integer columns and cum_rew / T_cat are what step() reads (:339-440, :525-757, :330); f64s[0] and f64s[3..7] (reward and
+ * window means) are overwritten by the next step (:452-458, :468) and are stored only so that get_state reads them back.  The price
+ * columns and the clock follow from k and the episode offsets as step_one computes them for step k - 1 (:442-450), reset_one for k = 0.
+ * No behaviour of its own: ints are taken as given, so only states the reference can reach give reference results. */
+int ptgo_set_state(ptgo_env* h, const int64_t* ints, const double* f64s, const int64_t* noise_count)
+{
+    if (!h || !ints || !f64s) FAIL(-1, "ptgo_set_state: bad arguments");
+    const ptgo_config* c = &h->c;
+    for (int e = 0; e < h->n; e++) {
+        const int64_t* a = ints + (size_t)e * PTGO_N_INT;
+        const double* f = f64s + (size_t)e * PTGO_N_F64;
+        ptgo_slot* s = &h->s[e];
+        s->meth_state = (int)a[0]; s->i = (int)a[1]; s->j = (int)a[2]; s->hot_cold = (int)a[3];
+        s->standby_tid = (int)a[4]; s->startup_tid = (int)a[5]; s->partial_tid = (int)a[6]; s->full_tid = (int)a[7];
+        s->k = (int)a[8]; s->current_action = (int)a[9]; s->act_ep_h = a[10]; s->act_ep_d = a[11];
+        s->rew = f[0]; s->cum_rew = f[1]; s->T_cat = f[2];
+        s->H2 = f[3]; s->CH4 = f[4]; s->H2_res = f[5]; s->H2O = f[6]; s->el_heating = f[7];
+        if (noise_count) s->noise_count = noise_count[e];
+        s->clock_hours = (double)((int64_t)s->k * c->sim_step) / 3600;
+        s->h_idx = s->act_ep_h + (int64_t)floor(s->clock_hours);
+        s->d_idx = s->act_ep_d + (int64_t)floor(s->clock_hours / 24);
+        s->sin_h = py_sin(2 * M_PI * s->clock_hours);
+        s->cos_h = py_cos(2 * M_PI * s->clock_hours);
+        normalize(h, s);
+    }
+    return 0;
+}
+
+int ptgo_set_ep_index(ptgo_env* h, int64_t ep_index)
+{
+    if (!h) FAIL(-1, "ptgo_set_ep_index: bad arguments");
+    h->ep_index = ep_index;
+    return 0;
+}
+
 int64_t ptgo_ep_index(const ptgo_env* h) { return h->ep_index; }
 int64_t ptgo_noise_count(const ptgo_env* h, int e) { return (e >= 0 && e < h->n) ? h->s[e].noise_count : -1; }

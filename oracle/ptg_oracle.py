@@ -88,6 +88,8 @@ def lib():
         L.ptgo_step_mt.argtypes = [C.c_void_p, C.c_void_p, dp, dp, u8p, dp, dp, C.c_int]
         L.ptgo_get_last.argtypes = [C.c_void_p, i64p, dp]
         L.ptgo_get_state.argtypes = [C.c_void_p, i64p, dp]
+        L.ptgo_set_state.argtypes = [C.c_void_p, i64p, dp, i64p]
+        L.ptgo_set_ep_index.argtypes = [C.c_void_p, C.c_int64]
         L.ptgo_ep_index.argtypes = [C.c_void_p]
         L.ptgo_ep_index.restype = C.c_int64
         L.ptgo_noise_count.argtypes = [C.c_void_p, C.c_int]
@@ -246,9 +248,26 @@ class OracleVecEnv:
         self._chk(self._L.ptgo_get_state(self._h, ints.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(f)))
         return ints, f
 
+    def set_state(self, ints, f64s, noise_count=None):
+        """Put every env in the state state() / last() report (same columns); noise_count [n]: tape draws consumed so far."""
+        ints = np.ascontiguousarray(ints, dtype=np.int64)
+        f64s = np.ascontiguousarray(f64s, dtype=np.float64)
+        assert ints.shape == (self.n, 12) and f64s.shape == (self.n, 8)
+        nc = None
+        if noise_count is not None:
+            nc = np.ascontiguousarray(noise_count, dtype=np.int64)
+            assert nc.shape == (self.n,)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(self._L.ptgo_set_state(self._h, ints.ctypes.data_as(i64p), _dptr(f64s),
+                                         None if nc is None else nc.ctypes.data_as(i64p)))
+
     @property
     def ep_index(self):
         return int(self._L.ptgo_ep_index(self._h))
+
+    @ep_index.setter
+    def ep_index(self, v):
+        self._chk(self._L.ptgo_set_ep_index(self._h, int(v)))
 
     def noise_count(self, e):
         return int(self._L.ptgo_noise_count(self._h, e))

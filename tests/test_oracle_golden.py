@@ -94,3 +94,54 @@ def test_known_answers_from_survey():
     # ep_index: 3 constructions + 3 resets; env 0's first episode is eps_ind[3] = 0
     assert tr["reset_int"][0, 10] == 0 * 37 * 24 and tr["reset_int"][1, 10] == 8 * 37 * 24
     assert tr["reset_int"][0, 1] == 41218                      # argmin |cooldown.T - 16|
+
+
+@pytest.mark.parametrize("case", ["real_bs1_op1_raw_cont_evalval", "real_bs1_op1_mod_cont_train", "synth_bs2_op2_term_penalty",
+                                  "synth_bs1_op1_s60_toggle"])
+def test_set_state_continues_the_golden_trajectory(case):
+    """ptgo_set_state is complete: a FRESH oracle put into the state another one reached after K steps (same tape position, same
+    module-global ep_index) continues the reference's trajectory bit for bit -- obs, reward, done, state and noise draws, across the
+    auto-resets of the tail.  A field the setter forgot (or a price column / clock it did not derive from k) shows up as a difference."""
+    tr, consts, tables, market = H.load_traj(case)
+    Kt, n = tr["actions"].shape
+    meta = tr["meta"]
+    for K in (Kt // 7, Kt // 2 + 3, Kt - 40):
+        src = po.OracleVecEnv(consts, tables, market, n, ep_index0=meta["ep_index0"])
+        src.set_noise_tape(tr["noise"])
+        src.reset()
+        for t in range(K):
+            src.step(tr["actions"][t])
+        ints, f64s = src.state()
+        nc = [src.noise_count(e) for e in range(n)]
+        ep = src.ep_index
+        src.close()
+        env = po.OracleVecEnv(consts, tables, market, n, ep_index0=meta["ep_index0"] + 17)     # different episodes, on purpose
+        env.set_noise_tape(tr["noise"])
+        env.reset()
+        env.step(np.full(n, 0.9 if consts["action_type"] else 2, np.float32 if consts["action_type"] else np.int32))
+        env.set_state(ints, f64s, nc)
+        env.ep_index = ep
+        si, sf = env.state()
+        assert np.array_equal(si, ints) and np.array_equal(sf, f64s)
+        post_at = [tuple(x) for x in tr["post_reset_at"].tolist()]
+        n_post = sum(1 for (t, _) in post_at if t < K)
+        for t in range(K, Kt):
+            obs, rew, done, final, info = env.step(tr["actions"][t])
+            li, lf = env.last()
+            assert np.array_equal(li, tr["ints"][t]), f"K={K}: int state differs at step {t}"
+            assert np.array_equal(lf, tr["f64s"][t]), f"K={K}: float state differs at step {t}"
+            assert np.array_equal(done, tr["done"][t]) and np.array_equal(rew, tr["f64s"][t, :, 0])
+            for e in range(n):
+                if done[e]:
+                    assert post_at[n_post] == (t, e)
+                    assert np.array_equal(final[e], tr["obs"][t, e])
+                    assert np.array_equal(obs[e], tr["post_reset_obs"][n_post])
+                    n_post += 1
+                else:
+                    assert np.array_equal(obs[e], tr["obs"][t, e]), f"K={K}: obs differs at step {t} env {e}"
+                assert env.noise_count(e) == tr["n_noise"][t, e]
+            if "infos" in tr:
+                assert np.array_equal(info, tr["infos"][t])
+        assert n_post == len(post_at)
+        assert env.ep_index == int(tr["ep_index_end"])
+        env.close()
