@@ -243,7 +243,15 @@ int ptg_host_buffers_changed(ptg_env* env);
  *     synchronising call.
  *   * ptg_note_replays(env, n): after replaying captured launches that together advanced the batch by n vector steps BEYOND the first
  *     replay (the capture call counts as executed once, like an eager call), so that eager calls, ptg_steps_to_episode_end,
- *     ptg_rollout_launches and ptg_finished_episodes stay in step; the count wraps at the episode length.
+ *     ptg_rollout_launches and ptg_finished_episodes stay in step; the count wraps at the episode length.  On a de-synchronised batch
+ *     there is no common count: the call only tells ptg_finished_episodes that replays may have finished episodes.
+ *   * De-synchronising the batch (a partial ptg_reset, or ptg_set_state of unequal step counts) invalidates the hot launches captured
+ *     before it: their kernels take the step count from one env.  The library keeps a device word in stream order with the batch's
+ *     synchronisation (ptg_create, ptg_reset, ptg_set_state of the step count), and a replayed hot kernel that finds it set takes no
+ *     step: a default captured ptg_step or a captured ptg_rollout leaves the state and its outputs untouched and raises PTG_E_INVALID at
+ *     the next synchronising call; a replay-proof ptg_step hands every step to its generic kernel, which steps each env by its own
+ *     count (correct, at the generic kernel's speed).  A full ptg_reset (or ptg_set_state of equal step counts) re-arms the captured
+ *     launches.  A ptg_step captured while the batch is de-synchronised is the generic kernel and replays correctly either way.
  * Buffers are the graph's (fixed addresses); kernel-flagged errors surface at the next ptg_sync / ptg_step_host / ptg_finished_episodes.
  * No reference counterpart. */
 int ptg_note_replays(ptg_env* env, int n_steps);

@@ -109,7 +109,8 @@ struct DevParams {
     double* fin_ret; int* fin_len; int* fin_env; int* fin_count; int fin_cap;
     const int* cmap; int q_stat;          // SB3_FLAT layout: canonical column -> flat column; canonical index of METH_STATUS (else cmap = null)
     int split;                            // SPLIT layout (16 columns: status one-hot, 8 env features, hour / day series index; q_stat set too)
-    int* err;                             // [2] in pinned HOST memory: {invalid action seen, price index out of range}; kernels store 1 (plain
+    int* err;                             // [4] in pinned HOST memory: {invalid action seen, price index out of range, hot kernel on the
+                                          // terminating step, replay on a de-synchronised batch} (check_error_flags); kernels store 1 (plain
                                           // stores of a constant need no atomic), the host reads it after a stream synchronise -- no copy
     int* term_flag;                       // device word: "the hot step kernel of this (captured) step found the batch on the terminating step
                                           // and skipped it" -- written by k_step_hot, read by the k_step enqueued behind it
@@ -853,6 +854,8 @@ struct HotParams {
     StA* st_a; StB* st_b; StC* st_c;
     int* err;
     int* term_flag;
+    const int* desync;                                // device word, 1 while the host's sync_k < 0 (written in stream order by ptg_reset,
+                                                      // ptg_set_state(k), ptg_create): a replayed launch finds the batch de-synchronised
 };
 
 struct HotLds {                  // per-workgroup LDS image
@@ -1334,6 +1337,7 @@ k_step_hot(const HotParams P, const void* __restrict__ actions, int actk, OUT* _
     const int e = live ? e_raw : P.N - 1;
     ST_STAMP(0);
     const StA a = P.st_a[e]; const StB b = P.st_b[e];     // state + action loads in flight while LDS is staged
+    const int desync = *P.desync;                          // (uniform address, nothing stored before it: a scalar load)
     int ri = 0; float rf = 0.f;
     hot_fetch(actk, actions, (size_t)e, ri, rf);
     hot_stage_lds(P, L);
@@ -1344,6 +1348,14 @@ k_step_hot(const HotParams P, const void* __restrict__ actions, int actk, OUT* _
     // The common step count comes from the STATE, not from a kernel argument: a launch captured into a hipGraph (policy forward + this
     // step, say) can be replayed step after step.  What a replay cannot do is route the one terminating step of an episode to the generic
     // kernel -- the host does that for eager calls --, so a hot kernel that finds itself on that step raises the sequence flag (ptg_note_replays).
+    // A replay after the batch was de-synchronised (partial reset, unequal step counts set by hand): k0 is one lane's clock, and another
+    // wave may be on its terminating step.  The captured step takes no step of its own: in the replay-proof form the generic kernel behind
+    // it takes the step (it reads every env's own k), otherwise the replay is refused (err[3], state untouched).
+    if (desync) {
+        if (skip_term) { if (blockIdx.x == 0 && threadIdx.x == 0) *P.term_flag = 1; }
+        else if (threadIdx.x == 0) P.err[3] = 1;
+        return;
+    }
     const int k0 = __builtin_amdgcn_readfirstlane(a.k);
     if (skip_term) {                                        // captured form: tell the generic kernel enqueued behind this one whether the step is its
         const bool term = k0 >= P.eps_sim_steps - 6;
@@ -1531,6 +1543,7 @@ k_rollout_pc(const HotParams P, const void* __restrict__ actions, int actk, int 
     const int e_wave = __builtin_amdgcn_readfirstlane(e_raw);                            // the wave's first env
     const bool wave_full = FULL || e_wave + 63 < P.N;                                    // all 64 envs of this wave exist
     const StA a = P.st_a[e]; const StB b = P.st_b[e];
+    const int desync = *P.desync;                           // (scalar load; read behind the prologue's barrier, see k0)
     HotRegs R;
     R.i = a.i; R.j = a.j; R.k = a.k; R.flags = a.flags; R.cum = b.cum; R.act_d = b.act_d; R.nctr = b.nctr;
     if (LDSLUT) {
@@ -1639,6 +1652,7 @@ k_rollout_pc(const HotParams P, const void* __restrict__ actions, int actk, int 
     PTG_STAMP(3);
     // step count of the launch's first step: from the state (a captured launch can be replayed, see k_step_hot).  Read HERE, behind the
     // prologue's barrier, where the state has long arrived: right behind its load the wait would hold up the staging loads (+0.5 us per launch)
+    if (desync) { if (threadIdx.x == 0) P.err[3] = 1; return; }      // a replay on a de-synchronised batch (see k_step_hot): refused, no store
     const int k0 = __builtin_amdgcn_readfirstlane(R.k);
     if (k0 + T > P.eps_sim_steps - 6) { if (threadIdx.x == 0) P.err[2] = 1; }      // the launch would run over the episode's terminating step
     const unsigned short* lut = LDSLUT ? s_lut : nullptr;
@@ -2057,6 +2071,7 @@ struct ptg_env {
     int n_cu = 256;
     std::vector<const void*> attr_done;   // kernels whose dynamic-LDS limit has been raised on this handle's device
     int* err_host = nullptr;     // DevParams::err as the host sees it
+    int* d_desync = nullptr;     // HotParams::desync: sync_k < 0 as the device sees it (set_desync)
     // ptg_step_host: device staging for batches too large for zero-copy, and the classification of the caller's buffers
     void *hs_act = nullptr, *hs_out = nullptr, *hs_final = nullptr; double* hs_info = nullptr;
     struct HostStep {            // a ptg_step_host call between its phases (begin .. tail .. end)
@@ -2354,6 +2369,7 @@ HotParams make_hot_params(const ptg_env* h)
     F.recf = P.recf; F.tape = P.tape; F.pool32 = h->d_pool32; F.pool64 = h->d_pool64; F.setc = P.setc; F.argidx = P.argidx;
     F.tabmeta = P.tabmeta; F.ladder = h->d_ladder; F.st_a = P.st_a; F.st_b = P.st_b; F.st_c = P.st_c; F.err = P.err;
     F.term_flag = P.term_flag;
+    F.desync = h->d_desync;
     return F;
 }
 
@@ -2609,6 +2625,16 @@ using ptg_hot::launch_rollout_hot;
 
 hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
+// The device mirror of `sync_k < 0` that hot kernels replayed from a hipGraph check (HotParams::desync), written in stream order
+// wherever the host changes whether the batch is synchronised.  `blocking`: a synchronous copy, ordered like ptg_set_state's own.
+int set_desync(ptg_env* h, hipStream_t st, bool desync, bool blocking = false)
+{
+    const int v = desync ? 1 : 0;
+    if (blocking) HIP_TRY(h, hipMemcpy(h->d_desync, &v, sizeof(int), hipMemcpyHostToDevice));
+    else HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->d_desync, v, 1, st));
+    return 0;
+}
+
 int check_error_flags(ptg_env* h)          // after the stream has been synchronised
 {
     // each word is exchanged with 0 on its own, and only the one being reported: a flag that another stream's kernel raises between
@@ -2623,6 +2649,13 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
     if (__atomic_load_n(&e[1], __ATOMIC_RELAXED)) {
         __atomic_exchange_n(&e[1], 0, __ATOMIC_RELAXED);
         return set_err(h, PTG_E_RANGE, "a price index left the market series (episode longer than the data)");
+    }
+    if (__atomic_load_n(&e[3], __ATOMIC_RELAXED)) {
+        __atomic_exchange_n(&e[3], 0, __ATOMIC_RELAXED);
+        return set_err(h, PTG_E_INVALID, "a captured hot launch was replayed after the batch was de-synchronised (a partial ptg_reset, or "
+                       "ptg_set_state of unequal step counts, after the capture): the replay took no step and left the state as it was; "
+                       "step eagerly, or re-synchronise the batch (full ptg_reset) before replaying (ptg_set_replay_proof(env, 1) captures a "
+                       "ptg_step whose replays fall back to the generic kernel)");
     }
     if (__atomic_load_n(&e[2], __ATOMIC_RELAXED)) {
         __atomic_exchange_n(&e[2], 0, __ATOMIC_RELAXED);
@@ -2854,6 +2887,8 @@ int ptg_create(const ptg_config* cfg, const ptg_tables* tables, const ptg_market
     }
     if ((rc = dev_alloc(h, &P.term_flag, 4))) return fail(rc);
     if (hipMemset(P.term_flag, 0, 4 * sizeof(int)) != hipSuccess) { set_err(h, PTG_E_HIP, "hipMemset failed"); return fail(PTG_E_HIP); }
+    h->d_desync = P.term_flag + 1;                      // the second word of the flag block: de-synchronised until the first full reset
+    if ((rc = set_desync(h, nullptr, true, true))) return fail(rc);
     {   // pinned staging of ptg_finished_episodes, sized for the whole ring (allocated here: a first query pays no hipHostMalloc)
         const size_t need = (size_t)P.fin_cap * (sizeof(double) + 2 * sizeof(int));
         if (hipHostMalloc(&h->fin_stage, need, hipHostMallocDefault) == hipSuccess) h->fin_stage_bytes = need;
@@ -3051,7 +3086,7 @@ int ptg_reset(ptg_env* h, const uint8_t* mask_host, void* obs_dev, void* stream)
     if (mask_host) { all = true; for (int e = 0; e < h->n && all; e++) all = mask_host[e] != 0; }
     if (all) { h->reset_done = true; h->sync_k = 0; }      // (a mask that selects every env is a full reset)
     else h->sync_k = -1;                                 // a partial reset de-synchronises the batch: generic kernels from here on
-    return 0;
+    return set_desync(h, st, !all);                      // ... and launches captured before it refuse their replays
 }
 
 // generic (any configuration, handles termination + auto-reset) launch of one vector step
@@ -3212,12 +3247,14 @@ int ptg_rollout_launches(ptg_env* h, int n_steps)
 int ptg_note_replays(ptg_env* h, int n_steps)
 {
     if (!h || n_steps < 0) return set_err(h, PTG_E_INVALID, "ptg_note_replays: bad argument");
-    if (h->sync_k < 0) return set_err(h, PTG_E_INVALID, "ptg_note_replays: the batch is not synchronised (captured hot launches do not exist for it)");
+    h->fin_maybe = true;                                 // replays may have run generic kernels: they can finish episodes
+    // De-synchronised batch: the replayed launches were generic kernels (captured while it was de-synchronised), the generic half of a
+    // replay-proof step, or refused hot kernels (reported by the next synchronising call).  There is no common count to advance.
+    if (h->sync_k < 0) return 0;
     // a captured ptg_step carries its own terminating-step kernel: replays may run across episode ends (the step count wraps at k_term + 1).
     // (A captured ptg_rollout must not: its kernel flags the overrun, see check_error_flags.)
     const long long period = (long long)(h->cfg.eps_sim_steps - 6) + 1;
     h->sync_k = (int)(((long long)h->sync_k + n_steps) % period);
-    h->fin_maybe = true;
     return 0;
 }
 
@@ -3684,6 +3721,7 @@ int ptg_set_state(ptg_env* h, int field, const void* in_host)
         bool same = true;
         for (int e = 1; e < n; e++) same = same && (a[e].k == a[0].k);
         h->sync_k = (same && a[0].k >= 0 && a[0].k <= h->cfg.eps_sim_steps - 6) ? a[0].k : -1;
+        return set_desync(h, nullptr, h->sync_k < 0, true);
     }
     return 0;
 }

@@ -320,9 +320,11 @@ class HipEngine:
         return int(s.value)
 
     def note_replays(self, n_steps):
-        """Tell the handle that captured hot launches were REPLAYED for `n_steps` vector steps in all (include/ptg_env.h, "hipGraph
-        capture"): step() / rollout() captured into a graph can be replayed because the kernels read the step count from the device state;
-        the host-side count that routes an episode's terminating step only sees eager calls and the capture itself."""
+        """Tell the handle how far replays of captured launches advanced the batch (include/ptg_env.h, "hipGraph capture"): `n_steps` =
+        the vector steps of ALL replays minus those of one replay, because the capture call already counted as one execution -- R replays
+        of a captured step: R - 1; R replays of a captured T-step rollout: (R - 1) * T.  step() / rollout() captured into a graph can be
+        replayed because the kernels read the step count from the device state; the host-side count that routes an episode's terminating
+        step only sees eager calls and the capture itself.  On a de-synchronised batch it only marks finished episodes as possible."""
         self._chk(self._L.ptg_note_replays(self._h, int(n_steps)))
 
     def set_replay_proof(self, enable=True):
