@@ -27,10 +27,11 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 5   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 6   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
-                             * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed) */
+                             * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
+                             * 6: + ptg_vn_clear_done (frozen reward normalisation clears the returns of finished envs on the device) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -311,11 +312,15 @@ int ptg_finished_dropped(ptg_env* env, uint64_t* dropped_total);
  * handle's returns and yields per-step (count, mean, M2) of its envs; the caller merges the shards' moments (Chan's formula,
  * rl_ptg_amd.dist.merge_moments -- one all-gather per rollout) and hands the merged [T][3] array to ptg_vn_apply, which
  * updates the running statistics step by step and writes the normalised rewards.  moments_dev NULL = single-GPU: the
- * handle's own moments are used. */
+ * handle's own moments are used.  A NaN reward propagates as in np.clip (NaN statistics, NaN outputs from then on).
+ * Frozen statistics (SB3 training = False): skip ptg_vn_batch_moments, call ptg_vn_apply with training = 0 (returns not
+ * advanced, statistics unchanged) and ptg_vn_clear_done with the window's [T][N] done flags, which does returns[done] = 0:
+ * an env's return is zeroed iff any of its T flags is set. */
 int ptg_vn_init(ptg_env* env, double gamma, double epsilon, double clip_reward);      /* SB3 defaults: 0.99, 1e-8, 10.0 */
 int ptg_vn_batch_moments(ptg_env* env, const void* rew_dev, const uint8_t* done_dev, int n_steps, double* moments_dev, void* stream);
 int ptg_vn_apply(ptg_env* env, const void* rew_dev, int n_steps, const double* moments_dev, void* rew_out_dev, int training,
                  void* stream);
+int ptg_vn_clear_done(ptg_env* env, const uint8_t* done_dev, int n_steps, void* stream);
 /* running statistics {mean, var, count} and the per-env discounted returns (either pointer may be NULL) */
 int ptg_vn_get(ptg_env* env, double* stats3_host, double* returns_host);
 int ptg_vn_set(ptg_env* env, const double* stats3_host, const double* returns_host);

@@ -2024,7 +2024,20 @@ k_vn_norm(const OUT* __restrict__ rew, OUT* __restrict__ out, const double* __re
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
     const double v = (double)rew[g] / den[g / (size_t)N];
-    out[g] = (OUT)fmin(fmax(v, -clip), clip);               // np.clip
+    const double lo = v < -clip ? -clip : v;                // np.clip: compare-selects that fall through to v, so a NaN stays
+    out[g] = (OUT)(lo > clip ? clip : lo);                  // NaN (fmax(NaN, x) would be x)
+}
+
+// Frozen statistics (training == 0): the returns are not advanced, only returns[done] = 0 after every step -- so over a T-step
+// window an env's return is zeroed iff any of its T done flags is set.
+__global__ void __launch_bounds__(256)
+k_vn_clear_done(const uint8_t* __restrict__ done, int N, int T, double* __restrict__ returns)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    bool any = false;
+    for (int t = 0; t < T; t++) any |= done[(size_t)t * N + e] != 0;
+    if (any) returns[e] = 0.0;
 }
 
 }  // namespace
@@ -3539,6 +3552,15 @@ int ptg_vn_apply(ptg_env* h, const void* rew_dev, int n_steps, const double* mom
     else
         hipLaunchKernelGGL(k_vn_norm<float>, grid, block, 0, st, (const float*)rew_dev, (float*)rew_out_dev, h->vn_den, h->n, total, h->vn_clip);
     return launch_check(h, "k_vn_norm");
+}
+
+int ptg_vn_clear_done(ptg_env* h, const uint8_t* done_dev, int n_steps, void* stream)
+{
+    if (!h || !done_dev || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_vn_clear_done: bad argument");
+    if (!h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_vn_clear_done: call ptg_vn_init first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_vn_clear_done, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), done_dev, h->n, n_steps, h->vn_returns);
+    return launch_check(h, "k_vn_clear_done");
 }
 
 int ptg_vn_get(ptg_env* h, double* stats3_host, double* returns_host)

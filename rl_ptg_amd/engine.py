@@ -419,6 +419,7 @@ class HipEngine:
         d2 = done if done.dim() == 2 else done.unsqueeze(0)
         T = r2.shape[0]
         assert r2.shape == (T, self.n) and d2.shape == (T, self.n) and r2.is_contiguous() and d2.is_contiguous()
+        assert r2.dtype == self.out_dtype and d2.element_size() == 1, (r2.dtype, d2.dtype)    # what the kernels read
         res = torch.empty_like(r2) if out is None else (out if out.dim() == 2 else out.unsqueeze(0))
         with torch.cuda.device(self.device):
             mom = None
@@ -429,6 +430,8 @@ class HipEngine:
                 mom = ptg_dist.all_merge_moments(mom, group=group)
             self._chk(self._L.ptg_vn_apply(self._h, C.c_void_p(r2.data_ptr()), T, C.c_void_p(mom.data_ptr()) if mom is not None else None,
                                            C.c_void_p(res.data_ptr()), 1 if training else 0, self._stream()))
+            if not training:                                # frozen statistics: returns[done] = 0 all the same (SB3 step_wait)
+                self._chk(self._L.ptg_vn_clear_done(self._h, C.c_void_p(d2.data_ptr()), T, self._stream()))
         return res if rew.dim() == 2 else res[0]
 
     def vn_get(self):

@@ -451,10 +451,6 @@ class PtGVecEnv(_VecEnvBase):
             h_final = self._to_host("final", eng.rows(eng.final_obs))      # rare: only steps on which an episode ends
             eng.sync()
             final = h_final.numpy()
-            if not self.training:                             # VecNormalize: self.returns[dones] = 0 also with frozen statistics
-                _, ret = eng.vn_get()
-                ret[dones] = 0.0
-                eng.vn_set(returns=ret)
         infos = self._finish_infos(dones, n_done, final)
         if self.noise_mode == "numpy":
             self._steps_since_refill += 1
