@@ -182,7 +182,15 @@ class PtGVecEnv(_VecEnvBase):
         self.engine.set_noise_tape(self._tape)
         self._steps_since_refill = 0
 
+    def _count_noise_step(self):
+        """noise="numpy": one more step has read the tape (at most one draw per env); refill before it can wrap."""
+        if self.noise_mode == "numpy":
+            self._steps_since_refill += 1
+            if self._steps_since_refill >= self._tape_len:
+                self._refill_tape()
+
     def seed(self, seed=None):
+        self._drain()
         self._seed = seed
         self._apply_seed(seed)
         return [None if seed is None else seed + self.env_offset + e for e in range(self.num_envs)]
@@ -300,6 +308,7 @@ class PtGVecEnv(_VecEnvBase):
 
     # ------------------------------------------------------------------ VecEnv API
     def reset(self):
+        self._drain()
         obs = self.engine.rows(self.engine.reset()).cpu().numpy()
         self.engine.sync()
         self._ep_start[:] = time.time()
@@ -335,6 +344,9 @@ class PtGVecEnv(_VecEnvBase):
         return rows
 
     def step_async(self, actions):
+        if self._in_flight is not None:
+            # the kernels of the step in flight may still be reading the pinned action buffer: refuse before touching it
+            raise RuntimeError("PtGVecEnv: step_async() called again before step_wait() collected the previous step")
         a = np.asarray(actions)
         if self.action_type == "continuous":
             a = a.reshape(self.num_envs, -1)[:, 0]
@@ -358,6 +370,17 @@ class PtGVecEnv(_VecEnvBase):
         if rc:
             eng._chk(rc)
         self._in_flight = slot
+
+    def _drain(self):
+        """End a host step that step_async began and step_wait never collected (reset / load_state_dict / seed / close came first):
+        wait for its copies into the pinned blocks, discard its outputs.  The step itself has run -- its noise draws and episode
+        ends count -- so the noise tape is advanced as after any step."""
+        if self._in_flight is None:
+            return
+        self._in_flight = None
+        eng = self.engine
+        eng._L.ptg_step_host_end(eng._h)                      # status ignored: nothing of this step is handed out
+        self._count_noise_step()
 
     def _finish_infos(self, dones, n_done, final_mat):
         """Monitor / DummyVecEnv conventions for the envs whose episode ended; everything else keeps its persistent entry."""
@@ -423,10 +446,7 @@ class PtGVecEnv(_VecEnvBase):
         infos = self._finish_infos(dones, self._n_done.value, self._final_mat)
         if self._copy_out:
             infos = list(infos)                               # a new list object every step (entries shared), like DummyVecEnv's deepcopy'd buf_infos
-        if self.noise_mode == "numpy":
-            self._steps_since_refill += 1
-            if self._steps_since_refill >= self._tape_len:
-                self._refill_tape()
+        self._count_noise_step()
         return obs, rews, dones, infos
 
     def _step_wait_device(self):
@@ -452,10 +472,7 @@ class PtGVecEnv(_VecEnvBase):
             eng.sync()
             final = h_final.numpy()
         infos = self._finish_infos(dones, n_done, final)
-        if self.noise_mode == "numpy":
-            self._steps_since_refill += 1
-            if self._steps_since_refill >= self._tape_len:
-                self._refill_tape()
+        self._count_noise_step()
         return self._obs_dict(obs), rews, dones, infos          # copies: the staging buffers are reused by the next step
 
     def step(self, actions):
@@ -475,6 +492,7 @@ class PtGVecEnv(_VecEnvBase):
 
     def load_state_dict(self, sd):
         assert sd["noise_mode"] == self.noise_mode
+        self._drain()
         if self._needs_reset:
             self.reset()
         self.engine.load_state_dict(sd["engine"])
@@ -487,10 +505,17 @@ class PtGVecEnv(_VecEnvBase):
         self._needs_reset = bool(sd["needs_reset"])
 
     def step_tensors(self, actions):
-        """Device path: enqueue one step, return (obs, rewards, dones) ROCm tensors without synchronising."""
-        return self.engine.step(actions, want_final=False)
+        """Device path: enqueue one step, return (obs, rewards, dones) ROCm tensors without synchronising -- except with noise="numpy"
+        on every noise_tape_len-th step, where the tape is refilled as step() refills it (the counts of drawn noise are read back)."""
+        self._drain()
+        out = self.engine.step(actions, want_final=False)
+        if self.noise_mode == "numpy" and self._steps_since_refill + 1 >= self._tape_len:
+            self.engine.sync()
+        self._count_noise_step()
+        return out
 
     def close(self):
+        self._drain()
         self.engine.close()
 
     def get_attr(self, attr_name, indices=None):

@@ -176,12 +176,14 @@ def test_create_destroy_does_not_leak_device_memory():
     assert abs(free0 - free1) < (32 << 20), (free0, free1)
 
 
-@pytest.mark.parametrize("n,layout,dtype", [(6, "row", "float64"), (4096, "row", "float32"), (4096, "feature", "float64"), (333, "row", "float32")])
+@pytest.mark.parametrize("n,layout,dtype", [(6, "row", "float64"), (4096, "row", "float32"), (4096, "feature", "float64"), (333, "row", "float32"),
+                                             (1001, "row", "float64")])
 def test_host_step_phases_and_status_section(n, layout, dtype):
     """ptg_step_host_begin / _tail / _end (include/ptg_env.h) through raw ctypes, as a C caller would drive them: after `tail` the rewards,
     done flags and the contiguous METH_STATUS bytes are in the block, after `end` the observations; the three phases produce what the
-    one-call ptg_step_host produces on a twin handle (zero-copy route at n = 6, staged route above), and the status bytes equal the
-    METH_STATUS column of the returned rows.  Calling the phases out of order is PTG_E_INVALID, not UB."""
+    one-call ptg_step_host produces on a twin handle, and the status bytes equal the METH_STATUS column of the returned rows.  Calling
+    the phases out of order is PTG_E_INVALID, not UB.  Routes (block + final rows + actions against the 256 KiB zero-copy limit):
+    zero-copy at n = 6 and n = 333 (float32 rows: 48 618 + 46 620 + 1 332 bytes), staged at n = 1001 (float64 rows) and n = 4096."""
     import ctypes as C
     import torch
     from rl_ptg_amd.engine import HipEngine
@@ -198,7 +200,9 @@ def test_host_step_phases_and_status_section(n, layout, dtype):
         t3 = C.c_size_t()
         assert L.ptg_host_layout(h, None, None, C.byref(t3)) == 0 and t3.value == total.value      # the old call reports the same block size
         assert o_rew.value % 16 == 0 and o_done.value % 16 == 0 and o_stat.value % 16 == 0 and total.value >= o_stat.value + n
-        blk = torch.empty(total.value, dtype=torch.uint8, pin_memory=True)
+        staged = total.value + n * eng.obs_dim * (8 if dtype == "float64" else 4) + n * 4 > (256 << 10)
+        assert staged == (n >= 1001), (n, total.value)
+        blk = torch.zeros(total.value, dtype=torch.uint8, pin_memory=True)        # the padding between sections is never written: zero in both runs
         act = torch.empty(n, dtype=torch.int32, pin_memory=True)
         fin = torch.empty(n * eng.obs_dim * (8 if dtype == "float64" else 4), dtype=torch.uint8, pin_memory=True)
         nd = C.c_int(-1)
@@ -226,8 +230,8 @@ def test_host_step_phases_and_status_section(n, layout, dtype):
         assert len({int(x) for r in rows for x in np.unique(r[o_stat.value:o_stat.value + n])}) >= 3    # several METH_STATUS values occurred
         outs.append(rows)
         eng.close()
-    for a, b in zip(*outs):
-        assert np.array_equal(a, b)
+    for t, (a, b) in enumerate(zip(*outs)):
+        assert np.array_equal(a, b), (t, np.nonzero(a != b)[0][:16])
 
 
 def test_copy_obs_switch_and_layout_guard():
