@@ -27,11 +27,12 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 6   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 7   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
-                             * 6: + ptg_vn_clear_done (frozen reward normalisation clears the returns of finished envs on the device) */
+                             * 6: + ptg_vn_clear_done (frozen reward normalisation clears the returns of finished envs on the device);
+                             * 7: + ptg_debug_table_plan */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -333,6 +334,9 @@ int ptg_market_feature_series(ptg_env* env, int which, float* out_host, int cap,
 /* diagnostics for tests: the device-built lookup products */
 int ptg_debug_get_index_lut(ptg_env* env, double* T_values_host, int32_t* lut_host /*[6][nT]*/, int* n_T);
 int ptg_debug_window_record(ptg_env* env, int table_id, int start_row, double* out7_host /*T_last, 5 means, key*/);
+/* what the tables made of the handle (read-only): {16-bit lookup copy exists, the fused rollout keeps it in LDS, nT, key of the initial
+ * temperature, reset row of cooldown, key_cold_max, key_hot_min, key_standby_max} */
+int ptg_debug_table_plan(ptg_env* env, int32_t* out8_host);
 
 #ifdef __cplusplus
 }

@@ -2207,6 +2207,8 @@ int build_tables(ptg_env* h, const ptg_tables* tb)
         }
     }
     if (tb->rows[PTG_T_OP1_START_P] < S) return set_err(h, PTG_E_INVALID, "op1_start_p is shorter than one step");
+    // one window record per row and one more per table; k_rollout_pc hands the record index on in 24 bits (PcSlot)
+    if (total_rows + NT > 0xFFFFFFu) return set_err(h, PTG_E_INVALID, "more than 16777215 window records (%zu table rows)", total_rows);
     Tv.push_back(h->cfg.t_cat_initial);
     std::sort(Tv.begin(), Tv.end());
     Tv.erase(std::unique(Tv.begin(), Tv.end()), Tv.end());
@@ -3844,6 +3846,16 @@ int ptg_debug_window_record(ptg_env* h, int table_id, int start_row, double* out
     out7_host[0] = r.T;
     for (int c = 0; c < 5; c++) out7_host[1 + c] = r.m[c];
     out7_host[6] = (double)r.tkey;
+    return 0;
+}
+
+int ptg_debug_table_plan(ptg_env* h, int32_t* out8_host)
+{
+    if (!h || !out8_host) return set_err(h, PTG_E_INVALID, "null argument");
+    const PcPlan pl = pc_plan(h);
+    const DevParams& P = h->P;
+    const int32_t v[8] = {h->d_lut16 ? 1 : 0, pl.lds_lut ? 1 : 0, P.nT, P.key_init, P.i_reset, P.key_cold_max, P.key_hot_min, P.key_standby_max};
+    memcpy(out8_host, v, sizeof v);
     return 0;
 }
 

@@ -464,6 +464,13 @@ class HipEngine:
         self._chk(self._L.ptg_debug_get_index_lut(self._h, _dp(T), lut.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nT)))
         return T, lut
 
+    def debug_table_plan(self):
+        """What the tables made of this handle: dict(has_lut16, lds_lut, nT, key_init, i_reset, key_cold_max, key_hot_min, key_standby_max)."""
+        out = np.zeros(8, np.int32)
+        self._chk(self._L.ptg_debug_table_plan(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        keys = ("has_lut16", "lds_lut", "nT", "key_init", "i_reset", "key_cold_max", "key_hot_min", "key_standby_max")
+        return {k: int(v) for k, v in zip(keys, out)}
+
     def debug_window_record(self, table_id, start_row):
         out = np.zeros(7)
         self._chk(self._L.ptg_debug_window_record(self._h, int(table_id), int(start_row), _dp(out)))

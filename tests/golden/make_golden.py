@@ -13,6 +13,7 @@ Files written
                              bounds, r_level, T-OPT totals  (reference: load_data + Preprocessing)
   traj_<case>.npz            trajectories of n reference envs stepped in DummyVecEnv order
   units_<op>.npz             _get_index for every distinct T_cat x 6 destination tables
+`make_golden.py tables` writes only the trajectories on generated process tables (synthetic_table_cases).
 """
 import json
 import math
@@ -24,7 +25,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "oracle", "refharness"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
+import helpers as H                          # noqa: E402  (table generator, action tapes)
 import ref_driver as rd                      # noqa: E402
 import ptg_oracle as po                      # noqa: E402
 from rl_ptg_amd.synthetic import synthetic_market_csv_units  # noqa: E402
@@ -49,13 +52,8 @@ def synth_markets():
 
 
 def sticky_tape(rng, K, n, p=1 / 12.0):
-    a = np.zeros((K, n), np.int64)
-    cur = rng.integers(0, 5, n)
-    for t in range(K):
-        sw = rng.random(n) < p
-        cur = np.where(sw, rng.integers(0, 5, n), cur)
-        a[t] = cur
-    return a
+    """tests/helpers.sticky_tape (same draws), as the int64 the fixtures above were recorded with"""
+    return H.sticky_tape(rng, K, n, p).astype(np.int64)
 
 
 def toggler_tape(rng, K, n, max_hold=25, warm=None):
@@ -131,9 +129,11 @@ def save_prep(name, setup, extra_meta):
     print(f"  prep_{name}.npz  n_eps={pre.n_eps} eps_ind={len(pre.eps_ind)} r_level={pre.r_level[0]:.8f}")
 
 
-def save_traj(case, setup, prep_name, split, train_or_eval, actions, seed, kw_over=None, note="", extra_meta=None):
+def save_traj(case, setup, prep_name, split, train_or_eval, actions, seed, kw_over=None, note="", extra_meta=None, tables=None):
+    """tables: a generated table set handed to the reference in place of the one it loaded; it is stored in the fixture (tab_<name>)"""
     kw = dict(setup.kwargs(split))
     kw.update(kw_over or {})
+    kw.update(tables or {})
     out = rd.run_vector(kw, actions, seed=seed, train_or_eval=train_or_eval)
     consts, _, market = po.split_reference_kwargs(kw, train_or_eval)
     meta = dict(case=case, prep=prep_name, split=split, train_or_eval=train_or_eval, n_envs=int(actions.shape[1]),
@@ -147,6 +147,7 @@ def save_traj(case, setup, prep_name, split, train_or_eval, actions, seed, kw_ov
                 eps_ind=np.zeros(0) if market["eps_ind"] is None else market["eps_ind"])
     if "infos" in out:
         arrs["infos"] = out["infos"]
+    arrs.update({f"tab_{k}": np.asarray(v, dtype=np.float64) for k, v in (tables or {}).items()})
     np.savez_compressed(os.path.join(OUT, f"traj_{case}.npz"), meta=json.dumps(meta), **arrs)
     ints = out["ints"]
     pt, ft = set(ints[..., 6].reshape(-1).tolist()), set(ints[..., 7].reshape(-1).tolist())
@@ -331,7 +332,66 @@ def main():
               note="price_ahead=25, whole test split: the reference raises IndexError on step fail_step (hour fail_h), "
                    "which is not part of the trajectory", extra_meta=dict(fail_step=t_fail, fail_h=h_fail, fail_action=int(acts[t_fail, 0])))
     s.close()
+    synthetic_table_cases()
     print("done")
+
+
+def synthetic_table_cases():
+    """Process tables other than the shipped ones (tests/helpers.make_tables), handed to the unmodified reference: the oracle is pinned
+    to it on tables shorter than one window, on exact ties of _get_index and with thresholds outside the temperature range.  Runs on its
+    own too (`make_golden.py tables`): the files above are not touched."""
+    sm = synth_markets()
+    print("synthetic / BS2 / OP2 / generated tables around one window (S = 300), integer temperatures that tie")
+    g = np.random.default_rng(3001)
+    rows = dict(startup_cold=299, startup_hot=65, cooldown=601, standby_down=64, standby_up=63, op1_start_p=300, op2_start_f=301,
+                op3_p_f=2, op4_p_f_p_5=1, op5_p_f_p_10=700, op6_p_f_p_15=300, op7_p_f_p_22=299, op8_f_p=301, op9_f_p_f_5=64,
+                op10_f_p_f_10=1, op11_f_p_f_15=900, op12_f_p_f_20=65)
+    even, odd = np.arange(0.0, 600.0, 2.0), np.arange(1.0, 600.0, 2.0)
+    own = {k: (odd if k == "cooldown" or k not in H.DEST_KEYS else even) for k in rd.TABLE_KEYS}
+    tables = H.make_tables(g, dict(rows=rows, grid=np.arange(0.0, 600.0), grid_of=own))
+    tables["cooldown"] = tables["cooldown"][tables["cooldown"][:, 1] != 16.0]
+    tables["cooldown"][-3:-1, 1] = (17.0, 15.0)
+    # thresholds on temperatures the envs sit on: the last rows of cooldown (its only coldest), standby_up (its only hottest), op3_p_f, op8_f_p
+    cd, su = tables["cooldown"], tables["standby_up"]
+    cd[cd[:, 1] <= 1.0, 1] = 3.0
+    cd[-1, 1] = 1.0
+    su[su[:, 1] >= 598.0, 1] = 596.0
+    su[-1, 1] = 598.0
+    tables["op3_p_f"][-1, 1] = tables["op8_f_p"][-1, 1] = 251.0
+    assert H.count_lookup_ties(tables) > 100
+    s = rd.RefSetup(dict(scenario=2, operation="OP2", eps_len_d=2), synthetic_market=sm, train_steps=20000)
+    acts = H.toggler_tape(g, 420, 4, warm=6)
+    acts[:, 2:] = H.sticky_tape(g, 420, 2, 1 / 5.0)
+    out = save_traj("synth_bs2_tables_short_ties", s, "synth_bs2_OP2", "train", "train", acts, 3660, dict(t_cat_startup_cold=1.0,
+                    t_cat_startup_hot=598.0, t_cat_standby=251.0), tables=tables,
+                    note="generated tables of 1 .. 2 S + 1 rows (S = 300) on integer temperatures: ties of _get_index, thresholds on table "
+                         "temperatures, eps_len_d=2 (283-step episodes)")
+    # (both start-up tables are shorter than one window: a start-up hands over to partial load within its first step)
+    assert out["done"].sum() >= 4 and set(out["ints"][..., 0].reshape(-1).tolist()) == {0, 1, 3, 4}
+    assert set(out["ints"][..., 3].reshape(-1).tolist()) == {0, 1}
+    Tc, hc = out["f64s"][:-1, :, 2], out["ints"][:-1, :, 3]            # state a step starts from (no episode end in between matters here)
+    n_cold, n_hot = int(((Tc == 1.0) & (hc == 1)).sum()), int(((Tc == 598.0) & (hc == 0)).sum())
+    n_sb = int(((Tc == 251.0) & (out["ints"][:-1, :, 0] != 0) & (out["actions"][1:] == 0)).sum())
+    print(f"  steps decided by equality with a threshold: cold {n_cold}, hot {n_hot}, stand-by {n_sb}")
+    assert n_cold > 0 and n_hot > 0 and n_sb > 0
+    s.close()
+
+    print("synthetic / BS1 / OP1 / sim_step 60, generated tables around one window (S = 30), thresholds outside the temperature range")
+    g = np.random.default_rng(3002)
+    rows = dict(startup_cold=500, startup_hot=31, cooldown=61, standby_down=1, standby_up=2, op1_start_p=30, op2_start_f=63,
+                op3_p_f=64, op4_p_f_p_5=65, op5_p_f_p_10=30, op6_p_f_p_15=31, op7_p_f_p_22=29, op8_f_p=500, op9_f_p_f_5=1,
+                op10_f_p_f_10=2, op11_f_p_f_15=800, op12_f_p_f_20=64)
+    tables = H.make_tables(g, dict(rows=rows, grid=np.linspace(0.0, 598.7, 300)))
+    s = rd.RefSetup(dict(scenario=1, operation="OP1", eps_len_d=1, sim_step=60), synthetic_market=sm, train_steps=200000)
+    acts = H.toggler_tape(g, 600, 3, warm=20)
+    acts[:, 2:] = H.sticky_tape(g, 600, 1, 1 / 8.0)
+    out = save_traj("synth_bs1_tables_s30_thresholds_outside", s, "synth_bs1_OP1", "train", "train", acts, 3661,
+                    dict(t_cat_startup_cold=-5.0, t_cat_startup_hot=1000.0, t_cat_standby=-3.0), tables=tables,
+                    note="generated tables of 1 .. 2 S + 1 rows (S = 30) beside three of 500 .. 800; every threshold outside the tables' temperatures: hot_cold stays 0, "
+                         "stand-by always standby_down")
+    assert set(out["ints"][..., 0].reshape(-1).tolist()) == {0, 1, 2, 3, 4}
+    assert set(out["ints"][..., 3].reshape(-1).tolist()) == {0} and set(out["ints"][..., 4].reshape(-1).tolist()) == {3}
+    s.close()
 
 
 def ref_t_opt(setup):
@@ -369,4 +429,7 @@ def ref_failing_step(kw, actions, seed, train_or_eval):
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["tables"]:
+        synthetic_table_cases()
+    else:
+        main()

@@ -78,7 +78,9 @@ def load_traj(case):
     market = dict(_full_series(meta), eps_ind=tr["eps_ind"] if len(tr["eps_ind"]) else None)
     for k in ("el", "pot_rew", "part_full"):          # e_r_b covers all hours but the last, whatever P is
         market[k] = market[k][:-1]
-    return tr, dict(meta["consts"]), load_tables(meta["operation"]), market
+    # a fixture made on generated process tables carries them (tab_<name>); the others use the shipped set of their load level
+    tables = {k: tr[f"tab_{k}"] for k in po.TABLE_KEYS} if "tab_cooldown" in tr else load_tables(meta["operation"])
+    return tr, dict(meta["consts"]), tables, market
 
 
 def _full_series(meta):
@@ -128,3 +130,121 @@ def kwargs_from_fixture(case):
     kw.update({f"ptg_{k}": i for i, k in enumerate(["standby", "cooldown", "startup", "partial_load", "full_load"])})
     kw.update(tables)
     return tr, kw
+
+
+# ------------------------------------------------------------------------------------------------ synthetic process tables
+DEST_KEYS = ["cooldown", "standby_up", "standby_down", "startup_cold", "startup_hot", "op1_start_p"]      # _get_index destinations, lookup order
+# magnitudes of the shipped tables' columns n_h2, n_ch4, n_h2_res, m_h2o, P_el (their largest entries; no row is copied)
+COL_HI = np.array([0.0485, 0.0118, 0.0027, 1.55, 1750.0])
+# (lowest, highest) fraction of COL_HI per column, by the role of a table
+_LEVELS = {"startup": [(0.0, 0.15), (0.0, 0.14), (0.0, 0.04), (0.0, 0.001), (0.1, 1.0)],
+           "idle": [(0.0, 0.08), (0.0, 0.0), (0.0, 0.0), (0.0, 0.0006), (0.0, 0.4)],
+           "partial": [(0.14, 0.45), (0.14, 0.42), (0.03, 0.6), (0.0, 0.6), (0.08, 0.37)],
+           "full": [(0.4, 1.0), (0.4, 1.0), (0.1, 1.0), (0.3, 1.0), (0.1, 0.28)]}
+
+
+def _role(key):
+    if key.startswith("startup"):
+        return "startup"
+    if key in ("cooldown", "standby_down", "standby_up"):
+        return "idle"
+    return "partial" if key in ("op1_start_p", "op4_p_f_p_5", "op5_p_f_p_10", "op6_p_f_p_15", "op7_p_f_p_22", "op8_f_p") else "full"
+
+
+def make_tables(rng, spec):
+    """The 17 process tables as `[rows, 7]` float64 arrays (columns t, T_cat, n_h2, n_ch4, n_h2_res, m_h2o, P_el), generated.
+
+    spec: rows      {table: rows}; tables not named get `default_rows` (an int, or (lo, hi) drawn per table)
+          grid      1-D array of distinct catalyst temperatures.  With `cover` (default) every grid value occurs in at least one table,
+                    so the number of distinct temperatures of the set is exactly len(grid) (+ 1 when 16.0, the reset temperature, is
+                    not in the grid)
+          grid_of   {table: 1-D array}: that table draws from its own values instead (tie families: destinations on even, sources on
+                    odd integers); such tables take no part in the covering
+          shape     {table: "rise" | "fall" | "tent"}; default: cooldown and standby_down fall, start-up tables and standby_up rise,
+                    load tables go up and come back
+    Like the shipped tables, a temperature column is not monotonic (neighbouring rows are swapped at random) and holds runs of equal
+    values wherever a table has more rows than temperatures; flows and power follow slow waves at the shipped tables' magnitudes, low for
+    the idle tables and high for the load tables, and the second half of cooldown draws no power at all (rewards of exactly zero)."""
+    grid = np.unique(np.asarray(spec["grid"], dtype=np.float64))
+    rows, own = dict(spec.get("rows", {})), spec.get("grid_of", {})
+    dr = spec.get("default_rows", 2500)
+    for k in po.TABLE_KEYS:
+        if k not in rows:
+            rows[k] = int(dr) if np.isscalar(dr) else int(rng.integers(dr[0], dr[1] + 1))
+    # which temperatures each table uses
+    vals = {}
+    for k in po.TABLE_KEYS:
+        src = np.unique(np.asarray(own[k], dtype=np.float64)) if k in own else grid
+        m = max(1, min(int(rows[k] * rng.uniform(0.3, 0.7)), int(len(src) * rng.uniform(0.35, 1.0))))
+        vals[k] = np.sort(rng.choice(src, size=m, replace=False))
+    free = [k for k in po.TABLE_KEYS if k not in own]
+    if spec.get("cover", True) and free:
+        missing = np.setdiff1d(grid, np.concatenate([vals[k] for k in free]))
+        for k in sorted(free, key=lambda k: len(vals[k]) - rows[k]):
+            take = min(len(missing), rows[k] - len(vals[k]))
+            vals[k] = np.union1d(vals[k], missing[:take])
+            missing = missing[take:]
+        if len(missing):
+            raise ValueError(f"{len(missing)} temperatures of the grid do not fit into the tables' rows")
+    out = {}
+    for k in po.TABLE_KEYS:
+        n, v = rows[k], vals[k]
+        m = len(v)
+        idx = np.sort(np.concatenate([np.arange(m), rng.integers(0, m, n - m)]))
+        shape = spec.get("shape", {}).get(k) or ("fall" if k in ("cooldown", "standby_down") else
+                                                "rise" if _role(k) == "startup" or k == "standby_up" else "tent")
+        if shape == "fall":
+            idx = idx[::-1].copy()
+        elif shape == "tent":
+            idx = np.concatenate([idx[::2], idx[1::2][::-1]])
+        for p in np.flatnonzero(rng.random(max(n - 1, 0)) < 0.15):          # not monotonic
+            idx[p], idx[p + 1] = idx[p + 1], idx[p]
+        a = np.zeros((n, 7))
+        a[:, 0] = 2.0 * np.arange(n)
+        a[:, 1] = v[idx]
+        u = np.arange(n) / max(n, 64)
+        for c, (lo, hi) in enumerate(_LEVELS[_role(k)]):
+            wave = 0.5 + 0.5 * np.sin(2 * np.pi * (rng.uniform(0.5, 3.0) * u + rng.random()))
+            a[:, 2 + c] = COL_HI[c] * (lo + (hi - lo) * wave) * np.abs(1.0 + 0.02 * rng.normal(size=n))
+        if k == "cooldown":
+            a[n // 2:, 2:] = 0.0
+        out[k] = a
+    return out
+
+
+def count_lookup_ties(tables, t_initial=16.0):
+    """(keys x destination tables) pairs whose nearest temperature is tied between two DIFFERENT table temperatures, one on each side of
+    the key: there `_get_index` depends on "the first minimum wins"."""
+    keys = np.unique(np.concatenate([tables[k][:, 1] for k in po.TABLE_KEYS] + [np.array([t_initial])]))
+    ties = 0
+    for k in DEST_KEYS:
+        col = np.unique(tables[k][:, 1])
+        d = np.abs(col[None, :] - keys[:, None])
+        ties += int(np.sum((d == d.min(axis=1, keepdims=True)).sum(axis=1) > 1))
+    return ties
+
+
+def sticky_tape(rng, K, n, p=1 / 12.0):
+    a = np.zeros((K, n), np.int32)
+    cur = rng.integers(0, 5, n)
+    for t in range(K):
+        cur = np.where(rng.random(n) < p, rng.integers(0, 5, n), cur)
+        a[t] = cur
+    return a
+
+
+def toggler_tape(rng, K, n, warm):
+    """start-up for `warm` steps, then holds of random length over all five actions with a bias towards partial <-> full toggles (the
+    tape of test_fuzz_config.py as an array)"""
+    a = np.zeros((K, n), np.int32)
+    hold = rng.integers(1, 14, n)
+    cur = rng.integers(0, 5, n)
+    for t in range(K):
+        if t < warm:
+            a[t] = 2
+            continue
+        flip = (t - warm) % hold == 0
+        toggle = rng.random(n) < 0.6
+        cur = np.where(flip, np.where(toggle & (cur >= 3), 7 - cur, rng.integers(0, 5, n)), cur)
+        a[t] = cur
+    return a
