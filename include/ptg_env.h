@@ -27,12 +27,13 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 7   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 8   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
                              * 6: + ptg_vn_clear_done (frozen reward normalisation clears the returns of finished envs on the device);
-                             * 7: + ptg_debug_table_plan */
+                             * 7: + ptg_debug_table_plan;
+                             * 8: + ptg_finished_episodes_dev, ptg_episode_stats_dev (the finished-episode list handed over on the device) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -300,8 +301,29 @@ int ptg_finished_episodes(ptg_env* env, double* returns_host, int32_t* lengths_h
  * A sharded job uses it to issue the episodic-return all-gather only in windows that contain an episode boundary. */
 int ptg_steps_to_episode_end(ptg_env* env, int* steps);
 /* Finished episodes that were never handed out since ptg_create: overwritten in the ring before a query came, or cut off by a
- * query's `cap`.  0 for every caller that queries at least once per 2 * n_envs finished episodes with cap >= that. */
+ * query's `cap`.  0 for every caller that queries at least once per 2 * n_envs finished episodes with cap >= that.  Counts the host
+ * query (ptg_finished_episodes) only: a device drain reports its own drops in count_dev[1]. */
 int ptg_finished_dropped(ptg_env* env, uint64_t* dropped_total);
+/* Stream-ordered hand-over of the finished-episode list, device to device.  Enqueues kernels only: no host
+ * synchronisation, no host copy, so it may be captured into a hipGraph behind a (replay-proof) ptg_step.
+ *   ret_dev  [cap] float64   len_dev [cap] int32   env_dev [cap] int32 (GLOBAL env index = offset + e)   -- each nullable
+ *   count_dev uint32[2]: [0] entries in the caller's list, [1] entries dropped
+ *   append = 0: the list starts at 0 (count_dev is overwritten);  append = 1: entries go behind count_dev[0], drops add to [1]
+ * Takes the live entries of the ring oldest first (the order ptg_finished_episodes hands out), at most cap - count_dev[0]
+ * of them; what does not fit, and what the ring had already overwritten, is counted in count_dev[1]; the ring is empty
+ * afterwards either way.  Must be ordered (same stream, or events) behind the launches whose episodes it collects.
+ * PTG_E_INVALID (nothing enqueued): count_dev NULL, cap < 1, or all three arrays NULL.  The host query's bookkeeping is not
+ * touched: a ptg_finished_episodes after a drain still synchronises and finds an empty ring.
+ * Replaces: reading Monitor's info["episode"] out of the step infos on the host (SB3 monitor.py, as the reference wraps its
+ * envs in src/rl_utils.py:448-453) for a collect loop that never leaves the device. */
+int ptg_finished_episodes_dev(ptg_env* env, double* ret_dev, int32_t* len_dev, int32_t* env_dev, int cap,
+                              uint32_t* count_dev, int append, void* stream);
+/* Monitor's statistic of a device list: stats_dev float64[6] = {count, sum r, sum r^2, sum len, min r, max r} over the first
+ * count_dev[0] entries (accumulate = 1: merged into what stats_dev holds; min / max of an empty list are +inf / -inf).
+ * len_dev may be NULL (sum len = 0).  Deterministic: a fixed reduction order, no floating-point atomics -- the same list gives
+ * the same bits on every call.  ep_rew_mean = stats[1] / stats[0]. */
+int ptg_episode_stats_dev(ptg_env* env, const double* ret_dev, const int32_t* len_dev, const uint32_t* count_dev,
+                          double* stats_dev, int accumulate, void* stream);
 
 /* ---- VecNormalize(env, norm_obs=False) reward normalisation on the device ------------------------------------------
  * Replaces: stable_baselines3.common.vec_env.VecNormalize.step_wait / _update_reward / normalize_reward and

@@ -2704,6 +2704,91 @@ int collect_error(ptg_env* h, hipStream_t st)
     return check_error_flags(h);
 }
 
+// ---- the finished-episode ring handed over on the device (ptg_finished_episodes_dev, ptg_episode_stats_dev) ----------------------
+// What a drain takes, from the ring's running counter and the caller's count: the same arithmetic as ptg_finished_episodes does on the
+// host.  Entries [total - have, total) of the running count are live; the oldest n of them go behind the c0 entries the caller holds.
+struct FinSpan { unsigned s0, n, c0, dropped; };
+__device__ __forceinline__ FinSpan fin_span(unsigned total, unsigned ring_cap, unsigned cap, const unsigned* count, int append)
+{
+    FinSpan s;
+    const unsigned have = total < ring_cap ? total : ring_cap;
+    const unsigned held = append ? count[0] : 0u;
+    s.c0 = held < cap ? held : cap;                          // a count above cap (not ours) is taken as a full list: nothing is written
+    const unsigned room = cap - s.c0;
+    s.n = have < room ? have : room;
+    s.s0 = (total - have) % ring_cap;
+    s.dropped = total - s.n;                                 // overwritten in the ring (total - have) + cut off by cap (have - n)
+    return s;
+}
+
+// Copy kernel of the drain: entry i of the span is ring slot (s0 + i) mod ring_cap, so consecutive lanes read and write consecutive
+// elements of each array (the span is at most two contiguous pieces of the ring).  Every block derives the span from the two counters
+// itself and nobody writes them here: k_fin_commit, the next kernel on the stream, does.
+__global__ void __launch_bounds__(256)
+k_fin_drain(const double* __restrict__ r_ret, const int* __restrict__ r_len, const int* __restrict__ r_env, const unsigned* __restrict__ r_count,
+            unsigned ring_cap, double* __restrict__ ret, int* __restrict__ len, int* __restrict__ env, unsigned cap,
+            const unsigned* __restrict__ count, int append, int env_offset)
+{
+    const FinSpan s = fin_span(*r_count, ring_cap, cap, count, append);
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < s.n; i += gridDim.x * 256u) {
+        unsigned slot = s.s0 + i;
+        if (slot >= ring_cap) slot -= ring_cap;
+        if (ret) ret[s.c0 + i] = r_ret[slot];
+        if (len) len[s.c0 + i] = r_len[slot];
+        if (env) env[s.c0 + i] = r_env[slot] + env_offset;
+    }
+}
+
+// One thread, behind the copy: the caller's counts, and the ring is empty again.
+__global__ void __launch_bounds__(64)
+k_fin_commit(unsigned* r_count, unsigned ring_cap, unsigned cap, unsigned* count, int append)
+{
+    if (threadIdx.x != 0) return;
+    const FinSpan s = fin_span(*r_count, ring_cap, cap, count, append);
+    const unsigned before = append ? count[1] : 0u;
+    count[0] = s.c0 + s.n;
+    count[1] = before + s.dropped;
+    *r_count = 0u;
+}
+
+// {count, sum r, sum r^2, sum len, min r, max r} of a list in ONE block: thread t takes entries t, t + 1024, ... in that order, the 64
+// lanes of a wave are folded by a fixed shuffle tree, the 16 waves by thread 0 in wave order -- the order depends on the list's length
+// alone, so the same list gives the same bits.  No atomics.
+__global__ void __launch_bounds__(1024)
+k_fin_stats(const double* __restrict__ ret, const int* __restrict__ len, const unsigned* __restrict__ count, double* __restrict__ stats,
+            int accumulate)
+{
+    __shared__ double part[16][5];
+    const unsigned n = count[0];
+    double s = 0.0, s2 = 0.0, sl = 0.0, mn = INFINITY, mx = -INFINITY;
+#pragma unroll 4
+    for (unsigned i = threadIdx.x; i < n; i += 1024u) {
+        const double r = ret[i];
+        s += r; s2 += r * r;
+        if (len) sl += (double)len[i];
+        mn = r < mn ? r : mn; mx = r > mx ? r : mx;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_down(s, off); s2 += __shfl_down(s2, off); sl += __shfl_down(sl, off);
+        const double a = __shfl_down(mn, off), b = __shfl_down(mx, off);
+        mn = a < mn ? a : mn; mx = b > mx ? b : mx;
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { part[wave][0] = s; part[wave][1] = s2; part[wave][2] = sl; part[wave][3] = mn; part[wave][4] = mx; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 16; w++) {
+        s += part[w][0]; s2 += part[w][1]; sl += part[w][2];
+        mn = part[w][3] < mn ? part[w][3] : mn; mx = part[w][4] > mx ? part[w][4] : mx;
+    }
+    double c = (double)n;
+    if (accumulate) {
+        c += stats[0]; s += stats[1]; s2 += stats[2]; sl += stats[3];
+        mn = stats[4] < mn ? stats[4] : mn; mx = stats[5] > mx ? stats[5] : mx;
+    }
+    stats[0] = c; stats[1] = s; stats[2] = s2; stats[3] = sl; stats[4] = mn; stats[5] = mx;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3805,6 +3890,34 @@ int ptg_finished_dropped(ptg_env* h, uint64_t* dropped_total)
     if (!h || !dropped_total) return set_err(h, PTG_E_INVALID, "bad argument");
     *dropped_total = h->fin_dropped;
     return 0;
+}
+
+int ptg_finished_episodes_dev(ptg_env* h, double* ret_dev, int32_t* len_dev, int32_t* env_dev, int cap, uint32_t* count_dev, int append,
+                              void* stream)
+{
+    if (!h || !count_dev || cap < 1 || (!ret_dev && !len_dev && !env_dev)) return set_err(h, PTG_E_INVALID, "ptg_finished_episodes_dev: bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const DevParams& P = h->P;
+    hipStream_t st = as_stream(stream);
+    // two kernels, no host round trip (fin_maybe / fin_dropped stay the host query's): every block of the copy reads both counters, the
+    // one-thread kernel behind it writes them
+    const int blocks = std::min(grid_for(std::min(cap, P.fin_cap), 256), 1024);
+    hipLaunchKernelGGL(k_fin_drain, dim3((unsigned)blocks), dim3(256), 0, st, (const double*)P.fin_ret, (const int*)P.fin_len, (const int*)P.fin_env,
+                       (const unsigned*)P.fin_count, (unsigned)P.fin_cap, ret_dev, len_dev, env_dev, (unsigned)cap, (const unsigned*)count_dev,
+                       append ? 1 : 0, (int)P.env_offset);
+    int rc = launch_check(h, "k_fin_drain");
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_fin_commit, dim3(1), dim3(64), 0, st, (unsigned*)P.fin_count, (unsigned)P.fin_cap, (unsigned)cap, count_dev, append ? 1 : 0);
+    return launch_check(h, "k_fin_commit");
+}
+
+int ptg_episode_stats_dev(ptg_env* h, const double* ret_dev, const int32_t* len_dev, const uint32_t* count_dev, double* stats_dev,
+                          int accumulate, void* stream)
+{
+    if (!h || !ret_dev || !count_dev || !stats_dev) return set_err(h, PTG_E_INVALID, "ptg_episode_stats_dev: bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_fin_stats, dim3(1), dim3(1024), 0, as_stream(stream), ret_dev, len_dev, count_dev, stats_dev, accumulate ? 1 : 0);
+    return launch_check(h, "k_fin_stats");
 }
 
 int ptg_market_feature_series(ptg_env* h, int which, float* out_host, int cap, int* count)

@@ -6,6 +6,8 @@ coupling, the module-global `ep_index` (env/ptg_gym_env.py:9,487-493), has a clo
 vector step terminate together: env with GLOBAL index e takes eps_ind[N_total + e + m*N_total] at its m-th reset
 (`episode_plan`).  The one collective is an all-gather of the finished-episode (return, length) lists for the
 episodic-return statistic (SB3's rollout/ep_rew_mean) -- RCCL over xGMI on GPUs (backend "nccl"), gloo in CPU tests.
+Two routes: `all_gather_finished` takes the host lists of HipEngine.finished_episodes(); `all_gather_finished_dev` /
+`all_reduce_episode_stats` take the device block of HipEngine.finished_episodes_dev() and its statistic as they are.
 """
 import numpy as np
 
@@ -161,3 +163,130 @@ def all_merge_moments(moments, group=None):
     parts = [torch.empty_like(src) for _ in range(world)]
     dist.all_gather(parts, src, group=group)
     return merge_moments(torch.stack(parts)).to(moments.device).contiguous()
+
+
+# ---- the device route: a fixed-size block per rank, one collective (SURVEY.md 8e: "fixed-size N/G returns + lengths + a count") ----
+FIN_HEAD = 16        # bytes in front of the arrays: counts uint32[2] = (entries in the list, entries dropped), padded to 16
+
+
+def finished_block_nbytes(cap):
+    """[counts u32 x 2 | pad to 16 | returns f64 x cap | lengths i32 x cap | env_ids i32 x cap]"""
+    return FIN_HEAD + 16 * int(cap)
+
+
+class FinishedBlock:
+    """A finished-episode list as ONE contiguous uint8 tensor (`block`) and typed views of it: `counts` int32[2] (the library writes
+    them as uint32; a list never holds 2**31 entries), `returns` float64[cap], `lengths` int32[cap], `env_ids` int32[cap] (global env
+    indices).  Only the first counts[0] entries of the arrays mean anything.  The block is what travels in the collective."""
+
+    def __init__(self, block, cap):
+        import torch
+        cap = int(cap)
+        if block.dtype != torch.uint8 or block.dim() != 1 or block.numel() != finished_block_nbytes(cap) or not block.is_contiguous():
+            raise ValueError(f"a finished-episode block of cap {cap} is a contiguous uint8 tensor of {finished_block_nbytes(cap)} bytes")
+        self.block, self.cap = block, cap
+        self.counts = block[0:8].view(torch.int32)
+        self.returns = block[FIN_HEAD:FIN_HEAD + 8 * cap].view(torch.float64)
+        self.lengths = block[FIN_HEAD + 8 * cap:FIN_HEAD + 12 * cap].view(torch.int32)
+        self.env_ids = block[FIN_HEAD + 12 * cap:FIN_HEAD + 16 * cap].view(torch.int32)
+
+    @classmethod
+    def empty(cls, cap, device):
+        """an empty list (all bytes zero) on `device`"""
+        import torch
+        return cls(torch.zeros(finished_block_nbytes(cap), dtype=torch.uint8, device=device), cap)
+
+    def count(self):
+        """entries in the list, on the host (synchronises a device block)"""
+        return int(self.counts[0].item())
+
+    def lists(self):
+        """(returns, lengths, env_ids) trimmed to the count: views of the block (synchronises a device block for the count)"""
+        c = min(self.count(), self.cap)
+        return self.returns[:c], self.lengths[:c], self.env_ids[:c]
+
+
+def pack_finished_block(returns, lengths, env_ids, cap, device=None, dropped=0):
+    """The block HipEngine.finished_episodes_dev() fills, built from host lists (at most `cap` entries) -- for rehearsing the collective
+    without a GPU, or for handing host-collected episodes to the device route."""
+    import torch
+    cap = int(cap)
+    r = np.asarray(returns, dtype=np.float64).reshape(-1)
+    l = np.asarray(lengths, dtype=np.int32).reshape(-1)
+    e = np.asarray(env_ids, dtype=np.int32).reshape(-1)
+    if not (len(r) == len(l) == len(e)) or len(r) > cap:
+        raise ValueError(f"lists of {len(r)}, {len(l)}, {len(e)} entries do not make a block of cap {cap}")
+    c = len(r)
+    raw = np.zeros(finished_block_nbytes(cap), np.uint8)
+    raw[0:8].view(np.uint32)[:] = (c, int(dropped))
+    raw[FIN_HEAD:FIN_HEAD + 8 * cap].view(np.float64)[:c] = r
+    raw[FIN_HEAD + 8 * cap:FIN_HEAD + 12 * cap].view(np.int32)[:c] = l
+    raw[FIN_HEAD + 12 * cap:FIN_HEAD + 16 * cap].view(np.int32)[:c] = e
+    block = torch.from_numpy(raw)
+    if device is not None and torch.device(device).type != "cpu":
+        block = block.to(device)
+    return FinishedBlock(block, cap)
+
+
+def _gather_flat(src, group):
+    """src: contiguous 1-D tensor, the same size on every rank -> [world, numel] on src's device: ONE all_gather_into_tensor.  Under
+    "nccl" the tensor goes in as it is; under a CPU backend (gloo rehearsals) a device tensor goes through a host copy, as in
+    all_merge_moments."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    x = src
+    if x.is_cuda and dist.get_backend(group) != "nccl":
+        x = x.cpu()
+    out = torch.empty(world * x.numel(), dtype=x.dtype, device=x.device)
+    dist.all_gather_into_tensor(out, x, group=group)
+    return out.view(world, x.numel()).to(src.device)
+
+
+def all_gather_finished_dev(fin, group=None):
+    """All-gather the ranks' finished-episode blocks (FinishedBlock, the same cap on every rank): ONE collective of
+    16 + 16 * cap bytes per rank whatever the counts are -- a synchronised batch whose envs all finish on one step included.
+    Returns (returns_all, lengths_all, env_ids_all) in rank order, each rank's part trimmed to its count, as tensors on the block's
+    device.  The counts come to the host (one small copy) to trim; the lists stay where the block is.  With no initialised process
+    group this is the identity."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return fin.lists()
+    cap = fin.cap
+    allb = _gather_flat(fin.block, group)                              # [world, nbytes]
+    world = allb.shape[0]
+    counts = allb[:, 0:4].contiguous().view(torch.int32).reshape(world).cpu().tolist()
+    ret = allb[:, FIN_HEAD:FIN_HEAD + 8 * cap].contiguous().view(torch.float64)              # [world, cap]
+    ln = allb[:, FIN_HEAD + 8 * cap:FIN_HEAD + 12 * cap].contiguous().view(torch.int32)
+    ids = allb[:, FIN_HEAD + 12 * cap:FIN_HEAD + 16 * cap].contiguous().view(torch.int32)
+    keep = [min(max(int(c), 0), cap) for c in counts]
+    if all(c == cap for c in keep):                                     # every rank full: the gathered arrays are the lists
+        return ret.reshape(-1), ln.reshape(-1), ids.reshape(-1)
+    return (torch.cat([ret[k, :c] for k, c in enumerate(keep)]), torch.cat([ln[k, :c] for k, c in enumerate(keep)]),
+            torch.cat([ids[k, :c] for k, c in enumerate(keep)]))
+
+
+def merge_episode_stats(parts):
+    """[world, 6] of {count, sum r, sum r^2, sum len, min r, max r} (a CPU tensor) -> [6]: the sums added in rank order, min / max
+    folded in rank order -- every rank that holds the same parts computes the same bits."""
+    acc = parts[0].clone()
+    for p in parts[1:]:
+        acc[0:4] = acc[0:4] + p[0:4]
+        if p[4] < acc[4]:
+            acc[4] = p[4]
+        if p[5] > acc[5]:
+            acc[5] = p[5]
+    return acc
+
+
+def all_reduce_episode_stats(stats, group=None):
+    """The survey's other form of the collective: HipEngine.episode_stats_dev()'s float64[6] of this rank's list -> the statistic
+    over all ranks' lists.  ONE gather of the 6 values per rank and a merge in rank order (merge_episode_stats), rather than an
+    all-reduce(SUM) plus two for min / max: a single collective, and identical bits on every rank by construction instead of by the
+    backend's reduction order.  The 6 x world numbers are folded on the host.  Identity without a process group."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return stats
+    parts = _gather_flat(stats.contiguous().reshape(-1), group)
+    return merge_episode_stats(parts.cpu()).to(stats.device)

@@ -402,6 +402,42 @@ class HipEngine:
         n = cnt.value
         return r[:n].copy(), l[:n].copy(), ids[:n].copy()
 
+    def finished_episodes_dev(self, block=None, append=False):
+        """The device route out of the finished-episode ring: enqueue, on the current stream, the hand-over of the episodes finished
+        since the last drain (or host query) into a rl_ptg_amd.dist.FinishedBlock on this GPU -- no synchronisation, no host copy, so
+        it can be captured into a graph behind a replay-proof step().  block None: the engine's own block of cap n_envs, allocated
+        once and reused (the fixed N/G of SURVEY.md 8e); append: entries go behind the block's count instead of replacing the list.
+        Returns the block; its counts are valid once the stream has run (fin.count() synchronises).  finished_episodes() is the
+        host query of the same ring: an episode leaves through whichever is called first."""
+        from . import dist as ptg_dist
+        if block is None:
+            if self.__dict__.get("_fin_dev") is None:
+                self._fin_dev = ptg_dist.FinishedBlock.empty(self.n, self.device)
+            block = self._fin_dev
+        if block.block.device != self.device:
+            raise ValueError(f"the block lives on {block.block.device}, the engine on {self.device}")
+        with self._torch.cuda.device(self.device):
+            self._chk(self._L.ptg_finished_episodes_dev(self._h, C.c_void_p(block.returns.data_ptr()), C.c_void_p(block.lengths.data_ptr()),
+                                                        C.c_void_p(block.env_ids.data_ptr()), block.cap, C.c_void_p(block.counts.data_ptr()),
+                                                        1 if append else 0, self._stream()))
+        return block
+
+    def episode_stats_dev(self, fin, stats=None, accumulate=False):
+        """Enqueue Monitor's statistic of a device list: float64[6] = {count, sum r, sum r^2, sum len, min r, max r} of `fin` (a
+        FinishedBlock), written to `stats` (None: the engine's own tensor, which starts as the empty statistic) or, with accumulate,
+        merged into it.  Deterministic (fixed reduction order).  ep_rew_mean = stats[1] / stats[0]."""
+        torch = self._torch
+        if stats is None:
+            if self.__dict__.get("_fin_stats") is None:
+                self._fin_stats = torch.tensor([0.0, 0.0, 0.0, 0.0, float("inf"), float("-inf")], dtype=torch.float64, device=self.device)
+            stats = self._fin_stats
+        assert stats.dtype == torch.float64 and stats.numel() == 6 and stats.is_contiguous() and stats.device == self.device
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_episode_stats_dev(self._h, C.c_void_p(fin.returns.data_ptr()), C.c_void_p(fin.lengths.data_ptr()),
+                                                    C.c_void_p(fin.counts.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                                    1 if accumulate else 0, self._stream()))
+        return stats
+
     # ------------------------------------------------------------------ VecNormalize(norm_obs=False) on the device
     def vn_init(self, gamma=0.99, epsilon=1e-8, clip_reward=10.0):
         """Start reward normalisation as the reference wraps its envs (src/rl_utils.py:453, SB3 defaults)."""
