@@ -27,13 +27,14 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 8   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 9   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
                              * 6: + ptg_vn_clear_done (frozen reward normalisation clears the returns of finished envs on the device);
                              * 7: + ptg_debug_table_plan;
-                             * 8: + ptg_finished_episodes_dev, ptg_episode_stats_dev (the finished-episode list handed over on the device) */
+                             * 8: + ptg_finished_episodes_dev, ptg_episode_stats_dev (the finished-episode list handed over on the device);
+                             * 9: + ptg_gae (advantages and returns of a rollout on the device) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -347,6 +348,35 @@ int ptg_vn_clear_done(ptg_env* env, const uint8_t* done_dev, int n_steps, void* 
 /* running statistics {mean, var, count} and the per-env discounted returns (either pointer may be NULL) */
 int ptg_vn_get(ptg_env* env, double* stats3_host, double* returns_host);
 int ptg_vn_set(ptg_env* env, const double* stats3_host, const double* returns_host);
+
+/* ---- generalised advantage estimation of a rollout on the device ----------------------------------------------------
+ * Replaces: stable_baselines3.common.buffers.RolloutBuffer.compute_returns_and_advantage (SB3 2.0.0a13), which the
+ * reference's A2C and PPO run after every collect (gamma / gae_lambda / n_steps of config/config_agent.yaml) -- a Python loop
+ * backwards over the n_steps rows of the buffer -- over the [T][N] matrices a rollout leaves on the device:
+ *   rew_dev  [T][N]  rewards (as ptg_rollout or ptg_vn_apply wrote them)
+ *   val_dev  [T][N]  V of the observation the action of step t was chosen from
+ *   done_dev [T][N]  uint8, ptg_rollout's convention: done[t][e] != 0 = env e's episode ended ON step t.  SB3's
+ *                    episode_starts[t + 1] is done[t] and its final `dones` argument is done[T - 1], so the non-terminal
+ *                    factor of step t is 1 - done[t] for every t, the last one included
+ *   last_val_dev [N] V of the observation after step T - 1
+ *   adv_dev  [T][N]  advantages;  ret_dev [T][N] (nullable) returns = advantages + values
+ * dtype (PTG_OUT_F32 | PTG_OUT_F64) is the element type of all five float arrays, whatever the handle's out_dtype is (a
+ * critic is float32 on a float64 engine too).  Arithmetic: SB3's, in that type, in SB3's operand order, every operation
+ * rounded once (no fused multiply-add), backwards over t with last = 0 before t = T - 1:
+ *   nnt = 1 - done[t];   nv = t == T - 1 ? last_val : val[t + 1];   g = (dtype)gamma;   gl = (dtype)(gamma * gae_lambda)
+ *   delta = (rew[t] + (g * nv) * nnt) - val[t];   last = delta + ((gl * nnt) * last);   adv[t] = last;   ret[t] = last + val[t]
+ * -- bit for bit what NumPy computes on arrays of that type.  nnt multiplies, it does not select: a NaN or Inf next value at a
+ * finished step poisons that step's result as it does in NumPy.
+ * Aliasing: adv_dev may be rew_dev and ret_dev may be val_dev (a lane reads its column's element before it writes it);
+ * no other overlap between inputs and outputs.
+ * The reference never truncates an episode (env/ptg_gym_env.py:478-481: truncated is always False), so there is no
+ * time-limit bootstrap to add to the rewards and none is needed.
+ * Enqueues one kernel on `stream`: no host synchronisation, no allocation, so it may be captured into a hipGraph.  Reads
+ * nothing of the handle but its n_envs and device and writes nothing of it but, on a refusal, the ptg_last_error text:
+ * env state, the finished-episode ring and the ptg_vn_* statistics are untouched.  PTG_E_INVALID (nothing enqueued): NULL handle, NULL rew / val / done / last_val / adv,
+ * n_steps < 1, a dtype other than the two, a non-finite gamma or gae_lambda. */
+int ptg_gae(ptg_env* env, const void* rew_dev, const void* val_dev, const uint8_t* done_dev, const void* last_val_dev,
+            int n_steps, int dtype, double gamma, double gae_lambda, void* adv_dev, void* ret_dev, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

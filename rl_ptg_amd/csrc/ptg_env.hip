@@ -12,6 +12,7 @@
 //   k_step_hot / k_rollout_pc   the float32 hot path of the same step (one launch per step / T fused steps).
 //   k_fill_noise      the normal(0, noise) draws of :585/:599/:621 as a counter-based device RNG (noise_draw).
 //   k_vn_*            VecNormalize(norm_obs=False) reward normalisation over the [T][N] rewards.
+//   k_gae             SB3's RolloutBuffer.compute_returns_and_advantage (GAE) over the [T][N] rewards, values and done flags.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "../../include/ptg_env.h"
 
@@ -2040,6 +2041,57 @@ k_vn_clear_done(const uint8_t* __restrict__ done, int N, int T, double* __restri
     if (any) returns[e] = 0.0;
 }
 
+// ================================================================================== generalised advantage estimation
+// stable-baselines3 2.0.0a13, common/buffers.py RolloutBuffer.compute_returns_and_advantage, as the reference's A2C and PPO run it
+// after every collect (config/config_agent.yaml: gamma / gae_lambda / n_steps).  With done[t] = episode_starts[t + 1] (and the
+// method's `dones` argument = done[T - 1]) the loop over `step` backwards is, in the arrays' own precision F:
+//   nnt = 1 - done[t];  nv = t == T - 1 ? last_val : val[t + 1]
+//   delta = rew[t] + gamma * nv * nnt - val[t];  last = delta + gamma * gae_lambda * nnt * last;  adv[t] = last;  ret[t] = last + val[t]
+// evaluated left to right as Python does: (g * nv) * nnt and (gl * nnt) * last, g = F(gamma), gl = F(gamma * gae_lambda), every
+// operation rounded once (no contraction into an FMA: bit equality with NumPy depends on it).  nnt multiplies, it does not
+// select: a NaN / Inf next value at a finished step poisons the result as it does in NumPy.
+// The same shape as k_vn_moments' recurrence: one lane per env, serial in t, every load and store coalesced over the envs, the
+// loads of a batch of steps issued ahead of the dependent arithmetic.  The next value is carried in a register, and a batch's
+// loads are all issued before its first store, so a lane reads every element of its column before it writes it: adv may be
+// rew's buffer and ret may be val's (hence no __restrict__ on those four).
+__device__ __forceinline__ float rn_mul(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float rn_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float rn_sub(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ double rn_mul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double rn_add(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double rn_sub(double a, double b) { return __dsub_rn(a, b); }
+
+template <typename F, int U>
+__global__ void __launch_bounds__(64)
+k_gae(const F* rew, const F* val, const uint8_t* __restrict__ done, const F* __restrict__ last_val, int N, int T, F g, F gl,
+      F* adv, F* ret)
+{
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * 64 + threadIdx.x;            // one wave per workgroup: a mid-size batch spreads over the CUs
+    if (e >= N) return;
+    F nv = last_val[e], last = (F)0;
+    for (int tb = T - 1; tb >= 0; tb -= U) {                // steps tb, tb - 1, ... tb - U + 1
+        F r[U], v[U]; uint8_t d[U];
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            const size_t i = (size_t)max(tb - j, 0) * N + e;
+            r[j] = rew[i]; v[j] = val[i]; d[j] = done[i];
+        }
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            if (tb - j >= 0) {
+                const size_t i = (size_t)(tb - j) * N + e;
+                const F nnt = d[j] ? (F)0 : (F)1;           // 1 - done, exactly
+                const F delta = rn_sub(rn_add(r[j], rn_mul(rn_mul(g, nv), nnt)), v[j]);
+                last = rn_add(delta, rn_mul(rn_mul(gl, nnt), last));
+                adv[i] = last;
+                if (ret) ret[i] = rn_add(last, v[j]);
+                nv = v[j];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ================================================================================================= host side
@@ -3668,6 +3720,26 @@ int ptg_vn_set(ptg_env* h, const double* stats3_host, const double* returns_host
     if (stats3_host) HIP_TRY(h, hipMemcpy(h->vn_stats, stats3_host, sizeof(double) * 3, hipMemcpyHostToDevice));
     if (returns_host) HIP_TRY(h, hipMemcpy(h->vn_returns, returns_host, sizeof(double) * h->n, hipMemcpyHostToDevice));
     return 0;
+}
+
+// ---- RolloutBuffer.compute_returns_and_advantage on the device ------------------------------------------------------
+int ptg_gae(ptg_env* h, const void* rew_dev, const void* val_dev, const uint8_t* done_dev, const void* last_val_dev, int n_steps,
+            int dtype, double gamma, double gae_lambda, void* adv_dev, void* ret_dev, void* stream)
+{
+    if (!h || !rew_dev || !val_dev || !done_dev || !last_val_dev || !adv_dev || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_gae: bad argument");
+    if (dtype != PTG_OUT_F32 && dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_gae: bad dtype");
+    if (!std::isfinite(gamma) || !std::isfinite(gae_lambda)) return set_err(h, PTG_E_INVALID, "ptg_gae: gamma / gae_lambda must be finite");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const double gl = gamma * gae_lambda;                   // Python's float product, before it meets the array's dtype
+    const dim3 grid((unsigned)((h->n + 63) / 64)), block(64);
+    // 32 (float64: 16) steps of loads in flight per lane: 18 KiB per wave, 72 KiB per CU at the 4 waves per CU of 65 536 envs
+    if (dtype == PTG_OUT_F64)
+        hipLaunchKernelGGL((k_gae<double, 16>), grid, block, 0, as_stream(stream), (const double*)rew_dev, (const double*)val_dev, done_dev,
+                           (const double*)last_val_dev, h->n, n_steps, gamma, gl, (double*)adv_dev, (double*)ret_dev);
+    else
+        hipLaunchKernelGGL((k_gae<float, 32>), grid, block, 0, as_stream(stream), (const float*)rew_dev, (const float*)val_dev, done_dev,
+                           (const float*)last_val_dev, h->n, n_steps, (float)gamma, (float)gl, (float*)adv_dev, (float*)ret_dev);
+    return launch_check(h, "k_gae");
 }
 
 int ptg_profile(ptg_env* h, int enable)

@@ -480,6 +480,39 @@ class HipEngine:
         rt = None if returns is None else np.ascontiguousarray(returns, dtype=np.float64)
         self._chk(self._L.ptg_vn_set(self._h, None if st is None else _dp(st), None if rt is None else _dp(rt)))
 
+    # ------------------------------------------------------------------ RolloutBuffer.compute_returns_and_advantage on the device
+    def gae(self, rew, values, done, last_values, gamma, gae_lambda, adv=None, ret=None):
+        """Enqueue, on the current stream, the advantages and returns of a rollout in place of SB3's
+        RolloutBuffer.compute_returns_and_advantage (include/ptg_env.h: ptg_gae): rew, values [T, N] (or [N] for T = 1) and
+        last_values [N] of ONE float dtype (float32 or float64, whatever the engine's out_dtype), done [T, N] of a 1-byte dtype with
+        rollout()'s meaning (done[t] != 0: the episode ended on step t), values[t] = V of the observation step t's action was chosen
+        from, last_values = V of the observation after step T - 1.  Returns (adv, ret), allocated when not given; adv may be rew and
+        ret may be values.  No synchronisation; bit for bit what NumPy computes with SB3's lines on arrays of that dtype."""
+        torch = self._torch
+        one = rew.dim() == 1
+        r2, v2, d2 = (x.unsqueeze(0) if one and x.dim() == 1 else x for x in (rew, values, done))
+        T = r2.shape[0] if r2.dim() == 2 else -1
+        if r2.shape != (T, self.n) or v2.shape != (T, self.n) or d2.shape != (T, self.n) or last_values.shape != (self.n,):
+            raise ValueError(f"gae: expected rew / values / done [T, {self.n}] and last_values [{self.n}], got {tuple(rew.shape)}, "
+                             f"{tuple(values.shape)}, {tuple(done.shape)}, {tuple(last_values.shape)}")
+        if r2.dtype not in (torch.float32, torch.float64) or v2.dtype != r2.dtype or last_values.dtype != r2.dtype:
+            raise TypeError(f"gae: rew, values and last_values must share float32 or float64, got {r2.dtype}, {v2.dtype}, {last_values.dtype}")
+        if d2.element_size() != 1:
+            raise TypeError(f"gae: done must have a 1-byte dtype, got {d2.dtype}")
+        a2 = torch.empty_like(r2) if adv is None else (adv.unsqueeze(0) if one and adv.dim() == 1 else adv)
+        t2 = torch.empty_like(r2) if ret is None else (ret.unsqueeze(0) if one and ret.dim() == 1 else ret)
+        for name, x in (("adv", a2), ("ret", t2)):
+            if x.shape != (T, self.n) or x.dtype != r2.dtype:
+                raise ValueError(f"gae: {name} must be [{T}, {self.n}] of {r2.dtype}, got {tuple(x.shape)} of {x.dtype}")
+        for name, x in (("rew", r2), ("values", v2), ("done", d2), ("last_values", last_values), ("adv", a2), ("ret", t2)):
+            if not x.is_contiguous() or x.device != self.device:
+                raise ValueError(f"gae: {name} must be a contiguous tensor on {self.device}")
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_gae(self._h, C.c_void_p(r2.data_ptr()), C.c_void_p(v2.data_ptr()), C.c_void_p(d2.data_ptr()),
+                                      C.c_void_p(last_values.data_ptr()), T, _lib.OUT_F64 if r2.dtype == torch.float64 else _lib.OUT_F32,
+                                      float(gamma), float(gae_lambda), C.c_void_p(a2.data_ptr()), C.c_void_p(t2.data_ptr()), self._stream()))
+        return (a2[0], t2[0]) if one else (a2, t2)
+
     def market_feature_series(self):
         """The pre-normalised float32 feature series the kernels read, each [n_sets, length]: dict(featA, featB (hourly), gas_n, eua_n
         (daily)).  Columns 14 / 15 of a "split" observation row index the flattened arrays."""
