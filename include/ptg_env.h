@@ -27,14 +27,15 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 9   /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 10  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
                              * 6: + ptg_vn_clear_done (frozen reward normalisation clears the returns of finished envs on the device);
                              * 7: + ptg_debug_table_plan;
                              * 8: + ptg_finished_episodes_dev, ptg_episode_stats_dev (the finished-episode list handed over on the device);
-                             * 9: + ptg_gae (advantages and returns of a rollout on the device) */
+                             * 9: + ptg_gae (advantages and returns of a rollout on the device);
+                             * 10: + ptg_minibatch, PTG_E_INDEX (shuffled minibatches gathered from the rollout buffers on the device) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -45,7 +46,8 @@ enum {
     PTG_E_INVALID = -1,        /* bad argument / call order */
     PTG_E_HIP = -2,            /* a HIP runtime call failed (no device, out of memory, ...) */
     PTG_E_ACTION = -3,         /* a discrete action outside [-5, 4] reached a kernel (reference: IndexError, :347) */
-    PTG_E_RANGE = -4           /* a price index left the series (reference: IndexError, :446-447) */
+    PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
+    PTG_E_INDEX = -5           /* ptg_minibatch met a sample index outside [0, n_steps * n_envs) (NumPy: IndexError) */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -277,7 +279,7 @@ int ptg_profile_read(ptg_env* env, double* us_host, int cap, int* count);
  * = its helper's duration or 0, span_us_host (nullable) = the length of the UNION of the two intervals, first start to last end --
  * the figure bench.py's roofline uses. */
 int ptg_profile_read_ex(ptg_env* env, double* us_host, double* helper_us_host, double* span_us_host, int cap, int* count);
-/* hipStreamSynchronize(stream) + report an error a kernel flagged (PTG_E_ACTION / PTG_E_RANGE). */
+/* hipStreamSynchronize(stream) + report an error a kernel flagged (PTG_E_ACTION / PTG_E_RANGE / PTG_E_INDEX). */
 int ptg_sync(ptg_env* env, void* stream);
 
 /* ---- state access (parity tests, checkpointing) -------------------------------------------------------- */
@@ -377,6 +379,41 @@ int ptg_vn_set(ptg_env* env, const double* stats3_host, const double* returns_ho
  * n_steps < 1, a dtype other than the two, a non-finite gamma or gae_lambda. */
 int ptg_gae(ptg_env* env, const void* rew_dev, const void* val_dev, const uint8_t* done_dev, const void* last_val_dev,
             int n_steps, int dtype, double gamma, double gae_lambda, void* adv_dev, void* ret_dev, void* stream);
+
+/* ---- one shuffled minibatch gathered from the buffers of a rollout on the device -----------------------------------
+ * Replaces: stable_baselines3.common.buffers.RolloutBuffer.get / _get_samples (SB3 2.0.0a13), through which the reference's
+ * PPO (config/config_agent.yaml: batch_size 203, n_steps 21 * batch_size) and A2C (get(None): one batch of everything) read
+ * every training batch: swap_and_flatten turns each [T][N][...] buffer into [N * T][...], a permutation of T * N is drawn,
+ * and each batch is the rows indices[start : start + batch_size] of every buffer.  Here nothing is transposed or copied
+ * beforehand: one launch gathers one batch straight from the [T][N] layout the rollout, ptg_vn_apply and ptg_gae leave.
+ *   idx_dev [B]        int32 (idx_bytes 4) or int64 (idx_bytes 8) sample indices in swap_and_flatten's order:
+ *                      i = e * n_steps + t, 0 <= i < n_steps * n_envs, names step t of env e.  The caller draws the
+ *                      permutation (any device RNG) and passes consecutive slices; repeats are legal (a gather).
+ *   obs_dev            (nullable, with obs_out_dev) the rollout's observations, addressed by strides in ELEMENTS: feature
+ *                      f of step t, env e is element t * obs_s_t + e * obs_s_n + f * obs_s_f; obs_dim features of
+ *                      obs_bytes (4 | 8) bytes.  [T][N][F] row-major, SB3_FLAT and SPLIT buffers: (N * F, F, 1);
+ *                      [T][F][N] feature-major with plane pitch p (ptg_set_feature_pitch; p = N without): (F * p, 1, p).
+ *   obs_out_dev        [B][obs_dim] row-major contiguous
+ *   cols_host [n_cols] device pointers of up to 8 contiguous [T][N] arrays of col_bytes_host[c] (1 | 2 | 4 | 8) bytes per
+ *                      element, copied as raw bytes: actions, values, log-probs, advantages, returns, done flags ...
+ *   cols_out_host      device pointers of their outputs, [B] contiguous each
+ * The three host arrays are read during the call; the kernel receives the pointers by value, so a captured call
+ * holds no host memory.  Output row b is the source row (t, e) = (idx[b] % n_steps, idx[b] / n_steps), byte for byte
+ * (no arithmetic touches the payload: NaN payloads, signed zeros and subnormals arrive as they are).
+ * An index outside [0, n_steps * n_envs) is rejected before any address is formed from it: its output row and
+ * column entries are left untouched, the other rows are gathered as usual, and the next ptg_sync (or any call that reports
+ * kernel-flagged errors) returns PTG_E_INDEX once.  Outputs must not overlap inputs or each other: this is not checked.
+ * Enqueues one kernel on `stream`: no host synchronisation, no allocation, so it may be captured into a hipGraph
+ * and replayed with other contents in idx_dev.  Reads nothing of the handle but its n_envs and device: env state, the
+ * finished-episode ring and the ptg_vn_* statistics are untouched.  Observations are optional (columns only is valid), and
+ * so are columns.  PTG_E_INVALID (nothing enqueued): NULL handle, NULL idx_dev, idx_bytes other than 4 | 8, batch < 1,
+ * n_steps < 1, obs_dev without obs_out_dev or the reverse, obs_dim < 1, obs_bytes other than 4 | 8 or a negative stride
+ * with observations, n_cols outside [0, 8], a NULL column or column output (or NULL arrays with n_cols > 0), a column
+ * element size other than 1 | 2 | 4 | 8, neither observations nor a column. */
+#define PTG_MB_MAX_COLS 8
+int ptg_minibatch(ptg_env* env, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps,
+                  const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev,
+                  int n_cols, const void* const* cols_host, const int* col_bytes_host, void* const* cols_out_host, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -13,6 +13,7 @@
 //   k_fill_noise      the normal(0, noise) draws of :585/:599/:621 as a counter-based device RNG (noise_draw).
 //   k_vn_*            VecNormalize(norm_obs=False) reward normalisation over the [T][N] rewards.
 //   k_gae             SB3's RolloutBuffer.compute_returns_and_advantage (GAE) over the [T][N] rewards, values and done flags.
+//   k_minibatch       SB3's RolloutBuffer.get / _get_samples: one shuffled minibatch gathered from the [T][N] buffers of a rollout.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "../../include/ptg_env.h"
 
@@ -110,8 +111,8 @@ struct DevParams {
     double* fin_ret; int* fin_len; int* fin_env; int* fin_count; int fin_cap;
     const int* cmap; int q_stat;          // SB3_FLAT layout: canonical column -> flat column; canonical index of METH_STATUS (else cmap = null)
     int split;                            // SPLIT layout (16 columns: status one-hot, 8 env features, hour / day series index; q_stat set too)
-    int* err;                             // [4] in pinned HOST memory: {invalid action seen, price index out of range, hot kernel on the
-                                          // terminating step, replay on a de-synchronised batch} (check_error_flags); kernels store 1 (plain
+    int* err;                             // [5] in pinned HOST memory: {invalid action seen, price index out of range, hot kernel on the
+                                          // terminating step, replay on a de-synchronised batch, minibatch index out of range} (check_error_flags); kernels store 1 (plain
                                           // stores of a constant need no atomic), the host reads it after a stream synchronise -- no copy
     int* term_flag;                       // device word: "the hot step kernel of this (captured) step found the batch on the terminating step
                                           // and skipped it" -- written by k_step_hot, read by the k_step enqueued behind it
@@ -2092,6 +2093,92 @@ k_gae(const F* rew, const F* val, const uint8_t* __restrict__ done, const F* __r
     }
 }
 
+// ================================================================================== shuffled minibatches of a rollout
+// stable-baselines3 2.0.0a13, common/buffers.py RolloutBuffer.get / _get_samples: swap_and_flatten every [T][N][...] buffer to
+// [N * T][...] (flat index i = e * T + t), draw a permutation, yield the rows indices[start : start + batch_size] of every buffer.
+// k_minibatch gathers ONE such batch straight from the [T][N] layout: output row b = source row (idx[b] % T, idx[b] / T), the
+// observations through strides (row-major [T][N][F] and feature-major [T][F][pitch] alike), up to PTG_MB_MAX_COLS [T][N] columns
+// of 1 / 2 / 4 / 8-byte elements as raw bytes.  A byte copy: no arithmetic touches the payload.
+// One wave owns MB_ROWS consecutive output rows.  Lane l < MB_ROWS loads idx[b0 + l], checks it, does the row's ONE division by T
+// and keeps the source row's byte offset; it also copies the row's column entries (consecutive lanes, consecutive output elements).
+// Then all 64 lanes run over the consecutive units (16-byte pieces when row length and every row base allow it, else elements) of
+// the wave's MB_ROWS x F output block -- every store instruction is one contiguous segment, every load a run of whole rows -- and
+// fetch each unit's row offset from the owning lane (two ds_bpermute, no LDS allocation).  (row, unit-in-row) advance by the
+// wave-uniform (64 / P, 64 % P) per step, so there is no division per unit.  MB_U units per lane are loaded before the first is
+// stored.  An index outside [0, T * N) never becomes an address: its row is skipped and err[4] is set (PTG_E_INDEX).
+constexpr int MB_ROWS = 16;              // rows per wave: a 203-row PPO batch spreads over 13 waves, 65 536 rows over 16 waves per CU
+constexpr int MB_WAVES = 4;              // waves per workgroup
+constexpr int MB_U = 4;                  // units in flight per lane
+constexpr unsigned MB_BAD = 0xFFFFFFFFu; // high word of the row offset of a rejected index (a real offset stays far below 2^63)
+
+struct MbCols {                          // by value in the launch: a captured call holds no host memory
+    const void* src[PTG_MB_MAX_COLS];
+    void* dst[PTG_MB_MAX_COLS];
+    int bytes[PTG_MB_MAX_COLS];
+    int n;
+};
+
+template <typename V>
+__device__ __forceinline__ void mb_copy_col(const void* src, void* dst, size_t from, size_t to)
+{
+    ((V*)dst)[to] = ((const V*)src)[from];
+}
+
+template <typename V, typename I>
+__global__ void __launch_bounds__(64 * MB_WAVES)
+k_minibatch(const I* __restrict__ idx, size_t B, unsigned T, size_t N, size_t TN, const char* __restrict__ obs, size_t s_t, size_t s_n,
+            size_t unit_stride, unsigned P, char* __restrict__ obs_out, MbCols cols, int* err)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t b0 = ((size_t)blockIdx.x * MB_WAVES + (threadIdx.x >> 6)) * MB_ROWS;
+    if (b0 >= B) return;                                     // wave-uniform
+    const unsigned rows = (unsigned)min((size_t)MB_ROWS, B - b0);
+    size_t off = (size_t)MB_BAD << 32;                       // byte offset of this lane's source row in the observation buffer
+    if (lane < rows) {
+        const long long v = (long long)idx[b0 + lane];
+        if ((unsigned long long)v < (unsigned long long)TN) {
+            size_t e, t;
+            if (TN <= 0xFFFFFFFFull) { const unsigned u = (unsigned)v; e = u / T; t = u - (unsigned)e * T; }   // the common case: 32-bit division
+            else { e = (size_t)v / T; t = (size_t)v - e * T; }
+            off = t * s_t + e * s_n;
+            const size_t from = t * N + e, to = b0 + lane;
+            for (int c = 0; c < cols.n; c++) {               // wave-uniform trip count and switch
+                switch (cols.bytes[c]) {
+                    case 1: mb_copy_col<uint8_t>(cols.src[c], cols.dst[c], from, to); break;
+                    case 2: mb_copy_col<uint16_t>(cols.src[c], cols.dst[c], from, to); break;
+                    case 4: mb_copy_col<uint32_t>(cols.src[c], cols.dst[c], from, to); break;
+                    default: mb_copy_col<uint64_t>(cols.src[c], cols.dst[c], from, to); break;
+                }
+            }
+        } else {
+            err[4] = 1;
+        }
+    }
+    if (!obs) return;
+    const unsigned off_lo = (unsigned)off, off_hi = (unsigned)(off >> 32);
+    const unsigned dr = 64u / P, dp = 64u - dr * P;          // one step of 64 units, in (rows, units of a row)
+    unsigned r = lane / P, p = lane - r * P;
+    V* const out = (V*)(obs_out + b0 * P * sizeof(V));       // the wave's block of rows x P units, unit q = r * P + p at out[q]
+    const unsigned units = rows * P;                         // host: P <= 2^20
+    for (unsigned q = lane; q - lane < units; q += 64u * MB_U) {            // wave-uniform trip count: every lane stays for the cross-lane reads
+        V v[MB_U];
+        bool ok[MB_U];
+#pragma unroll
+        for (int j = 0; j < MB_U; j++) {
+            const unsigned rr = min(r, (unsigned)MB_ROWS - 1);              // a lane in range for the cross-lane read
+            const unsigned lo = __shfl(off_lo, (int)rr), hi = __shfl(off_hi, (int)rr);
+            ok[j] = r < rows && hi != MB_BAD;
+            v[j] = V();
+            if (ok[j]) v[j] = *(const V*)(obs + (((size_t)hi << 32) | lo) + (size_t)p * unit_stride);
+            r += dr; p += dp;
+            if (p >= P) { p -= P; r++; }
+        }
+#pragma unroll
+        for (int j = 0; j < MB_U; j++)
+            if (ok[j]) out[q + 64u * j] = v[j];
+    }
+}
+
 }  // namespace
 
 // ================================================================================================= host side
@@ -2730,6 +2817,11 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
                        "ptg_steps_to_episode_end (ptg_set_replay_proof(env, 1) before capturing ptg_step lifts that; a fused ptg_rollout cannot cross "
                        "an episode end), or replays were not reported with ptg_note_replays");
     }
+    if (__atomic_load_n(&e[4], __ATOMIC_RELAXED)) {
+        __atomic_exchange_n(&e[4], 0, __ATOMIC_RELAXED);
+        return set_err(h, PTG_E_INDEX, "ptg_minibatch: a sample index outside [0, n_steps * n_envs) was passed (NumPy raises IndexError); "
+                       "its output row and column entries were left untouched");
+    }
     return 0;
 }
 
@@ -2754,6 +2846,18 @@ int collect_error(ptg_env* h, hipStream_t st)
     const int rc = wait_stream(h, st);
     if (rc) return rc;
     return check_error_flags(h);
+}
+
+// ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
+template <typename V>
+void launch_minibatch(hipStream_t st, const void* idx, int idx_bytes, size_t B, unsigned T, size_t N, const char* obs, size_t s_t,
+                             size_t s_n, size_t unit_stride, unsigned P, char* obs_out, const MbCols& cols, int* err)
+{
+    const dim3 grid((unsigned)((B + MB_ROWS * MB_WAVES - 1) / (MB_ROWS * MB_WAVES))), block(64 * MB_WAVES);
+    if (idx_bytes == 8)
+        hipLaunchKernelGGL((k_minibatch<V, long long>), grid, block, 0, st, (const long long*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+    else
+        hipLaunchKernelGGL((k_minibatch<V, int>), grid, block, 0, st, (const int*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
 }
 
 // ---- the finished-episode ring handed over on the device (ptg_finished_episodes_dev, ptg_episode_stats_dev) ----------------------
@@ -3032,9 +3136,9 @@ int ptg_create(const ptg_config* cfg, const ptg_tables* tables, const ptg_market
         return fail(rc);
     {   // the error words live in pinned host memory the kernels can write (see DevParams::err)
         void* dp = nullptr;
-        if (hipHostMalloc((void**)&h->err_host, 4 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
+        if (hipHostMalloc((void**)&h->err_host, 5 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
             hipHostGetDevicePointer(&dp, h->err_host, 0) != hipSuccess) { set_err(h, PTG_E_HIP, "hipHostMalloc of the error words failed"); return fail(PTG_E_HIP); }
-        h->err_host[0] = 0; h->err_host[1] = 0; h->err_host[2] = 0; h->err_host[3] = 0;
+        h->err_host[0] = 0; h->err_host[1] = 0; h->err_host[2] = 0; h->err_host[3] = 0; h->err_host[4] = 0;
         P.err = (int*)dp;
     }
     if ((rc = dev_alloc(h, &P.term_flag, 4))) return fail(rc);
@@ -3740,6 +3844,44 @@ int ptg_gae(ptg_env* h, const void* rew_dev, const void* val_dev, const uint8_t*
         hipLaunchKernelGGL((k_gae<float, 32>), grid, block, 0, as_stream(stream), (const float*)rew_dev, (const float*)val_dev, done_dev,
                            (const float*)last_val_dev, h->n, n_steps, (float)gamma, (float)gl, (float*)adv_dev, (float*)ret_dev);
     return launch_check(h, "k_gae");
+}
+
+// ---- RolloutBuffer.get's _get_samples on the device: one minibatch per launch ---------------------------------------
+int ptg_minibatch(ptg_env* h, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps, const void* obs_dev, int64_t obs_s_t,
+                  int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev, int n_cols, const void* const* cols_host,
+                  const int* col_bytes_host, void* const* cols_out_host, void* stream)
+{
+    if (!h || !idx_dev || batch < 1 || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_minibatch: bad argument");
+    if (idx_bytes != 4 && idx_bytes != 8) return set_err(h, PTG_E_INVALID, "ptg_minibatch: indices must be int32 or int64");
+    if (batch > (int64_t)0x7FFFFFFF * (MB_ROWS * MB_WAVES)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: batch too large for one launch");
+    if ((obs_dev == nullptr) != (obs_out_dev == nullptr)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: observations and their output go together");
+    if (obs_dev && (obs_dim < 1 || obs_dim > (1 << 20) || (obs_bytes != 4 && obs_bytes != 8) || obs_s_t < 0 || obs_s_n < 0 || obs_s_f < 0))
+        return set_err(h, PTG_E_INVALID, "ptg_minibatch: bad observation shape (obs_dim in [1, 2^20], 4- or 8-byte elements, strides >= 0)");
+    if (n_cols < 0 || n_cols > PTG_MB_MAX_COLS) return set_err(h, PTG_E_INVALID, "ptg_minibatch: at most %d columns", PTG_MB_MAX_COLS);
+    if (n_cols > 0 && (!cols_host || !col_bytes_host || !cols_out_host)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: null column arrays");
+    if (!obs_dev && n_cols == 0) return set_err(h, PTG_E_INVALID, "ptg_minibatch: nothing to gather");
+    MbCols cols{};
+    cols.n = n_cols;
+    for (int c = 0; c < n_cols; c++) {
+        const int s = col_bytes_host[c];
+        if (!cols_host[c] || !cols_out_host[c]) return set_err(h, PTG_E_INVALID, "ptg_minibatch: column %d or its output is null", c);
+        if (s != 1 && s != 2 && s != 4 && s != 8) return set_err(h, PTG_E_INVALID, "ptg_minibatch: column %d has %d-byte elements (1, 2, 4 or 8)", c, s);
+        cols.src[c] = cols_host[c]; cols.dst[c] = cols_out_host[c]; cols.bytes[c] = s;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t B = (size_t)batch, N = (size_t)h->n, sz = (size_t)obs_bytes;
+    const unsigned T = (unsigned)n_steps;
+    const char* obs = (const char*)obs_dev;
+    char* out = (char*)obs_out_dev;
+    const size_t row_bytes = obs_dev ? (size_t)obs_dim * sz : 0, s_t = (size_t)obs_s_t * sz, s_n = (size_t)obs_s_n * sz;
+    // 16-byte pieces when a row is contiguous, a whole number of them, and every row starts on one -- in the buffer and in the output
+    const bool wide = obs_dev && obs_s_f == 1 && row_bytes % 16 == 0 && s_t % 16 == 0 && s_n % 16 == 0 &&
+                      (uintptr_t)obs % 16 == 0 && (uintptr_t)out % 16 == 0;
+    if (wide) launch_minibatch<uint4>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, 16, (unsigned)(row_bytes / 16), out, cols, h->P.err);
+    else if (obs_bytes == 8) launch_minibatch<uint64_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 8, (unsigned)obs_dim, out, cols, h->P.err);
+    else launch_minibatch<uint32_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 4, obs_dev ? (unsigned)obs_dim : 1u, out, cols, h->P.err);
+    return launch_check(h, "k_minibatch");
 }
 
 int ptg_profile(ptg_env* h, int enable)

@@ -513,6 +513,85 @@ class HipEngine:
                                       float(gamma), float(gae_lambda), C.c_void_p(a2.data_ptr()), C.c_void_p(t2.data_ptr()), self._stream()))
         return (a2[0], t2[0]) if one else (a2, t2)
 
+    # ------------------------------------------------------------------ RolloutBuffer.get on the device
+    def minibatch(self, idx, obs=None, columns=(), obs_out=None, columns_out=None):
+        """Enqueue, on the current stream, the gather of ONE minibatch in place of SB3's RolloutBuffer._get_samples
+        (include/ptg_env.h: ptg_minibatch): idx [B] int32 / int64 sample indices in swap_and_flatten's order, i = env * T + step,
+        0 <= i < T * N (slices of a torch.randperm(T * N)); obs a rollout's observation buffer as alloc_obs(T) / rollout() make it
+        ([T, N, F], or [T, F, N] feature-major with the engine's pitch); columns up to 8 contiguous [T, N] tensors of 1-, 2-, 4- or
+        8-byte elements (actions, values, log-probs, advantages, returns, done flags ...).  Returns (obs_out [B, F] or None,
+        [column outputs [B]]), allocated when not given; row b is source row (idx[b] % T, idx[b] // T), byte for byte.  Outputs must
+        not overlap inputs (not checked).  No synchronisation; an index out of range leaves its row untouched and makes the next
+        sync() raise PtgError with code PTG_E_INDEX."""
+        torch = self._torch
+        columns = list(columns)
+        if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"minibatch: idx must be an int32 or int64 tensor, got {getattr(idx, 'dtype', type(idx))}")
+        if idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError(f"minibatch: idx must be 1-D and contiguous, got shape {tuple(idx.shape)}, strides {tuple(idx.stride())}")
+        if obs is None and not columns:
+            raise ValueError("minibatch: neither observations nor columns given")
+        if len(columns) > _lib.MB_MAX_COLS:
+            raise ValueError(f"minibatch: at most {_lib.MB_MAX_COLS} columns, got {len(columns)}")
+        B = idx.shape[0]
+        F = s_t = s_n = s_f = 0
+        if obs is not None:
+            if obs.dim() != 3 or obs.shape[1:] != ((self.obs_dim, self.n) if self.feature_major else (self.n, self.obs_dim)):
+                raise ValueError(f"minibatch: obs must be a [T, ...] buffer of alloc_obs(T), got shape {tuple(obs.shape)}")
+            if obs.element_size() not in (4, 8):
+                raise TypeError(f"minibatch: obs must have 4- or 8-byte elements, got {obs.dtype}")
+            self._check_obs(obs)
+            T, F = obs.shape[0], self.obs_dim
+            s_t, (s_n, s_f) = obs.stride(0), ((obs.stride(2), obs.stride(1)) if self.feature_major else (obs.stride(1), obs.stride(2)))
+        else:
+            T = columns[0].shape[0] if columns[0].dim() == 2 else -1
+        for c, x in enumerate(columns):
+            if x.shape != (T, self.n) or not x.is_contiguous():
+                raise ValueError(f"minibatch: column {c} must be a contiguous [{T}, {self.n}] tensor, got shape {tuple(x.shape)}, strides {tuple(x.stride())}")
+            if x.element_size() not in (1, 2, 4, 8):
+                raise TypeError(f"minibatch: column {c} must have 1-, 2-, 4- or 8-byte elements, got {x.dtype}")
+        if columns_out is not None and len(columns_out) != len(columns):
+            raise ValueError(f"minibatch: {len(columns)} columns but {len(columns_out)} column outputs")
+        if obs is None and obs_out is not None:
+            raise ValueError("minibatch: obs_out given without obs")
+        for name, x in [("idx", idx)] + ([("obs", obs)] if obs is not None else []) + [(f"column {c}", x) for c, x in enumerate(columns)]:
+            if x.device != self.device:
+                raise ValueError(f"minibatch: {name} lives on {x.device}, the engine on {self.device}")
+        with torch.cuda.device(self.device):
+            if obs is not None and obs_out is None:
+                obs_out = torch.empty((B, F), dtype=obs.dtype, device=self.device)
+            outs = [torch.empty((B,), dtype=x.dtype, device=self.device) for x in columns] if columns_out is None else list(columns_out)
+            if obs is not None and (obs_out.shape != (B, F) or obs_out.dtype != obs.dtype or not obs_out.is_contiguous() or obs_out.device != self.device):
+                raise ValueError(f"minibatch: obs_out must be a contiguous [{B}, {F}] tensor of {obs.dtype} on {self.device}, got "
+                                 f"{tuple(obs_out.shape)} of {obs_out.dtype} on {obs_out.device}")
+            for c, (x, o) in enumerate(zip(columns, outs)):
+                if o.shape != (B,) or o.dtype != x.dtype or not o.is_contiguous() or o.device != self.device:
+                    raise ValueError(f"minibatch: output of column {c} must be a contiguous [{B}] tensor of {x.dtype} on {self.device}, got "
+                                     f"{tuple(o.shape)} of {o.dtype} on {o.device}")
+            k = len(columns)
+            src = (C.c_void_p * max(k, 1))(*[x.data_ptr() for x in columns])
+            dst = (C.c_void_p * max(k, 1))(*[o.data_ptr() for o in outs])
+            size = (C.c_int32 * max(k, 1))(*[x.element_size() for x in columns])
+            self._chk(self._L.ptg_minibatch(self._h, C.c_void_p(idx.data_ptr()), idx.element_size(), B, T,
+                                            C.c_void_p(obs.data_ptr()) if obs is not None else None, s_t, s_n, s_f, F,
+                                            obs.element_size() if obs is not None else 0,
+                                            C.c_void_p(obs_out.data_ptr()) if obs is not None else None, k, src, size, dst, self._stream()))
+        return obs_out, outs
+
+    def minibatches(self, perm, batch_size, obs=None, columns=()):
+        """SB3's RolloutBuffer.get loop: yields minibatch(perm[start : start + batch_size], obs, columns) for start = 0, batch_size,
+        ... -- the last slice short when batch_size does not divide len(perm); batch_size None: one batch of all of perm (A2C).
+        perm: a permutation of T * N on the device, e.g. torch.randperm(T * N, device=...).  Every yield has fresh outputs."""
+        total = perm.shape[0]
+        if batch_size is None:
+            batch_size = total
+        if int(batch_size) < 1:
+            raise ValueError(f"minibatches: batch_size must be >= 1 or None, got {batch_size}")
+        start = 0
+        while start < total:
+            yield self.minibatch(perm[start:start + int(batch_size)], obs, columns)
+            start += int(batch_size)
+
     def market_feature_series(self):
         """The pre-normalised float32 feature series the kernels read, each [n_sets, length]: dict(featA, featB (hourly), gas_n, eua_n
         (daily)).  Columns 14 / 15 of a "split" observation row index the flattened arrays."""
