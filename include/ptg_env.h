@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 10  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 11  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
@@ -35,7 +35,8 @@ extern "C" {
                              * 7: + ptg_debug_table_plan;
                              * 8: + ptg_finished_episodes_dev, ptg_episode_stats_dev (the finished-episode list handed over on the device);
                              * 9: + ptg_gae (advantages and returns of a rollout on the device);
-                             * 10: + ptg_minibatch, PTG_E_INDEX (shuffled minibatches gathered from the rollout buffers on the device) */
+                             * 10: + ptg_minibatch, PTG_E_INDEX (shuffled minibatches gathered from the rollout buffers on the device);
+                             * 11: + ptg_replay, ptg_replay_add, ptg_replay_sample (the off-policy algorithms' replay buffer on the device) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -47,7 +48,7 @@ enum {
     PTG_E_HIP = -2,            /* a HIP runtime call failed (no device, out of memory, ...) */
     PTG_E_ACTION = -3,         /* a discrete action outside [-5, 4] reached a kernel (reference: IndexError, :347) */
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
-    PTG_E_INDEX = -5           /* ptg_minibatch met a sample index outside [0, n_steps * n_envs) (NumPy: IndexError) */
+    PTG_E_INDEX = -5           /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError) */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -414,6 +415,78 @@ int ptg_gae(ptg_env* env, const void* rew_dev, const void* val_dev, const uint8_
 int ptg_minibatch(ptg_env* env, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps,
                   const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev,
                   int n_cols, const void* const* cols_host, const int* col_bytes_host, void* const* cols_out_host, void* stream);
+
+/* ---- the replay buffer of the off-policy algorithms on the device ---------------------------------------------------
+ * Replaces: stable_baselines3.common.buffers.ReplayBuffer / DictReplayBuffer .add, .sample and ._get_samples (SB3 2.0.0a13,
+ * optimize_memory_usage off), from which the reference's DQN, TD3, SAC and TQC train (src/rl_config_agent.py:80-222; buffers of
+ * 1 M - 20 M transitions, train_freq 1 - 9): every env step is followed by an add and, shortly after, by a sample.  With these two
+ * calls collect -> store -> sample stays on the GPU and can be captured in a hipGraph behind ptg_step / ptg_rollout.
+ * Storage is the caller's (the library allocates nothing) and is described by a ptg_replay, read during the call:
+ *   capacity           S = max(buffer_size / n_envs, 1) rows of n_envs transitions (SB3's rule)
+ *   obs_ring, next_ring  [S][N][obs_dim] row-major contiguous, obs_bytes (4 | 8) per element: observations, next observations
+ *   col_ring[c]        n_cols <= PTG_MB_MAX_COLS contiguous [S][N] arrays of col_bytes[c] (1 | 2 | 4 | 8) bytes per element:
+ *                      actions, rewards, dones ...
+ *   cursor_dev         uint64[2] on the device, zero at creation: {vector steps added since creation, batches drawn on the device
+ *                      so far}.  It lives on the device so that captured launches can be replayed, as the hot kernels take the
+ *                      step count from device state.  pos = cursor[0] % S, full = cursor[0] >= S, size = min(cursor[0], S).
+ * Transition (slot s, env e) has the flat index i = s * N + e, 0 <= i < size * N: it is the row number in every ring.
+ *
+ * ptg_replay_add stores a window of T = n_steps vector steps as ptg_step (T = 1) or ptg_rollout left them.  With a = cursor[0]
+ * read on the device, step t goes to slot (a + t) % S (a window may wrap; n_steps <= S, so its slots are distinct):
+ *   obs_ring slot      t == 0 ? prev_obs[e] : obs[t - 1][e]; prev_obs_dev [N][obs_dim] is the observation the first action was
+ *                      chosen from, addressed with obs_s_n, obs_s_f
+ *   next_ring slot     obs[t][e], or final_obs[t][e] where done[t][e] != 0 and final_obs_dev (nullable; the strides of obs_dev) is
+ *                      given: OffPolicyAlgorithm._store_transition's infos[e]["terminal_observation"].  Without final_obs_dev a
+ *                      finished row keeps the post-reset observation; no SB3 off-policy target reads it there: every target
+ *                      multiplies the next value by (1 - done), and the reference never truncates (env/ptg_gym_env.py:478-481),
+ *                      so `timeouts` is identically 0 and is not stored.
+ *   col_ring[c] slot   cols_host[c][t][e] (contiguous [T][N] device arrays), byte for byte; column done_col (-1: none) is instead
+ *                      written as float32 0.0f / 1.0f from done_dev (uint8 [T][N]): SB3's dtype, so sampling is a pure copy.
+ *                      cols_host[done_col] is not read.
+ * Observations are addressed through element strides exactly as in ptg_minibatch: row-major / SB3_FLAT / SPLIT (N * F, F, 1),
+ * feature-major with pitch p (F * p, 1, p).  A trailing one-thread kernel does cursor[0] += T in stream order.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, ring, cursor, prev_obs_dev, obs_dev or column; capacity < 1;
+ * n_steps < 1 or > capacity; obs_dim outside [1, 2^20]; obs_bytes other than 4 | 8; a negative stride; n_cols other than the
+ * descriptor's or outside [0, 8]; a column element size other than 1 | 2 | 4 | 8; done_col outside [-1, n_cols) or naming a
+ * column that is not 4 bytes; done_dev NULL with final_obs_dev or a done column.
+ *
+ * ptg_replay_sample gathers `batch` transitions: [batch][obs_dim] rows of obs_ring into obs_out_dev and of next_ring into
+ * next_obs_out_dev, [batch] entries of column c into cols_out_host[c] (raw bytes), the indices used into idx_out_dev (int64
+ * [batch]).  Every output is nullable (cols_out_host itself too), but at least one is required.
+ *   idx_dev            int64 [batch] flat indices supplied by the caller (repeats are legal), or NULL: the kernel draws them.
+ *                      Row b of the c-th drawn batch (c = cursor[1]) takes, with h = lowbias32 (x ^= x >> 16; x *= 0x7feb352d;
+ *                      x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16) and lo / hi the 32-bit halves, all arithmetic modulo 2^32:
+ *                        k = h(lo(seed) ^ 0x9E3779B9); k = h(k + hi(seed)); k = h(k ^ lo(c)); k = h(k + hi(c));
+ *                        k = h(k ^ lo(b)); k = h(k + hi(b)); w0 = h(k ^ 0x85EBCA6B); w1 = h(k ^ 0xC2B2AE35);
+ *                        i = floor(((w0 << 32) | w1) * (size * N) / 2^64)        (__umul64hi; bias at most size * N / 2^64)
+ *                      and a trailing one-thread kernel does cursor[1] += 1, so a replayed graph draws a fresh batch.
+ *   norm_col           >= 0: the reward column; its output is what ptg_vn_apply(training = 0) writes for the same raw values with the
+ *                      statistics the handle holds when the kernel runs -- (OUT)clip((double)r / sqrt(var + epsilon)), the same
+ *                      expression, operand types and rounding: SB3's _normalize_reward (rewards are stored raw and normalised at
+ *                      sample time with the current variance).  Its element size must match the handle's out_dtype, ptg_vn_init must
+ *                      have been called and the column must have an output.  -1: raw bytes.
+ * size = min(cursor[0], S) is read on the device.  An explicit index outside [0, size * N) (a negative one included), or any draw
+ * from an empty buffer, never becomes an address: the row, its column entries and its idx_out entry are left untouched, the other
+ * rows are gathered as usual, and the next ptg_sync returns PTG_E_INDEX once.  Outputs must not overlap the rings or each other.
+ * Both calls enqueue kernels only (no host synchronisation, no allocation), so both may be captured into a hipGraph and replayed;
+ * neither touches env state, the finished-episode ring or the ptg_vn_* statistics.
+ * PTG_E_INVALID (nothing enqueued): the descriptor's faults above; batch < 1; no output at all; norm_col outside [-1, n_cols),
+ * before ptg_vn_init, on a column of another element size than out_dtype, or without an output. */
+typedef struct ptg_replay {
+    int64_t capacity;
+    int32_t obs_dim, obs_bytes;
+    void* obs_ring;
+    void* next_ring;
+    int32_t n_cols;
+    int32_t col_bytes[PTG_MB_MAX_COLS];
+    void* col_ring[PTG_MB_MAX_COLS];
+    uint64_t* cursor_dev;
+} ptg_replay;
+int ptg_replay_add(ptg_env* env, const ptg_replay* rb, const void* prev_obs_dev, const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n,
+                   int64_t obs_s_f, const void* final_obs_dev, const uint8_t* done_dev, int done_col, int n_cols, const void* const* cols_host,
+                   int64_t n_steps, void* stream);
+int ptg_replay_sample(ptg_env* env, const ptg_replay* rb, const int64_t* idx_dev, int64_t batch, uint64_t seed, void* obs_out_dev,
+                      void* next_obs_out_dev, void* const* cols_out_host, int norm_col, int64_t* idx_out_dev, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

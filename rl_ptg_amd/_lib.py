@@ -54,6 +54,12 @@ class PtgMarket(C.Structure):
                 ("rew_l_b", C.c_double), ("rew_u_b", C.c_double), ("r_0", C.c_double)]
 
 
+class PtgReplay(C.Structure):                               # ptg_replay: caller-owned replay buffer storage
+    _fields_ = [("capacity", C.c_int64), ("obs_dim", C.c_int32), ("obs_bytes", C.c_int32), ("obs_ring", C.c_void_p),
+                ("next_ring", C.c_void_p), ("n_cols", C.c_int32), ("col_bytes", C.c_int32 * MB_MAX_COLS),
+                ("col_ring", C.c_void_p * MB_MAX_COLS), ("cursor_dev", C.c_void_p)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -62,7 +68,7 @@ STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby
 EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_obs_dim", "ptg_last_error",
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
-           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch",
+           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -174,6 +180,8 @@ def lib():
     L.ptg_gae.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
     L.ptg_minibatch.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp,
                                 C.c_int, C.POINTER(vp), i32p, C.POINTER(vp), vp]
+    L.ptg_replay_add.argtypes = [vp, C.POINTER(PtgReplay), vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int64, vp]
+    L.ptg_replay_sample.argtypes = [vp, C.POINTER(PtgReplay), vp, C.c_int64, C.c_uint64, vp, vp, C.POINTER(vp), C.c_int, vp, vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

@@ -14,6 +14,7 @@
 //   k_vn_*            VecNormalize(norm_obs=False) reward normalisation over the [T][N] rewards.
 //   k_gae             SB3's RolloutBuffer.compute_returns_and_advantage (GAE) over the [T][N] rewards, values and done flags.
 //   k_minibatch       SB3's RolloutBuffer.get / _get_samples: one shuffled minibatch gathered from the [T][N] buffers of a rollout.
+//   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "../../include/ptg_env.h"
 
@@ -112,7 +113,7 @@ struct DevParams {
     const int* cmap; int q_stat;          // SB3_FLAT layout: canonical column -> flat column; canonical index of METH_STATUS (else cmap = null)
     int split;                            // SPLIT layout (16 columns: status one-hot, 8 env features, hour / day series index; q_stat set too)
     int* err;                             // [5] in pinned HOST memory: {invalid action seen, price index out of range, hot kernel on the
-                                          // terminating step, replay on a de-synchronised batch, minibatch index out of range} (check_error_flags); kernels store 1 (plain
+                                          // terminating step, replay on a de-synchronised batch, minibatch / replay sample index out of range} (check_error_flags); kernels store 1 (plain
                                           // stores of a constant need no atomic), the host reads it after a stream synchronise -- no copy
     int* term_flag;                       // device word: "the hot step kernel of this (captured) step found the batch on the terminating step
                                           // and skipped it" -- written by k_step_hot, read by the k_step enqueued behind it
@@ -2124,6 +2125,46 @@ __device__ __forceinline__ void mb_copy_col(const void* src, void* dst, size_t f
     ((V*)dst)[to] = ((const V*)src)[from];
 }
 
+__device__ __forceinline__ void mb_copy_entry(int bytes, const void* src, void* dst, size_t from, size_t to)
+{
+    switch (bytes) {
+        case 1: mb_copy_col<uint8_t>(src, dst, from, to); break;
+        case 2: mb_copy_col<uint16_t>(src, dst, from, to); break;
+        case 4: mb_copy_col<uint32_t>(src, dst, from, to); break;
+        default: mb_copy_col<uint64_t>(src, dst, from, to); break;
+    }
+}
+
+// The second half of a gathering wave (k_minibatch, k_rb_sample): lane l < rows holds `off`, the byte offset of its source row in
+// `src` (high word MB_BAD: a rejected row); all 64 lanes stream the rows x P units of the wave's contiguous output block `out`.
+template <typename V>
+__device__ __forceinline__ void mb_stream_rows(const char* __restrict__ src, size_t unit_stride, unsigned P, size_t off, unsigned rows,
+                                               unsigned lane, char* __restrict__ out_block)
+{
+    const unsigned off_lo = (unsigned)off, off_hi = (unsigned)(off >> 32);
+    const unsigned dr = 64u / P, dp = 64u - dr * P;          // one step of 64 units, in (rows, units of a row)
+    unsigned r = lane / P, p = lane - r * P;
+    V* const out = (V*)out_block;                            // the wave's block of rows x P units, unit q = r * P + p at out[q]
+    const unsigned units = rows * P;                         // host: P <= 2^20
+    for (unsigned q = lane; q - lane < units; q += 64u * MB_U) {            // wave-uniform trip count: every lane stays for the cross-lane reads
+        V v[MB_U];
+        bool ok[MB_U];
+#pragma unroll
+        for (int j = 0; j < MB_U; j++) {
+            const unsigned rr = min(r, (unsigned)MB_ROWS - 1);              // a lane in range for the cross-lane read
+            const unsigned lo = __shfl(off_lo, (int)rr), hi = __shfl(off_hi, (int)rr);
+            ok[j] = r < rows && hi != MB_BAD;
+            v[j] = V();
+            if (ok[j]) v[j] = *(const V*)(src + (((size_t)hi << 32) | lo) + (size_t)p * unit_stride);
+            r += dr; p += dp;
+            if (p >= P) { p -= P; r++; }
+        }
+#pragma unroll
+        for (int j = 0; j < MB_U; j++)
+            if (ok[j]) out[q + 64u * j] = v[j];
+    }
+}
+
 template <typename V, typename I>
 __global__ void __launch_bounds__(64 * MB_WAVES)
 k_minibatch(const I* __restrict__ idx, size_t B, unsigned T, size_t N, size_t TN, const char* __restrict__ obs, size_t s_t, size_t s_n,
@@ -2142,41 +2183,185 @@ k_minibatch(const I* __restrict__ idx, size_t B, unsigned T, size_t N, size_t TN
             else { e = (size_t)v / T; t = (size_t)v - e * T; }
             off = t * s_t + e * s_n;
             const size_t from = t * N + e, to = b0 + lane;
-            for (int c = 0; c < cols.n; c++) {               // wave-uniform trip count and switch
-                switch (cols.bytes[c]) {
-                    case 1: mb_copy_col<uint8_t>(cols.src[c], cols.dst[c], from, to); break;
-                    case 2: mb_copy_col<uint16_t>(cols.src[c], cols.dst[c], from, to); break;
-                    case 4: mb_copy_col<uint32_t>(cols.src[c], cols.dst[c], from, to); break;
-                    default: mb_copy_col<uint64_t>(cols.src[c], cols.dst[c], from, to); break;
+            for (int c = 0; c < cols.n; c++)                 // wave-uniform trip count and switch
+                mb_copy_entry(cols.bytes[c], cols.src[c], cols.dst[c], from, to);
+        } else {
+            err[4] = 1;
+        }
+    }
+    if (obs) mb_stream_rows<V>(obs, unit_stride, P, off, rows, lane, obs_out + b0 * P * sizeof(V));
+}
+
+// ================================================================================== replay buffer of the off-policy algorithms
+// stable-baselines3 2.0.0a13, common/buffers.py ReplayBuffer.add / sample / _get_samples (optimize_memory_usage off), which the
+// reference's DQN, TD3, SAC and TQC train from.  The caller owns the rings (ptg_replay, include/ptg_env.h): observations and next
+// observations [S][N][F] row-major, up to PTG_MB_MAX_COLS columns [S][N], and a device cursor {steps added, batches drawn}.
+// k_rb_add / k_rb_add_tr store a window of T vector steps at slots (cursor[0] + t) % S; k_rb_sample gathers a batch at flat indices
+// i = slot * N + e -- the caller's, or drawn on the device -- which in these rings ARE the row numbers: no division per row.
+// k_rb_bump advances a cursor word in stream order behind them, so a captured add / sample can be replayed.
+struct RbAdd {                           // by value in the launch
+    const char *prev, *obs, *fin;        // prev [N][F]; obs, fin (nullable) [T][N][F], all through the byte strides s_t, s_n (and s_f)
+    const uint8_t* done;                 // [T][N], nullable when neither fin nor a done column needs it
+    size_t s_t, s_n, s_f;                // bytes
+    char *ring0, *ring1;                 // observations, next observations
+    const unsigned long long* cursor;
+    size_t S, N;
+    unsigned T, F;
+    MbCols cols;                         // src: the window's [T][N] columns, dst: their rings [S][N]
+    int done_col;                        // the column written as float32 0 / 1 from `done`, or -1
+};
+
+__device__ __forceinline__ void rb_add_cols(const RbAdd& a, size_t from, size_t to)
+{
+    for (int c = 0; c < a.cols.n; c++) {
+        if (c == a.done_col) ((float*)a.cols.dst[c])[to] = a.done[from] ? 1.0f : 0.0f;
+        else mb_copy_entry(a.cols.bytes[c], a.cols.src[c], a.cols.dst[c], from, to);
+    }
+}
+
+// Rows that are contiguous in the source (s_f = one element): a slot [N][F] of either ring is then ONE contiguous run of N * P units
+// (V = a 16-byte piece when row length and every base allow it, else an element), unit u of the slot = (env u / P, unit u % P of
+// its row); consecutive lanes take consecutive units, so every store is a contiguous segment and every load a run of whole rows
+// (a single run for a [T][N][F] contiguous source).  A finished env's next observation comes from `fin`: a per-row select of the
+// source pointer.  The lane on a row's first unit also moves the row's column entries.  blockIdx.y strides over the steps.
+template <typename V>
+__global__ void __launch_bounds__(256)
+k_rb_add(RbAdd a, unsigned P, size_t NP)
+{
+    const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= NP) return;
+    size_t e; unsigned p;
+    if (NP <= 0xFFFFFFFFull) { const unsigned q = (unsigned)u / P; e = q; p = (unsigned)u - q * P; }
+    else { e = u / P; p = (unsigned)(u - e * P); }
+    const size_t a0 = (size_t)(a.cursor[0] % a.S);
+    const size_t in_row = e * a.s_n + (size_t)p * sizeof(V);
+    for (unsigned t = blockIdx.y; t < a.T; t += gridDim.y) {
+        size_t slot = a0 + t;                                // T <= S: at most one wrap
+        if (slot >= a.S) slot -= a.S;
+        const size_t from = (size_t)t * a.N + e, to = slot * a.N + e;
+        const char* s0 = (t == 0 ? a.prev : a.obs + (size_t)(t - 1) * a.s_t) + in_row;
+        const char* s1 = (a.fin && a.done[from] ? a.fin : a.obs) + (size_t)t * a.s_t + in_row;
+        const V v0 = *(const V*)s0, v1 = *(const V*)s1;
+        const size_t o = (slot * NP + u) * sizeof(V);
+        *(V*)(a.ring0 + o) = v0;
+        *(V*)(a.ring1 + o) = v1;
+        if (p == 0) rb_add_cols(a, from, to);
+    }
+}
+
+// Any other source (feature-major [T][F][pitch]: s_n = one element): a 64-env x 32-feature tile of each ring goes through LDS, read
+// with the lanes along the envs (coalesced in a feature plane), written with the lanes along the features (128- / 256-byte
+// segments of the ring's rows).  The 33-element pitch keeps both phases off one bank.
+constexpr int RB_TE = 64, RB_TF = 32;
+template <typename E>
+__global__ void __launch_bounds__(256)
+k_rb_add_tr(RbAdd a)
+{
+    __shared__ E tile[2][RB_TE][RB_TF + 1];
+    const unsigned tid = threadIdx.x;
+    const size_t e0 = (size_t)blockIdx.x * RB_TE;
+    const unsigned el = tid & 63u, fr = tid >> 6, fl = tid & 31u, er = tid >> 5;
+    const size_t a0 = (size_t)(a.cursor[0] % a.S);
+    for (unsigned t = blockIdx.y; t < a.T; t += gridDim.y) {
+        size_t slot = a0 + t;
+        if (slot >= a.S) slot -= a.S;
+        const size_t e = e0 + el;
+        const bool live = e < a.N;
+        const char *s0 = nullptr, *s1 = nullptr;
+        if (live) {
+            s0 = (t == 0 ? a.prev : a.obs + (size_t)(t - 1) * a.s_t) + e * a.s_n;
+            s1 = (a.fin && a.done[(size_t)t * a.N + e] ? a.fin : a.obs) + (size_t)t * a.s_t + e * a.s_n;
+        }
+        for (unsigned f0 = 0; f0 < a.F; f0 += RB_TF) {
+            if (live)
+                for (unsigned f = fr; f < RB_TF && f0 + f < a.F; f += 4) {
+                    tile[0][el][f] = *(const E*)(s0 + (size_t)(f0 + f) * a.s_f);
+                    tile[1][el][f] = *(const E*)(s1 + (size_t)(f0 + f) * a.s_f);
+                }
+            __syncthreads();
+            if (f0 + fl < a.F)
+                for (unsigned r = er; r < RB_TE && e0 + r < a.N; r += 8) {
+                    const size_t o = ((slot * a.N + e0 + r) * a.F + f0 + fl) * sizeof(E);
+                    *(E*)(a.ring0 + o) = tile[0][r][fl];
+                    *(E*)(a.ring1 + o) = tile[1][r][fl];
+                }
+            __syncthreads();
+        }
+        if (tid < 64 && live) rb_add_cols(a, (size_t)t * a.N + e, slot * a.N + e);
+    }
+}
+
+__global__ void k_rb_bump(unsigned long long* word, unsigned long long by) { *word += by; }
+
+// The two 32-bit words of row b of the c-th device-drawn batch under `seed` (include/ptg_env.h states the same lines; the tests
+// restate them in integer arithmetic): a chain of lowbias32 over the six 32-bit halves of (seed, c, b), then two finalisers.
+__device__ __forceinline__ unsigned long long rb_draw_word(unsigned long long seed, unsigned long long c, unsigned long long b)
+{
+    unsigned k = lowbias32((unsigned)seed ^ 0x9E3779B9u);
+    k = lowbias32(k + (unsigned)(seed >> 32));
+    k = lowbias32(k ^ (unsigned)c);
+    k = lowbias32(k + (unsigned)(c >> 32));
+    k = lowbias32(k ^ (unsigned)b);
+    k = lowbias32(k + (unsigned)(b >> 32));
+    const unsigned w0 = lowbias32(k ^ 0x85EBCA6Bu), w1 = lowbias32(k ^ 0xC2B2AE35u);
+    return ((unsigned long long)w0 << 32) | w1;
+}
+
+struct RbNorm {                          // SB3's _normalize_reward at sample time: column `col` through k_vn_norm's expression
+    int col;                             // -1: none
+    const double* stats;                 // the handle's {mean, var, count}
+    double eps, clip;
+};
+
+template <typename OUT>
+__device__ __forceinline__ void rb_norm_entry(const void* src, void* dst, size_t from, size_t to, double den, double clip)
+{
+    const double v = (double)((const OUT*)src)[from] / den;                 // k_vn_norm's lines
+    const double lo = v < -clip ? -clip : v;
+    ((OUT*)dst)[to] = (OUT)(lo > clip ? clip : lo);
+}
+
+// k_minibatch's scheme with two row sources sharing one offset: a wave owns MB_ROWS output rows; lane l < rows takes or draws
+// the index of row b0 + l, checks it against size * N (size = min(cursor[0], S), read here: the launch may be a replay) and moves
+// the row's column entries; then all 64 lanes stream the rows x F block of each ring.  An index out of range, or any draw from an
+// empty buffer, never becomes an address: the row is left as it was and err[4] is set (PTG_E_INDEX).
+template <typename V>
+__global__ void __launch_bounds__(64 * MB_WAVES)
+k_rb_sample(const long long* __restrict__ idx, size_t B, unsigned long long seed, const unsigned long long* __restrict__ cursor, size_t S,
+            size_t N, size_t row_bytes, unsigned P, const char* __restrict__ ring0, const char* __restrict__ ring1, char* __restrict__ out0,
+            char* __restrict__ out1, MbCols cols, RbNorm norm, long long* __restrict__ idx_out, int* err)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t b0 = ((size_t)blockIdx.x * MB_WAVES + (threadIdx.x >> 6)) * MB_ROWS;
+    if (b0 >= B) return;                                     // wave-uniform
+    const unsigned rows = (unsigned)min((size_t)MB_ROWS, B - b0);
+    size_t off = (size_t)MB_BAD << 32;
+    if (lane < rows) {
+        const unsigned long long added = cursor[0];
+        const unsigned long long total = (added < S ? added : S) * N;
+        const size_t to = b0 + lane;
+        unsigned long long i;
+        if (idx) i = (unsigned long long)idx[to];            // a negative index is a huge one
+        else i = total ? __umul64hi(rb_draw_word(seed, cursor[1], to), total) : ~0ull;
+        if (i < total) {
+            off = (size_t)i * row_bytes;
+            if (idx_out) idx_out[to] = (long long)i;
+            for (int c = 0; c < cols.n; c++) {
+                if (!cols.dst[c]) continue;
+                if (c == norm.col) {
+                    const double den = sqrt(norm.stats[1] + norm.eps);      // k_vn_scan's frozen denominator
+                    if (cols.bytes[c] == 8) rb_norm_entry<double>(cols.src[c], cols.dst[c], (size_t)i, to, den, norm.clip);
+                    else rb_norm_entry<float>(cols.src[c], cols.dst[c], (size_t)i, to, den, norm.clip);
+                } else {
+                    mb_copy_entry(cols.bytes[c], cols.src[c], cols.dst[c], (size_t)i, to);
                 }
             }
         } else {
             err[4] = 1;
         }
     }
-    if (!obs) return;
-    const unsigned off_lo = (unsigned)off, off_hi = (unsigned)(off >> 32);
-    const unsigned dr = 64u / P, dp = 64u - dr * P;          // one step of 64 units, in (rows, units of a row)
-    unsigned r = lane / P, p = lane - r * P;
-    V* const out = (V*)(obs_out + b0 * P * sizeof(V));       // the wave's block of rows x P units, unit q = r * P + p at out[q]
-    const unsigned units = rows * P;                         // host: P <= 2^20
-    for (unsigned q = lane; q - lane < units; q += 64u * MB_U) {            // wave-uniform trip count: every lane stays for the cross-lane reads
-        V v[MB_U];
-        bool ok[MB_U];
-#pragma unroll
-        for (int j = 0; j < MB_U; j++) {
-            const unsigned rr = min(r, (unsigned)MB_ROWS - 1);              // a lane in range for the cross-lane read
-            const unsigned lo = __shfl(off_lo, (int)rr), hi = __shfl(off_hi, (int)rr);
-            ok[j] = r < rows && hi != MB_BAD;
-            v[j] = V();
-            if (ok[j]) v[j] = *(const V*)(obs + (((size_t)hi << 32) | lo) + (size_t)p * unit_stride);
-            r += dr; p += dp;
-            if (p >= P) { p -= P; r++; }
-        }
-#pragma unroll
-        for (int j = 0; j < MB_U; j++)
-            if (ok[j]) out[q + 64u * j] = v[j];
-    }
+    if (out0) mb_stream_rows<V>(ring0, sizeof(V), P, off, rows, lane, out0 + b0 * row_bytes);
+    if (out1) mb_stream_rows<V>(ring1, sizeof(V), P, off, rows, lane, out1 + b0 * row_bytes);
 }
 
 }  // namespace
@@ -2819,7 +3004,8 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
     }
     if (__atomic_load_n(&e[4], __ATOMIC_RELAXED)) {
         __atomic_exchange_n(&e[4], 0, __ATOMIC_RELAXED);
-        return set_err(h, PTG_E_INDEX, "ptg_minibatch: a sample index outside [0, n_steps * n_envs) was passed (NumPy raises IndexError); "
+        return set_err(h, PTG_E_INDEX, "ptg_minibatch / ptg_replay_sample: a sample index outside [0, n_steps * n_envs) (of the replay buffer: "
+                       "[0, size * n_envs), or a draw from an empty buffer) was passed (NumPy raises IndexError); "
                        "its output row and column entries were left untouched");
     }
     return 0;
@@ -3882,6 +4068,110 @@ int ptg_minibatch(ptg_env* h, const void* idx_dev, int idx_bytes, int64_t batch,
     else if (obs_bytes == 8) launch_minibatch<uint64_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 8, (unsigned)obs_dim, out, cols, h->P.err);
     else launch_minibatch<uint32_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 4, obs_dev ? (unsigned)obs_dim : 1u, out, cols, h->P.err);
     return launch_check(h, "k_minibatch");
+}
+
+// ---- ReplayBuffer.add / sample on the device, over the caller's rings ------------------------------------------------
+static const char* replay_desc_error(const ptg_replay* rb)
+{
+    if (!rb) return "null descriptor";
+    if (!rb->obs_ring || !rb->next_ring || !rb->cursor_dev) return "null ring or cursor in the descriptor";
+    if (rb->capacity < 1) return "capacity < 1";
+    if (rb->obs_dim < 1 || rb->obs_dim > (1 << 20) || (rb->obs_bytes != 4 && rb->obs_bytes != 8)) return "obs_dim outside [1, 2^20] or obs_bytes other than 4 | 8";
+    if (rb->n_cols < 0 || rb->n_cols > PTG_MB_MAX_COLS) return "n_cols outside [0, 8]";
+    for (int c = 0; c < rb->n_cols; c++) {
+        const int s = rb->col_bytes[c];
+        if (!rb->col_ring[c]) return "null column ring";
+        if (s != 1 && s != 2 && s != 4 && s != 8) return "a column element size other than 1 | 2 | 4 | 8";
+    }
+    return nullptr;
+}
+
+int ptg_replay_add(ptg_env* h, const ptg_replay* rb, const void* prev_obs_dev, const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n,
+                   int64_t obs_s_f, const void* final_obs_dev, const uint8_t* done_dev, int done_col, int n_cols, const void* const* cols_host,
+                   int64_t n_steps, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (const char* why = replay_desc_error(rb)) return set_err(h, PTG_E_INVALID, "ptg_replay_add: %s", why);
+    if (!prev_obs_dev || !obs_dev) return set_err(h, PTG_E_INVALID, "ptg_replay_add: null observations");
+    if (n_steps < 1 || n_steps > rb->capacity || n_steps > 0x7FFFFFFF) return set_err(h, PTG_E_INVALID, "ptg_replay_add: n_steps outside [1, capacity]");
+    if (obs_s_t < 0 || obs_s_n < 0 || obs_s_f < 0) return set_err(h, PTG_E_INVALID, "ptg_replay_add: negative stride");
+    if (n_cols != rb->n_cols || (n_cols > 0 && !cols_host)) return set_err(h, PTG_E_INVALID, "ptg_replay_add: n_cols differs from the descriptor's, or null column array");
+    if (done_col < -1 || done_col >= n_cols) return set_err(h, PTG_E_INVALID, "ptg_replay_add: done_col outside [-1, n_cols)");
+    if (done_col >= 0 && rb->col_bytes[done_col] != 4) return set_err(h, PTG_E_INVALID, "ptg_replay_add: the done column must have 4-byte (float32) elements");
+    if ((done_col >= 0 || final_obs_dev) && !done_dev) return set_err(h, PTG_E_INVALID, "ptg_replay_add: done_dev is needed by final_obs_dev and by the done column");
+    RbAdd a{};
+    for (int c = 0; c < n_cols; c++) {
+        if (c != done_col && !cols_host[c]) return set_err(h, PTG_E_INVALID, "ptg_replay_add: column %d is null", c);
+        a.cols.src[c] = cols_host[c]; a.cols.dst[c] = rb->col_ring[c]; a.cols.bytes[c] = rb->col_bytes[c];
+    }
+    a.cols.n = n_cols;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t sz = (size_t)rb->obs_bytes, N = (size_t)h->n, row_bytes = (size_t)rb->obs_dim * sz;
+    a.prev = (const char*)prev_obs_dev; a.obs = (const char*)obs_dev; a.fin = (const char*)final_obs_dev; a.done = done_dev;
+    a.s_t = (size_t)obs_s_t * sz; a.s_n = (size_t)obs_s_n * sz; a.s_f = (size_t)obs_s_f * sz;
+    a.ring0 = (char*)rb->obs_ring; a.ring1 = (char*)rb->next_ring; a.cursor = (const unsigned long long*)rb->cursor_dev;
+    a.S = (size_t)rb->capacity; a.N = N; a.T = (unsigned)n_steps; a.F = (unsigned)rb->obs_dim; a.done_col = done_col;
+    const unsigned gy = (unsigned)std::min<int64_t>(n_steps, 65535);
+    if (obs_s_f == 1) {
+        // 16-byte pieces when a row is a whole number of them and every row starts on one, in the sources and in the rings
+        const auto al = [](const void* q) { return (uintptr_t)q % 16 == 0; };
+        const bool wide = row_bytes % 16 == 0 && a.s_t % 16 == 0 && a.s_n % 16 == 0 && al(a.prev) && al(a.obs) && al(a.fin) && al(a.ring0) && al(a.ring1);
+        const unsigned P = wide ? (unsigned)(row_bytes / 16) : (unsigned)rb->obs_dim;
+        const size_t NP = N * P;
+        const dim3 grid((unsigned)((NP + 255) / 256), gy), block(256);
+        if (wide) hipLaunchKernelGGL(k_rb_add<uint4>, grid, block, 0, st, a, P, NP);
+        else if (sz == 8) hipLaunchKernelGGL(k_rb_add<uint64_t>, grid, block, 0, st, a, P, NP);
+        else hipLaunchKernelGGL(k_rb_add<uint32_t>, grid, block, 0, st, a, P, NP);
+    } else {
+        const dim3 grid((unsigned)((N + RB_TE - 1) / RB_TE), gy), block(256);
+        if (sz == 8) hipLaunchKernelGGL(k_rb_add_tr<uint64_t>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_rb_add_tr<uint32_t>, grid, block, 0, st, a);
+    }
+    hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)rb->cursor_dev, (unsigned long long)n_steps);
+    return launch_check(h, "k_rb_add");
+}
+
+int ptg_replay_sample(ptg_env* h, const ptg_replay* rb, const int64_t* idx_dev, int64_t batch, uint64_t seed, void* obs_out_dev,
+                      void* next_obs_out_dev, void* const* cols_out_host, int norm_col, int64_t* idx_out_dev, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (const char* why = replay_desc_error(rb)) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: %s", why);
+    if (batch < 1 || batch > (int64_t)0x7FFFFFFF * (MB_ROWS * MB_WAVES)) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: batch < 1 or too large for one launch");
+    if (norm_col < -1 || norm_col >= rb->n_cols) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: norm_col outside [-1, n_cols)");
+    MbCols cols{};
+    cols.n = rb->n_cols;
+    bool any = obs_out_dev || next_obs_out_dev || idx_out_dev;
+    for (int c = 0; c < rb->n_cols; c++) {
+        cols.src[c] = rb->col_ring[c]; cols.dst[c] = cols_out_host ? cols_out_host[c] : nullptr; cols.bytes[c] = rb->col_bytes[c];
+        any = any || cols.dst[c];
+    }
+    if (!any) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: no output");
+    RbNorm norm{-1, nullptr, 0.0, 0.0};
+    if (norm_col >= 0) {
+        if (!h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: norm_col needs ptg_vn_init first");
+        if (rb->col_bytes[norm_col] != (h->cfg.out_dtype == PTG_OUT_F64 ? 8 : 4))
+            return set_err(h, PTG_E_INVALID, "ptg_replay_sample: the reward column's element size differs from the handle's out_dtype");
+        if (!cols.dst[norm_col]) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: norm_col names a column without an output");
+        norm = RbNorm{norm_col, h->vn_stats, h->vn_eps, h->vn_clip};
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t B = (size_t)batch, N = (size_t)h->n, row_bytes = (size_t)rb->obs_dim * (size_t)rb->obs_bytes;
+    const char *r0 = (const char*)rb->obs_ring, *r1 = (const char*)rb->next_ring;
+    char *o0 = (char*)obs_out_dev, *o1 = (char*)next_obs_out_dev;
+    const unsigned long long* cur = (const unsigned long long*)rb->cursor_dev;
+    const auto al = [](const void* q) { return (uintptr_t)q % 16 == 0; };
+    const bool wide = row_bytes % 16 == 0 && al(r0) && al(r1) && al(o0) && al(o1);
+    const dim3 grid((unsigned)((B + MB_ROWS * MB_WAVES - 1) / (MB_ROWS * MB_WAVES))), block(64 * MB_WAVES);
+    const long long* idx = (const long long*)idx_dev;
+    long long* idx_out = (long long*)idx_out_dev;
+    const size_t S = (size_t)rb->capacity;
+    if (wide) hipLaunchKernelGGL(k_rb_sample<uint4>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)(row_bytes / 16), r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
+    else if (rb->obs_bytes == 8) hipLaunchKernelGGL(k_rb_sample<uint64_t>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)rb->obs_dim, r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
+    else hipLaunchKernelGGL(k_rb_sample<uint32_t>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)rb->obs_dim, r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
+    if (!idx_dev) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)rb->cursor_dev + 1, 1ull);
+    return launch_check(h, "k_rb_sample");
 }
 
 int ptg_profile(ptg_env* h, int enable)

@@ -592,6 +592,151 @@ class HipEngine:
             yield self.minibatch(perm[start:start + int(batch_size)], obs, columns)
             start += int(batch_size)
 
+    # ------------------------------------------------------------------ ReplayBuffer.add / sample on the device
+    def _replay_desc(self, st, who):
+        """the ptg_replay descriptor of a storage object (rl_ptg_amd.replay.ReplayStorage: obs_ring, next_ring [S, N, F], col_rings
+        [S, N] each, cursor uint64-as-int64 [2]), its tensors checked"""
+        torch = self._torch
+        o, nx, cols, cur = st.obs_ring, st.next_ring, list(st.col_rings), st.cursor
+        if o.dim() != 3 or o.shape[1] != self.n or o.shape[0] < 1 or o.shape[2] < 1:
+            raise ValueError(f"{who}: obs_ring must be [S, {self.n}, F], got shape {tuple(o.shape)}")
+        if nx.shape != o.shape or nx.dtype != o.dtype:
+            raise ValueError(f"{who}: next_ring must match obs_ring, got {tuple(nx.shape)} of {nx.dtype}")
+        if o.element_size() not in (4, 8):
+            raise TypeError(f"{who}: the observation rings must have 4- or 8-byte elements, got {o.dtype}")
+        if len(cols) > _lib.MB_MAX_COLS:
+            raise ValueError(f"{who}: at most {_lib.MB_MAX_COLS} column rings, got {len(cols)}")
+        for c, x in enumerate(cols):
+            if x.shape != o.shape[:2]:
+                raise ValueError(f"{who}: column ring {c} must be [{o.shape[0]}, {self.n}], got shape {tuple(x.shape)}")
+            if x.element_size() not in (1, 2, 4, 8):
+                raise TypeError(f"{who}: column ring {c} must have 1-, 2-, 4- or 8-byte elements, got {x.dtype}")
+        if cur.dtype != torch.int64 or cur.shape != (2,):
+            raise TypeError(f"{who}: cursor must be an int64 tensor of 2 elements, got {cur.dtype} {tuple(cur.shape)}")
+        for name, x in [("obs_ring", o), ("next_ring", nx), ("cursor", cur)] + [(f"column ring {c}", x) for c, x in enumerate(cols)]:
+            if x.device != self.device or not x.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous tensor on {self.device}")
+        d = _lib.PtgReplay()
+        d.capacity, d.obs_dim, d.obs_bytes = o.shape[0], o.shape[2], o.element_size()
+        d.obs_ring, d.next_ring, d.n_cols, d.cursor_dev = o.data_ptr(), nx.data_ptr(), len(cols), cur.data_ptr()
+        for c, x in enumerate(cols):
+            d.col_bytes[c], d.col_ring[c] = x.element_size(), x.data_ptr()
+        return d
+
+    def replay_add(self, storage, prev_obs, obs, columns=(), done=None, final_obs=None, done_col=-1):
+        """Enqueue, on the current stream, SB3's ReplayBuffer.add for a window of T vector steps (include/ptg_env.h: ptg_replay_add).
+        obs is the ROW VIEW [T, N, F] of the window's observations -- rows(buffer) for a feature-major engine; any non-negative
+        strides -- prev_obs [N, F] the observation the first action was chosen from and final_obs (optional, [T, N, F]) the terminal
+        observations, both with obs's strides; columns one contiguous [T, N] tensor per column ring, of the ring's dtype (None at
+        done_col, which is written as float32 0 / 1 from done); done [T, N] of a 1-byte dtype.  Step t goes to slot
+        (cursor[0] + t) % S; the cursor advances on the device.  No synchronisation."""
+        torch = self._torch
+        d = self._replay_desc(storage, "replay_add")
+        columns = list(columns)
+        F, ring_dt = storage.obs_ring.shape[2], storage.obs_ring.dtype
+        if not torch.is_tensor(obs) or obs.dim() != 3 or obs.shape[1:] != (self.n, F):
+            raise ValueError(f"replay_add: obs must be a [T, {self.n}, {F}] row view, got shape {tuple(getattr(obs, 'shape', ()))}")
+        T = obs.shape[0]
+        if T < 1 or T > storage.obs_ring.shape[0]:
+            raise ValueError(f"replay_add: a window of {T} steps does not fit a buffer of {storage.obs_ring.shape[0]} rows (1 <= T <= S)")
+        if not torch.is_tensor(prev_obs) or prev_obs.shape != (self.n, F) or tuple(prev_obs.stride()) != tuple(obs.stride()[1:]):
+            raise ValueError(f"replay_add: prev_obs must be [{self.n}, {F}] with obs's strides {tuple(obs.stride()[1:])}, got "
+                             f"{tuple(getattr(prev_obs, 'shape', ()))}, strides {tuple(prev_obs.stride()) if torch.is_tensor(prev_obs) else None}")
+        if final_obs is not None and (final_obs.shape != obs.shape or tuple(final_obs.stride())[T == 1:] != tuple(obs.stride())[T == 1:]):
+            raise ValueError(f"replay_add: final_obs must have obs's shape and strides, got {tuple(final_obs.shape)}, {tuple(final_obs.stride())}")
+        views = [("obs", obs), ("prev_obs", prev_obs)] + ([("final_obs", final_obs)] if final_obs is not None else [])
+        for name, x in views:
+            if x.dtype != ring_dt:
+                raise TypeError(f"replay_add: {name} is {x.dtype}, the rings hold {ring_dt}")
+            if min(x.stride()) < 0:
+                raise ValueError(f"replay_add: {name} has a negative stride")
+        if len(columns) != len(storage.col_rings):
+            raise ValueError(f"replay_add: {len(storage.col_rings)} column rings but {len(columns)} columns")
+        if not -1 <= done_col < len(columns):
+            raise ValueError(f"replay_add: done_col {done_col} outside [-1, {len(columns)})")
+        if done_col >= 0 and storage.col_rings[done_col].dtype != torch.float32:
+            raise TypeError(f"replay_add: the done column ring must be float32, got {storage.col_rings[done_col].dtype}")
+        if (done_col >= 0 or final_obs is not None) and done is None:
+            raise ValueError("replay_add: final_obs and a done column need done")
+        flat = [(f"column {c}", x, storage.col_rings[c].dtype) for c, x in enumerate(columns) if c != done_col]
+        if done is not None:
+            if not torch.is_tensor(done) or done.element_size() != 1:
+                raise TypeError(f"replay_add: done must have a 1-byte dtype, got {getattr(done, 'dtype', type(done))}")
+            flat.append(("done", done, done.dtype))
+        for name, x, dt in flat:
+            if not torch.is_tensor(x) or x.shape != (T, self.n) or not x.is_contiguous():
+                raise ValueError(f"replay_add: {name} must be a contiguous [{T}, {self.n}] tensor, got {tuple(getattr(x, 'shape', ()))}")
+            if x.dtype != dt:
+                raise TypeError(f"replay_add: {name} is {x.dtype}, its ring holds {dt}")
+        for name, x in views + [(n_, x) for n_, x, _ in flat]:
+            if x.device != self.device:
+                raise ValueError(f"replay_add: {name} lives on {x.device}, the engine on {self.device}")
+        k = len(columns)
+        src = (C.c_void_p * max(k, 1))(*[None if c == done_col else x.data_ptr() for c, x in enumerate(columns)])
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_replay_add(self._h, C.byref(d), C.c_void_p(prev_obs.data_ptr()), C.c_void_p(obs.data_ptr()),
+                                             obs.stride(0), obs.stride(1), obs.stride(2),
+                                             C.c_void_p(final_obs.data_ptr()) if final_obs is not None else None,
+                                             C.c_void_p(done.data_ptr()) if done is not None else None, done_col, k, src, T, self._stream()))
+
+    def replay_sample(self, storage, batch_size=None, idx=None, seed=0, want_obs=True, want_next=True, want_cols=None, norm_col=-1,
+                      want_idx=False, out=None):
+        """Enqueue, on the current stream, SB3's ReplayBuffer.sample / _get_samples (include/ptg_env.h: ptg_replay_sample): a gather
+        at the flat indices idx (int64 [B], i = slot * N + env) or, with idx None, at batch_size indices drawn on the device from
+        (seed, cursor[1], row).  Returns (obs [B, F] | None, next_obs [B, F] | None, [column outputs [B] | None], idx_out [B] | None);
+        want_cols: a bool per column ring (None: all); norm_col: the reward column, normalised as vn_normalize(training=False)
+        would; out: the same 4-tuple of preallocated outputs (for a captured call).  No synchronisation; an index out of range, or a
+        draw from an empty buffer, leaves its row untouched and makes the next sync() raise PtgError with code PTG_E_INDEX."""
+        torch = self._torch
+        d = self._replay_desc(storage, "replay_sample")
+        k = len(storage.col_rings)
+        F = storage.obs_ring.shape[2]
+        if idx is not None:
+            if not torch.is_tensor(idx) or idx.dtype != torch.int64:
+                raise TypeError(f"replay_sample: idx must be an int64 tensor, got {getattr(idx, 'dtype', type(idx))}")
+            if idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
+                raise ValueError(f"replay_sample: idx must be 1-D and contiguous on {self.device}, got shape {tuple(idx.shape)} on {idx.device}")
+            if batch_size is not None and int(batch_size) != idx.shape[0]:
+                raise ValueError(f"replay_sample: batch_size {batch_size} but {idx.shape[0]} indices")
+            B = idx.shape[0]
+        else:
+            if batch_size is None:
+                raise ValueError("replay_sample: neither idx nor batch_size given")
+            B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"replay_sample: an empty batch ({B} rows)")
+        if not -1 <= norm_col < k:
+            raise ValueError(f"replay_sample: norm_col {norm_col} outside [-1, {k})")
+        want_cols = [True] * k if want_cols is None else [bool(w) for w in want_cols]
+        if len(want_cols) != k:
+            raise ValueError(f"replay_sample: {k} column rings but {len(want_cols)} entries in want_cols")
+        with torch.cuda.device(self.device):
+            if out is None:
+                mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+                out = (mk((B, F), storage.obs_ring.dtype) if want_obs else None, mk((B, F), storage.obs_ring.dtype) if want_next else None,
+                       [mk((B,), x.dtype) if w else None for x, w in zip(storage.col_rings, want_cols)], mk((B,), torch.int64) if want_idx else None)
+            o0, o1, outs, io = out
+            outs = list(outs)
+            if len(outs) != k:
+                raise ValueError(f"replay_sample: {k} column rings but {len(outs)} column outputs")
+            exp = [("obs output", o0, (B, F), storage.obs_ring.dtype), ("next_obs output", o1, (B, F), storage.obs_ring.dtype), ("idx output", io, (B,), torch.int64)]
+            exp += [(f"output of column {c}", o, (B,), x.dtype) for c, (o, x) in enumerate(zip(outs, storage.col_rings))]
+            for name, x, shape, dt in exp:
+                if x is not None and (not torch.is_tensor(x) or x.shape != shape or x.dtype != dt or not x.is_contiguous() or x.device != self.device):
+                    raise ValueError(f"replay_sample: {name} must be a contiguous {list(shape)} tensor of {dt} on {self.device}, got "
+                                     f"{tuple(getattr(x, 'shape', ()))} of {getattr(x, 'dtype', type(x))}")
+            if all(x is None for _, x, _, _ in exp):
+                raise ValueError("replay_sample: no output asked for")
+            if norm_col >= 0 and outs[norm_col] is None:
+                raise ValueError("replay_sample: norm_col names a column without an output")
+            if norm_col >= 0 and storage.col_rings[norm_col].dtype != self.out_dtype:
+                raise TypeError(f"replay_sample: the reward column is {storage.col_rings[norm_col].dtype}, the engine normalises {self.out_dtype}")
+            dst = (C.c_void_p * max(k, 1))(*[None if o is None else o.data_ptr() for o in outs])
+            ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
+            self._chk(self._L.ptg_replay_sample(self._h, C.byref(d), ptr(idx), B, int(seed) & (2 ** 64 - 1), ptr(o0), ptr(o1), dst,
+                                                norm_col, ptr(io), self._stream()))
+        return o0, o1, outs, io
+
     def market_feature_series(self):
         """The pre-normalised float32 feature series the kernels read, each [n_sets, length]: dict(featA, featB (hourly), gas_n, eua_n
         (daily)).  Columns 14 / 15 of a "split" observation row index the flattened arrays."""
