@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 11  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 12  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
@@ -36,7 +36,8 @@ extern "C" {
                              * 8: + ptg_finished_episodes_dev, ptg_episode_stats_dev (the finished-episode list handed over on the device);
                              * 9: + ptg_gae (advantages and returns of a rollout on the device);
                              * 10: + ptg_minibatch, PTG_E_INDEX (shuffled minibatches gathered from the rollout buffers on the device);
-                             * 11: + ptg_replay, ptg_replay_add, ptg_replay_sample (the off-policy algorithms' replay buffer on the device) */
+                             * 11: + ptg_replay, ptg_replay_add, ptg_replay_sample (the off-policy algorithms' replay buffer on the device);
+                             * 12: + ptg_head, ptg_act, PTG_E_NONFINITE (policy outputs to actions, log-probs and entropy in one launch) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -48,7 +49,8 @@ enum {
     PTG_E_HIP = -2,            /* a HIP runtime call failed (no device, out of memory, ...) */
     PTG_E_ACTION = -3,         /* a discrete action outside [-5, 4] reached a kernel (reference: IndexError, :347) */
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
-    PTG_E_INDEX = -5           /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError) */
+    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError) */
+    PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1] */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -280,7 +282,7 @@ int ptg_profile_read(ptg_env* env, double* us_host, int cap, int* count);
  * = its helper's duration or 0, span_us_host (nullable) = the length of the UNION of the two intervals, first start to last end --
  * the figure bench.py's roofline uses. */
 int ptg_profile_read_ex(ptg_env* env, double* us_host, double* helper_us_host, double* span_us_host, int cap, int* count);
-/* hipStreamSynchronize(stream) + report an error a kernel flagged (PTG_E_ACTION / PTG_E_RANGE / PTG_E_INDEX). */
+/* hipStreamSynchronize(stream) + report an error a kernel flagged (PTG_E_ACTION / PTG_E_RANGE / PTG_E_INDEX / PTG_E_NONFINITE). */
 int ptg_sync(ptg_env* env, void* stream);
 
 /* ---- state access (parity tests, checkpointing) -------------------------------------------------------- */
@@ -487,6 +489,80 @@ int ptg_replay_add(ptg_env* env, const ptg_replay* rb, const void* prev_obs_dev,
                    int64_t n_steps, void* stream);
 int ptg_replay_sample(ptg_env* env, const ptg_replay* rb, const int64_t* idx_dev, int64_t batch, uint64_t seed, void* obs_out_dev,
                       void* next_obs_out_dev, void* const* cols_out_host, int norm_col, int64_t* idx_out_dev, void* stream);
+
+/* ---- the action head: policy outputs to actions, log-probs and entropy in one launch --------------------------------
+ * Replaces what the reference's algorithms (src/rl_config_agent.py:80-222) run between the network's output and env.step while
+ * collecting (SB3 2.0.0a13 common/distributions.py, dqn/policies.py, common/off_policy_algorithm.py):
+ *   PTG_HEAD_CATEGORICAL  A2C / PPO, action_type "discrete": CategoricalDistribution.sample / log_prob / entropy of the logits
+ *   PTG_HEAD_EPS_GREEDY   DQN: a uniform random action with probability epsilon (_sample_action), else argmax of the Q-values
+ *   PTG_HEAD_GAUSSIAN     TD3 clip(mu + N(0, sigma_exp), -1, 1); SAC / TQC tanh(mu + sigma z) (PTG_HEAD_SQUASH); A2C / PPO with
+ *                         action_type "continuous": DiagGaussianDistribution, clipped to the Box for the env and stored unclipped
+ * -- six to ten element-wise launches in torch.  The env's Box is one-dimensional, so the Gaussian head has D = 1: one mean and one
+ * action per env.  Out of scope: the networks, evaluate_actions at training time (autograd), gSDE.
+ * The head is described by a ptg_head, read during the call:
+ *   kind          PTG_HEAD_CATEGORICAL | PTG_HEAD_EPS_GREEDY | PTG_HEAD_GAUSSIAN
+ *   flags         PTG_HEAD_DETERMINISTIC: the mode; nothing is drawn, counter_dev is neither read nor advanced (and may be NULL).
+ *                 PTG_HEAD_SQUASH (Gaussian only): tanh
+ *   in_dtype      PTG_OUT_F32 | PTG_OUT_F64: the element type of in_dev, of the Gaussian param_dev and of raw / logp / ent
+ *   in_dev        discrete kinds: [N][A] logits or Q-values, element (e, j) at e * in_s_n + j, in_s_n >= A = n_actions, 2 <= A <= 32
+ *                 (a stride above A reads a slice of a wider [N, A + 1] actor-critic output).  Gaussian: the means [N], element
+ *                 e at e * in_s_n, in_s_n >= 1 (n_actions is not read)
+ *   param_dev     on the device, so that a replayed graph sees an update.  EPS_GREEDY: epsilon, float64 [1] (not read and
+ *                 nullable when deterministic).  GAUSSIAN: log_std in in_dtype, element e at e * param_s_n with param_s_n 0 (one
+ *                 value: SB3's state-independent parameter, or log(sigma_exp) for TD3) or 1 (per env: SAC's actor).
+ *   clip_lo, clip_hi   Gaussian: bounds of the env action (host doubles)
+ *   seed, counter_dev  the draw: counter_dev is the caller's uint64 [1] on the device.  Row e of the c-th call (c = *counter_dev
+ *                 read on the device) takes the words (w0, w1) of ptg_replay_sample's chain above with the key
+ *                 (seed, c, global env offset + e) in place of (seed, c, b): a shard draws what its slice of one big batch would
+ *                 draw (ptg_set_global_env_offset).  A trailing one-thread kernel does *counter_dev += 1 in stream order, unless
+ *                 the call is deterministic: a replayed graph draws afresh.
+ *   act_dev       [N] of act_kind: PTG_ACT_I32 | PTG_ACT_I64 for the discrete kinds, PTG_ACT_F32 for Gaussian -- what ptg_step takes
+ *   raw_dev       [N] in_dtype, nullable, Gaussian only: the unclipped, unsquashed sample (what an on-policy buffer stores)
+ *   logp_dev, ent_dev  [N] in_dtype, nullable: log-probability of the action taken, entropy of the row's distribution
+ * Arithmetic: all of it in float64 whatever in_dtype is, every operation rounded once (no fused multiply-add), results rounded
+ * once on the store.  l_j = (double)in[e][j]; exp, log, sqrt, cos, tanh are the double-precision library functions.
+ *   categorical   m = max_j l_j;  e_j = exp(l_j - m);  s = e_0 + e_1 + ... in index order;  logp_j = (l_j - m) - log(s)
+ *                 entropy = -(t_0 + t_1 + ...), t_j = (e_j / s) * logp_j in index order, terms with e_j == 0 left out
+ *                 draw: u = ((w0 << 21) | (w1 >> 11)) * 2^-53;  action = the first j with u * s < e_0 + ... + e_j (the partial
+ *                 sums of s), or A - 1 if there is none;  mode: the first j with l_j == m.  logp = logp_action
+ *   eps-greedy    integers only: t = (uint64)(eps * 2^32);  explore iff w0 < t (eps = 1: always; eps = 0: never);
+ *                 exploring: action = (w1 * A) >> 32 (64-bit product), else the first j with l_j == m.  Deterministic: the latter
+ *   Gaussian      u1 = (w0 + 1) * 2^-32;  u2 = w1 * 2^-32;  z = sqrt(-2 * log(u1)) * cos(6.283185307179586 * u2), so |z| <=
+ *                 sqrt(64 ln 2) = 6.66;  deterministic: z = 0.   g = mu + exp(log_std) * z;  raw = g
+ *                 plain: action = clip(g, lo, hi);  logp = ((-(z * z) / 2) - log_std) - 0.9189385332046727 (= 1/2 log 2 pi);
+ *                 entropy = 1.4189385332046727 + log_std
+ *                 squashed: a = tanh(g);  action = clip(a, lo, hi);  logp = plain logp - log((1 - a * a) + 1e-6) (SB3's epsilon);
+ *                 no entropy.   clip(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x), then rounded to float32
+ * Bad rows: a discrete row whose maximum is not finite (a NaN or +Inf entry, or every entry -Inf), a Gaussian row whose mean is
+ * not finite or whose log_std is NaN or +Inf, and every row of a stochastic eps-greedy call whose epsilon is NaN or outside [0, 1]
+ * get action 0 and NaN in raw / logp / ent; the other rows are computed as usual, and the next ptg_sync (or any call that
+ * reports kernel-flagged errors) returns PTG_E_NONFINITE once.  A -Inf logit beside a finite one is legal: probability 0.
+ * Enqueues kernels only (one, plus the counter kernel): no host synchronisation, no allocation, so it may be captured into a
+ * hipGraph and replayed.  Reads nothing of the handle but its n_envs, device and global env offset: env state, the
+ * finished-episode ring, the ptg_vn_* statistics and every replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, head, in_dev or act_dev; NULL counter_dev unless deterministic; an unknown kind
+ * or flag; PTG_HEAD_SQUASH on a discrete kind; n_actions outside [2, 32] or in_s_n < n_actions (discrete), in_s_n < 1
+ * (Gaussian); an in_dtype other than the two; an act_kind that is not the kind's; a missing param_dev; param_s_n other than
+ * 0 | 1 (Gaussian); clip_lo > clip_hi or a NaN bound (Gaussian); raw_dev on a discrete kind; logp_dev or ent_dev on eps-greedy;
+ * ent_dev on a squashed head. */
+enum { PTG_HEAD_CATEGORICAL = 0, PTG_HEAD_EPS_GREEDY = 1, PTG_HEAD_GAUSSIAN = 2 };
+enum { PTG_HEAD_DETERMINISTIC = 1, PTG_HEAD_SQUASH = 2 };
+typedef struct ptg_head {
+    int32_t kind, flags;
+    int32_t n_actions, in_dtype;
+    const void* in_dev;
+    int64_t in_s_n;
+    const void* param_dev;
+    int32_t param_s_n, act_kind;
+    double clip_lo, clip_hi;
+    uint64_t seed;
+    uint64_t* counter_dev;
+    void* act_dev;
+    void* raw_dev;
+    void* logp_dev;
+    void* ent_dev;
+} ptg_head;
+int ptg_act(ptg_env* env, const ptg_head* head, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -15,9 +15,11 @@ N_PARTS = 9          # translation units of the parallel build: -DPTG_PART=0..8 
 N_TABLES, N_INFO = 17, 24
 ACT_I32, ACT_F32, ACT_I64 = 0, 1, 2
 OUT_F32, OUT_F64 = 0, 1
-E_INVALID, E_HIP, E_ACTION, E_RANGE, E_INDEX = -1, -2, -3, -4, -5
+E_INVALID, E_HIP, E_ACTION, E_RANGE, E_INDEX, E_NONFINITE = -1, -2, -3, -4, -5, -6
 MB_MAX_COLS = 8
 OBS_ROW_MAJOR, OBS_FEATURE_MAJOR, OBS_SB3_FLAT, OBS_SPLIT = 0, 1, 2, 3
+HEAD_CATEGORICAL, HEAD_EPS_GREEDY, HEAD_GAUSSIAN = 0, 1, 2
+HEAD_DETERMINISTIC, HEAD_SQUASH = 1, 2
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -60,6 +62,13 @@ class PtgReplay(C.Structure):                               # ptg_replay: caller
                 ("col_ring", C.c_void_p * MB_MAX_COLS), ("cursor_dev", C.c_void_p)]
 
 
+class PtgHead(C.Structure):                                 # ptg_head: one call of the action head
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("n_actions", C.c_int32), ("in_dtype", C.c_int32), ("in_dev", C.c_void_p),
+                ("in_s_n", C.c_int64), ("param_dev", C.c_void_p), ("param_s_n", C.c_int32), ("act_kind", C.c_int32),
+                ("clip_lo", C.c_double), ("clip_hi", C.c_double), ("seed", C.c_uint64), ("counter_dev", C.c_void_p),
+                ("act_dev", C.c_void_p), ("raw_dev", C.c_void_p), ("logp_dev", C.c_void_p), ("ent_dev", C.c_void_p)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -68,7 +77,7 @@ STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby
 EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_obs_dim", "ptg_last_error",
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
-           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample",
+           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -182,6 +191,7 @@ def lib():
                                 C.c_int, C.POINTER(vp), i32p, C.POINTER(vp), vp]
     L.ptg_replay_add.argtypes = [vp, C.POINTER(PtgReplay), vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int64, vp]
     L.ptg_replay_sample.argtypes = [vp, C.POINTER(PtgReplay), vp, C.c_int64, C.c_uint64, vp, vp, C.POINTER(vp), C.c_int, vp, vp]
+    L.ptg_act.argtypes = [vp, C.POINTER(PtgHead), vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

@@ -15,6 +15,7 @@
 //   k_gae             SB3's RolloutBuffer.compute_returns_and_advantage (GAE) over the [T][N] rewards, values and done flags.
 //   k_minibatch       SB3's RolloutBuffer.get / _get_samples: one shuffled minibatch gathered from the [T][N] buffers of a rollout.
 //   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
+//   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "../../include/ptg_env.h"
 
@@ -112,8 +113,9 @@ struct DevParams {
     double* fin_ret; int* fin_len; int* fin_env; int* fin_count; int fin_cap;
     const int* cmap; int q_stat;          // SB3_FLAT layout: canonical column -> flat column; canonical index of METH_STATUS (else cmap = null)
     int split;                            // SPLIT layout (16 columns: status one-hot, 8 env features, hour / day series index; q_stat set too)
-    int* err;                             // [5] in pinned HOST memory: {invalid action seen, price index out of range, hot kernel on the
-                                          // terminating step, replay on a de-synchronised batch, minibatch / replay sample index out of range} (check_error_flags); kernels store 1 (plain
+    int* err;                             // [6] in pinned HOST memory: {invalid action seen, price index out of range, hot kernel on the
+                                          // terminating step, replay on a de-synchronised batch, minibatch / replay sample index out of range,
+                                          // action head met a non-finite row} (check_error_flags); kernels store 1 (plain
                                           // stores of a constant need no atomic), the host reads it after a stream synchronise -- no copy
     int* term_flag;                       // device word: "the hot step kernel of this (captured) step found the batch on the terminating step
                                           // and skipped it" -- written by k_step_hot, read by the k_step enqueued behind it
@@ -2364,6 +2366,129 @@ k_rb_sample(const long long* __restrict__ idx, size_t B, unsigned long long seed
     if (out1) mb_stream_rows<V>(ring1, sizeof(V), P, off, rows, lane, out1 + b0 * row_bytes);
 }
 
+// ================================================================================== the action head
+// What runs between the network's output and env.step while collecting (include/ptg_env.h, ptg_act, states the lines; the tests
+// restate them in NumPy): SB3's CategoricalDistribution sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads of
+// TD3 / SAC / TQC / continuous A2C and PPO.  One lane per env on consecutive envs, no cross-lane traffic; float64 arithmetic
+// whatever the input type, rounded once on the store.  A discrete row is read three times (maximum; sum; partial sums, entropy and
+// the chosen log-prob) straight from global memory: a wave's 64 x A block is 64 * A * sizeof(IN) contiguous bytes (1 280 at float32,
+// A = 5), every pass after the first finds its lines in the L1 / L2, and the launch is bound by its own latency at every batch
+// the project runs -- an LDS-staged tile was measured beside it and bought nothing, so it is not in the tree.
+// Nothing per lane is indexed dynamically, so nothing spills to scratch for A up to 32.
+struct ActArgs {                         // by value in the launch
+    const void* in; size_t s_n;          // elements
+    const void* param; size_t param_s;   // EPS_GREEDY: const double* epsilon; GAUSSIAN: log_std in IN, stride 0 | 1
+    void *act, *raw, *logp, *ent;
+    const unsigned long long* counter;   // null when deterministic
+    unsigned long long seed;
+    long long env_offset;
+    double lo, hi;
+    size_t N;
+    int A, kind, flags, act_kind;
+    int* err;
+};
+
+__device__ __forceinline__ void act_store_action(const ActArgs& a, size_t e, long long v)
+{
+    if (a.act_kind == PTG_ACT_I64) ((long long*)a.act)[e] = v; else ((int*)a.act)[e] = (int)v;
+}
+
+constexpr int ACT_BLOCK = 256;
+template <typename IN>
+__global__ void __launch_bounds__(ACT_BLOCK)
+k_act(ActArgs a)
+{
+    const size_t e = (size_t)blockIdx.x * ACT_BLOCK + threadIdx.x;
+    if (e >= a.N) return;                                    // the ragged last wave
+    const bool det = (a.flags & PTG_HEAD_DETERMINISTIC) != 0;
+    unsigned w0 = 0, w1 = 0;
+    if (!det) {
+        const unsigned long long w = rb_draw_word(a.seed, a.counter[0], (unsigned long long)(a.env_offset + (long long)e));
+        w0 = (unsigned)(w >> 32); w1 = (unsigned)w;
+    }
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    IN* const logp_o = (IN*)a.logp; IN* const ent_o = (IN*)a.ent; IN* const raw_o = (IN*)a.raw;
+    if (a.kind == PTG_HEAD_GAUSSIAN) {
+        const double mu = (double)((const IN*)a.in)[e * a.s_n];
+        const double ls = (double)((const IN*)a.param)[e * a.param_s];
+        if (!(fabs(mu) <= 1.7976931348623157e308) || !(ls <= 1.7976931348623157e308)) {       // NaN or Inf mean; NaN or +Inf log_std
+            ((float*)a.act)[e] = 0.0f;
+            if (raw_o) raw_o[e] = (IN)nan;
+            if (logp_o) logp_o[e] = (IN)nan;
+            if (ent_o) ent_o[e] = (IN)nan;
+            a.err[5] = 1;
+            return;
+        }
+        double z = 0.0;
+        if (!det) {
+            const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = (double)w1 * 2.3283064365386963e-10;      // 2^-32
+            z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        }
+        const double g = mu + exp(ls) * z;
+        double lp = ((-(z * z) / 2.0) - ls) - 0.9189385332046727;
+        double x = g;
+        if (a.flags & PTG_HEAD_SQUASH) {
+            x = tanh(g);
+            lp = lp - log((1.0 - x * x) + 1e-6);
+        }
+        x = x < a.lo ? a.lo : (x > a.hi ? a.hi : x);
+        ((float*)a.act)[e] = (float)x;
+        if (raw_o) raw_o[e] = (IN)g;
+        if (logp_o) logp_o[e] = (IN)lp;
+        if (ent_o) ent_o[e] = (IN)(1.4189385332046727 + ls);
+        return;
+    }
+    // discrete kinds: maximum and its first index
+    const IN* __restrict__ row = (const IN*)a.in + e * a.s_n;
+    const int A = a.A;
+    double m = (double)row[0];
+    int jm = 0;
+    bool bad = m != m;
+    for (int j = 1; j < A; j++) {
+        const double l = (double)row[j];
+        bad = bad || l != l;
+        if (l > m) { m = l; jm = j; }
+    }
+    bad = bad || !(fabs(m) <= 1.7976931348623157e308);       // +Inf somewhere, or -Inf everywhere
+    if (a.kind == PTG_HEAD_EPS_GREEDY) {
+        long long action = jm;
+        if (!det) {
+            const double eps = ((const double*)a.param)[0];
+            if (!(eps >= 0.0 && eps <= 1.0)) bad = true;
+            else if ((unsigned long long)w0 < (unsigned long long)(eps * 4294967296.0))
+                action = (long long)(((unsigned long long)w1 * (unsigned long long)A) >> 32);
+        }
+        if (bad) { action = 0; a.err[5] = 1; }
+        act_store_action(a, e, action);
+        return;
+    }
+    if (bad) {
+        act_store_action(a, e, 0);
+        if (logp_o) logp_o[e] = (IN)nan;
+        if (ent_o) ent_o[e] = (IN)nan;
+        a.err[5] = 1;
+        return;
+    }
+    double s = 0.0;
+    for (int j = 0; j < A; j++) s += exp((double)row[j] - m);
+    const double log_s = log(s);
+    const double us = det ? 0.0 : (double)(((unsigned long long)w0 << 21) | (unsigned long long)(w1 >> 11)) * 1.1102230246251565e-16 * s;      // 2^-53
+    double c = 0.0, ent = 0.0, lp = 0.0;
+    int action = det ? jm : -1;
+    for (int j = 0; j < A; j++) {
+        const double d = (double)row[j] - m;
+        const double ej = exp(d);
+        const double lpj = d - log_s;
+        c += ej;
+        if (ej != 0.0) ent += (ej / s) * lpj;
+        const bool take = det ? j == jm : (action < 0 && (us < c || j == A - 1));
+        if (take) { action = j; lp = lpj; }
+    }
+    act_store_action(a, e, action);
+    if (logp_o) logp_o[e] = (IN)lp;
+    if (ent_o) ent_o[e] = (IN)(-ent);
+}
+
 }  // namespace
 
 // ================================================================================================= host side
@@ -3008,6 +3133,11 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
                        "[0, size * n_envs), or a draw from an empty buffer) was passed (NumPy raises IndexError); "
                        "its output row and column entries were left untouched");
     }
+    if (__atomic_load_n(&e[5], __ATOMIC_RELAXED)) {
+        __atomic_exchange_n(&e[5], 0, __ATOMIC_RELAXED);
+        return set_err(h, PTG_E_NONFINITE, "ptg_act: a row it cannot act on (a NaN or +Inf input, all -Inf logits, a non-finite mean, a NaN or +Inf "
+                       "log_std, or an epsilon outside [0, 1]); such rows got action 0 and NaN log-prob / entropy / raw sample, the others were computed");
+    }
     return 0;
 }
 
@@ -3322,9 +3452,9 @@ int ptg_create(const ptg_config* cfg, const ptg_tables* tables, const ptg_market
         return fail(rc);
     {   // the error words live in pinned host memory the kernels can write (see DevParams::err)
         void* dp = nullptr;
-        if (hipHostMalloc((void**)&h->err_host, 5 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
+        if (hipHostMalloc((void**)&h->err_host, 6 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
             hipHostGetDevicePointer(&dp, h->err_host, 0) != hipSuccess) { set_err(h, PTG_E_HIP, "hipHostMalloc of the error words failed"); return fail(PTG_E_HIP); }
-        h->err_host[0] = 0; h->err_host[1] = 0; h->err_host[2] = 0; h->err_host[3] = 0; h->err_host[4] = 0;
+        h->err_host[0] = 0; h->err_host[1] = 0; h->err_host[2] = 0; h->err_host[3] = 0; h->err_host[4] = 0; h->err_host[5] = 0;
         P.err = (int*)dp;
     }
     if ((rc = dev_alloc(h, &P.term_flag, 4))) return fail(rc);
@@ -4172,6 +4302,51 @@ int ptg_replay_sample(ptg_env* h, const ptg_replay* rb, const int64_t* idx_dev, 
     else hipLaunchKernelGGL(k_rb_sample<uint32_t>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)rb->obs_dim, r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
     if (!idx_dev) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)rb->cursor_dev + 1, 1ull);
     return launch_check(h, "k_rb_sample");
+}
+
+// ---- the action head: policy outputs -> actions, log-probs, entropy ----------------------------------------------------
+int ptg_act(ptg_env* h, const ptg_head* hd, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!hd) return set_err(h, PTG_E_INVALID, "ptg_act: null head");
+    const int kind = hd->kind, flags = hd->flags;
+    if (kind != PTG_HEAD_CATEGORICAL && kind != PTG_HEAD_EPS_GREEDY && kind != PTG_HEAD_GAUSSIAN) return set_err(h, PTG_E_INVALID, "ptg_act: unknown kind %d", kind);
+    if (flags & ~(PTG_HEAD_DETERMINISTIC | PTG_HEAD_SQUASH)) return set_err(h, PTG_E_INVALID, "ptg_act: unknown flag in %d", flags);
+    const bool gauss = kind == PTG_HEAD_GAUSSIAN, det = (flags & PTG_HEAD_DETERMINISTIC) != 0, squash = (flags & PTG_HEAD_SQUASH) != 0;
+    if (squash && !gauss) return set_err(h, PTG_E_INVALID, "ptg_act: PTG_HEAD_SQUASH applies to the Gaussian head only");
+    if (!hd->in_dev || !hd->act_dev) return set_err(h, PTG_E_INVALID, "ptg_act: null input or action output");
+    if (!det && !hd->counter_dev) return set_err(h, PTG_E_INVALID, "ptg_act: a stochastic head needs counter_dev");
+    if (hd->in_dtype != PTG_OUT_F32 && hd->in_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_act: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (gauss) {
+        if (hd->in_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_act: in_s_n < 1");
+        if (hd->act_kind != PTG_ACT_F32) return set_err(h, PTG_E_INVALID, "ptg_act: the Gaussian head writes PTG_ACT_F32 actions");
+        if (!hd->param_dev) return set_err(h, PTG_E_INVALID, "ptg_act: the Gaussian head needs log_std in param_dev");
+        if (hd->param_s_n != 0 && hd->param_s_n != 1) return set_err(h, PTG_E_INVALID, "ptg_act: param_s_n must be 0 or 1");
+        if (!(hd->clip_lo <= hd->clip_hi)) return set_err(h, PTG_E_INVALID, "ptg_act: clip_lo > clip_hi (or a NaN bound)");
+        if (squash && hd->ent_dev) return set_err(h, PTG_E_INVALID, "ptg_act: a squashed Gaussian has no closed-form entropy");
+    } else {
+        if (hd->n_actions < 2 || hd->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_act: n_actions outside [2, 32]");
+        if (hd->in_s_n < hd->n_actions) return set_err(h, PTG_E_INVALID, "ptg_act: in_s_n < n_actions");
+        if (hd->act_kind != PTG_ACT_I32 && hd->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_act: a discrete head writes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (hd->raw_dev) return set_err(h, PTG_E_INVALID, "ptg_act: raw_dev is the Gaussian head's");
+        if (kind == PTG_HEAD_EPS_GREEDY) {
+            if (hd->logp_dev || hd->ent_dev) return set_err(h, PTG_E_INVALID, "ptg_act: epsilon-greedy has no log-prob or entropy");
+            if (!det && !hd->param_dev) return set_err(h, PTG_E_INVALID, "ptg_act: epsilon-greedy needs epsilon in param_dev");
+        }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    ActArgs a{};
+    a.in = hd->in_dev; a.s_n = (size_t)hd->in_s_n; a.param = hd->param_dev; a.param_s = gauss ? (size_t)hd->param_s_n : 0;
+    a.act = hd->act_dev; a.raw = hd->raw_dev; a.logp = hd->logp_dev; a.ent = hd->ent_dev;
+    a.counter = det ? nullptr : (const unsigned long long*)hd->counter_dev; a.seed = (unsigned long long)hd->seed; a.env_offset = h->P.env_offset;
+    a.lo = hd->clip_lo; a.hi = hd->clip_hi; a.N = (size_t)h->n; a.A = hd->n_actions; a.kind = kind; a.flags = flags; a.act_kind = hd->act_kind;
+    a.err = h->P.err;
+    const dim3 grid((unsigned)((a.N + ACT_BLOCK - 1) / ACT_BLOCK)), block(ACT_BLOCK);
+    if (hd->in_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_act<double>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_act<float>, grid, block, 0, st, a);
+    if (!det) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)hd->counter_dev, 1ull);
+    return launch_check(h, "k_act");
 }
 
 int ptg_profile(ptg_env* h, int enable)

@@ -10,6 +10,7 @@ already mapped to ints: raw_modified {0 raw, 1 mod}, action_type {0 discrete, 1 
 train_or_eval {0 train, 1 eval}.  `markets` is a list (one per business scenario in the batch) of dicts
 with el, pot_rew, part_full, gas, eua (1-D float64), scenario, rew_l_b, rew_u_b, r_0.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -25,6 +26,12 @@ ACTIONS = ["standby", "cooldown", "startup", "partial_load", "full_load"]
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# what the action heads return: device tensors [N]; a field that was not asked for (or that the head does not have) is None
+CategoricalAct = collections.namedtuple("CategoricalAct", "actions log_prob entropy")
+EpsGreedyAct = collections.namedtuple("EpsGreedyAct", "actions")
+GaussianAct = collections.namedtuple("GaussianAct", "actions raw log_prob entropy")
 
 
 class PtgError(RuntimeError):
@@ -736,6 +743,172 @@ class HipEngine:
             self._chk(self._L.ptg_replay_sample(self._h, C.byref(d), ptr(idx), B, int(seed) & (2 ** 64 - 1), ptr(o0), ptr(o1), dst,
                                                 norm_col, ptr(io), self._stream()))
         return o0, o1, outs, io
+
+    # ------------------------------------------------------------------ the action head while collecting
+    def new_draw_counter(self):
+        """The zeroed device counter of the action heads' draws: uint64 [1], held as an int64 tensor.  A stochastic act_* call advances
+        it by one on the device, so a replayed graph draws afresh; checkpoint it with int(counter)."""
+        return self._torch.zeros(1, dtype=self._torch.int64, device=self.device)
+
+    def _act_counter(self, who, counter, deterministic):
+        torch = self._torch
+        if counter is None:
+            if not deterministic:
+                raise ValueError(f"{who}: a stochastic head needs a draw counter (new_draw_counter())")
+            return None
+        if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.shape != (1,):
+            raise TypeError(f"{who}: counter must be an int64 tensor of 1 element (new_draw_counter()), got "
+                            f"{getattr(counter, 'dtype', type(counter))} {tuple(getattr(counter, 'shape', ()))}")
+        if counter.device != self.device:
+            raise ValueError(f"{who}: counter lives on {counter.device}, the engine on {self.device}")
+        return counter
+
+    def _act_outputs(self, who, kind, out, specs):
+        """the output tensors of a head: out's (checked) or fresh ones; specs = [(field, wanted, dtype)] in the namedtuple's order"""
+        torch = self._torch
+        if out is not None and (not isinstance(out, tuple) or len(out) != len(specs)):
+            raise ValueError(f"{who}: out must be the {kind.__name__} of an earlier call")
+        res = []
+        for k, (name, wanted, dt) in enumerate(specs):
+            x = None if out is None else out[k]
+            if out is None and wanted:
+                with torch.cuda.device(self.device):
+                    x = torch.empty(self.n, dtype=dt, device=self.device)
+            if x is not None:
+                if not wanted:
+                    raise ValueError(f"{who}: out.{name} given, but the head has no such output or it was not asked for")
+                if not torch.is_tensor(x) or x.shape != (self.n,) or x.dtype != dt or not x.is_contiguous() or x.device != self.device:
+                    raise ValueError(f"{who}: out.{name} must be a contiguous [{self.n}] tensor of {dt} on {self.device}, got "
+                                     f"{tuple(getattr(x, 'shape', ()))} of {getattr(x, 'dtype', type(x))}")
+            elif name == "actions":
+                raise ValueError(f"{who}: out.actions is missing")
+            res.append(x)
+        return kind(*res)
+
+    def _act_input(self, who, x, name, discrete):
+        """logits / Q-values [N, A] with unit column stride and a row stride >= A (a slice of a wider output), or means [N] / [N, 1]"""
+        torch = self._torch
+        if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{who}: {name} must be a float32 or float64 tensor, got {getattr(x, 'dtype', type(x))}")
+        if x.device != self.device:
+            raise ValueError(f"{who}: {name} lives on {x.device}, the engine on {self.device}")
+        if discrete:
+            if x.dim() != 2 or x.shape[0] != self.n or not 2 <= x.shape[1] <= 32:
+                raise ValueError(f"{who}: {name} must be [{self.n}, A] with 2 <= A <= 32, got shape {tuple(x.shape)}")
+            if x.stride(1) != 1 or (self.n > 1 and x.stride(0) < x.shape[1]):
+                raise ValueError(f"{who}: {name} needs unit column stride and a row stride >= A, got strides {tuple(x.stride())}")
+            return x.shape[1], max(x.stride(0), x.shape[1])
+        if x.dim() == 2 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.shape != (self.n,):
+            raise ValueError(f"{who}: {name} must be [{self.n}] (or [{self.n}, 1]: the env's Box has one dimension), got shape {tuple(x.shape)}")
+        if self.n > 1 and x.stride(0) < 1:
+            raise ValueError(f"{who}: {name} has stride {x.stride(0)}")
+        return 1, max(x.stride(0), 1)
+
+    def _act_dtype(self, who, act_dtype, out):
+        """the discrete heads' action dtype: the caller's, else that of out.actions, else int32"""
+        torch = self._torch
+        if act_dtype is None and isinstance(out, tuple) and out and torch.is_tensor(out[0]):
+            act_dtype = out[0].dtype
+        act_dtype = torch.int32 if act_dtype is None else act_dtype
+        if act_dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{who}: act_dtype must be torch.int32 or torch.int64, got {act_dtype}")
+        return act_dtype
+
+    def _act_launch(self, head, x, counter, seed, res):
+        torch = self._torch
+        ptr = lambda t: None if t is None else t.data_ptr()
+        head.in_dtype = _lib.OUT_F64 if x.dtype == torch.float64 else _lib.OUT_F32
+        head.in_dev, head.seed, head.counter_dev = x.data_ptr(), int(seed) & (2 ** 64 - 1), ptr(counter)
+        head.act_dev, head.logp_dev, head.ent_dev = ptr(res.actions), ptr(getattr(res, "log_prob", None)), ptr(getattr(res, "entropy", None))
+        head.raw_dev = ptr(getattr(res, "raw", None))
+        head.act_kind = self._action_kind(res.actions)
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_act(self._h, C.byref(head), self._stream()))
+        return res
+
+    def act_categorical(self, logits, counter, seed=0, deterministic=False, out=None, want_logp=True, want_entropy=True, act_dtype=None):
+        """Enqueue, on the current stream, SB3's CategoricalDistribution.sample (deterministic: mode), log_prob and entropy of the
+        logits [N, A] (float32 / float64, 2 <= A <= 32, a column slice of a wider tensor is fine) in ONE launch (include/ptg_env.h:
+        ptg_act, which states the arithmetic).  act_dtype None: the dtype of out.actions when out is given, else torch.int32 (torch is
+        imported lazily here, so the default is spelled None).  counter: new_draw_counter(); row e of the c-th call draws from (seed, c, global env
+        offset + e).  Returns CategoricalAct(actions [N] of act_dtype (torch.int32, the default, or int64: what step() takes), log_prob
+        [N], entropy [N] in the logits' dtype, or None when not wanted); out: an earlier call's result, reused (a captured call).
+        No synchronisation; a row with a NaN or +Inf logit, or -Inf in every column, gets action 0 and NaN outputs and makes the next
+        sync() raise PtgError with code PTG_E_NONFINITE."""
+        who = "act_categorical"
+        A, s_n = self._act_input(who, logits, "logits", True)
+        counter = self._act_counter(who, counter, deterministic)
+        res = self._act_outputs(who, CategoricalAct, out, [("actions", True, self._act_dtype(who, act_dtype, out)), ("log_prob", want_logp, logits.dtype),
+                                                           ("entropy", want_entropy, logits.dtype)])
+        head = _lib.PtgHead(kind=_lib.HEAD_CATEGORICAL, flags=_lib.HEAD_DETERMINISTIC if deterministic else 0, n_actions=A, in_s_n=s_n)
+        return self._act_launch(head, logits, counter, seed, res)
+
+    def act_eps_greedy(self, q, eps, counter, seed=0, deterministic=False, out=None, act_dtype=None):
+        """DQN's collecting policy in one launch: with probability eps a uniform random action, else the first maximal Q-value of
+        q [N, A]; deterministic: always the latter (eps is not read).  eps: a float64 device tensor of 1 element, read when the kernel
+        runs (anneal it in place between replays), or a Python float, written to a fresh device scalar by a fill kernel ahead of the head
+        on the same stream -- a captured call then keeps that value on every replay.
+        Returns EpsGreedyAct(actions).  A row with a NaN or +Inf value, and every row when eps is NaN or outside [0, 1], gets action 0
+        and makes the next sync() raise PtgError with code PTG_E_NONFINITE."""
+        torch = self._torch
+        who = "act_eps_greedy"
+        A, s_n = self._act_input(who, q, "q", True)
+        counter = self._act_counter(who, counter, deterministic)
+        if torch.is_tensor(eps):
+            if eps.dtype != torch.float64 or eps.numel() != 1 or not eps.is_contiguous():
+                raise TypeError(f"{who}: a tensor eps must be float64 with 1 element, got {eps.dtype} {tuple(eps.shape)}")
+            if eps.device != self.device:
+                raise ValueError(f"{who}: eps lives on {eps.device}, the engine on {self.device}")
+        elif eps is None:
+            if not deterministic:
+                raise ValueError(f"{who}: a stochastic call needs eps")
+        else:
+            eps = float(eps)                                  # written to the device below, once every check has passed
+        res = self._act_outputs(who, EpsGreedyAct, out, [("actions", True, self._act_dtype(who, act_dtype, out))])
+        if isinstance(eps, float):                            # a fill kernel on the current stream, not a host copy: it can be captured, and
+            with torch.cuda.device(self.device):              # a replay then writes the same value into the graph's own memory
+                eps = torch.full((1,), eps, dtype=torch.float64, device=self.device)
+        head = _lib.PtgHead(kind=_lib.HEAD_EPS_GREEDY, flags=_lib.HEAD_DETERMINISTIC if deterministic else 0, n_actions=A, in_s_n=s_n,
+                            param_dev=None if eps is None else eps.data_ptr())
+        return self._act_launch(head, q, counter, seed, res)
+
+    def act_gaussian(self, mean, log_std, counter, clip=(-1.0, 1.0), squash=False, seed=0, deterministic=False, out=None, want_raw=True,
+                     want_logp=True, want_entropy=None):
+        """The Gaussian heads in one launch: g = mean + exp(log_std) * z, z a Box-Muller normal (deterministic: z = 0).  Plain
+        (TD3 with log_std = log(sigma_exp); continuous A2C / PPO): actions = clip(g), log_prob and entropy of N(mean, sigma);
+        squash=True (SAC / TQC): actions = clip(tanh(g)), log_prob with SB3's tanh correction, no entropy.  mean [N] (or [N, 1]),
+        log_std of mean's dtype: 1 element (state-independent) or [N]; both may be rewritten between replays.  Returns
+        GaussianAct(actions float32 [N] for step(), raw = g unclipped and unsquashed (what an on-policy buffer stores), log_prob,
+        entropy).  A non-finite mean or a NaN / +Inf log_std gives action 0, NaN outputs and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "act_gaussian"
+        self._act_input(who, mean, "mean", False)
+        m1 = mean[:, 0] if mean.dim() == 2 else mean
+        if not torch.is_tensor(log_std) or log_std.dtype != mean.dtype:
+            raise TypeError(f"{who}: log_std must be a tensor of mean's dtype {mean.dtype}, got {getattr(log_std, 'dtype', type(log_std))}")
+        if log_std.device != self.device:
+            raise ValueError(f"{who}: log_std lives on {log_std.device}, the engine on {self.device}")
+        if log_std.numel() == 1:
+            p_s = 0
+        elif log_std.numel() == self.n and log_std.is_contiguous() and log_std.dim() <= 2:
+            p_s = 1
+        else:
+            raise ValueError(f"{who}: log_std must have 1 element or be a contiguous [{self.n}] tensor, got shape {tuple(log_std.shape)}")
+        lo, hi = float(clip[0]), float(clip[1])
+        if not lo <= hi:
+            raise ValueError(f"{who}: clip {clip} is not an interval")
+        if want_entropy is None:
+            want_entropy = not squash
+        if squash and want_entropy:
+            raise ValueError(f"{who}: a squashed Gaussian has no closed-form entropy")
+        counter = self._act_counter(who, counter, deterministic)
+        res = self._act_outputs(who, GaussianAct, out, [("actions", True, torch.float32), ("raw", want_raw, mean.dtype), ("log_prob", want_logp, mean.dtype),
+                                                        ("entropy", want_entropy, mean.dtype)])
+        flags = (_lib.HEAD_DETERMINISTIC if deterministic else 0) | (_lib.HEAD_SQUASH if squash else 0)
+        head = _lib.PtgHead(kind=_lib.HEAD_GAUSSIAN, flags=flags, in_s_n=max(m1.stride(0), 1), param_dev=log_std.data_ptr(), param_s_n=p_s, clip_lo=lo, clip_hi=hi)
+        return self._act_launch(head, m1, counter, seed, res)
 
     def market_feature_series(self):
         """The pre-normalised float32 feature series the kernels read, each [n_sets, length]: dict(featA, featB (hourly), gas_n, eua_n
