@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PTG_ABI_VERSION 12  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
+#define PTG_ABI_VERSION 13  /* 2: + ptg_rollout_launches, ptg_rollout_info, ptg_vn_*, PTG_OBS_SB3_FLAT;  3: + ptg_profile*, ptg_step_host, ptg_host_layout, PTG_OBS_SPLIT, ptg_market_feature_series;
                              * 4: + ptg_profile_read_ex, ptg_finished_dropped, ptg_host_buffers_changed, ptg_steps_to_episode_end,
                              *    ptg_host_layout_ex (status section), ptg_step_host_begin / _tail / _end / _finish, ptg_set_feature_pitch;
                              * 5: + ptg_note_replays, ptg_set_replay_proof (the hot kernels read the step count from the device state: captured launches can be replayed);
@@ -37,7 +37,8 @@ extern "C" {
                              * 9: + ptg_gae (advantages and returns of a rollout on the device);
                              * 10: + ptg_minibatch, PTG_E_INDEX (shuffled minibatches gathered from the rollout buffers on the device);
                              * 11: + ptg_replay, ptg_replay_add, ptg_replay_sample (the off-policy algorithms' replay buffer on the device);
-                             * 12: + ptg_head, ptg_act, PTG_E_NONFINITE (policy outputs to actions, log-probs and entropy in one launch) */
+                             * 12: + ptg_head, ptg_act, PTG_E_NONFINITE (policy outputs to actions, log-probs and entropy in one launch);
+                             * 13: + ptg_loss, ptg_policy_loss, ptg_policy_loss_workspace (the PPO / A2C loss and its gradients in one pass) */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -49,8 +50,9 @@ enum {
     PTG_E_HIP = -2,            /* a HIP runtime call failed (no device, out of memory, ...) */
     PTG_E_ACTION = -3,         /* a discrete action outside [-5, 4] reached a kernel (reference: IndexError, :347) */
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
-    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError) */
-    PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1] */
+    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss an action outside [0, A) */
+    PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1];
+                                * ptg_policy_loss a row it has no finite loss for */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -498,7 +500,7 @@ int ptg_replay_sample(ptg_env* env, const ptg_replay* rb, const int64_t* idx_dev
  *   PTG_HEAD_GAUSSIAN     TD3 clip(mu + N(0, sigma_exp), -1, 1); SAC / TQC tanh(mu + sigma z) (PTG_HEAD_SQUASH); A2C / PPO with
  *                         action_type "continuous": DiagGaussianDistribution, clipped to the Box for the env and stored unclipped
  * -- six to ten element-wise launches in torch.  The env's Box is one-dimensional, so the Gaussian head has D = 1: one mean and one
- * action per env.  Out of scope: the networks, evaluate_actions at training time (autograd), gSDE.
+ * action per env.  Out of scope: the networks, gSDE (evaluate_actions at training time is ptg_policy_loss, below).
  * The head is described by a ptg_head, read during the call:
  *   kind          PTG_HEAD_CATEGORICAL | PTG_HEAD_EPS_GREEDY | PTG_HEAD_GAUSSIAN
  *   flags         PTG_HEAD_DETERMINISTIC: the mode; nothing is drawn, counter_dev is neither read nor advanced (and may be NULL).
@@ -563,6 +565,113 @@ typedef struct ptg_head {
     void* ent_dev;
 } ptg_head;
 int ptg_act(ptg_env* env, const ptg_head* head, void* stream);
+
+/* ---- the policy loss: PPO / A2C loss, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass ------
+ * Replaces what the reference's A2C and PPO (src/rl_config_agent.py:80-222) run on every minibatch between the network's output
+ * and the gradient that goes back into the network (SB3 2.0.0a13): ActorCriticPolicy.evaluate_actions' Categorical / DiagGaussian
+ * log_prob and entropy, the loss lines of PPO.train (ppo/ppo.py) / A2C.train (a2c/a2c.py) -- advantage normalisation; ratio,
+ * clamp and min; value clipping and MSE; the entropy term; approx_kl and clip_fraction -- and autograd's walk back over the same
+ * graph: some forty element-wise launches forward and as many backward.  Every gradient of these losses with respect to the
+ * network's outputs is a closed form of quantities the forward pass holds, so one pass emits the loss, the statistics SB3 logs,
+ * d loss / d logits (or means), d loss / d values and d loss / d log_std; the caller's backward starts from those
+ * (rl_ptg_amd/loss.py wraps the call in a torch.autograd.Function).  Out of scope: the networks, the optimiser, max_grad_norm,
+ * target_kl's early stop (the caller reads stats[4]), gSDE, the squashed and off-policy losses, a per-env log_std.
+ * The call is described by a ptg_loss, read during the call (B = batch, A = n_actions):
+ *   kind          PTG_LOSS_PPO | PTG_LOSS_A2C
+ *   head          PTG_HEAD_CATEGORICAL | PTG_HEAD_GAUSSIAN (unsquashed, D = 1, as in ptg_act)
+ *   flags         PTG_LOSS_NORM_ADV: normalise the advantages over the batch.  PTG_LOSS_CLIP_VF: clip the value step
+ *   batch         B >= 1, a 64-bit count that is not tied to the handle's n_envs (A2C's one batch is all T * N rows)
+ *   in_dtype      PTG_OUT_F32 | PTG_OUT_F64: the element type of EVERY float input and of every gradient
+ *   in_dev        categorical: logits [B][A], element (i, j) at i * in_s_n + j, in_s_n >= A, 2 <= A <= 32.  Gaussian: the means [B],
+ *                 element i at i * in_s_n, in_s_n >= 1 (n_actions is not read)
+ *   val_dev       values [B], element i at i * val_s_n, val_s_n >= 1: a column of an [B][A + 1] actor-critic output is read in place
+ *   act_dev       [B] contiguous.  Categorical: the chosen actions, act_kind PTG_ACT_I32 | PTG_ACT_I64.  Gaussian: the stored raw
+ *                 (unclipped) samples in in_dtype; act_kind is not read
+ *   old_logp_dev, adv_dev, ret_dev   [B] contiguous in in_dtype, what ptg_minibatch gathers (old_logp_dev: PPO only; A2C neither
+ *                 needs nor reads it)
+ *   old_val_dev   [B] contiguous, required iff PTG_LOSS_CLIP_VF
+ *   log_std_dev   Gaussian only: one value in in_dtype on the device (SB3's state-independent log_std), so that a replayed graph
+ *                 sees the optimiser's update
+ *   clip_range, clip_range_vf, ent_coef, vf_coef   host doubles eps, eps_v, c_e, c_v; a captured call keeps them.  clip_range is
+ *                 read by PPO only, clip_range_vf with PTG_LOSS_CLIP_VF only
+ *   stats_dev     float64 [8] = {loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv mean, adv std}; the last
+ *                 two are the moments actually used, 0 and 1 when the advantages are not normalised
+ *   grad_in_dev   d loss / d in_dev in in_dtype with the shape rules of in_dev and the row stride g_s_n
+ *   grad_val_dev  d loss / d values, element i at i * gv_s_n.  With g_s_n = gv_s_n = A + 1 the two fill one [B][A + 1] tensor
+ *   grad_log_std_dev   [1] in in_dtype, Gaussian only, nullable
+ *   ws_dev        caller-owned device scratch, 8-byte aligned, at least ptg_policy_loss_workspace(batch) bytes; its contents
+ *                 mean nothing before or after the call
+ * Arithmetic: all of it in float64 whatever in_dtype is, every operation rounded once (no fused multiply-add), gradients rounded
+ * once on the store; exp, log, sqrt are the double-precision library functions.  Row i, l_j = (double)in[i][j], a = its action:
+ *   categorical   m, e_j, s, logp_j and the entropy H exactly as ptg_act states them;  p_j = e_j / s;  lp = logp_a
+ *   Gaussian      sigma = exp(ls);  z = (a - mu) / sigma;  lp = ((-(z * z) / 2) - ls) - 0.9189385332046727;  H = 1.4189385332046727 + ls
+ *   advantages    PTG_LOSS_NORM_ADV and B > 1: Ah = (adv - mean) / (std + 1e-8), std = sqrt(M2 / (B - 1)) (torch.std's unbiased one),
+ *                 (count, mean, M2) merged over the batch with Chan's formula;  otherwise (SB3 skips a batch of one) Ah = adv.
+ *                 Advantages are data: nothing is differentiated through them or their moments
+ *   PPO           d = lp - old;  r = exp(d);  c = r < 1 - eps ? 1 - eps : (r > 1 + eps ? 1 + eps : r);  t1 = Ah * r;  t2 = Ah * c;
+ *                 surrogate = t2 < t1 ? t2 : t1;  g = t1 if t1 < t2 or 1 - eps <= r <= 1 + eps, else 0 (torch.minimum's and
+ *                 clamp's tie rules: on a tie each branch carries half, and an unclipped ratio is always a tie);
+ *                 kl = (r - 1) - d;  cf = |r - 1| > eps ? 1 : 0
+ *   A2C           surrogate = Ah * lp;  g = Ah;  kl = cf = 0
+ *   value         without PTG_LOSS_CLIP_VF vh = v and pass = 1; with it dv = v - old_v, vh = old_v + clamp(dv, -eps_v, eps_v),
+ *                 pass = -eps_v <= dv <= eps_v;   dq = ret - vh;  q = dq * dq;  h = pass ? 2 * (vh - ret) : 0
+ *   means         policy_loss = -(sum surrogate / B);  value_loss = sum q / B;  entropy_loss = -(sum H / B);  approx_kl = sum kl / B;
+ *                 clip_fraction = sum cf / B;  loss = (policy_loss + c_e * entropy_loss) + c_v * value_loss
+ *   gradients     d loss / d l_j = ((-g) * ([j == a] - p_j) + c_e * (p_j * (logp_j + H))) / B, the c_e term left out where e_j == 0 (as
+ *                 H leaves that column out): a column of probability 0 that was not chosen gets 0
+ *                 d loss / d v = (c_v * h) / B;   Gaussian: d loss / d mu = ((-g) * (z / sigma)) / B,
+ *                 d loss / d log_std = (-(sum g * ((z * z) - 1)) / B) - c_e
+ * Sums run in a fixed order that depends on B alone (per wave a shuffle tree, the waves of a 256-row block in order, the blocks'
+ * partials in ws_dev, a last pass over the partials; no floating-point atomics): the same inputs give the same bits on every run.
+ * Known difference from SB3: it normalises float32 advantages in float32; here the moments and Ah are float64.
+ * Bad rows.  No index ever becomes an address: a categorical action outside [0, A) leaves the row's gradients untouched and the
+ * next ptg_sync (or any call that reports kernel-flagged errors) returns PTG_E_INDEX once.  A row whose logit maximum is not finite
+ * (a NaN or +Inf entry, or every entry -Inf), a non-finite value, advantage, return, old log-prob (PPO), old value (with
+ * PTG_LOSS_CLIP_VF) or mean, a NaN or +Inf log_std, an action whose log-probability is not finite (a -Inf logit, a zero sigma, a
+ * non-finite sample), and a PPO row whose ratio r = exp(lp - old) is not finite (it overflows: Ah * r would be Inf, or NaN where Ah
+ * is 0) gets NaN gradients and the next ptg_sync returns PTG_E_NONFINITE once.  Either kind of row makes stats[0..5]
+ * (and the log_std gradient) NaN; the other rows' gradients are computed as usual -- except that a non-finite advantage under
+ * PTG_LOSS_NORM_ADV makes the moments, and with them every row, NaN, as the arithmetic says.  A -Inf logit on a column that was
+ * not chosen is legal: probability 0.
+ * Enqueues kernels only -- one for B <= 256 (PPO's minibatch of 203); else rows + final merge, and two more in front for the
+ * moments under PTG_LOSS_NORM_ADV -- with no host synchronisation and no allocation, so it may be captured into a hipGraph and
+ * replayed.  Reads nothing of the handle but its device: env state, the finished-episode ring, the ptg_vn_* statistics and every
+ * replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, in_dev, val_dev, act_dev, adv_dev, ret_dev, stats_dev, grad_in_dev,
+ * grad_val_dev or ws_dev (or a ws_dev that is not 8-byte aligned); NULL old_logp_dev for PPO; an unknown kind, head or flag; batch < 1
+ * (or above 2^31: the row kernel's grid stays at half of the 2^32 threads one launch may have; the largest batch run is 20 x 65 536); n_actions outside [2, 32] (categorical); in_s_n or g_s_n below n_actions (Gaussian: below 1), val_s_n or gv_s_n
+ * below 1; an in_dtype other than the two; an act_kind other than PTG_ACT_I32 | PTG_ACT_I64 (categorical); PTG_LOSS_CLIP_VF without
+ * old_val_dev; the Gaussian head without log_std_dev; grad_log_std_dev on the categorical head; a NaN or negative clip_range (PPO)
+ * or clip_range_vf (with PTG_LOSS_CLIP_VF).
+ * ptg_policy_loss_workspace(batch): bytes of scratch a batch of that size needs (88 per 256 rows + 32); negative for batch < 1 or above 2^31. */
+enum { PTG_LOSS_PPO = 0, PTG_LOSS_A2C = 1 };
+enum { PTG_LOSS_NORM_ADV = 1, PTG_LOSS_CLIP_VF = 2 };
+typedef struct ptg_loss {
+    int32_t kind, head;
+    int32_t flags, n_actions;
+    int32_t in_dtype, act_kind;
+    int64_t batch;
+    const void* in_dev;
+    int64_t in_s_n;
+    const void* val_dev;
+    int64_t val_s_n;
+    const void* act_dev;
+    const void* old_logp_dev;
+    const void* adv_dev;
+    const void* ret_dev;
+    const void* old_val_dev;
+    const void* log_std_dev;
+    double clip_range, clip_range_vf, ent_coef, vf_coef;
+    double* stats_dev;
+    void* grad_in_dev;
+    int64_t g_s_n;
+    void* grad_val_dev;
+    int64_t gv_s_n;
+    void* grad_log_std_dev;
+    void* ws_dev;
+} ptg_loss;
+int64_t ptg_policy_loss_workspace(int64_t batch);
+int ptg_policy_loss(ptg_env* env, const ptg_loss* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -20,6 +20,8 @@ MB_MAX_COLS = 8
 OBS_ROW_MAJOR, OBS_FEATURE_MAJOR, OBS_SB3_FLAT, OBS_SPLIT = 0, 1, 2, 3
 HEAD_CATEGORICAL, HEAD_EPS_GREEDY, HEAD_GAUSSIAN = 0, 1, 2
 HEAD_DETERMINISTIC, HEAD_SQUASH = 1, 2
+LOSS_PPO, LOSS_A2C = 0, 1
+LOSS_NORM_ADV, LOSS_CLIP_VF = 1, 2
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -69,6 +71,15 @@ class PtgHead(C.Structure):                                 # ptg_head: one call
                 ("act_dev", C.c_void_p), ("raw_dev", C.c_void_p), ("logp_dev", C.c_void_p), ("ent_dev", C.c_void_p)]
 
 
+class PtgLoss(C.Structure):                                 # ptg_loss: one call of the policy loss
+    _fields_ = [("kind", C.c_int32), ("head", C.c_int32), ("flags", C.c_int32), ("n_actions", C.c_int32), ("in_dtype", C.c_int32),
+                ("act_kind", C.c_int32), ("batch", C.c_int64), ("in_dev", C.c_void_p), ("in_s_n", C.c_int64), ("val_dev", C.c_void_p),
+                ("val_s_n", C.c_int64), ("act_dev", C.c_void_p), ("old_logp_dev", C.c_void_p), ("adv_dev", C.c_void_p), ("ret_dev", C.c_void_p),
+                ("old_val_dev", C.c_void_p), ("log_std_dev", C.c_void_p), ("clip_range", C.c_double), ("clip_range_vf", C.c_double),
+                ("ent_coef", C.c_double), ("vf_coef", C.c_double), ("stats_dev", C.c_void_p), ("grad_in_dev", C.c_void_p), ("g_s_n", C.c_int64),
+                ("grad_val_dev", C.c_void_p), ("gv_s_n", C.c_int64), ("grad_log_std_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -77,7 +88,7 @@ STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby
 EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_obs_dim", "ptg_last_error",
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
-           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act",
+           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -192,6 +203,9 @@ def lib():
     L.ptg_replay_add.argtypes = [vp, C.POINTER(PtgReplay), vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int64, vp]
     L.ptg_replay_sample.argtypes = [vp, C.POINTER(PtgReplay), vp, C.c_int64, C.c_uint64, vp, vp, C.POINTER(vp), C.c_int, vp, vp]
     L.ptg_act.argtypes = [vp, C.POINTER(PtgHead), vp]
+    L.ptg_policy_loss_workspace.argtypes = [C.c_int64]
+    L.ptg_policy_loss_workspace.restype = C.c_int64
+    L.ptg_policy_loss.argtypes = [vp, C.POINTER(PtgLoss), vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

@@ -16,6 +16,7 @@
 //   k_minibatch       SB3's RolloutBuffer.get / _get_samples: one shuffled minibatch gathered from the [T][N] buffers of a rollout.
 //   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
 //   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
+//   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "../../include/ptg_env.h"
 
@@ -2489,6 +2490,272 @@ k_act(ActArgs a)
     if (ent_o) ent_o[e] = (IN)(-ent);
 }
 
+// ================================================================================== the policy loss
+// What runs between the network's output on a minibatch and the gradient that goes back into it (include/ptg_env.h, ptg_policy_loss,
+// states the lines; tests/policy_loss_restatement.py restates them in NumPy): SB3's evaluate_actions (Categorical / DiagGaussian
+// log_prob and entropy) and the loss lines of PPO.train / A2C.train, with d loss / d logits (or means), d loss / d values and
+// d loss / d log_std in closed form -- every one is a function of quantities the forward pass holds, so no graph is walked back.
+// One lane per row on consecutive rows, float64 arithmetic whatever the input type, gradients rounded once on the store.  A
+// categorical row is read as k_act reads it (maximum; sum; entropy and the chosen log-prob) plus a fourth pass that writes the
+// gradients, which need the row's complete entropy; exp is evaluated again instead of kept, so nothing per lane is indexed dynamically.
+// Batch-wide quantities (the advantage moments, six sums, the log_std gradient) are reduced in a fixed order: a shuffle tree per wave,
+// the block's four waves in wave order, one partial per block in the caller's workspace, and a merge that walks the partials in an
+// order given by the block count alone.  No floating-point atomics: the same inputs give the same bits.  Moments travel as
+// (count, mean, M2) and meet in chan_merge, as the reward normalisation's do.
+struct LossArgs {                        // by value in the launch
+    const void* in; size_t s_n;          // elements
+    const void* val; size_t v_s;
+    const void *act, *old_lp, *adv, *ret, *old_val, *log_std;
+    void* g_in; size_t g_s;
+    void* g_val; size_t gv_s;
+    void* g_ls;
+    double* stats;
+    double* ws;                          // [0..2] merged advantage moments; [4 ..) moment partials [nblk][3]; then row partials [nblk][8]
+    double eps, eps_v, ent_coef, vf_coef;
+    size_t B;
+    int A, kind, head, flags, act_kind, nblk;
+    int* err;
+};
+struct PlRow { double surr, q, H, kl, cf, gls; };     // a row's terms of the five means and of the log_std gradient's sum
+
+constexpr int PL_BLOCK = 256, PL_WAVES = PL_BLOCK / 64, PL_TERMS = 6, PL_PITCH = 8;
+constexpr double PL_DBL_MAX = 1.7976931348623157e308;
+
+__device__ __forceinline__ double pl_wave_sum(double v)      // a + b == b + a: every lane ends with the same bits
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ bool pl_finite(double x) { return fabs(x) <= PL_DBL_MAX; }
+
+// (count, mean, M2) of the block's advantages: two shuffle trees per wave (sum -> mean, then squared deviations from it: a sum of
+// squares would cancel), the block's waves merged in wave order.  Every thread of the block calls it; `sh` holds PL_WAVES * 3 doubles.
+template <typename IN>
+__device__ __forceinline__ void pl_block_moments(const LossArgs& a, size_t i, bool live, double* sh, double& c, double& m, double& M)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double x = live ? (double)((const IN*)a.adv)[i] : 0.0;
+    const double n = pl_wave_sum(live ? 1.0 : 0.0);
+    const double s = pl_wave_sum(x);
+    const double mean = n > 0.0 ? s / n : 0.0;
+    const double dv = live ? x - mean : 0.0;
+    const double m2 = pl_wave_sum(dv * dv);
+    if (lane == 0) { sh[w * 3 + 0] = n; sh[w * 3 + 1] = mean; sh[w * 3 + 2] = m2; }
+    __syncthreads();
+    c = 0.0; m = 0.0; M = 0.0;
+    for (int k = 0; k < PL_WAVES; k++) chan_merge(c, m, M, sh[k * 3 + 0], sh[k * 3 + 1], sh[k * 3 + 2]);
+}
+
+// One row: its gradients are stored, its terms returned.  mean / den: the advantage moments in use (den = std + 1e-8).
+template <typename IN>
+__device__ __forceinline__ PlRow pl_row(const LossArgs& a, size_t i, bool norm, double mean, double den)
+{
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const PlRow poison{nan, nan, nan, nan, nan, nan};
+    const double Bd = (double)a.B;
+    const bool ppo = a.kind == PTG_LOSS_PPO, clipv = (a.flags & PTG_LOSS_CLIP_VF) != 0, cat = a.head == PTG_HEAD_CATEGORICAL;
+    const int A = a.A;
+    long long act = 0;
+    if (cat) {
+        act = a.act_kind == PTG_ACT_I64 ? ((const long long*)a.act)[i] : (long long)((const int*)a.act)[i];
+        if (act < 0 || act >= (long long)A) { a.err[4] = 1; return poison; }      // never an address; the row's gradients stay as they were
+    }
+    const double v = (double)((const IN*)a.val)[i * a.v_s];
+    const double adv = (double)((const IN*)a.adv)[i], ret = (double)((const IN*)a.ret)[i];
+    const double old = ppo ? (double)((const IN*)a.old_lp)[i] : 0.0;
+    const double ov = clipv ? (double)((const IN*)a.old_val)[i] : 0.0;
+    bool bad = !pl_finite(v) || !pl_finite(adv) || !pl_finite(ret) || !pl_finite(old) || !pl_finite(ov);
+    IN* const g_row = (IN*)a.g_in + i * a.g_s;
+    const IN* __restrict__ row = (const IN*)a.in + i * a.s_n;
+    double lp = 0.0, H = 0.0, m = 0.0, s = 1.0, log_s = 0.0, z = 0.0, sigma = 1.0;
+    if (cat) {
+        m = (double)row[0];
+        bad = bad || m != m;
+        for (int j = 1; j < A; j++) {
+            const double l = (double)row[j];
+            bad = bad || l != l;
+            if (l > m) m = l;
+        }
+        bad = bad || !pl_finite(m);                          // +Inf somewhere, or -Inf everywhere
+        if (!bad) {
+            s = 0.0;
+            for (int j = 0; j < A; j++) s += exp((double)row[j] - m);
+            log_s = log(s);
+            double ent = 0.0;
+            for (int j = 0; j < A; j++) {
+                const double d = (double)row[j] - m;
+                const double ej = exp(d);
+                const double lpj = d - log_s;
+                if (ej != 0.0) ent += (ej / s) * lpj;
+                if (j == (int)act) lp = lpj;
+            }
+            H = -ent;
+        }
+    } else {
+        const double mu = (double)row[0], ls = (double)((const IN*)a.log_std)[0], x = (double)((const IN*)a.act)[i];
+        bad = bad || !pl_finite(mu) || !(ls <= PL_DBL_MAX);   // NaN or Inf mean; NaN or +Inf log_std
+        sigma = exp(ls);
+        z = (x - mu) / sigma;
+        lp = ((-(z * z) / 2.0) - ls) - 0.9189385332046727;
+        H = 1.4189385332046727 + ls;
+    }
+    bad = bad || !pl_finite(lp);                             // an action of probability 0 (a -Inf logit, a zero sigma), a non-finite sample
+    double d = 0.0, r = 1.0;
+    if (ppo) {
+        d = lp - old;
+        r = exp(d);
+        bad = bad || !pl_finite(r);                          // a ratio that overflows: Ah * r would be Inf, or NaN where Ah is 0
+    }
+    IN* const g_v = (IN*)a.g_val + i * a.gv_s;
+    if (bad) {
+        if (cat) { for (int j = 0; j < A; j++) g_row[j] = (IN)nan; } else g_row[0] = (IN)nan;
+        g_v[0] = (IN)nan;
+        a.err[5] = 1;
+        return poison;
+    }
+    const double ah = norm ? (adv - mean) / den : adv;
+    PlRow t{0.0, 0.0, H, 0.0, 0.0, 0.0};
+    double g;
+    if (ppo) {
+        const double lo = 1.0 - a.eps, hi = 1.0 + a.eps;
+        const double c = r < lo ? lo : (r > hi ? hi : r);
+        const double t1 = ah * r, t2 = ah * c;
+        t.surr = (t1 != t1 || t2 != t2) ? nan : (t2 < t1 ? t2 : t1);
+        g = (t1 < t2 || (r >= lo && r <= hi)) ? t1 : 0.0;
+        t.kl = (r - 1.0) - d;
+        t.cf = fabs(r - 1.0) > a.eps ? 1.0 : 0.0;
+    } else {
+        t.surr = ah * lp;
+        g = ah;
+    }
+    double vh = v;
+    bool pass = true;
+    if (clipv) {
+        const double dv = v - ov;
+        const double cl = dv < -a.eps_v ? -a.eps_v : (dv > a.eps_v ? a.eps_v : dv);
+        vh = ov + cl;
+        pass = dv >= -a.eps_v && dv <= a.eps_v;
+    }
+    const double dq = ret - vh;
+    t.q = dq * dq;
+    const double h = pass ? 2.0 * (vh - ret) : 0.0;
+    g_v[0] = (IN)((a.vf_coef * h) / Bd);
+    if (cat) {
+        for (int j = 0; j < A; j++) {
+            const double d = (double)row[j] - m;
+            const double ej = exp(d);
+            const double p = ej / s;
+            double gr = (-g) * ((j == (int)act ? 1.0 : 0.0) - p);
+            if (ej != 0.0) gr = gr + a.ent_coef * (p * ((d - log_s) + H));      // the entropy term of a probability-0 column is left out, as in H
+            g_row[j] = (IN)(gr / Bd);
+        }
+    } else {
+        g_row[0] = (IN)(((-g) * (z / sigma)) / Bd);
+        t.gls = g * ((z * z) - 1.0);
+    }
+    return t;
+}
+
+// the sums of a whole batch -> the eight statistics and the log_std gradient; one thread
+template <typename IN>
+__device__ __forceinline__ void pl_finish(const LossArgs& a, const double* sum, double mean, double sd)
+{
+    const double Bd = (double)a.B;
+    const double pl = -(sum[0] / Bd), vl = sum[1] / Bd, el = -(sum[2] / Bd);
+    a.stats[0] = (pl + a.ent_coef * el) + a.vf_coef * vl;
+    a.stats[1] = pl; a.stats[2] = vl; a.stats[3] = el;
+    a.stats[4] = sum[3] / Bd; a.stats[5] = sum[4] / Bd;
+    a.stats[6] = mean; a.stats[7] = sd;
+    if (a.g_ls) ((IN*)a.g_ls)[0] = (IN)((-(sum[5]) / Bd) - a.ent_coef);
+}
+
+// the block's sums of PL_TERMS values: a shuffle tree per wave, then the waves in wave order (thread 0 holds the result)
+__device__ __forceinline__ void pl_block_sum(double* v, double* sh)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < PL_TERMS; k++) {
+        v[k] = pl_wave_sum(v[k]);
+        if (lane == 0) sh[w * PL_PITCH + k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) {
+            double s = sh[k];
+            for (int q = 1; q < PL_WAVES; q++) s += sh[q * PL_PITCH + k];
+            v[k] = s;
+        }
+    }
+}
+
+template <typename IN>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_pl_moments(LossArgs a)
+{
+    __shared__ double sh[PL_WAVES * 3];
+    const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    double c, m, M;
+    pl_block_moments<IN>(a, i, i < a.B, sh, c, m, M);
+    if (threadIdx.x == 0) {
+        double* p = a.ws + 4 + (size_t)blockIdx.x * 3;
+        p[0] = c; p[1] = m; p[2] = M;
+    }
+}
+
+// ONE: the whole batch is this block (B <= PL_BLOCK): moments, rows and statistics in one launch.  Otherwise the moments come
+// merged from the workspace and the block leaves its partial sums there for k_pl_final.
+template <typename IN, bool ONE>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_pl_rows(LossArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
+    const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
+    double mean = 0.0, sd = 1.0;
+    if (norm) {
+        double c, m, M;
+        if (ONE) { pl_block_moments<IN>(a, i, live, sh, c, m, M); __syncthreads(); }
+        else { c = a.ws[0]; m = a.ws[1]; M = a.ws[2]; }
+        mean = m;
+        sd = sqrt(M / ((double)a.B - 1.0));                  // torch.std: the unbiased one
+    }
+    PlRow t{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (live) t = pl_row<IN>(a, i, norm, mean, sd + 1e-8);
+    double v[PL_TERMS] = {t.surr, t.q, t.H, t.kl, t.cf, t.gls};
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        if (ONE) pl_finish<IN>(a, v, mean, sd);
+        else {
+            double* p = a.ws + 4 + (size_t)a.nblk * 3 + (size_t)blockIdx.x * PL_PITCH;
+#pragma unroll
+            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
+        }
+    }
+}
+
+// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
+template <typename IN>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_pl_final(LossArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const double* part = a.ws + 4 + (size_t)a.nblk * 3;
+    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) v[k] += part[(size_t)b * PL_PITCH + k];
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
+        pl_finish<IN>(a, v, norm ? a.ws[1] : 0.0, norm ? sqrt(a.ws[2] / ((double)a.B - 1.0)) : 1.0);
+    }
+}
+
 }  // namespace
 
 // ================================================================================================= host side
@@ -3131,12 +3398,15 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
         __atomic_exchange_n(&e[4], 0, __ATOMIC_RELAXED);
         return set_err(h, PTG_E_INDEX, "ptg_minibatch / ptg_replay_sample: a sample index outside [0, n_steps * n_envs) (of the replay buffer: "
                        "[0, size * n_envs), or a draw from an empty buffer) was passed (NumPy raises IndexError); "
-                       "its output row and column entries were left untouched");
+                       "its output row and column entries were left untouched -- or ptg_policy_loss met an action outside [0, n_actions): "
+                       "that row's gradients were left untouched and the statistics are NaN");
     }
     if (__atomic_load_n(&e[5], __ATOMIC_RELAXED)) {
         __atomic_exchange_n(&e[5], 0, __ATOMIC_RELAXED);
         return set_err(h, PTG_E_NONFINITE, "ptg_act: a row it cannot act on (a NaN or +Inf input, all -Inf logits, a non-finite mean, a NaN or +Inf "
-                       "log_std, or an epsilon outside [0, 1]); such rows got action 0 and NaN log-prob / entropy / raw sample, the others were computed");
+                       "log_std, or an epsilon outside [0, 1]); such rows got action 0 and NaN log-prob / entropy / raw sample, the others were computed "
+                       "-- or ptg_policy_loss: a row with such an input, a non-finite value, advantage, return, old log-prob or old value, an "
+                       "action of probability 0, or a PPO ratio that overflows; such rows got NaN gradients and the statistics are NaN, the other rows' gradients were computed");
     }
     return 0;
 }
@@ -4347,6 +4617,75 @@ int ptg_act(ptg_env* h, const ptg_head* hd, void* stream)
     else hipLaunchKernelGGL(k_act<float>, grid, block, 0, st, a);
     if (!det) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)hd->counter_dev, 1ull);
     return launch_check(h, "k_act");
+}
+
+// ---- the policy loss: PPO / A2C loss, SB3's logged statistics and the gradients w.r.t. the network's outputs --------------
+int64_t ptg_policy_loss_workspace(int64_t batch)
+{
+    if (batch < 1) return PTG_E_INVALID;
+    if (batch > (int64_t)1 << 31) return PTG_E_INVALID;     // 2^23 blocks of 256 threads: half of the 2^32 threads one launch may have
+    const int64_t nblk = (batch - 1) / PL_BLOCK + 1;
+    return (4 + nblk * (3 + PL_PITCH)) * (int64_t)sizeof(double);
+}
+
+int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null descriptor");
+    if (d->kind != PTG_LOSS_PPO && d->kind != PTG_LOSS_A2C) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: unknown kind %d", d->kind);
+    if (d->head != PTG_HEAD_CATEGORICAL && d->head != PTG_HEAD_GAUSSIAN) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: head %d is neither categorical nor Gaussian", d->head);
+    if (d->flags & ~(PTG_LOSS_NORM_ADV | PTG_LOSS_CLIP_VF)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: unknown flag in %d", d->flags);
+    const bool ppo = d->kind == PTG_LOSS_PPO, gauss = d->head == PTG_HEAD_GAUSSIAN, clipv = (d->flags & PTG_LOSS_CLIP_VF) != 0;
+    if (ptg_policy_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (d->in_dtype != PTG_OUT_F32 && d->in_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->in_dev || !d->val_dev || !d->act_dev || !d->adv_dev || !d->ret_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null input, values, actions, advantages or returns");
+    if (ppo && !d->old_logp_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: PPO needs old_logp_dev");
+    if (!d->stats_dev || !d->grad_in_dev || !d->grad_val_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null stats_dev, grad_in_dev or grad_val_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: ws_dev is null or not aligned to 8 bytes");
+    if (clipv && !d->old_val_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: PTG_LOSS_CLIP_VF needs old_val_dev");
+    if (d->val_s_n < 1 || d->gv_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: val_s_n or gv_s_n < 1");
+    if (gauss) {
+        if (d->in_s_n < 1 || d->g_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_s_n or g_s_n < 1");
+        if (!d->log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: the Gaussian head needs log_std_dev");
+    } else {
+        if (d->n_actions < 2 || d->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: n_actions outside [2, 32]");
+        if (d->in_s_n < d->n_actions || d->g_s_n < d->n_actions) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_s_n or g_s_n < n_actions");
+        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: the categorical head takes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (d->grad_log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: grad_log_std_dev is the Gaussian head's");
+    }
+    if (ppo && !(d->clip_range >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: clip_range is negative or NaN");
+    if (clipv && !(d->clip_range_vf >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: clip_range_vf is negative or NaN");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    LossArgs a{};
+    a.in = d->in_dev; a.s_n = (size_t)d->in_s_n; a.val = d->val_dev; a.v_s = (size_t)d->val_s_n;
+    a.act = d->act_dev; a.old_lp = d->old_logp_dev; a.adv = d->adv_dev; a.ret = d->ret_dev; a.old_val = d->old_val_dev; a.log_std = d->log_std_dev;
+    a.g_in = d->grad_in_dev; a.g_s = (size_t)d->g_s_n; a.g_val = d->grad_val_dev; a.gv_s = (size_t)d->gv_s_n; a.g_ls = d->grad_log_std_dev;
+    a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.eps = d->clip_range; a.eps_v = d->clip_range_vf; a.ent_coef = d->ent_coef; a.vf_coef = d->vf_coef;
+    a.B = (size_t)d->batch; a.A = d->n_actions; a.kind = d->kind; a.head = d->head; a.flags = d->flags; a.act_kind = d->act_kind;
+    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.err = h->P.err;
+    const bool f64 = d->in_dtype == PTG_OUT_F64, norm = (d->flags & PTG_LOSS_NORM_ADV) != 0 && d->batch > 1;
+    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
+    if (a.nblk == 1) {                                       // PPO's minibatch: everything in one launch
+        if (f64) hipLaunchKernelGGL((k_pl_rows<double, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pl_rows<float, true>), grid, block, 0, st, a);
+        return launch_check(h, "k_pl_rows");
+    }
+    if (norm) {
+        if (f64) hipLaunchKernelGGL(k_pl_moments<double>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_pl_moments<float>, grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_vn_merge, dim3(1), dim3(64), 0, st, (const double*)(a.ws + 4), a.nblk, a.ws);
+    }
+    if (f64) {
+        hipLaunchKernelGGL((k_pl_rows<double, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_pl_final<double>, dim3(1), block, 0, st, a);
+    } else {
+        hipLaunchKernelGGL((k_pl_rows<float, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_pl_final<float>, dim3(1), block, 0, st, a);
+    }
+    return launch_check(h, "k_pl_rows");
 }
 
 int ptg_profile(ptg_env* h, int enable)

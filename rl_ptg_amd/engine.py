@@ -32,6 +32,8 @@ def _dp(a):
 CategoricalAct = collections.namedtuple("CategoricalAct", "actions log_prob entropy")
 EpsGreedyAct = collections.namedtuple("EpsGreedyAct", "actions")
 GaussianAct = collections.namedtuple("GaussianAct", "actions raw log_prob entropy")
+# what policy_loss returns: stats float64 [8], the gradients w.r.t. the head's input, the values and (Gaussian head) log_std
+PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values grad_log_std")
 
 
 class PtgError(RuntimeError):
@@ -909,6 +911,132 @@ class HipEngine:
         flags = (_lib.HEAD_DETERMINISTIC if deterministic else 0) | (_lib.HEAD_SQUASH if squash else 0)
         head = _lib.PtgHead(kind=_lib.HEAD_GAUSSIAN, flags=flags, in_s_n=max(m1.stride(0), 1), param_dev=log_std.data_ptr(), param_s_n=p_s, clip_lo=lo, clip_hi=hi)
         return self._act_launch(head, m1, counter, seed, res)
+
+    # ------------------------------------------------------------------ the loss of a minibatch and its gradients
+    def policy_loss_workspace(self, batch):
+        """the device scratch of policy_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
+        nbytes = self._L.ptg_policy_loss_workspace(int(batch))
+        if nbytes < 0:
+            raise ValueError(f"policy_loss_workspace: batch must be >= 1, got {batch}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def policy_loss(self, kind, head_input, values, actions, old_log_prob, advantages, returns, *, clip_range=None, clip_range_vf=None,
+                    ent_coef=0.0, vf_coef=0.5, normalize_advantage=None, old_values=None, log_std=None, out=None, workspace=None):
+        """Enqueue, on the current stream, SB3's evaluate_actions and the loss lines of PPO.train (kind "ppo") or A2C.train ("a2c") on
+        one minibatch together with their gradients (include/ptg_env.h: ptg_policy_loss, which states the arithmetic).
+        head_input: logits [B, A] (2 <= A <= 32, unit column stride, row stride >= A: a column slice of an [B, A + 1] actor-critic
+        output is fine) with int32 / int64 actions [B] -- or, with log_std (a 1-element tensor), the Gaussian head's means [B] /
+        [B, 1] with the stored raw samples [B] as actions.  values [B] (any stride >= 1); old_log_prob (PPO; None for A2C),
+        advantages, returns and old_values (required iff clip_range_vf is given) contiguous [B]; every float tensor of ONE dtype,
+        float32 or float64.  clip_range is required for PPO.  normalize_advantage None: SB3's default, True for PPO, False for A2C.
+        Returns PolicyLoss(stats float64 [8] = loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv mean, adv
+        std; grad_input = d loss / d head_input, shaped like it; grad_values [B]; grad_log_std [1] or None).  out: an earlier result
+        (or any such tuple: grad_input and grad_values may be views of one [B, A + 1] tensor), reused by a captured call; workspace:
+        policy_loss_workspace(B) or larger, allocated when missing.  Fresh gradients are torch.empty: a row refused for its action
+        keeps what was there.  No synchronisation; a bad row makes the next sync() raise PtgError (PTG_E_INDEX / PTG_E_NONFINITE)."""
+        torch = self._torch
+        who = "policy_loss"
+        if kind not in ("ppo", "a2c"):
+            raise ValueError(f"{who}: kind must be 'ppo' or 'a2c', got {kind!r}")
+        ppo = kind == "ppo"
+        x = head_input
+        if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{who}: head_input must be a float32 or float64 tensor, got {getattr(x, 'dtype', type(x))}")
+        gauss = log_std is not None
+        dt = x.dtype
+        if gauss:
+            if x.dim() == 2 and x.shape[1] == 1:
+                x = x[:, 0]
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"{who}: with log_std, head_input must be the means [B] or [B, 1], got shape {tuple(head_input.shape)}")
+            B, A = x.shape[0], 0
+            if B > 1 and x.stride(0) < 1:
+                raise ValueError(f"{who}: head_input has stride {x.stride(0)}")
+            s_n = max(x.stride(0), 1)
+            if not torch.is_tensor(log_std) or log_std.dtype != dt or log_std.numel() != 1:
+                raise TypeError(f"{who}: log_std must be a 1-element tensor of {dt}, got {getattr(log_std, 'dtype', type(log_std))} "
+                                f"{tuple(getattr(log_std, 'shape', ()))}")
+        else:
+            if x.dim() != 2 or x.shape[0] < 1 or not 2 <= x.shape[1] <= 32:
+                raise ValueError(f"{who}: head_input must be logits [B, A] with 2 <= A <= 32 (or means [B] with log_std), got shape {tuple(x.shape)}")
+            B, A = x.shape
+            if x.stride(1) != 1 or (B > 1 and x.stride(0) < A):
+                raise ValueError(f"{who}: logits need unit column stride and a row stride >= A, got strides {tuple(x.stride())}")
+            s_n = max(x.stride(0), A)
+        if not torch.is_tensor(actions) or actions.dtype not in ((dt,) if gauss else (torch.int32, torch.int64)):
+            raise TypeError(f"{who}: actions must be {'the raw samples in ' + str(dt) if gauss else 'int32 or int64'}, got {getattr(actions, 'dtype', type(actions))}")
+        if not torch.is_tensor(values) or values.dtype != dt:
+            raise TypeError(f"{who}: values must be a tensor of {dt}, got {getattr(values, 'dtype', type(values))}")
+        if values.dim() == 2 and values.shape[1] == 1:
+            values = values[:, 0]
+        if values.shape != (B,) or (B > 1 and values.stride(0) < 1):
+            raise ValueError(f"{who}: values must be [{B}] with a stride >= 1, got shape {tuple(values.shape)}, strides {tuple(values.stride())}")
+        if clip_range_vf is not None and old_values is None:
+            raise ValueError(f"{who}: clip_range_vf needs old_values")
+        if ppo and old_log_prob is None:
+            raise ValueError(f"{who}: PPO needs old_log_prob")
+        cols = [("actions", actions), ("advantages", advantages), ("returns", returns)]
+        cols += [("old_log_prob", old_log_prob)] if ppo else []
+        cols += [("old_values", old_values)] if clip_range_vf is not None else []
+        for name, c in cols:
+            if not torch.is_tensor(c) or (name != "actions" and c.dtype != dt):
+                raise TypeError(f"{who}: {name} must be a tensor of {dt}, got {getattr(c, 'dtype', type(c))}")
+            if c.shape != (B,) or not c.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous [{B}] tensor, got shape {tuple(c.shape)}, strides {tuple(c.stride())}")
+        for name, c in [("head_input", x), ("values", values)] + cols + ([("log_std", log_std)] if gauss else []):
+            if c.device != self.device:
+                raise ValueError(f"{who}: {name} lives on {c.device}, the engine on {self.device}")
+        if ppo:
+            if clip_range is None or not float(clip_range) >= 0.0:
+                raise ValueError(f"{who}: PPO needs a clip_range >= 0, got {clip_range}")
+        if clip_range_vf is not None and not float(clip_range_vf) >= 0.0:
+            raise ValueError(f"{who}: clip_range_vf must be >= 0 (or None), got {clip_range_vf}")
+        if normalize_advantage is None:
+            normalize_advantage = ppo
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 4:
+                raise ValueError(f"{who}: out must be the PolicyLoss of an earlier call")
+            stats, g_in, g_val, g_ls = out
+        else:
+            with torch.cuda.device(self.device):
+                stats = torch.empty(8, dtype=torch.float64, device=self.device)
+                g_in = torch.empty((B,) if gauss else (B, A), dtype=dt, device=self.device)
+                g_val = torch.empty(B, dtype=dt, device=self.device)
+                g_ls = torch.empty(1, dtype=dt, device=self.device) if gauss else None
+        if gauss and torch.is_tensor(g_in) and g_in.dim() == 2 and g_in.shape[1] == 1:
+            g_in = g_in[:, 0]
+        for name, t, shape, tdt in (("stats", stats, (8,), torch.float64), ("grad_input", g_in, (B,) if gauss else (B, A), dt), ("grad_values", g_val, (B,), dt)) + \
+                ((("grad_log_std", g_ls, (1,), dt),) if gauss else ()):
+            if not torch.is_tensor(t) or t.shape != shape or t.dtype != tdt or t.device != self.device:
+                raise ValueError(f"{who}: out.{name} must be a {list(shape)} tensor of {tdt} on {self.device}, got "
+                                 f"{tuple(getattr(t, 'shape', ()))} of {getattr(t, 'dtype', type(t))}")
+        if not gauss and g_ls is not None:
+            raise ValueError(f"{who}: out.grad_log_std given, but the categorical head has no log_std")
+        if not stats.is_contiguous() or (not gauss and g_in.stride(1) != 1) or (B > 1 and (g_in.stride(0) < max(A, 1) or g_val.stride(0) < 1)):
+            raise ValueError(f"{who}: out.stats must be contiguous, out.grad_input needs unit column stride and a row stride >= A, out.grad_values a "
+                             f"stride >= 1; got strides {tuple(stats.stride())}, {tuple(g_in.stride())}, {tuple(g_val.stride())}")
+        if workspace is not None:
+            if not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != self.device:
+                raise ValueError(f"{who}: workspace must be a contiguous uint8 tensor on {self.device} (policy_loss_workspace({B}))")
+            if workspace.numel() < self._L.ptg_policy_loss_workspace(B):
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_policy_loss_workspace(B)}")
+        else:
+            workspace = self.policy_loss_workspace(B)
+        d = _lib.PtgLoss(kind=_lib.LOSS_PPO if ppo else _lib.LOSS_A2C, head=_lib.HEAD_GAUSSIAN if gauss else _lib.HEAD_CATEGORICAL,
+                         flags=(_lib.LOSS_NORM_ADV if normalize_advantage else 0) | (_lib.LOSS_CLIP_VF if clip_range_vf is not None else 0),
+                         n_actions=A, in_dtype=_lib.OUT_F64 if dt == torch.float64 else _lib.OUT_F32,
+                         act_kind=_lib.ACT_I64 if actions.dtype == torch.int64 else _lib.ACT_I32, batch=B,
+                         in_dev=x.data_ptr(), in_s_n=s_n, val_dev=values.data_ptr(), val_s_n=max(values.stride(0), 1), act_dev=actions.data_ptr(),
+                         old_logp_dev=old_log_prob.data_ptr() if ppo else None, adv_dev=advantages.data_ptr(), ret_dev=returns.data_ptr(),
+                         old_val_dev=old_values.data_ptr() if clip_range_vf is not None else None, log_std_dev=log_std.data_ptr() if gauss else None,
+                         clip_range=float(clip_range) if ppo else 0.0, clip_range_vf=float(clip_range_vf) if clip_range_vf is not None else 0.0,
+                         ent_coef=float(ent_coef), vf_coef=float(vf_coef), stats_dev=stats.data_ptr(), grad_in_dev=g_in.data_ptr(),
+                         g_s_n=max(g_in.stride(0), A, 1), grad_val_dev=g_val.data_ptr(), gv_s_n=max(g_val.stride(0), 1),
+                         grad_log_std_dev=g_ls.data_ptr() if gauss else None, ws_dev=workspace.data_ptr())
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_policy_loss(self._h, C.byref(d), self._stream()))
+        return PolicyLoss(stats, g_in, g_val, g_ls)
 
     def market_feature_series(self):
         """The pre-normalised float32 feature series the kernels read, each [n_sets, length]: dict(featA, featB (hourly), gas_n, eua_n

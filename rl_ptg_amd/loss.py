@@ -1,0 +1,58 @@
+"""ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd.
+
+    out = net(obs)                                            # [B, A + 1]: logits and a value column
+    loss, stats = ppo_loss(engine, out[:, :A], out[:, A], actions, old_log_prob, advantages, returns, clip_range=0.2)
+    loss.backward()                                           # drives the network exactly as SB3's loss.backward() does
+
+Forward launches the kernel, which computes the loss, SB3's logged statistics and d loss / d logits (or means), d loss / d values
+and d loss / d log_std in one pass; backward hands those to autograd, scaled by the incoming gradient.  Nothing else of the call is
+differentiable: actions, old log-probs, advantages, returns and old values are data, as they are in SB3.  Without out= the gradient
+tensors are allocated zeroed, so a row the kernel leaves untouched (an action out of range, reported at the next sync) adds nothing
+to the network's gradients; with out= the caller's tensors are used as they are and must not be reused before backward has run.  There is no torch
+fall-back: without the library or a GPU the engine does not exist."""
+import torch
+
+
+class _PolicyLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, kind, head_input, values, log_std, actions, old_log_prob, advantages, returns, old_values, kw):
+        if kw.get("out") is None:                            # fresh gradients are zeroed here: a row refused for its action (PTG_E_INDEX at the next
+            dev, dt = head_input.device, head_input.dtype    # sync) then contributes nothing to the network's gradients instead of uninitialised memory
+            kw = dict(kw, out=(torch.empty(8, dtype=torch.float64, device=dev), torch.zeros(head_input.shape, dtype=dt, device=dev),
+                               torch.zeros(values.shape[0], dtype=dt, device=dev), None if log_std is None else torch.zeros(1, dtype=dt, device=dev)))
+        res = engine.policy_loss(kind, head_input.detach(), values.detach(), actions, old_log_prob, advantages, returns, old_values=old_values,
+                                 log_std=None if log_std is None else log_std.detach(), **kw)
+        ctx.res = res
+        ctx.shapes = (head_input.shape, values.shape, None if log_std is None else log_std.shape)
+        stats = res.stats
+        ctx.mark_non_differentiable(stats)
+        return res.stats[0].to(head_input.dtype, copy=True), stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        res, (s_in, s_val, s_ls) = ctx.res, ctx.shapes
+        g_ls = None if s_ls is None else (res.grad_log_std * grad_loss).reshape(s_ls)
+        return (None, None, (res.grad_input * grad_loss).reshape(s_in), (res.grad_values * grad_loss).reshape(s_val), g_ls,
+                None, None, None, None, None, None)
+
+
+def _call(kind, engine, head_input, values, actions, old_log_prob, advantages, returns, old_values, log_std, kw):
+    return _PolicyLossFn.apply(engine, kind, head_input, values, log_std, actions, old_log_prob, advantages, returns, old_values, kw)
+
+
+def ppo_loss(engine, head_input, values, actions, old_log_prob, advantages, returns, *, clip_range, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5,
+             normalize_advantage=True, old_values=None, log_std=None, out=None, workspace=None):
+    """SB3's PPO.train loss of one minibatch -> (loss, stats): loss a 0-dim tensor in head_input's dtype that carries the graph,
+    stats float64 [8] = loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv mean, adv std (read stats[4]
+    for target_kl).  head_input: logits [B, A] with integer actions, or the Gaussian head's means with log_std (a 1-element
+    parameter) and the stored raw samples as actions.  Arguments as HipEngine.policy_loss."""
+    kw = dict(clip_range=clip_range, clip_range_vf=clip_range_vf, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage,
+              out=out, workspace=workspace)
+    return _call("ppo", engine, head_input, values, actions, old_log_prob, advantages, returns, old_values, log_std, kw)
+
+
+def a2c_loss(engine, head_input, values, actions, advantages, returns, *, ent_coef=0.0, vf_coef=0.5, normalize_advantage=False, log_std=None,
+             out=None, workspace=None):
+    """SB3's A2C.train loss of its one batch -> (loss, stats) as ppo_loss gives them (approx_kl and clip_fraction are 0)."""
+    kw = dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, out=out, workspace=workspace)
+    return _call("a2c", engine, head_input, values, actions, None, advantages, returns, None, log_std, kw)
