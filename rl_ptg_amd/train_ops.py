@@ -1,0 +1,581 @@
+"""TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
+action heads and the policy loss.  Each method checks its tensors, marshals pointers and strides and makes one library call
+(include/ptg_env.h states the arithmetic); none of them steps the environment.  HipEngine inherits them.
+
+The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
+_action_kind; torch stays lazily imported (torch = self._torch).
+
+Every tensor argument goes through ONE checker, check(), which raises in a fixed order: TypeError for what the value is (not a
+tensor, a refused dtype, element size or element count), then ValueError for its shape, its strides, its device.  Nothing touches
+the library and no device memory is allocated before every check of a call has passed.  Relations between arguments (old_values
+iff clip_range_vf, done_col inside the columns ...) stay plain `if`s in the methods."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+# what the action heads return: device tensors [N]; a field that was not asked for (or that the head does not have) is None
+CategoricalAct = collections.namedtuple("CategoricalAct", "actions log_prob entropy")
+EpsGreedyAct = collections.namedtuple("EpsGreedyAct", "actions")
+GaussianAct = collections.namedtuple("GaussianAct", "actions raw log_prob entropy")
+# what policy_loss returns: stats float64 [8], the gradients w.r.t. the head's input, the values and (Gaussian head) log_std
+PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values grad_log_std")
+
+
+# ------------------------------------------------------------------ stride rules: None when x obeys, else what was expected
+def contiguous(x):
+    return None if x.is_contiguous() else "a contiguous tensor"
+
+
+def rows(x):
+    """[B, A] logits, possibly a column slice of a wider tensor"""
+    return None if x.stride(1) == 1 and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1]) else "unit column stride and a row stride >= A"
+
+
+def step(x):
+    """[B] values, possibly a column of a wider tensor"""
+    return None if x.shape[0] <= 1 or x.stride(0) >= 1 else "a stride >= 1"
+
+
+def one_or_all(n):
+    """a parameter shared by the batch (1 element) or one per row (contiguous [n], [n, 1] or [1, n])"""
+    return lambda x: None if x.numel() == 1 or (x.numel() == n and x.dim() <= 2 and x.is_contiguous()) else f"1 element or a contiguous [{n}] tensor"
+
+
+def non_negative(x):
+    return None if min(x.stride()) >= 0 else "non-negative strides"
+
+
+def strides_of(ref, dims):
+    """the last `dims` strides of ref, none of them negative"""
+    want = tuple(ref.stride())[-dims:]
+    return lambda x: None if tuple(x.stride())[-dims:] == want and min(x.stride()) >= 0 else f"the non-negative strides {want}"
+
+
+def check(eng, who, name, x, dtypes=None, sizes=None, numel=None, shape=None, rule=None, optional=False, exc=TypeError):
+    """The one argument check of the training ops: x must be a tensor with one of `dtypes` or of `sizes` bytes per element and, for the
+    scalar-like arguments (counter, cursor, eps, log_std), `numel` elements -- else `exc`, TypeError for inputs and ValueError for
+    outputs, whose dtype is set by the inputs; then of `shape` (None entries: any size), obeying the stride `rule`, on the engine's
+    device -- else ValueError.  optional: None passes.  Returns x."""
+    if x is None and optional:
+        return None
+    if not eng._torch.is_tensor(x):
+        raise exc(f"{who}: {name} must be a tensor, got {type(x).__name__}")
+    if dtypes is not None and x.dtype not in dtypes:
+        raise exc(f"{who}: {name} must be of {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
+    if sizes is not None and x.element_size() not in sizes:
+        raise exc(f"{who}: {name} must have {'-, '.join(str(s) for s in sizes)}-byte elements, got {x.dtype}")
+    if numel is not None and x.numel() != numel:
+        raise exc(f"{who}: {name} must have {numel} element(s), got shape {tuple(x.shape)}")
+    if shape is not None:
+        got = x.shape
+        ok = len(got) == len(shape)
+        for s, g in zip(shape, got):
+            ok = ok and (s is None or s == g)
+        if not ok:
+            raise ValueError(f"{who}: {name} must be {['*' if s is None else s for s in shape]}, got shape {tuple(got)}")
+    bad = rule(x) if rule is not None else None
+    if bad:
+        raise ValueError(f"{who}: {name} needs {bad}, got shape {tuple(x.shape)}, strides {tuple(x.stride())}")
+    if x.device != eng.device:
+        raise ValueError(f"{who}: {name} lives on {x.device}, the engine on {eng.device}")
+    return x
+
+
+def _dims(eng, x):
+    """x.dim(); -1 for what is not a tensor, which check() then refuses"""
+    return x.dim() if eng._torch.is_tensor(x) else -1
+
+
+def _ptr(x):
+    """device pointer or NULL of a tensor; of a list of tensors, the pointer array the library takes for a column list"""
+    if isinstance(x, (list, tuple)):
+        return (C.c_void_p * max(len(x), 1))(*[None if t is None else t.data_ptr() for t in x])
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
+def _out_code(torch, dtype):
+    return _lib.OUT_F64 if dtype == torch.float64 else _lib.OUT_F32
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+class TrainOps:
+    # ------------------------------------------------------------------ VecNormalize(norm_obs=False) on the device
+    def vn_init(self, gamma=0.99, epsilon=1e-8, clip_reward=10.0):
+        """Start reward normalisation as the reference wraps its envs (src/rl_utils.py:453, SB3 defaults)."""
+        self._chk(self._L.ptg_vn_init(self._h, float(gamma), float(epsilon), float(clip_reward)))
+        self._vn_hyper = {"gamma": float(gamma), "epsilon": float(epsilon), "clip_reward": float(clip_reward)}
+
+    def vn_normalize(self, rew, done, training=True, out=None, group=None):
+        """Normalise a [T, N] (or [N]) reward tensor in place of VecNormalize.step_wait: advances the discounted returns,
+        updates the running moments step by step (training=True) and returns the clipped, scaled rewards.  With an
+        initialised torch.distributed process group the per-step moments of all ranks' envs are merged first (one
+        all-gather per call), so every rank holds the statistics of the whole job."""
+        torch = self._torch
+        from . import dist as ptg_dist
+        who = "vn_normalize"
+        one = _dims(self, rew) == 1
+        shape = (self.n,) if one else (None, self.n)
+        check(self, who, "rew", rew, dtypes=(self.out_dtype,), shape=shape, rule=contiguous)      # what the kernels read
+        check(self, who, "done", done, sizes=(1,), shape=rew.shape, rule=contiguous)
+        check(self, who, "out", out, dtypes=(self.out_dtype,), shape=rew.shape, rule=contiguous, optional=True)
+        r2, d2 = (rew.unsqueeze(0), done.unsqueeze(0)) if one else (rew, done)
+        T = r2.shape[0]
+        res = torch.empty_like(r2) if out is None else (out.unsqueeze(0) if one else out)
+        with torch.cuda.device(self.device):
+            mom = None
+            if training:
+                mom = torch.empty((T, 3), dtype=torch.float64, device=self.device)
+                self._chk(self._L.ptg_vn_batch_moments(self._h, _ptr(r2), _ptr(d2), T, _ptr(mom), self._stream()))
+                mom = ptg_dist.all_merge_moments(mom, group=group)
+            self._chk(self._L.ptg_vn_apply(self._h, _ptr(r2), T, _ptr(mom), _ptr(res), 1 if training else 0, self._stream()))
+            if not training:                                # frozen statistics: returns[done] = 0 all the same (SB3 step_wait)
+                self._chk(self._L.ptg_vn_clear_done(self._h, _ptr(d2), T, self._stream()))
+        return res[0] if one else res
+
+    def vn_get(self):
+        st, ret = np.zeros(3), np.zeros(self.n)
+        self._chk(self._L.ptg_vn_get(self._h, _dp(st), _dp(ret)))
+        return dict(mean=st[0], var=st[1], count=st[2]), ret
+
+    def vn_set(self, stats=None, returns=None):
+        st = None if stats is None else np.array([stats["mean"], stats["var"], stats["count"]], dtype=np.float64)
+        rt = None if returns is None else np.ascontiguousarray(returns, dtype=np.float64)
+        self._chk(self._L.ptg_vn_set(self._h, None if st is None else _dp(st), None if rt is None else _dp(rt)))
+
+    # ------------------------------------------------------------------ RolloutBuffer.compute_returns_and_advantage on the device
+    def gae(self, rew, values, done, last_values, gamma, gae_lambda, adv=None, ret=None):
+        """Enqueue, on the current stream, the advantages and returns of a rollout in place of SB3's
+        RolloutBuffer.compute_returns_and_advantage (include/ptg_env.h: ptg_gae): rew, values [T, N] (or [N] for T = 1) and
+        last_values [N] of ONE float dtype (float32 or float64, whatever the engine's out_dtype), done [T, N] of a 1-byte dtype with
+        rollout()'s meaning (done[t] != 0: the episode ended on step t), values[t] = V of the observation step t's action was chosen
+        from, last_values = V of the observation after step T - 1.  Returns (adv, ret), allocated when not given; adv may be rew and
+        ret may be values.  No synchronisation; bit for bit what NumPy computes with SB3's lines on arrays of that dtype."""
+        torch = self._torch
+        who = "gae"
+        one = _dims(self, rew) == 1
+        up = lambda x: x.unsqueeze(0) if one and _dims(self, x) == 1 else x
+        r2 = check(self, who, "rew", up(rew), dtypes=(torch.float32, torch.float64), shape=(None, self.n), rule=contiguous)
+        T, dt = r2.shape[0], (r2.dtype,)
+        v2 = check(self, who, "values", up(values), dtypes=dt, shape=(T, self.n), rule=contiguous)
+        d2 = check(self, who, "done", up(done), sizes=(1,), shape=(T, self.n), rule=contiguous)
+        check(self, who, "last_values", last_values, dtypes=dt, shape=(self.n,), rule=contiguous)
+        a2 = check(self, who, "adv", up(adv), dtypes=dt, shape=(T, self.n), rule=contiguous, optional=True, exc=ValueError)
+        t2 = check(self, who, "ret", up(ret), dtypes=dt, shape=(T, self.n), rule=contiguous, optional=True, exc=ValueError)
+        a2 = torch.empty_like(r2) if a2 is None else a2
+        t2 = torch.empty_like(r2) if t2 is None else t2
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_gae(self._h, _ptr(r2), _ptr(v2), _ptr(d2), _ptr(last_values), T, _out_code(torch, r2.dtype),
+                                      float(gamma), float(gae_lambda), _ptr(a2), _ptr(t2), self._stream()))
+        return (a2[0], t2[0]) if one else (a2, t2)
+
+    # ------------------------------------------------------------------ RolloutBuffer.get on the device
+    def minibatch(self, idx, obs=None, columns=(), obs_out=None, columns_out=None):
+        """Enqueue, on the current stream, the gather of ONE minibatch in place of SB3's RolloutBuffer._get_samples
+        (include/ptg_env.h: ptg_minibatch): idx [B] int32 / int64 sample indices in swap_and_flatten's order, i = env * T + step,
+        0 <= i < T * N (slices of a torch.randperm(T * N)); obs a rollout's observation buffer as alloc_obs(T) / rollout() make it
+        ([T, N, F], or [T, F, N] feature-major with the engine's pitch); columns up to 8 contiguous [T, N] tensors of 1-, 2-, 4- or
+        8-byte elements (actions, values, log-probs, advantages, returns, done flags ...).  Returns (obs_out [B, F] or None,
+        [column outputs [B]]), allocated when not given; row b is source row (idx[b] % T, idx[b] // T), byte for byte.  Outputs must
+        not overlap inputs (not checked).  No synchronisation; an index out of range leaves its row untouched and makes the next
+        sync() raise PtgError with code PTG_E_INDEX."""
+        torch = self._torch
+        who = "minibatch"
+        columns = list(columns)
+        check(self, who, "idx", idx, dtypes=(torch.int32, torch.int64), shape=(None,), rule=contiguous)
+        if obs is None and not columns:
+            raise ValueError("minibatch: neither observations nor columns given")
+        if len(columns) > _lib.MB_MAX_COLS:
+            raise ValueError(f"minibatch: at most {_lib.MB_MAX_COLS} columns, got {len(columns)}")
+        B = idx.shape[0]
+        T, F, s_t, s_n, s_f = None, 0, 0, 0, 0
+        if obs is not None:                                 # a [T, ...] buffer of alloc_obs(T)
+            check(self, who, "obs", obs, sizes=(4, 8), shape=(None, self.obs_dim, self.n) if self.feature_major else (None, self.n, self.obs_dim),
+                  rule=self._check_obs)
+            T, F = obs.shape[0], self.obs_dim
+            s_t, (s_n, s_f) = obs.stride(0), ((obs.stride(2), obs.stride(1)) if self.feature_major else (obs.stride(1), obs.stride(2)))
+        for c, x in enumerate(columns):                     # without observations the first column sets T
+            T = check(self, who, f"column {c}", x, sizes=(1, 2, 4, 8), shape=(T, self.n), rule=contiguous).shape[0]
+        if columns_out is not None and len(columns_out) != len(columns):
+            raise ValueError(f"minibatch: {len(columns)} columns but {len(columns_out)} column outputs")
+        if obs is None and obs_out is not None:
+            raise ValueError("minibatch: obs_out given without obs")
+        if obs is not None:
+            check(self, who, "obs_out", obs_out, dtypes=(obs.dtype,), shape=(B, F), rule=contiguous, optional=True, exc=ValueError)
+        for c, (x, o) in enumerate(zip(columns, columns_out or ())):
+            check(self, who, f"output of column {c}", o, dtypes=(x.dtype,), shape=(B,), rule=contiguous, exc=ValueError)
+        with torch.cuda.device(self.device):
+            if obs is not None and obs_out is None:
+                obs_out = torch.empty((B, F), dtype=obs.dtype, device=self.device)
+            outs = [torch.empty((B,), dtype=x.dtype, device=self.device) for x in columns] if columns_out is None else list(columns_out)
+            k = len(columns)
+            size = (C.c_int32 * max(k, 1))(*[x.element_size() for x in columns])
+            self._chk(self._L.ptg_minibatch(self._h, _ptr(idx), idx.element_size(), B, T, _ptr(obs), s_t, s_n, s_f, F,
+                                            obs.element_size() if obs is not None else 0, _ptr(obs_out),
+                                            k, _ptr(columns), size, _ptr(outs), self._stream()))
+        return obs_out, outs
+
+    def minibatches(self, perm, batch_size, obs=None, columns=()):
+        """SB3's RolloutBuffer.get loop: yields minibatch(perm[start : start + batch_size], obs, columns) for start = 0, batch_size,
+        ... -- the last slice short when batch_size does not divide len(perm); batch_size None: one batch of all of perm (A2C).
+        perm: a permutation of T * N on the device, e.g. torch.randperm(T * N, device=...).  Every yield has fresh outputs."""
+        total = perm.shape[0]
+        if batch_size is None:
+            batch_size = total
+        if int(batch_size) < 1:
+            raise ValueError(f"minibatches: batch_size must be >= 1 or None, got {batch_size}")
+        start = 0
+        while start < total:
+            yield self.minibatch(perm[start:start + int(batch_size)], obs, columns)
+            start += int(batch_size)
+
+    # ------------------------------------------------------------------ ReplayBuffer.add / sample on the device
+    def _replay_desc(self, st, who):
+        """the ptg_replay descriptor of a storage object (rl_ptg_amd.replay.ReplayStorage: obs_ring, next_ring [S, N, F], col_rings
+        [S, N] each, cursor uint64-as-int64 [2]), its tensors checked"""
+        torch = self._torch
+        o, nx, cols, cur = st.obs_ring, st.next_ring, list(st.col_rings), st.cursor
+        check(self, who, "obs_ring", o, sizes=(4, 8), shape=(None, self.n, None), rule=contiguous)
+        if o.shape[0] < 1 or o.shape[2] < 1:
+            raise ValueError(f"{who}: obs_ring must be [S, {self.n}, F], got shape {tuple(o.shape)}")
+        check(self, who, "next_ring", nx, dtypes=(o.dtype,), shape=o.shape, rule=contiguous, exc=ValueError)
+        if len(cols) > _lib.MB_MAX_COLS:
+            raise ValueError(f"{who}: at most {_lib.MB_MAX_COLS} column rings, got {len(cols)}")
+        for c, x in enumerate(cols):
+            check(self, who, f"column ring {c}", x, sizes=(1, 2, 4, 8), shape=o.shape[:2], rule=contiguous)
+        check(self, who, "cursor", cur, dtypes=(torch.int64,), numel=2, shape=(2,), rule=contiguous)
+        d = _lib.PtgReplay()
+        d.capacity, d.obs_dim, d.obs_bytes = o.shape[0], o.shape[2], o.element_size()
+        d.obs_ring, d.next_ring, d.n_cols, d.cursor_dev = _ptr(o), _ptr(nx), len(cols), _ptr(cur)
+        for c, x in enumerate(cols):
+            d.col_bytes[c], d.col_ring[c] = x.element_size(), x.data_ptr()
+        return d
+
+    def replay_add(self, storage, prev_obs, obs, columns=(), done=None, final_obs=None, done_col=-1):
+        """Enqueue, on the current stream, SB3's ReplayBuffer.add for a window of T vector steps (include/ptg_env.h: ptg_replay_add).
+        obs is the ROW VIEW [T, N, F] of the window's observations -- rows(buffer) for a feature-major engine; any non-negative
+        strides -- prev_obs [N, F] the observation the first action was chosen from and final_obs (optional, [T, N, F]) the terminal
+        observations, both with obs's strides; columns one contiguous [T, N] tensor per column ring, of the ring's dtype (None at
+        done_col, which is written as float32 0 / 1 from done); done [T, N] of a 1-byte dtype.  Step t goes to slot
+        (cursor[0] + t) % S; the cursor advances on the device.  No synchronisation."""
+        torch = self._torch
+        who = "replay_add"
+        d = self._replay_desc(storage, who)
+        columns = list(columns)
+        S, F, ring_dt = storage.obs_ring.shape[0], storage.obs_ring.shape[2], (storage.obs_ring.dtype,)
+        check(self, who, "obs", obs, dtypes=ring_dt, shape=(None, self.n, F), rule=non_negative)
+        T = obs.shape[0]
+        if T < 1 or T > S:
+            raise ValueError(f"replay_add: a window of {T} steps does not fit a buffer of {S} rows (1 <= T <= S)")
+        check(self, who, "prev_obs", prev_obs, dtypes=ring_dt, shape=(self.n, F), rule=strides_of(obs, 2))
+        check(self, who, "final_obs", final_obs, dtypes=ring_dt, shape=obs.shape, rule=strides_of(obs, 2 if T == 1 else 3), optional=True)
+        if len(columns) != len(storage.col_rings):
+            raise ValueError(f"replay_add: {len(storage.col_rings)} column rings but {len(columns)} columns")
+        if not -1 <= done_col < len(columns):
+            raise ValueError(f"replay_add: done_col {done_col} outside [-1, {len(columns)})")
+        if done_col >= 0 and storage.col_rings[done_col].dtype != torch.float32:
+            raise TypeError(f"replay_add: the done column ring must be float32, got {storage.col_rings[done_col].dtype}")
+        if (done_col >= 0 or final_obs is not None) and done is None:
+            raise ValueError("replay_add: final_obs and a done column need done")
+        for c, x in enumerate(columns):
+            if c == done_col:
+                continue
+            if x is None:
+                raise ValueError(f"replay_add: column {c} is missing (None stands for the done column only)")
+            check(self, who, f"column {c}", x, dtypes=(storage.col_rings[c].dtype,), shape=(T, self.n), rule=contiguous)
+        check(self, who, "done", done, sizes=(1,), shape=(T, self.n), rule=contiguous, optional=True)
+        src = _ptr([None if c == done_col else x for c, x in enumerate(columns)])
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_replay_add(self._h, C.byref(d), _ptr(prev_obs), _ptr(obs), obs.stride(0), obs.stride(1), obs.stride(2),
+                                             _ptr(final_obs), _ptr(done), done_col, len(columns), src, T, self._stream()))
+
+    def replay_sample(self, storage, batch_size=None, idx=None, seed=0, want_obs=True, want_next=True, want_cols=None, norm_col=-1,
+                      want_idx=False, out=None):
+        """Enqueue, on the current stream, SB3's ReplayBuffer.sample / _get_samples (include/ptg_env.h: ptg_replay_sample): a gather
+        at the flat indices idx (int64 [B], i = slot * N + env) or, with idx None, at batch_size indices drawn on the device from
+        (seed, cursor[1], row).  Returns (obs [B, F] | None, next_obs [B, F] | None, [column outputs [B] | None], idx_out [B] | None);
+        want_cols: a bool per column ring (None: all); norm_col: the reward column, normalised as vn_normalize(training=False)
+        would; out: the same 4-tuple of preallocated outputs (for a captured call).  No synchronisation; an index out of range, or a
+        draw from an empty buffer, leaves its row untouched and makes the next sync() raise PtgError with code PTG_E_INDEX."""
+        torch = self._torch
+        who = "replay_sample"
+        d = self._replay_desc(storage, who)
+        k = len(storage.col_rings)
+        F, ring_dt = storage.obs_ring.shape[2], storage.obs_ring.dtype
+        if idx is not None:
+            check(self, who, "idx", idx, dtypes=(torch.int64,), shape=(None,), rule=contiguous)
+            if batch_size is not None and int(batch_size) != idx.shape[0]:
+                raise ValueError(f"replay_sample: batch_size {batch_size} but {idx.shape[0]} indices")
+            B = idx.shape[0]
+        else:
+            if batch_size is None:
+                raise ValueError("replay_sample: neither idx nor batch_size given")
+            B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"replay_sample: an empty batch ({B} rows)")
+        if not -1 <= norm_col < k:
+            raise ValueError(f"replay_sample: norm_col {norm_col} outside [-1, {k})")
+        want_cols = [True] * k if want_cols is None else [bool(w) for w in want_cols]
+        if len(want_cols) != k:
+            raise ValueError(f"replay_sample: {k} column rings but {len(want_cols)} entries in want_cols")
+        wanted = (want_obs, want_next, want_cols, want_idx)
+        if out is not None:
+            o0, o1, outs, io = out
+            outs = list(outs)
+            if len(outs) != k:
+                raise ValueError(f"replay_sample: {k} column rings but {len(outs)} column outputs")
+            check(self, who, "obs output", o0, dtypes=(ring_dt,), shape=(B, F), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "next_obs output", o1, dtypes=(ring_dt,), shape=(B, F), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "idx output", io, dtypes=(torch.int64,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            for c, (o, x) in enumerate(zip(outs, storage.col_rings)):
+                check(self, who, f"output of column {c}", o, dtypes=(x.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            wanted = (o0 is not None, o1 is not None, [o is not None for o in outs], io is not None)
+        if not (wanted[0] or wanted[1] or any(wanted[2]) or wanted[3]):
+            raise ValueError("replay_sample: no output asked for")
+        if norm_col >= 0 and not wanted[2][norm_col]:
+            raise ValueError("replay_sample: norm_col names a column without an output")
+        if norm_col >= 0 and storage.col_rings[norm_col].dtype != self.out_dtype:
+            raise TypeError(f"replay_sample: the reward column is {storage.col_rings[norm_col].dtype}, the engine normalises {self.out_dtype}")
+        with torch.cuda.device(self.device):
+            if out is None:
+                mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+                o0, o1 = mk((B, F), ring_dt) if want_obs else None, mk((B, F), ring_dt) if want_next else None
+                outs = [mk((B,), x.dtype) if w else None for x, w in zip(storage.col_rings, want_cols)]
+                io = mk((B,), torch.int64) if want_idx else None
+            self._chk(self._L.ptg_replay_sample(self._h, C.byref(d), _ptr(idx), B, int(seed) & (2 ** 64 - 1), _ptr(o0), _ptr(o1), _ptr(outs),
+                                                norm_col, _ptr(io), self._stream()))
+        return o0, o1, outs, io
+
+    # ------------------------------------------------------------------ the action head while collecting
+    def new_draw_counter(self):
+        """The zeroed device counter of the action heads' draws: uint64 [1], held as an int64 tensor.  A stochastic act_* call advances
+        it by one on the device, so a replayed graph draws afresh; checkpoint it with int(counter)."""
+        return self._torch.zeros(1, dtype=self._torch.int64, device=self.device)
+
+    def _act_counter(self, who, counter, deterministic):
+        if counter is None and not deterministic:
+            raise ValueError(f"{who}: a stochastic head needs a draw counter (new_draw_counter())")
+        return check(self, who, "counter (new_draw_counter())", counter, dtypes=(self._torch.int64,), numel=1, shape=(1,), optional=True)
+
+    def _act_outputs(self, who, kind, out, specs):
+        """the output tensors of a head: out's (checked) or fresh ones; specs = [(field, wanted, dtype)] in the namedtuple's order"""
+        torch = self._torch
+        if out is not None and (not isinstance(out, tuple) or len(out) != len(specs)):
+            raise ValueError(f"{who}: out must be the {kind.__name__} of an earlier call")
+        res = []
+        for k, (name, wanted, dt) in enumerate(specs):
+            x = None if out is None else out[k]
+            if x is not None and not wanted:
+                raise ValueError(f"{who}: out.{name} given, but the head has no such output or it was not asked for")
+            if out is not None and x is None and name == "actions":
+                raise ValueError(f"{who}: out.actions is missing")
+            res.append(check(self, who, f"out.{name}", x, dtypes=(dt,), shape=(self.n,), rule=contiguous, optional=True, exc=ValueError))
+        if out is None:                                     # fresh outputs, once every given one has passed
+            with torch.cuda.device(self.device):
+                res = [torch.empty(self.n, dtype=dt, device=self.device) if wanted else None for _, wanted, dt in specs]
+        return kind(*res)
+
+    def _act_input(self, who, x, name, discrete):
+        """logits / Q-values [N, A] with unit column stride and a row stride >= A (a slice of a wider output), or means [N] / [N, 1]"""
+        torch = self._torch
+        floats = (torch.float32, torch.float64)
+        if discrete:
+            check(self, who, name, x, dtypes=floats, shape=(self.n, None), rule=rows)
+            if not 2 <= x.shape[1] <= 32:
+                raise ValueError(f"{who}: {name} must be [{self.n}, A] with 2 <= A <= 32, got shape {tuple(x.shape)}")
+            return x.shape[1], max(x.stride(0), x.shape[1])
+        if _dims(self, x) == 2 and x.shape[1] == 1:                         # [N, 1]: the env's Box has one dimension
+            x = x[:, 0]
+        check(self, who, name, x, dtypes=floats, shape=(self.n,), rule=step)
+        return 1, max(x.stride(0), 1)
+
+    def _act_dtype(self, who, act_dtype, out):
+        """the discrete heads' action dtype: the caller's, else that of out.actions, else int32"""
+        torch = self._torch
+        if act_dtype is None and isinstance(out, tuple) and out and torch.is_tensor(out[0]):
+            act_dtype = out[0].dtype
+        act_dtype = torch.int32 if act_dtype is None else act_dtype
+        if act_dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{who}: act_dtype must be torch.int32 or torch.int64, got {act_dtype}")
+        return act_dtype
+
+    def _act_launch(self, head, x, counter, seed, res):
+        torch = self._torch
+        head.in_dtype = _out_code(torch, x.dtype)
+        head.in_dev, head.seed, head.counter_dev = _ptr(x), int(seed) & (2 ** 64 - 1), _ptr(counter)
+        head.act_dev, head.logp_dev, head.ent_dev = _ptr(res.actions), _ptr(getattr(res, "log_prob", None)), _ptr(getattr(res, "entropy", None))
+        head.raw_dev = _ptr(getattr(res, "raw", None))
+        head.act_kind = self._action_kind(res.actions)
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_act(self._h, C.byref(head), self._stream()))
+        return res
+
+    def act_categorical(self, logits, counter, seed=0, deterministic=False, out=None, want_logp=True, want_entropy=True, act_dtype=None):
+        """Enqueue, on the current stream, SB3's CategoricalDistribution.sample (deterministic: mode), log_prob and entropy of the
+        logits [N, A] (float32 / float64, 2 <= A <= 32, a column slice of a wider tensor is fine) in ONE launch (include/ptg_env.h:
+        ptg_act, which states the arithmetic).  act_dtype None: the dtype of out.actions when out is given, else torch.int32 (torch is
+        imported lazily here, so the default is spelled None).  counter: new_draw_counter(); row e of the c-th call draws from (seed, c, global env
+        offset + e).  Returns CategoricalAct(actions [N] of act_dtype (torch.int32, the default, or int64: what step() takes), log_prob
+        [N], entropy [N] in the logits' dtype, or None when not wanted); out: an earlier call's result, reused (a captured call).
+        No synchronisation; a row with a NaN or +Inf logit, or -Inf in every column, gets action 0 and NaN outputs and makes the next
+        sync() raise PtgError with code PTG_E_NONFINITE."""
+        who = "act_categorical"
+        A, s_n = self._act_input(who, logits, "logits", True)
+        counter = self._act_counter(who, counter, deterministic)
+        res = self._act_outputs(who, CategoricalAct, out, [("actions", True, self._act_dtype(who, act_dtype, out)), ("log_prob", want_logp, logits.dtype),
+                                                           ("entropy", want_entropy, logits.dtype)])
+        head = _lib.PtgHead(kind=_lib.HEAD_CATEGORICAL, flags=_lib.HEAD_DETERMINISTIC if deterministic else 0, n_actions=A, in_s_n=s_n)
+        return self._act_launch(head, logits, counter, seed, res)
+
+    def act_eps_greedy(self, q, eps, counter, seed=0, deterministic=False, out=None, act_dtype=None):
+        """DQN's collecting policy in one launch: with probability eps a uniform random action, else the first maximal Q-value of
+        q [N, A]; deterministic: always the latter (eps is not read).  eps: a float64 device tensor of 1 element, read when the kernel
+        runs (anneal it in place between replays), or a Python float, written to a fresh device scalar by a fill kernel ahead of the head
+        on the same stream -- a captured call then keeps that value on every replay.
+        Returns EpsGreedyAct(actions).  A row with a NaN or +Inf value, and every row when eps is NaN or outside [0, 1], gets action 0
+        and makes the next sync() raise PtgError with code PTG_E_NONFINITE."""
+        torch = self._torch
+        who = "act_eps_greedy"
+        A, s_n = self._act_input(who, q, "q", True)
+        counter = self._act_counter(who, counter, deterministic)
+        if torch.is_tensor(eps):
+            check(self, who, "a tensor eps", eps, dtypes=(torch.float64,), numel=1)
+        elif eps is None:
+            if not deterministic:
+                raise ValueError(f"{who}: a stochastic call needs eps")
+        else:
+            eps = float(eps)                                  # written to the device below, once every check has passed
+        res = self._act_outputs(who, EpsGreedyAct, out, [("actions", True, self._act_dtype(who, act_dtype, out))])
+        if isinstance(eps, float):                            # a fill kernel on the current stream, not a host copy: it can be captured, and
+            with torch.cuda.device(self.device):              # a replay then writes the same value into the graph's own memory
+                eps = torch.full((1,), eps, dtype=torch.float64, device=self.device)
+        head = _lib.PtgHead(kind=_lib.HEAD_EPS_GREEDY, flags=_lib.HEAD_DETERMINISTIC if deterministic else 0, n_actions=A, in_s_n=s_n,
+                            param_dev=_ptr(eps))
+        return self._act_launch(head, q, counter, seed, res)
+
+    def act_gaussian(self, mean, log_std, counter, clip=(-1.0, 1.0), squash=False, seed=0, deterministic=False, out=None, want_raw=True,
+                     want_logp=True, want_entropy=None):
+        """The Gaussian heads in one launch: g = mean + exp(log_std) * z, z a Box-Muller normal (deterministic: z = 0).  Plain
+        (TD3 with log_std = log(sigma_exp); continuous A2C / PPO): actions = clip(g), log_prob and entropy of N(mean, sigma);
+        squash=True (SAC / TQC): actions = clip(tanh(g)), log_prob with SB3's tanh correction, no entropy.  mean [N] (or [N, 1]),
+        log_std of mean's dtype: 1 element (state-independent) or [N]; both may be rewritten between replays.  Returns
+        GaussianAct(actions float32 [N] for step(), raw = g unclipped and unsquashed (what an on-policy buffer stores), log_prob,
+        entropy).  A non-finite mean or a NaN / +Inf log_std gives action 0, NaN outputs and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "act_gaussian"
+        _, s_n = self._act_input(who, mean, "mean", False)
+        m1 = mean[:, 0] if mean.dim() == 2 else mean
+        check(self, who, "log_std", log_std, dtypes=(mean.dtype,), rule=one_or_all(self.n))
+        lo, hi = float(clip[0]), float(clip[1])
+        if not lo <= hi:
+            raise ValueError(f"{who}: clip {clip} is not an interval")
+        if want_entropy is None:
+            want_entropy = not squash
+        if squash and want_entropy:
+            raise ValueError(f"{who}: a squashed Gaussian has no closed-form entropy")
+        counter = self._act_counter(who, counter, deterministic)
+        res = self._act_outputs(who, GaussianAct, out, [("actions", True, torch.float32), ("raw", want_raw, mean.dtype), ("log_prob", want_logp, mean.dtype),
+                                                        ("entropy", want_entropy, mean.dtype)])
+        flags = (_lib.HEAD_DETERMINISTIC if deterministic else 0) | (_lib.HEAD_SQUASH if squash else 0)
+        head = _lib.PtgHead(kind=_lib.HEAD_GAUSSIAN, flags=flags, in_s_n=s_n, param_dev=_ptr(log_std), param_s_n=0 if log_std.numel() == 1 else 1,
+                            clip_lo=lo, clip_hi=hi)
+        return self._act_launch(head, m1, counter, seed, res)
+
+    # ------------------------------------------------------------------ the loss of a minibatch and its gradients
+    def policy_loss_workspace(self, batch):
+        """the device scratch of policy_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
+        nbytes = self._L.ptg_policy_loss_workspace(int(batch))
+        if nbytes < 0:
+            raise ValueError(f"policy_loss_workspace: batch must be >= 1, got {batch}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def policy_loss(self, kind, head_input, values, actions, old_log_prob, advantages, returns, *, clip_range=None, clip_range_vf=None,
+                    ent_coef=0.0, vf_coef=0.5, normalize_advantage=None, old_values=None, log_std=None, out=None, workspace=None):
+        """Enqueue, on the current stream, SB3's evaluate_actions and the loss lines of PPO.train (kind "ppo") or A2C.train ("a2c") on
+        one minibatch together with their gradients (include/ptg_env.h: ptg_policy_loss, which states the arithmetic).
+        head_input: logits [B, A] (2 <= A <= 32, unit column stride, row stride >= A: a column slice of an [B, A + 1] actor-critic
+        output is fine) with int32 / int64 actions [B] -- or, with log_std (a 1-element tensor), the Gaussian head's means [B] /
+        [B, 1] with the stored raw samples [B] as actions.  values [B] (any stride >= 1); old_log_prob (PPO; None for A2C),
+        advantages, returns and old_values (required iff clip_range_vf is given) contiguous [B]; every float tensor of ONE dtype,
+        float32 or float64.  clip_range is required for PPO.  normalize_advantage None: SB3's default, True for PPO, False for A2C.
+        Returns PolicyLoss(stats float64 [8] = loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv mean, adv
+        std; grad_input = d loss / d head_input, shaped like it; grad_values [B]; grad_log_std [1] or None).  out: an earlier result
+        (or any such tuple: grad_input and grad_values may be views of one [B, A + 1] tensor), reused by a captured call; workspace:
+        policy_loss_workspace(B) or larger, allocated when missing.  Fresh gradients are torch.empty: a row refused for its action
+        keeps what was there.  No synchronisation; a bad row makes the next sync() raise PtgError (PTG_E_INDEX / PTG_E_NONFINITE)."""
+        torch = self._torch
+        who = "policy_loss"
+        if kind not in ("ppo", "a2c"):
+            raise ValueError(f"{who}: kind must be 'ppo' or 'a2c', got {kind!r}")
+        ppo, gauss = kind == "ppo", log_std is not None
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
+        if gauss:                                           # the means [B] or [B, 1]
+            x = check(self, who, "head_input (the means, with log_std)", column(head_input), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
+            (B,), A = x.shape, 0
+        else:
+            x = check(self, who, "head_input (logits; or means with log_std)", head_input, dtypes=(torch.float32, torch.float64), shape=(None, None), rule=rows)
+            B, A = x.shape
+            if not 2 <= A <= 32:
+                raise ValueError(f"{who}: head_input must be logits [B, A] with 2 <= A <= 32 (or means [B] with log_std), got shape {tuple(x.shape)}")
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch, head_input has shape {tuple(head_input.shape)}")
+        dt = (x.dtype,)
+        check(self, who, "log_std", log_std, dtypes=dt, numel=1, optional=True)
+        values = check(self, who, "values", column(values), dtypes=dt, shape=(B,), rule=step)
+        if clip_range_vf is not None and old_values is None:
+            raise ValueError(f"{who}: clip_range_vf needs old_values")
+        if ppo and old_log_prob is None:
+            raise ValueError(f"{who}: PPO needs old_log_prob")
+        check(self, who, "actions (the raw samples)" if gauss else "actions", actions, dtypes=dt if gauss else (torch.int32, torch.int64), shape=(B,), rule=contiguous)
+        cols = [("advantages", advantages), ("returns", returns)] + ([("old_log_prob", old_log_prob)] if ppo else [])
+        for name, c in cols + ([("old_values", old_values)] if clip_range_vf is not None else []):
+            check(self, who, name, c, dtypes=dt, shape=(B,), rule=contiguous)
+        if ppo:
+            if clip_range is None or not float(clip_range) >= 0.0:
+                raise ValueError(f"{who}: PPO needs a clip_range >= 0, got {clip_range}")
+        if clip_range_vf is not None and not float(clip_range_vf) >= 0.0:
+            raise ValueError(f"{who}: clip_range_vf must be >= 0 (or None), got {clip_range_vf}")
+        if normalize_advantage is None:
+            normalize_advantage = ppo
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 4:
+                raise ValueError(f"{who}: out must be the PolicyLoss of an earlier call")
+            stats, g_in, g_val, g_ls = out
+            if not gauss and g_ls is not None:
+                raise ValueError(f"{who}: out.grad_log_std given, but the categorical head has no log_std")
+            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            g_in = check(self, who, "out.grad_input", column(g_in) if gauss else g_in, dtypes=dt, shape=x.shape, rule=step if gauss else rows, exc=ValueError)
+            check(self, who, "out.grad_values", g_val, dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            if gauss:
+                check(self, who, "out.grad_log_std", g_ls, dtypes=dt, shape=(1,), exc=ValueError)
+        if workspace is not None:
+            check(self, who, f"workspace (policy_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
+            if workspace.numel() < self._L.ptg_policy_loss_workspace(B):
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_policy_loss_workspace(B)}")
+        else:
+            workspace = self.policy_loss_workspace(B)
+        if out is None:
+            with torch.cuda.device(self.device):
+                stats = torch.empty(8, dtype=torch.float64, device=self.device)
+                g_in = torch.empty(tuple(x.shape), dtype=x.dtype, device=self.device)
+                g_val = torch.empty(B, dtype=x.dtype, device=self.device)
+                g_ls = torch.empty(1, dtype=x.dtype, device=self.device) if gauss else None
+        d = _lib.PtgLoss(kind=_lib.LOSS_PPO if ppo else _lib.LOSS_A2C, head=_lib.HEAD_GAUSSIAN if gauss else _lib.HEAD_CATEGORICAL,
+                         flags=(_lib.LOSS_NORM_ADV if normalize_advantage else 0) | (_lib.LOSS_CLIP_VF if clip_range_vf is not None else 0),
+                         n_actions=A, in_dtype=_out_code(torch, x.dtype), act_kind=_lib.ACT_I64 if actions.dtype == torch.int64 else _lib.ACT_I32,
+                         batch=B, in_dev=_ptr(x), in_s_n=max(x.stride(0), A, 1), val_dev=_ptr(values), val_s_n=max(values.stride(0), 1),
+                         act_dev=_ptr(actions), old_logp_dev=_ptr(old_log_prob if ppo else None), adv_dev=_ptr(advantages), ret_dev=_ptr(returns),
+                         old_val_dev=_ptr(old_values if clip_range_vf is not None else None), log_std_dev=_ptr(log_std),
+                         clip_range=float(clip_range) if ppo else 0.0, clip_range_vf=float(clip_range_vf) if clip_range_vf is not None else 0.0,
+                         ent_coef=float(ent_coef), vf_coef=float(vf_coef), stats_dev=_ptr(stats), grad_in_dev=_ptr(g_in),
+                         g_s_n=max(g_in.stride(0), A, 1), grad_val_dev=_ptr(g_val), gv_s_n=max(g_val.stride(0), 1),
+                         grad_log_std_dev=_ptr(g_ls if gauss else None), ws_dev=_ptr(workspace))
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_policy_loss(self._h, C.byref(d), self._stream()))
+        return PolicyLoss(stats, g_in, g_val, g_ls)

@@ -1,5 +1,6 @@
 """Shared fixture loading for the parity tests (test infrastructure; may import the oracle)."""
 import atexit
+import contextlib
 import glob
 import json
 import os
@@ -248,3 +249,49 @@ def toggler_tape(rng, K, n, warm):
         cur = np.where(flip, np.where(toggle & (cur >= 3), 7 - cur, rng.integers(0, 5, n)), cur)
         a[t] = cur
     return a
+
+
+# ------------------------------------------------------------------------------------------------ engine shells on the CPU
+def host_engine(n, **attrs):
+    """a HipEngine shell on the CPU: enough for the Python argument checks of the training ops, which run before anything touches the
+    library (the tests assert `eng._L is None` after every refusal)"""
+    import torch
+    from rl_ptg_amd.engine import HipEngine
+    eng = HipEngine.__new__(HipEngine)
+    eng._torch, eng.n, eng.device, eng._h, eng._L = torch, n, torch.device("cpu"), None, None
+    eng.out_dtype, eng.obs_dim, eng.feature_major, eng.pitch = torch.float32, 3, False, n
+    for k, v in attrs.items():
+        setattr(eng, k, v)
+    return eng
+
+
+class RecordingLib:
+    """stands in for the loaded library: every attribute is a function that stores (name, args) in `calls` and returns 0 --
+    ptg_policy_loss_workspace returns the size the library computes (32 bytes + 88 per block of 256 rows, < 0 for a batch < 1)"""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def f(*args):
+            self.calls.append((name, args))
+            if name == "ptg_policy_loss_workspace":
+                return 32 + 88 * ((args[0] + 255) // 256) if args[0] >= 1 else -1
+            return 0
+        return f
+
+
+class CpuTorch:
+    """torch, except that cuda.device(...) is a null context"""
+
+    class cuda:
+        device = staticmethod(lambda *a, **kw: contextlib.nullcontext())
+
+    def __getattr__(self, name):
+        import torch
+        return getattr(torch, name)
+
+
+def recording_engine(n, **attrs):
+    """host_engine whose accepted calls run on CPU tensors up to the library call, which a RecordingLib keeps in eng._L.calls"""
+    return host_engine(n, _h="H", _L=RecordingLib(), _torch=CpuTorch(), _stream=lambda: None, **attrs)

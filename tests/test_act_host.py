@@ -195,18 +195,10 @@ def test_the_entry_point_refuses_a_null_handle_and_the_error_code_is_minus_six()
     assert (_lib.HEAD_CATEGORICAL, _lib.HEAD_EPS_GREEDY, _lib.HEAD_GAUSSIAN, _lib.HEAD_DETERMINISTIC, _lib.HEAD_SQUASH) == (0, 1, 2, 1, 2)
 
 
-def _host_engine(n):
-    """a HipEngine shell on the CPU: enough for the argument checks, which run before anything touches the library"""
-    import torch
-    from rl_ptg_amd.engine import HipEngine
-    eng = HipEngine.__new__(HipEngine)
-    eng._torch, eng.n, eng.device, eng._h, eng._L = torch, n, torch.device("cpu"), None, None
-    return eng
-
-
 def test_python_argument_checks_need_no_device():
     import torch
-    eng = _host_engine(6)
+    from helpers import host_engine
+    eng = host_engine(6)
     x, cnt = torch.zeros(6, 5), torch.zeros(1, dtype=torch.int64)
     mean, ls = torch.zeros(6), torch.zeros(1)
     other = torch.device("meta")

@@ -172,18 +172,10 @@ def test_the_workspace_size_and_the_null_handle():
     assert L.ptg_policy_loss(None, C.byref(_lib.PtgLoss()), None) == _lib.E_INVALID
 
 
-def _host_engine():
-    """a HipEngine shell on the CPU: enough for the argument checks, which run before anything touches the library"""
-    import torch
-    from rl_ptg_amd.engine import HipEngine
-    eng = HipEngine.__new__(HipEngine)
-    eng._torch, eng.n, eng.device, eng._h, eng._L = torch, 4, torch.device("cpu"), None, None
-    return eng
-
-
 def test_python_argument_checks_need_no_device():
     import torch
-    eng = _host_engine()
+    from helpers import host_engine
+    eng = host_engine(4)
     B, A = 6, 5
     x, v, act = torch.zeros(B, A), torch.zeros(B), torch.zeros(B, dtype=torch.int64)
     col = torch.zeros(B)

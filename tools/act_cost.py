@@ -24,6 +24,7 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import cost_timing  # noqa: E402
 
 NS = [6, 4096, 65536]
 A = 5
@@ -42,26 +43,9 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     spec, _ = synthetic_spec(scenario=1, operation="OP1", eps_len_d=32)          # tools/policy_loop.py's engine
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    def timed(fn):
-        torch.cuda._sleep(200000)                             # ~100 us of device time: the host runs ahead of the first event
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3
-
-    def stats(v):
-        return f"{statistics.median(v):8.1f} [{min(v):6.1f} - {max(v):6.1f}]"
-
-    def alternate(fa, fb):
-        ta, tb = [], []
-        for rep in range(args.warmup + args.reps):
-            a, b = timed(fa), timed(fb)
-            if rep >= args.warmup:
-                ta.append(a); tb.append(b)
-        return ta, tb
+    stats = lambda v: cost_timing.stats(v, width=8)
+    alternate = lambda fa, fb: cost_timing.alternate(fa, fb, args.warmup, args.reps)
 
     def engine(n):
         eng = HipEngine(spec.consts, spec.tables, spec.markets, n, device=0, out_dtype="float32", obs_layout="sb3_flat")

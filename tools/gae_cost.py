@@ -20,6 +20,7 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_timing import stats, timed  # noqa: E402
 
 SHAPES = [(658, 6), (658, 4096), (20, 65536), (658, 65536)]
 GAMMA, LAMBDA = 0.9393, 0.9819          # the reference's A2C pair (config/config_agent.yaml)
@@ -54,15 +55,6 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     spec, _ = synthetic_spec(scenario=2, operation="OP2", eps_len_d=32)          # 4 608-step episodes: no boundary inside a window
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        torch.cuda._sleep(200000)                             # ~100 us of device time: the host runs ahead of the first event
-        e0.record()
-        out = fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3, out
 
     print(f"# tools/gae_cost.py: float32, gamma {GAMMA}, gae_lambda {LAMBDA}; {args.reps} repetitions after {args.warmup} warm-up, variants "
           f"alternating; device time from HIP events [us]: median [min - max]")
@@ -106,7 +98,7 @@ def main():
         same = torch.equal(adv, adv_t) and torch.equal(ret, ret_t)
         nbytes = T * n * 17 + 4 * n
         med = {k: statistics.median(v) for k, v in times.items()}
-        fmt = lambda k: f"{med[k]:9.1f} [{min(times[k]):7.1f} - {max(times[k]):7.1f}]"
+        fmt = lambda k: stats(times[k])
         gbs = nbytes / (med["gae"] * 1e-6) / 1e9
         print(f"{T:4d} {n:6d}  {fmt('gae'):>26s}  {fmt('torch'):>32s}  {fmt('rollout'):>29s}  {nbytes:11d} {gbs:7.1f} {gbs * 1e9 / HBM_PEAK:9.3f} "
               f"{med['torch'] / med['gae']:9.1f} {med['gae'] / med['rollout']:11.3f}   # torch loop bit-equal: {same}")

@@ -23,6 +23,8 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import cost_timing  # noqa: E402
+from cost_timing import stats  # noqa: E402
 
 BS = [203, 4096, 20 * 65536]
 A = 5
@@ -44,31 +46,13 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     spec, _ = synthetic_spec(scenario=1, operation="OP1", eps_len_d=32)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     lines = []
 
     def say(s):
         print(s, flush=True)
         lines.append(s)
 
-    def timed(fn):
-        torch.cuda._sleep(200000)                             # ~100 us of device time: the host runs ahead of the first event
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3
-
-    def stats(v):
-        return f"{statistics.median(v):9.1f} [{min(v):7.1f} - {max(v):7.1f}]"
-
-    def alternate(fa, fb):
-        ta, tb = [], []
-        for rep in range(args.warmup + args.reps):
-            a, b = timed(fa), timed(fb)
-            if rep >= args.warmup:
-                ta.append(a); tb.append(b)
-        return ta, tb
+    alternate = lambda fa, fb: cost_timing.alternate(fa, fb, args.warmup, args.reps)
 
     eng = HipEngine(spec.consts, spec.tables, spec.markets, 6, device=0, out_dtype="float32", obs_layout="sb3_flat")      # the reference's 6 envs; B is not tied to it
     first_ptr, stride = ptg_dist.episode_plan(6, 1, 0)

@@ -22,6 +22,7 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_timing import stats, timed  # noqa: E402
 
 SHAPES = [(658, 6, 203), (658, 4096, 203), (20, 65536, 65536), (658, 65536, 65536)]
 HBM_PEAK = 8.0e12
@@ -38,15 +39,6 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     spec, _ = synthetic_spec(scenario=2, operation="OP2", eps_len_d=32)          # 4 608-step episodes: no boundary inside a window
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        torch.cuda._sleep(200000)                             # ~100 us of device time: the host runs ahead of the first event
-        e0.record()
-        out = fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3, out
 
     print(f"# tools/minibatch_cost.py: float32 SB3_FLAT rows (160 B), 5 float32 columns + int32 actions, int64 indices; {args.reps} repetitions "
           f"after {args.warmup} warm-up, variants alternating; device time from HIP events [us]: median [min - max]")
@@ -88,7 +80,7 @@ def main():
         assert same, "the torch route and ptg_minibatch disagree"
         nbytes = B * (2 * F * 4 + 8 + 2 * 4 * len(cols))
         med = {k: statistics.median(v) for k, v in times.items()}
-        fmt = lambda k: f"{med[k]:9.1f} [{min(times[k]):7.1f} - {max(times[k]):7.1f}]"
+        fmt = lambda k: stats(times[k])
         gbs = nbytes / (med["mb"] * 1e-6) / 1e9
         gbs_c = B * 2 * F * 4 / (med["copy"] * 1e-6) / 1e9
         print(f"{T:4d} {n:6d} {B:6d}  {fmt('mb'):>26s}  {fmt('torch'):>29s}  {fmt('copy'):>26s}  {nbytes:10d} {gbs:7.1f} {gbs * 1e9 / HBM_PEAK:9.4f} "

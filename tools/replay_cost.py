@@ -24,6 +24,7 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cost_timing import stats, timed  # noqa: E402
 
 ADD_SHAPES = [(6, 1), (6, 20), (65536, 1), (65536, 20)]      # (N, T)
 SAMPLE_SHAPES = [(6, 544), (6, 257), (6, 470), (6, 290), (6, 65536), (65536, 544), (65536, 65536)]      # (N, B)
@@ -42,18 +43,6 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     spec, _ = synthetic_spec(scenario=2, operation="OP2", eps_len_d=32)          # 4 608-step episodes: no boundary inside a window
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        torch.cuda._sleep(200000)                             # ~100 us of device time: the host runs ahead of the first event
-        e0.record()
-        out = fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3, out
-
-    def stats(v):
-        return f"{statistics.median(v):9.1f} [{min(v):7.1f} - {max(v):7.1f}]"
 
     print(f"# tools/replay_cost.py: float32 SB3_FLAT rows (160 B), int32 actions, float32 rewards and dones; {args.reps} repetitions after "
           f"{args.warmup} warm-up, variants alternating; device time from HIP events [us]: median [min - max]")
