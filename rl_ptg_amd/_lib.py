@@ -6,11 +6,13 @@ import subprocess
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
-SRC = os.path.join(PKG, "csrc", "ptg_env.hip")
+CSRC = os.path.join(PKG, "csrc")
+SRC = os.path.join(CSRC, "ptg_env.hip")                # the environment: N_PARTS translation units of the parallel build
+SRC_TRAIN = os.path.join(CSRC, "ptg_train.hip")        # the training ops: one translation unit
 HDR = os.path.join(ROOT, "include", "ptg_env.h")
 LIB_PATH = os.environ.get("PTG_LIB_PATH") or os.path.join(PKG, "lib", "libptg_env.so")      # PTG_LIB_PATH: an experiment build of the same source
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
-N_PARTS = 9          # translation units of the parallel build: -DPTG_PART=0..8 (ptg_env.hip, "PTG_PART")
+N_PARTS = 9          # translation units of ptg_env.hip in the parallel build: -DPTG_PART=0..8 (ptg_env.hip, "PTG_PART")
 
 N_TABLES, N_INFO = 17, 24
 ACT_I32, ACT_F32, ACT_I64 = 0, 1, 2
@@ -95,22 +97,24 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
 def build(force=False, verbose=False):
     """hipcc cross-compiles the extension for gfx950 in-tree (no GPU needed to build)."""
     os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
-    newest = max(os.path.getmtime(SRC), os.path.getmtime(HDR))
+    newest = max([os.path.getmtime(HDR)] + [os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC)])
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    jobs = int(os.environ.get("PTG_BUILD_JOBS", "0")) or min(N_PARTS, os.cpu_count() or 1)
-    if jobs <= 1:                                             # one translation unit: the whole file in one hipcc call
-        cmd = [hipcc] + HIPCC_FLAGS + ["-shared", "-o", LIB_PATH, SRC]
+    jobs = int(os.environ.get("PTG_BUILD_JOBS", "0")) or min(N_PARTS + 1, os.cpu_count() or 1)
+    if jobs <= 1:                                             # both files whole (no PTG_PART) in one hipcc call
+        cmd = [hipcc] + HIPCC_FLAGS + ["-shared", "-o", LIB_PATH, SRC, SRC_TRAIN]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
         return LIB_PATH
-    # the same source compiled N_PARTS times, each time with a different share of the hot-kernel instantiations, `jobs` at a time
+    # ptg_env.hip compiled N_PARTS times, each time with a different share of the hot-kernel instantiations, and ptg_train.hip once,
+    # `jobs` at a time
     obj_dir = os.path.join(os.path.dirname(LIB_PATH), "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    objs = [os.path.join(obj_dir, f"ptg_env_part{k}.o") for k in range(N_PARTS)]
+    objs = [os.path.join(obj_dir, f"ptg_env_part{k}.o") for k in range(N_PARTS)] + [os.path.join(obj_dir, "ptg_train.o")]
     cmds = [[hipcc] + HIPCC_FLAGS + ["-Wno-unused-function", f"-DPTG_PART={k}", "-c", "-o", objs[k], SRC] for k in range(N_PARTS)]
+    cmds.append([hipcc] + HIPCC_FLAGS + ["-c", "-o", objs[N_PARTS], SRC_TRAIN])
     running, todo, failed = [], list(enumerate(cmds)), []
     while todo or running:
         while todo and len(running) < jobs:
@@ -122,7 +126,7 @@ def build(force=False, verbose=False):
         if proc.wait() != 0:
             failed.append(k)
     if failed:
-        raise RuntimeError(f"hipcc failed on part(s) {failed} of {SRC}")
+        raise RuntimeError(f"hipcc failed on {[os.path.basename(objs[k]) for k in failed]} ({SRC}, {SRC_TRAIN})")
     link = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB_PATH] + objs
     if verbose:
         print(" ".join(link))

@@ -1,0 +1,1271 @@
+// ptg_train.hip -- the training-side operations of include/ptg_env.h (rl_ptg_amd/train_ops.py): HIP kernels + C ABI.  They read
+// and write the caller's rollout buffers and step no environment; of a handle they use n, device, cfg.out_dtype, P.err, P.env_offset
+// and the vn_* members (ptg_handle.h).  One translation unit of its own beside the parts of ptg_env.hip.
+//
+// What replaces what:
+//   k_vn_*            VecNormalize(norm_obs=False) reward normalisation over the [T][N] rewards.
+//   k_gae             SB3's RolloutBuffer.compute_returns_and_advantage (GAE) over the [T][N] rewards, values and done flags.
+//   k_minibatch       SB3's RolloutBuffer.get / _get_samples: one shuffled minibatch gathered from the [T][N] buffers of a rollout.
+//   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
+//   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
+//   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
+// Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
+#include "ptg_handle.h"
+
+#include <cmath>
+
+namespace {
+
+// ================================================================================== VecNormalize reward normalisation
+// stable-baselines3 2.0.0a13 (the reference's pin, requirements.txt:5; un-vendored), vec_env/vec_normalize.py + running_mean_std.py,
+// as the reference uses it: VecNormalize(env, norm_obs=False) (src/rl_utils.py:453).  Per vector step:
+//   returns = returns * gamma + reward;  ret_rms.update(returns)   [batch mean / population variance over the envs, merged into
+//   the running moments];  reward_out = clip(reward / sqrt(ret_rms.var + epsilon), +-clip_reward);  returns[done] = 0.
+// Over a [T][N] reward matrix that is: a per-env recurrence with per-step moments over the envs (k_vn_moments, k_vn_merge), a
+// T-step scalar scan of the running moments (k_vn_scan) and an elementwise pass (k_vn_norm).  Moments travel as
+// (count, mean, M2) and are merged with Chan's formula -- across waves here, across GPUs in rl_ptg_amd/dist.py.
+__device__ __forceinline__ void chan_merge(double& ca, double& ma, double& Ma, double cb, double mb, double Mb)
+{
+    if (cb == 0.0) return;
+    if (ca == 0.0) { ca = cb; ma = mb; Ma = Mb; return; }
+    const double tot = ca + cb, delta = mb - ma;
+    ma = ma + delta * cb / tot;
+    Ma = Ma + Mb + delta * delta * ca * cb / tot;
+    ca = tot;
+}
+
+// Per-env recurrence + per-step moments of every wave (one wave per workgroup).  Cross-lane reductions per step would
+// dominate (a float64 butterfly is 12 dependent ds_bpermute or DPP stages: measured 0.33-0.46 us per step at one wave per SIMD),
+// so the work is transposed instead: for 64 steps at a time lane e runs the recurrence of ITS env and parks the 64 returns in
+// an LDS tile [step][env]; then lane t sums row t -- the moments of step t over the wave's envs -- in a private loop (two
+// passes: mean, then squared deviations) and writes that step's partial.  No cross-lane instruction at all.
+template <typename OUT>
+__global__ void __launch_bounds__(64)
+k_vn_moments(const OUT* __restrict__ rew, const uint8_t* __restrict__ done, int N, int T, double gamma, double* __restrict__ returns,
+             double* __restrict__ partials, int nW)
+{
+    constexpr int TS = 64, PITCH = 65;                      // 65: row t starts 2 banks after row t-1
+    __shared__ double tile[TS * PITCH];
+    const int lane = threadIdx.x, w = blockIdx.x;           // w = wave index = workgroup index
+    const int e_raw = w * 64 + lane;
+    const bool live = e_raw < N;
+    const int e = live ? e_raw : N - 1;
+    const int n_live = min(64, N - w * 64);
+    double ret = live ? returns[e] : 0.0;
+    for (int t0 = 0; t0 < T; t0 += TS) {
+        const int nt = min(TS, T - t0);
+        for (int tb = 0; tb < nt; tb += 8) {                // recurrence, loads batched eight steps at a time
+            OUT r[8]; uint8_t d[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const size_t g = (size_t)(t0 + min(tb + j, nt - 1)) * N + e;
+                r[j] = rew[g]; d[j] = done[g];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                if (tb + j < nt) {
+                    ret = ret * gamma + (double)r[j];       // _update_reward
+                    tile[(tb + j) * PITCH + lane] = ret;
+                    ret = d[j] ? 0.0 : ret;                 // self.returns[dones] = 0
+                }
+            }
+        }
+        __syncthreads();
+        if (lane < nt) {                                    // lane t: moments of step t0 + t over this wave's envs
+            const double* row = tile + lane * PITCH;
+            double s = 0.0;
+            for (int q = 0; q < n_live; q++) s += row[q];
+            const double mean = s / (double)n_live;         // np.mean
+            double m2 = 0.0;
+            for (int q = 0; q < n_live; q++) { const double dv = row[q] - mean; m2 += dv * dv; }
+            double* p = partials + ((size_t)(t0 + lane) * nW + w) * 3;
+            p[0] = (double)n_live; p[1] = mean; p[2] = m2;
+        }
+        __syncthreads();
+    }
+    if (live) returns[e] = ret;
+}
+
+__global__ void __launch_bounds__(64)
+k_vn_merge(const double* __restrict__ partials, int nW, double* __restrict__ moments)
+{
+    const int t = blockIdx.x, lane = threadIdx.x;
+    double c = 0.0, m = 0.0, M = 0.0;
+    for (int w = lane; w < nW; w += 64) {
+        const double* p = partials + ((size_t)t * nW + w) * 3;
+        chan_merge(c, m, M, p[0], p[1], p[2]);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double cb = __shfl_xor(c, off, 64), mb = __shfl_xor(m, off, 64), Mb = __shfl_xor(M, off, 64);
+        // both partners must end with the same value: merge in a fixed (lower lane first) order
+        double ca = c, ma = m, Ma = M;
+        if (lane & off) { double tc = cb, tm = mb, tM = Mb; chan_merge(tc, tm, tM, ca, ma, Ma); c = tc; m = tm; M = tM; }
+        else { chan_merge(ca, ma, Ma, cb, mb, Mb); c = ca; m = ma; M = Ma; }
+    }
+    if (lane == 0) { moments[t * 3 + 0] = c; moments[t * 3 + 1] = m; moments[t * 3 + 2] = M; }
+}
+
+// RunningMeanStd.update_from_moments over the T steps of a launch; den[t] = sqrt(var + epsilon) AFTER the update of step t
+// (step_wait updates before it normalises).  update_from_moments IS Chan's merge of (count, mean, var * count), which is
+// associative: one wave runs it as a prefix scan (per-lane chunks of the steps, a 6-stage scan of the lane totals, then the
+// chunks again) -- a chain of ~2 T / 64 + 6 merges instead of T, each a float64 division.  training == 0: frozen statistics.
+__global__ void __launch_bounds__(64)
+k_vn_scan(const double* __restrict__ moments, int T, int training, double epsilon, double* __restrict__ stats, double* __restrict__ den)
+{
+    const int lane = threadIdx.x;
+    const double mean0 = stats[0], var0 = stats[1], count0 = stats[2];
+    const int chunk = (T + 63) / 64, t_lo = min(T, lane * chunk), t_hi = min(T, t_lo + chunk);
+    if (!training) {
+        for (int t = t_lo; t < t_hi; t++) den[t] = sqrt(var0 + epsilon);
+        return;
+    }
+    double c = 0.0, m = 0.0, M = 0.0;                       // this lane's chunk, merged
+    for (int t = t_lo; t < t_hi; t++) chan_merge(c, m, M, moments[t * 3 + 0], moments[t * 3 + 1], moments[t * 3 + 2]);
+    double ic = c, im = m, iM = M;                          // inclusive scan over the lanes (earlier steps first)
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        double pc = __shfl_up(ic, off, 64), pm = __shfl_up(im, off, 64), pM = __shfl_up(iM, off, 64);
+        if (lane >= off) { chan_merge(pc, pm, pM, ic, im, iM); ic = pc; im = pm; iM = pM; }
+    }
+    double rc = __shfl_up(ic, 1, 64), rm = __shfl_up(im, 1, 64), rM = __shfl_up(iM, 1, 64);      // exclusive prefix
+    if (lane == 0) { rc = 0.0; rm = 0.0; rM = 0.0; }
+    double qc = count0, qm = mean0, qM = var0 * count0;     // running moments before this lane's first step
+    chan_merge(qc, qm, qM, rc, rm, rM);
+    for (int t = t_lo; t < t_hi; t++) {
+        chan_merge(qc, qm, qM, moments[t * 3 + 0], moments[t * 3 + 1], moments[t * 3 + 2]);
+        den[t] = sqrt(qM / qc + epsilon);
+    }
+    if (lane == 63) { stats[0] = qm; stats[1] = qM / qc; stats[2] = qc; }      // lane 63's prefix + chunk = all T steps
+}
+
+template <typename OUT>
+__global__ void __launch_bounds__(256)
+k_vn_norm(const OUT* __restrict__ rew, OUT* __restrict__ out, const double* __restrict__ den, int N, size_t total, double clip)
+{
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const double v = (double)rew[g] / den[g / (size_t)N];
+    const double lo = v < -clip ? -clip : v;                // np.clip: compare-selects that fall through to v, so a NaN stays
+    out[g] = (OUT)(lo > clip ? clip : lo);                  // NaN (fmax(NaN, x) would be x)
+}
+
+// Frozen statistics (training == 0): the returns are not advanced, only returns[done] = 0 after every step -- so over a T-step
+// window an env's return is zeroed iff any of its T done flags is set.
+__global__ void __launch_bounds__(256)
+k_vn_clear_done(const uint8_t* __restrict__ done, int N, int T, double* __restrict__ returns)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= N) return;
+    bool any = false;
+    for (int t = 0; t < T; t++) any |= done[(size_t)t * N + e] != 0;
+    if (any) returns[e] = 0.0;
+}
+
+// ================================================================================== generalised advantage estimation
+// stable-baselines3 2.0.0a13, common/buffers.py RolloutBuffer.compute_returns_and_advantage, as the reference's A2C and PPO run it
+// after every collect (config/config_agent.yaml: gamma / gae_lambda / n_steps).  With done[t] = episode_starts[t + 1] (and the
+// method's `dones` argument = done[T - 1]) the loop over `step` backwards is, in the arrays' own precision F:
+//   nnt = 1 - done[t];  nv = t == T - 1 ? last_val : val[t + 1]
+//   delta = rew[t] + gamma * nv * nnt - val[t];  last = delta + gamma * gae_lambda * nnt * last;  adv[t] = last;  ret[t] = last + val[t]
+// evaluated left to right as Python does: (g * nv) * nnt and (gl * nnt) * last, g = F(gamma), gl = F(gamma * gae_lambda), every
+// operation rounded once (no contraction into an FMA: bit equality with NumPy depends on it).  nnt multiplies, it does not
+// select: a NaN / Inf next value at a finished step poisons the result as it does in NumPy.
+// The same shape as k_vn_moments' recurrence: one lane per env, serial in t, every load and store coalesced over the envs, the
+// loads of a batch of steps issued ahead of the dependent arithmetic.  The next value is carried in a register, and a batch's
+// loads are all issued before its first store, so a lane reads every element of its column before it writes it: adv may be
+// rew's buffer and ret may be val's (hence no __restrict__ on those four).
+__device__ __forceinline__ float rn_mul(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float rn_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float rn_sub(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ double rn_mul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double rn_add(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double rn_sub(double a, double b) { return __dsub_rn(a, b); }
+
+template <typename F, int U>
+__global__ void __launch_bounds__(64)
+k_gae(const F* rew, const F* val, const uint8_t* __restrict__ done, const F* __restrict__ last_val, int N, int T, F g, F gl,
+      F* adv, F* ret)
+{
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * 64 + threadIdx.x;            // one wave per workgroup: a mid-size batch spreads over the CUs
+    if (e >= N) return;
+    F nv = last_val[e], last = (F)0;
+    for (int tb = T - 1; tb >= 0; tb -= U) {                // steps tb, tb - 1, ... tb - U + 1
+        F r[U], v[U]; uint8_t d[U];
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            const size_t i = (size_t)max(tb - j, 0) * N + e;
+            r[j] = rew[i]; v[j] = val[i]; d[j] = done[i];
+        }
+#pragma unroll
+        for (int j = 0; j < U; j++) {
+            if (tb - j >= 0) {
+                const size_t i = (size_t)(tb - j) * N + e;
+                const F nnt = d[j] ? (F)0 : (F)1;           // 1 - done, exactly
+                const F delta = rn_sub(rn_add(r[j], rn_mul(rn_mul(g, nv), nnt)), v[j]);
+                last = rn_add(delta, rn_mul(rn_mul(gl, nnt), last));
+                adv[i] = last;
+                if (ret) ret[i] = rn_add(last, v[j]);
+                nv = v[j];
+            }
+        }
+    }
+}
+
+// ================================================================================== shuffled minibatches of a rollout
+// stable-baselines3 2.0.0a13, common/buffers.py RolloutBuffer.get / _get_samples: swap_and_flatten every [T][N][...] buffer to
+// [N * T][...] (flat index i = e * T + t), draw a permutation, yield the rows indices[start : start + batch_size] of every buffer.
+// k_minibatch gathers ONE such batch straight from the [T][N] layout: output row b = source row (idx[b] % T, idx[b] / T), the
+// observations through strides (row-major [T][N][F] and feature-major [T][F][pitch] alike), up to PTG_MB_MAX_COLS [T][N] columns
+// of 1 / 2 / 4 / 8-byte elements as raw bytes.  A byte copy: no arithmetic touches the payload.
+// One wave owns MB_ROWS consecutive output rows.  Lane l < MB_ROWS loads idx[b0 + l], checks it, does the row's ONE division by T
+// and keeps the source row's byte offset; it also copies the row's column entries (consecutive lanes, consecutive output elements).
+// Then all 64 lanes run over the consecutive units (16-byte pieces when row length and every row base allow it, else elements) of
+// the wave's MB_ROWS x F output block -- every store instruction is one contiguous segment, every load a run of whole rows -- and
+// fetch each unit's row offset from the owning lane (two ds_bpermute, no LDS allocation).  (row, unit-in-row) advance by the
+// wave-uniform (64 / P, 64 % P) per step, so there is no division per unit.  MB_U units per lane are loaded before the first is
+// stored.  An index outside [0, T * N) never becomes an address: its row is skipped and err[4] is set (PTG_E_INDEX).
+constexpr int MB_ROWS = 16;              // rows per wave: a 203-row PPO batch spreads over 13 waves, 65 536 rows over 16 waves per CU
+constexpr int MB_WAVES = 4;              // waves per workgroup
+constexpr int MB_U = 4;                  // units in flight per lane
+constexpr unsigned MB_BAD = 0xFFFFFFFFu; // high word of the row offset of a rejected index (a real offset stays far below 2^63)
+
+struct MbCols {                          // by value in the launch: a captured call holds no host memory
+    const void* src[PTG_MB_MAX_COLS];
+    void* dst[PTG_MB_MAX_COLS];
+    int bytes[PTG_MB_MAX_COLS];
+    int n;
+};
+
+template <typename V>
+__device__ __forceinline__ void mb_copy_col(const void* src, void* dst, size_t from, size_t to)
+{
+    ((V*)dst)[to] = ((const V*)src)[from];
+}
+
+__device__ __forceinline__ void mb_copy_entry(int bytes, const void* src, void* dst, size_t from, size_t to)
+{
+    switch (bytes) {
+        case 1: mb_copy_col<uint8_t>(src, dst, from, to); break;
+        case 2: mb_copy_col<uint16_t>(src, dst, from, to); break;
+        case 4: mb_copy_col<uint32_t>(src, dst, from, to); break;
+        default: mb_copy_col<uint64_t>(src, dst, from, to); break;
+    }
+}
+
+// The second half of a gathering wave (k_minibatch, k_rb_sample): lane l < rows holds `off`, the byte offset of its source row in
+// `src` (high word MB_BAD: a rejected row); all 64 lanes stream the rows x P units of the wave's contiguous output block `out`.
+template <typename V>
+__device__ __forceinline__ void mb_stream_rows(const char* __restrict__ src, size_t unit_stride, unsigned P, size_t off, unsigned rows,
+                                               unsigned lane, char* __restrict__ out_block)
+{
+    const unsigned off_lo = (unsigned)off, off_hi = (unsigned)(off >> 32);
+    const unsigned dr = 64u / P, dp = 64u - dr * P;          // one step of 64 units, in (rows, units of a row)
+    unsigned r = lane / P, p = lane - r * P;
+    V* const out = (V*)out_block;                            // the wave's block of rows x P units, unit q = r * P + p at out[q]
+    const unsigned units = rows * P;                         // host: P <= 2^20
+    for (unsigned q = lane; q - lane < units; q += 64u * MB_U) {            // wave-uniform trip count: every lane stays for the cross-lane reads
+        V v[MB_U];
+        bool ok[MB_U];
+#pragma unroll
+        for (int j = 0; j < MB_U; j++) {
+            const unsigned rr = min(r, (unsigned)MB_ROWS - 1);              // a lane in range for the cross-lane read
+            const unsigned lo = __shfl(off_lo, (int)rr), hi = __shfl(off_hi, (int)rr);
+            ok[j] = r < rows && hi != MB_BAD;
+            v[j] = V();
+            if (ok[j]) v[j] = *(const V*)(src + (((size_t)hi << 32) | lo) + (size_t)p * unit_stride);
+            r += dr; p += dp;
+            if (p >= P) { p -= P; r++; }
+        }
+#pragma unroll
+        for (int j = 0; j < MB_U; j++)
+            if (ok[j]) out[q + 64u * j] = v[j];
+    }
+}
+
+template <typename V, typename I>
+__global__ void __launch_bounds__(64 * MB_WAVES)
+k_minibatch(const I* __restrict__ idx, size_t B, unsigned T, size_t N, size_t TN, const char* __restrict__ obs, size_t s_t, size_t s_n,
+            size_t unit_stride, unsigned P, char* __restrict__ obs_out, MbCols cols, int* err)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t b0 = ((size_t)blockIdx.x * MB_WAVES + (threadIdx.x >> 6)) * MB_ROWS;
+    if (b0 >= B) return;                                     // wave-uniform
+    const unsigned rows = (unsigned)min((size_t)MB_ROWS, B - b0);
+    size_t off = (size_t)MB_BAD << 32;                       // byte offset of this lane's source row in the observation buffer
+    if (lane < rows) {
+        const long long v = (long long)idx[b0 + lane];
+        if ((unsigned long long)v < (unsigned long long)TN) {
+            size_t e, t;
+            if (TN <= 0xFFFFFFFFull) { const unsigned u = (unsigned)v; e = u / T; t = u - (unsigned)e * T; }   // the common case: 32-bit division
+            else { e = (size_t)v / T; t = (size_t)v - e * T; }
+            off = t * s_t + e * s_n;
+            const size_t from = t * N + e, to = b0 + lane;
+            for (int c = 0; c < cols.n; c++)                 // wave-uniform trip count and switch
+                mb_copy_entry(cols.bytes[c], cols.src[c], cols.dst[c], from, to);
+        } else {
+            err[4] = 1;
+        }
+    }
+    if (obs) mb_stream_rows<V>(obs, unit_stride, P, off, rows, lane, obs_out + b0 * P * sizeof(V));
+}
+
+// ================================================================================== replay buffer of the off-policy algorithms
+// stable-baselines3 2.0.0a13, common/buffers.py ReplayBuffer.add / sample / _get_samples (optimize_memory_usage off), which the
+// reference's DQN, TD3, SAC and TQC train from.  The caller owns the rings (ptg_replay, include/ptg_env.h): observations and next
+// observations [S][N][F] row-major, up to PTG_MB_MAX_COLS columns [S][N], and a device cursor {steps added, batches drawn}.
+// k_rb_add / k_rb_add_tr store a window of T vector steps at slots (cursor[0] + t) % S; k_rb_sample gathers a batch at flat indices
+// i = slot * N + e -- the caller's, or drawn on the device -- which in these rings ARE the row numbers: no division per row.
+// k_rb_bump advances a cursor word in stream order behind them, so a captured add / sample can be replayed.
+struct RbAdd {                           // by value in the launch
+    const char *prev, *obs, *fin;        // prev [N][F]; obs, fin (nullable) [T][N][F], all through the byte strides s_t, s_n (and s_f)
+    const uint8_t* done;                 // [T][N], nullable when neither fin nor a done column needs it
+    size_t s_t, s_n, s_f;                // bytes
+    char *ring0, *ring1;                 // observations, next observations
+    const unsigned long long* cursor;
+    size_t S, N;
+    unsigned T, F;
+    MbCols cols;                         // src: the window's [T][N] columns, dst: their rings [S][N]
+    int done_col;                        // the column written as float32 0 / 1 from `done`, or -1
+};
+
+__device__ __forceinline__ void rb_add_cols(const RbAdd& a, size_t from, size_t to)
+{
+    for (int c = 0; c < a.cols.n; c++) {
+        if (c == a.done_col) ((float*)a.cols.dst[c])[to] = a.done[from] ? 1.0f : 0.0f;
+        else mb_copy_entry(a.cols.bytes[c], a.cols.src[c], a.cols.dst[c], from, to);
+    }
+}
+
+// Rows that are contiguous in the source (s_f = one element): a slot [N][F] of either ring is then ONE contiguous run of N * P units
+// (V = a 16-byte piece when row length and every base allow it, else an element), unit u of the slot = (env u / P, unit u % P of
+// its row); consecutive lanes take consecutive units, so every store is a contiguous segment and every load a run of whole rows
+// (a single run for a [T][N][F] contiguous source).  A finished env's next observation comes from `fin`: a per-row select of the
+// source pointer.  The lane on a row's first unit also moves the row's column entries.  blockIdx.y strides over the steps.
+template <typename V>
+__global__ void __launch_bounds__(256)
+k_rb_add(RbAdd a, unsigned P, size_t NP)
+{
+    const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (u >= NP) return;
+    size_t e; unsigned p;
+    if (NP <= 0xFFFFFFFFull) { const unsigned q = (unsigned)u / P; e = q; p = (unsigned)u - q * P; }
+    else { e = u / P; p = (unsigned)(u - e * P); }
+    const size_t a0 = (size_t)(a.cursor[0] % a.S);
+    const size_t in_row = e * a.s_n + (size_t)p * sizeof(V);
+    for (unsigned t = blockIdx.y; t < a.T; t += gridDim.y) {
+        size_t slot = a0 + t;                                // T <= S: at most one wrap
+        if (slot >= a.S) slot -= a.S;
+        const size_t from = (size_t)t * a.N + e, to = slot * a.N + e;
+        const char* s0 = (t == 0 ? a.prev : a.obs + (size_t)(t - 1) * a.s_t) + in_row;
+        const char* s1 = (a.fin && a.done[from] ? a.fin : a.obs) + (size_t)t * a.s_t + in_row;
+        const V v0 = *(const V*)s0, v1 = *(const V*)s1;
+        const size_t o = (slot * NP + u) * sizeof(V);
+        *(V*)(a.ring0 + o) = v0;
+        *(V*)(a.ring1 + o) = v1;
+        if (p == 0) rb_add_cols(a, from, to);
+    }
+}
+
+// Any other source (feature-major [T][F][pitch]: s_n = one element): a 64-env x 32-feature tile of each ring goes through LDS, read
+// with the lanes along the envs (coalesced in a feature plane), written with the lanes along the features (128- / 256-byte
+// segments of the ring's rows).  The 33-element pitch keeps both phases off one bank.
+constexpr int RB_TE = 64, RB_TF = 32;
+template <typename E>
+__global__ void __launch_bounds__(256)
+k_rb_add_tr(RbAdd a)
+{
+    __shared__ E tile[2][RB_TE][RB_TF + 1];
+    const unsigned tid = threadIdx.x;
+    const size_t e0 = (size_t)blockIdx.x * RB_TE;
+    const unsigned el = tid & 63u, fr = tid >> 6, fl = tid & 31u, er = tid >> 5;
+    const size_t a0 = (size_t)(a.cursor[0] % a.S);
+    for (unsigned t = blockIdx.y; t < a.T; t += gridDim.y) {
+        size_t slot = a0 + t;
+        if (slot >= a.S) slot -= a.S;
+        const size_t e = e0 + el;
+        const bool live = e < a.N;
+        const char *s0 = nullptr, *s1 = nullptr;
+        if (live) {
+            s0 = (t == 0 ? a.prev : a.obs + (size_t)(t - 1) * a.s_t) + e * a.s_n;
+            s1 = (a.fin && a.done[(size_t)t * a.N + e] ? a.fin : a.obs) + (size_t)t * a.s_t + e * a.s_n;
+        }
+        for (unsigned f0 = 0; f0 < a.F; f0 += RB_TF) {
+            if (live)
+                for (unsigned f = fr; f < RB_TF && f0 + f < a.F; f += 4) {
+                    tile[0][el][f] = *(const E*)(s0 + (size_t)(f0 + f) * a.s_f);
+                    tile[1][el][f] = *(const E*)(s1 + (size_t)(f0 + f) * a.s_f);
+                }
+            __syncthreads();
+            if (f0 + fl < a.F)
+                for (unsigned r = er; r < RB_TE && e0 + r < a.N; r += 8) {
+                    const size_t o = ((slot * a.N + e0 + r) * a.F + f0 + fl) * sizeof(E);
+                    *(E*)(a.ring0 + o) = tile[0][r][fl];
+                    *(E*)(a.ring1 + o) = tile[1][r][fl];
+                }
+            __syncthreads();
+        }
+        if (tid < 64 && live) rb_add_cols(a, (size_t)t * a.N + e, slot * a.N + e);
+    }
+}
+
+__global__ void k_rb_bump(unsigned long long* word, unsigned long long by) { *word += by; }
+
+// The two 32-bit words of row b of the c-th device-drawn batch under `seed` (include/ptg_env.h states the same lines; the tests
+// restate them in integer arithmetic): a chain of lowbias32 over the six 32-bit halves of (seed, c, b), then two finalisers.
+__device__ __forceinline__ unsigned long long rb_draw_word(unsigned long long seed, unsigned long long c, unsigned long long b)
+{
+    unsigned k = lowbias32((unsigned)seed ^ 0x9E3779B9u);
+    k = lowbias32(k + (unsigned)(seed >> 32));
+    k = lowbias32(k ^ (unsigned)c);
+    k = lowbias32(k + (unsigned)(c >> 32));
+    k = lowbias32(k ^ (unsigned)b);
+    k = lowbias32(k + (unsigned)(b >> 32));
+    const unsigned w0 = lowbias32(k ^ 0x85EBCA6Bu), w1 = lowbias32(k ^ 0xC2B2AE35u);
+    return ((unsigned long long)w0 << 32) | w1;
+}
+
+struct RbNorm {                          // SB3's _normalize_reward at sample time: column `col` through k_vn_norm's expression
+    int col;                             // -1: none
+    const double* stats;                 // the handle's {mean, var, count}
+    double eps, clip;
+};
+
+template <typename OUT>
+__device__ __forceinline__ void rb_norm_entry(const void* src, void* dst, size_t from, size_t to, double den, double clip)
+{
+    const double v = (double)((const OUT*)src)[from] / den;                 // k_vn_norm's lines
+    const double lo = v < -clip ? -clip : v;
+    ((OUT*)dst)[to] = (OUT)(lo > clip ? clip : lo);
+}
+
+// k_minibatch's scheme with two row sources sharing one offset: a wave owns MB_ROWS output rows; lane l < rows takes or draws
+// the index of row b0 + l, checks it against size * N (size = min(cursor[0], S), read here: the launch may be a replay) and moves
+// the row's column entries; then all 64 lanes stream the rows x F block of each ring.  An index out of range, or any draw from an
+// empty buffer, never becomes an address: the row is left as it was and err[4] is set (PTG_E_INDEX).
+template <typename V>
+__global__ void __launch_bounds__(64 * MB_WAVES)
+k_rb_sample(const long long* __restrict__ idx, size_t B, unsigned long long seed, const unsigned long long* __restrict__ cursor, size_t S,
+            size_t N, size_t row_bytes, unsigned P, const char* __restrict__ ring0, const char* __restrict__ ring1, char* __restrict__ out0,
+            char* __restrict__ out1, MbCols cols, RbNorm norm, long long* __restrict__ idx_out, int* err)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t b0 = ((size_t)blockIdx.x * MB_WAVES + (threadIdx.x >> 6)) * MB_ROWS;
+    if (b0 >= B) return;                                     // wave-uniform
+    const unsigned rows = (unsigned)min((size_t)MB_ROWS, B - b0);
+    size_t off = (size_t)MB_BAD << 32;
+    if (lane < rows) {
+        const unsigned long long added = cursor[0];
+        const unsigned long long total = (added < S ? added : S) * N;
+        const size_t to = b0 + lane;
+        unsigned long long i;
+        if (idx) i = (unsigned long long)idx[to];            // a negative index is a huge one
+        else i = total ? __umul64hi(rb_draw_word(seed, cursor[1], to), total) : ~0ull;
+        if (i < total) {
+            off = (size_t)i * row_bytes;
+            if (idx_out) idx_out[to] = (long long)i;
+            for (int c = 0; c < cols.n; c++) {
+                if (!cols.dst[c]) continue;
+                if (c == norm.col) {
+                    const double den = sqrt(norm.stats[1] + norm.eps);      // k_vn_scan's frozen denominator
+                    if (cols.bytes[c] == 8) rb_norm_entry<double>(cols.src[c], cols.dst[c], (size_t)i, to, den, norm.clip);
+                    else rb_norm_entry<float>(cols.src[c], cols.dst[c], (size_t)i, to, den, norm.clip);
+                } else {
+                    mb_copy_entry(cols.bytes[c], cols.src[c], cols.dst[c], (size_t)i, to);
+                }
+            }
+        } else {
+            err[4] = 1;
+        }
+    }
+    if (out0) mb_stream_rows<V>(ring0, sizeof(V), P, off, rows, lane, out0 + b0 * row_bytes);
+    if (out1) mb_stream_rows<V>(ring1, sizeof(V), P, off, rows, lane, out1 + b0 * row_bytes);
+}
+
+// ================================================================================== the action head
+// What runs between the network's output and env.step while collecting (include/ptg_env.h, ptg_act, states the lines; the tests
+// restate them in NumPy): SB3's CategoricalDistribution sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads of
+// TD3 / SAC / TQC / continuous A2C and PPO.  One lane per env on consecutive envs, no cross-lane traffic; float64 arithmetic
+// whatever the input type, rounded once on the store.  A discrete row is read three times (maximum; sum; partial sums, entropy and
+// the chosen log-prob) straight from global memory: a wave's 64 x A block is 64 * A * sizeof(IN) contiguous bytes (1 280 at float32,
+// A = 5), every pass after the first finds its lines in the L1 / L2, and the launch is bound by its own latency at every batch
+// the project runs -- an LDS-staged tile was measured beside it and bought nothing, so it is not in the tree.
+// Nothing per lane is indexed dynamically, so nothing spills to scratch for A up to 32.
+struct ActArgs {                         // by value in the launch
+    const void* in; size_t s_n;          // elements
+    const void* param; size_t param_s;   // EPS_GREEDY: const double* epsilon; GAUSSIAN: log_std in IN, stride 0 | 1
+    void *act, *raw, *logp, *ent;
+    const unsigned long long* counter;   // null when deterministic
+    unsigned long long seed;
+    long long env_offset;
+    double lo, hi;
+    size_t N;
+    int A, kind, flags, act_kind;
+    int* err;
+};
+
+__device__ __forceinline__ void act_store_action(const ActArgs& a, size_t e, long long v)
+{
+    if (a.act_kind == PTG_ACT_I64) ((long long*)a.act)[e] = v; else ((int*)a.act)[e] = (int)v;
+}
+
+constexpr int ACT_BLOCK = 256;
+template <typename IN>
+__global__ void __launch_bounds__(ACT_BLOCK)
+k_act(ActArgs a)
+{
+    const size_t e = (size_t)blockIdx.x * ACT_BLOCK + threadIdx.x;
+    if (e >= a.N) return;                                    // the ragged last wave
+    const bool det = (a.flags & PTG_HEAD_DETERMINISTIC) != 0;
+    unsigned w0 = 0, w1 = 0;
+    if (!det) {
+        const unsigned long long w = rb_draw_word(a.seed, a.counter[0], (unsigned long long)(a.env_offset + (long long)e));
+        w0 = (unsigned)(w >> 32); w1 = (unsigned)w;
+    }
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    IN* const logp_o = (IN*)a.logp; IN* const ent_o = (IN*)a.ent; IN* const raw_o = (IN*)a.raw;
+    if (a.kind == PTG_HEAD_GAUSSIAN) {
+        const double mu = (double)((const IN*)a.in)[e * a.s_n];
+        const double ls = (double)((const IN*)a.param)[e * a.param_s];
+        if (!(fabs(mu) <= 1.7976931348623157e308) || !(ls <= 1.7976931348623157e308)) {       // NaN or Inf mean; NaN or +Inf log_std
+            ((float*)a.act)[e] = 0.0f;
+            if (raw_o) raw_o[e] = (IN)nan;
+            if (logp_o) logp_o[e] = (IN)nan;
+            if (ent_o) ent_o[e] = (IN)nan;
+            a.err[5] = 1;
+            return;
+        }
+        double z = 0.0;
+        if (!det) {
+            const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = (double)w1 * 2.3283064365386963e-10;      // 2^-32
+            z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        }
+        const double g = mu + exp(ls) * z;
+        double lp = ((-(z * z) / 2.0) - ls) - 0.9189385332046727;
+        double x = g;
+        if (a.flags & PTG_HEAD_SQUASH) {
+            x = tanh(g);
+            lp = lp - log((1.0 - x * x) + 1e-6);
+        }
+        x = x < a.lo ? a.lo : (x > a.hi ? a.hi : x);
+        ((float*)a.act)[e] = (float)x;
+        if (raw_o) raw_o[e] = (IN)g;
+        if (logp_o) logp_o[e] = (IN)lp;
+        if (ent_o) ent_o[e] = (IN)(1.4189385332046727 + ls);
+        return;
+    }
+    // discrete kinds: maximum and its first index
+    const IN* __restrict__ row = (const IN*)a.in + e * a.s_n;
+    const int A = a.A;
+    double m = (double)row[0];
+    int jm = 0;
+    bool bad = m != m;
+    for (int j = 1; j < A; j++) {
+        const double l = (double)row[j];
+        bad = bad || l != l;
+        if (l > m) { m = l; jm = j; }
+    }
+    bad = bad || !(fabs(m) <= 1.7976931348623157e308);       // +Inf somewhere, or -Inf everywhere
+    if (a.kind == PTG_HEAD_EPS_GREEDY) {
+        long long action = jm;
+        if (!det) {
+            const double eps = ((const double*)a.param)[0];
+            if (!(eps >= 0.0 && eps <= 1.0)) bad = true;
+            else if ((unsigned long long)w0 < (unsigned long long)(eps * 4294967296.0))
+                action = (long long)(((unsigned long long)w1 * (unsigned long long)A) >> 32);
+        }
+        if (bad) { action = 0; a.err[5] = 1; }
+        act_store_action(a, e, action);
+        return;
+    }
+    if (bad) {
+        act_store_action(a, e, 0);
+        if (logp_o) logp_o[e] = (IN)nan;
+        if (ent_o) ent_o[e] = (IN)nan;
+        a.err[5] = 1;
+        return;
+    }
+    double s = 0.0;
+    for (int j = 0; j < A; j++) s += exp((double)row[j] - m);
+    const double log_s = log(s);
+    const double us = det ? 0.0 : (double)(((unsigned long long)w0 << 21) | (unsigned long long)(w1 >> 11)) * 1.1102230246251565e-16 * s;      // 2^-53
+    double c = 0.0, ent = 0.0, lp = 0.0;
+    int action = det ? jm : -1;
+    for (int j = 0; j < A; j++) {
+        const double d = (double)row[j] - m;
+        const double ej = exp(d);
+        const double lpj = d - log_s;
+        c += ej;
+        if (ej != 0.0) ent += (ej / s) * lpj;
+        const bool take = det ? j == jm : (action < 0 && (us < c || j == A - 1));
+        if (take) { action = j; lp = lpj; }
+    }
+    act_store_action(a, e, action);
+    if (logp_o) logp_o[e] = (IN)lp;
+    if (ent_o) ent_o[e] = (IN)(-ent);
+}
+
+// ================================================================================== the policy loss
+// What runs between the network's output on a minibatch and the gradient that goes back into it (include/ptg_env.h, ptg_policy_loss,
+// states the lines; tests/policy_loss_restatement.py restates them in NumPy): SB3's evaluate_actions (Categorical / DiagGaussian
+// log_prob and entropy) and the loss lines of PPO.train / A2C.train, with d loss / d logits (or means), d loss / d values and
+// d loss / d log_std in closed form -- every one is a function of quantities the forward pass holds, so no graph is walked back.
+// One lane per row on consecutive rows, float64 arithmetic whatever the input type, gradients rounded once on the store.  A
+// categorical row is read as k_act reads it (maximum; sum; entropy and the chosen log-prob) plus a fourth pass that writes the
+// gradients, which need the row's complete entropy; exp is evaluated again instead of kept, so nothing per lane is indexed dynamically.
+// Batch-wide quantities (the advantage moments, six sums, the log_std gradient) are reduced in a fixed order: a shuffle tree per wave,
+// the block's four waves in wave order, one partial per block in the caller's workspace, and a merge that walks the partials in an
+// order given by the block count alone.  No floating-point atomics: the same inputs give the same bits.  Moments travel as
+// (count, mean, M2) and meet in chan_merge, as the reward normalisation's do.
+struct LossArgs {                        // by value in the launch
+    const void* in; size_t s_n;          // elements
+    const void* val; size_t v_s;
+    const void *act, *old_lp, *adv, *ret, *old_val, *log_std;
+    void* g_in; size_t g_s;
+    void* g_val; size_t gv_s;
+    void* g_ls;
+    double* stats;
+    double* ws;                          // [0..2] merged advantage moments; [4 ..) moment partials [nblk][3]; then row partials [nblk][8]
+    double eps, eps_v, ent_coef, vf_coef;
+    size_t B;
+    int A, kind, head, flags, act_kind, nblk;
+    int* err;
+};
+struct PlRow { double surr, q, H, kl, cf, gls; };     // a row's terms of the five means and of the log_std gradient's sum
+
+constexpr int PL_BLOCK = 256, PL_WAVES = PL_BLOCK / 64, PL_TERMS = 6, PL_PITCH = 8;
+constexpr double PL_DBL_MAX = 1.7976931348623157e308;
+
+__device__ __forceinline__ double pl_wave_sum(double v)      // a + b == b + a: every lane ends with the same bits
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ bool pl_finite(double x) { return fabs(x) <= PL_DBL_MAX; }
+
+// (count, mean, M2) of the block's advantages: two shuffle trees per wave (sum -> mean, then squared deviations from it: a sum of
+// squares would cancel), the block's waves merged in wave order.  Every thread of the block calls it; `sh` holds PL_WAVES * 3 doubles.
+template <typename IN>
+__device__ __forceinline__ void pl_block_moments(const LossArgs& a, size_t i, bool live, double* sh, double& c, double& m, double& M)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const double x = live ? (double)((const IN*)a.adv)[i] : 0.0;
+    const double n = pl_wave_sum(live ? 1.0 : 0.0);
+    const double s = pl_wave_sum(x);
+    const double mean = n > 0.0 ? s / n : 0.0;
+    const double dv = live ? x - mean : 0.0;
+    const double m2 = pl_wave_sum(dv * dv);
+    if (lane == 0) { sh[w * 3 + 0] = n; sh[w * 3 + 1] = mean; sh[w * 3 + 2] = m2; }
+    __syncthreads();
+    c = 0.0; m = 0.0; M = 0.0;
+    for (int k = 0; k < PL_WAVES; k++) chan_merge(c, m, M, sh[k * 3 + 0], sh[k * 3 + 1], sh[k * 3 + 2]);
+}
+
+// One row: its gradients are stored, its terms returned.  mean / den: the advantage moments in use (den = std + 1e-8).
+template <typename IN>
+__device__ __forceinline__ PlRow pl_row(const LossArgs& a, size_t i, bool norm, double mean, double den)
+{
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const PlRow poison{nan, nan, nan, nan, nan, nan};
+    const double Bd = (double)a.B;
+    const bool ppo = a.kind == PTG_LOSS_PPO, clipv = (a.flags & PTG_LOSS_CLIP_VF) != 0, cat = a.head == PTG_HEAD_CATEGORICAL;
+    const int A = a.A;
+    long long act = 0;
+    if (cat) {
+        act = a.act_kind == PTG_ACT_I64 ? ((const long long*)a.act)[i] : (long long)((const int*)a.act)[i];
+        if (act < 0 || act >= (long long)A) { a.err[4] = 1; return poison; }      // never an address; the row's gradients stay as they were
+    }
+    const double v = (double)((const IN*)a.val)[i * a.v_s];
+    const double adv = (double)((const IN*)a.adv)[i], ret = (double)((const IN*)a.ret)[i];
+    const double old = ppo ? (double)((const IN*)a.old_lp)[i] : 0.0;
+    const double ov = clipv ? (double)((const IN*)a.old_val)[i] : 0.0;
+    bool bad = !pl_finite(v) || !pl_finite(adv) || !pl_finite(ret) || !pl_finite(old) || !pl_finite(ov);
+    IN* const g_row = (IN*)a.g_in + i * a.g_s;
+    const IN* __restrict__ row = (const IN*)a.in + i * a.s_n;
+    double lp = 0.0, H = 0.0, m = 0.0, s = 1.0, log_s = 0.0, z = 0.0, sigma = 1.0;
+    if (cat) {
+        m = (double)row[0];
+        bad = bad || m != m;
+        for (int j = 1; j < A; j++) {
+            const double l = (double)row[j];
+            bad = bad || l != l;
+            if (l > m) m = l;
+        }
+        bad = bad || !pl_finite(m);                          // +Inf somewhere, or -Inf everywhere
+        if (!bad) {
+            s = 0.0;
+            for (int j = 0; j < A; j++) s += exp((double)row[j] - m);
+            log_s = log(s);
+            double ent = 0.0;
+            for (int j = 0; j < A; j++) {
+                const double d = (double)row[j] - m;
+                const double ej = exp(d);
+                const double lpj = d - log_s;
+                if (ej != 0.0) ent += (ej / s) * lpj;
+                if (j == (int)act) lp = lpj;
+            }
+            H = -ent;
+        }
+    } else {
+        const double mu = (double)row[0], ls = (double)((const IN*)a.log_std)[0], x = (double)((const IN*)a.act)[i];
+        bad = bad || !pl_finite(mu) || !(ls <= PL_DBL_MAX);   // NaN or Inf mean; NaN or +Inf log_std
+        sigma = exp(ls);
+        z = (x - mu) / sigma;
+        lp = ((-(z * z) / 2.0) - ls) - 0.9189385332046727;
+        H = 1.4189385332046727 + ls;
+    }
+    bad = bad || !pl_finite(lp);                             // an action of probability 0 (a -Inf logit, a zero sigma), a non-finite sample
+    double d = 0.0, r = 1.0;
+    if (ppo) {
+        d = lp - old;
+        r = exp(d);
+        bad = bad || !pl_finite(r);                          // a ratio that overflows: Ah * r would be Inf, or NaN where Ah is 0
+    }
+    IN* const g_v = (IN*)a.g_val + i * a.gv_s;
+    if (bad) {
+        if (cat) { for (int j = 0; j < A; j++) g_row[j] = (IN)nan; } else g_row[0] = (IN)nan;
+        g_v[0] = (IN)nan;
+        a.err[5] = 1;
+        return poison;
+    }
+    const double ah = norm ? (adv - mean) / den : adv;
+    PlRow t{0.0, 0.0, H, 0.0, 0.0, 0.0};
+    double g;
+    if (ppo) {
+        const double lo = 1.0 - a.eps, hi = 1.0 + a.eps;
+        const double c = r < lo ? lo : (r > hi ? hi : r);
+        const double t1 = ah * r, t2 = ah * c;
+        t.surr = (t1 != t1 || t2 != t2) ? nan : (t2 < t1 ? t2 : t1);
+        g = (t1 < t2 || (r >= lo && r <= hi)) ? t1 : 0.0;
+        t.kl = (r - 1.0) - d;
+        t.cf = fabs(r - 1.0) > a.eps ? 1.0 : 0.0;
+    } else {
+        t.surr = ah * lp;
+        g = ah;
+    }
+    double vh = v;
+    bool pass = true;
+    if (clipv) {
+        const double dv = v - ov;
+        const double cl = dv < -a.eps_v ? -a.eps_v : (dv > a.eps_v ? a.eps_v : dv);
+        vh = ov + cl;
+        pass = dv >= -a.eps_v && dv <= a.eps_v;
+    }
+    const double dq = ret - vh;
+    t.q = dq * dq;
+    const double h = pass ? 2.0 * (vh - ret) : 0.0;
+    g_v[0] = (IN)((a.vf_coef * h) / Bd);
+    if (cat) {
+        for (int j = 0; j < A; j++) {
+            const double d = (double)row[j] - m;
+            const double ej = exp(d);
+            const double p = ej / s;
+            double gr = (-g) * ((j == (int)act ? 1.0 : 0.0) - p);
+            if (ej != 0.0) gr = gr + a.ent_coef * (p * ((d - log_s) + H));      // the entropy term of a probability-0 column is left out, as in H
+            g_row[j] = (IN)(gr / Bd);
+        }
+    } else {
+        g_row[0] = (IN)(((-g) * (z / sigma)) / Bd);
+        t.gls = g * ((z * z) - 1.0);
+    }
+    return t;
+}
+
+// the sums of a whole batch -> the eight statistics and the log_std gradient; one thread
+template <typename IN>
+__device__ __forceinline__ void pl_finish(const LossArgs& a, const double* sum, double mean, double sd)
+{
+    const double Bd = (double)a.B;
+    const double pl = -(sum[0] / Bd), vl = sum[1] / Bd, el = -(sum[2] / Bd);
+    a.stats[0] = (pl + a.ent_coef * el) + a.vf_coef * vl;
+    a.stats[1] = pl; a.stats[2] = vl; a.stats[3] = el;
+    a.stats[4] = sum[3] / Bd; a.stats[5] = sum[4] / Bd;
+    a.stats[6] = mean; a.stats[7] = sd;
+    if (a.g_ls) ((IN*)a.g_ls)[0] = (IN)((-(sum[5]) / Bd) - a.ent_coef);
+}
+
+// the block's sums of PL_TERMS values: a shuffle tree per wave, then the waves in wave order (thread 0 holds the result)
+__device__ __forceinline__ void pl_block_sum(double* v, double* sh)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < PL_TERMS; k++) {
+        v[k] = pl_wave_sum(v[k]);
+        if (lane == 0) sh[w * PL_PITCH + k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) {
+            double s = sh[k];
+            for (int q = 1; q < PL_WAVES; q++) s += sh[q * PL_PITCH + k];
+            v[k] = s;
+        }
+    }
+}
+
+template <typename IN>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_pl_moments(LossArgs a)
+{
+    __shared__ double sh[PL_WAVES * 3];
+    const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    double c, m, M;
+    pl_block_moments<IN>(a, i, i < a.B, sh, c, m, M);
+    if (threadIdx.x == 0) {
+        double* p = a.ws + 4 + (size_t)blockIdx.x * 3;
+        p[0] = c; p[1] = m; p[2] = M;
+    }
+}
+
+// ONE: the whole batch is this block (B <= PL_BLOCK): moments, rows and statistics in one launch.  Otherwise the moments come
+// merged from the workspace and the block leaves its partial sums there for k_pl_final.
+template <typename IN, bool ONE>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_pl_rows(LossArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
+    const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
+    double mean = 0.0, sd = 1.0;
+    if (norm) {
+        double c, m, M;
+        if (ONE) { pl_block_moments<IN>(a, i, live, sh, c, m, M); __syncthreads(); }
+        else { c = a.ws[0]; m = a.ws[1]; M = a.ws[2]; }
+        mean = m;
+        sd = sqrt(M / ((double)a.B - 1.0));                  // torch.std: the unbiased one
+    }
+    PlRow t{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (live) t = pl_row<IN>(a, i, norm, mean, sd + 1e-8);
+    double v[PL_TERMS] = {t.surr, t.q, t.H, t.kl, t.cf, t.gls};
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        if (ONE) pl_finish<IN>(a, v, mean, sd);
+        else {
+            double* p = a.ws + 4 + (size_t)a.nblk * 3 + (size_t)blockIdx.x * PL_PITCH;
+#pragma unroll
+            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
+        }
+    }
+}
+
+// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
+template <typename IN>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_pl_final(LossArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const double* part = a.ws + 4 + (size_t)a.nblk * 3;
+    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) v[k] += part[(size_t)b * PL_PITCH + k];
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
+        pl_finish<IN>(a, v, norm ? a.ws[1] : 0.0, norm ? sqrt(a.ws[2] / ((double)a.B - 1.0)) : 1.0);
+    }
+}
+
+// ================================================================================================= host side
+// ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
+template <typename V>
+void launch_minibatch(hipStream_t st, const void* idx, int idx_bytes, size_t B, unsigned T, size_t N, const char* obs, size_t s_t,
+                             size_t s_n, size_t unit_stride, unsigned P, char* obs_out, const MbCols& cols, int* err)
+{
+    const dim3 grid((unsigned)((B + MB_ROWS * MB_WAVES - 1) / (MB_ROWS * MB_WAVES))), block(64 * MB_WAVES);
+    if (idx_bytes == 8)
+        hipLaunchKernelGGL((k_minibatch<V, long long>), grid, block, 0, st, (const long long*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+    else
+        hipLaunchKernelGGL((k_minibatch<V, int>), grid, block, 0, st, (const int*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- VecNormalize(norm_obs=False) on the device ---------------------------------------------------------------------
+int ptg_vn_init(ptg_env* h, double gamma, double epsilon, double clip_reward)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!(gamma >= 0.0) || !(epsilon >= 0.0) || !(clip_reward > 0.0)) return set_err(h, PTG_E_INVALID, "ptg_vn_init: bad gamma / epsilon / clip_reward");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if (!h->vn_returns) {
+        if ((rc = dev_alloc(h, &h->vn_returns, (size_t)h->n)) || (rc = dev_alloc(h, &h->vn_stats, 3))) return rc;
+    }
+    h->vn_gamma = gamma; h->vn_eps = epsilon; h->vn_clip = clip_reward;
+    const double st[3] = {0.0, 1.0, 1e-4};                  // RunningMeanStd(epsilon=1e-4): mean 0, var 1, count 1e-4
+    HIP_TRY(h, hipMemset(h->vn_returns, 0, sizeof(double) * h->n));
+    HIP_TRY(h, hipMemcpy(h->vn_stats, st, sizeof st, hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int vn_scratch(ptg_env* h, int T)
+{
+    const int nW = (h->n + 63) / 64;
+    const size_t need = (size_t)T * nW * 3;
+    if (need > h->vn_partials_cap) {
+        if (h->vn_partials) (void)hipFree(h->vn_partials);
+        h->vn_partials = nullptr; h->vn_partials_cap = 0;
+        if (hipMalloc((void**)&h->vn_partials, need * sizeof(double)) != hipSuccess) return set_err(h, PTG_E_HIP, "hipMalloc of %zu bytes failed", need * sizeof(double));
+        h->vn_partials_cap = need;
+    }
+    if (T > h->vn_T_cap) {
+        if (h->vn_den) (void)hipFree(h->vn_den);
+        if (h->vn_moments) (void)hipFree(h->vn_moments);
+        h->vn_den = h->vn_moments = nullptr; h->vn_T_cap = 0;
+        if (hipMalloc((void**)&h->vn_den, sizeof(double) * T) != hipSuccess || hipMalloc((void**)&h->vn_moments, sizeof(double) * 3 * T) != hipSuccess)
+            return set_err(h, PTG_E_HIP, "hipMalloc failed");
+        h->vn_T_cap = T;
+    }
+    return 0;
+}
+
+int ptg_vn_batch_moments(ptg_env* h, const void* rew_dev, const uint8_t* done_dev, int n_steps, double* moments_dev, void* stream)
+{
+    if (!h || !rew_dev || !done_dev || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_vn_batch_moments: bad argument");
+    if (!h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_vn_batch_moments: call ptg_vn_init first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = vn_scratch(h, n_steps))) return rc;
+    hipStream_t st = as_stream(stream);
+    const int nW = (h->n + 63) / 64;
+    const dim3 grid(nW), block(64);
+    if (h->cfg.out_dtype == PTG_OUT_F64)
+        hipLaunchKernelGGL(k_vn_moments<double>, grid, block, 0, st, (const double*)rew_dev, done_dev, h->n, n_steps, h->vn_gamma, h->vn_returns, h->vn_partials, nW);
+    else
+        hipLaunchKernelGGL(k_vn_moments<float>, grid, block, 0, st, (const float*)rew_dev, done_dev, h->n, n_steps, h->vn_gamma, h->vn_returns, h->vn_partials, nW);
+    hipLaunchKernelGGL(k_vn_merge, dim3(n_steps), dim3(64), 0, st, h->vn_partials, nW, moments_dev ? moments_dev : h->vn_moments);
+    return launch_check(h, "k_vn_moments");
+}
+
+int ptg_vn_apply(ptg_env* h, const void* rew_dev, int n_steps, const double* moments_dev, void* rew_out_dev, int training, void* stream)
+{
+    if (!h || !rew_dev || !rew_out_dev || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_vn_apply: bad argument");
+    if (!h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_vn_apply: call ptg_vn_init first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = vn_scratch(h, n_steps))) return rc;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(k_vn_scan, dim3(1), dim3(64), 0, st, moments_dev ? moments_dev : h->vn_moments, n_steps, training, h->vn_eps, h->vn_stats, h->vn_den);
+    const size_t total = (size_t)n_steps * h->n;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    if (h->cfg.out_dtype == PTG_OUT_F64)
+        hipLaunchKernelGGL(k_vn_norm<double>, grid, block, 0, st, (const double*)rew_dev, (double*)rew_out_dev, h->vn_den, h->n, total, h->vn_clip);
+    else
+        hipLaunchKernelGGL(k_vn_norm<float>, grid, block, 0, st, (const float*)rew_dev, (float*)rew_out_dev, h->vn_den, h->n, total, h->vn_clip);
+    return launch_check(h, "k_vn_norm");
+}
+
+int ptg_vn_clear_done(ptg_env* h, const uint8_t* done_dev, int n_steps, void* stream)
+{
+    if (!h || !done_dev || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_vn_clear_done: bad argument");
+    if (!h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_vn_clear_done: call ptg_vn_init first");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_vn_clear_done, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, as_stream(stream), done_dev, h->n, n_steps, h->vn_returns);
+    return launch_check(h, "k_vn_clear_done");
+}
+
+int ptg_vn_get(ptg_env* h, double* stats3_host, double* returns_host)
+{
+    if (!h || !h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_vn_get: not initialised");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (stats3_host) HIP_TRY(h, hipMemcpy(stats3_host, h->vn_stats, sizeof(double) * 3, hipMemcpyDeviceToHost));
+    if (returns_host) HIP_TRY(h, hipMemcpy(returns_host, h->vn_returns, sizeof(double) * h->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int ptg_vn_set(ptg_env* h, const double* stats3_host, const double* returns_host)
+{
+    if (!h || !h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_vn_set: not initialised");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (stats3_host) HIP_TRY(h, hipMemcpy(h->vn_stats, stats3_host, sizeof(double) * 3, hipMemcpyHostToDevice));
+    if (returns_host) HIP_TRY(h, hipMemcpy(h->vn_returns, returns_host, sizeof(double) * h->n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ---- RolloutBuffer.compute_returns_and_advantage on the device ------------------------------------------------------
+int ptg_gae(ptg_env* h, const void* rew_dev, const void* val_dev, const uint8_t* done_dev, const void* last_val_dev, int n_steps,
+            int dtype, double gamma, double gae_lambda, void* adv_dev, void* ret_dev, void* stream)
+{
+    if (!h || !rew_dev || !val_dev || !done_dev || !last_val_dev || !adv_dev || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_gae: bad argument");
+    if (dtype != PTG_OUT_F32 && dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_gae: bad dtype");
+    if (!std::isfinite(gamma) || !std::isfinite(gae_lambda)) return set_err(h, PTG_E_INVALID, "ptg_gae: gamma / gae_lambda must be finite");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const double gl = gamma * gae_lambda;                   // Python's float product, before it meets the array's dtype
+    const dim3 grid((unsigned)((h->n + 63) / 64)), block(64);
+    // 32 (float64: 16) steps of loads in flight per lane: 18 KiB per wave, 72 KiB per CU at the 4 waves per CU of 65 536 envs
+    if (dtype == PTG_OUT_F64)
+        hipLaunchKernelGGL((k_gae<double, 16>), grid, block, 0, as_stream(stream), (const double*)rew_dev, (const double*)val_dev, done_dev,
+                           (const double*)last_val_dev, h->n, n_steps, gamma, gl, (double*)adv_dev, (double*)ret_dev);
+    else
+        hipLaunchKernelGGL((k_gae<float, 32>), grid, block, 0, as_stream(stream), (const float*)rew_dev, (const float*)val_dev, done_dev,
+                           (const float*)last_val_dev, h->n, n_steps, (float)gamma, (float)gl, (float*)adv_dev, (float*)ret_dev);
+    return launch_check(h, "k_gae");
+}
+
+// ---- RolloutBuffer.get's _get_samples on the device: one minibatch per launch ---------------------------------------
+int ptg_minibatch(ptg_env* h, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps, const void* obs_dev, int64_t obs_s_t,
+                  int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev, int n_cols, const void* const* cols_host,
+                  const int* col_bytes_host, void* const* cols_out_host, void* stream)
+{
+    if (!h || !idx_dev || batch < 1 || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_minibatch: bad argument");
+    if (idx_bytes != 4 && idx_bytes != 8) return set_err(h, PTG_E_INVALID, "ptg_minibatch: indices must be int32 or int64");
+    if (batch > (int64_t)0x7FFFFFFF * (MB_ROWS * MB_WAVES)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: batch too large for one launch");
+    if ((obs_dev == nullptr) != (obs_out_dev == nullptr)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: observations and their output go together");
+    if (obs_dev && (obs_dim < 1 || obs_dim > (1 << 20) || (obs_bytes != 4 && obs_bytes != 8) || obs_s_t < 0 || obs_s_n < 0 || obs_s_f < 0))
+        return set_err(h, PTG_E_INVALID, "ptg_minibatch: bad observation shape (obs_dim in [1, 2^20], 4- or 8-byte elements, strides >= 0)");
+    if (n_cols < 0 || n_cols > PTG_MB_MAX_COLS) return set_err(h, PTG_E_INVALID, "ptg_minibatch: at most %d columns", PTG_MB_MAX_COLS);
+    if (n_cols > 0 && (!cols_host || !col_bytes_host || !cols_out_host)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: null column arrays");
+    if (!obs_dev && n_cols == 0) return set_err(h, PTG_E_INVALID, "ptg_minibatch: nothing to gather");
+    MbCols cols{};
+    cols.n = n_cols;
+    for (int c = 0; c < n_cols; c++) {
+        const int s = col_bytes_host[c];
+        if (!cols_host[c] || !cols_out_host[c]) return set_err(h, PTG_E_INVALID, "ptg_minibatch: column %d or its output is null", c);
+        if (s != 1 && s != 2 && s != 4 && s != 8) return set_err(h, PTG_E_INVALID, "ptg_minibatch: column %d has %d-byte elements (1, 2, 4 or 8)", c, s);
+        cols.src[c] = cols_host[c]; cols.dst[c] = cols_out_host[c]; cols.bytes[c] = s;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t B = (size_t)batch, N = (size_t)h->n, sz = (size_t)obs_bytes;
+    const unsigned T = (unsigned)n_steps;
+    const char* obs = (const char*)obs_dev;
+    char* out = (char*)obs_out_dev;
+    const size_t row_bytes = obs_dev ? (size_t)obs_dim * sz : 0, s_t = (size_t)obs_s_t * sz, s_n = (size_t)obs_s_n * sz;
+    // 16-byte pieces when a row is contiguous, a whole number of them, and every row starts on one -- in the buffer and in the output
+    const bool wide = obs_dev && obs_s_f == 1 && row_bytes % 16 == 0 && s_t % 16 == 0 && s_n % 16 == 0 &&
+                      (uintptr_t)obs % 16 == 0 && (uintptr_t)out % 16 == 0;
+    if (wide) launch_minibatch<uint4>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, 16, (unsigned)(row_bytes / 16), out, cols, h->P.err);
+    else if (obs_bytes == 8) launch_minibatch<uint64_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 8, (unsigned)obs_dim, out, cols, h->P.err);
+    else launch_minibatch<uint32_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 4, obs_dev ? (unsigned)obs_dim : 1u, out, cols, h->P.err);
+    return launch_check(h, "k_minibatch");
+}
+
+// ---- ReplayBuffer.add / sample on the device, over the caller's rings ------------------------------------------------
+static const char* replay_desc_error(const ptg_replay* rb)
+{
+    if (!rb) return "null descriptor";
+    if (!rb->obs_ring || !rb->next_ring || !rb->cursor_dev) return "null ring or cursor in the descriptor";
+    if (rb->capacity < 1) return "capacity < 1";
+    if (rb->obs_dim < 1 || rb->obs_dim > (1 << 20) || (rb->obs_bytes != 4 && rb->obs_bytes != 8)) return "obs_dim outside [1, 2^20] or obs_bytes other than 4 | 8";
+    if (rb->n_cols < 0 || rb->n_cols > PTG_MB_MAX_COLS) return "n_cols outside [0, 8]";
+    for (int c = 0; c < rb->n_cols; c++) {
+        const int s = rb->col_bytes[c];
+        if (!rb->col_ring[c]) return "null column ring";
+        if (s != 1 && s != 2 && s != 4 && s != 8) return "a column element size other than 1 | 2 | 4 | 8";
+    }
+    return nullptr;
+}
+
+int ptg_replay_add(ptg_env* h, const ptg_replay* rb, const void* prev_obs_dev, const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n,
+                   int64_t obs_s_f, const void* final_obs_dev, const uint8_t* done_dev, int done_col, int n_cols, const void* const* cols_host,
+                   int64_t n_steps, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (const char* why = replay_desc_error(rb)) return set_err(h, PTG_E_INVALID, "ptg_replay_add: %s", why);
+    if (!prev_obs_dev || !obs_dev) return set_err(h, PTG_E_INVALID, "ptg_replay_add: null observations");
+    if (n_steps < 1 || n_steps > rb->capacity || n_steps > 0x7FFFFFFF) return set_err(h, PTG_E_INVALID, "ptg_replay_add: n_steps outside [1, capacity]");
+    if (obs_s_t < 0 || obs_s_n < 0 || obs_s_f < 0) return set_err(h, PTG_E_INVALID, "ptg_replay_add: negative stride");
+    if (n_cols != rb->n_cols || (n_cols > 0 && !cols_host)) return set_err(h, PTG_E_INVALID, "ptg_replay_add: n_cols differs from the descriptor's, or null column array");
+    if (done_col < -1 || done_col >= n_cols) return set_err(h, PTG_E_INVALID, "ptg_replay_add: done_col outside [-1, n_cols)");
+    if (done_col >= 0 && rb->col_bytes[done_col] != 4) return set_err(h, PTG_E_INVALID, "ptg_replay_add: the done column must have 4-byte (float32) elements");
+    if ((done_col >= 0 || final_obs_dev) && !done_dev) return set_err(h, PTG_E_INVALID, "ptg_replay_add: done_dev is needed by final_obs_dev and by the done column");
+    RbAdd a{};
+    for (int c = 0; c < n_cols; c++) {
+        if (c != done_col && !cols_host[c]) return set_err(h, PTG_E_INVALID, "ptg_replay_add: column %d is null", c);
+        a.cols.src[c] = cols_host[c]; a.cols.dst[c] = rb->col_ring[c]; a.cols.bytes[c] = rb->col_bytes[c];
+    }
+    a.cols.n = n_cols;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t sz = (size_t)rb->obs_bytes, N = (size_t)h->n, row_bytes = (size_t)rb->obs_dim * sz;
+    a.prev = (const char*)prev_obs_dev; a.obs = (const char*)obs_dev; a.fin = (const char*)final_obs_dev; a.done = done_dev;
+    a.s_t = (size_t)obs_s_t * sz; a.s_n = (size_t)obs_s_n * sz; a.s_f = (size_t)obs_s_f * sz;
+    a.ring0 = (char*)rb->obs_ring; a.ring1 = (char*)rb->next_ring; a.cursor = (const unsigned long long*)rb->cursor_dev;
+    a.S = (size_t)rb->capacity; a.N = N; a.T = (unsigned)n_steps; a.F = (unsigned)rb->obs_dim; a.done_col = done_col;
+    const unsigned gy = (unsigned)std::min<int64_t>(n_steps, 65535);
+    if (obs_s_f == 1) {
+        // 16-byte pieces when a row is a whole number of them and every row starts on one, in the sources and in the rings
+        const auto al = [](const void* q) { return (uintptr_t)q % 16 == 0; };
+        const bool wide = row_bytes % 16 == 0 && a.s_t % 16 == 0 && a.s_n % 16 == 0 && al(a.prev) && al(a.obs) && al(a.fin) && al(a.ring0) && al(a.ring1);
+        const unsigned P = wide ? (unsigned)(row_bytes / 16) : (unsigned)rb->obs_dim;
+        const size_t NP = N * P;
+        const dim3 grid((unsigned)((NP + 255) / 256), gy), block(256);
+        if (wide) hipLaunchKernelGGL(k_rb_add<uint4>, grid, block, 0, st, a, P, NP);
+        else if (sz == 8) hipLaunchKernelGGL(k_rb_add<uint64_t>, grid, block, 0, st, a, P, NP);
+        else hipLaunchKernelGGL(k_rb_add<uint32_t>, grid, block, 0, st, a, P, NP);
+    } else {
+        const dim3 grid((unsigned)((N + RB_TE - 1) / RB_TE), gy), block(256);
+        if (sz == 8) hipLaunchKernelGGL(k_rb_add_tr<uint64_t>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_rb_add_tr<uint32_t>, grid, block, 0, st, a);
+    }
+    hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)rb->cursor_dev, (unsigned long long)n_steps);
+    return launch_check(h, "k_rb_add");
+}
+
+int ptg_replay_sample(ptg_env* h, const ptg_replay* rb, const int64_t* idx_dev, int64_t batch, uint64_t seed, void* obs_out_dev,
+                      void* next_obs_out_dev, void* const* cols_out_host, int norm_col, int64_t* idx_out_dev, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (const char* why = replay_desc_error(rb)) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: %s", why);
+    if (batch < 1 || batch > (int64_t)0x7FFFFFFF * (MB_ROWS * MB_WAVES)) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: batch < 1 or too large for one launch");
+    if (norm_col < -1 || norm_col >= rb->n_cols) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: norm_col outside [-1, n_cols)");
+    MbCols cols{};
+    cols.n = rb->n_cols;
+    bool any = obs_out_dev || next_obs_out_dev || idx_out_dev;
+    for (int c = 0; c < rb->n_cols; c++) {
+        cols.src[c] = rb->col_ring[c]; cols.dst[c] = cols_out_host ? cols_out_host[c] : nullptr; cols.bytes[c] = rb->col_bytes[c];
+        any = any || cols.dst[c];
+    }
+    if (!any) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: no output");
+    RbNorm norm{-1, nullptr, 0.0, 0.0};
+    if (norm_col >= 0) {
+        if (!h->vn_returns) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: norm_col needs ptg_vn_init first");
+        if (rb->col_bytes[norm_col] != (h->cfg.out_dtype == PTG_OUT_F64 ? 8 : 4))
+            return set_err(h, PTG_E_INVALID, "ptg_replay_sample: the reward column's element size differs from the handle's out_dtype");
+        if (!cols.dst[norm_col]) return set_err(h, PTG_E_INVALID, "ptg_replay_sample: norm_col names a column without an output");
+        norm = RbNorm{norm_col, h->vn_stats, h->vn_eps, h->vn_clip};
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t B = (size_t)batch, N = (size_t)h->n, row_bytes = (size_t)rb->obs_dim * (size_t)rb->obs_bytes;
+    const char *r0 = (const char*)rb->obs_ring, *r1 = (const char*)rb->next_ring;
+    char *o0 = (char*)obs_out_dev, *o1 = (char*)next_obs_out_dev;
+    const unsigned long long* cur = (const unsigned long long*)rb->cursor_dev;
+    const auto al = [](const void* q) { return (uintptr_t)q % 16 == 0; };
+    const bool wide = row_bytes % 16 == 0 && al(r0) && al(r1) && al(o0) && al(o1);
+    const dim3 grid((unsigned)((B + MB_ROWS * MB_WAVES - 1) / (MB_ROWS * MB_WAVES))), block(64 * MB_WAVES);
+    const long long* idx = (const long long*)idx_dev;
+    long long* idx_out = (long long*)idx_out_dev;
+    const size_t S = (size_t)rb->capacity;
+    if (wide) hipLaunchKernelGGL(k_rb_sample<uint4>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)(row_bytes / 16), r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
+    else if (rb->obs_bytes == 8) hipLaunchKernelGGL(k_rb_sample<uint64_t>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)rb->obs_dim, r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
+    else hipLaunchKernelGGL(k_rb_sample<uint32_t>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)rb->obs_dim, r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
+    if (!idx_dev) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)rb->cursor_dev + 1, 1ull);
+    return launch_check(h, "k_rb_sample");
+}
+
+// ---- the action head: policy outputs -> actions, log-probs, entropy ----------------------------------------------------
+int ptg_act(ptg_env* h, const ptg_head* hd, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!hd) return set_err(h, PTG_E_INVALID, "ptg_act: null head");
+    const int kind = hd->kind, flags = hd->flags;
+    if (kind != PTG_HEAD_CATEGORICAL && kind != PTG_HEAD_EPS_GREEDY && kind != PTG_HEAD_GAUSSIAN) return set_err(h, PTG_E_INVALID, "ptg_act: unknown kind %d", kind);
+    if (flags & ~(PTG_HEAD_DETERMINISTIC | PTG_HEAD_SQUASH)) return set_err(h, PTG_E_INVALID, "ptg_act: unknown flag in %d", flags);
+    const bool gauss = kind == PTG_HEAD_GAUSSIAN, det = (flags & PTG_HEAD_DETERMINISTIC) != 0, squash = (flags & PTG_HEAD_SQUASH) != 0;
+    if (squash && !gauss) return set_err(h, PTG_E_INVALID, "ptg_act: PTG_HEAD_SQUASH applies to the Gaussian head only");
+    if (!hd->in_dev || !hd->act_dev) return set_err(h, PTG_E_INVALID, "ptg_act: null input or action output");
+    if (!det && !hd->counter_dev) return set_err(h, PTG_E_INVALID, "ptg_act: a stochastic head needs counter_dev");
+    if (hd->in_dtype != PTG_OUT_F32 && hd->in_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_act: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (gauss) {
+        if (hd->in_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_act: in_s_n < 1");
+        if (hd->act_kind != PTG_ACT_F32) return set_err(h, PTG_E_INVALID, "ptg_act: the Gaussian head writes PTG_ACT_F32 actions");
+        if (!hd->param_dev) return set_err(h, PTG_E_INVALID, "ptg_act: the Gaussian head needs log_std in param_dev");
+        if (hd->param_s_n != 0 && hd->param_s_n != 1) return set_err(h, PTG_E_INVALID, "ptg_act: param_s_n must be 0 or 1");
+        if (!(hd->clip_lo <= hd->clip_hi)) return set_err(h, PTG_E_INVALID, "ptg_act: clip_lo > clip_hi (or a NaN bound)");
+        if (squash && hd->ent_dev) return set_err(h, PTG_E_INVALID, "ptg_act: a squashed Gaussian has no closed-form entropy");
+    } else {
+        if (hd->n_actions < 2 || hd->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_act: n_actions outside [2, 32]");
+        if (hd->in_s_n < hd->n_actions) return set_err(h, PTG_E_INVALID, "ptg_act: in_s_n < n_actions");
+        if (hd->act_kind != PTG_ACT_I32 && hd->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_act: a discrete head writes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (hd->raw_dev) return set_err(h, PTG_E_INVALID, "ptg_act: raw_dev is the Gaussian head's");
+        if (kind == PTG_HEAD_EPS_GREEDY) {
+            if (hd->logp_dev || hd->ent_dev) return set_err(h, PTG_E_INVALID, "ptg_act: epsilon-greedy has no log-prob or entropy");
+            if (!det && !hd->param_dev) return set_err(h, PTG_E_INVALID, "ptg_act: epsilon-greedy needs epsilon in param_dev");
+        }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    ActArgs a{};
+    a.in = hd->in_dev; a.s_n = (size_t)hd->in_s_n; a.param = hd->param_dev; a.param_s = gauss ? (size_t)hd->param_s_n : 0;
+    a.act = hd->act_dev; a.raw = hd->raw_dev; a.logp = hd->logp_dev; a.ent = hd->ent_dev;
+    a.counter = det ? nullptr : (const unsigned long long*)hd->counter_dev; a.seed = (unsigned long long)hd->seed; a.env_offset = h->P.env_offset;
+    a.lo = hd->clip_lo; a.hi = hd->clip_hi; a.N = (size_t)h->n; a.A = hd->n_actions; a.kind = kind; a.flags = flags; a.act_kind = hd->act_kind;
+    a.err = h->P.err;
+    const dim3 grid((unsigned)((a.N + ACT_BLOCK - 1) / ACT_BLOCK)), block(ACT_BLOCK);
+    if (hd->in_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_act<double>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_act<float>, grid, block, 0, st, a);
+    if (!det) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)hd->counter_dev, 1ull);
+    return launch_check(h, "k_act");
+}
+
+// ---- the policy loss: PPO / A2C loss, SB3's logged statistics and the gradients w.r.t. the network's outputs --------------
+int64_t ptg_policy_loss_workspace(int64_t batch)
+{
+    if (batch < 1) return PTG_E_INVALID;
+    if (batch > (int64_t)1 << 31) return PTG_E_INVALID;     // 2^23 blocks of 256 threads: half of the 2^32 threads one launch may have
+    const int64_t nblk = (batch - 1) / PL_BLOCK + 1;
+    return (4 + nblk * (3 + PL_PITCH)) * (int64_t)sizeof(double);
+}
+
+int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null descriptor");
+    if (d->kind != PTG_LOSS_PPO && d->kind != PTG_LOSS_A2C) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: unknown kind %d", d->kind);
+    if (d->head != PTG_HEAD_CATEGORICAL && d->head != PTG_HEAD_GAUSSIAN) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: head %d is neither categorical nor Gaussian", d->head);
+    if (d->flags & ~(PTG_LOSS_NORM_ADV | PTG_LOSS_CLIP_VF)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: unknown flag in %d", d->flags);
+    const bool ppo = d->kind == PTG_LOSS_PPO, gauss = d->head == PTG_HEAD_GAUSSIAN, clipv = (d->flags & PTG_LOSS_CLIP_VF) != 0;
+    if (ptg_policy_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (d->in_dtype != PTG_OUT_F32 && d->in_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->in_dev || !d->val_dev || !d->act_dev || !d->adv_dev || !d->ret_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null input, values, actions, advantages or returns");
+    if (ppo && !d->old_logp_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: PPO needs old_logp_dev");
+    if (!d->stats_dev || !d->grad_in_dev || !d->grad_val_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null stats_dev, grad_in_dev or grad_val_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: ws_dev is null or not aligned to 8 bytes");
+    if (clipv && !d->old_val_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: PTG_LOSS_CLIP_VF needs old_val_dev");
+    if (d->val_s_n < 1 || d->gv_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: val_s_n or gv_s_n < 1");
+    if (gauss) {
+        if (d->in_s_n < 1 || d->g_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_s_n or g_s_n < 1");
+        if (!d->log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: the Gaussian head needs log_std_dev");
+    } else {
+        if (d->n_actions < 2 || d->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: n_actions outside [2, 32]");
+        if (d->in_s_n < d->n_actions || d->g_s_n < d->n_actions) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_s_n or g_s_n < n_actions");
+        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: the categorical head takes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (d->grad_log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: grad_log_std_dev is the Gaussian head's");
+    }
+    if (ppo && !(d->clip_range >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: clip_range is negative or NaN");
+    if (clipv && !(d->clip_range_vf >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: clip_range_vf is negative or NaN");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    LossArgs a{};
+    a.in = d->in_dev; a.s_n = (size_t)d->in_s_n; a.val = d->val_dev; a.v_s = (size_t)d->val_s_n;
+    a.act = d->act_dev; a.old_lp = d->old_logp_dev; a.adv = d->adv_dev; a.ret = d->ret_dev; a.old_val = d->old_val_dev; a.log_std = d->log_std_dev;
+    a.g_in = d->grad_in_dev; a.g_s = (size_t)d->g_s_n; a.g_val = d->grad_val_dev; a.gv_s = (size_t)d->gv_s_n; a.g_ls = d->grad_log_std_dev;
+    a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.eps = d->clip_range; a.eps_v = d->clip_range_vf; a.ent_coef = d->ent_coef; a.vf_coef = d->vf_coef;
+    a.B = (size_t)d->batch; a.A = d->n_actions; a.kind = d->kind; a.head = d->head; a.flags = d->flags; a.act_kind = d->act_kind;
+    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.err = h->P.err;
+    const bool f64 = d->in_dtype == PTG_OUT_F64, norm = (d->flags & PTG_LOSS_NORM_ADV) != 0 && d->batch > 1;
+    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
+    if (a.nblk == 1) {                                       // PPO's minibatch: everything in one launch
+        if (f64) hipLaunchKernelGGL((k_pl_rows<double, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pl_rows<float, true>), grid, block, 0, st, a);
+        return launch_check(h, "k_pl_rows");
+    }
+    if (norm) {
+        if (f64) hipLaunchKernelGGL(k_pl_moments<double>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_pl_moments<float>, grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_vn_merge, dim3(1), dim3(64), 0, st, (const double*)(a.ws + 4), a.nblk, a.ws);
+    }
+    if (f64) {
+        hipLaunchKernelGGL((k_pl_rows<double, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_pl_final<double>, dim3(1), block, 0, st, a);
+    } else {
+        hipLaunchKernelGGL((k_pl_rows<float, false>), grid, block, 0, st, a);
+        hipLaunchKernelGGL(k_pl_final<float>, dim3(1), block, 0, st, a);
+    }
+    return launch_check(h, "k_pl_rows");
+}
+
+}  // extern "C"

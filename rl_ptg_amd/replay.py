@@ -1,7 +1,7 @@
 """DeviceReplayBuffer: the replay buffer the reference's off-policy algorithms (DQN, TD3, SAC, TQC) train from, resident on the GPU.
 
 It restates stable-baselines3 2.0.0a13 common/buffers.py ReplayBuffer (optimize_memory_usage off) over torch tensors that never leave
-the device: add() and sample() each enqueue kernels of csrc/ptg_env.hip (ptg_replay_add, ptg_replay_sample in include/ptg_env.h) on
+the device: add() and sample() each enqueue kernels of csrc/ptg_train.hip (ptg_replay_add, ptg_replay_sample in include/ptg_env.h) on
 the current stream, without synchronisation, so a collect -> store -> sample step can be captured into one graph behind
 HipEngine.step().  The write position lives on the device (cursor), like the step count of the hot kernels.
 """

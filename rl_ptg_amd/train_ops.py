@@ -1,6 +1,6 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
 action heads and the policy loss.  Each method checks its tensors, marshals pointers and strides and makes one library call
-(include/ptg_env.h states the arithmetic); none of them steps the environment.  HipEngine inherits them.
+(include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
 _action_kind; torch stays lazily imported (torch = self._torch).

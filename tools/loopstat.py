@@ -1,5 +1,6 @@
 """Instruction mix of the loops that contain a barrier in one kernel of a hipcc -S listing (the producer / consumer loops of k_rollout_pc):
-python tools/loopstat.py <file.s> [regex of the kernel symbol line].  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DPTG_PART=1 --cuda-device-only -S ..."""
+python tools/loopstat.py <file.s> [regex of the kernel symbol line].  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DPTG_PART=1 --cuda-device-only -S rl_ptg_amd/csrc/ptg_env.hip
+(a training kernel: the same line without -DPTG_PART on rl_ptg_amd/csrc/ptg_train.hip)."""
 import re,collections,sys
 lines=open(sys.argv[1]).read().split('\n')
 pat=sys.argv[2] if len(sys.argv)>2 else r'^_ZN12_GLOBAL__N_112k_rollout_pcILi0ELb1ELi2ELb1ELb1EfLb0E.*:'
