@@ -38,7 +38,9 @@ extern "C" {
                              * 10: + ptg_minibatch, PTG_E_INDEX (shuffled minibatches gathered from the rollout buffers on the device);
                              * 11: + ptg_replay, ptg_replay_add, ptg_replay_sample (the off-policy algorithms' replay buffer on the device);
                              * 12: + ptg_head, ptg_act, PTG_E_NONFINITE (policy outputs to actions, log-probs and entropy in one launch);
-                             * 13: + ptg_loss, ptg_policy_loss, ptg_policy_loss_workspace (the PPO / A2C loss and its gradients in one pass) */
+                             * 13: + ptg_loss, ptg_policy_loss, ptg_policy_loss_workspace (the PPO / A2C loss and its gradients in one pass);
+                             *     additive, version unchanged: + ptg_optim, ptg_optim_step, ptg_optim_workspace, ptg_optim_chunk (the optimiser step behind
+                             *     the loss: grad-norm clip, Adam / RMSprop, Polyak, zero_grad); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -574,8 +576,9 @@ int ptg_act(ptg_env* env, const ptg_head* head, void* stream);
  * graph: some forty element-wise launches forward and as many backward.  Every gradient of these losses with respect to the
  * network's outputs is a closed form of quantities the forward pass holds, so one pass emits the loss, the statistics SB3 logs,
  * d loss / d logits (or means), d loss / d values and d loss / d log_std; the caller's backward starts from those
- * (rl_ptg_amd/loss.py wraps the call in a torch.autograd.Function).  Out of scope: the networks, the optimiser, max_grad_norm,
- * target_kl's early stop (the caller reads stats[4]), gSDE, the squashed and off-policy losses, a per-env log_std.
+ * (rl_ptg_amd/loss.py wraps the call in a torch.autograd.Function).  Out of scope: the networks, target_kl's early stop (the
+ * caller reads stats[4]), gSDE, the squashed and off-policy losses, a per-env log_std.  The optimiser and max_grad_norm follow the
+ * backward pass as ptg_optim_step, below.
  * The call is described by a ptg_loss, read during the call (B = batch, A = n_actions):
  *   kind          PTG_LOSS_PPO | PTG_LOSS_A2C
  *   head          PTG_HEAD_CATEGORICAL | PTG_HEAD_GAUSSIAN (unsquashed, D = 1, as in ptg_act)
@@ -672,6 +675,109 @@ typedef struct ptg_loss {
 } ptg_loss;
 int64_t ptg_policy_loss_workspace(int64_t batch);
 int ptg_policy_loss(ptg_env* env, const ptg_loss* d, void* stream);
+
+/* ---- the optimiser step: grad-norm clip, Adam / RMSprop, Polyak and zero_grad for all tensors of an optimiser --------------------
+ * Replaces what the reference's agents (src/rl_config_agent.py; SB3 2.0.0a13 on torch) run behind loss.backward() on every minibatch:
+ * torch.nn.utils.clip_grad_norm_(params, max_grad_norm), optimizer.step() of torch.optim.Adam (PPO, DQN, TD3, SAC, TQC) or RMSprop
+ * (A2C), optimizer.zero_grad(), and -- TD3 / SAC / TQC after every gradient step, DQN every target_update_interval -- SB3's
+ * polyak_update(params, targets, tau).  ALL parameter tensors of one optimiser take the step in a chain of at most three launches,
+ * whatever their number: the tensor list does not travel in the launch arguments but in two caller-owned device tables.
+ *   ptg_optim_tensor [n_tensors]   one record per tensor: device pointers to the parameter, its gradient, state 1 (Adam: exp_avg;
+ *                 RMSprop: square_avg), state 2 (Adam: exp_avg_sq; else unused), its target (with PTG_OPTIM_TARGETS / PTG_OPTIM_POLYAK;
+ *                 else unused) -- each `numel` contiguous elements of the descriptor's dtype; unused pointers are NULL
+ *   ptg_optim_span [n_chunks]      one record per chunk: the index of its tensor and the element offset of the chunk in it.  A chunk is
+ *                 C = 1024 consecutive elements of one tensor (the value ptg_optim_chunk returns); a tensor of numel elements has
+ *                 ceil(numel / C) chunks at offsets 0, C, 2 C ..., the last one ragged.  One workgroup of 256 threads owns one chunk,
+ *                 thread t its elements 4 t .. 4 t + 3.  C = 1024: PPO's 0.3 M parameters make some 300 chunks, more than the 256 CUs
+ * The library cannot check what the tables point at: that every pointer covers numel elements, that the spans tile the tensors exactly
+ * once -- every offset a multiple of C, every multiple of C below numel present -- and that no two tensors overlap is the caller's
+ * contract (rl_ptg_amd/train_ops.py builds the tables from checked tensors).  A span whose tensor index is outside [0, n_tensors) or
+ * whose offset is negative or no multiple of C (the 16-byte accesses rest on that) never becomes an address: it is skipped and the
+ * next ptg_sync returns PTG_E_INDEX once.  Elements move as 16-byte pieces where every base a chunk uses is 16-byte aligned, else one by one: a
+ * parameter may be a view at an odd element offset of a flat buffer.  Addressing is size_t throughout.
+ * The call is described by a ptg_optim, read during the call:
+ *   kind          PTG_OPTIM_ADAM | PTG_OPTIM_RMSPROP | PTG_OPTIM_POLYAK (targets only: no gradient, no state, one launch)
+ *   flags         PTG_OPTIM_CLIP: clip by the total norm (max_norm).  PTG_OPTIM_TARGETS: also move the targets (tau).
+ *                 PTG_OPTIM_ZERO_GRAD: write 0 to every gradient element after reading it (zero_grad(set_to_none=False): the
+ *                 gradient pointers stay valid for the next replay).  PTG_OPTIM_POLYAK takes neither CLIP nor ZERO_GRAD
+ *   dtype         PTG_OUT_F32 | PTG_OUT_F64: the ONE element type of every parameter, gradient, state and target tensor
+ *   n_tensors, n_chunks, tensors_dev, chunks_dev   the two tables, 8-byte aligned
+ *   state_dev     float64 [4] on the device = {t, beta1^t, beta2^t, spare}: the step count and the running products, {0, 1, 1, 0}
+ *                 before the first step.  They advance on the device, by one multiplication per call, so a replayed graph takes step
+ *                 t + 1.  RMSprop advances t only
+ *   lr_dev        float64 [1] on the device, read when the kernel runs (anneal it in place between replays); NULL: the host double lr
+ *   norm_dev      float64 [1] on the device: receives the total norm, the value clip_grad_norm_ returns.  Required with PTG_OPTIM_CLIP,
+ *                 not written without it
+ *   ws_dev        caller-owned device scratch, 8-byte aligned, at least ptg_optim_workspace(n_chunks) bytes; its contents mean
+ *                 nothing before or after the call.  PTG_OPTIM_POLYAK does not use it
+ *   lr, beta1, beta2, eps, alpha, tau, max_norm   host doubles; a captured call keeps them
+ * Arithmetic.  Every element is loaded, converted to float64, computed in float64 with every operation rounded once (no fused
+ * multiply-add; sqrt and the division are the correctly rounded ones) and rounded once to dtype on the store; the operand order is
+ * torch's (CPU kernels).  g = (double)grad[i], and likewise m, v, s, p, q for exp_avg, exp_avg_sq, square_avg, parameter, target:
+ *   total norm    with PTG_OPTIM_CLIP, clip_grad_norm_'s L2 norm with error_if_nonfinite=False: total = sqrt(sum g * g) over every element
+ *                 of every gradient, in float64 in a fixed order -- thread t of a chunk adds its four squares in element order
+ *                 (to 0.0), a shuffle tree over the wave's 64 lanes (xor 32, 16, 8, 4, 2, 1), the chunk's four waves in wave order, one
+ *                 partial per chunk in ws_dev; then one workgroup in which thread u adds the partials of chunks u, u + 256, ... in that
+ *                 order, the same tree, the four waves in wave order.  No floating-point atomics: the same inputs give the same bits
+ *                 on every run, and the order depends on the tables alone.  A partial sum passes through at most
+ *                 d = 22 + ceil(n_chunks / 256) roundings (1 square + 3, 6, 3 additions in the chunk; ceil(n_chunks / 256), 6, 3 after)
+ *                 coef = min(max_norm / (total + 1e-6), 1.0) (torch.clamp: a NaN stays);  g' = g * coef.  Without PTG_OPTIM_CLIP there is
+ *                 no norm pass and coef = 1.0 (g' = g exactly).  Known difference: the gradient tensors are NOT rewritten with
+ *                 g'; no caller reads them after the step, and g' is not rounded to dtype on its way into the update
+ *   Adam          torch.optim.Adam's single-tensor lines, no amsgrad, weight decay or maximize:
+ *                 t += 1;  P1 = P1 * beta1;  P2 = P2 * beta2  (the running products in state_dev; torch evaluates beta ** t -- known
+ *                 difference, a few ulp);  step_size = lr / (1 - P1);  bc2 = sqrt(1 - P2)
+ *                 m = beta1 * m + (1 - beta1) * g'  (torch's lerp form m + (g' - m) * (1 - beta1) differs by an ulp: known difference)
+ *                 v = beta2 * v + ((1 - beta2) * g') * g'
+ *                 p = p + ((-step_size) * m) / (sqrt(v) / bc2 + eps)          with the unrounded m and v of this step
+ *   RMSprop       torch.optim.RMSprop without momentum, not centered, no weight decay:
+ *                 s = alpha * s + ((1 - alpha) * g') * g';   p = p + ((-lr) * g') / (sqrt(s) + eps)
+ *   Polyak        SB3's polyak_update: q = (1 - tau) * q + tau * p, with p the parameter AS STORED by this call (rounded to dtype), so
+ *                 the fused call equals the step followed by a PTG_OPTIM_POLYAK call, bit for bit.  tau = 1 copies a finite parameter
+ *                 onto a finite target (DQN's hard update), as SB3's lines do: -0.0 arrives as +0.0 over a positive target, and a
+ *                 non-finite target stays poisoned (0 * Inf)
+ * Non-finite gradients propagate as the arithmetic says, as they do in torch.  A non-finite total norm, or without a norm pass a
+ * non-finite gradient element, makes the next ptg_sync return PTG_E_NONFINITE once (its text names the calls that share that word).
+ * Enqueues kernels only: the norm pass (with PTG_OPTIM_CLIP), a one-workgroup head kernel that merges the partials, advances
+ * state_dev and writes the scalars of the update, and the update -- three launches, two without clipping, one for PTG_OPTIM_POLYAK --
+ * with no host synchronisation and no allocation, so the call may be captured into a hipGraph and replayed.  Reads nothing of the
+ * handle but its device: env state, the finished-episode ring, the ptg_vn_* statistics and every replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle or descriptor; an unknown kind, flag or dtype; PTG_OPTIM_POLYAK with PTG_OPTIM_CLIP
+ * or PTG_OPTIM_ZERO_GRAD; n_tensors < 1; n_chunks outside [1, 2^31); a NULL or misaligned table; tau outside [0, 1] or NaN (with
+ * targets); and for the two optimisers a NULL state_dev, a NULL or misaligned ws_dev, a negative or non-finite lr (with lr_dev NULL)
+ * or eps, a beta outside [0, 1) (Adam), a negative or non-finite alpha (RMSprop), PTG_OPTIM_CLIP without norm_dev or with a negative
+ * or NaN max_norm.
+ * ptg_optim_workspace(n_chunks): bytes of scratch (8 per chunk + 32); negative for n_chunks outside [1, 2^31).
+ * ptg_optim_chunk(): C, so that callers and tests find the chunk edges without hard-coding it. */
+enum { PTG_OPTIM_ADAM = 0, PTG_OPTIM_RMSPROP = 1, PTG_OPTIM_POLYAK = 2 };
+enum { PTG_OPTIM_CLIP = 1, PTG_OPTIM_TARGETS = 2, PTG_OPTIM_ZERO_GRAD = 4 };
+typedef struct ptg_optim_tensor {
+    void* param;
+    void* grad;
+    void* state1;
+    void* state2;
+    void* target;
+    int64_t numel;
+} ptg_optim_tensor;
+typedef struct ptg_optim_span {
+    int64_t tensor;
+    int64_t offset;
+} ptg_optim_span;
+typedef struct ptg_optim {
+    int32_t kind, flags;
+    int32_t dtype, reserved;
+    int64_t n_tensors, n_chunks;
+    const void* tensors_dev;
+    const void* chunks_dev;
+    double* state_dev;
+    const double* lr_dev;
+    double* norm_dev;
+    void* ws_dev;
+    double lr, beta1, beta2, eps, alpha, tau, max_norm;
+} ptg_optim;
+int ptg_optim_chunk(void);
+int64_t ptg_optim_workspace(int64_t n_chunks);
+int ptg_optim_step(ptg_env* env, const ptg_optim* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -1,10 +1,10 @@
 """rl_ptg_amd: MI355X-native batched Power-to-Gas environment (HIP kernels behind a C ABI, SB3 VecEnv surface).
 
-    from rl_ptg_amd import PtGVecEnv, PTGEnv, HipEngine, DeviceReplayBuffer, EnvConfig, Preprocessing, EnvSpec
+    from rl_ptg_amd import PtGVecEnv, PTGEnv, HipEngine, DeviceReplayBuffer, DeviceOptimizer, EnvConfig, Preprocessing, EnvSpec
 """
 __version__ = "0.1.0"
 
-_LAZY = {"PtGVecEnv": "vec_env", "PTGEnv": "vec_env", "HipEngine": "engine", "PtgError": "engine", "CategoricalAct": "engine", "EpsGreedyAct": "engine", "GaussianAct": "engine", "PolicyLoss": "engine", "ppo_loss": "loss", "a2c_loss": "loss", "DeviceReplayBuffer": "replay", "ReplayStorage": "replay", "ReplaySamples": "replay", "EnvConfig": "config",
+_LAZY = {"PtGVecEnv": "vec_env", "PTGEnv": "vec_env", "HipEngine": "engine", "PtgError": "engine", "CategoricalAct": "engine", "EpsGreedyAct": "engine", "GaussianAct": "engine", "PolicyLoss": "engine", "ppo_loss": "loss", "a2c_loss": "loss", "DeviceOptimizer": "optim", "OptimPlan": "train_ops", "DeviceReplayBuffer": "replay", "ReplayStorage": "replay", "ReplaySamples": "replay", "EnvConfig": "config",
          "Preprocessing": "prep", "EnvSpec": "prep", "synthetic_spec": "prep", "load_op_tables": "tables", "load_data": "market", "import_market_data": "market"}
 
 

@@ -9,6 +9,7 @@
 //   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
 //   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
 //   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
+//   k_optim_*         clip_grad_norm_, torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad over all tensors of an optimiser.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "ptg_handle.h"
 
@@ -872,6 +873,205 @@ k_pl_final(LossArgs a)
     }
 }
 
+// ================================================================================== the optimiser step
+// What runs behind loss.backward() (include/ptg_env.h, ptg_optim_step, states the lines; tests/optim_restatement.py restates them in
+// NumPy): torch's clip_grad_norm_, the single-tensor lines of torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad, for ALL
+// parameter tensors of an optimiser in a chain of launches whose length does not depend on the tensor count.  The tensor list lives in
+// two caller-owned device tables: one ptg_optim_tensor per tensor, one ptg_optim_span per chunk of OPT_CHUNK consecutive elements of
+// one tensor.  One workgroup owns one chunk; thread t owns its elements 4 t .. 4 t + 3 -- one 16-byte piece in float32, two in float64
+// -- and moves them as such when every base of the chunk is 16-byte aligned, else element by element (a view at an odd offset of a flat
+// buffer).  Arithmetic in float64 whatever the tensors' type, rounded once on the store.
+//   k_optim_norm    sum of g * g per chunk: the lane's four terms in order, a shuffle tree, the four waves in wave order -> ws[4 + chunk]
+//   k_optim_head    one block: the partials in an order given by the chunk count alone -> total norm, clip coefficient; advances the
+//                   step count and the running beta products; writes the float64 scalars k_optim_update reads.  A kernel of its own,
+//                   so that no block of the update can meet a half-advanced state
+//   k_optim_update  clip, moments, parameter, target, zeroed gradient: every element read once and written once
+// No floating-point atomics, no grid-wide wait: the same inputs give the same bits.
+constexpr int OPT_BLOCK = 256, OPT_PER = 4, OPT_CHUNK = OPT_BLOCK * OPT_PER, OPT_WAVES = OPT_BLOCK / 64, OPT_WS_HEAD = 4;
+
+struct OptArgs {                         // by value in the launch: a captured call holds no host memory
+    const ptg_optim_tensor* tensors;
+    const ptg_optim_span* chunks;
+    double* ws;                          // [0] clip coefficient, [1] step size, [2] sqrt(1 - beta2^t), [3] spare; [4 ..) one partial per chunk
+    double* state;                       // {t, beta1^t, beta2^t, spare}
+    const double* lr_dev;
+    double* norm;
+    double lr, b1, b2, eps, alpha, tau, max_norm;
+    long long n_tensors;
+    unsigned n_chunks;
+    int kind, flags;
+    int* err;
+};
+
+// the chunk of this block: false when its record names no tensor of the table or an offset that is no multiple of OPT_CHUNK (never an
+// address; err[4])
+__device__ __forceinline__ bool opt_chunk(const OptArgs& a, ptg_optim_tensor& t, size_t& e0, int& n)
+{
+    const ptg_optim_span c = a.chunks[blockIdx.x];
+    if (c.tensor < 0 || c.tensor >= a.n_tensors || c.offset < 0 || c.offset % OPT_CHUNK != 0) { a.err[4] = 1; return false; }
+    t = a.tensors[c.tensor];
+    const size_t off = (size_t)c.offset, numel = t.numel > 0 ? (size_t)t.numel : 0;
+    e0 = off + (size_t)threadIdx.x * OPT_PER;
+    n = e0 < numel ? (int)min((size_t)OPT_PER, numel - e0) : 0;            // this thread's live elements: 4, or fewer in a ragged last chunk
+    return true;
+}
+
+__device__ __forceinline__ bool opt_al16(const void* base) { return ((uintptr_t)base & 15u) == 0; }      // a null (unused) base passes
+
+template <typename T>
+__device__ __forceinline__ void opt_load(const void* base, size_t e0, int n, bool wide, double* x)
+{
+    const T* p = (const T*)base + e0;
+    if (wide && n == OPT_PER) {
+        if (sizeof(T) == 4) {
+            const float4 q = *(const float4*)p;
+            x[0] = (double)q.x; x[1] = (double)q.y; x[2] = (double)q.z; x[3] = (double)q.w;
+        } else {
+            const double2 q0 = ((const double2*)p)[0], q1 = ((const double2*)p)[1];
+            x[0] = q0.x; x[1] = q0.y; x[2] = q1.x; x[3] = q1.y;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < OPT_PER; j++) x[j] = j < n ? (double)p[j] : 0.0;
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void opt_store(void* base, size_t e0, int n, bool wide, const double* x)
+{
+    T* p = (T*)base + e0;
+    if (wide && n == OPT_PER) {
+        if (sizeof(T) == 4) {
+            *(float4*)p = make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
+        } else {
+            ((double2*)p)[0] = make_double2(x[0], x[1]);
+            ((double2*)p)[1] = make_double2(x[2], x[3]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < OPT_PER; j++)
+            if (j < n) p[j] = (T)x[j];
+    }
+}
+
+// the block's sum: a shuffle tree per wave, then the waves in wave order (thread 0 holds the result)
+__device__ __forceinline__ double opt_block_sum(double v, double* sh)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    v = pl_wave_sum(v);
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0) {
+        s = sh[0];
+        for (int q = 1; q < OPT_WAVES; q++) s += sh[q];
+    }
+    return s;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(OPT_BLOCK)
+k_optim_norm(OptArgs a)
+{
+    __shared__ double sh[OPT_WAVES];
+    ptg_optim_tensor t; size_t e0; int n;
+    const bool ok = opt_chunk(a, t, e0, n);                  // block-uniform
+    double s = 0.0;
+    if (ok && n > 0) {
+        double g[OPT_PER];
+        opt_load<T>(t.grad, e0, n, opt_al16(t.grad), g);
+#pragma unroll
+        for (int j = 0; j < OPT_PER; j++) s += g[j] * g[j];  // a dead element adds +0.0
+    }
+    s = opt_block_sum(s, sh);
+    if (threadIdx.x == 0) a.ws[OPT_WS_HEAD + blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(OPT_BLOCK)
+k_optim_head(OptArgs a)
+{
+    __shared__ double sh[OPT_WAVES];
+    const bool clip = (a.flags & PTG_OPTIM_CLIP) != 0;
+    double s = 0.0;
+    if (clip)
+        for (unsigned c = threadIdx.x; c < a.n_chunks; c += OPT_BLOCK) s += a.ws[OPT_WS_HEAD + c];
+    s = opt_block_sum(s, sh);
+    if (threadIdx.x != 0) return;
+    double coef = 1.0;
+    if (clip) {
+        const double total = sqrt(s);
+        a.norm[0] = total;
+        const double c = a.max_norm / (total + 1e-6);
+        coef = c > 1.0 ? 1.0 : c;                            // torch.clamp(max=1.0): a NaN stays
+        if (!pl_finite(total)) a.err[5] = 1;
+    }
+    const double lr = a.lr_dev ? a.lr_dev[0] : a.lr;
+    a.ws[0] = coef;
+    if (a.kind == PTG_OPTIM_ADAM) {
+        const double t = a.state[0] + 1.0, p1 = a.state[1] * a.b1, p2 = a.state[2] * a.b2;
+        a.state[0] = t; a.state[1] = p1; a.state[2] = p2;
+        a.ws[1] = lr / (1.0 - p1);                           // step_size = lr / bias_correction1
+        a.ws[2] = sqrt(1.0 - p2);                            // bias_correction2_sqrt
+    } else {
+        a.state[0] = a.state[0] + 1.0;
+        a.ws[1] = lr;
+        a.ws[2] = 1.0;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(OPT_BLOCK)
+k_optim_update(OptArgs a)
+{
+    ptg_optim_tensor t; size_t e0; int n;
+    if (!opt_chunk(a, t, e0, n) || n == 0) return;
+    const bool polyak = a.kind == PTG_OPTIM_POLYAK, adam = a.kind == PTG_OPTIM_ADAM;
+    const bool targets = polyak || (a.flags & PTG_OPTIM_TARGETS) != 0;
+    const void* s2 = adam ? t.state2 : nullptr;
+    const void* tg = targets ? t.target : nullptr;
+    // a chunk starts a multiple of OPT_CHUNK elements into its tensor (opt_chunk refuses any other offset) and a thread a multiple of
+    // four elements into the chunk, so the tensors' bases decide the alignment of every 16-byte piece
+    const bool wide = opt_al16(t.param) && opt_al16(polyak ? nullptr : t.grad) && opt_al16(polyak ? nullptr : t.state1) && opt_al16(s2) && opt_al16(tg);
+    double p[OPT_PER];
+    opt_load<T>(t.param, e0, n, wide, p);
+    if (!polyak) {
+        const double coef = a.ws[0], ss = a.ws[1], bc2 = a.ws[2];
+        double g[OPT_PER], m[OPT_PER], v[OPT_PER];
+        opt_load<T>(t.grad, e0, n, wide, g);
+        opt_load<T>(t.state1, e0, n, wide, m);
+        if (adam) opt_load<T>(t.state2, e0, n, wide, v);
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < OPT_PER; j++) {
+            bad = bad || !pl_finite(g[j]);
+            const double gp = g[j] * coef;                   // coef == 1.0 without clipping: the gradient itself
+            if (adam) {
+                m[j] = a.b1 * m[j] + (1.0 - a.b1) * gp;
+                v[j] = a.b2 * v[j] + ((1.0 - a.b2) * gp) * gp;
+                const double denom = sqrt(v[j]) / bc2 + a.eps;
+                p[j] = p[j] + ((-ss) * m[j]) / denom;
+            } else {                                         // RMSprop: state1 is square_avg
+                m[j] = a.alpha * m[j] + ((1.0 - a.alpha) * gp) * gp;
+                const double avg = sqrt(m[j]) + a.eps;
+                p[j] = p[j] + ((-ss) * gp) / avg;
+            }
+            g[j] = 0.0;
+        }
+        if (bad && !(a.flags & PTG_OPTIM_CLIP)) a.err[5] = 1;      // with a norm pass the head kernel reports it: total is not finite
+        opt_store<T>(t.param, e0, n, wide, p);
+        opt_store<T>(t.state1, e0, n, wide, m);
+        if (adam) opt_store<T>(t.state2, e0, n, wide, v);
+        if (a.flags & PTG_OPTIM_ZERO_GRAD) opt_store<T>(t.grad, e0, n, wide, g);
+    }
+    if (targets) {
+        double q[OPT_PER];
+        opt_load<T>(t.target, e0, n, wide, q);
+#pragma unroll
+        for (int j = 0; j < OPT_PER; j++) q[j] = (1.0 - a.tau) * q[j] + a.tau * (double)(T)p[j];      // the parameter as it was just stored
+        opt_store<T>(t.target, e0, n, wide, q);
+    }
+}
+
 // ================================================================================================= host side
 // ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
 template <typename V>
@@ -1266,6 +1466,62 @@ int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
         hipLaunchKernelGGL(k_pl_final<float>, dim3(1), block, 0, st, a);
     }
     return launch_check(h, "k_pl_rows");
+}
+
+// ---- the optimiser step: grad-norm clip, Adam / RMSprop, Polyak and zero_grad for all tensors of an optimiser -----------
+int ptg_optim_chunk(void) { return OPT_CHUNK; }
+
+int64_t ptg_optim_workspace(int64_t n_chunks)
+{
+    if (n_chunks < 1 || n_chunks > 0x7FFFFFFF) return PTG_E_INVALID;      // one workgroup per chunk: the grid's x dimension
+    return (OPT_WS_HEAD + n_chunks) * (int64_t)sizeof(double);
+}
+
+int ptg_optim_step(ptg_env* h, const ptg_optim* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_optim_step: null descriptor");
+    const int kind = d->kind, flags = d->flags;
+    if (kind != PTG_OPTIM_ADAM && kind != PTG_OPTIM_RMSPROP && kind != PTG_OPTIM_POLYAK) return set_err(h, PTG_E_INVALID, "ptg_optim_step: unknown kind %d", kind);
+    if (flags & ~(PTG_OPTIM_CLIP | PTG_OPTIM_TARGETS | PTG_OPTIM_ZERO_GRAD)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: unknown flag in %d", flags);
+    const bool polyak = kind == PTG_OPTIM_POLYAK, clip = (flags & PTG_OPTIM_CLIP) != 0, targets = polyak || (flags & PTG_OPTIM_TARGETS) != 0;
+    if (polyak && (flags & (PTG_OPTIM_CLIP | PTG_OPTIM_ZERO_GRAD))) return set_err(h, PTG_E_INVALID, "ptg_optim_step: PTG_OPTIM_POLYAK reads no gradient: no PTG_OPTIM_CLIP, no PTG_OPTIM_ZERO_GRAD");
+    if (d->dtype != PTG_OUT_F32 && d->dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_optim_step: dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (d->n_tensors < 1) return set_err(h, PTG_E_INVALID, "ptg_optim_step: n_tensors < 1");
+    if (ptg_optim_workspace(d->n_chunks) < 0) return set_err(h, PTG_E_INVALID, "ptg_optim_step: n_chunks %lld outside [1, 2^31)", (long long)d->n_chunks);
+    if (!d->tensors_dev || !d->chunks_dev) return set_err(h, PTG_E_INVALID, "ptg_optim_step: null tensor or chunk table");
+    if ((uintptr_t)d->tensors_dev % 8 != 0 || (uintptr_t)d->chunks_dev % 8 != 0) return set_err(h, PTG_E_INVALID, "ptg_optim_step: a table is not aligned to 8 bytes");
+    if (targets && !(d->tau >= 0.0 && d->tau <= 1.0)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: tau outside [0, 1] (or NaN)");
+    if (!polyak) {
+        if (!d->state_dev) return set_err(h, PTG_E_INVALID, "ptg_optim_step: null state_dev");
+        if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_optim_step: ws_dev is null or not aligned to 8 bytes");
+        if (!d->lr_dev && !(d->lr >= 0.0 && std::isfinite(d->lr))) return set_err(h, PTG_E_INVALID, "ptg_optim_step: lr is negative or not finite (and lr_dev is null)");
+        if (!(d->eps >= 0.0) || !std::isfinite(d->eps)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: eps is negative or not finite");
+        if (kind == PTG_OPTIM_ADAM && (!(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0)))
+            return set_err(h, PTG_E_INVALID, "ptg_optim_step: a beta outside [0, 1)");
+        if (kind == PTG_OPTIM_RMSPROP && !(d->alpha >= 0.0 && std::isfinite(d->alpha))) return set_err(h, PTG_E_INVALID, "ptg_optim_step: alpha is negative or not finite");
+        if (clip && !d->norm_dev) return set_err(h, PTG_E_INVALID, "ptg_optim_step: PTG_OPTIM_CLIP needs norm_dev");
+        if (clip && !(d->max_norm >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: max_norm is negative or NaN");
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    OptArgs a{};
+    a.tensors = (const ptg_optim_tensor*)d->tensors_dev; a.chunks = (const ptg_optim_span*)d->chunks_dev;
+    a.ws = (double*)d->ws_dev; a.state = d->state_dev; a.lr_dev = d->lr_dev; a.norm = d->norm_dev;
+    a.lr = d->lr; a.b1 = d->beta1; a.b2 = d->beta2; a.eps = d->eps; a.alpha = d->alpha; a.tau = d->tau; a.max_norm = d->max_norm;
+    a.n_tensors = (long long)d->n_tensors; a.n_chunks = (unsigned)d->n_chunks; a.kind = kind; a.flags = flags; a.err = h->P.err;
+    const bool f64 = d->dtype == PTG_OUT_F64;
+    const dim3 grid((unsigned)d->n_chunks), block(OPT_BLOCK);
+    if (!polyak) {
+        if (clip) {
+            if (f64) hipLaunchKernelGGL(k_optim_norm<double>, grid, block, 0, st, a);
+            else hipLaunchKernelGGL(k_optim_norm<float>, grid, block, 0, st, a);
+        }
+        hipLaunchKernelGGL(k_optim_head, dim3(1), block, 0, st, a);
+    }
+    if (f64) hipLaunchKernelGGL(k_optim_update<double>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_optim_update<float>, grid, block, 0, st, a);
+    return launch_check(h, "k_optim_update");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads and the policy loss.  Each method checks its tensors, marshals pointers and strides and makes one library call
+action heads, the policy loss and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
@@ -22,6 +22,13 @@ EpsGreedyAct = collections.namedtuple("EpsGreedyAct", "actions")
 GaussianAct = collections.namedtuple("GaussianAct", "actions raw log_prob entropy")
 # what policy_loss returns: stats float64 [8], the gradients w.r.t. the head's input, the values and (Gaussian head) log_std
 PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values grad_log_std")
+
+
+class OptimPlan:
+    """What optim_plan makes of an optimiser's tensor lists: the checked tensors (kept alive here: the device tables hold their
+    addresses), the state tensors, the two device tables, the float64 device scalars and the scratch of ptg_optim_step."""
+    __slots__ = ("kind", "dtype", "params", "grads", "targets", "state1", "state2", "state", "norm", "tensors_dev", "chunks_dev", "workspace",
+                 "n_chunks", "grad_ptrs")
 
 
 # ------------------------------------------------------------------ stride rules: None when x obeys, else what was expected
@@ -579,3 +586,158 @@ class TrainOps:
         with torch.cuda.device(self.device):
             self._chk(self._L.ptg_policy_loss(self._h, C.byref(d), self._stream()))
         return PolicyLoss(stats, g_in, g_val, g_ls)
+
+    # ------------------------------------------------------------------ the optimiser step behind loss.backward()
+    def optim_chunk(self):
+        """elements per chunk of the optimiser kernels (one workgroup each)"""
+        return int(self._L.ptg_optim_chunk())
+
+    def optim_plan(self, params, grads, kind, targets=None, state=None):
+        """Check the tensor lists of one optimiser and build what optim_step needs (include/ptg_env.h: ptg_optim_step): params, grads
+        (None for kind "polyak") and targets (optional) are lists of contiguous tensors of ONE float dtype (float32 or float64) on the
+        engine's device, grads[k] and targets[k] shaped like params[k]; a parameter may be a view into a flat buffer at any element
+        offset.  kind: "adam" | "rmsprop" | "polyak".  Allocates the zeroed state tensors (state: an earlier plan of the same
+        parameters whose state is taken over instead -- the gradients moved), the device scalars {t, beta1^t, beta2^t} and the total
+        norm, the scratch, and uploads the tensor and chunk tables.  Returns an OptimPlan; it keeps every tensor alive.  Not for use
+        under stream capture (it allocates and copies)."""
+        torch = self._torch
+        who = "optim_plan"
+        if kind not in ("adam", "rmsprop", "polyak"):
+            raise ValueError(f"{who}: kind must be 'adam', 'rmsprop' or 'polyak', got {kind!r}")
+        polyak = kind == "polyak"
+        params = list(params)
+        grads = None if grads is None else list(grads)
+        targets = None if targets is None else list(targets)
+        floats = (torch.float32, torch.float64)
+        for k, p in enumerate(params):                      # TypeError first: what every value is
+            if not torch.is_tensor(p) or p.dtype not in floats:
+                check(self, who, f"params[{k}]", p, dtypes=floats)
+        dt = (params[0].dtype,) if params else floats
+        lists = [("params", params), ("grads", grads), ("targets", targets)]
+        if state is not None:
+            lists += [(name, xs) for name, xs in (("state.state1", state.state1), ("state.state2", state.state2)) if xs]
+        for name, xs in lists:
+            for k, x in enumerate(xs or ()):
+                if x is None and name == "grads":
+                    continue                                # refused below, as a ValueError
+                if not torch.is_tensor(x) or x.dtype not in dt:
+                    check(self, who, f"{name}[{k}]", x, dtypes=dt)
+        if not params:
+            raise ValueError(f"{who}: an empty parameter list")
+        if polyak and grads is not None:
+            raise ValueError(f"{who}: kind 'polyak' takes no gradients")
+        if not polyak and grads is None:
+            raise ValueError(f"{who}: kind {kind!r} needs the gradients")
+        if polyak and targets is None:
+            raise ValueError(f"{who}: kind 'polyak' needs targets")
+        for name, xs in lists[1:]:
+            if xs is not None and len(xs) != len(params):
+                raise ValueError(f"{who}: {len(params)} parameters but {len(xs)} {name}")
+        for k, p in enumerate(params):
+            check(self, who, f"params[{k}]", p, dtypes=dt, rule=contiguous)
+            if p.numel() < 1:
+                raise ValueError(f"{who}: params[{k}] is empty")
+            for name, xs in lists[1:]:
+                if xs is None:
+                    continue
+                if xs[k] is None:
+                    raise ValueError(f"{who}: params[{k}] has no gradient (torch.optim skips such a parameter; here every parameter of the plan takes the step)")
+                check(self, who, f"{name}[{k}]", xs[k], dtypes=dt, shape=tuple(p.shape), rule=contiguous)
+        C_ = self.optim_chunk()
+        n_chunks = sum((p.numel() + C_ - 1) // C_ for p in params)
+        nbytes = self._L.ptg_optim_workspace(n_chunks)
+        if nbytes < 0:
+            raise ValueError(f"{who}: {n_chunks} chunks of {C_} elements are more than one launch takes")
+        plan = OptimPlan()
+        plan.kind, plan.dtype, plan.params, plan.grads, plan.targets, plan.n_chunks = kind, params[0].dtype, params, grads, targets, n_chunks
+        with torch.cuda.device(self.device):
+            if state is not None:
+                plan.state1, plan.state2, plan.state, plan.norm = state.state1, state.state2, state.state, state.norm
+            else:
+                plan.state1 = [] if polyak else [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in params]
+                plan.state2 = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in params] if kind == "adam" else []
+                plan.state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64).to(self.device)
+                plan.norm = torch.zeros(1, dtype=torch.float64, device=self.device)
+            ptr = lambda xs, k: xs[k].data_ptr() if xs else 0
+            tab = np.array([[p.data_ptr(), ptr(grads, k), ptr(plan.state1, k), ptr(plan.state2, k), ptr(targets, k), p.numel()]
+                            for k, p in enumerate(params)], dtype=np.int64)
+            spans = np.array([[k, off] for k, p in enumerate(params) for off in range(0, p.numel(), C_)], dtype=np.int64)
+            plan.tensors_dev = torch.from_numpy(tab).to(self.device)
+            plan.chunks_dev = torch.from_numpy(spans).to(self.device)
+            plan.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        plan.grad_ptrs = None if grads is None else [g.data_ptr() for g in grads]
+        return plan
+
+    def _optim_desc(self, plan, kind, flags):
+        return _lib.PtgOptim(kind=kind, flags=flags, dtype=_out_code(self._torch, plan.dtype), n_tensors=len(plan.params), n_chunks=plan.n_chunks,
+                             tensors_dev=_ptr(plan.tensors_dev), chunks_dev=_ptr(plan.chunks_dev), ws_dev=_ptr(plan.workspace))
+
+    def optim_step(self, plan, lr, betas=(0.9, 0.999), eps=1e-8, alpha=0.99, max_grad_norm=None, tau=None, zero_grad=False):
+        """Enqueue, on the current stream, ONE step of every parameter of the plan (include/ptg_env.h: ptg_optim_step, which states the
+        arithmetic): clip_grad_norm_(max_grad_norm) unless it is None, torch.optim.Adam (plan kind "adam": betas, eps) or RMSprop
+        ("rmsprop": alpha, eps; no momentum, not centered), SB3's polyak_update(params, targets, tau) when the plan has targets, and
+        zero_grad(set_to_none=False).  lr: a Python float, kept by a captured call, or a float64 device tensor of 1 element, read when
+        the kernel runs.  Three launches (two without clipping) whatever the number of tensors, no synchronisation, no allocation:
+        the call may be captured and replayed, and every replay takes the next step t + 1.  plan.norm holds the total norm afterwards.
+        A non-finite total norm (without clipping: gradient element) makes the next sync() raise PtgError with code PTG_E_NONFINITE."""
+        torch = self._torch
+        who = "optim_step"
+        if not isinstance(plan, OptimPlan):
+            raise TypeError(f"{who}: plan must be an OptimPlan (optim_plan()), got {type(plan).__name__}")
+        if torch.is_tensor(lr):
+            check(self, who, "a tensor lr", lr, dtypes=(torch.float64,), numel=1)
+        else:
+            lr = float(lr)
+        if plan.kind == "polyak":
+            raise ValueError(f"{who}: a 'polyak' plan has no optimiser (polyak_update takes it)")
+        if not torch.is_tensor(lr) and not (lr >= 0.0 and np.isfinite(lr)):
+            raise ValueError(f"{who}: lr must be finite and >= 0, got {lr}")
+        b1, b2 = float(betas[0]), float(betas[1])
+        if plan.kind == "adam" and not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"{who}: betas must be in [0, 1), got {betas}")
+        if not (float(eps) >= 0.0 and np.isfinite(float(eps))):
+            raise ValueError(f"{who}: eps must be finite and >= 0, got {eps}")
+        if not (float(alpha) >= 0.0 and np.isfinite(float(alpha))):
+            raise ValueError(f"{who}: alpha must be finite and >= 0, got {alpha}")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"{who}: max_grad_norm must be >= 0 (or None), got {max_grad_norm}")
+        if plan.targets is not None and tau is None:
+            raise ValueError(f"{who}: a plan with targets needs tau")
+        if plan.targets is None and tau is not None:
+            raise ValueError(f"{who}: tau given, but the plan has no targets")
+        if tau is not None and not 0.0 <= float(tau) <= 1.0:
+            raise ValueError(f"{who}: tau must be in [0, 1], got {tau}")
+        flags = (_lib.OPTIM_CLIP if max_grad_norm is not None else 0) | (_lib.OPTIM_TARGETS if plan.targets is not None else 0) | \
+                (_lib.OPTIM_ZERO_GRAD if zero_grad else 0)
+        d = self._optim_desc(plan, _lib.OPTIM_ADAM if plan.kind == "adam" else _lib.OPTIM_RMSPROP, flags)
+        d.state_dev, d.norm_dev = _ptr(plan.state), _ptr(plan.norm)
+        if torch.is_tensor(lr):
+            d.lr_dev = _ptr(lr)
+        else:
+            d.lr = lr
+        d.beta1, d.beta2, d.eps, d.alpha = b1, b2, float(eps), float(alpha)
+        d.tau = float(tau) if tau is not None else 0.0
+        d.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_optim_step(self._h, C.byref(d), self._stream()))
+
+    def polyak_update(self, params, targets, tau, plan=None):
+        """Enqueue, on the current stream, SB3's polyak_update(params, targets, tau) for lists that no optimiser steps -- DQN's hard
+        update with tau = 1, batch-norm statistics: target = (1 - tau) * target + tau * param in ONE launch.  plan: the OptimPlan of an
+        earlier call on the same lists (returned here), which makes the call free of allocation and fit for capture; without it the
+        lists are checked and a plan is built first.  Returns the plan."""
+        who = "polyak_update"
+        if plan is not None and (not isinstance(plan, OptimPlan) or plan.kind != "polyak"):
+            raise TypeError(f"{who}: plan must be the OptimPlan an earlier polyak_update returned")
+        if not 0.0 <= float(tau) <= 1.0:
+            raise ValueError(f"{who}: tau must be in [0, 1], got {tau}")
+        if plan is None:
+            plan = self.optim_plan(params, None, "polyak", targets=targets)
+        elif params is not None and ([p.data_ptr() for p in params] != [p.data_ptr() for p in plan.params] or
+                                     [q.data_ptr() for q in targets] != [q.data_ptr() for q in plan.targets]):
+            raise ValueError(f"{who}: the plan was built for other tensors")
+        d = self._optim_desc(plan, _lib.OPTIM_POLYAK, 0)
+        d.tau = float(tau)
+        with self._torch.cuda.device(self.device):
+            self._chk(self._L.ptg_optim_step(self._h, C.byref(d), self._stream()))
+        return plan
