@@ -40,7 +40,8 @@ extern "C" {
                              * 12: + ptg_head, ptg_act, PTG_E_NONFINITE (policy outputs to actions, log-probs and entropy in one launch);
                              * 13: + ptg_loss, ptg_policy_loss, ptg_policy_loss_workspace (the PPO / A2C loss and its gradients in one pass);
                              *     additive, version unchanged: + ptg_optim, ptg_optim_step, ptg_optim_workspace, ptg_optim_chunk (the optimiser step behind
-                             *     the loss: grad-norm clip, Adam / RMSprop, Polyak, zero_grad); no earlier declaration changed */
+                             *     the loss: grad-norm clip, Adam / RMSprop, Polyak, zero_grad); + ptg_td, ptg_td_loss, ptg_td_loss_workspace (DQN's
+                             *     and the TD3 / SAC critics' loss with its gradients); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -52,9 +53,9 @@ enum {
     PTG_E_HIP = -2,            /* a HIP runtime call failed (no device, out of memory, ...) */
     PTG_E_ACTION = -3,         /* a discrete action outside [-5, 4] reached a kernel (reference: IndexError, :347) */
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
-    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss an action outside [0, A) */
+    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss / ptg_td_loss an action outside [0, A) */
     PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1];
-                                * ptg_policy_loss a row it has no finite loss for */
+                                * ptg_policy_loss / ptg_td_loss a row it has no finite loss for */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -778,6 +779,102 @@ typedef struct ptg_optim {
 int ptg_optim_chunk(void);
 int64_t ptg_optim_workspace(int64_t n_chunks);
 int ptg_optim_step(ptg_env* env, const ptg_optim* d, void* stream);
+
+/* ---- the TD losses of the off-policy algorithms: DQN's and the TD3 / SAC critics', with their gradients, in one pass ----------------
+ * Replaces what the reference's DQN, TD3 and SAC (src/rl_config_agent.py:80-222; SB3 2.0.0a13 DQN.train, TD3.train, SAC.train) run on
+ * every gradient step between ptg_replay_sample's batch and the gradient that goes back into the Q network(s): the TD target
+ * (th.max / th.min over the target network's outputs, the (1 - dones) * gamma product, SAC's entropy term), the gather of the chosen
+ * Q-value, smooth_l1_loss or the sum of mse_loss, and autograd's walk back over the same graph.  Every gradient with respect to the
+ * current Q-values is a closed form of what the forward pass holds, so one pass emits the loss, five statistics, d loss / d Q and
+ * (optionally) the target; the caller's backward starts from those (rl_ptg_amd/loss.py: dqn_loss, td3_critic_loss, sac_critic_loss).
+ * Out of scope: TQC's quantile-Huber critic loss (kind 2 is left free for it), the actor and entropy-coefficient losses, TD3's
+ * target-action noise (it precedes the target networks), double DQN, prioritised replay, the networks.
+ * The call is described by a ptg_td, read during the call (B = batch, A = n_actions, K = n_critics):
+ *   kind          PTG_TD_DQN | PTG_TD_CRITICS
+ *   flags         PTG_TD_ENTROPY (critics only): SAC's term, the minimum loses alpha * next_log_prob.  PTG_TD_LOG_ALPHA (with
+ *                 PTG_TD_ENTROPY and alpha_dev): the device scalar holds log alpha (SAC's learned log_ent_coef), alpha = exp of it
+ *   batch         B >= 1, a 64-bit count that is not tied to the handle's n_envs; at most 2^31
+ *   q_dtype       PTG_OUT_F32 | PTG_OUT_F64: the element type of every Q tensor, of next_logp_dev, of every gradient and of y_dev
+ *   rew_dtype, done_dtype   PTG_OUT_F32 | PTG_OUT_F64, each on its own: the replay buffer's done column is float32, its reward column
+ *                 has the engine's out_dtype
+ *   DQN           q_dev[0] = Q(s, .) [B][A] and next_q_dev[0] = Q_target(s', .) [B][A], element (i, j) at i * s_n + j with the row strides
+ *                 q_s_n[0], next_s_n[0] >= A, 2 <= A <= 32; act_dev the chosen actions [B] contiguous, act_kind PTG_ACT_I32 | PTG_ACT_I64;
+ *                 grad_q_dev[0] [B][A] with the row stride g_s_n[0] >= A.  The other array entries and n_critics are not read
+ *   critics       q_dev[k], next_q_dev[k], grad_q_dev[k] for k < K, 1 <= K <= PTG_TD_MAX_CRITICS: [B] each, element i at i * stride with its
+ *                 own stride >= 1 -- SB3's tuple of [B, 1] tensors and the columns of one [B, K] tensor both fit.  The pointers and
+ *                 strides travel by value in the launch.  n_actions, act_dev and act_kind are not read
+ *   rew_dev, done_dev   [B] contiguous.  done is a number, not a flag: it need not be 0 or 1
+ *   next_logp_dev [B] contiguous in q_dtype: log pi(a' | s') of the next action; required iff PTG_TD_ENTROPY
+ *   alpha_dev     float64 [1] on the device, read when the kernel runs (the optimiser moves it between replays); NULL: the host double alpha
+ *   gamma, alpha, scale   host doubles; a captured call keeps them.  scale = c: 1 for TD3, 0.5 for SAC; not read by DQN
+ *   stats_dev     float64 [8] = {loss, mean current Q (DQN: the chosen one; critics: over k and rows), mean y, mean |delta|, share of the
+ *                 delta with |delta| >= 1 (critics: over k and rows), alpha as used (0 without PTG_TD_ENTROPY), 0, 0}
+ *   y_dev         nullable: receives the target y [B] contiguous in q_dtype
+ *   ws_dev        caller-owned device scratch, 8-byte aligned, at least ptg_td_loss_workspace(batch) bytes; its contents mean nothing
+ *                 before or after the call
+ * Arithmetic: all of it in float64 whatever the dtypes are, every operation rounded once (no fused multiply-add), outputs rounded once
+ * on the store; exp (PTG_TD_LOG_ALPHA only) is the double-precision library function.  Row i, r = rew[i], d = done[i]:
+ *   DQN           m = next_q[i][0];  for j = 1 .. A - 1: l = next_q[i][j], m = l if l > m or l != l  (torch.max's NaN rule: a NaN in any
+ *                 column makes m NaN -- fmax would drop it)
+ *                 y = r + ((1 - d) * gamma) * m;   delta = q[i][a] - y
+ *                 term = |delta| < 1 ? 0.5 * (delta * delta) : |delta| - 0.5        (smooth_l1_loss, beta = 1)
+ *                 loss = (sum term) / B;   d loss / d q[i][j] = [j == a] * clamp(delta, -1, 1) / B: the whole row is written, zeros off
+ *                 the chosen column
+ *   critics       m = next_q_0[i];  for k = 1 .. K - 1: l = next_q_k[i], m = l if l < m or l != l  (th.min, the same NaN rule)
+ *                 with PTG_TD_ENTROPY: m = m - alpha * next_logp[i]
+ *                 y = r + ((1 - d) * gamma) * m;   delta_k = q_k[i] - y
+ *                 term = ((0 + delta_0 * delta_0) + delta_1 * delta_1) + ...  in k order
+ *                 loss = (c * (sum term)) / B;   d loss / d q_k[i] = ((c * 2) * delta_k) / B
+ *   statistics    stats[1] = (sum of the current Q) / n, stats[2] = (sum y) / B, stats[3] = (sum |delta|) / n, stats[4] = (number of
+ *                 |delta| >= 1) / n, with n = B (DQN) or B * K (critics; a row adds its K values in k order before it enters the sum)
+ * Sums run in ptg_policy_loss's fixed order (per wave a shuffle tree, the four waves of a 256-row block in order, one partial per block
+ * in ws_dev, a last pass over the partials; no floating-point atomics): the same inputs give the same bits on every run.
+ * Known differences from SB3: it computes these lines in float32 where the networks are float32; here they are float64 and rounded
+ * once.  SB3 adds K per-critic means, sum_k mean_i delta_k^2; here the rows' sums of K terms are added and divided once.
+ * Bad rows.  No index ever becomes an address: a DQN action outside [0, A) leaves the row's gradient row and its y untouched and the
+ * next ptg_sync (or any call that reports kernel-flagged errors) returns PTG_E_INDEX once.  A row is non-finite when its y or its
+ * chosen (critics: any current) Q is not finite -- a non-finite reward, done, next-Q extremum, log-prob or alpha, a NaN anywhere in the
+ * next-Q row, or 0 * Inf where (1 - d) * gamma is 0: it gets NaN gradients (DQN: the whole row), its y as computed, and the next
+ * ptg_sync returns PTG_E_NONFINITE once.  Either kind of row makes stats[0..4] NaN; the other rows are computed as usual.  A -Inf
+ * next-Q beside a larger one is legal for DQN's max (a +Inf beside a smaller one for the critics' min), and so is a non-finite current
+ * Q on a column that was not chosen: it is not read.
+ * Enqueues kernels only -- one for B <= 256, else the rows and a one-workgroup merge of the block partials (the reference's batches,
+ * DQN's 544, TD3's 257 and SAC's 470, take these two) -- with no host synchronisation and no allocation, so the call may be captured into a
+ * hipGraph and replayed.  Reads nothing of the handle but its device: env state, the finished-episode ring, the ptg_vn_* statistics and
+ * every replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, stats_dev, rew_dev, done_dev or ws_dev (or a ws_dev that is not 8-byte
+ * aligned); a NULL q_dev, next_q_dev or grad_q_dev entry in use; NULL act_dev (DQN); an unknown kind, flag or dtype code; batch < 1 or
+ * above 2^31; n_actions outside [2, 32] or an act_kind other than PTG_ACT_I32 | PTG_ACT_I64 (DQN); n_critics outside [1, 4] (critics);
+ * a row stride below A (DQN) or a stride below 1 (critics); PTG_TD_ENTROPY on DQN, or without next_logp_dev; PTG_TD_LOG_ALPHA without
+ * PTG_TD_ENTROPY or without alpha_dev.
+ * ptg_td_loss_workspace(batch): bytes of scratch a batch of that size needs (64 per 256 rows); negative for batch < 1 or above 2^31. */
+#define PTG_TD_MAX_CRITICS 4
+enum { PTG_TD_DQN = 0, PTG_TD_CRITICS = 1 };      /* 2: left free for the quantile critics (TQC) */
+enum { PTG_TD_ENTROPY = 1, PTG_TD_LOG_ALPHA = 2 };
+typedef struct ptg_td {
+    int32_t kind, flags;
+    int32_t n_actions, n_critics;
+    int32_t q_dtype, act_kind;
+    int32_t rew_dtype, done_dtype;
+    int64_t batch;
+    const void* q_dev[PTG_TD_MAX_CRITICS];
+    int64_t q_s_n[PTG_TD_MAX_CRITICS];
+    const void* next_q_dev[PTG_TD_MAX_CRITICS];
+    int64_t next_s_n[PTG_TD_MAX_CRITICS];
+    const void* act_dev;
+    const void* rew_dev;
+    const void* done_dev;
+    const void* next_logp_dev;
+    const double* alpha_dev;
+    double gamma, alpha, scale;
+    double* stats_dev;
+    void* grad_q_dev[PTG_TD_MAX_CRITICS];
+    int64_t g_s_n[PTG_TD_MAX_CRITICS];
+    void* y_dev;
+    void* ws_dev;
+} ptg_td;
+int64_t ptg_td_loss_workspace(int64_t batch);
+int ptg_td_loss(ptg_env* env, const ptg_td* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -10,6 +10,7 @@
 //   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
 //   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
 //   k_optim_*         clip_grad_norm_, torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad over all tensors of an optimiser.
+//   k_td_*            the TD loss of DQN / the TD3 and SAC critics on a replay batch, its statistics and the gradients w.r.t. the Q-values.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "ptg_handle.h"
 
@@ -1072,6 +1073,175 @@ k_optim_update(OptArgs a)
     }
 }
 
+// ================================================================================== the TD losses of the off-policy algorithms
+// What runs between ptg_replay_sample's batch and the gradient that goes back into the Q network(s) (include/ptg_env.h, ptg_td_loss,
+// states the lines; tests/td_loss_restatement.py restates them in NumPy): the TD target, the chosen Q-value, smooth_l1_loss (DQN.train)
+// or the sum of the critics' squared errors (TD3.train, SAC.train) and d loss / d Q in closed form.  One lane per row on consecutive
+// rows, float64 arithmetic whatever the input types, outputs rounded once on the store.  A DQN row of next-Q values is read once,
+// straight from memory as k_act and pl_row read theirs; the critics' K pointers and strides sit in the launch arguments and every loop
+// over them is unrolled over PTG_TD_MAX_CRITICS with a k < K guard, so nothing per lane (and no launch argument) is indexed
+// dynamically.  The reward and done columns have dtypes of their own, read behind a wave-uniform branch.  The five sums go through
+// the policy loss's fixed-order scheme: pl_wave_sum, pl_block_sum, one partial per block in the caller's workspace, k_td_final.
+constexpr int TD_K = PTG_TD_MAX_CRITICS;
+
+struct TdArgs {                          // by value in the launch: a captured call holds no host memory
+    const void* q[TD_K]; size_t q_s[TD_K];       // elements
+    const void* nq[TD_K]; size_t nq_s[TD_K];
+    void* g[TD_K]; size_t g_s[TD_K];
+    const void *act, *rew, *done, *lp;
+    const double* alpha_dev;
+    void* y;
+    double* stats;
+    double* ws;                          // one partial [PL_PITCH] per block
+    double gamma, alpha, scale;
+    size_t B;
+    int A, K, kind, flags, act_kind, rew_f64, done_f64, nblk;
+    int* err;
+};
+struct TdRow { double term, q, y, ad, ge; };      // a row's terms of the five means
+
+__device__ __forceinline__ double td_rd(const void* p, int f64, size_t i)
+{
+    return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i];
+}
+
+// alpha as this call uses it: 0 without the entropy term; else the host double, the device scalar, or exp of it
+__device__ __forceinline__ double td_alpha(const TdArgs& a)
+{
+    if (!(a.flags & PTG_TD_ENTROPY)) return 0.0;
+    if (!a.alpha_dev) return a.alpha;
+    const double s = a.alpha_dev[0];
+    return (a.flags & PTG_TD_LOG_ALPHA) ? exp(s) : s;
+}
+
+template <typename IN>
+__device__ __forceinline__ TdRow td_row_dqn(const TdArgs& a, size_t i)
+{
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const TdRow poison{nan, nan, nan, nan, nan};
+    const int A = a.A;
+    const long long act = a.act_kind == PTG_ACT_I64 ? ((const long long*)a.act)[i] : (long long)((const int*)a.act)[i];
+    if (act < 0 || act >= (long long)A) { a.err[4] = 1; return poison; }      // never an address; the row's gradients and y stay as they were
+    const IN* __restrict__ nrow = (const IN*)a.nq[0] + i * a.nq_s[0];
+    double m = (double)nrow[0];
+    for (int j = 1; j < A; j++) {
+        const double l = (double)nrow[j];
+        if (l > m || l != l) m = l;                          // torch.max: a NaN wins and then stays (NaN > x and x > NaN are false)
+    }
+    const double r = td_rd(a.rew, a.rew_f64, i), d = td_rd(a.done, a.done_f64, i);
+    const double y = r + ((1.0 - d) * a.gamma) * m;
+    const double qa = (double)((const IN*)a.q[0])[i * a.q_s[0] + (size_t)act];
+    if (a.y) ((IN*)a.y)[i] = (IN)y;
+    IN* const g_row = (IN*)a.g[0] + i * a.g_s[0];
+    if (!pl_finite(y) || !pl_finite(qa)) {
+        for (int j = 0; j < A; j++) g_row[j] = (IN)nan;
+        a.err[5] = 1;
+        return poison;
+    }
+    const double dl = qa - y, ad = fabs(dl);
+    const double gc = (dl < -1.0 ? -1.0 : (dl > 1.0 ? 1.0 : dl)) / (double)a.B;
+    for (int j = 0; j < A; j++) g_row[j] = (IN)(j == (int)act ? gc : 0.0);
+    return TdRow{ad < 1.0 ? 0.5 * (dl * dl) : ad - 0.5, qa, y, ad, ad >= 1.0 ? 1.0 : 0.0};
+}
+
+template <typename IN>
+__device__ __forceinline__ TdRow td_row_critics(const TdArgs& a, size_t i, double alpha)
+{
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const int K = a.K;
+    double m = (double)((const IN*)a.nq[0])[i * a.nq_s[0]];
+#pragma unroll
+    for (int k = 1; k < TD_K; k++) {
+        if (k < K) {
+            const double l = (double)((const IN*)a.nq[k])[i * a.nq_s[k]];
+            if (l < m || l != l) m = l;                      // th.min, the same NaN rule
+        }
+    }
+    if (a.flags & PTG_TD_ENTROPY) m = m - alpha * (double)((const IN*)a.lp)[i];
+    const double r = td_rd(a.rew, a.rew_f64, i), d = td_rd(a.done, a.done_f64, i);
+    const double y = r + ((1.0 - d) * a.gamma) * m;
+    double qk[TD_K];
+    bool bad = !pl_finite(y);
+#pragma unroll
+    for (int k = 0; k < TD_K; k++) {
+        qk[k] = 0.0;
+        if (k < K) {
+            qk[k] = (double)((const IN*)a.q[k])[i * a.q_s[k]];
+            bad = bad || !pl_finite(qk[k]);
+        }
+    }
+    if (a.y) ((IN*)a.y)[i] = (IN)y;
+    if (bad) {
+#pragma unroll
+        for (int k = 0; k < TD_K; k++)
+            if (k < K) ((IN*)a.g[k])[i * a.g_s[k]] = (IN)nan;
+        a.err[5] = 1;
+        return TdRow{nan, nan, nan, nan, nan};
+    }
+    const double c2 = a.scale * 2.0, Bd = (double)a.B;
+    TdRow t{0.0, 0.0, y, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < TD_K; k++) {
+        if (k < K) {
+            const double dl = qk[k] - y, ad = fabs(dl);
+            ((IN*)a.g[k])[i * a.g_s[k]] = (IN)((c2 * dl) / Bd);
+            t.term = t.term + dl * dl;
+            t.q = t.q + qk[k];
+            t.ad = t.ad + ad;
+            t.ge = t.ge + (ad >= 1.0 ? 1.0 : 0.0);
+        }
+    }
+    return t;
+}
+
+// the sums of a whole batch -> the eight statistics; one thread
+__device__ __forceinline__ void td_finish(const TdArgs& a, const double* sum, double alpha)
+{
+    const bool dqn = a.kind == PTG_TD_DQN;
+    const double Bd = (double)a.B, n = dqn ? Bd : Bd * (double)a.K;
+    a.stats[0] = dqn ? sum[0] / Bd : (a.scale * sum[0]) / Bd;
+    a.stats[1] = sum[1] / n; a.stats[2] = sum[2] / Bd; a.stats[3] = sum[3] / n; a.stats[4] = sum[4] / n;
+    a.stats[5] = alpha; a.stats[6] = 0.0; a.stats[7] = 0.0;
+}
+
+// ONE: the whole batch is this block (B <= PL_BLOCK): rows and statistics in one launch.  Otherwise the block leaves its partial sums
+// in the workspace for k_td_final.
+template <typename IN, bool DQN, bool ONE>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_td_rows(TdArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
+    const double alpha = td_alpha(a);
+    TdRow t{0.0, 0.0, 0.0, 0.0, 0.0};
+    if (live) t = DQN ? td_row_dqn<IN>(a, i) : td_row_critics<IN>(a, i, alpha);
+    double v[PL_TERMS] = {t.term, t.q, t.y, t.ad, t.ge, 0.0};
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        if (ONE) td_finish(a, v, alpha);
+        else {
+            double* p = a.ws + (size_t)blockIdx.x * PL_PITCH;
+#pragma unroll
+            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
+        }
+    }
+}
+
+// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
+__global__ void __launch_bounds__(PL_BLOCK)
+k_td_final(TdArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) v[k] += a.ws[(size_t)b * PL_PITCH + k];
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) td_finish(a, v, td_alpha(a));
+}
+
 // ================================================================================================= host side
 // ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
 template <typename V>
@@ -1083,6 +1253,21 @@ void launch_minibatch(hipStream_t st, const void* idx, int idx_bytes, size_t B, 
         hipLaunchKernelGGL((k_minibatch<V, long long>), grid, block, 0, st, (const long long*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
     else
         hipLaunchKernelGGL((k_minibatch<V, int>), grid, block, 0, st, (const int*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+}
+
+// ptg_td_loss's launches: the Q dtype and the kind are the row kernel's template axes
+template <typename IN>
+void launch_td(hipStream_t st, const TdArgs& a, bool dqn)
+{
+    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
+    if (a.nblk == 1) {                                       // up to 256 rows: everything in one launch
+        if (dqn) hipLaunchKernelGGL((k_td_rows<IN, true, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_td_rows<IN, false, true>), grid, block, 0, st, a);
+        return;
+    }
+    if (dqn) hipLaunchKernelGGL((k_td_rows<IN, true, false>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_td_rows<IN, false, false>), grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_td_final, dim3(1), block, 0, st, a);
 }
 
 }  // namespace
@@ -1522,6 +1707,67 @@ int ptg_optim_step(ptg_env* h, const ptg_optim* d, void* stream)
     if (f64) hipLaunchKernelGGL(k_optim_update<double>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_optim_update<float>, grid, block, 0, st, a);
     return launch_check(h, "k_optim_update");
+}
+
+// ---- the TD losses: DQN's and the TD3 / SAC critics', the statistics and the gradients w.r.t. the current Q-values ---------
+int64_t ptg_td_loss_workspace(int64_t batch)
+{
+    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;      // ptg_policy_loss's limit: 2^23 blocks of 256 threads
+    return ((batch - 1) / PL_BLOCK + 1) * PL_PITCH * (int64_t)sizeof(double);
+}
+
+int ptg_td_loss(ptg_env* h, const ptg_td* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_td_loss: null descriptor");
+    if (d->kind != PTG_TD_DQN && d->kind != PTG_TD_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_td_loss: unknown kind %d", d->kind);
+    if (d->flags & ~(PTG_TD_ENTROPY | PTG_TD_LOG_ALPHA)) return set_err(h, PTG_E_INVALID, "ptg_td_loss: unknown flag in %d", d->flags);
+    const bool dqn = d->kind == PTG_TD_DQN, ent = (d->flags & PTG_TD_ENTROPY) != 0, log_alpha = (d->flags & PTG_TD_LOG_ALPHA) != 0;
+    const auto dtype_ok = [](int c) { return c == PTG_OUT_F32 || c == PTG_OUT_F64; };
+    if (ptg_td_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_td_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (!dtype_ok(d->q_dtype) || !dtype_ok(d->rew_dtype) || !dtype_ok(d->done_dtype))
+        return set_err(h, PTG_E_INVALID, "ptg_td_loss: q_dtype, rew_dtype and done_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->rew_dev || !d->done_dev || !d->stats_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: null rew_dev, done_dev or stats_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_td_loss: ws_dev is null or not aligned to 8 bytes");
+    if (dqn && ent) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_ENTROPY applies to the critics only");
+    if (log_alpha && !ent) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_LOG_ALPHA needs PTG_TD_ENTROPY");
+    if (ent && !d->next_logp_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_ENTROPY needs next_logp_dev");
+    if (log_alpha && !d->alpha_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_LOG_ALPHA needs alpha_dev");
+    int K = 1;
+    int64_t min_stride = 1;
+    if (dqn) {
+        if (d->n_actions < 2 || d->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_td_loss: n_actions outside [2, 32]");
+        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_td_loss: DQN takes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (!d->act_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: DQN needs act_dev");
+        min_stride = d->n_actions;
+    } else {
+        if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_td_loss: n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
+        K = d->n_critics;
+    }
+    for (int k = 0; k < K; k++) {
+        if (!d->q_dev[k] || !d->next_q_dev[k] || !d->grad_q_dev[k]) return set_err(h, PTG_E_INVALID, "ptg_td_loss: null q_dev, next_q_dev or grad_q_dev [%d]", k);
+        if (d->q_s_n[k] < min_stride || d->next_s_n[k] < min_stride || d->g_s_n[k] < min_stride)
+            return set_err(h, PTG_E_INVALID, "ptg_td_loss: q_s_n, next_s_n or g_s_n [%d] below %lld", k, (long long)min_stride);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    TdArgs a{};
+    for (int k = 0; k < K; k++) {
+        a.q[k] = d->q_dev[k]; a.q_s[k] = (size_t)d->q_s_n[k];
+        a.nq[k] = d->next_q_dev[k]; a.nq_s[k] = (size_t)d->next_s_n[k];
+        a.g[k] = d->grad_q_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    }
+    a.act = d->act_dev; a.rew = d->rew_dev; a.done = d->done_dev; a.lp = ent ? d->next_logp_dev : nullptr;
+    a.alpha_dev = ent ? d->alpha_dev : nullptr;
+    a.y = d->y_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.gamma = d->gamma; a.alpha = d->alpha; a.scale = d->scale;
+    a.B = (size_t)d->batch; a.A = d->n_actions; a.K = K; a.kind = d->kind; a.flags = d->flags; a.act_kind = d->act_kind;
+    a.rew_f64 = d->rew_dtype == PTG_OUT_F64; a.done_f64 = d->done_dtype == PTG_OUT_F64;
+    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.err = h->P.err;
+    if (d->q_dtype == PTG_OUT_F64) launch_td<double>(st, a, dqn);
+    else launch_td<float>(st, a, dqn);
+    return launch_check(h, "k_td_rows");
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd.
+"""ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd;
+dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise -- see the end of the file.
 
     out = net(obs)                                            # [B, A + 1]: logits and a value column
     loss, stats = ppo_loss(engine, out[:, :A], out[:, A], actions, old_log_prob, advantages, returns, clip_range=0.2)
@@ -56,3 +57,55 @@ def a2c_loss(engine, head_input, values, actions, advantages, returns, *, ent_co
     """SB3's A2C.train loss of its one batch -> (loss, stats) as ppo_loss gives them (approx_kl and clip_fraction are 0)."""
     kw = dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, out=out, workspace=workspace)
     return _call("a2c", engine, head_input, values, actions, None, advantages, returns, None, log_std, kw)
+
+
+# ------------------------------------------------------------------------------------------------- the off-policy losses
+#     batch = buffer.sample(256)                                # DeviceReplayBuffer: observations, next observations, columns
+#     with torch.no_grad():
+#         next_q = [c(next_in) for c in critic_targets]         # K target critics on (s', a')
+#     loss, stats = sac_critic_loss(engine, [c(cur_in) for c in critics], next_q, rewards, dones, next_log_prob, gamma=0.96,
+#                                   log_ent_coef=log_alpha)
+#     loss.backward()
+# Only the current Q tensors are differentiable: the target Q-values, rewards, dones, log-probs and alpha are data, as they are under
+# SB3's torch.no_grad().  Without out= the gradient tensors are allocated zeroed, so a DQN row refused for its action adds nothing.
+class _TdLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, kind, next_q, rewards, dones, gamma, kw, *q):
+        dqn = kind == "dqn"
+        if kw.get("out") is None:
+            dev, dt = q[0].device, q[0].dtype
+            grads = [torch.zeros(t.shape, dtype=dt, device=dev) for t in q]
+            kw = dict(kw, out=(torch.empty(8, dtype=torch.float64, device=dev), grads[0] if dqn else grads, None))
+        qd = [t.detach() for t in q]
+        res = engine.td_loss(kind, qd[0] if dqn else qd, next_q, rewards, dones, gamma, **kw)
+        ctx.grads = [res.grad_q] if dqn else list(res.grad_q)
+        ctx.shapes = [t.shape for t in q]
+        ctx.mark_non_differentiable(res.stats)
+        return res.stats[0].to(q[0].dtype, copy=True), res.stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        return (None,) * 7 + tuple((g * grad_loss).reshape(s) for g, s in zip(ctx.grads, ctx.shapes))
+
+
+def dqn_loss(engine, q, next_q, actions, rewards, dones, *, gamma, out=None, workspace=None):
+    """SB3's DQN.train loss of one replay batch -> (loss, stats): smooth_l1_loss(q.gather(1, actions), rewards + (1 - dones) * gamma *
+    next_q.max(1)).  q = q_net(obs) [B, A] carries the graph, next_q = q_net_target(next_obs) [B, A] is data.  stats float64 [8] =
+    loss, mean chosen Q, mean target, mean |delta|, share of |delta| >= 1, 0, 0, 0.  Arguments as HipEngine.td_loss."""
+    return _TdLossFn.apply(engine, "dqn", next_q.detach(), rewards, dones, gamma, dict(actions=actions, out=out, workspace=workspace), q)
+
+
+def td3_critic_loss(engine, q, next_q, rewards, dones, *, gamma, out=None, workspace=None):
+    """SB3's TD3.train critic loss -> (loss, stats): sum_k mse_loss(q[k], rewards + (1 - dones) * gamma * min_k next_q[k]).  q: the list
+    of the K critics' outputs [B] / [B, 1] on (obs, actions), carrying the graph; next_q: the K target critics' outputs on (next_obs,
+    the smoothed target action), data."""
+    return _TdLossFn.apply(engine, "td3", [t.detach() for t in next_q], rewards, dones, gamma, dict(out=out, workspace=workspace), *q)
+
+
+def sac_critic_loss(engine, q, next_q, rewards, dones, next_log_prob, *, gamma, ent_coef=None, log_ent_coef=None, out=None, workspace=None):
+    """SB3's SAC.train critic loss -> (loss, stats): 0.5 * sum_k mse_loss(q[k], rewards + (1 - dones) * gamma * (min_k next_q[k] -
+    alpha * next_log_prob)).  alpha: ent_coef (a float, or a float64 device tensor of 1 element) or exp(log_ent_coef) (SAC's learned
+    parameter, a float64 device tensor of 1 element read when the kernel runs); stats[5] holds the alpha that was used."""
+    kw = dict(next_log_prob=next_log_prob.detach(), ent_coef=ent_coef.detach() if torch.is_tensor(ent_coef) else ent_coef,
+              log_ent_coef=log_ent_coef.detach() if torch.is_tensor(log_ent_coef) else log_ent_coef, out=out, workspace=workspace)
+    return _TdLossFn.apply(engine, "sac", [t.detach() for t in next_q], rewards, dones, gamma, kw, *q)

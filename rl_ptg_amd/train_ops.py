@@ -1,5 +1,5 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+action heads, the policy loss, the TD losses and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
@@ -22,6 +22,9 @@ EpsGreedyAct = collections.namedtuple("EpsGreedyAct", "actions")
 GaussianAct = collections.namedtuple("GaussianAct", "actions raw log_prob entropy")
 # what policy_loss returns: stats float64 [8], the gradients w.r.t. the head's input, the values and (Gaussian head) log_std
 PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values grad_log_std")
+# what td_loss returns: stats float64 [8], the gradients w.r.t. the current Q-values (DQN: one tensor [B, A]; critics: a list of K tensors
+# shaped like q[k]) and the TD target [B] (None when not asked for)
+TdLoss = collections.namedtuple("TdLoss", "stats grad_q target")
 
 
 class OptimPlan:
@@ -586,6 +589,125 @@ class TrainOps:
         with torch.cuda.device(self.device):
             self._chk(self._L.ptg_policy_loss(self._h, C.byref(d), self._stream()))
         return PolicyLoss(stats, g_in, g_val, g_ls)
+
+    # ------------------------------------------------------------------ the TD loss of a replay batch and its gradients
+    def td_loss_workspace(self, batch):
+        """the device scratch of td_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
+        nbytes = self._L.ptg_td_loss_workspace(int(batch))
+        if nbytes < 0:
+            raise ValueError(f"td_loss_workspace: batch must be in [1, 2^31], got {batch}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def td_loss(self, kind, q, next_q, rewards, dones, gamma, *, actions=None, next_log_prob=None, ent_coef=None, log_ent_coef=None,
+                want_target=False, out=None, workspace=None):
+        """Enqueue, on the current stream, the TD target and the loss lines of SB3's DQN.train (kind "dqn"), TD3.train ("td3") or
+        SAC.train ("sac") on one replay batch together with their gradients with respect to the current Q-values (include/ptg_env.h:
+        ptg_td_loss, which states the arithmetic).
+        "dqn": q = Q(s, .) and next_q = Q_target(s', .), both [B, A] (2 <= A <= 32, unit column stride, row stride >= A) of one float
+        dtype, with int32 / int64 actions [B].  "td3" / "sac": q and next_q are lists of K tensors (1 <= K <= 4), [B] or [B, 1] each
+        with any stride >= 1 -- SB3's tuples of critic outputs, or the columns of one [B, K] tensor; "sac" also takes next_log_prob [B]
+        in the Q dtype and exactly one of ent_coef (a Python float, kept by a captured call, or a float64 device tensor of 1 element,
+        read when the kernel runs) and log_ent_coef (a float64 device tensor of 1 element holding log alpha: SAC's learned
+        parameter).  rewards and dones: contiguous [B] (or [B, 1]), float32 or float64 each on its own -- what
+        DeviceReplayBuffer.sample() returns.  gamma: a finite Python float.
+        Returns TdLoss(stats float64 [8] = loss, mean current Q, mean target, mean |delta|, share of |delta| >= 1, alpha as used, 0, 0;
+        grad_q = d loss / d q, a tensor for "dqn" and a list for the critics; target [B] with want_target, else None).  out: an earlier
+        result, reused by a captured call (its target, when not None, is written); workspace: td_loss_workspace(B) or larger,
+        allocated when missing.  Fresh gradients are torch.empty: a row refused for its action keeps what was there.  Outputs must
+        not overlap each other or the inputs: a tensor given twice is refused, any other overlap is not checked.  No
+        synchronisation; a bad row makes the next sync() raise PtgError (PTG_E_INDEX / PTG_E_NONFINITE)."""
+        torch = self._torch
+        who = "td_loss"
+        if kind not in ("dqn", "td3", "sac"):
+            raise ValueError(f"{who}: kind must be 'dqn', 'td3' or 'sac', got {kind!r}")
+        dqn, sac = kind == "dqn", kind == "sac"
+        floats = (torch.float32, torch.float64)
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
+        if dqn:
+            x = check(self, who, "q", q, dtypes=floats, shape=(None, None), rule=rows)
+            B, A = x.shape
+            if not 2 <= A <= 32:
+                raise ValueError(f"{who}: q must be [B, A] with 2 <= A <= 32, got shape {tuple(x.shape)}")
+            dt = (x.dtype,)
+            qs, nqs = [x], [check(self, who, "next_q", next_q, dtypes=dt, shape=(B, A), rule=rows)]
+        else:
+            for name, xs in (("q", q), ("next_q", next_q)):
+                if not isinstance(xs, (list, tuple)):
+                    raise TypeError(f"{who}: {name} must be a list of critic outputs for kind {kind!r}, got {type(xs).__name__}")
+            if not 1 <= len(q) <= _lib.TD_MAX_CRITICS or len(next_q) != len(q):
+                raise ValueError(f"{who}: q and next_q must hold the same number of critics, 1 to {_lib.TD_MAX_CRITICS}, got {len(q)} and {len(next_q)}")
+            A = 0
+            x = check(self, who, "q[0]", column(q[0]), dtypes=floats, shape=(None,), rule=step)
+            (B,), dt = x.shape, (x.dtype,)
+            qs = [x] + [check(self, who, f"q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step) for k, t in enumerate(q) if k > 0]
+            nqs = [check(self, who, f"next_q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step) for k, t in enumerate(next_q)]
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch, q has shape {tuple(x.shape)}")
+        K = len(qs)
+        rewards = check(self, who, "rewards", column(rewards), dtypes=floats, shape=(B,), rule=contiguous)
+        dones = check(self, who, "dones", column(dones), dtypes=floats, shape=(B,), rule=contiguous)
+        if dqn != (actions is not None):
+            raise ValueError(f"{who}: actions go with kind 'dqn' and with no other")
+        if sac != (next_log_prob is not None):
+            raise ValueError(f"{who}: next_log_prob goes with kind 'sac' and with no other")
+        if (ent_coef is not None) + (log_ent_coef is not None) != (1 if sac else 0):
+            raise ValueError(f"{who}: kind 'sac' takes exactly one of ent_coef and log_ent_coef, the other kinds neither")
+        if not np.isfinite(float(gamma)):
+            raise ValueError(f"{who}: gamma must be finite, got {gamma}")
+        actions = check(self, who, "actions", column(actions), dtypes=(torch.int32, torch.int64), shape=(B,), rule=contiguous, optional=True)
+        next_log_prob = check(self, who, "next_log_prob", column(next_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        alpha_dev = None
+        if log_ent_coef is not None or torch.is_tensor(ent_coef):
+            alpha_dev = check(self, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
+                              dtypes=(torch.float64,), numel=1)
+        alpha = float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 3:
+                raise ValueError(f"{who}: out must be the TdLoss of an earlier call")
+            stats, g_q, target = out
+            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            if dqn:
+                gs = [check(self, who, "out.grad_q", g_q, dtypes=dt, shape=(B, A), rule=rows, exc=ValueError)]
+            else:
+                if not isinstance(g_q, (list, tuple)) or len(g_q) != K:
+                    raise ValueError(f"{who}: out.grad_q must be a list of {K} tensors")
+                gs = [check(self, who, f"out.grad_q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step, exc=ValueError) for k, t in enumerate(g_q)]
+            if want_target and target is None:
+                raise ValueError(f"{who}: want_target, but out.target is None")
+            check(self, who, "out.target", target, dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            starts = [t.data_ptr() for t in gs + qs + nqs + ([target] if target is not None else [])]
+            if len(set(starts)) != len(starts):             # the cheap half of "outputs must not overlap": one tensor given twice
+                raise ValueError(f"{who}: two of out.grad_q, out.target, q and next_q start at the same address; the outputs must not overlap each other or the inputs")
+        if workspace is not None:
+            check(self, who, f"workspace (td_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
+            if workspace.numel() < self._L.ptg_td_loss_workspace(B):
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_td_loss_workspace(B)}")
+        else:
+            workspace = self.td_loss_workspace(B)
+        if out is None:
+            with torch.cuda.device(self.device):
+                stats = torch.empty(8, dtype=torch.float64, device=self.device)
+                g_q = [torch.empty(tuple(t.shape), dtype=x.dtype, device=self.device) for t in ([q] if dqn else q)]
+                gs = g_q if dqn else [column(t) for t in g_q]
+                g_q = g_q[0] if dqn else g_q
+                target = torch.empty(B, dtype=x.dtype, device=self.device) if want_target else None
+        d = _lib.PtgTd(kind=_lib.TD_DQN if dqn else _lib.TD_CRITICS,
+                       flags=(_lib.TD_ENTROPY if sac else 0) | (_lib.TD_LOG_ALPHA if log_ent_coef is not None else 0),
+                       n_actions=A, n_critics=0 if dqn else K, q_dtype=_out_code(torch, x.dtype),
+                       act_kind=_lib.ACT_I64 if dqn and actions.dtype == torch.int64 else _lib.ACT_I32,
+                       rew_dtype=_out_code(torch, rewards.dtype), done_dtype=_out_code(torch, dones.dtype), batch=B,
+                       act_dev=_ptr(actions), rew_dev=_ptr(rewards), done_dev=_ptr(dones), next_logp_dev=_ptr(next_log_prob),
+                       alpha_dev=_ptr(alpha_dev), gamma=float(gamma), alpha=alpha, scale=0.5 if sac else 1.0,
+                       stats_dev=_ptr(stats), y_dev=_ptr(target), ws_dev=_ptr(workspace))
+        least = max(A, 1)
+        for k in range(K):
+            d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), least)
+            d.next_q_dev[k], d.next_s_n[k] = nqs[k].data_ptr(), max(nqs[k].stride(0), least)
+            d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), least)
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_td_loss(self._h, C.byref(d), self._stream()))
+        return TdLoss(stats, g_q, target)
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):
