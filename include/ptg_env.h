@@ -41,7 +41,8 @@ extern "C" {
                              * 13: + ptg_loss, ptg_policy_loss, ptg_policy_loss_workspace (the PPO / A2C loss and its gradients in one pass);
                              *     additive, version unchanged: + ptg_optim, ptg_optim_step, ptg_optim_workspace, ptg_optim_chunk (the optimiser step behind
                              *     the loss: grad-norm clip, Adam / RMSprop, Polyak, zero_grad); + ptg_td, ptg_td_loss, ptg_td_loss_workspace (DQN's
-                             *     and the TD3 / SAC critics' loss with its gradients); no earlier declaration changed */
+                             *     and the TD3 / SAC critics' loss with its gradients); + ptg_ql, ptg_quantile_loss, ptg_quantile_loss_workspace (TQC's
+                             *     quantile-Huber critic loss with its gradients); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -55,7 +56,7 @@ enum {
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
     PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss / ptg_td_loss an action outside [0, A) */
     PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1];
-                                * ptg_policy_loss / ptg_td_loss a row it has no finite loss for */
+                                * ptg_policy_loss / ptg_td_loss / ptg_quantile_loss a row it has no finite loss for */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -787,7 +788,8 @@ int ptg_optim_step(ptg_env* env, const ptg_optim* d, void* stream);
  * Q-value, smooth_l1_loss or the sum of mse_loss, and autograd's walk back over the same graph.  Every gradient with respect to the
  * current Q-values is a closed form of what the forward pass holds, so one pass emits the loss, five statistics, d loss / d Q and
  * (optionally) the target; the caller's backward starts from those (rl_ptg_amd/loss.py: dqn_loss, td3_critic_loss, sac_critic_loss).
- * Out of scope: TQC's quantile-Huber critic loss (kind 2 is left free for it), the actor and entropy-coefficient losses, TD3's
+ * Out of scope: TQC's quantile-Huber critic loss (it has its own entry point, ptg_quantile_loss below; kind 2 stays refused here), the
+ * actor and entropy-coefficient losses, TD3's
  * target-action noise (it precedes the target networks), double DQN, prioritised replay, the networks.
  * The call is described by a ptg_td, read during the call (B = batch, A = n_actions, K = n_critics):
  *   kind          PTG_TD_DQN | PTG_TD_CRITICS
@@ -849,7 +851,7 @@ int ptg_optim_step(ptg_env* env, const ptg_optim* d, void* stream);
  * PTG_TD_ENTROPY or without alpha_dev.
  * ptg_td_loss_workspace(batch): bytes of scratch a batch of that size needs (64 per 256 rows); negative for batch < 1 or above 2^31. */
 #define PTG_TD_MAX_CRITICS 4
-enum { PTG_TD_DQN = 0, PTG_TD_CRITICS = 1 };      /* 2: left free for the quantile critics (TQC) */
+enum { PTG_TD_DQN = 0, PTG_TD_CRITICS = 1 };      /* the quantile critics (TQC) have their own entry point: ptg_quantile_loss */
 enum { PTG_TD_ENTROPY = 1, PTG_TD_LOG_ALPHA = 2 };
 typedef struct ptg_td {
     int32_t kind, flags;
@@ -875,6 +877,93 @@ typedef struct ptg_td {
 } ptg_td;
 int64_t ptg_td_loss_workspace(int64_t batch);
 int ptg_td_loss(ptg_env* env, const ptg_td* d, void* stream);
+
+/* ---- the quantile-Huber loss of TQC's critics, with its gradients, in one pass -------------------------------------------------------
+ * Replaces what the reference's TQC (src/rl_config_agent.py:80-222; sb3_contrib's TQC.train, critic part, and
+ * quantile_huber_loss(current_quantiles, target_quantiles, sum_over_quantiles=False)) runs on every gradient step between
+ * ptg_replay_sample's batch and the gradient that goes back into the quantile critics: th.sort over the target critics' K * Q quantiles,
+ * the slice that drops the top d * K of them, the entropy term, the (1 - dones) * gamma product, the [B, K, Q, M] tensor of pairwise
+ * differences, abs / where / comparison / mean over it, and autograd's walk back.  The kernel never stores a pair: one pass emits the
+ * loss, four statistics, d loss / d current quantile and (optionally) the targets; the caller's backward starts from those
+ * (rl_ptg_amd/loss.py: tqc_critic_loss).
+ * Out of scope: the actor and entropy-coefficient losses, the networks.
+ * The call is described by a ptg_ql, read during the call.  Sizes: B = batch rows, K = n_critics, Q = n_quantiles per critic,
+ * d = n_drop (top_quantiles_to_drop_per_net), M = K * (Q - d) kept target quantiles.  The reference: B = 290, K = 2, Q = 30, d = 2,
+ * M = 56, gamma = 0.9639, alpha = 0.00047; SB3's defaults: Q = 25, d = 2.
+ *   flags         PTG_QL_LOG_ALPHA (with alpha_dev): the device scalar holds log alpha (the learned log_ent_coef), alpha = exp of it
+ *   n_critics     1 <= K <= PTG_TD_MAX_CRITICS;   n_quantiles  1 <= Q <= PTG_QL_MAX_QUANTILES;   n_drop  0 <= d < Q
+ *   batch         B >= 1, a 64-bit count that is not tied to the handle's n_envs; at most 2^31
+ *   q_dtype       PTG_OUT_F32 | PTG_OUT_F64: the element type of every quantile tensor, of next_logp_dev, of every gradient and of y_dev
+ *   rew_dtype, done_dtype   PTG_OUT_F32 | PTG_OUT_F64, each on its own
+ *   cur_dev[k], next_dev[k], grad_dev[k]   for k < K: [B][Q] each, element (b, i) at b * stride + i with its own row stride cur_s_n[k],
+ *                 next_s_n[k], g_s_n[k] >= Q.  SB3's stacked [B, K, Q] tensor fits (pointer offset k * Q, stride K * Q) and so does a
+ *                 tuple of K [B, Q] tensors.  The pointers and strides travel by value in the launch
+ *   rew_dev, done_dev   [B] contiguous.  done is a number, not a flag
+ *   next_logp_dev [B] contiguous in q_dtype: log pi(a' | s') of the next action.  The entropy term is always present
+ *   alpha_dev     float64 [1] on the device, read when the kernel runs; NULL: the host double alpha
+ *   gamma, alpha  host doubles; a captured call keeps them
+ *   stats_dev     float64 [8] = {loss, mean current quantile (over B * K * Q), mean y (over B * M), mean |delta| (over n), share of the
+ *                 pairs with |delta| > 1 (over n: the linear branch; strictly greater, where ptg_td_loss counts >=), alpha as used, 0, 0}
+ *   y_dev         nullable: receives the targets y [B][M] contiguous in q_dtype
+ *   ws_dev        caller-owned device scratch, 8-byte aligned, at least ptg_quantile_loss_workspace(batch) bytes; its contents mean
+ *                 nothing before or after the call
+ * Arithmetic: all of it in float64 whatever the dtypes are, every operation rounded once (no fused multiply-add), outputs rounded once
+ * on the store; exp (PTG_QL_LOG_ALPHA only) is the double-precision library function.  Row b, r = rew[b], dn = done[b], lp = next_logp[b]:
+ *   sort          s = the K * Q next quantiles of the row, all critics together, ascending in torch.sort's order: element p (flat index
+ *                 k * Q + i, value v_p) comes before element e iff v_p < v_e, or v_e is a NaN and v_p is not; otherwise the smaller
+ *                 flat index comes first.  A NaN ranks above +Inf.  s_0 .. s_(M-1) are kept
+ *   target        t_j = s_j - alpha * lp;   y_j = r + ((1 - dn) * gamma) * t_j
+ *   pairs         for every current quantile theta = cur_k[b][i], tau_i = (i + 0.5) / Q:  acc = 0, ls = 0, then for j = 0 .. M - 1 in
+ *                 this order:  delta = y_j - theta;  a = |delta|;  w = |tau_i - (delta < 0 ? 1 : 0)|;
+ *                 h = a > 1 ? a - 0.5 : 0.5 * (delta * delta);  c = clamp(delta, -1, 1);  acc = acc + w * c;  ls = ls + w * h
+ *   gradient      n = ((B * K) * Q) * M as a double;   d loss / d cur_k[b][i] = (-acc) / n
+ *   loss          (sum of ls over all rows, critics and quantiles) / n
+ *   statistics    stats[1] = (sum theta) / ((B * K) * Q), stats[2] = (sum y) / (B * M), stats[3] = (sum a) / n, stats[4] = (number of
+ *                 pairs with a > 1) / n
+ * Sums run in a fixed order (a lane adds its pairs in flat-index order, per wave a shuffle tree, the four waves = rows of a block in
+ * order, one partial per block in ws_dev, a last pass over the partials; no floating-point atomics): the same inputs give the same bits
+ * on every run.
+ * Known differences from SB3: it keeps cum_prob and, with float32 networks, every one of these lines in float32; here everything is
+ * float64 and rounded once.  SB3's .mean() sums in torch's order; here the order is the fixed one above.
+ * Bad rows.  There is no index, so PTG_E_INDEX never arises.  A row is non-finite when any kept y_j or any of its current quantiles is
+ * not finite: all of its K * Q gradients become NaN, its y is written as computed, stats[0..4] become NaN and the next ptg_sync returns
+ * PTG_E_NONFINITE once; the other rows are computed as usual.  A NaN or +Inf among the dropped top d * K values is legal, as a -Inf
+ * beside a larger value is for DQN's max; with d = 0 nothing is dropped, so a NaN or +Inf anywhere among the next quantiles makes the
+ * row non-finite.
+ * Enqueues kernels only -- one wave per row, four rows per 256-thread workgroup; one launch for B <= 4, else the rows and a
+ * one-workgroup merge of the block partials -- with no host synchronisation and no allocation, so the call may be captured into a
+ * hipGraph and replayed.  Reads nothing of the handle but its device: env state, the finished-episode ring, the ptg_vn_* statistics and
+ * every replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, stats_dev, rew_dev, done_dev, next_logp_dev or ws_dev (or a ws_dev that is
+ * not 8-byte aligned); a NULL cur_dev, next_dev or grad_dev entry in use; an unknown flag or dtype code; batch < 1 or above 2^31;
+ * n_critics outside [1, 4]; n_quantiles outside [1, 64]; n_drop outside [0, n_quantiles); a row stride below Q; PTG_QL_LOG_ALPHA
+ * without alpha_dev.
+ * ptg_quantile_loss_workspace(batch): bytes of scratch a batch of that size needs (64 per 4 rows); negative for batch < 1 or above 2^31. */
+#define PTG_QL_MAX_QUANTILES 64
+enum { PTG_QL_LOG_ALPHA = 1 };
+typedef struct ptg_ql {
+    int32_t flags, n_critics;
+    int32_t n_quantiles, n_drop;
+    int32_t q_dtype, rew_dtype;
+    int32_t done_dtype, reserved;
+    int64_t batch;
+    const void* cur_dev[PTG_TD_MAX_CRITICS];
+    int64_t cur_s_n[PTG_TD_MAX_CRITICS];
+    const void* next_dev[PTG_TD_MAX_CRITICS];
+    int64_t next_s_n[PTG_TD_MAX_CRITICS];
+    void* grad_dev[PTG_TD_MAX_CRITICS];
+    int64_t g_s_n[PTG_TD_MAX_CRITICS];
+    const void* rew_dev;
+    const void* done_dev;
+    const void* next_logp_dev;
+    const double* alpha_dev;
+    double gamma, alpha;
+    double* stats_dev;
+    void* y_dev;
+    void* ws_dev;
+} ptg_ql;
+int64_t ptg_quantile_loss_workspace(int64_t batch);
+int ptg_quantile_loss(ptg_env* env, const ptg_ql* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -26,9 +26,11 @@ LOSS_PPO, LOSS_A2C = 0, 1
 LOSS_NORM_ADV, LOSS_CLIP_VF = 1, 2
 OPTIM_ADAM, OPTIM_RMSPROP, OPTIM_POLYAK = 0, 1, 2
 OPTIM_CLIP, OPTIM_TARGETS, OPTIM_ZERO_GRAD = 1, 2, 4
-TD_DQN, TD_CRITICS = 0, 1                                 # 2 is left free for the quantile critics (TQC)
+TD_DQN, TD_CRITICS = 0, 1                                 # the quantile critics (TQC) have their own entry point: ptg_quantile_loss
 TD_ENTROPY, TD_LOG_ALPHA = 1, 2
 TD_MAX_CRITICS = 4
+QL_LOG_ALPHA = 1
+QL_MAX_QUANTILES = 64
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -113,6 +115,15 @@ class PtgTd(C.Structure):                                   # ptg_td: one call o
                 ("y_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
 
 
+class PtgQl(C.Structure):                                   # ptg_ql: one call of the quantile-Huber loss
+    _fields_ = [("flags", C.c_int32), ("n_critics", C.c_int32), ("n_quantiles", C.c_int32), ("n_drop", C.c_int32), ("q_dtype", C.c_int32),
+                ("rew_dtype", C.c_int32), ("done_dtype", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int64),
+                ("cur_dev", C.c_void_p * TD_MAX_CRITICS), ("cur_s_n", C.c_int64 * TD_MAX_CRITICS), ("next_dev", C.c_void_p * TD_MAX_CRITICS),
+                ("next_s_n", C.c_int64 * TD_MAX_CRITICS), ("grad_dev", C.c_void_p * TD_MAX_CRITICS), ("g_s_n", C.c_int64 * TD_MAX_CRITICS),
+                ("rew_dev", C.c_void_p), ("done_dev", C.c_void_p), ("next_logp_dev", C.c_void_p), ("alpha_dev", C.c_void_p),
+                ("gamma", C.c_double), ("alpha", C.c_double), ("stats_dev", C.c_void_p), ("y_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -122,7 +133,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
-           "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss",
+           "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -249,6 +260,9 @@ def lib():
     L.ptg_td_loss_workspace.argtypes = [C.c_int64]
     L.ptg_td_loss_workspace.restype = C.c_int64
     L.ptg_td_loss.argtypes = [vp, C.POINTER(PtgTd), vp]
+    L.ptg_quantile_loss_workspace.argtypes = [C.c_int64]
+    L.ptg_quantile_loss_workspace.restype = C.c_int64
+    L.ptg_quantile_loss.argtypes = [vp, C.POINTER(PtgQl), vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

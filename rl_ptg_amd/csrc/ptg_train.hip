@@ -11,6 +11,7 @@
 //   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
 //   k_optim_*         clip_grad_norm_, torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad over all tensors of an optimiser.
 //   k_td_*            the TD loss of DQN / the TD3 and SAC critics on a replay batch, its statistics and the gradients w.r.t. the Q-values.
+//   k_ql_*            TQC's quantile-Huber critic loss on a replay batch, its statistics and the gradients w.r.t. the current quantiles.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "ptg_handle.h"
 
@@ -1242,6 +1243,201 @@ k_td_final(TdArgs a)
     if (threadIdx.x == 0) td_finish(a, v, td_alpha(a));
 }
 
+// ================================================================================== the quantile-Huber loss of TQC's critics
+// sb3_contrib's TQC.train critic lines and quantile_huber_loss(sum_over_quantiles=False) (include/ptg_env.h, ptg_quantile_loss, states
+// the lines; tests/quantile_loss_restatement.py restates them): per row the K * Q next quantiles of all critics are sorted, the lowest
+// M = K * (Q - d) become targets, and every current quantile meets every target in a Huber pair -- K * Q * M pairs a row, none of which
+// is ever stored.  The one loss whose kernel is not "one lane per row": one WAVE per row, four rows per 256-thread block.  A wave's
+// slice of LDS (QL_MAX doubles) holds the staged next quantiles, then -- in place -- the kept ones in ascending order, then the targets
+// y.  The sort is a rank count: every element counts the elements that precede it under a strict total order (value, NaN last, flat
+// index), so the ranks are a permutation and the kept values depend on no race.  The lanes then stride over the K * Q (k, i) pairs and
+// run the j loop over the targets out of LDS (every lane reads the same address: a broadcast) in the header's order.  The K pointers
+// travel by value and are picked behind an unrolled k == kk guard, as td_row_critics picks its.  A wave without a row takes every
+// barrier and every tree with zero terms.  Sums: pl_block_sum (the four waves = rows in wave order), one partial per block, k_ql_final.
+constexpr int QL_MAX = PTG_TD_MAX_CRITICS * PTG_QL_MAX_QUANTILES, QL_PER = QL_MAX / 64;      // 256 values a row, at most 4 a lane
+
+struct QlArgs {                          // by value in the launch: a captured call holds no host memory
+    const void* cur[TD_K]; size_t cur_s[TD_K];   // elements
+    const void* nq[TD_K]; size_t nq_s[TD_K];
+    void* g[TD_K]; size_t g_s[TD_K];
+    const void *rew, *done, *lp;
+    const double* alpha_dev;
+    void* y;
+    double* stats;
+    double* ws;                          // one partial [PL_PITCH] per block
+    double gamma, alpha;
+    size_t B;
+    int K, Q, M, KQ, flags, rew_f64, done_f64, nblk;
+    int* err;
+};
+
+__device__ __forceinline__ double ql_alpha(const QlArgs& a)
+{
+    if (!a.alpha_dev) return a.alpha;
+    const double s = a.alpha_dev[0];
+    return (a.flags & PTG_QL_LOG_ALPHA) ? exp(s) : s;
+}
+
+// element (row, i) of critic k: the pointer is chosen behind an unrolled guard, never indexed by k
+template <typename IN>
+__device__ __forceinline__ double ql_pick(const void* const (&ptr)[TD_K], const size_t (&st)[TD_K], int k, size_t row, int i)
+{
+    double v = 0.0;
+#pragma unroll
+    for (int kk = 0; kk < TD_K; kk++)
+        if (kk == k) v = (double)((const IN*)ptr[kk])[row * st[kk] + (size_t)i];
+    return v;
+}
+
+// the sums of a whole batch -> the eight statistics; one thread
+__device__ __forceinline__ void ql_finish(const QlArgs& a, const double* sum, double alpha)
+{
+    const double BK = (double)a.B * (double)a.K, BKQ = BK * (double)a.Q, n = BKQ * (double)a.M;
+    a.stats[0] = sum[0] / n; a.stats[1] = sum[1] / BKQ; a.stats[2] = sum[2] / ((double)a.B * (double)a.M);
+    a.stats[3] = sum[3] / n; a.stats[4] = sum[4] / n;
+    a.stats[5] = alpha; a.stats[6] = 0.0; a.stats[7] = 0.0;
+}
+
+// ONE: the whole batch is this block (B <= 4 rows): rows and statistics in one launch
+template <typename IN, bool ONE>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_ql_rows(QlArgs a)
+{
+    __shared__ double slab[PL_WAVES * QL_MAX];               // 8 KiB: a wave's next quantiles -> the kept ones, sorted -> the targets
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const size_t row = (size_t)blockIdx.x * PL_WAVES + (size_t)w;
+    const bool live = row < a.B;                             // the ragged last block: no row, zero terms, every barrier and tree
+    const int KQ = a.KQ, Q = a.Q, M = a.M;
+    double* const s = slab + w * QL_MAX;
+    const double alpha = ql_alpha(a);
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    // 1. stage: the lanes stride over the flat index p = k * Q + i
+    double v[QL_PER];
+#pragma unroll
+    for (int t = 0; t < QL_PER; t++) {
+        const int p = lane + 64 * t;
+        v[t] = 0.0;
+        if (live && p < KQ) {
+            v[t] = ql_pick<IN>(a.nq, a.nq_s, p / Q, row, p % Q);
+            s[p] = v[t];
+        }
+    }
+    __syncthreads();
+    // 2. rank: e precedes p iff v_e < v_p, or v_p is a NaN and v_e is not, or neither precedes by value and e < p (torch.sort's order)
+    int rank[QL_PER];
+#pragma unroll
+    for (int t = 0; t < QL_PER; t++) {
+        const int p = lane + 64 * t;
+        rank[t] = QL_MAX;
+        if (live && p < KQ) {
+            const double x = v[t];
+            const bool xn = x != x;
+            int c = 0;
+#pragma unroll 4
+            for (int e = 0; e < KQ; e++) {
+                const double z = s[e];
+                const bool zn = z != z;
+                const bool e_first = z < x || (xn && !zn), p_first = x < z || (zn && !xn);
+                c += (e_first || (!p_first && e < p)) ? 1 : 0;
+            }
+            rank[t] = c;
+        }
+    }
+    __syncthreads();                                         // every read of the staged values is over: the slice is rewritten in place
+#pragma unroll
+    for (int t = 0; t < QL_PER; t++)
+        if (rank[t] < M) s[rank[t]] = v[t];                  // a permutation of 0 .. KQ - 1: one writer per slot
+    __syncthreads();
+    // 3. targets, in place; the current quantiles of this lane's pairs
+    bool bad = false;
+    double sum_y = 0.0;
+    if (live) {
+        const double r = td_rd(a.rew, a.rew_f64, row), dn = td_rd(a.done, a.done_f64, row);
+        const double al = alpha * (double)((const IN*)a.lp)[row], c = (1.0 - dn) * a.gamma;
+        for (int j = lane; j < M; j += 64) {
+            const double y = r + c * (s[j] - al);
+            s[j] = y;
+            if (a.y) ((IN*)a.y)[row * (size_t)M + (size_t)j] = (IN)y;
+            bad = bad || !pl_finite(y);
+            sum_y = sum_y + y;
+        }
+    }
+    double th[QL_PER];
+#pragma unroll
+    for (int t = 0; t < QL_PER; t++) {
+        const int p = lane + 64 * t;
+        th[t] = 0.0;
+        if (live && p < KQ) {
+            th[t] = ql_pick<IN>(a.cur, a.cur_s, p / Q, row, p % Q);
+            bad = bad || !pl_finite(th[t]);
+        }
+    }
+    __syncthreads();
+    bad = __any(bad ? 1 : 0) != 0;                           // the wave's row: any kept target or any current quantile not finite
+    // 4. pairs: the j loop in order, all of it out of LDS
+    const double n = (((double)a.B * (double)a.K) * (double)Q) * (double)M;
+    double sum_ls = 0.0, sum_q = 0.0, sum_ad = 0.0, sum_gt = 0.0;
+#pragma unroll
+    for (int t = 0; t < QL_PER; t++) {
+        const int p = lane + 64 * t;
+        if (live && p < KQ) {
+            const int k = p / Q, i = p % Q;
+            double g = nan;
+            if (!bad) {
+                const double theta = th[t], tau = ((double)i + 0.5) / (double)Q;
+                double acc = 0.0, ls = 0.0, ad = 0.0;
+                int gt = 0;
+#pragma unroll 4
+                for (int j = 0; j < M; j++) {                // unrolled for the LDS reads only: each accumulator still adds in j order
+                    const double dl = s[j] - theta, ab = fabs(dl);
+                    const double wt = fabs(tau - (dl < 0.0 ? 1.0 : 0.0));
+                    const double hb = ab > 1.0 ? ab - 0.5 : 0.5 * (dl * dl);
+                    const double cl = dl < -1.0 ? -1.0 : (dl > 1.0 ? 1.0 : dl);
+                    acc = acc + wt * cl;
+                    ls = ls + wt * hb;
+                    ad = ad + ab;
+                    gt += ab > 1.0 ? 1 : 0;
+                }
+                g = (-acc) / n;
+                sum_ls = sum_ls + ls; sum_q = sum_q + theta; sum_ad = sum_ad + ad; sum_gt = sum_gt + (double)gt;
+            }
+#pragma unroll
+            for (int kk = 0; kk < TD_K; kk++)
+                if (kk == k) ((IN*)a.g[kk])[row * a.g_s[kk] + (size_t)i] = (IN)g;
+        }
+    }
+    if (live && bad) {
+        sum_ls = sum_q = sum_y = sum_ad = sum_gt = nan;
+        if (lane == 0) a.err[5] = 1;
+    }
+    // 5. the row's terms -> the block's partial
+    double sums[PL_TERMS] = {sum_ls, sum_q, sum_y, sum_ad, sum_gt, 0.0};
+    pl_block_sum(sums, sh);
+    if (threadIdx.x == 0) {
+        if (ONE) ql_finish(a, sums, alpha);
+        else {
+            double* p = a.ws + (size_t)blockIdx.x * PL_PITCH;
+#pragma unroll
+            for (int k = 0; k < PL_TERMS; k++) p[k] = sums[k];
+        }
+    }
+}
+
+// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
+__global__ void __launch_bounds__(PL_BLOCK)
+k_ql_final(QlArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) v[k] += a.ws[(size_t)b * PL_PITCH + k];
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) ql_finish(a, v, ql_alpha(a));
+}
+
 // ================================================================================================= host side
 // ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
 template <typename V>
@@ -1268,6 +1464,19 @@ void launch_td(hipStream_t st, const TdArgs& a, bool dqn)
     if (dqn) hipLaunchKernelGGL((k_td_rows<IN, true, false>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_td_rows<IN, false, false>), grid, block, 0, st, a);
     hipLaunchKernelGGL(k_td_final, dim3(1), block, 0, st, a);
+}
+
+// ptg_quantile_loss's launches: the quantile dtype is the row kernel's template axis
+template <typename IN>
+void launch_ql(hipStream_t st, const QlArgs& a)
+{
+    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
+    if (a.nblk == 1) {                                       // up to 4 rows: everything in one launch
+        hipLaunchKernelGGL((k_ql_rows<IN, true>), grid, block, 0, st, a);
+        return;
+    }
+    hipLaunchKernelGGL((k_ql_rows<IN, false>), grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_ql_final, dim3(1), block, 0, st, a);
 }
 
 }  // namespace
@@ -1768,6 +1977,56 @@ int ptg_td_loss(ptg_env* h, const ptg_td* d, void* stream)
     if (d->q_dtype == PTG_OUT_F64) launch_td<double>(st, a, dqn);
     else launch_td<float>(st, a, dqn);
     return launch_check(h, "k_td_rows");
+}
+
+// ---- the quantile-Huber loss of TQC's critics, the statistics and the gradients w.r.t. the current quantiles -------------------------
+int64_t ptg_quantile_loss_workspace(int64_t batch)
+{
+    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;      // 2^29 blocks of four rows
+    return ((batch - 1) / PL_WAVES + 1) * PL_PITCH * (int64_t)sizeof(double);
+}
+
+int ptg_quantile_loss(ptg_env* h, const ptg_ql* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: null descriptor");
+    if (d->flags & ~PTG_QL_LOG_ALPHA) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: unknown flag in %d", d->flags);
+    const auto dtype_ok = [](int c) { return c == PTG_OUT_F32 || c == PTG_OUT_F64; };
+    if (ptg_quantile_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (!dtype_ok(d->q_dtype) || !dtype_ok(d->rew_dtype) || !dtype_ok(d->done_dtype))
+        return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: q_dtype, rew_dtype and done_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->rew_dev || !d->done_dev || !d->next_logp_dev || !d->stats_dev)
+        return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: null rew_dev, done_dev, next_logp_dev or stats_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: ws_dev is null or not aligned to 8 bytes");
+    if ((d->flags & PTG_QL_LOG_ALPHA) && !d->alpha_dev) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: PTG_QL_LOG_ALPHA needs alpha_dev");
+    if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
+    if (d->n_quantiles < 1 || d->n_quantiles > PTG_QL_MAX_QUANTILES)
+        return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: n_quantiles outside [1, %d]", PTG_QL_MAX_QUANTILES);
+    if (d->n_drop < 0 || d->n_drop >= d->n_quantiles) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: n_drop outside [0, n_quantiles)");
+    const int K = d->n_critics, Q = d->n_quantiles;
+    for (int k = 0; k < K; k++) {
+        if (!d->cur_dev[k] || !d->next_dev[k] || !d->grad_dev[k]) return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: null cur_dev, next_dev or grad_dev [%d]", k);
+        if (d->cur_s_n[k] < Q || d->next_s_n[k] < Q || d->g_s_n[k] < Q)
+            return set_err(h, PTG_E_INVALID, "ptg_quantile_loss: cur_s_n, next_s_n or g_s_n [%d] below %d", k, Q);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    QlArgs a{};
+    for (int k = 0; k < K; k++) {
+        a.cur[k] = d->cur_dev[k]; a.cur_s[k] = (size_t)d->cur_s_n[k];
+        a.nq[k] = d->next_dev[k]; a.nq_s[k] = (size_t)d->next_s_n[k];
+        a.g[k] = d->grad_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    }
+    a.rew = d->rew_dev; a.done = d->done_dev; a.lp = d->next_logp_dev; a.alpha_dev = d->alpha_dev;
+    a.y = d->y_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.gamma = d->gamma; a.alpha = d->alpha;
+    a.B = (size_t)d->batch; a.K = K; a.Q = Q; a.M = K * (Q - d->n_drop); a.KQ = K * Q; a.flags = d->flags;
+    a.rew_f64 = d->rew_dtype == PTG_OUT_F64; a.done_f64 = d->done_dtype == PTG_OUT_F64;
+    a.nblk = (int)((d->batch - 1) / PL_WAVES + 1);
+    a.err = h->P.err;
+    if (d->q_dtype == PTG_OUT_F64) launch_ql<double>(st, a);
+    else launch_ql<float>(st, a);
+    return launch_check(h, "k_ql_rows");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 """ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd;
-dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise -- see the end of the file.
+dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise, and tqc_critic_loss: TQC's
+quantile-Huber critic loss (HipEngine.quantile_loss, ptg_quantile_loss) -- see the end of the file.
 
     out = net(obs)                                            # [B, A + 1]: logits and a value column
     loss, stats = ppo_loss(engine, out[:, :A], out[:, A], actions, old_log_prob, advantages, returns, clip_range=0.2)
@@ -109,3 +110,40 @@ def sac_critic_loss(engine, q, next_q, rewards, dones, next_log_prob, *, gamma, 
     kw = dict(next_log_prob=next_log_prob.detach(), ent_coef=ent_coef.detach() if torch.is_tensor(ent_coef) else ent_coef,
               log_ent_coef=log_ent_coef.detach() if torch.is_tensor(log_ent_coef) else log_ent_coef, out=out, workspace=workspace)
     return _TdLossFn.apply(engine, "sac", [t.detach() for t in next_q], rewards, dones, gamma, kw, *q)
+
+
+# ------------------------------------------------------------------------------------------------- TQC's quantile critics
+#     with torch.no_grad():
+#         next_quantiles = critic_target(next_obs, next_actions)          # [B, K, Q]
+#     loss, stats = tqc_critic_loss(engine, critic(obs, actions), next_quantiles, rewards, dones, next_log_prob, gamma=0.9639,
+#                                   top_quantiles_to_drop_per_net=2, log_ent_coef=log_alpha)
+#     loss.backward()
+# Only the current quantiles are differentiable; the sort, the dropped tops, the entropy term and the targets are data, as they are
+# under sb3_contrib's torch.no_grad().
+class _QuantileLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, as_list, next_quantiles, rewards, dones, next_log_prob, gamma, drop, kw, *q):
+        res = engine.quantile_loss([t.detach() for t in q] if as_list else q[0].detach(), next_quantiles, rewards, dones, next_log_prob, gamma, drop, **kw)
+        ctx.grads = list(res.grad_quantiles) if as_list else [res.grad_quantiles]
+        ctx.mark_non_differentiable(res.stats)
+        return res.stats[0].to(q[0].dtype, copy=True), res.stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        return (None,) * 9 + tuple(g * grad_loss for g in ctx.grads)
+
+
+def tqc_critic_loss(engine, quantiles, next_quantiles, rewards, dones, next_log_prob, *, gamma, top_quantiles_to_drop_per_net, ent_coef=None,
+                    log_ent_coef=None, out=None, workspace=None):
+    """sb3_contrib's TQC.train critic loss -> (loss, stats): quantile_huber_loss(quantiles, rewards + (1 - dones) * gamma * (the lowest
+    K * (Q - d) of the sorted next_quantiles - alpha * next_log_prob), sum_over_quantiles=False).  quantiles: the critics' output on
+    (obs, actions), a [B, K, Q] tensor or a list of K [B, Q] tensors, carrying the graph; next_quantiles: the target critics' on
+    (next_obs, next_actions), data.  alpha: ent_coef (a float, or a float64 device tensor of 1 element) or exp(log_ent_coef) (a float64
+    device tensor of 1 element read when the kernel runs); stats float64 [8] = loss, mean current quantile, mean target, mean |delta|,
+    share of the pairs with |delta| > 1, alpha as used, 0, 0.  Arguments as HipEngine.quantile_loss."""
+    as_list = isinstance(quantiles, (list, tuple))
+    det = lambda t: t.detach() if torch.is_tensor(t) else t
+    kw = dict(ent_coef=det(ent_coef), log_ent_coef=det(log_ent_coef), out=out, workspace=workspace)
+    nxt = [det(t) for t in next_quantiles] if isinstance(next_quantiles, (list, tuple)) else det(next_quantiles)
+    return _QuantileLossFn.apply(engine, as_list, nxt, rewards, dones, det(next_log_prob), gamma, top_quantiles_to_drop_per_net, kw,
+                                 *(quantiles if as_list else (quantiles,)))

@@ -1,5 +1,5 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss, the TD losses and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+action heads, the policy loss, the TD losses, TQC's quantile loss and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
@@ -25,6 +25,9 @@ PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values 
 # what td_loss returns: stats float64 [8], the gradients w.r.t. the current Q-values (DQN: one tensor [B, A]; critics: a list of K tensors
 # shaped like q[k]) and the TD target [B] (None when not asked for)
 TdLoss = collections.namedtuple("TdLoss", "stats grad_q target")
+# what quantile_loss returns: stats float64 [8], the gradients w.r.t. the current quantiles (a [B, K, Q] tensor or a list of K [B, Q]
+# tensors, as the quantiles came) and the targets [B, M] (None when not asked for)
+QuantileLoss = collections.namedtuple("QuantileLoss", "stats grad_quantiles target")
 
 
 class OptimPlan:
@@ -52,6 +55,12 @@ def step(x):
 def one_or_all(n):
     """a parameter shared by the batch (1 element) or one per row (contiguous [n], [n, 1] or [1, n])"""
     return lambda x: None if x.numel() == 1 or (x.numel() == n and x.dim() <= 2 and x.is_contiguous()) else f"1 element or a contiguous [{n}] tensor"
+
+
+def stacked(x):
+    """[B, K, Q] quantiles of K critics, possibly a slice of a wider tensor: critic k is the [B, Q] view x[:, k]"""
+    ok = (x.shape[2] <= 1 or x.stride(2) == 1) and x.stride(1) >= 0 and (x.shape[0] <= 1 or x.stride(0) >= x.shape[2])
+    return None if ok else "unit stride along the quantiles, a row stride >= Q and a non-negative critic stride"
 
 
 def non_negative(x):
@@ -708,6 +717,120 @@ class TrainOps:
         with torch.cuda.device(self.device):
             self._chk(self._L.ptg_td_loss(self._h, C.byref(d), self._stream()))
         return TdLoss(stats, g_q, target)
+
+    # ------------------------------------------------------------------ TQC's quantile-Huber critic loss and its gradients
+    def quantile_loss_workspace(self, batch):
+        """the device scratch of quantile_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
+        nbytes = self._L.ptg_quantile_loss_workspace(int(batch))
+        if nbytes < 0:
+            raise ValueError(f"quantile_loss_workspace: batch must be in [1, 2^31], got {batch}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def _quantile_views(self, who, name, x, dtypes, B=None, K=None, Q=None, exc=TypeError):
+        """a [B, K, Q] tensor or a list of K [B, Q] tensors -> the K checked [B, Q] views"""
+        if isinstance(x, (list, tuple)):
+            if not 1 <= len(x) <= _lib.TD_MAX_CRITICS or (K is not None and len(x) != K):
+                raise ValueError(f"{who}: {name} must hold {K if K is not None else f'1 to {_lib.TD_MAX_CRITICS}'} critics, got {len(x)}")
+            views = []
+            for k, t in enumerate(x):
+                views.append(check(self, who, f"{name}[{k}]", t, dtypes=dtypes, shape=(B, Q), rule=rows, exc=exc))
+                if k == 0:
+                    dtypes, (B, Q) = (t.dtype,), t.shape
+            return views
+        x = check(self, who, name, x, dtypes=dtypes, shape=(B, K, Q), rule=stacked, exc=exc)
+        if not 1 <= x.shape[1] <= _lib.TD_MAX_CRITICS:
+            raise ValueError(f"{who}: {name} must be [B, K, Q] with 1 <= K <= {_lib.TD_MAX_CRITICS}, got shape {tuple(x.shape)}")
+        return [x[:, k] for k in range(x.shape[1])]
+
+    def quantile_loss(self, quantiles, next_quantiles, rewards, dones, next_log_prob, gamma, top_quantiles_to_drop_per_net, *, ent_coef=None,
+                      log_ent_coef=None, out=None, workspace=None, want_target=False):
+        """Enqueue, on the current stream, the critic lines of sb3_contrib's TQC.train on one replay batch -- the sort of the target
+        critics' quantiles, the drop of the top ones, the entropy term, the TD targets and quantile_huber_loss(sum_over_quantiles=False)
+        -- together with the gradients with respect to the current quantiles (include/ptg_env.h: ptg_quantile_loss, which states the
+        arithmetic).
+        quantiles (current critics on (s, a)) and next_quantiles (target critics on (s', a')): a [B, K, Q] tensor with unit stride along
+        Q and a row stride >= Q, or a list of K [B, Q] tensors with unit column stride and a row stride >= Q each; 1 <= K <= 4,
+        1 <= Q <= 64, one float dtype for both.  top_quantiles_to_drop_per_net: an int d, 0 <= d < Q; M = K * (Q - d) targets are kept.
+        rewards and dones: contiguous [B] (or [B, 1]), float32 or float64 each on its own -- what DeviceReplayBuffer.sample() returns;
+        next_log_prob [B] (or [B, 1]) in the quantiles' dtype.  Exactly one of ent_coef (a Python float, kept by a captured call, or a
+        float64 device tensor of 1 element, read when the kernel runs) and log_ent_coef (a float64 device tensor of 1 element holding
+        log alpha).  gamma: a finite Python float.
+        Returns QuantileLoss(stats float64 [8] = loss, mean current quantile, mean target, mean |delta|, share of the pairs with
+        |delta| > 1, alpha as used, 0, 0; grad_quantiles = d loss / d quantiles, a tensor or a list as the quantiles came; target
+        [B, M] with want_target, else None).  out: an earlier result, reused by a captured call (its target, when not None, is
+        written); workspace: quantile_loss_workspace(B) or larger, allocated when missing.  Outputs must not overlap each other or the
+        inputs: a tensor given twice is refused, any other overlap is not checked.  No synchronisation; a non-finite row makes the
+        next sync() raise PtgError (PTG_E_NONFINITE)."""
+        torch = self._torch
+        who = "quantile_loss"
+        floats = (torch.float32, torch.float64)
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
+        as_list = isinstance(quantiles, (list, tuple))
+        cur = self._quantile_views(who, "quantiles", quantiles, floats)
+        (B, Q), K, dt = cur[0].shape, len(cur), (cur[0].dtype,)
+        if B < 1 or not 1 <= Q <= _lib.QL_MAX_QUANTILES:
+            raise ValueError(f"{who}: quantiles need B >= 1 and 1 <= Q <= {_lib.QL_MAX_QUANTILES}, got B = {B}, Q = {Q}")
+        nxt = self._quantile_views(who, "next_quantiles", next_quantiles, dt, B, K, Q)
+        rewards = check(self, who, "rewards", column(rewards), dtypes=floats, shape=(B,), rule=contiguous)
+        dones = check(self, who, "dones", column(dones), dtypes=floats, shape=(B,), rule=contiguous)
+        next_log_prob = check(self, who, "next_log_prob", column(next_log_prob), dtypes=dt, shape=(B,), rule=contiguous)
+        drop = top_quantiles_to_drop_per_net
+        if isinstance(drop, bool) or not isinstance(drop, (int, np.integer)):
+            raise TypeError(f"{who}: top_quantiles_to_drop_per_net must be an int, got {type(drop).__name__}")
+        if not 0 <= drop < Q:
+            raise ValueError(f"{who}: top_quantiles_to_drop_per_net must be in [0, {Q}), got {drop}")
+        M = K * (Q - int(drop))
+        if (ent_coef is not None) + (log_ent_coef is not None) != 1:
+            raise ValueError(f"{who}: exactly one of ent_coef and log_ent_coef")
+        if not np.isfinite(float(gamma)):
+            raise ValueError(f"{who}: gamma must be finite, got {gamma}")
+        alpha_dev = None
+        if log_ent_coef is not None or torch.is_tensor(ent_coef):
+            alpha_dev = check(self, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
+                              dtypes=(torch.float64,), numel=1)
+        alpha = float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 3:
+                raise ValueError(f"{who}: out must be the QuantileLoss of an earlier call")
+            stats, g_q, target = out
+            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            if isinstance(g_q, (list, tuple)) != as_list:
+                raise ValueError(f"{who}: out.grad_quantiles must be a {'list of ' + str(K) + ' tensors' if as_list else 'tensor'}, as the quantiles are")
+            gs = self._quantile_views(who, "out.grad_quantiles", g_q, dt, B, K, Q, exc=ValueError)
+            if want_target and target is None:
+                raise ValueError(f"{who}: want_target, but out.target is None")
+            check(self, who, "out.target", target, dtypes=dt, shape=(B, M), rule=contiguous, optional=True, exc=ValueError)
+            starts = [t.data_ptr() for t in gs + cur + nxt + ([target] if target is not None else [])]
+            if len(set(starts)) != len(starts):             # the cheap half of "outputs must not overlap": one tensor given twice
+                raise ValueError(f"{who}: two of out.grad_quantiles, out.target, quantiles and next_quantiles start at the same address; the outputs must not "
+                                 "overlap each other or the inputs")
+        if workspace is not None:
+            check(self, who, f"workspace (quantile_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
+            if workspace.numel() < self._L.ptg_quantile_loss_workspace(B):
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_quantile_loss_workspace(B)}")
+        else:
+            workspace = self.quantile_loss_workspace(B)
+        if out is None:
+            with torch.cuda.device(self.device):
+                stats = torch.empty(8, dtype=torch.float64, device=self.device)
+                if as_list:
+                    g_q = gs = [torch.empty((B, Q), dtype=dt[0], device=self.device) for _ in range(K)]
+                else:
+                    g_q = torch.empty((B, K, Q), dtype=dt[0], device=self.device)
+                    gs = [g_q[:, k] for k in range(K)]
+                target = torch.empty((B, M), dtype=dt[0], device=self.device) if want_target else None
+        d = _lib.PtgQl(flags=_lib.QL_LOG_ALPHA if log_ent_coef is not None else 0, n_critics=K, n_quantiles=Q, n_drop=int(drop),
+                       q_dtype=_out_code(torch, dt[0]), rew_dtype=_out_code(torch, rewards.dtype), done_dtype=_out_code(torch, dones.dtype), batch=B,
+                       rew_dev=_ptr(rewards), done_dev=_ptr(dones), next_logp_dev=_ptr(next_log_prob), alpha_dev=_ptr(alpha_dev), gamma=float(gamma),
+                       alpha=alpha, stats_dev=_ptr(stats), y_dev=_ptr(target), ws_dev=_ptr(workspace))
+        for k in range(K):
+            d.cur_dev[k], d.cur_s_n[k] = cur[k].data_ptr(), max(cur[k].stride(0), Q)
+            d.next_dev[k], d.next_s_n[k] = nxt[k].data_ptr(), max(nxt[k].stride(0), Q)
+            d.grad_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), Q)
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_quantile_loss(self._h, C.byref(d), self._stream()))
+        return QuantileLoss(stats, g_q, target)
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):
