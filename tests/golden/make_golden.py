@@ -13,7 +13,8 @@ Files written
                              bounds, r_level, T-OPT totals  (reference: load_data + Preprocessing)
   traj_<case>.npz            trajectories of n reference envs stepped in DummyVecEnv order
   units_<op>.npz             _get_index for every distinct T_cat x 6 destination tables
-`make_golden.py tables` writes only the trajectories on generated process tables (synthetic_table_cases).
+`make_golden.py tables` writes only the trajectories on generated process tables (synthetic_table_cases), `make_golden.py config`
+only the fixtures under an edited config_env.yaml (edited_config_cases: traj_cfg_*, prep_cfg_*, cfg_liveness.json).
 """
 import json
 import math
@@ -333,6 +334,7 @@ def main():
                    "which is not part of the trajectory", extra_meta=dict(fail_step=t_fail, fail_h=h_fail, fail_action=int(acts[t_fail, 0])))
     s.close()
     synthetic_table_cases()
+    edited_config_cases()
     print("done")
 
 
@@ -394,6 +396,167 @@ def synthetic_table_cases():
     s.close()
 
 
+def edited_config():
+    """config_env.yaml with every scalar numeric constant moved off its default (scenario, load level, step sizes, episode length and
+    price_ahead are set per case).  Keys that share a default get different values -- the six ladder rungs 1, 2, 23, 3, 34, 4 of the two
+    directions and time2_start_f_p, the five lower bounds that default to 0.  Kept valid: upper above lower bounds with every range at
+    least half its default width, each ladder strictly increasing in the order the reference compares it, t_cat_startup_cold <
+    t_cat_startup_hot, the [off, partial, full] entries of meth_stats_load ordered."""
+    ov = dict(
+        noise=7, state_change_penalty=0.15,
+        ch4_price_fix=14.2, heat_price=5.1, o2_price=9.3, water_price=7.5, eeg_el_price=16.9,
+        H_u_CH4=36.5, H_u_H2=10.5, h_H2O_evap=2300, dt_water=85, cp_water=4.3, rho_water=970, convert_mol_to_Nm3=0.0229,
+        Molar_mass_CO2=46.0, Molar_mass_H2O=19.0, min_load_electrolyzer=0.2, eta_CHP=0.41,
+        t_cat_standby=201.5, t_cat_startup_cold=172, t_cat_startup_hot=331,
+        # each threshold is moved across a value `time_op = i + j * step_size` takes on the sim_step 60 tape (multiples of 30 from i = 0), so
+        # that putting it back changes a decision
+        time1_start_p_f=2400, time2_start_f_p=450,
+        # partial -> full -> partial, in the order env/ptg_gym_env.py:649-679 walks it
+        time1_p_f_p=65, time2_p_f_p=125, time_p_f=230, time23_p_f_p=250, time3_p_f_p=295, time34_p_f_p=395, time4_p_f_p=443,
+        time45_p_f_p=575, time5_p_f_p=655,
+        # full -> partial -> full (:715-745)
+        time1_f_p_f=25, time_f_p=115, time2_f_p_f=159, time23_f_p_f=205, time3_f_p_f=309, time34_f_p_f=355, time4_f_p_f=459,
+        time45_f_p_f=505, time5_f_p_f=595,
+        i_fully_developed=11000, j_fully_developed=90,
+        el_l_b=-12, el_u_b=95, gas_l_b=0.5, gas_u_b=30, eua_l_b=20, eua_u_b=105, T_l_b=8, T_u_b=620, h2_l_b=0.002, ch4_l_b=0.0005,
+        h2_res_l_b=0.00002, h2o_l_b=0.05, heat_l_b=40, heat_u_b=1900,
+        r_0_values=dict(el_price=[3], gas_price=[7], eua_price=[40]))
+    import yaml
+    with open(os.path.join(rd.REF, "config", "config_env.yaml")) as f:
+        base = yaml.safe_load(f)
+    msl = {}
+    for op, d in base["meth_stats_load"].items():           # partial load x 1.07, full load x 0.93 (heating: x 1.02 / x 0.98, which keeps OP2's ordered)
+        msl[op] = {k: list(v) for k, v in d.items()}
+        for k in ("Meth_H2_flow", "Meth_CH4_flow", "Meth_H2_res_flow", "Meth_H2O_flow", "Meth_el_heating"):
+            up, dn = (1.02, 0.98) if k == "Meth_el_heating" else (1.07, 0.93)
+            msl[op][k] = [d[k][0], d[k][1] * up, d[k][2] * dn]
+            assert msl[op][k][0] <= msl[op][k][1] <= msl[op][k][2], (op, k)
+    ov["meth_stats_load"] = msl
+    scalars = [k for k, v in base.items() if isinstance(v, (int, float)) and not isinstance(v, bool)
+               and k not in ("scenario", "price_ahead", "time_step_op", "eps_len_d", "sim_step")]
+    assert sorted(k for k in ov if k not in ("meth_stats_load", "r_0_values")) == sorted(scalars)
+    assert all(ov[k] != base[k] for k in scalars)
+    for grp in (["time1_p_f_p", "time2_p_f_p", "time_p_f", "time23_p_f_p", "time3_p_f_p", "time34_p_f_p", "time4_p_f_p", "time45_p_f_p",
+                 "time5_p_f_p"], ["time1_f_p_f", "time_f_p", "time2_f_p_f", "time23_f_p_f", "time3_f_p_f", "time34_f_p_f", "time4_f_p_f",
+                                  "time45_f_p_f", "time5_f_p_f"]):
+        assert all(ov[a] < ov[b] for a, b in zip(grp, grp[1:])), grp
+    ints = [ov[k] for k in scalars if k.startswith("time") or k.endswith("fully_developed")]
+    assert len(set(ints)) == len(ints) == 22
+    assert ov["t_cat_startup_cold"] < ov["t_cat_startup_hot"]
+    for lo, hi in (("el_l_b", "el_u_b"), ("gas_l_b", "gas_u_b"), ("eua_l_b", "eua_u_b"), ("T_l_b", "T_u_b"), ("heat_l_b", "heat_u_b")):
+        assert ov[hi] - ov[lo] >= 0.5 * (base[hi] - base[lo]), lo
+    for op in msl:
+        for lo, k in (("h2_l_b", "Meth_H2_flow"), ("ch4_l_b", "Meth_CH4_flow"), ("h2_res_l_b", "Meth_H2_res_flow"), ("h2o_l_b", "Meth_H2O_flow")):
+            assert msl[op][k][2] - ov[lo] >= 0.5 * (base["meth_stats_load"][op][k][2] - base[lo]), (op, lo)
+    return ov
+
+
+# reference kwargs name of an oracle constant
+_KW_OF = {"r_0": "reward_level"}
+LIVE_SKIP = ("raw_modified", "action_type", "train_or_eval")
+
+
+def _ref_outputs(kw, actions, seed, train_or_eval):
+    out = rd.run_vector(kw, actions, seed=seed, train_or_eval=train_or_eval)
+    return {k: np.asarray(out[k]) for k in ("ints", "f64s", "obs", "done", "n_noise", "infos", "post_reset_obs", "post_reset_int",
+                                            "post_reset_at", "reset_obs", "reset_int", "reset_info") if k in out}
+
+
+def liveness(kw, kw_default, actions, seed, train_or_eval):
+    """Decided by the reference alone: for every constant of the env's input contract (src/rl_utils.py:337-405) whose value under the
+    edited config differs from its value under the default config, the reference env runs again with that one constant put back
+    (`prefix` steps of the tape) -> (defaults, {key: dict(max_rel, max_excess, int_changed)} of the keys with any recorded output changed).
+    max_excess: the largest |change| / (ATOL32 + RTOL32 |value|) over observations, rewards and info rows."""
+    c_e, _, _ = po.split_reference_kwargs(kw, train_or_eval)
+    c_d, _, _ = po.split_reference_kwargs(kw_default, train_or_eval)
+    keys = [k for k in po.CONST_KEYS if k not in LIVE_SKIP and c_e[k] != c_d[k]]
+    base = _ref_outputs(kw, actions, seed, train_or_eval)
+    defaults, live = {}, {}
+    for k in keys:
+        kk = _KW_OF.get(k, k)
+        kw1 = dict(kw)
+        kw1[kk] = kw_default[kk]
+        defaults[k] = c_d[k]
+        got = _ref_outputs(kw1, actions, seed, train_or_eval)
+        if all(a.shape == got[q].shape and np.array_equal(a, got[q], equal_nan=True) for q, a in base.items()):
+            continue
+        int_changed = any(base[q].shape != got[q].shape or not np.array_equal(base[q], got[q])
+                          for q in ("ints", "done", "n_noise", "post_reset_int", "post_reset_at", "reset_int"))
+        rel = exc = 0.0
+        for a, b in [(got[q], base[q]) for q in ("obs", "infos", "reset_obs") if q in base] + [(got["f64s"][..., 0], base["f64s"][..., 0])]:
+            d = np.abs(a - b)
+            nz = b != 0
+            rel = max(rel, float(np.max(d[nz] / np.abs(b[nz]))) if nz.any() else 0.0)
+            exc = max(exc, float(np.max(d / (H.ATOL32 + H.RTOL32 * np.abs(b)))))
+        live[k] = dict(max_rel=rel, max_excess=exc, int_changed=bool(int_changed))
+    return defaults, live
+
+
+def edited_config_cases():
+    """Trajectories and Preprocessing products of the unmodified reference under an edited config_env.yaml (`edited_config`), on the
+    synthetic markets.  Runs on its own (`make_golden.py config`); the files above are not touched.  Each trajectory's meta carries the
+    whole override dict (`env_overrides`), the default value of every constant the edits reach (`defaults`), the keys that are live in
+    it (`live_keys`, `liveness`) and the tape prefix the liveness runs used (`live_prefix`); cfg_liveness.json lists the reached
+    constants that are dead in every case."""
+    sm = synth_markets()
+    ov = edited_config()
+    cases = [
+        # (name, per-case config, train_steps, split, mode, traj kwargs, seed, tape maker, liveness prefix)
+        ("a", dict(scenario=2, operation="OP2", eps_len_d=1, sim_step=60), 200000, "train", "train", {}, 4001,
+         lambda g: toggler_tape(g, 2600, 2), 2600,
+         "edited config, sim_step=60 toggler: every ladder rung with the edited ladders; eps_len_d=1 (1435-step episodes)"),
+        ("b", dict(scenario=1, operation="OP1", eps_len_d=2, raw_modified="raw"), 20000, "train", "train", dict(action_type="continuous"), 4002,
+         lambda g: to_continuous(g, sticky_tape(g, 700, 3, 1 / 5.0)), 700,
+         "edited config, raw features (gas / EUA bounds live), continuous actions with decode edge cases, eps_len_d=2: terminations"),
+        ("c", dict(scenario=3, operation="OP2", eps_len_d=32), 1500000, "val", "eval", {}, 4003,
+         lambda g: sticky_tape(g, 700, 2, 1 / 6.0), 700,
+         "edited config, BS3 (CHP / EEG path), val split in eval mode: the 24 info fields carry every revenue and cost term"),
+        ("d", dict(scenario=1, operation="OP1", eps_len_d=2, time_step_op=3, sim_step=120, raw_modified="raw", price_ahead=9), 200000,
+         "train", "train", {}, 4004, lambda g: H.toggler_tape(g, 900, 2, warm=70).astype(np.int64), 900,
+         "edited config, time_step_op=3 with sim_step=120 (window 40), raw features, price_ahead=9"),
+        ("e", dict(scenario=2, operation="OP2", eps_len_d=2, time_step_op=4, sim_step=300, price_ahead=5), 100000, "train", "train",
+         dict(action_type="continuous"), 4005, lambda g: to_continuous(g, H.toggler_tape(g, 800, 2, warm=30).astype(np.int64)), 800,
+         "edited config, time_step_op=4 with sim_step=300 (window 75), continuous actions, price_ahead=5, eps_len_d=2: a termination"),
+    ]
+    reached, live_any = set(), set()
+    for name, cfg, train_steps, split, mode, kw_over, seed, tape, prefix, note in cases:
+        scen, op = cfg["scenario"], cfg["operation"]
+        full = dict(ov, **cfg)
+        print(f"synthetic / edited config / case {name}: BS{scen} / {op} / {cfg}")
+        s = rd.RefSetup(full, synthetic_market=sm, train_steps=train_steps)
+        # the same case on the default constants (time_step_op is one of them: only the env reads it)
+        s0 = rd.RefSetup({k: v for k, v in cfg.items() if k != "time_step_op"}, synthetic_market=sm, train_steps=train_steps)
+        g = np.random.default_rng(seed)
+        acts = tape(g)
+        kw, kw0 = dict(s.kwargs(split), **kw_over), dict(s0.kwargs(split), **kw_over)
+        defaults, live = liveness(kw, kw0, acts[:prefix], seed, mode)
+        reached |= set(defaults)
+        live_any |= set(live)
+        for k, v in live.items():
+            print(f"    live {k:24s} max_rel={v['max_rel']:.3e} max_excess={v['max_excess']:.3e} int_changed={v['int_changed']}")
+        print(f"    dead here: {sorted(set(defaults) - set(live))}")
+        pname = f"cfg_{name}_bs{scen}_{op}"
+        pmeta = dict(market="synth", eps_len_d=cfg["eps_len_d"], sim_step=cfg.get("sim_step", 600), price_ahead=cfg.get("price_ahead", 13),
+                     env_overrides=full, t_opt=ref_t_opt(s))
+        save_prep(pname, s, pmeta)
+        tname = f"cfg_{name}_bs{scen}_{op.lower()}_{cfg.get('raw_modified', 'mod')}_{'cont' if kw_over else 'disc'}"
+        out = save_traj(tname, s, pname, split, mode, acts, seed, kw_over, note=note,
+                        extra_meta=dict(env_overrides=full, defaults=jsonable(defaults), live_keys=sorted(live), liveness=live,
+                                        live_prefix=int(prefix)))
+        pt, ft = set(out["ints"][..., 6].reshape(-1).tolist()), set(out["ints"][..., 7].reshape(-1).tolist())
+        if name == "a":
+            assert pt >= {5, 8, 9, 10, 11, 12} and ft >= {6, 7, 13, 14, 15, 16}, (pt, ft)
+            assert set(out["ints"][..., 0].reshape(-1).tolist()) == {0, 1, 2, 3, 4}
+        if name in ("b", "e"):
+            assert out["done"].sum() >= 1
+        s.close(); s0.close()
+    dead = sorted(reached - live_any)
+    with open(os.path.join(OUT, "cfg_liveness.json"), "w") as f:
+        json.dump(dict(reached=sorted(reached), dead_everywhere=dead), f, indent=1)
+        f.write("\n")
+    print(f"  cfg_liveness.json reached={len(reached)} dead_everywhere={dead}")
+
+
 def ref_t_opt(setup):
     """T-OPT of each split as the reference prints it, unrounded: Meth_cum_reward_stats[-price_ahead] of its own calculate_optimum
     (src/rl_opt.py:145-147), which reads config_env.yaml relative to the working directory"""
@@ -431,5 +594,7 @@ def ref_failing_step(kw, actions, seed, train_or_eval):
 if __name__ == "__main__":
     if sys.argv[1:] == ["tables"]:
         synthetic_table_cases()
+    elif sys.argv[1:] == ["config"]:
+        edited_config_cases()
     else:
         main()

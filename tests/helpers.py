@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import ptg_oracle as po  # noqa: E402
 
 TRAJ_CASES = sorted(os.path.basename(p)[5:-4] for p in glob.glob(os.path.join(GOLD, "traj_*.npz")))
+CFG_CASES = [c for c in TRAJ_CASES if c.startswith("cfg_")]          # recorded under an edited config_env.yaml (make_golden.py config)
 PREP_CASES = sorted(os.path.basename(p)[5:-4] for p in glob.glob(os.path.join(GOLD, "prep_*.npz")))
 
 _cache = {}

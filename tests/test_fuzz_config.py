@@ -1,7 +1,8 @@
 """Differential fuzz against the CPU oracle with constants OTHER than the reference's config_env.yaml defaults: a user of the reference
 edits that file (thresholds of the partial / full-load ladders `config/config_env.yaml:133-155`, catalyst temperature thresholds `:130-131`,
-noise `:28`, prices `:104-120`, normalisation bounds `:158-173`, step size `:27`), and every one of those values reaches the kernels through
-`ptg_config` -- the golden fixtures pin the defaults only.  Each seed draws a configuration, drives 65 .. 1 000 envs through the step path
+noise `:28`, prices and species constants `:104-120`, normalisation bounds `:158-173`, step size `:27`), and every one of those values
+reaches the kernels through `ptg_config`.  (The oracle is pinned to the reference off the defaults by the edited-config fixtures,
+tests/golden/traj_cfg_*.npz, constant by constant: tests/test_config_liveness.py.)  Each seed draws a configuration, drives 65 .. 1 000 envs through the step path
 (`ptg_step`: hot kernel, generic kernel on the terminating step) and the fused path (`ptg_rollout`) with actions that visit every handler,
 and compares every observation, reward, done flag and the final integer state with `oracle/ptg_oracle.c` on the same action and noise tapes.
 Integers bit-exact, floats within the tolerances below."""
@@ -16,7 +17,9 @@ RTOL64, ATOL64 = 1e-11, 1e-13
 RTOL32, ATOL32 = 2e-7, 1e-9
 
 
-def _draw_config(rng, consts):
+def _draw_config(rng, consts, rng2):
+    """rng: the draws this test has always made, in their order; rng2: the constants added later (a generator of their own, so that
+    every value drawn before -- these constants, the noise tape, the actions -- is what it was)"""
     c = dict(consts)
     c["noise"] = float(rng.choice([0.0, 2.5, 10.0, 40.0]))
     cold = float(rng.uniform(40.0, 220.0))
@@ -43,6 +46,19 @@ def _draw_config(rng, consts):
     c["heat_u_b"] = float(rng.uniform(900, 2500))
     c["el_l_b"], c["el_u_b"] = float(rng.uniform(-30, 0)), float(rng.uniform(60, 120))
     c["state_change_penalty"] = float(rng.choice([0.0, 0.0, 0.25]))
+    # ---- appended: the constants the draws above leave at their defaults.  Upper bounds stay above lower bounds and every range at
+    # least half its default width, as for the edited-config fixtures (tests/golden/make_golden.py, edited_config)
+    c["gas_l_b"], c["gas_u_b"] = float(rng2.uniform(0.0, 2.0)), float(rng2.uniform(20.0, 45.0))          # live with raw features only
+    c["eua_l_b"], c["eua_u_b"] = float(rng2.uniform(5.0, 30.0)), float(rng2.uniform(80.0, 130.0))
+    for k in ("h2", "ch4", "h2_res", "h2o"):              # the lower bounds default to 0: a normalisation that drops one is exact there
+        c[f"{k}_u_b"] = float(consts[f"{k}_u_b"] * rng2.uniform(0.8, 1.3))
+        c[f"{k}_l_b"] = float(consts[f"{k}_u_b"] * rng2.uniform(0.0, 0.2))
+    c["heat_l_b"] = float(rng2.uniform(0.0, c["heat_u_b"] - 900.0))
+    for k in ("H_u_CH4", "H_u_H2", "dt_water", "cp_water", "rho_water", "Molar_mass_CO2", "Molar_mass_H2O", "h_H2O_evap"):
+        c[k] = float(consts[k] * rng2.uniform(0.85, 1.15))
+    c["convert_mol_to_Nm3"] = float(consts["convert_mol_to_Nm3"] * rng2.uniform(0.9, 1.1))
+    c["max_h2_volumeflow"] = c["convert_mol_to_Nm3"] * c["h2_u_b"]          # as EnvConfiguration derives it (src/rl_config_env.py:33)
+    # (ch4_price_fix is no field of ptg_config: it reaches the kernels as the gas series of business scenario 2)
     return c
 
 
@@ -60,7 +76,7 @@ def test_random_constants_vs_oracle(seed):
     layout = ["row", "feature", "row", "sb3_flat"][seed % 4] if out_dtype == "float32" else ["row", "feature"][(seed // 2) % 2]
     spec, _ = synthetic_spec(scenario=scenario, operation=operation, eps_len_d=4, sim_step=sim_step, raw_modified=raw_modified,
                              action_type=action_type, train_steps=60 * 8 * (4 * 86400 // sim_step))
-    base = _draw_config(rng, spec.consts)
+    base = _draw_config(rng, spec.consts, np.random.default_rng(7100 + seed))
     n, K1, K2 = [512, 777, 65, 1000][(seed // 4) % 4], 150, 130      # ragged last waves / workgroups too
     m = spec.markets[0]
     eng = HipEngine(base, spec.tables, spec.markets, n, device=0, out_dtype=out_dtype, obs_layout=layout)

@@ -35,6 +35,8 @@ def test_trajectory_vs_reference_golden(case, out_dtype, layout):
     n_post = 0
     check_every = 1 if K <= 1000 else 7
     ret_acc = np.zeros(n)
+    if case in H.CFG_CASES:                                    # an edited config_env.yaml: count the launches of k_step_hot
+        eng.profile(True)
     fin_expect, fin_got = [], []
     for t in range(K):
         obs, rew, done = eng.step(tr["actions"][t])
@@ -71,6 +73,12 @@ def test_trajectory_vs_reference_golden(case, out_dtype, layout):
             info = eng.info.cpu().numpy()
             np.testing.assert_allclose(info, tr["infos"][t], rtol=RTOL64, atol=ATOL64, err_msg=f"info rows, step {t}")
     assert n_post == len(post_at)
+    if case in H.CFG_CASES:
+        # with price_ahead 13 every step but an episode's last one ran on the hot kernel (the comparison above is about its records);
+        # other widths, and eval mode with its info rows, run on the generic kernel
+        hot = tr["meta"]["consts"]["price_ahead"] == 13 and not tr["meta"]["consts"]["train_or_eval"]
+        assert len(eng.profile_read()) == (K - int(tr["done"].any(axis=1).sum()) if hot else 0)
+        eng.profile(False)
     assert np.array_equal(eng.get_state("noise_count"), tr["noise_len"])
     r, l, ids = eng.finished_episodes()
     assert len(r) == 0

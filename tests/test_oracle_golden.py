@@ -97,7 +97,7 @@ def test_known_answers_from_survey():
 
 
 @pytest.mark.parametrize("case", ["real_bs1_op1_raw_cont_evalval", "real_bs1_op1_mod_cont_train", "synth_bs2_op2_term_penalty",
-                                  "synth_bs1_op1_s60_toggle"])
+                                  "synth_bs1_op1_s60_toggle", "cfg_a_bs2_op2_mod_disc"])
 def test_set_state_continues_the_golden_trajectory(case):
     """ptgo_set_state is complete: a FRESH oracle put into the state another one reached after K steps (same tape position, same
     module-global ep_index) continues the reference's trajectory bit for bit -- obs, reward, done, state and noise draws, across the
