@@ -42,7 +42,10 @@ extern "C" {
                              *     additive, version unchanged: + ptg_optim, ptg_optim_step, ptg_optim_workspace, ptg_optim_chunk (the optimiser step behind
                              *     the loss: grad-norm clip, Adam / RMSprop, Polyak, zero_grad); + ptg_td, ptg_td_loss, ptg_td_loss_workspace (DQN's
                              *     and the TD3 / SAC critics' loss with its gradients); + ptg_ql, ptg_quantile_loss, ptg_quantile_loss_workspace (TQC's
-                             *     quantile-Huber critic loss with its gradients); no earlier declaration changed */
+                             *     quantile-Huber critic loss with its gradients); + ptg_rs, ptg_rsample, ptg_rsample_backward (the training-time
+                             *     actor head of SAC / TQC forward and backward, TD3's smoothed target action); + ptg_al, ptg_actor_loss,
+                             *     ptg_actor_loss_workspace (the SAC / TQC / TD3 actor loss and the entropy-coefficient loss with their
+                             *     gradients); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -56,7 +59,8 @@ enum {
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
     PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss / ptg_td_loss an action outside [0, A) */
     PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1];
-                                * ptg_policy_loss / ptg_td_loss / ptg_quantile_loss a row it has no finite loss for */
+                                * ptg_policy_loss / ptg_td_loss / ptg_quantile_loss / ptg_actor_loss a row it has no finite loss for;
+                                * ptg_rsample / ptg_rsample_backward a non-finite mean, log_std, noise or incoming gradient */
 };
 
 /* table ids: order of op_data_files, src/rl_utils.py:108-113 */
@@ -789,8 +793,8 @@ int ptg_optim_step(ptg_env* env, const ptg_optim* d, void* stream);
  * current Q-values is a closed form of what the forward pass holds, so one pass emits the loss, five statistics, d loss / d Q and
  * (optionally) the target; the caller's backward starts from those (rl_ptg_amd/loss.py: dqn_loss, td3_critic_loss, sac_critic_loss).
  * Out of scope: TQC's quantile-Huber critic loss (it has its own entry point, ptg_quantile_loss below; kind 2 stays refused here), the
- * actor and entropy-coefficient losses, TD3's
- * target-action noise (it precedes the target networks), double DQN, prioritised replay, the networks.
+ * actor and entropy-coefficient losses (ptg_actor_loss), TD3's target-action noise (it precedes the target networks: ptg_rsample,
+ * PTG_RS_SMOOTH), double DQN, prioritised replay, the networks.
  * The call is described by a ptg_td, read during the call (B = batch, A = n_actions, K = n_critics):
  *   kind          PTG_TD_DQN | PTG_TD_CRITICS
  *   flags         PTG_TD_ENTROPY (critics only): SAC's term, the minimum loses alpha * next_log_prob.  PTG_TD_LOG_ALPHA (with
@@ -886,7 +890,7 @@ int ptg_td_loss(ptg_env* env, const ptg_td* d, void* stream);
  * differences, abs / where / comparison / mean over it, and autograd's walk back.  The kernel never stores a pair: one pass emits the
  * loss, four statistics, d loss / d current quantile and (optionally) the targets; the caller's backward starts from those
  * (rl_ptg_amd/loss.py: tqc_critic_loss).
- * Out of scope: the actor and entropy-coefficient losses, the networks.
+ * Out of scope: the actor and entropy-coefficient losses (ptg_actor_loss below), the networks.
  * The call is described by a ptg_ql, read during the call.  Sizes: B = batch rows, K = n_critics, Q = n_quantiles per critic,
  * d = n_drop (top_quantiles_to_drop_per_net), M = K * (Q - d) kept target quantiles.  The reference: B = 290, K = 2, Q = 30, d = 2,
  * M = 56, gamma = 0.9639, alpha = 0.00047; SB3's defaults: Q = 25, d = 2.
@@ -964,6 +968,163 @@ typedef struct ptg_ql {
 } ptg_ql;
 int64_t ptg_quantile_loss_workspace(int64_t batch);
 int ptg_quantile_loss(ptg_env* env, const ptg_ql* d, void* stream);
+
+/* ---- the training-time actor head: reparametrised sample, log-prob and their backward; TD3's smoothed target action -----------------
+ * Replaces what the reference's SAC and TQC (src/rl_config_agent.py:80-222; SB3 2.0.0a13 sac/policies.py Actor.action_log_prob with
+ * SquashedDiagGaussianDistribution) run on every gradient step between the actor network's (mean, log_std) and the critics: the
+ * log_std clamp to [-20, 2], exp, rsample, tanh, the Gaussian log-density, the log(1 - a^2 + 1e-6) correction -- and autograd's walk
+ * back over all of it -- and TD3.train's target-policy smoothing (normal_(0, target_policy_noise).clamp(-c, c), added, clamped again).
+ * ptg_act's squashed Gaussian serves while collecting: it is sized by n_envs, has no clamp and no gradient.  D = 1 as everywhere.
+ * The call is described by a ptg_rs, read during the call; ptg_rsample is the forward, ptg_rsample_backward the backward:
+ *   kind          PTG_RS_SQUASH (SAC / TQC) | PTG_RS_SMOOTH (TD3's target action: forward only, no log-prob)
+ *   flags         PTG_RS_DETERMINISTIC: z = 0; counter_dev is neither read nor advanced (and may be NULL)
+ *   q_dtype       PTG_OUT_F32 | PTG_OUT_F64: the element type of mean, log_std, act, logp and of the four gradient tensors
+ *   batch         B >= 1, a 64-bit count that is not tied to the handle's n_envs; at most 2^31
+ *   mean_dev      [B], element b at b * mean_s_n, mean_s_n >= 1
+ *   log_std_dev   [B], element b at b * log_std_s_n >= 1: the network's UNCLAMPED output.  Not read by PTG_RS_SMOOTH
+ *   seed, counter_dev   the draw: row b of the c-th call (c = *counter_dev, uint64 [1], read on the device) takes the words (w0, w1) of
+ *                 ptg_replay_sample's chain keyed (seed, c, b) -- NO global env offset: a row is a batch row, not an env.  A trailing
+ *                 one-thread kernel does *counter_dev += 1 in stream order unless the call is deterministic, as ptg_act does
+ *   noise_std, noise_clip, clip_lo, clip_hi   PTG_RS_SMOOTH only, host doubles: sigma_t >= 0 and finite, c >= 0, lo <= hi
+ *   act_dev       [B] contiguous in q_dtype: the action, unclipped (tanh keeps it inside [-1, 1])
+ *   logp_dev      [B] contiguous in q_dtype, nullable; refused for PTG_RS_SMOOTH
+ *   noise_dev     float64 [B] contiguous, nullable in the forward, where it receives z; the backward reads it (so it does not depend on
+ *                 the counter) and requires it
+ *   grad_act_dev, grad_logp_dev   backward inputs, [B] contiguous in q_dtype: d L / d act and d L / d logp; each nullable (= 0), not both
+ *   grad_mean_dev, grad_log_std_dev   backward outputs, element b at b * gm_s_n and b * gl_s_n (>= 1), both required
+ * Arithmetic: all of it in float64 whatever q_dtype is, every operation rounded once (no fused multiply-add), outputs rounded once on
+ * the store; exp, log, sqrt, cos, tanh are the double-precision library functions.  Row b, mu = mean[b], l = log_std[b]:
+ *   clamp         ls = l < -20 ? -20 : (l > 2 ? 2 : l)  (a NaN stays NaN);   pass = (-20 <= l && l <= 2);   sigma = exp(ls)
+ *   draw          u1 = (w0 + 1) * 2^-32;  u2 = w1 * 2^-32;  z = sqrt(-2 * log(u1)) * cos(6.283185307179586 * u2): ptg_act's Gaussian
+ *                 lines;  deterministic: z = 0
+ *   squash        g = mu + sigma * z;   a = tanh(g);   act = a
+ *                 logp = (((-(z * z)) / 2 - ls) - 0.9189385332046727) - log((1 - a * a) + 1e-6)
+ *   smooth        act = clip(mu + clip(sigma_t * z, -c, c), lo, hi),  clip(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x)  (ptg_act's)
+ *   backward      ls, pass, sigma, g, a recomputed as above with z = noise[b];  ga = grad_act[b], gl = grad_logp[b] (0 when NULL)
+ *                 d = 1 - a * a;   sz = sigma * z;   q = ((2 * a) * d) / (d + 1e-6)
+ *                 grad_mean = ga * d + gl * q
+ *                 grad_log_std = pass ? (ga * (d * sz) + gl * (q * sz - 1)) : 0      (torch's clamp gradient, inclusive at both ends)
+ * With log_std inside the clamp the forward gives the bits of ptg_act's squashed head at the same (seed, counter) on a handle with
+ * n_envs = B and no global env offset.
+ * Known difference from SB3: it computes these lines in float32 where the networks are float32, and draws with torch's generator.
+ * Bad rows: a non-finite mean or a NaN log_std (an infinite log_std clamps and is legal); in the backward also a non-finite incoming
+ * gradient or noise value.  A bad row gets NaN in act and logp (backward: in both gradients; its noise is written as drawn), the other
+ * rows are computed as usual, and the next ptg_sync (or any call that reports kernel-flagged errors) returns PTG_E_NONFINITE once.
+ * Enqueues kernels only -- one lane per row, 256-thread workgroups, one launch plus the counter kernel -- with no host synchronisation
+ * and no allocation, so a call may be captured into a hipGraph and replayed (a replay draws afresh).  Reads nothing of the handle but
+ * its device: env state, the finished-episode ring, the ptg_vn_* statistics and every replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor or mean_dev; an unknown kind, flag or dtype code; batch < 1 or above 2^31;
+ * a stride below 1; PTG_RS_SQUASH without log_std_dev; forward: NULL act_dev, NULL counter_dev unless deterministic, a noise_dev
+ * that is not 8-byte aligned, PTG_RS_SMOOTH with logp_dev, with a negative, NaN or infinite noise_std, a negative or NaN noise_clip,
+ * clip_lo > clip_hi or a NaN bound; backward: PTG_RS_SMOOTH, NULL (or misaligned) noise_dev, both incoming gradients NULL, a NULL
+ * gradient output. */
+enum { PTG_RS_SQUASH = 0, PTG_RS_SMOOTH = 1 };
+enum { PTG_RS_DETERMINISTIC = 1 };
+typedef struct ptg_rs {
+    int32_t kind, flags;
+    int32_t q_dtype, reserved;
+    int64_t batch;
+    const void* mean_dev;
+    int64_t mean_s_n;
+    const void* log_std_dev;
+    int64_t log_std_s_n;
+    uint64_t seed;
+    uint64_t* counter_dev;
+    double noise_std, noise_clip, clip_lo, clip_hi;
+    void* act_dev;
+    void* logp_dev;
+    double* noise_dev;
+    const void* grad_act_dev;
+    const void* grad_logp_dev;
+    void* grad_mean_dev;
+    int64_t gm_s_n;
+    void* grad_log_std_dev;
+    int64_t gl_s_n;
+} ptg_rs;
+int ptg_rsample(ptg_env* env, const ptg_rs* d, void* stream);
+int ptg_rsample_backward(ptg_env* env, const ptg_rs* d, void* stream);
+
+/* ---- the actor and entropy-coefficient losses of SAC / TQC / TD3, with their gradients, in one pass ---------------------------------
+ * Replaces the actor half of a gradient step of the reference's TD3, SAC and TQC (src/rl_config_agent.py:80-222; SB3 2.0.0a13 SAC.train,
+ * TD3.train, sb3_contrib's TQC.train):
+ *   ent_coef_loss = -(log_ent_coef * (log_prob + target_entropy).detach()).mean()
+ *   SAC  actor_loss = (ent_coef * log_prob - th.min(q_values_pi, dim=1)).mean()
+ *   TQC  actor_loss = (ent_coef * log_prob - critic(obs, a_pi).mean(2).mean(1)).mean()
+ *   TD3  actor_loss = -critic.q1_forward(obs, actor(obs)).mean()
+ * and autograd's walk back to the critics' outputs, the log-prob and log_ent_coef: closed forms of what the forward pass holds.
+ * The call is described by a ptg_al, read during the call (B = batch, K = n_critics, Q = n_quantiles):
+ *   kind          PTG_AL_MIN (SAC): q_dev[k] is [B], element b at b * q_s_n[k], stride >= 1, 1 <= K <= PTG_TD_MAX_CRITICS; n_quantiles
+ *                 is not read.  PTG_AL_MEAN (TQC; TD3 is K = Q = 1 without PTG_AL_ENTROPY): q_dev[k] is [B][Q], element (b, i) at
+ *                 b * q_s_n[k] + i with a row stride >= Q, 1 <= Q <= PTG_QL_MAX_QUANTILES: the stacked [B, K, Q] tensor (pointer offset
+ *                 k * Q, stride K * Q) and a list both fit.  PTG_AL_ALPHA_ONLY: only the entropy-coefficient loss; no q is read,
+ *                 n_critics and n_quantiles are not read, the flags must be PTG_AL_LOG_ALPHA | PTG_AL_ENT_COEF
+ *   flags         PTG_AL_ENTROPY: the alpha * lp term; needs logp_dev.  PTG_AL_LOG_ALPHA (with alpha_dev): the device scalar holds
+ *                 log alpha, alpha = exp of it; needs PTG_AL_ENTROPY or PTG_AL_ENT_COEF.  PTG_AL_ENT_COEF: also emit the
+ *                 entropy-coefficient loss; needs PTG_AL_LOG_ALPHA, logp_dev and a finite target_entropy
+ *   q_dtype       PTG_OUT_F32 | PTG_OUT_F64: the element type of every q tensor, of logp_dev and of the gradients but grad_log_alpha_dev
+ *   logp_dev      [B] contiguous in q_dtype: log pi(a_pi | s)
+ *   alpha_dev     float64 [1] on the device, read when the kernel runs; NULL: the host double alpha.  The three forms of alpha are
+ *                 ptg_td_loss's: a host double, a device scalar, a device log alpha.  Without PTG_AL_ENTROPY and PTG_AL_ENT_COEF alpha
+ *                 is 0 and nothing is read
+ *   target_entropy   H_t, a host double (SB3: -dim(action space) = -1)
+ *   stats_dev     float64 [8] = {actor_loss, ent_coef_loss, mean lp, mean m, alpha as used, d ent_coef_loss / d log alpha, 0, 0}, with 0
+ *                 where a part is not asked for (actor_loss and mean m for PTG_AL_ALPHA_ONLY; ent_coef_loss and its gradient without
+ *                 PTG_AL_ENT_COEF; mean lp when no flag reads it).  &stats_dev[4] is a float64 device scalar that ptg_td_loss,
+ *                 ptg_quantile_loss and a later ptg_actor_loss accept as alpha_dev (not a log: without their LOG_ALPHA flag)
+ *   grad_q_dev[k] shaped and strided (g_s_n[k]) like q_dev[k], required for k < K
+ *   grad_logp_dev [B] contiguous in q_dtype, nullable; goes with PTG_AL_ENTROPY
+ *   grad_log_alpha_dev   float64 [1], nullable; goes with PTG_AL_ENT_COEF
+ *   ws_dev        caller-owned device scratch, 8-byte aligned, at least ptg_actor_loss_workspace(batch) bytes
+ * Arithmetic: all of it in float64 whatever q_dtype is, every operation rounded once, outputs rounded once on the store; exp
+ * (PTG_AL_LOG_ALPHA only) is the double-precision library function.  Row b, lp = logp[b]:
+ *   MIN           m = q_0[b], k* = 0;  for k = 1 .. K - 1: l = q_k[b], and m = l, k* = k if l < m or l != l  (th.min's NaN rule; of
+ *                 equal values the first index wins);   d loss / d q_k[b] = [k == k*] * ((-1) / B), every k written
+ *   MEAN          m = (sum_k ((sum_i theta_ki) / Q)) / K, both sums from 0 in index order;   d loss / d theta = (-1) / ((B * K) * Q)
+ *   both          term = alpha * lp - m with PTG_AL_ENTROPY, else -m;   d loss / d lp[b] = alpha / B
+ *   batch         actor_loss = (sum term) / B;   mean lp = (sum lp) / B;   mean m = (sum m) / B
+ *                 with PTG_AL_ENT_COEF: S = sum (lp + H_t);  ent_coef_loss = -(log alpha * (S / B));  d / d log alpha = -(S / B)
+ * Sums run in ptg_policy_loss's fixed order (per wave a shuffle tree, the four waves of a 256-row block in order, one partial per block
+ * in ws_dev, a last pass over the partials; no floating-point atomics): the same inputs give the same bits on every run.
+ * Known differences from SB3: it computes these lines in float32 where the networks are float32, and sums in torch's order; here
+ * everything is float64, rounded once, in the fixed order above.
+ * Call order: SB3 computes ent_coef_loss BEFORE the critic update and the actor loss AFTER it, both with the alpha from before the
+ * alpha optimiser's step.  PTG_AL_ALPHA_ONLY exists so that the order can be reproduced: its stats_dev[4] keeps that alpha on the
+ * device for the critic loss and the later actor loss while the optimiser moves log alpha.
+ * Bad rows.  There is no index.  A row whose m or lp (when read) is not finite -- a NaN critic, a -Inf minimum, any non-finite
+ * quantile -- and every row when alpha (or, with alpha_dev, the scalar it is made from) is not finite gets NaN gradients; stats[0..3]
+ * and stats[5] (and grad_log_alpha_dev) become NaN and the next ptg_sync returns PTG_E_NONFINITE once; the other rows are computed as
+ * usual.  A +Inf critic beside a smaller one is legal for the minimum.
+ * Enqueues kernels only -- one lane per row; one launch for B <= 256, else the rows and a one-workgroup merge of the block partials --
+ * with no host synchronisation and no allocation, so the call may be captured into a hipGraph and replayed.  Reads nothing of the
+ * handle but its device: env state, the finished-episode ring, the ptg_vn_* statistics and every replay cursor are untouched.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, stats_dev or ws_dev (or a ws_dev that is not 8-byte aligned); an unknown
+ * kind, flag or dtype code; batch < 1 or above 2^31; n_critics outside [1, 4]; n_quantiles outside [1, 64] (MEAN); a NULL q_dev or
+ * grad_q_dev entry in use; a stride below 1 (MIN) or below Q (MEAN); PTG_AL_ALPHA_ONLY with PTG_AL_ENTROPY or without PTG_AL_ENT_COEF;
+ * PTG_AL_ENT_COEF without PTG_AL_LOG_ALPHA or with a target_entropy that is not finite; PTG_AL_LOG_ALPHA without alpha_dev or without
+ * a flag that uses alpha; a flag that reads logp_dev without it; grad_logp_dev without PTG_AL_ENTROPY; grad_log_alpha_dev without
+ * PTG_AL_ENT_COEF or not 8-byte aligned.
+ * ptg_actor_loss_workspace(batch): bytes of scratch a batch of that size needs (64 per 256 rows); negative for batch < 1 or above 2^31. */
+enum { PTG_AL_MIN = 0, PTG_AL_MEAN = 1, PTG_AL_ALPHA_ONLY = 2 };
+enum { PTG_AL_ENTROPY = 1, PTG_AL_LOG_ALPHA = 2, PTG_AL_ENT_COEF = 4 };
+typedef struct ptg_al {
+    int32_t kind, flags;
+    int32_t n_critics, n_quantiles;
+    int32_t q_dtype, reserved;
+    int64_t batch;
+    const void* q_dev[PTG_TD_MAX_CRITICS];
+    int64_t q_s_n[PTG_TD_MAX_CRITICS];
+    const void* logp_dev;
+    const double* alpha_dev;
+    double alpha, target_entropy;
+    double* stats_dev;
+    void* grad_q_dev[PTG_TD_MAX_CRITICS];
+    int64_t g_s_n[PTG_TD_MAX_CRITICS];
+    void* grad_logp_dev;
+    double* grad_log_alpha_dev;
+    void* ws_dev;
+} ptg_al;
+int64_t ptg_actor_loss_workspace(int64_t batch);
+int ptg_actor_loss(ptg_env* env, const ptg_al* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

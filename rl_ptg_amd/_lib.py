@@ -31,6 +31,10 @@ TD_ENTROPY, TD_LOG_ALPHA = 1, 2
 TD_MAX_CRITICS = 4
 QL_LOG_ALPHA = 1
 QL_MAX_QUANTILES = 64
+RS_SQUASH, RS_SMOOTH = 0, 1
+RS_DETERMINISTIC = 1
+AL_MIN, AL_MEAN, AL_ALPHA_ONLY = 0, 1, 2
+AL_ENTROPY, AL_LOG_ALPHA, AL_ENT_COEF = 1, 2, 4
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -124,6 +128,23 @@ class PtgQl(C.Structure):                                   # ptg_ql: one call o
                 ("gamma", C.c_double), ("alpha", C.c_double), ("stats_dev", C.c_void_p), ("y_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
 
 
+class PtgRs(C.Structure):                                   # ptg_rs: one call of the training-time actor head, forward or backward
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("q_dtype", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int64),
+                ("mean_dev", C.c_void_p), ("mean_s_n", C.c_int64), ("log_std_dev", C.c_void_p), ("log_std_s_n", C.c_int64),
+                ("seed", C.c_uint64), ("counter_dev", C.c_void_p), ("noise_std", C.c_double), ("noise_clip", C.c_double),
+                ("clip_lo", C.c_double), ("clip_hi", C.c_double), ("act_dev", C.c_void_p), ("logp_dev", C.c_void_p), ("noise_dev", C.c_void_p),
+                ("grad_act_dev", C.c_void_p), ("grad_logp_dev", C.c_void_p), ("grad_mean_dev", C.c_void_p), ("gm_s_n", C.c_int64),
+                ("grad_log_std_dev", C.c_void_p), ("gl_s_n", C.c_int64)]
+
+
+class PtgAl(C.Structure):                                   # ptg_al: one call of the actor / entropy-coefficient loss
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("n_critics", C.c_int32), ("n_quantiles", C.c_int32), ("q_dtype", C.c_int32),
+                ("reserved", C.c_int32), ("batch", C.c_int64), ("q_dev", C.c_void_p * TD_MAX_CRITICS), ("q_s_n", C.c_int64 * TD_MAX_CRITICS),
+                ("logp_dev", C.c_void_p), ("alpha_dev", C.c_void_p), ("alpha", C.c_double), ("target_entropy", C.c_double),
+                ("stats_dev", C.c_void_p), ("grad_q_dev", C.c_void_p * TD_MAX_CRITICS), ("g_s_n", C.c_int64 * TD_MAX_CRITICS),
+                ("grad_logp_dev", C.c_void_p), ("grad_log_alpha_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -134,6 +155,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
+           "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -263,6 +285,11 @@ def lib():
     L.ptg_quantile_loss_workspace.argtypes = [C.c_int64]
     L.ptg_quantile_loss_workspace.restype = C.c_int64
     L.ptg_quantile_loss.argtypes = [vp, C.POINTER(PtgQl), vp]
+    L.ptg_rsample.argtypes = [vp, C.POINTER(PtgRs), vp]
+    L.ptg_rsample_backward.argtypes = [vp, C.POINTER(PtgRs), vp]
+    L.ptg_actor_loss_workspace.argtypes = [C.c_int64]
+    L.ptg_actor_loss_workspace.restype = C.c_int64
+    L.ptg_actor_loss.argtypes = [vp, C.POINTER(PtgAl), vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

@@ -12,6 +12,8 @@
 //   k_optim_*         clip_grad_norm_, torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad over all tensors of an optimiser.
 //   k_td_*            the TD loss of DQN / the TD3 and SAC critics on a replay batch, its statistics and the gradients w.r.t. the Q-values.
 //   k_ql_*            TQC's quantile-Huber critic loss on a replay batch, its statistics and the gradients w.r.t. the current quantiles.
+//   k_rs_*            SB3's Actor.action_log_prob on a replay batch (SAC / TQC), forward and backward, and TD3's target-policy smoothing.
+//   k_al_*            the SAC / TQC / TD3 actor loss and the entropy-coefficient loss with their gradients.
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "ptg_handle.h"
 
@@ -1438,6 +1440,249 @@ k_ql_final(QlArgs a)
     if (threadIdx.x == 0) ql_finish(a, v, ql_alpha(a));
 }
 
+// ================================================================================== the training-time actor head
+// SB3's Actor.action_log_prob as SAC and TQC run it on a replay batch (include/ptg_env.h, ptg_rsample, states the lines;
+// tests/actor_restatement.py restates them): the log_std clamp, exp, the reparametrised sample, tanh, the Gaussian log-density and the
+// tanh correction -- and, in k_rs_bwd, autograd's walk back over all of it in closed form from the stored noise.  TD3's smoothed
+// target action is the third kind.  k_act's shape: one lane per row on consecutive rows, no cross-lane traffic, float64 arithmetic
+// whatever the dtype, rounded once on the store.  The draw is k_act's, keyed (seed, *counter, row) with no env offset.
+struct RsArgs {                          // by value in the launch: a captured call holds no host memory
+    const void* mean; size_t m_s;        // elements
+    const void* ls; size_t ls_s;
+    void *act, *logp;
+    double* noise;
+    const void *g_act, *g_logp;
+    void* g_mean; size_t gm_s;
+    void* g_ls; size_t gl_s;
+    const unsigned long long* counter;   // null when deterministic
+    unsigned long long seed;
+    double sigma_t, c, lo, hi;           // PTG_RS_SMOOTH
+    size_t B;
+    int kind;
+    int* err;
+};
+
+__device__ __forceinline__ double rs_clamp_log_std(double l) { return l < -20.0 ? -20.0 : (l > 2.0 ? 2.0 : l); }      // a NaN falls through
+
+template <typename IN>
+__global__ void __launch_bounds__(ACT_BLOCK)
+k_rs_fwd(RsArgs a)
+{
+    const size_t b = (size_t)blockIdx.x * ACT_BLOCK + threadIdx.x;
+    if (b >= a.B) return;                                    // the ragged last wave
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    double z = 0.0;
+    if (a.counter) {
+        const unsigned long long w = rb_draw_word(a.seed, a.counter[0], (unsigned long long)b);
+        const unsigned w0 = (unsigned)(w >> 32), w1 = (unsigned)w;
+        const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = (double)w1 * 2.3283064365386963e-10;      // 2^-32
+        z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    }
+    if (a.noise) a.noise[b] = z;
+    const double mu = (double)((const IN*)a.mean)[b * a.m_s];
+    IN* const act_o = (IN*)a.act; IN* const logp_o = (IN*)a.logp;
+    if (a.kind == PTG_RS_SMOOTH) {
+        if (!pl_finite(mu)) { act_o[b] = (IN)nan; a.err[5] = 1; return; }
+        const double n = a.sigma_t * z;
+        const double nc = n < -a.c ? -a.c : (n > a.c ? a.c : n);
+        const double x = mu + nc;
+        act_o[b] = (IN)(x < a.lo ? a.lo : (x > a.hi ? a.hi : x));
+        return;
+    }
+    const double l = (double)((const IN*)a.ls)[b * a.ls_s];
+    if (!pl_finite(mu) || l != l) {                          // NaN or Inf mean; NaN log_std (an infinite one clamps)
+        act_o[b] = (IN)nan;
+        if (logp_o) logp_o[b] = (IN)nan;
+        a.err[5] = 1;
+        return;
+    }
+    const double ls = rs_clamp_log_std(l);
+    const double g = mu + exp(ls) * z;
+    const double x = tanh(g);
+    act_o[b] = (IN)x;
+    if (logp_o) logp_o[b] = (IN)((((-(z * z) / 2.0) - ls) - 0.9189385332046727) - log((1.0 - x * x) + 1e-6));
+}
+
+template <typename IN>
+__global__ void __launch_bounds__(ACT_BLOCK)
+k_rs_bwd(RsArgs a)
+{
+    const size_t b = (size_t)blockIdx.x * ACT_BLOCK + threadIdx.x;
+    if (b >= a.B) return;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double mu = (double)((const IN*)a.mean)[b * a.m_s], l = (double)((const IN*)a.ls)[b * a.ls_s], z = a.noise[b];
+    const double ga = a.g_act ? (double)((const IN*)a.g_act)[b] : 0.0, gl = a.g_logp ? (double)((const IN*)a.g_logp)[b] : 0.0;
+    IN* const gm_o = (IN*)a.g_mean + b * a.gm_s; IN* const gls_o = (IN*)a.g_ls + b * a.gl_s;
+    if (!pl_finite(mu) || l != l || !pl_finite(z) || !pl_finite(ga) || !pl_finite(gl)) {
+        gm_o[0] = (IN)nan; gls_o[0] = (IN)nan;
+        a.err[5] = 1;
+        return;
+    }
+    const double ls = rs_clamp_log_std(l);
+    const bool pass = -20.0 <= l && l <= 2.0;                // torch's clamp gradient: inclusive at both ends
+    const double sigma = exp(ls);
+    const double x = tanh(mu + sigma * z);
+    const double d = 1.0 - x * x, sz = sigma * z;
+    const double q = ((2.0 * x) * d) / (d + 1e-6);
+    gm_o[0] = (IN)(ga * d + gl * q);
+    gls_o[0] = (IN)(pass ? ga * (d * sz) + gl * (q * sz - 1.0) : 0.0);
+}
+
+// ================================================================================== the actor and entropy-coefficient losses
+// SB3's SAC.train / TD3.train and sb3_contrib's TQC.train actor lines and the entropy-coefficient loss (include/ptg_env.h,
+// ptg_actor_loss, states the lines; tests/actor_restatement.py restates them) with d loss / d Q (or quantile), d loss / d log_prob and
+// d loss / d log alpha in closed form.  k_td_rows' shape: one lane per row, the critics' pointers and strides by value, every loop over
+// them unrolled over PTG_TD_MAX_CRITICS behind a k < K guard; a TQC lane walks its K * Q quantiles in index order (two strided reads
+// and one store each).  Four sums and a poison word go through the policy loss's fixed-order scheme.
+struct AlArgs {                          // by value in the launch
+    const void* q[TD_K]; size_t q_s[TD_K];       // elements
+    void* g[TD_K]; size_t g_s[TD_K];
+    const void* lp;
+    const double* alpha_dev;
+    void* g_lp;
+    double* g_la;
+    double* stats;
+    double* ws;                          // one partial [PL_PITCH] per block
+    double alpha, H_t;
+    size_t B;
+    int K, Q, kind, flags, nblk;
+    int* err;
+};
+
+// alpha as this call uses it (0 when neither the entropy term nor the entropy-coefficient loss is asked for) and whether it is usable
+__device__ __forceinline__ double al_alpha(const AlArgs& a, bool& ok)
+{
+    ok = true;
+    if (!(a.flags & (PTG_AL_ENTROPY | PTG_AL_ENT_COEF))) return 0.0;
+    double al = a.alpha;
+    if (a.alpha_dev) {
+        const double s = a.alpha_dev[0];
+        al = (a.flags & PTG_AL_LOG_ALPHA) ? exp(s) : s;
+        ok = pl_finite(s);
+    }
+    ok = ok && pl_finite(al);
+    return al;
+}
+
+// the sums of a whole batch -> the eight statistics and d loss / d log alpha; one thread
+__device__ __forceinline__ void al_finish(const AlArgs& a, const double* sum, double alpha)
+{
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double Bd = (double)a.B;
+    const bool bad = sum[4] != sum[4], ec = (a.flags & PTG_AL_ENT_COEF) != 0;
+    const bool reads_lp = (a.flags & (PTG_AL_ENTROPY | PTG_AL_ENT_COEF)) != 0;
+    double el = 0.0, gla = 0.0;
+    if (ec) {
+        const double sb = sum[3] / Bd;
+        el = -(a.alpha_dev[0] * sb);
+        gla = -sb;
+    }
+    a.stats[0] = bad ? nan : (a.kind == PTG_AL_ALPHA_ONLY ? 0.0 : sum[0] / Bd);
+    a.stats[1] = bad ? nan : el;
+    a.stats[2] = bad ? nan : (reads_lp ? sum[1] / Bd : 0.0);
+    a.stats[3] = bad ? nan : (a.kind == PTG_AL_ALPHA_ONLY ? 0.0 : sum[2] / Bd);
+    a.stats[4] = alpha;
+    a.stats[5] = bad ? nan : gla;
+    a.stats[6] = 0.0; a.stats[7] = 0.0;
+    if (ec && a.g_la) a.g_la[0] = bad ? nan : gla;
+}
+
+// ONE: the whole batch is this block (B <= PL_BLOCK): rows and statistics in one launch.  Otherwise the block leaves its partial sums
+// in the workspace for k_al_final.
+template <typename IN, bool ONE>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_al_rows(AlArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
+    const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    bool alpha_ok;
+    const double alpha = al_alpha(a, alpha_ok);
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // term, lp, m, lp + H_t, poison (NaN once a row is bad), unused
+    if (live) {
+        const int K = a.K, Q = a.Q;
+        const double Bd = (double)a.B;
+        const bool ent = (a.flags & PTG_AL_ENTROPY) != 0, reads_lp = (a.flags & (PTG_AL_ENTROPY | PTG_AL_ENT_COEF)) != 0;
+        const double lp = reads_lp ? (double)((const IN*)a.lp)[i] : 0.0;
+        double m = 0.0;
+        int ks = 0;
+        if (a.kind == PTG_AL_MIN) {
+            m = (double)((const IN*)a.q[0])[i * a.q_s[0]];
+#pragma unroll
+            for (int k = 1; k < TD_K; k++) {
+                if (k < K) {
+                    const double l = (double)((const IN*)a.q[k])[i * a.q_s[k]];
+                    if (l < m || l != l) { m = l; ks = k; }  // th.min: a NaN wins and then stays; of equal values the first
+                }
+            }
+        } else if (a.kind == PTG_AL_MEAN) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < TD_K; k++) {
+                if (k < K) {
+                    const IN* __restrict__ row = (const IN*)a.q[k] + i * a.q_s[k];
+                    double t = 0.0;
+                    for (int j = 0; j < Q; j++) t += (double)row[j];
+                    s += t / (double)Q;
+                }
+            }
+            m = s / (double)K;
+        }
+        const bool bad = !alpha_ok || !pl_finite(m) || !pl_finite(lp);
+        if (a.kind == PTG_AL_MIN) {
+            const double gq = (-1.0) / Bd;
+#pragma unroll
+            for (int k = 0; k < TD_K; k++)
+                if (k < K) ((IN*)a.g[k])[i * a.g_s[k]] = (IN)(bad ? nan : (k == ks ? gq : 0.0));
+        } else if (a.kind == PTG_AL_MEAN) {
+            const double gq = bad ? nan : (-1.0) / ((Bd * (double)K) * (double)Q);
+#pragma unroll
+            for (int k = 0; k < TD_K; k++) {
+                if (k < K) {
+                    IN* __restrict__ row = (IN*)a.g[k] + i * a.g_s[k];
+                    for (int j = 0; j < Q; j++) row[j] = (IN)gq;
+                }
+            }
+        }
+        if (a.g_lp) ((IN*)a.g_lp)[i] = (IN)(bad ? nan : alpha / Bd);
+        if (bad) {
+            a.err[5] = 1;
+            v[0] = nan; v[1] = nan; v[2] = nan; v[3] = nan; v[4] = nan;
+        } else {
+            v[0] = ent ? alpha * lp - m : -m;
+            v[1] = lp; v[2] = m; v[3] = lp + a.H_t;
+        }
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        if (ONE) al_finish(a, v, alpha);
+        else {
+            double* p = a.ws + (size_t)blockIdx.x * PL_PITCH;
+#pragma unroll
+            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
+        }
+    }
+}
+
+// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
+__global__ void __launch_bounds__(PL_BLOCK)
+k_al_final(AlArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) v[k] += a.ws[(size_t)b * PL_PITCH + k];
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        bool ok;
+        const double alpha = al_alpha(a, ok);
+        al_finish(a, v, alpha);
+    }
+}
+
 // ================================================================================================= host side
 // ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
 template <typename V>
@@ -1477,6 +1722,48 @@ void launch_ql(hipStream_t st, const QlArgs& a)
     }
     hipLaunchKernelGGL((k_ql_rows<IN, false>), grid, block, 0, st, a);
     hipLaunchKernelGGL(k_ql_final, dim3(1), block, 0, st, a);
+}
+
+// ptg_actor_loss's launches: the dtype of the Q-values and log-probs is the row kernel's template axis
+template <typename IN>
+void launch_al(hipStream_t st, const AlArgs& a)
+{
+    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
+    if (a.nblk == 1) {                                       // up to 256 rows: everything in one launch
+        hipLaunchKernelGGL((k_al_rows<IN, true>), grid, block, 0, st, a);
+        return;
+    }
+    hipLaunchKernelGGL((k_al_rows<IN, false>), grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_al_final, dim3(1), block, 0, st, a);
+}
+
+// what ptg_rsample and ptg_rsample_backward refuse alike; the text of the first fault, or null
+const char* rs_desc_error(const ptg_rs* d, bool backward)
+{
+    if (d->kind != PTG_RS_SQUASH && d->kind != PTG_RS_SMOOTH) return "unknown kind";
+    if (d->flags & ~PTG_RS_DETERMINISTIC) return "unknown flag";
+    if (d->q_dtype != PTG_OUT_F32 && d->q_dtype != PTG_OUT_F64) return "q_dtype must be PTG_OUT_F32 or PTG_OUT_F64";
+    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return "batch outside [1, 2^31]";
+    if (!d->mean_dev || d->mean_s_n < 1) return "null mean_dev or mean_s_n < 1";
+    if (d->kind == PTG_RS_SQUASH && (!d->log_std_dev || d->log_std_s_n < 1)) return "null log_std_dev or log_std_s_n < 1";
+    if (backward) {
+        if (d->kind != PTG_RS_SQUASH) return "PTG_RS_SMOOTH has no backward";
+        if (!d->noise_dev || (uintptr_t)d->noise_dev % sizeof(double) != 0) return "noise_dev is null or not aligned to 8 bytes";
+        if (!d->grad_act_dev && !d->grad_logp_dev) return "grad_act_dev and grad_logp_dev are both null";
+        if (!d->grad_mean_dev || !d->grad_log_std_dev) return "null grad_mean_dev or grad_log_std_dev";
+        if (d->gm_s_n < 1 || d->gl_s_n < 1) return "gm_s_n or gl_s_n < 1";
+        return nullptr;
+    }
+    if (!d->act_dev) return "null act_dev";
+    if (!(d->flags & PTG_RS_DETERMINISTIC) && !d->counter_dev) return "a stochastic call needs counter_dev";
+    if (d->noise_dev && (uintptr_t)d->noise_dev % sizeof(double) != 0) return "noise_dev is not aligned to 8 bytes";
+    if (d->kind == PTG_RS_SMOOTH) {
+        if (d->logp_dev) return "PTG_RS_SMOOTH has no log-prob";
+        if (!(d->noise_std >= 0.0) || !std::isfinite(d->noise_std)) return "noise_std is negative or not finite";
+        if (!(d->noise_clip >= 0.0)) return "noise_clip is negative or NaN";
+        if (!(d->clip_lo <= d->clip_hi)) return "clip_lo > clip_hi (or a NaN bound)";
+    }
+    return nullptr;
 }
 
 }  // namespace
@@ -2027,6 +2314,108 @@ int ptg_quantile_loss(ptg_env* h, const ptg_ql* d, void* stream)
     if (d->q_dtype == PTG_OUT_F64) launch_ql<double>(st, a);
     else launch_ql<float>(st, a);
     return launch_check(h, "k_ql_rows");
+}
+
+// ---- the training-time actor head: reparametrised squashed-Gaussian sample with its log-prob, its backward, TD3's smoothed target action ----
+static void rs_args(ptg_env* h, const ptg_rs* d, RsArgs& a)
+{
+    a.mean = d->mean_dev; a.m_s = (size_t)d->mean_s_n; a.ls = d->log_std_dev; a.ls_s = (size_t)d->log_std_s_n;
+    a.act = d->act_dev; a.logp = d->logp_dev; a.noise = d->noise_dev;
+    a.g_act = d->grad_act_dev; a.g_logp = d->grad_logp_dev;
+    a.g_mean = d->grad_mean_dev; a.gm_s = (size_t)d->gm_s_n; a.g_ls = d->grad_log_std_dev; a.gl_s = (size_t)d->gl_s_n;
+    a.counter = (d->flags & PTG_RS_DETERMINISTIC) ? nullptr : (const unsigned long long*)d->counter_dev; a.seed = (unsigned long long)d->seed;
+    a.sigma_t = d->noise_std; a.c = d->noise_clip; a.lo = d->clip_lo; a.hi = d->clip_hi;
+    a.B = (size_t)d->batch; a.kind = d->kind; a.err = h->P.err;
+}
+
+int ptg_rsample(ptg_env* h, const ptg_rs* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_rsample: null descriptor");
+    if (const char* why = rs_desc_error(d, false)) return set_err(h, PTG_E_INVALID, "ptg_rsample: %s", why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    RsArgs a{};
+    rs_args(h, d, a);
+    const dim3 grid((unsigned)((a.B + ACT_BLOCK - 1) / ACT_BLOCK)), block(ACT_BLOCK);
+    if (d->q_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_rs_fwd<double>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_rs_fwd<float>, grid, block, 0, st, a);
+    if (a.counter) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)d->counter_dev, 1ull);
+    return launch_check(h, "k_rs_fwd");
+}
+
+int ptg_rsample_backward(ptg_env* h, const ptg_rs* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_rsample_backward: null descriptor");
+    if (const char* why = rs_desc_error(d, true)) return set_err(h, PTG_E_INVALID, "ptg_rsample_backward: %s", why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    RsArgs a{};
+    rs_args(h, d, a);
+    const dim3 grid((unsigned)((a.B + ACT_BLOCK - 1) / ACT_BLOCK)), block(ACT_BLOCK);
+    if (d->q_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_rs_bwd<double>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_rs_bwd<float>, grid, block, 0, st, a);
+    return launch_check(h, "k_rs_bwd");
+}
+
+// ---- the actor and entropy-coefficient losses of SAC / TQC / TD3, the statistics and the gradients -----------------------------------
+int64_t ptg_actor_loss_workspace(int64_t batch)
+{
+    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;      // ptg_policy_loss's limit: 2^23 blocks of 256 threads
+    return ((batch - 1) / PL_BLOCK + 1) * PL_PITCH * (int64_t)sizeof(double);
+}
+
+int ptg_actor_loss(ptg_env* h, const ptg_al* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: null descriptor");
+    if (d->kind != PTG_AL_MIN && d->kind != PTG_AL_MEAN && d->kind != PTG_AL_ALPHA_ONLY) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: unknown kind %d", d->kind);
+    if (d->flags & ~(PTG_AL_ENTROPY | PTG_AL_LOG_ALPHA | PTG_AL_ENT_COEF)) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: unknown flag in %d", d->flags);
+    const bool only = d->kind == PTG_AL_ALPHA_ONLY, ent = (d->flags & PTG_AL_ENTROPY) != 0, log_alpha = (d->flags & PTG_AL_LOG_ALPHA) != 0,
+               ec = (d->flags & PTG_AL_ENT_COEF) != 0;
+    if (ptg_actor_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (d->q_dtype != PTG_OUT_F32 && d->q_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: q_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->stats_dev) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: null stats_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: ws_dev is null or not aligned to 8 bytes");
+    if (only && (ent || !ec)) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ALPHA_ONLY takes PTG_AL_ENT_COEF and no PTG_AL_ENTROPY");
+    if (ec && !log_alpha) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ENT_COEF needs PTG_AL_LOG_ALPHA");
+    if (log_alpha && !ent && !ec) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_LOG_ALPHA needs PTG_AL_ENTROPY or PTG_AL_ENT_COEF");
+    if (log_alpha && !d->alpha_dev) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_LOG_ALPHA needs alpha_dev");
+    if ((ent || ec) && !d->logp_dev) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ENTROPY and PTG_AL_ENT_COEF need logp_dev");
+    if (ec && !std::isfinite(d->target_entropy)) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ENT_COEF needs a finite target_entropy");
+    if (d->grad_logp_dev && !ent) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: grad_logp_dev goes with PTG_AL_ENTROPY");
+    if (d->grad_log_alpha_dev && (!ec || (uintptr_t)d->grad_log_alpha_dev % sizeof(double) != 0))
+        return set_err(h, PTG_E_INVALID, "ptg_actor_loss: grad_log_alpha_dev goes with PTG_AL_ENT_COEF and is aligned to 8 bytes");
+    int K = 0, Q = 1;
+    if (!only) {
+        if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
+        K = d->n_critics;
+        if (d->kind == PTG_AL_MEAN) {
+            if (d->n_quantiles < 1 || d->n_quantiles > PTG_QL_MAX_QUANTILES) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: n_quantiles outside [1, %d]", PTG_QL_MAX_QUANTILES);
+            Q = d->n_quantiles;
+        }
+        for (int k = 0; k < K; k++) {
+            if (!d->q_dev[k] || !d->grad_q_dev[k]) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: null q_dev or grad_q_dev [%d]", k);
+            if (d->q_s_n[k] < Q || d->g_s_n[k] < Q) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: q_s_n or g_s_n [%d] below %d", k, Q);
+        }
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    AlArgs a{};
+    for (int k = 0; k < K; k++) {
+        a.q[k] = d->q_dev[k]; a.q_s[k] = (size_t)d->q_s_n[k];
+        a.g[k] = d->grad_q_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    }
+    a.lp = (ent || ec) ? d->logp_dev : nullptr; a.alpha_dev = (ent || ec) ? d->alpha_dev : nullptr;
+    a.g_lp = d->grad_logp_dev; a.g_la = d->grad_log_alpha_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.alpha = d->alpha; a.H_t = ec ? d->target_entropy : 0.0;
+    a.B = (size_t)d->batch; a.K = K; a.Q = Q; a.kind = d->kind; a.flags = d->flags;
+    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.err = h->P.err;
+    if (d->q_dtype == PTG_OUT_F64) launch_al<double>(st, a);
+    else launch_al<float>(st, a);
+    return launch_check(h, "k_al_rows");
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 """ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd;
 dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise, and tqc_critic_loss: TQC's
-quantile-Huber critic loss (HipEngine.quantile_loss, ptg_quantile_loss) -- see the end of the file.
+quantile-Huber critic loss (HipEngine.quantile_loss, ptg_quantile_loss); squashed_rsample (HipEngine.rsample / rsample_backward,
+ptg_rsample) and sac_actor_loss / tqc_actor_loss / td3_actor_loss / ent_coef_loss (HipEngine.actor_loss, ptg_actor_loss): the actor
+half of an off-policy step -- see the end of the file.
 
     out = net(obs)                                            # [B, A + 1]: logits and a value column
     loss, stats = ppo_loss(engine, out[:, :A], out[:, A], actions, old_log_prob, advantages, returns, clip_range=0.2)
@@ -147,3 +149,99 @@ def tqc_critic_loss(engine, quantiles, next_quantiles, rewards, dones, next_log_
     nxt = [det(t) for t in next_quantiles] if isinstance(next_quantiles, (list, tuple)) else det(next_quantiles)
     return _QuantileLossFn.apply(engine, as_list, nxt, rewards, dones, det(next_log_prob), gamma, top_quantiles_to_drop_per_net, kw,
                                  *(quantiles if as_list else (quantiles,)))
+
+
+# ------------------------------------------------------------------------------------------------- the actor half of an off-policy step
+#     mean, log_std = actor(obs)                                            # [B, 1] each; log_std unclamped
+#     actions, log_prob = squashed_rsample(engine, mean, log_std, counter, seed=seed)
+#     a_loss, _ = ent_coef_loss(engine, log_prob, log_alpha, target_entropy=-1.0)     # SB3's order: before the critic update
+#     ...
+#     loss, stats = sac_actor_loss(engine, [c(obs, actions) for c in critics], log_prob, ent_coef=a_stats[4:5])
+#     loss.backward()                                                       # through the critics into actions and log_prob, then
+#                                                                           # through rsample_backward into the actor
+# squashed_rsample is the first op here whose backward is a kernel too: the reparametrised path through tanh(mean + sigma * z) IS
+# SAC's actor gradient.  The draw itself is data; the backward reads the noise the forward stored, not the counter.
+class _RSampleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, mean, log_std, counter, seed, deterministic, out):
+        res = engine.rsample(mean.detach(), log_std.detach(), counter, seed=seed, deterministic=deterministic, out=out)
+        if res.noise is None:
+            raise ValueError("squashed_rsample: out.noise is None, but the backward reads it")
+        ctx.engine, ctx.noise = engine, res.noise
+        ctx.save_for_backward(mean, log_std)
+        return res.actions, res.log_prob
+
+    @staticmethod
+    def backward(ctx, grad_actions, grad_log_prob):
+        mean, log_std = ctx.saved_tensors
+        ga = None if grad_actions is None else grad_actions.contiguous()
+        gl = None if grad_log_prob is None else grad_log_prob.contiguous()
+        g = ctx.engine.rsample_backward(mean.detach(), log_std.detach(), ctx.noise, ga, gl)
+        return None, g.grad_mean, g.grad_log_std, None, None, None, None
+
+
+def squashed_rsample(engine, mean, log_std, counter, *, seed=0, deterministic=False, out=None):
+    """SB3's Actor.action_log_prob (SAC / TQC) -> (actions, log_prob), shaped like mean and differentiable in mean and log_std: the
+    forward is HipEngine.rsample, the backward HipEngine.rsample_backward on the stored noise.  Under torch.no_grad() (the next
+    observations, for the critic target) nothing is kept.  Arguments as HipEngine.rsample."""
+    return _RSampleFn.apply(engine, mean, log_std, counter, seed, deterministic, out)
+
+
+class _ActorLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, kind, as_list, n_q, kw, *diff):
+        # diff: the tensors a gradient may go back to, per kind as below; everything else of the call travels in kw
+        d = [t.detach() for t in diff]
+        if kind == "ent_coef":                               # diff = (log_prob, log_ent_coef): the gradient goes to the latter alone
+            res = engine.actor_loss(kind, log_prob=d[0], log_ent_coef=d[1], **kw)
+            ctx.grads = [None, res.grad_log_ent_coef]
+        elif kind == "td3":                                  # diff = (q1,)
+            res = engine.actor_loss(kind, q=d[0], **kw)
+            ctx.grads = [res.grad_q]
+        else:                                                # diff = the critics' outputs (one tensor when stacked), then log_prob
+            res = engine.actor_loss(kind, q=d[:n_q] if as_list else d[0], log_prob=d[n_q], **kw)
+            ctx.grads = (list(res.grad_q) if as_list else [res.grad_q]) + [res.grad_log_prob]
+        ctx.shapes = [t.shape for t in diff]
+        ctx.mark_non_differentiable(res.stats)
+        if kind == "ent_coef":
+            return res.stats[1].clone(), res.stats
+        return res.stats[0].to(diff[0].dtype, copy=True), res.stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        return (None,) * 5 + tuple(None if g is None else (g * grad_loss).reshape(s) for g, s in zip(ctx.grads, ctx.shapes))
+
+
+def _det(t):
+    return t.detach() if torch.is_tensor(t) else t
+
+
+def sac_actor_loss(engine, q, log_prob, *, ent_coef=None, log_ent_coef=None, out=None, workspace=None):
+    """SB3's SAC.train actor loss -> (loss, stats): (alpha * log_prob - min_k q[k]).mean().  q: the list of the K critics' outputs [B] /
+    [B, 1] on (obs, actions_pi); q and log_prob carry the graph, alpha is data: ent_coef (a float, or a float64 device tensor of 1
+    element) or exp(log_ent_coef), as SB3 detaches it.  stats as HipEngine.actor_loss gives them."""
+    kw = dict(ent_coef=_det(ent_coef), log_ent_coef=_det(log_ent_coef), out=out, workspace=workspace)
+    return _ActorLossFn.apply(engine, "sac", True, len(q), kw, *q, log_prob)
+
+
+def tqc_actor_loss(engine, quantiles, log_prob, *, ent_coef=None, log_ent_coef=None, out=None, workspace=None):
+    """sb3_contrib's TQC.train actor loss -> (loss, stats): (alpha * log_prob - quantiles.mean(2).mean(1)).mean().  quantiles: the
+    critics' output on (obs, actions_pi), a [B, K, Q] tensor or a list of K [B, Q] tensors, carrying the graph."""
+    as_list = isinstance(quantiles, (list, tuple))
+    kw = dict(ent_coef=_det(ent_coef), log_ent_coef=_det(log_ent_coef), out=out, workspace=workspace)
+    qs = tuple(quantiles) if as_list else (quantiles,)
+    return _ActorLossFn.apply(engine, "tqc", as_list, len(qs), kw, *qs, log_prob)
+
+
+def td3_actor_loss(engine, q1, *, out=None, workspace=None):
+    """SB3's TD3.train actor loss -> (loss, stats): -critic.q1_forward(obs, actor(obs)).mean().  q1 [B] / [B, 1] carries the graph."""
+    return _ActorLossFn.apply(engine, "td3", False, 1, dict(out=out, workspace=workspace), q1)
+
+
+def ent_coef_loss(engine, log_prob, log_ent_coef, *, target_entropy, out=None, workspace=None):
+    """SB3's entropy-coefficient loss -> (loss, stats): -(log_ent_coef * (log_prob + target_entropy).detach()).mean(), a 0-dim float64
+    tensor differentiable in log_ent_coef (a float64 device tensor of 1 element) alone.  stats[4:5] is the alpha = exp(log_ent_coef)
+    of this call on the device: hand it as ent_coef= to the critic loss and to the later actor loss, as SB3 uses the alpha from before
+    the alpha optimiser's step for both."""
+    kw = dict(target_entropy=target_entropy, out=out, workspace=workspace)
+    return _ActorLossFn.apply(engine, "ent_coef", False, 0, kw, log_prob.detach(), log_ent_coef)

@@ -1,5 +1,5 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss, the TD losses, TQC's quantile loss and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+action heads, the policy loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
@@ -28,6 +28,12 @@ TdLoss = collections.namedtuple("TdLoss", "stats grad_q target")
 # what quantile_loss returns: stats float64 [8], the gradients w.r.t. the current quantiles (a [B, K, Q] tensor or a list of K [B, Q]
 # tensors, as the quantiles came) and the targets [B, M] (None when not asked for)
 QuantileLoss = collections.namedtuple("QuantileLoss", "stats grad_quantiles target")
+# what rsample returns: actions and log_prob shaped like mean, noise float64 (the z of every row); rsample_backward: the two gradients
+RSample = collections.namedtuple("RSample", "actions log_prob noise")
+RSampleGrad = collections.namedtuple("RSampleGrad", "grad_mean grad_log_std")
+# what actor_loss returns: stats float64 [8], the gradients w.r.t. q (as q came; None for kind "ent_coef"), w.r.t. log_prob (None for
+# "td3" / "ent_coef") and w.r.t. log alpha (float64 [1]; None without target_entropy)
+ActorLoss = collections.namedtuple("ActorLoss", "stats grad_q grad_log_prob grad_log_ent_coef")
 
 
 class OptimPlan:
@@ -831,6 +837,253 @@ class TrainOps:
         with torch.cuda.device(self.device):
             self._chk(self._L.ptg_quantile_loss(self._h, C.byref(d), self._stream()))
         return QuantileLoss(stats, g_q, target)
+
+    # ------------------------------------------------------------------ the training-time actor head: SAC / TQC rsample, TD3's target action
+    def _rs_rows(self, who, mean, log_std):
+        """mean and log_std [B] / [B, 1] of one float dtype, any stride >= 1 -> their [B] views and B"""
+        torch = self._torch
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
+        m = check(self, who, "mean", column(mean), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
+        B = m.shape[0]
+        ls = check(self, who, "log_std", column(log_std), dtypes=(m.dtype,), shape=(B,), rule=step) if log_std is not None else None
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch, mean has shape {tuple(mean.shape)}")
+        return m, ls, B
+
+    def rsample(self, mean, log_std, counter, seed=0, deterministic=False, out=None):
+        """Enqueue, on the current stream, SB3's Actor.action_log_prob of SAC / TQC on a replay batch (include/ptg_env.h: ptg_rsample,
+        which states the arithmetic): log_std clamped to [-20, 2], a = tanh(mean + exp(log_std) * z) with z the c-th Box-Muller draw of
+        row b under (seed, c, b), c = the counter's value on the device (deterministic: z = 0), and log pi(a) with SB3's tanh correction.
+        mean, log_std: [B] or [B, 1] of one float dtype (float32 / float64), any stride >= 1 -- B is not tied to n_envs; log_std is the
+        network's unclamped output.  counter: new_draw_counter(); a stochastic call advances it by one on the device.
+        Returns RSample(actions, log_prob in the inputs' dtype and shaped like mean, noise float64: z, which rsample_backward reads).
+        out: an earlier result, reused by a captured call; its log_prob and noise may be None (not written).  No synchronisation; a
+        non-finite mean or a NaN log_std gives NaN outputs and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "rsample"
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t
+        m, ls, B = self._rs_rows(who, mean, log_std)
+        if ls is None:
+            raise TypeError(f"{who}: log_std must be a tensor, got NoneType")
+        counter = self._act_counter(who, counter, deterministic)
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 3:
+                raise ValueError(f"{who}: out must be the RSample of an earlier call")
+            act, lp, noise = out
+            check(self, who, "out.actions", column(act), dtypes=(m.dtype,), shape=(B,), rule=contiguous, exc=ValueError)
+            check(self, who, "out.log_prob", column(lp), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "out.noise", column(noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+        else:
+            with torch.cuda.device(self.device):
+                act, lp = (torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device) for _ in range(2))
+                noise = torch.empty(tuple(mean.shape), dtype=torch.float64, device=self.device)
+        d = _lib.PtgRs(kind=_lib.RS_SQUASH, flags=_lib.RS_DETERMINISTIC if deterministic else 0, q_dtype=_out_code(torch, m.dtype), batch=B,
+                       mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1), log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1),
+                       seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), act_dev=_ptr(act), logp_dev=_ptr(lp), noise_dev=_ptr(noise))
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_rsample(self._h, C.byref(d), self._stream()))
+        return RSample(act, lp, noise)
+
+    def rsample_backward(self, mean, log_std, noise, grad_actions, grad_log_prob, out=None):
+        """Enqueue, on the current stream, the backward of rsample (include/ptg_env.h: ptg_rsample_backward): from the same mean and log_std,
+        the noise rsample stored, and the incoming gradients d L / d actions and d L / d log_prob ([B] or [B, 1], contiguous, in the inputs'
+        dtype; either may be None = 0, not both), the gradients with respect to mean and to the unclamped log_std (0 outside the clamp).
+        Returns RSampleGrad(grad_mean, grad_log_std), shaped like mean and log_std; out: such a pair, any stride >= 1.  No synchronisation;
+        a non-finite input row gives NaN gradients and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "rsample_backward"
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t
+        m, ls, B = self._rs_rows(who, mean, log_std)
+        if ls is None:
+            raise TypeError(f"{who}: log_std must be a tensor, got NoneType")
+        dt = (m.dtype,)
+        noise = check(self, who, "noise", column(noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous)
+        ga = check(self, who, "grad_actions", column(grad_actions), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        gl = check(self, who, "grad_log_prob", column(grad_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        if ga is None and gl is None:
+            raise ValueError(f"{who}: grad_actions and grad_log_prob are both None")
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 2:
+                raise ValueError(f"{who}: out must be the RSampleGrad of an earlier call")
+            gm, gs = out
+            gm1 = check(self, who, "out.grad_mean", column(gm), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            gs1 = check(self, who, "out.grad_log_std", column(gs), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+        else:
+            with torch.cuda.device(self.device):
+                gm = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
+                gs = torch.empty(tuple(log_std.shape), dtype=m.dtype, device=self.device)
+            gm1, gs1 = column(gm), column(gs)
+        d = _lib.PtgRs(kind=_lib.RS_SQUASH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
+                       log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1), noise_dev=_ptr(noise), grad_act_dev=_ptr(ga), grad_logp_dev=_ptr(gl),
+                       grad_mean_dev=_ptr(gm1), gm_s_n=max(gm1.stride(0), 1), grad_log_std_dev=_ptr(gs1), gl_s_n=max(gs1.stride(0), 1))
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_rsample_backward(self._h, C.byref(d), self._stream()))
+        return RSampleGrad(gm, gs)
+
+    def smooth_target_action(self, mean, counter, noise_std, noise_clip, clip=(-1.0, 1.0), seed=0, out=None):
+        """Enqueue, on the current stream, TD3.train's target-policy smoothing (include/ptg_env.h: ptg_rsample, PTG_RS_SMOOTH):
+        clip(mean + clip(noise_std * z, -noise_clip, noise_clip), clip[0], clip[1]) with rsample's draw.  mean = actor_target(next_obs),
+        [B] or [B, 1], float32 / float64, any stride >= 1.  Returns the actions, shaped like mean (out: such a tensor, contiguous).
+        The counter advances by one on the device.  No synchronisation; a non-finite mean gives NaN and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "smooth_target_action"
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t
+        m, _, B = self._rs_rows(who, mean, None)
+        counter = self._act_counter(who, counter, False)
+        sd, c, lo, hi = float(noise_std), float(noise_clip), float(clip[0]), float(clip[1])
+        if not (0.0 <= sd < float("inf")) or not c >= 0.0:
+            raise ValueError(f"{who}: noise_std must be finite and >= 0 and noise_clip >= 0, got {noise_std} and {noise_clip}")
+        if not lo <= hi:
+            raise ValueError(f"{who}: clip {clip} is not an interval")
+        check(self, who, "out", column(out), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
+        d = _lib.PtgRs(kind=_lib.RS_SMOOTH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
+                       seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), noise_std=sd, noise_clip=c, clip_lo=lo, clip_hi=hi, act_dev=_ptr(out))
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_rsample(self._h, C.byref(d), self._stream()))
+        return out
+
+    # ------------------------------------------------------------------ the actor and entropy-coefficient losses and their gradients
+    def actor_loss_workspace(self, batch):
+        """the device scratch of actor_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
+        nbytes = self._L.ptg_actor_loss_workspace(int(batch))
+        if nbytes < 0:
+            raise ValueError(f"actor_loss_workspace: batch must be in [1, 2^31], got {batch}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def actor_loss(self, kind, q=None, log_prob=None, ent_coef=None, log_ent_coef=None, target_entropy=None, out=None, workspace=None):
+        """Enqueue, on the current stream, the actor loss of SB3's SAC.train (kind "sac"), sb3_contrib's TQC.train ("tqc") or TD3.train
+        ("td3"), and / or the entropy-coefficient loss ("ent_coef": that one alone), with their gradients (include/ptg_env.h:
+        ptg_actor_loss, which states the arithmetic).
+        "sac": q a list of K critic outputs on (obs, a_pi), [B] or [B, 1] each with any stride >= 1 (1 <= K <= 4).  "tqc": q a [B, K, Q]
+        tensor or a list of K [B, Q] tensors as quantile_loss takes them.  "td3": q the first critic's output [B] / [B, 1]; no log_prob,
+        no coefficient.  "sac" / "tqc" take log_prob [B] / [B, 1] contiguous in q's dtype and exactly one of ent_coef (a Python float, or
+        a float64 device tensor of 1 element read when the kernel runs -- e.g. stats[4:5] of an earlier "ent_coef" call) and
+        log_ent_coef (a float64 device tensor of 1 element).  target_entropy (a finite float; needs log_ent_coef): also emit the
+        entropy-coefficient loss.  "ent_coef": log_prob, log_ent_coef and target_entropy, no q.
+        Returns ActorLoss(stats float64 [8] = actor_loss, ent_coef_loss, mean log_prob, mean m, alpha as used, d ent_coef_loss / d
+        log alpha, 0, 0; grad_q as q came (None for "ent_coef"); grad_log_prob shaped like log_prob (None for "td3" / "ent_coef");
+        grad_log_ent_coef float64 [1] (None without target_entropy)).  out: an earlier result, reused by a captured call (its
+        grad_log_prob and grad_log_ent_coef may be None: not written); workspace: actor_loss_workspace(B) or larger.  No synchronisation;
+        a non-finite row makes the next sync() raise PtgError (PTG_E_NONFINITE)."""
+        torch = self._torch
+        who = "actor_loss"
+        if kind not in ("sac", "tqc", "td3", "ent_coef"):
+            raise ValueError(f"{who}: kind must be 'sac', 'tqc', 'td3' or 'ent_coef', got {kind!r}")
+        floats = (torch.float32, torch.float64)
+        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
+        only, td3 = kind == "ent_coef", kind == "td3"
+        as_list = isinstance(q, (list, tuple))
+        K, Q, dt, B, qs = 0, 1, floats, None, []
+        if only:
+            if q is not None:
+                raise ValueError(f"{who}: kind 'ent_coef' reads no q")
+        elif kind == "tqc":
+            qs = self._quantile_views(who, "q", q, floats)
+            (B, Q), K, dt = qs[0].shape, len(qs), (qs[0].dtype,)
+            if not 1 <= Q <= _lib.QL_MAX_QUANTILES:
+                raise ValueError(f"{who}: q needs 1 <= Q <= {_lib.QL_MAX_QUANTILES}, got Q = {Q}")
+        else:
+            if td3 and not as_list:
+                q_list = [q]
+            elif not as_list:
+                raise TypeError(f"{who}: q must be a list of critic outputs for kind {kind!r}, got {type(q).__name__}")
+            else:
+                q_list = list(q)
+            if not 1 <= len(q_list) <= (1 if td3 else _lib.TD_MAX_CRITICS):
+                raise ValueError(f"{who}: q must hold {'one critic' if td3 else f'1 to {_lib.TD_MAX_CRITICS} critics'}, got {len(q_list)}")
+            for k, t in enumerate(q_list):
+                qs.append(check(self, who, f"q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step))
+                if k == 0:
+                    dt, (B,) = (qs[0].dtype,), qs[0].shape
+            K = len(qs)
+        if td3 and not (log_prob is None and ent_coef is None and log_ent_coef is None and target_entropy is None):
+            raise ValueError(f"{who}: kind 'td3' takes q alone")
+        if not td3 and log_prob is None:
+            raise ValueError(f"{who}: kind {kind!r} needs log_prob")
+        lp = check(self, who, "log_prob", column(log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        if only:
+            B, dt = lp.shape[0], (lp.dtype,)
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch")
+        if not td3 and (ent_coef is not None) + (log_ent_coef is not None) != 1:
+            raise ValueError(f"{who}: kind {kind!r} takes exactly one of ent_coef and log_ent_coef")
+        if (only or target_entropy is not None) and log_ent_coef is None:
+            raise ValueError(f"{who}: the entropy-coefficient loss needs log_ent_coef")
+        if only and target_entropy is None:
+            raise ValueError(f"{who}: kind 'ent_coef' needs target_entropy")
+        if target_entropy is not None and not np.isfinite(float(target_entropy)):
+            raise ValueError(f"{who}: target_entropy must be finite, got {target_entropy}")
+        ec = target_entropy is not None
+        alpha_dev = None
+        if log_ent_coef is not None or torch.is_tensor(ent_coef):
+            alpha_dev = check(self, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
+                              dtypes=(torch.float64,), numel=1)
+        alpha = float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+        g_q = gs = g_lp = g_la = None
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 4:
+                raise ValueError(f"{who}: out must be the ActorLoss of an earlier call")
+            stats, g_q, g_lp, g_la = out
+            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            if only:
+                if g_q is not None:
+                    raise ValueError(f"{who}: out.grad_q given, but kind 'ent_coef' reads no q")
+                gs = []
+            elif kind == "tqc":
+                if isinstance(g_q, (list, tuple)) != as_list:
+                    raise ValueError(f"{who}: out.grad_q must be a {'list of ' + str(K) + ' tensors' if as_list else 'tensor'}, as q is")
+                gs = self._quantile_views(who, "out.grad_q", g_q, dt, B, K, Q, exc=ValueError)
+            else:
+                g_list = [g_q] if td3 and not as_list else g_q
+                if not isinstance(g_list, (list, tuple)) or len(g_list) != K:
+                    raise ValueError(f"{who}: out.grad_q must be {'a tensor' if td3 and not as_list else f'a list of {K} tensors'}")
+                gs = [check(self, who, f"out.grad_q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step, exc=ValueError) for k, t in enumerate(g_list)]
+            if g_lp is not None and (td3 or only):
+                raise ValueError(f"{who}: out.grad_log_prob given, but kind {kind!r} has no entropy term")
+            if g_la is not None and not ec:
+                raise ValueError(f"{who}: out.grad_log_ent_coef given without target_entropy")
+            check(self, who, "out.grad_log_prob", column(g_lp), dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "out.grad_log_ent_coef", g_la, dtypes=(torch.float64,), shape=(1,), optional=True, exc=ValueError)
+            starts = [t.data_ptr() for t in list(gs) + qs + [x for x in (lp, g_lp) if x is not None]]
+            if len(set(starts)) != len(starts):             # the cheap half of "outputs must not overlap": one tensor given twice
+                raise ValueError(f"{who}: two of out.grad_q, out.grad_log_prob, q and log_prob start at the same address; the outputs must not overlap each "
+                                 "other or the inputs")
+        if workspace is not None:
+            check(self, who, f"workspace (actor_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
+            if workspace.numel() < self._L.ptg_actor_loss_workspace(B):
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_actor_loss_workspace(B)}")
+        else:
+            workspace = self.actor_loss_workspace(B)
+        if out is None:
+            with torch.cuda.device(self.device):
+                mk = lambda shape, d=dt[0]: torch.empty(tuple(shape), dtype=d, device=self.device)
+                stats = mk((8,), torch.float64)
+                if kind == "tqc":
+                    if as_list:
+                        g_q = gs = [mk((B, Q)) for _ in range(K)]
+                    else:
+                        g_q = mk((B, K, Q))
+                        gs = [g_q[:, k] for k in range(K)]
+                elif not only:
+                    g_list = [mk(t.shape) for t in (q if as_list else [q])]
+                    gs, g_q = [column(t) for t in g_list], (g_list if as_list else g_list[0])
+                g_lp = mk(log_prob.shape) if not (td3 or only) else None
+                g_la = mk((1,), torch.float64) if ec else None
+        flags = (0 if td3 or only else _lib.AL_ENTROPY) | (_lib.AL_LOG_ALPHA if log_ent_coef is not None else 0) | (_lib.AL_ENT_COEF if ec else 0)
+        d = _lib.PtgAl(kind=_lib.AL_ALPHA_ONLY if only else (_lib.AL_MIN if kind == "sac" else _lib.AL_MEAN), flags=flags, n_critics=K, n_quantiles=Q,
+                       q_dtype=_out_code(torch, dt[0]), batch=B, logp_dev=_ptr(lp), alpha_dev=_ptr(alpha_dev), alpha=alpha,
+                       target_entropy=float(target_entropy) if ec else 0.0, stats_dev=_ptr(stats), grad_logp_dev=_ptr(column(g_lp) if g_lp is not None else None),
+                       grad_log_alpha_dev=_ptr(g_la), ws_dev=_ptr(workspace))
+        for k in range(K):
+            d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), Q)
+            d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), Q)
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_actor_loss(self._h, C.byref(d), self._stream()))
+        return ActorLoss(stats, g_q, g_lp, g_la)
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):
