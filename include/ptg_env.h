@@ -45,7 +45,8 @@ extern "C" {
                              *     quantile-Huber critic loss with its gradients); + ptg_rs, ptg_rsample, ptg_rsample_backward (the training-time
                              *     actor head of SAC / TQC forward and backward, TD3's smoothed target action); + ptg_al, ptg_actor_loss,
                              *     ptg_actor_loss_workspace (the SAC / TQC / TD3 actor loss and the entropy-coefficient loss with their
-                             *     gradients); no earlier declaration changed */
+                             *     gradients); + ptg_mlp, ptg_mlp_forward, ptg_mlp_workspace (the inference forward of the policy and target MLPs,
+                             *     one fused f32 MFMA launch per layer); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -1125,6 +1126,77 @@ typedef struct ptg_al {
 } ptg_al;
 int64_t ptg_actor_loss_workspace(int64_t batch);
 int ptg_actor_loss(ptg_env* env, const ptg_al* d, void* stream);
+
+/* ---- the inference forward of an MLP: one fused launch per layer, Linear + bias + activation on the f32 matrix cores -------------------
+ * Replaces th.no_grad() calls of the nets that SB3's create_mlp builds for the reference (config/config_agent.yaml: 2 - 7 hidden layers
+ * of 233 - 808 units, ReLU or Tanh): the policy while collecting and evaluating, the target actor / critics / q_net of a gradient step.
+ * The backward pass, and with it the training forward under autograd, stays torch's.
+ * The call is described by a ptg_mlp, read during the call and holding no host memory (B = batch, n = n_layers):
+ *   batch         B, 1 <= B <= 2^31
+ *   n_layers      n, 1 <= n <= PTG_MLP_MAX_LAYERS (the reference's deepest net is DQN's: 7 hidden layers and the output layer)
+ *   flags         PTG_MLP_KEEP_HIDDEN: every post-activation hidden layer stays in ws_dev (below).  PTG_MLP_NARROW / PTG_MLP_WIDE, for
+ *                 tests and measurements: every layer takes that tile route instead of the host's choice; both at once are refused
+ *   hidden_act    PTG_MLP_RELU | PTG_MLP_TANH, applied after every layer but the last
+ *   out_act       PTG_MLP_NONE | PTG_MLP_RELU | PTG_MLP_TANH, applied after the last (TD3's actor ends in tanh; a trunk called on its own
+ *                 ends in its hidden activation)
+ *   x_dev, x2_dev the input as one or two pieces [B][f1] and [B][f2], float32, element (b, k) at b * x_s_n + k (b * x2_s_n + k), row
+ *                 strides >= f1 (f2): a critic's th.cat([obs, action], 1) without the cat.  x2_dev NULL: one piece, f2 must be 0.
+ *                 f1 + f2 is the first layer's fan-in, 1 <= f1, 0 <= f2, f1 + f2 <= PTG_MLP_MAX_WIDTH
+ *   w_dev[l]      float32 [width[l]][in_l] in torch's Linear.weight layout, element (j, k) at j * w_s_n[l] + k, w_s_n[l] >= in_l, where
+ *                 in_0 = f1 + f2 and in_l = width[l - 1];  b_dev[l] float32 [width[l]] contiguous;  1 <= width[l] <= PTG_MLP_MAX_WIDTH
+ *   out_dev       float32 [B][O], O = width[n - 1], element (b, j) at b * out_s_n + j, out_s_n >= O, 4-byte aligned
+ *   ws_dev        caller-owned device scratch, 4-byte aligned, ws_bytes >= ptg_mlp_workspace(batch, n_layers, width, flags).  The
+ *                 activations travel through it between the launches.  With P(w) = w rounded up to a multiple of 4 (rows 16 bytes
+ *                 apart or a multiple of that, counted from ws_dev): without PTG_MLP_KEEP_HIDDEN two alternating buffers of
+ *                 B * P(widest hidden layer) floats, hidden layer l in buffer l & 1 at byte offset (l & 1) * 4 * B * P(widest); with
+ *                 it hidden layer l (l = 0 .. n - 2, post-activation) is [B][width[l]] float32 with row stride P(width[l]) at byte
+ *                 offset 4 * B * (P(width[0]) + ... + P(width[l - 1])) -- the tensors a backward pass would read.  16 bytes for n = 1
+ * Arithmetic, which is the definition (tests/mlp_restatement.py restates it).  Row b, unit j of a layer with fan-in K, input x, in float32:
+ *   acc = bias[j]
+ *   for k = 0 .. K - 1 in ascending order:  acc = fmaf(x[b][k], W[j][k], acc)        one rounding per step, subnormals kept
+ *   y[b][j] = act(acc):  NONE acc;  RELU acc > 0 ? acc : (acc != acc ? acc : 0) (a NaN stays a NaN, -0 gives +0);  TANH the
+ *             double-precision library tanh of the float32 acc, rounded once to float32
+ * v_mfma_f32_16x16x4_f32 (four ascending k per instruction) and v_mfma_f32_32x32x2_f32 (two) both realise this chain with the bias as
+ * the initial accumulator, so an element's bits do not depend on B, on the row's place in the batch, on the tile route or on the grid;
+ * there is no split-K and no atomic.  Padding is exact: in a padded k position both operands are 0 and fmaf(0, 0, acc) = acc, with one
+ * exception, fmaf(0, 0, -0) = +0: a result of -0 may come out as +0 (compare with +0 == -0).  The lanes of padded rows, padded units
+ * and padded k get 0 (such a lane re-reads an element inside the tensor and discards it: nothing outside a tensor is read) and are never stored.
+ * Non-finite values propagate as IEEE 754 dictates, inside their own row only; the op has no error word of its own (ptg_act, which
+ * consumes the logits, reports such a row).  float64 networks are out of scope.
+ * Enqueues n kernels, k_mlp_layer, with no host synchronisation and no allocation, so the call may be captured into a hipGraph and
+ * replayed; the weights are read when the kernels run, so a replay sees an optimiser step or a Polyak update made in place.  Reads
+ * nothing of the handle but its device: env state, the finished-episode ring, the ptg_vn_* statistics and every replay cursor are
+ * untouched.  Overlap between any two of the buffers is NOT checked; out_dev and ws_dev must not overlap anything the call reads.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, x_dev, w_dev[l] or b_dev[l] (l < n), out_dev or ws_dev; batch outside
+ * [1, 2^31]; n_layers outside [1, PTG_MLP_MAX_LAYERS]; f1 < 1, f2 < 0, f1 + f2 or a width outside [1, PTG_MLP_MAX_WIDTH]; x2_dev with
+ * f2 = 0 or f2 > 0 without it; a row stride below its width; an unknown activation code (NONE as hidden_act too); an unknown flag or both
+ * route flags; ws_bytes below what ptg_mlp_workspace returns; an out_dev or ws_dev that is not 4-byte aligned.
+ * ptg_mlp_workspace(batch, n_layers, widths, flags): bytes of scratch such a call needs, widths = the n_layers layer widths; negative for
+ * a NULL widths or a count, width or flag the call would refuse. */
+#define PTG_MLP_MAX_LAYERS 10
+#define PTG_MLP_MAX_WIDTH 1024
+enum { PTG_MLP_RELU = 0, PTG_MLP_TANH = 1, PTG_MLP_NONE = 2 };
+enum { PTG_MLP_KEEP_HIDDEN = 1, PTG_MLP_NARROW = 2, PTG_MLP_WIDE = 4 };
+typedef struct ptg_mlp {
+    int64_t batch;
+    int32_t n_layers, flags;
+    int32_t hidden_act, out_act;
+    int32_t f1, f2;
+    const float* x_dev;
+    int64_t x_s_n;
+    const float* x2_dev;
+    int64_t x2_s_n;
+    const float* w_dev[PTG_MLP_MAX_LAYERS];
+    int64_t w_s_n[PTG_MLP_MAX_LAYERS];
+    const float* b_dev[PTG_MLP_MAX_LAYERS];
+    int32_t width[PTG_MLP_MAX_LAYERS];
+    float* out_dev;
+    int64_t out_s_n;
+    void* ws_dev;
+    int64_t ws_bytes;
+} ptg_mlp;
+int64_t ptg_mlp_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags);
+int ptg_mlp_forward(ptg_env* env, const ptg_mlp* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -9,6 +9,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "ptg_env.hip")                # the environment: N_PARTS translation units of the parallel build
 SRC_TRAIN = os.path.join(CSRC, "ptg_train.hip")        # the training ops: one translation unit
+SRC_MLP = os.path.join(CSRC, "ptg_mlp.hip")            # the MLP forward: one translation unit
 HDR = os.path.join(ROOT, "include", "ptg_env.h")
 LIB_PATH = os.environ.get("PTG_LIB_PATH") or os.path.join(PKG, "lib", "libptg_env.so")      # PTG_LIB_PATH: an experiment build of the same source
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
@@ -35,6 +36,9 @@ RS_SQUASH, RS_SMOOTH = 0, 1
 RS_DETERMINISTIC = 1
 AL_MIN, AL_MEAN, AL_ALPHA_ONLY = 0, 1, 2
 AL_ENTROPY, AL_LOG_ALPHA, AL_ENT_COEF = 1, 2, 4
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 10, 1024
+MLP_RELU, MLP_TANH, MLP_NONE = 0, 1, 2
+MLP_KEEP_HIDDEN, MLP_NARROW, MLP_WIDE = 1, 2, 4
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -145,6 +149,13 @@ class PtgAl(C.Structure):                                   # ptg_al: one call o
                 ("grad_logp_dev", C.c_void_p), ("grad_log_alpha_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
 
 
+class PtgMlp(C.Structure):                                  # ptg_mlp: one call of the MLP forward
+    _fields_ = [("batch", C.c_int64), ("n_layers", C.c_int32), ("flags", C.c_int32), ("hidden_act", C.c_int32), ("out_act", C.c_int32),
+                ("f1", C.c_int32), ("f2", C.c_int32), ("x_dev", C.c_void_p), ("x_s_n", C.c_int64), ("x2_dev", C.c_void_p), ("x2_s_n", C.c_int64),
+                ("w_dev", C.c_void_p * MLP_MAX_LAYERS), ("w_s_n", C.c_int64 * MLP_MAX_LAYERS), ("b_dev", C.c_void_p * MLP_MAX_LAYERS),
+                ("width", C.c_int32 * MLP_MAX_LAYERS), ("out_dev", C.c_void_p), ("out_s_n", C.c_int64), ("ws_dev", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -155,7 +166,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
-           "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss",
+           "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -166,20 +177,21 @@ def build(force=False, verbose=False):
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest:
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    jobs = int(os.environ.get("PTG_BUILD_JOBS", "0")) or min(N_PARTS + 1, os.cpu_count() or 1)
-    if jobs <= 1:                                             # both files whole (no PTG_PART) in one hipcc call
-        cmd = [hipcc] + HIPCC_FLAGS + ["-shared", "-o", LIB_PATH, SRC, SRC_TRAIN]
+    jobs = int(os.environ.get("PTG_BUILD_JOBS", "0")) or min(N_PARTS + 2, os.cpu_count() or 1)
+    if jobs <= 1:                                             # the three files whole (no PTG_PART) in one hipcc call
+        cmd = [hipcc] + HIPCC_FLAGS + ["-shared", "-o", LIB_PATH, SRC, SRC_TRAIN, SRC_MLP]
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
         return LIB_PATH
-    # ptg_env.hip compiled N_PARTS times, each time with a different share of the hot-kernel instantiations, and ptg_train.hip once,
-    # `jobs` at a time
+    # ptg_env.hip compiled N_PARTS times, each time with a different share of the hot-kernel instantiations, ptg_train.hip and
+    # ptg_mlp.hip once each, `jobs` at a time
     obj_dir = os.path.join(os.path.dirname(LIB_PATH), "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    objs = [os.path.join(obj_dir, f"ptg_env_part{k}.o") for k in range(N_PARTS)] + [os.path.join(obj_dir, "ptg_train.o")]
+    objs = [os.path.join(obj_dir, f"ptg_env_part{k}.o") for k in range(N_PARTS)] + [os.path.join(obj_dir, "ptg_train.o"), os.path.join(obj_dir, "ptg_mlp.o")]
     cmds = [[hipcc] + HIPCC_FLAGS + ["-Wno-unused-function", f"-DPTG_PART={k}", "-c", "-o", objs[k], SRC] for k in range(N_PARTS)]
     cmds.append([hipcc] + HIPCC_FLAGS + ["-c", "-o", objs[N_PARTS], SRC_TRAIN])
+    cmds.append([hipcc] + HIPCC_FLAGS + ["-c", "-o", objs[N_PARTS + 1], SRC_MLP])
     running, todo, failed = [], list(enumerate(cmds)), []
     while todo or running:
         while todo and len(running) < jobs:
@@ -191,7 +203,7 @@ def build(force=False, verbose=False):
         if proc.wait() != 0:
             failed.append(k)
     if failed:
-        raise RuntimeError(f"hipcc failed on {[os.path.basename(objs[k]) for k in failed]} ({SRC}, {SRC_TRAIN})")
+        raise RuntimeError(f"hipcc failed on {[os.path.basename(objs[k]) for k in failed]} ({SRC}, {SRC_TRAIN}, {SRC_MLP})")
     link = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB_PATH] + objs
     if verbose:
         print(" ".join(link))
@@ -290,6 +302,9 @@ def lib():
     L.ptg_actor_loss_workspace.argtypes = [C.c_int64]
     L.ptg_actor_loss_workspace.restype = C.c_int64
     L.ptg_actor_loss.argtypes = [vp, C.POINTER(PtgAl), vp]
+    L.ptg_mlp_workspace.argtypes = [C.c_int64, C.c_int32, i32p, C.c_int32]
+    L.ptg_mlp_workspace.restype = C.c_int64
+    L.ptg_mlp_forward.argtypes = [vp, C.POINTER(PtgMlp), vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

@@ -1,0 +1,108 @@
+"""DeviceMLP: the inference forward of a torch MLP as one fused launch per layer (HipEngine.mlp_forward, include/ptg_env.h:
+ptg_mlp_forward, which states the arithmetic).
+
+    policy = DeviceMLP(engine, q_net, batch=engine.n)                 # an nn.Sequential of Linear / ReLU / Tanh, as SB3's create_mlp returns
+    logits = policy(obs)                                              # no autograd graph, no allocation, no synchronisation
+    mean = DeviceMLP(engine, [latent_pi, mu], batch=256)              # a list chains: the trunk, then a head
+    q_next = DeviceMLP(engine, target_qf, batch=256)(next_obs, x2=next_actions)      # th.cat([obs, action], 1) without the cat
+
+The parameters are held BY REFERENCE, never copied: what DeviceOptimizer.step() and polyak_update write in place is what the next call,
+and the next replay of a captured call, reads.  Output and workspace are allocated once, for `batch` rows; a call with fewer rows
+returns the first rows of the output tensor, and every call overwrites it.
+
+Not supported: obs_layout="split" rows (policy_split.FirstLayerSplit) as input -- feed row-major observations; float64 nets; a Linear
+without bias; anything but Linear / ReLU / Tanh in the sequence.  There is no torch fall-back.
+
+Cost (profiles/mlp_cost.txt; DESIGN.md section 18 has the table and its one condition, which is MISSED at 7 of its 12 shapes).  Device time
+against the same nn.Sequential under torch.no_grad(): faster for the deep, narrow nets at the reference's batch sizes (DQN's 7 x 366 at B = 6
+and 544: 1.6x - 1.8x; SAC's 6 x 233 critic at 6 and 470: 1.9x; PPO's 2 x 358 at 203: 1.09x), SLOWER for the wide ones there (A2C's 4 x 808 at
+B = 6 and 658: 0.69x and 0.56x; TQC's 3 x 708 critic at 6 and 290: 0.64x; TD3's 3 x 743 critic at 6 and 257: 0.84x and 0.87x; PPO at B = 6:
+0.85x) and slower at thousands of rows (0.47x - 1.01x of the vendor GEMM at 4 096 - 65 536).  Inside a captured collect loop with a
+40 -> 64 -> 64 -> 5 policy it is faster than torch's kernels at 4 096 envs and slower at 65 536.  What it gives at every shape is the fixed summation order -- the same bits for a row at every
+batch size -- and calls that capture into a graph without allocation."""
+import torch
+
+from . import _lib
+
+
+def parse_mlp(modules):
+    """(linears, hidden_activation, out_activation) of an nn.Sequential, a Linear, or a list of those to chain.  TypeError for a module
+    that is not Linear / ReLU / Tanh / Sequential of them or a parameter that is not float32; then ValueError for a sequence that is not
+    Linear (activation Linear)* [activation], for mixed hidden activations, for a Linear without bias and for too many layers."""
+    nn = torch.nn
+    flat = []
+
+    def walk(m):
+        if isinstance(m, nn.Sequential) or isinstance(m, (list, tuple)):
+            for c in m:
+                walk(c)
+        elif isinstance(m, (nn.Linear, nn.ReLU, nn.Tanh)):
+            flat.append(m)
+        else:
+            raise TypeError(f"DeviceMLP: only Linear, ReLU and Tanh (in a Sequential or a list) are supported, got {type(m).__name__}")
+
+    walk(modules)
+    for m in flat:
+        if isinstance(m, nn.Linear):
+            for name, p in (("weight", m.weight), ("bias", m.bias)):
+                if p is not None and p.dtype != torch.float32:
+                    raise TypeError(f"DeviceMLP: Linear.{name} must be torch.float32, got {p.dtype}")
+    linears, acts = [], []                                   # acts[l]: the activation behind linears[l], or None
+    for m in flat:
+        if isinstance(m, nn.Linear):
+            linears.append(m)
+            acts.append(None)
+        elif not linears or acts[-1] is not None:
+            raise ValueError("DeviceMLP: an activation must follow a Linear, one at most")
+        else:
+            acts[-1] = "relu" if isinstance(m, nn.ReLU) else "tanh"
+    if not 1 <= len(linears) <= _lib.MLP_MAX_LAYERS:
+        raise ValueError(f"DeviceMLP: 1 to {_lib.MLP_MAX_LAYERS} Linear layers, got {len(linears)}")
+    hidden = set(acts[:-1])
+    if None in hidden:
+        raise ValueError("DeviceMLP: two Linear layers with no activation between them")
+    if len(hidden) > 1:
+        raise ValueError("DeviceMLP: mixed hidden activations; one of ReLU and Tanh serves every hidden layer")
+    for l, m in enumerate(linears):
+        if m.bias is None:
+            raise ValueError(f"DeviceMLP: Linear {l} has no bias")
+        if l and m.in_features != linears[l - 1].out_features:
+            raise ValueError(f"DeviceMLP: Linear {l} takes {m.in_features} features, Linear {l - 1} gives {linears[l - 1].out_features}")
+    return linears, (hidden.pop() if hidden else "relu"), acts[-1]
+
+
+class DeviceMLP:
+    def __init__(self, engine, modules, batch, hidden=False):
+        """engine: the HipEngine whose device and library serve the calls; modules: see parse_mlp; batch: the most rows a call takes;
+        hidden: keep the post-activation hidden layers of the last call in `self.hidden` (views into the workspace: what a backward
+        pass would read)."""
+        self.engine = engine
+        self.linears, self.hidden_activation, self.out_activation = parse_mlp(modules)
+        for l, m in enumerate(self.linears):
+            if not m.weight.is_contiguous() or not m.bias.is_contiguous():
+                raise ValueError(f"DeviceMLP: the parameters of Linear {l} must be contiguous, got weight strides {tuple(m.weight.stride())}")
+        for l, m in enumerate(self.linears):
+            for p in (m.weight, m.bias):
+                if p.device != engine.device:
+                    raise ValueError(f"DeviceMLP: Linear {l} lives on {p.device}, the engine on {engine.device}")
+        self.batch = int(batch)
+        self.widths = [m.out_features for m in self.linears]
+        self.in_features = self.linears[0].in_features
+        self.keep_hidden = bool(hidden)
+        nbytes = engine.mlp_workspace(self.batch, self.widths, self.keep_hidden)      # ValueError for a batch or a width out of range
+        with engine._torch.cuda.device(engine.device):
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=engine.device)
+            self.out = torch.empty((self.batch, self.widths[-1]), dtype=torch.float32, device=engine.device)
+        self.hidden = None
+
+    def __call__(self, x, x2=None):
+        """x [B, F1] (and x2 [B, F2]) float32 with B <= batch -> the output [B, O]: the first B rows of the preallocated tensor, which
+        the next call overwrites.  Reads the parameters where they are now."""
+        B = x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else None
+        if B is not None and B > self.batch:
+            raise ValueError(f"DeviceMLP: {B} rows, allocated for {self.batch}")
+        res = self.engine.mlp_forward(x, [m.weight.detach() for m in self.linears], [m.bias.detach() for m in self.linears],
+                                      hidden_activation=self.hidden_activation, out_activation=self.out_activation, x2=x2,
+                                      out=None if B is None else self.out[:B], workspace=self.workspace, keep_hidden=self.keep_hidden)
+        self.hidden = res.hidden
+        return res.out

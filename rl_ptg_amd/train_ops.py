@@ -1,6 +1,6 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
-(include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels); none of them steps the environment.  HipEngine inherits them.
+action heads, the policy loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the inference forward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+(include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
 _action_kind; torch stays lazily imported (torch = self._torch).
@@ -34,6 +34,9 @@ RSampleGrad = collections.namedtuple("RSampleGrad", "grad_mean grad_log_std")
 # what actor_loss returns: stats float64 [8], the gradients w.r.t. q (as q came; None for kind "ent_coef"), w.r.t. log_prob (None for
 # "td3" / "ent_coef") and w.r.t. log alpha (float64 [1]; None without target_entropy)
 ActorLoss = collections.namedtuple("ActorLoss", "stats grad_q grad_log_prob grad_log_ent_coef")
+# what mlp_forward returns: out [B, O] float32; hidden: with keep_hidden the n - 1 post-activation hidden layers as [B, width_l] views into
+# the workspace, else None
+MlpOut = collections.namedtuple("MlpOut", "out hidden")
 
 
 class OptimPlan:
@@ -1084,6 +1087,98 @@ class TrainOps:
         with torch.cuda.device(self.device):
             self._chk(self._L.ptg_actor_loss(self._h, C.byref(d), self._stream()))
         return ActorLoss(stats, g_q, g_lp, g_la)
+
+    # ------------------------------------------------------------------ the inference forward of an MLP
+    def mlp_workspace(self, batch, widths, keep_hidden=False):
+        """bytes of device scratch mlp_forward needs for `batch` rows of a net with these layer widths: what ptg_mlp_workspace returns
+        (include/ptg_env.h documents the layout), computed here so that the argument checks need no library"""
+        widths = [int(w) for w in widths]
+        if not (1 <= int(batch) <= 2 ** 31 and 1 <= len(widths) <= _lib.MLP_MAX_LAYERS and all(1 <= w <= _lib.MLP_MAX_WIDTH for w in widths)):
+            raise ValueError(f"mlp_workspace: batch must be in [1, 2^31], 1 to {_lib.MLP_MAX_LAYERS} layers, widths in [1, {_lib.MLP_MAX_WIDTH}]; got {batch}, {widths}")
+        pitches = [(w + 3) // 4 * 4 for w in widths[:-1]]
+        floats = int(batch) * sum(pitches) if keep_hidden else 2 * int(batch) * max(pitches, default=0)
+        return max(16, 4 * floats)
+
+    def mlp_forward(self, x, weights, biases, hidden_activation="relu", out_activation=None, x2=None, out=None, workspace=None, keep_hidden=False,
+                    _route=None):
+        """Enqueue, on the current stream, the forward pass of an MLP without autograd: one fused launch per layer (include/ptg_env.h:
+        ptg_mlp_forward, which states the arithmetic -- per unit a float32 fmaf chain from the bias over ascending k, then the activation).
+        x [B, F1] float32 with unit column stride and a row stride >= F1 (a column slice of a wider tensor fits); x2 [B, F2] likewise, or
+        None: the net reads th.cat([x, x2], 1) without the cat.  weights[l] [out_l, in_l] float32 in torch's Linear.weight layout with
+        unit column stride, biases[l] [out_l] contiguous; in_0 = F1 + F2, in_l = out_(l-1); 1 to 10 layers, every width and the fan-in in
+        [1, 1024].  hidden_activation "relu" | "tanh" after every layer but the last, out_activation None | "relu" | "tanh" after the last.
+        out: [B, O] float32 with unit column stride and a row stride >= O, allocated when None.  workspace: a contiguous uint8 tensor
+        of at least mlp_workspace(B, widths, keep_hidden) bytes, 4-byte aligned, allocated when None.  keep_hidden: the post-activation
+        hidden layers stay in the workspace and are returned as views into it.  Returns MlpOut(out, hidden): hidden a tuple of n - 1
+        [B, width_l] views, or None.  No synchronisation and, with out= and workspace=, no allocation; a -0 result may come out as +0.
+        `_route` ("narrow" | "wide") forces one tile route in every layer: for tests and measurements, the bits do not depend on it."""
+        torch = self._torch
+        who = "mlp_forward"
+        f32 = (torch.float32,)
+        acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
+        if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)):
+            raise TypeError(f"{who}: weights and biases must be lists of tensors, got {type(weights).__name__} and {type(biases).__name__}")
+        named = [("x", x), ("x2", x2)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases)]
+        for name, t in named:                                # TypeError first: what every value is
+            if not (t is None and name == "x2") and (not torch.is_tensor(t) or t.dtype not in f32):
+                check(self, who, name, t, dtypes=f32)
+        if hidden_activation not in ("relu", "tanh"):
+            raise ValueError(f"{who}: hidden_activation must be 'relu' or 'tanh', got {hidden_activation!r}")
+        if out_activation not in acts:
+            raise ValueError(f"{who}: out_activation must be None, 'relu' or 'tanh', got {out_activation!r}")
+        if _route not in (None, "narrow", "wide"):
+            raise ValueError(f"{who}: _route must be None, 'narrow' or 'wide', got {_route!r}")
+        n = len(weights)
+        if not 1 <= n <= _lib.MLP_MAX_LAYERS or len(biases) != n:
+            raise ValueError(f"{who}: 1 to {_lib.MLP_MAX_LAYERS} layers with one bias each, got {n} weights and {len(biases)} biases")
+        check(self, who, "x", x, dtypes=f32, shape=(None, None), rule=rows)
+        B, F1 = x.shape
+        check(self, who, "x2", x2, dtypes=f32, shape=(B, None), rule=rows, optional=True)
+        F2 = 0 if x2 is None else x2.shape[1]
+        if B < 1 or F1 < 1 or (x2 is not None and F2 < 1):
+            raise ValueError(f"{who}: an empty batch or an empty input piece: x {tuple(x.shape)}" + ("" if x2 is None else f", x2 {tuple(x2.shape)}"))
+        fan_in, widths = F1 + F2, []
+        for l in range(n):
+            if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
+                raise ValueError(f"{who}: the fan-in of layer {l} is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
+            check(self, who, f"weights[{l}]", weights[l], dtypes=f32, shape=(None, fan_in), rule=rows)
+            fan_in = weights[l].shape[0]
+            check(self, who, f"biases[{l}]", biases[l], dtypes=f32, shape=(fan_in,), rule=contiguous)
+            widths.append(fan_in)
+        if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
+            raise ValueError(f"{who}: the output width is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
+        check(self, who, "out", out, dtypes=f32, shape=(B, fan_in), rule=rows, optional=True, exc=ValueError)
+        need = self.mlp_workspace(B, widths, keep_hidden)
+        if workspace is not None:
+            check(self, who, f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspace, dtypes=(torch.uint8,), shape=(None,), rule=contiguous,
+                  exc=ValueError)
+            if workspace.numel() < need:
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, the call needs {need}")
+            if workspace.data_ptr() % 4:
+                raise ValueError(f"{who}: workspace must be 4-byte aligned")
+        with torch.cuda.device(self.device):
+            if workspace is None:
+                workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if out is None:
+                out = torch.empty((B, fan_in), dtype=torch.float32, device=self.device)
+        row_stride = lambda t: max(t.stride(0), t.shape[1])      # a one-row tensor may report any row stride
+        flags = (_lib.MLP_KEEP_HIDDEN if keep_hidden else 0) | {None: 0, "narrow": _lib.MLP_NARROW, "wide": _lib.MLP_WIDE}[_route]
+        d = _lib.PtgMlp(batch=B, n_layers=n, flags=flags, hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
+                        x_dev=_ptr(x), x_s_n=row_stride(x), x2_dev=_ptr(x2), x2_s_n=0 if x2 is None else row_stride(x2), out_dev=_ptr(out),
+                        out_s_n=row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
+        for l in range(n):
+            d.w_dev[l], d.w_s_n[l], d.b_dev[l], d.width[l] = weights[l].data_ptr(), row_stride(weights[l]), biases[l].data_ptr(), widths[l]
+        with torch.cuda.device(self.device):
+            self._chk(self._L.ptg_mlp_forward(self._h, C.byref(d), self._stream()))
+        hidden = None
+        if keep_hidden:
+            hidden, off = [], 0
+            for w in widths[:-1]:
+                p = (w + 3) // 4 * 4
+                hidden.append(workspace[off:off + 4 * B * p].view(torch.float32).view(B, p)[:, :w])
+                off += 4 * B * p
+            hidden = tuple(hidden)
+        return MlpOut(out, hidden)
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):

@@ -1,8 +1,10 @@
 """What the SB3-facing observation hand-off buys end to end: a collect loop  obs -> policy -> action -> env step  with a
 policy of the shape the reference trains (SB3 "MultiInputPolicy": CombinedExtractor's 40 columns -> 64 -> 64 -> 5 logits, tanh; random
-weights, greedy actions), four ways:
+weights, greedy actions), five ways:
   flat    PTG_OBS_SB3_FLAT rows stay on the device: torch MLP on the [N, 40] tensor the kernel wrote, ptg_step on the action tensor it produced
   graph   the flat loop captured once (policy forward + ptg_step) and replayed as one hipGraph per step (ptg_note_replays afterwards)
+  mlp     the graph loop with rl_ptg_amd.DeviceMLP (ptg_mlp_forward: one fused launch per layer) + act_categorical(deterministic=True) in place of
+          torch's three Linears, two tanh kernels and the argmax
   split   PTG_OBS_SPLIT rows (16 columns) + policy_split.FirstLayerSplit for the first layer
   host    the drop-in route of the reference's loop: PtGVecEnv.step(numpy actions) -> dict of NumPy arrays -> flattened on the host ->
           torch.as_tensor(...).cuda() -> policy -> actions.cpu().numpy()   (what SB3's collect_rollouts does around a VecEnv)
@@ -80,6 +82,32 @@ eng.note_replays(50 + K - 1)                                 # the capture count
 eng.sync()
 assert eng.steps_to_episode_end() == int(spec.consts["eps_sim_steps"]) - 5 - (3 + 50 + K)
 print(f"graph  (flat rows, policy + ptg_step as one hipGraph): {dt * 1e6:6.1f} us per vector step = {n / dt:.3e} env-steps/s", flush=True)
+eng.close()
+
+# --- the graph loop with the policy as DeviceMLP (one fused launch per layer) and ptg_act's greedy head in place of the three Linears, the
+# two tanh kernels and the argmax
+from rl_ptg_amd import DeviceMLP
+eng = engine("sb3_flat")
+obs_static = eng.reset()
+policy = DeviceMLP(eng, torch.nn.Sequential(l1, torch.nn.Tanh(), l2, torch.nn.Tanh(), l3), batch=n)
+head = eng.act_categorical(policy(obs_static), None, deterministic=True, want_logp=False, want_entropy=False)      # the static outputs
+def body_mlp():
+    eng.act_categorical(policy(obs_static), None, deterministic=True, want_logp=False, want_entropy=False, out=head)
+    eng.step(head.actions, want_final=False)
+for _ in range(3):
+    body_mlp()
+side = torch.cuda.Stream()
+side.wait_stream(torch.cuda.current_stream())
+g2 = torch.cuda.CUDAGraph()
+with torch.cuda.stream(side):
+    with torch.cuda.graph(g2, stream=side):
+        body_mlp()
+torch.cuda.current_stream().wait_stream(side)
+dt = timed(lambda o: g2.replay(), None)
+eng.note_replays(50 + K - 1)
+eng.sync()
+assert eng.steps_to_episode_end() == int(spec.consts["eps_sim_steps"]) - 5 - (3 + 50 + K)
+print(f"mlp    (graph loop, DeviceMLP + act_categorical):      {dt * 1e6:6.1f} us per vector step = {n / dt:.3e} env-steps/s", flush=True)
 eng.close()
 
 # --- split rows + first layer from projection tables

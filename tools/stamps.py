@@ -1,6 +1,6 @@
 """Phases of one fused-rollout launch from in-kernel 100 MHz stamps: python tools/stamps.py [T].  Needs the diagnostic build, with ptg_env.hip as
 ONE translation unit (no PTG_PART: g_stamps is per translation unit): hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DPTG_STAMPS
--shared -o tools/libptg_stamps.so rl_ptg_amd/csrc/ptg_env.hip rl_ptg_amd/csrc/ptg_train.hip, loaded through PTG_LIB_PATH=tools/libptg_stamps.so.
+-shared -o tools/libptg_stamps.so rl_ptg_amd/csrc/ptg_env.hip rl_ptg_amd/csrc/ptg_train.hip rl_ptg_amd/csrc/ptg_mlp.hip, loaded through PTG_LIB_PATH=tools/libptg_stamps.so.
 Stamps per workgroup, wave 0 (producer) / first consumer wave: 0 kernel entry, 1 actions staged, 2 LDS staging issued, 3 past the
 barrier, 4 first hand-off (producer: step 0 produced; consumer: step 0 requested), 5 second step (consumer: first finish issued),
 6 loop done (producer: before the last barrier), 7 end (consumer: all stores retired)."""

@@ -1,5 +1,5 @@
 """Phases of one k_step_hot launch from in-kernel 100 MHz stamps (diagnostic build: hipcc ... -DPTG_STAMPS -o tools/libptg_stamps.so
-rl_ptg_amd/csrc/ptg_env.hip rl_ptg_amd/csrc/ptg_train.hip, loaded through PTG_LIB_PATH=tools/libptg_stamps.so): wave 0 of every workgroup stamps 0 entry, 1 past the LDS-stage barrier, 2 state + action arrived,
+rl_ptg_amd/csrc/ptg_env.hip rl_ptg_amd/csrc/ptg_train.hip rl_ptg_amd/csrc/ptg_mlp.hip, loaded through PTG_LIB_PATH=tools/libptg_stamps.so): wave 0 of every workgroup stamps 0 entry, 1 past the LDS-stage barrier, 2 state + action arrived,
 3 look-up done and record gather issued, 4 record arrived / reward done, 5 stores issued, 6 stores retired."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
