@@ -619,10 +619,15 @@ k_act(ActArgs a)
 // One lane per row on consecutive rows, float64 arithmetic whatever the input type, gradients rounded once on the store.  A
 // categorical row is read as k_act reads it (maximum; sum; entropy and the chosen log-prob) plus a fourth pass that writes the
 // gradients, which need the row's complete entropy; exp is evaluated again instead of kept, so nothing per lane is indexed dynamically.
-// Batch-wide quantities (the advantage moments, six sums, the log_std gradient) are reduced in a fixed order: a shuffle tree per wave,
-// the block's four waves in wave order, one partial per block in the caller's workspace, and a merge that walks the partials in an
-// order given by the block count alone.  No floating-point atomics: the same inputs give the same bits.  Moments travel as
-// (count, mean, M2) and meet in chan_merge, as the reward normalisation's do.
+// Batch-wide quantities (the advantage moments, six sums, the log_std gradient) are reduced in a fixed order, the same for every
+// loss of this file (loss_tail and k_loss_final are its only text):
+//   1. a shuffle tree per wave (pl_wave_sum: offsets 32, 16, ..., 1)
+//   2. the block's four waves in wave order (pl_block_sum)
+//   3. a batch of one block ends there; else every block stores its PL_TERMS sums at partials + block * PL_PITCH in the caller's
+//      workspace and one more block follows, whose thread t adds the partials of blocks t, t + PL_BLOCK, t + 2 PL_BLOCK, ... in that
+//      order from 0.0, then steps 1 and 2 again
+// The order is given by the block count alone and there are no floating-point atomics: the same inputs give the same bits.  Moments
+// travel as (count, mean, M2) and meet in chan_merge, as the reward normalisation's do.
 struct LossArgs {                        // by value in the launch
     const void* in; size_t s_n;          // elements
     const void* val; size_t v_s;
@@ -812,6 +817,41 @@ __device__ __forceinline__ void pl_block_sum(double* v, double* sh)
     }
 }
 
+// how every row kernel of a loss ends: the block's sums, then on thread 0 either the statistics (ONE: the block is the whole batch;
+// fin(v) is the loss's *_finish) or the block's partial for k_loss_final.  Every thread of the block calls it.
+template <bool ONE, typename FIN>
+__device__ __forceinline__ void loss_tail(double* v, double* sh, double* part, FIN fin)
+{
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) {
+        if (ONE) fin(v);
+        else {
+            double* p = part + (size_t)blockIdx.x * PL_PITCH;
+#pragma unroll
+            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
+        }
+    }
+}
+
+// the last launch of a loss of more than one block, one block: step 3 of the order above, then FIN()(a, v) -- the loss's *_finish --
+// on thread 0.  A: the loss's launch arguments (their nblk is read), part: where the row kernel left its partials.
+template <typename A, typename FIN>
+__global__ void __launch_bounds__(PL_BLOCK)
+k_loss_final(A a, const double* part)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < PL_TERMS; k++) v[k] += part[(size_t)b * PL_PITCH + k];
+    }
+    pl_block_sum(v, sh);
+    if (threadIdx.x == 0) FIN()(a, v);
+}
+
+// where the policy loss keeps its row partials: behind the merged moments and the moment partials
+__host__ __device__ __forceinline__ double* pl_partials(const LossArgs& a) { return a.ws + 4 + (size_t)a.nblk * 3; }
+
 template <typename IN>
 __global__ void __launch_bounds__(PL_BLOCK)
 k_pl_moments(LossArgs a)
@@ -827,7 +867,7 @@ k_pl_moments(LossArgs a)
 }
 
 // ONE: the whole batch is this block (B <= PL_BLOCK): moments, rows and statistics in one launch.  Otherwise the moments come
-// merged from the workspace and the block leaves its partial sums there for k_pl_final.
+// merged from the workspace and the block leaves its partial sums there for k_loss_final.
 template <typename IN, bool ONE>
 __global__ void __launch_bounds__(PL_BLOCK)
 k_pl_rows(LossArgs a)
@@ -847,35 +887,17 @@ k_pl_rows(LossArgs a)
     PlRow t{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (live) t = pl_row<IN>(a, i, norm, mean, sd + 1e-8);
     double v[PL_TERMS] = {t.surr, t.q, t.H, t.kl, t.cf, t.gls};
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) {
-        if (ONE) pl_finish<IN>(a, v, mean, sd);
-        else {
-            double* p = a.ws + 4 + (size_t)a.nblk * 3 + (size_t)blockIdx.x * PL_PITCH;
-#pragma unroll
-            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
-        }
-    }
+    loss_tail<ONE>(v, sh, pl_partials(a), [&](const double* s) { pl_finish<IN>(a, s, mean, sd); });
 }
 
-// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
 template <typename IN>
-__global__ void __launch_bounds__(PL_BLOCK)
-k_pl_final(LossArgs a)
-{
-    __shared__ double sh[PL_WAVES * PL_PITCH];
-    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const double* part = a.ws + 4 + (size_t)a.nblk * 3;
-    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < PL_TERMS; k++) v[k] += part[(size_t)b * PL_PITCH + k];
-    }
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) {
+struct PlFinal {                         // mean and sd once more from the merged moments, as k_pl_rows<IN, false> has them
+    __device__ void operator()(const LossArgs& a, const double* v) const
+    {
         const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
         pl_finish<IN>(a, v, norm ? a.ws[1] : 0.0, norm ? sqrt(a.ws[2] / ((double)a.B - 1.0)) : 1.0);
     }
-}
+};
 
 // ================================================================================== the optimiser step
 // What runs behind loss.backward() (include/ptg_env.h, ptg_optim_step, states the lines; tests/optim_restatement.py restates them in
@@ -1084,7 +1106,7 @@ k_optim_update(OptArgs a)
 // straight from memory as k_act and pl_row read theirs; the critics' K pointers and strides sit in the launch arguments and every loop
 // over them is unrolled over PTG_TD_MAX_CRITICS with a k < K guard, so nothing per lane (and no launch argument) is indexed
 // dynamically.  The reward and done columns have dtypes of their own, read behind a wave-uniform branch.  The five sums go through
-// the policy loss's fixed-order scheme: pl_wave_sum, pl_block_sum, one partial per block in the caller's workspace, k_td_final.
+// the fixed-order scheme stated above LossArgs (loss_tail, k_loss_final).
 constexpr int TD_K = PTG_TD_MAX_CRITICS;
 
 struct TdArgs {                          // by value in the launch: a captured call holds no host memory
@@ -1208,7 +1230,7 @@ __device__ __forceinline__ void td_finish(const TdArgs& a, const double* sum, do
 }
 
 // ONE: the whole batch is this block (B <= PL_BLOCK): rows and statistics in one launch.  Otherwise the block leaves its partial sums
-// in the workspace for k_td_final.
+// in the workspace for k_loss_final.
 template <typename IN, bool DQN, bool ONE>
 __global__ void __launch_bounds__(PL_BLOCK)
 k_td_rows(TdArgs a)
@@ -1220,30 +1242,12 @@ k_td_rows(TdArgs a)
     TdRow t{0.0, 0.0, 0.0, 0.0, 0.0};
     if (live) t = DQN ? td_row_dqn<IN>(a, i) : td_row_critics<IN>(a, i, alpha);
     double v[PL_TERMS] = {t.term, t.q, t.y, t.ad, t.ge, 0.0};
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) {
-        if (ONE) td_finish(a, v, alpha);
-        else {
-            double* p = a.ws + (size_t)blockIdx.x * PL_PITCH;
-#pragma unroll
-            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
-        }
-    }
+    loss_tail<ONE>(v, sh, a.ws, [&](const double* s) { td_finish(a, s, alpha); });
 }
 
-// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
-__global__ void __launch_bounds__(PL_BLOCK)
-k_td_final(TdArgs a)
-{
-    __shared__ double sh[PL_WAVES * PL_PITCH];
-    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < PL_TERMS; k++) v[k] += a.ws[(size_t)b * PL_PITCH + k];
-    }
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) td_finish(a, v, td_alpha(a));
-}
+struct TdFinal {
+    __device__ void operator()(const TdArgs& a, const double* v) const { td_finish(a, v, td_alpha(a)); }
+};
 
 // ================================================================================== the quantile-Huber loss of TQC's critics
 // sb3_contrib's TQC.train critic lines and quantile_huber_loss(sum_over_quantiles=False) (include/ptg_env.h, ptg_quantile_loss, states
@@ -1255,7 +1259,7 @@ k_td_final(TdArgs a)
 // index), so the ranks are a permutation and the kept values depend on no race.  The lanes then stride over the K * Q (k, i) pairs and
 // run the j loop over the targets out of LDS (every lane reads the same address: a broadcast) in the header's order.  The K pointers
 // travel by value and are picked behind an unrolled k == kk guard, as td_row_critics picks its.  A wave without a row takes every
-// barrier and every tree with zero terms.  Sums: pl_block_sum (the four waves = rows in wave order), one partial per block, k_ql_final.
+// barrier and every tree with zero terms.  Sums: the scheme stated above LossArgs, the block's four waves being its four rows.
 constexpr int QL_MAX = PTG_TD_MAX_CRITICS * PTG_QL_MAX_QUANTILES, QL_PER = QL_MAX / 64;      // 256 values a row, at most 4 a lane
 
 struct QlArgs {                          // by value in the launch: a captured call holds no host memory
@@ -1415,30 +1419,12 @@ k_ql_rows(QlArgs a)
     }
     // 5. the row's terms -> the block's partial
     double sums[PL_TERMS] = {sum_ls, sum_q, sum_y, sum_ad, sum_gt, 0.0};
-    pl_block_sum(sums, sh);
-    if (threadIdx.x == 0) {
-        if (ONE) ql_finish(a, sums, alpha);
-        else {
-            double* p = a.ws + (size_t)blockIdx.x * PL_PITCH;
-#pragma unroll
-            for (int k = 0; k < PL_TERMS; k++) p[k] = sums[k];
-        }
-    }
+    loss_tail<ONE>(sums, sh, a.ws, [&](const double* s) { ql_finish(a, s, alpha); });
 }
 
-// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
-__global__ void __launch_bounds__(PL_BLOCK)
-k_ql_final(QlArgs a)
-{
-    __shared__ double sh[PL_WAVES * PL_PITCH];
-    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < PL_TERMS; k++) v[k] += a.ws[(size_t)b * PL_PITCH + k];
-    }
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) ql_finish(a, v, ql_alpha(a));
-}
+struct QlFinal {
+    __device__ void operator()(const QlArgs& a, const double* v) const { ql_finish(a, v, ql_alpha(a)); }
+};
 
 // ================================================================================== the training-time actor head
 // SB3's Actor.action_log_prob as SAC and TQC run it on a replay batch (include/ptg_env.h, ptg_rsample, states the lines;
@@ -1533,7 +1519,7 @@ k_rs_bwd(RsArgs a)
 // ptg_actor_loss, states the lines; tests/actor_restatement.py restates them) with d loss / d Q (or quantile), d loss / d log_prob and
 // d loss / d log alpha in closed form.  k_td_rows' shape: one lane per row, the critics' pointers and strides by value, every loop over
 // them unrolled over PTG_TD_MAX_CRITICS behind a k < K guard; a TQC lane walks its K * Q quantiles in index order (two strided reads
-// and one store each).  Four sums and a poison word go through the policy loss's fixed-order scheme.
+// and one store each).  Four sums and a poison word go through the fixed-order scheme stated above LossArgs.
 struct AlArgs {                          // by value in the launch
     const void* q[TD_K]; size_t q_s[TD_K];       // elements
     void* g[TD_K]; size_t g_s[TD_K];
@@ -1588,7 +1574,7 @@ __device__ __forceinline__ void al_finish(const AlArgs& a, const double* sum, do
 }
 
 // ONE: the whole batch is this block (B <= PL_BLOCK): rows and statistics in one launch.  Otherwise the block leaves its partial sums
-// in the workspace for k_al_final.
+// in the workspace for k_loss_final.
 template <typename IN, bool ONE>
 __global__ void __launch_bounds__(PL_BLOCK)
 k_al_rows(AlArgs a)
@@ -1654,34 +1640,17 @@ k_al_rows(AlArgs a)
             v[1] = lp; v[2] = m; v[3] = lp + a.H_t;
         }
     }
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) {
-        if (ONE) al_finish(a, v, alpha);
-        else {
-            double* p = a.ws + (size_t)blockIdx.x * PL_PITCH;
-#pragma unroll
-            for (int k = 0; k < PL_TERMS; k++) p[k] = v[k];
-        }
-    }
+    loss_tail<ONE>(v, sh, a.ws, [&](const double* s) { al_finish(a, s, alpha); });
 }
 
-// one block: thread t sums the partials of blocks t, t + PL_BLOCK, ... in that order, then the block's tree
-__global__ void __launch_bounds__(PL_BLOCK)
-k_al_final(AlArgs a)
-{
-    __shared__ double sh[PL_WAVES * PL_PITCH];
-    double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < PL_TERMS; k++) v[k] += a.ws[(size_t)b * PL_PITCH + k];
-    }
-    pl_block_sum(v, sh);
-    if (threadIdx.x == 0) {
+struct AlFinal {
+    __device__ void operator()(const AlArgs& a, const double* v) const
+    {
         bool ok;
         const double alpha = al_alpha(a, ok);
         al_finish(a, v, alpha);
     }
-}
+};
 
 // ================================================================================================= host side
 // ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
@@ -1696,45 +1665,30 @@ void launch_minibatch(hipStream_t st, const void* idx, int idx_bytes, size_t B, 
         hipLaunchKernelGGL((k_minibatch<V, int>), grid, block, 0, st, (const int*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
 }
 
-// ptg_td_loss's launches: the Q dtype and the kind are the row kernel's template axes
-template <typename IN>
-void launch_td(hipStream_t st, const TdArgs& a, bool dqn)
+// the blocks of a loss's batch at `per` rows a block (PL_BLOCK; the quantile loss: PL_WAVES), and the bytes of that many partials
+static int64_t loss_blocks(int64_t batch, int per) { return (batch - 1) / per + 1; }
+static int64_t loss_partials_bytes(int64_t nblk) { return nblk * PL_PITCH * (int64_t)sizeof(double); }
+
+// the workspace of a loss that keeps nothing but its partials there; the limit is ptg_policy_loss's: 2^23 blocks of 256 threads (the
+// quantile loss: 2^29 blocks of four rows)
+static int64_t loss_workspace(int64_t batch, int per)
 {
-    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
-    if (a.nblk == 1) {                                       // up to 256 rows: everything in one launch
-        if (dqn) hipLaunchKernelGGL((k_td_rows<IN, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_td_rows<IN, false, true>), grid, block, 0, st, a);
-        return;
-    }
-    if (dqn) hipLaunchKernelGGL((k_td_rows<IN, true, false>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_td_rows<IN, false, false>), grid, block, 0, st, a);
-    hipLaunchKernelGGL(k_td_final, dim3(1), block, 0, st, a);
+    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;
+    return loss_partials_bytes(loss_blocks(batch, per));
 }
 
-// ptg_quantile_loss's launches: the quantile dtype is the row kernel's template axis
-template <typename IN>
-void launch_ql(hipStream_t st, const QlArgs& a)
+// the launches of a loss: a batch of one block has rows and statistics in one launch (`one`, the row kernel's ONE instantiation);
+// else the rows (`many`), then k_loss_final over the partials at `part`
+template <typename FIN, typename A>
+void launch_loss(hipStream_t st, const A& a, const double* part, void (*one)(A), void (*many)(A))
 {
     const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
-    if (a.nblk == 1) {                                       // up to 4 rows: everything in one launch
-        hipLaunchKernelGGL((k_ql_rows<IN, true>), grid, block, 0, st, a);
+    if (a.nblk == 1) {
+        hipLaunchKernelGGL(one, grid, block, 0, st, a);
         return;
     }
-    hipLaunchKernelGGL((k_ql_rows<IN, false>), grid, block, 0, st, a);
-    hipLaunchKernelGGL(k_ql_final, dim3(1), block, 0, st, a);
-}
-
-// ptg_actor_loss's launches: the dtype of the Q-values and log-probs is the row kernel's template axis
-template <typename IN>
-void launch_al(hipStream_t st, const AlArgs& a)
-{
-    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
-    if (a.nblk == 1) {                                       // up to 256 rows: everything in one launch
-        hipLaunchKernelGGL((k_al_rows<IN, true>), grid, block, 0, st, a);
-        return;
-    }
-    hipLaunchKernelGGL((k_al_rows<IN, false>), grid, block, 0, st, a);
-    hipLaunchKernelGGL(k_al_final, dim3(1), block, 0, st, a);
+    hipLaunchKernelGGL(many, grid, block, 0, st, a);
+    hipLaunchKernelGGL((k_loss_final<A, FIN>), dim3(1), block, 0, st, a, part);
 }
 
 // what ptg_rsample and ptg_rsample_backward refuse alike; the text of the first fault, or null
@@ -2085,8 +2039,8 @@ int64_t ptg_policy_loss_workspace(int64_t batch)
 {
     if (batch < 1) return PTG_E_INVALID;
     if (batch > (int64_t)1 << 31) return PTG_E_INVALID;     // 2^23 blocks of 256 threads: half of the 2^32 threads one launch may have
-    const int64_t nblk = (batch - 1) / PL_BLOCK + 1;
-    return (4 + nblk * (3 + PL_PITCH)) * (int64_t)sizeof(double);
+    const int64_t nblk = loss_blocks(batch, PL_BLOCK);
+    return (4 + nblk * 3) * (int64_t)sizeof(double) + loss_partials_bytes(nblk);
 }
 
 int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
@@ -2125,27 +2079,17 @@ int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
     a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
     a.eps = d->clip_range; a.eps_v = d->clip_range_vf; a.ent_coef = d->ent_coef; a.vf_coef = d->vf_coef;
     a.B = (size_t)d->batch; a.A = d->n_actions; a.kind = d->kind; a.head = d->head; a.flags = d->flags; a.act_kind = d->act_kind;
-    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
     a.err = h->P.err;
     const bool f64 = d->in_dtype == PTG_OUT_F64, norm = (d->flags & PTG_LOSS_NORM_ADV) != 0 && d->batch > 1;
-    const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
-    if (a.nblk == 1) {                                       // PPO's minibatch: everything in one launch
-        if (f64) hipLaunchKernelGGL((k_pl_rows<double, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_pl_rows<float, true>), grid, block, 0, st, a);
-        return launch_check(h, "k_pl_rows");
-    }
-    if (norm) {
+    if (a.nblk > 1 && norm) {                                // PPO's minibatch is one block, which takes its moments itself
+        const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
         if (f64) hipLaunchKernelGGL(k_pl_moments<double>, grid, block, 0, st, a);
         else hipLaunchKernelGGL(k_pl_moments<float>, grid, block, 0, st, a);
         hipLaunchKernelGGL(k_vn_merge, dim3(1), dim3(64), 0, st, (const double*)(a.ws + 4), a.nblk, a.ws);
     }
-    if (f64) {
-        hipLaunchKernelGGL((k_pl_rows<double, false>), grid, block, 0, st, a);
-        hipLaunchKernelGGL(k_pl_final<double>, dim3(1), block, 0, st, a);
-    } else {
-        hipLaunchKernelGGL((k_pl_rows<float, false>), grid, block, 0, st, a);
-        hipLaunchKernelGGL(k_pl_final<float>, dim3(1), block, 0, st, a);
-    }
+    if (f64) launch_loss<PlFinal<double>>(st, a, pl_partials(a), k_pl_rows<double, true>, k_pl_rows<double, false>);
+    else launch_loss<PlFinal<float>>(st, a, pl_partials(a), k_pl_rows<float, true>, k_pl_rows<float, false>);
     return launch_check(h, "k_pl_rows");
 }
 
@@ -2206,11 +2150,7 @@ int ptg_optim_step(ptg_env* h, const ptg_optim* d, void* stream)
 }
 
 // ---- the TD losses: DQN's and the TD3 / SAC critics', the statistics and the gradients w.r.t. the current Q-values ---------
-int64_t ptg_td_loss_workspace(int64_t batch)
-{
-    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;      // ptg_policy_loss's limit: 2^23 blocks of 256 threads
-    return ((batch - 1) / PL_BLOCK + 1) * PL_PITCH * (int64_t)sizeof(double);
-}
+int64_t ptg_td_loss_workspace(int64_t batch) { return loss_workspace(batch, PL_BLOCK); }
 
 int ptg_td_loss(ptg_env* h, const ptg_td* d, void* stream)
 {
@@ -2259,19 +2199,18 @@ int ptg_td_loss(ptg_env* h, const ptg_td* d, void* stream)
     a.gamma = d->gamma; a.alpha = d->alpha; a.scale = d->scale;
     a.B = (size_t)d->batch; a.A = d->n_actions; a.K = K; a.kind = d->kind; a.flags = d->flags; a.act_kind = d->act_kind;
     a.rew_f64 = d->rew_dtype == PTG_OUT_F64; a.done_f64 = d->done_dtype == PTG_OUT_F64;
-    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
     a.err = h->P.err;
-    if (d->q_dtype == PTG_OUT_F64) launch_td<double>(st, a, dqn);
-    else launch_td<float>(st, a, dqn);
+    const bool f64 = d->q_dtype == PTG_OUT_F64;               // the Q dtype and the kind are the row kernel's template axes
+    if (f64 && dqn) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<double, true, true>, k_td_rows<double, true, false>);
+    else if (f64) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<double, false, true>, k_td_rows<double, false, false>);
+    else if (dqn) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<float, true, true>, k_td_rows<float, true, false>);
+    else launch_loss<TdFinal>(st, a, a.ws, k_td_rows<float, false, true>, k_td_rows<float, false, false>);
     return launch_check(h, "k_td_rows");
 }
 
 // ---- the quantile-Huber loss of TQC's critics, the statistics and the gradients w.r.t. the current quantiles -------------------------
-int64_t ptg_quantile_loss_workspace(int64_t batch)
-{
-    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;      // 2^29 blocks of four rows
-    return ((batch - 1) / PL_WAVES + 1) * PL_PITCH * (int64_t)sizeof(double);
-}
+int64_t ptg_quantile_loss_workspace(int64_t batch) { return loss_workspace(batch, PL_WAVES); }
 
 int ptg_quantile_loss(ptg_env* h, const ptg_ql* d, void* stream)
 {
@@ -2309,10 +2248,10 @@ int ptg_quantile_loss(ptg_env* h, const ptg_ql* d, void* stream)
     a.gamma = d->gamma; a.alpha = d->alpha;
     a.B = (size_t)d->batch; a.K = K; a.Q = Q; a.M = K * (Q - d->n_drop); a.KQ = K * Q; a.flags = d->flags;
     a.rew_f64 = d->rew_dtype == PTG_OUT_F64; a.done_f64 = d->done_dtype == PTG_OUT_F64;
-    a.nblk = (int)((d->batch - 1) / PL_WAVES + 1);
+    a.nblk = (int)loss_blocks(d->batch, PL_WAVES);
     a.err = h->P.err;
-    if (d->q_dtype == PTG_OUT_F64) launch_ql<double>(st, a);
-    else launch_ql<float>(st, a);
+    if (d->q_dtype == PTG_OUT_F64) launch_loss<QlFinal>(st, a, a.ws, k_ql_rows<double, true>, k_ql_rows<double, false>);
+    else launch_loss<QlFinal>(st, a, a.ws, k_ql_rows<float, true>, k_ql_rows<float, false>);
     return launch_check(h, "k_ql_rows");
 }
 
@@ -2360,11 +2299,7 @@ int ptg_rsample_backward(ptg_env* h, const ptg_rs* d, void* stream)
 }
 
 // ---- the actor and entropy-coefficient losses of SAC / TQC / TD3, the statistics and the gradients -----------------------------------
-int64_t ptg_actor_loss_workspace(int64_t batch)
-{
-    if (batch < 1 || batch > (int64_t)1 << 31) return PTG_E_INVALID;      // ptg_policy_loss's limit: 2^23 blocks of 256 threads
-    return ((batch - 1) / PL_BLOCK + 1) * PL_PITCH * (int64_t)sizeof(double);
-}
+int64_t ptg_actor_loss_workspace(int64_t batch) { return loss_workspace(batch, PL_BLOCK); }
 
 int ptg_actor_loss(ptg_env* h, const ptg_al* d, void* stream)
 {
@@ -2411,10 +2346,10 @@ int ptg_actor_loss(ptg_env* h, const ptg_al* d, void* stream)
     a.g_lp = d->grad_logp_dev; a.g_la = d->grad_log_alpha_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
     a.alpha = d->alpha; a.H_t = ec ? d->target_entropy : 0.0;
     a.B = (size_t)d->batch; a.K = K; a.Q = Q; a.kind = d->kind; a.flags = d->flags;
-    a.nblk = (int)((d->batch - 1) / PL_BLOCK + 1);
+    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
     a.err = h->P.err;
-    if (d->q_dtype == PTG_OUT_F64) launch_al<double>(st, a);
-    else launch_al<float>(st, a);
+    if (d->q_dtype == PTG_OUT_F64) launch_loss<AlFinal>(st, a, a.ws, k_al_rows<double, true>, k_al_rows<double, false>);
+    else launch_loss<AlFinal>(st, a, a.ws, k_al_rows<float, true>, k_al_rows<float, false>);
     return launch_check(h, "k_al_rows");
 }
 

@@ -8,7 +8,9 @@ _action_kind; torch stays lazily imported (torch = self._torch).
 Every tensor argument goes through ONE checker, check(), which raises in a fixed order: TypeError for what the value is (not a
 tensor, a refused dtype, element size or element count), then ValueError for its shape, its strides, its device.  Nothing touches
 the library and no device memory is allocated before every check of a call has passed.  Relations between arguments (old_values
-iff clip_range_vf, done_col inside the columns ...) stay plain `if`s in the methods."""
+iff clip_range_vf, done_col inside the columns ...) stay plain `if`s in the methods.  The blocks several ops share (_column,
+_critic_columns, _alpha_arg, _out_tuple, _no_tensor_twice; TrainOps._take_workspace, _fresh_like_quantiles, _call) stand once, next
+to check(), and are called at the point of the order where each op had its own copy."""
 import collections
 import ctypes as C
 
@@ -117,6 +119,47 @@ def _dims(eng, x):
     return x.dim() if eng._torch.is_tensor(x) else -1
 
 
+# ------------------------------------------------------------------ blocks that several ops share; each is called where the op's own text stood
+def _column(eng, t):
+    """[B, 1] -> [B]; anything else (None, what is no tensor) as it came, for check() to judge"""
+    return t[:, 0] if _dims(eng, t) == 2 and t.shape[1] == 1 else t
+
+
+def _critic_columns(eng, who, name, xs, dtypes, B=None, exc=TypeError):
+    """a list of critic outputs, [B] or [B, 1] each with any stride >= 1 -> their checked [B] views; the first sets the dtype and B
+    of the others"""
+    cols = []
+    for k, t in enumerate(xs):
+        cols.append(check(eng, who, f"{name}[{k}]", _column(eng, t), dtypes=dtypes, shape=(B,), rule=step, exc=exc))
+        dtypes, B = (cols[0].dtype,), cols[0].shape[0]
+    return cols
+
+
+def _alpha_arg(eng, who, ent_coef, log_ent_coef):
+    """(alpha_dev, alpha) of a call that was given ent_coef or log_ent_coef: the checked float64 device scalar, or the Python float"""
+    alpha_dev = None
+    if log_ent_coef is not None or eng._torch.is_tensor(ent_coef):
+        alpha_dev = check(eng, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
+                          dtypes=(eng._torch.float64,), numel=1)
+    return alpha_dev, float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+
+
+def _out_tuple(eng, who, out, kind, stats=True):
+    """out= must be a tuple as long as the namedtuple `kind`; stats: its first field is the float64 [8] statistics.  Returns out."""
+    if not isinstance(out, tuple) or len(out) != len(kind._fields):
+        raise ValueError(f"{who}: out must be the {kind.__name__} of an earlier call")
+    if stats:
+        check(eng, who, "out.stats", out[0], dtypes=(eng._torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+    return out
+
+
+def _no_tensor_twice(who, tensors, what):
+    """the cheap half of "outputs must not overlap": one tensor given twice"""
+    starts = [t.data_ptr() for t in tensors]
+    if len(set(starts)) != len(starts):
+        raise ValueError(f"{who}: two of {what} start at the same address; the outputs must not overlap each other or the inputs")
+
+
 def _ptr(x):
     """device pointer or NULL of a tensor; of a list of tensors, the pointer array the library takes for a column list"""
     if isinstance(x, (list, tuple)):
@@ -133,6 +176,40 @@ def _dp(a):
 
 
 class TrainOps:
+    def _call(self, name, *args):
+        """one stream-ordered library call -- handle first, the current stream last -- on the engine's device, its return code checked"""
+        with self._torch.cuda.device(self.device):
+            self._chk(getattr(self._L, name)(self._h, *args, self._stream()))
+
+    def _loss_workspace(self, op, batch):
+        """what <op>_workspace(batch) returns: a fresh uint8 tensor of ptg_<op>_workspace(batch) bytes"""
+        nbytes = getattr(self._L, f"ptg_{op}_workspace")(int(batch))
+        if nbytes < 0:
+            raise ValueError(f"{op}_workspace: batch must be {'>= 1' if op == 'policy_loss' else 'in [1, 2^31]'}, got {batch}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def _take_workspace(self, op, B, workspace):
+        """the workspace= of the loss `op`: the caller's, once it is a contiguous uint8 tensor of ptg_<op>_workspace(B) bytes or more,
+        else a fresh one"""
+        if workspace is None:
+            return self._loss_workspace(op, B)
+        check(self, op, f"workspace ({op}_workspace({B}))", workspace, dtypes=(self._torch.uint8,), rule=contiguous, exc=ValueError)
+        size = getattr(self._L, f"ptg_{op}_workspace")
+        if workspace.numel() < size(B):
+            raise ValueError(f"{op}: workspace has {workspace.numel()} bytes, a batch of {B} needs {size(B)}")
+        return workspace
+
+    def _fresh_like_quantiles(self, as_list, B, K, Q, dtype):
+        """fresh gradients as the quantiles came -- a list of K [B, Q] tensors or one [B, K, Q] tensor -- and their K [B, Q] views;
+        called under a device guard"""
+        torch = self._torch
+        if as_list:
+            g = [torch.empty((B, Q), dtype=dtype, device=self.device) for _ in range(K)]
+            return g, g
+        g = torch.empty((B, K, Q), dtype=dtype, device=self.device)
+        return g, [g[:, k] for k in range(K)]
+
     # ------------------------------------------------------------------ VecNormalize(norm_obs=False) on the device
     def vn_init(self, gamma=0.99, epsilon=1e-8, clip_reward=10.0):
         """Start reward normalisation as the reference wraps its envs (src/rl_utils.py:453, SB3 defaults)."""
@@ -197,9 +274,7 @@ class TrainOps:
         t2 = check(self, who, "ret", up(ret), dtypes=dt, shape=(T, self.n), rule=contiguous, optional=True, exc=ValueError)
         a2 = torch.empty_like(r2) if a2 is None else a2
         t2 = torch.empty_like(r2) if t2 is None else t2
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_gae(self._h, _ptr(r2), _ptr(v2), _ptr(d2), _ptr(last_values), T, _out_code(torch, r2.dtype),
-                                      float(gamma), float(gae_lambda), _ptr(a2), _ptr(t2), self._stream()))
+        self._call("ptg_gae", _ptr(r2), _ptr(v2), _ptr(d2), _ptr(last_values), T, _out_code(torch, r2.dtype), float(gamma), float(gae_lambda), _ptr(a2), _ptr(t2))
         return (a2[0], t2[0]) if one else (a2, t2)
 
     # ------------------------------------------------------------------ RolloutBuffer.get on the device
@@ -241,11 +316,10 @@ class TrainOps:
             if obs is not None and obs_out is None:
                 obs_out = torch.empty((B, F), dtype=obs.dtype, device=self.device)
             outs = [torch.empty((B,), dtype=x.dtype, device=self.device) for x in columns] if columns_out is None else list(columns_out)
-            k = len(columns)
-            size = (C.c_int32 * max(k, 1))(*[x.element_size() for x in columns])
-            self._chk(self._L.ptg_minibatch(self._h, _ptr(idx), idx.element_size(), B, T, _ptr(obs), s_t, s_n, s_f, F,
-                                            obs.element_size() if obs is not None else 0, _ptr(obs_out),
-                                            k, _ptr(columns), size, _ptr(outs), self._stream()))
+        k = len(columns)
+        size = (C.c_int32 * max(k, 1))(*[x.element_size() for x in columns])
+        self._call("ptg_minibatch", _ptr(idx), idx.element_size(), B, T, _ptr(obs), s_t, s_n, s_f, F, obs.element_size() if obs is not None else 0,
+                   _ptr(obs_out), k, _ptr(columns), size, _ptr(outs))
         return obs_out, outs
 
     def minibatches(self, perm, batch_size, obs=None, columns=()):
@@ -318,9 +392,8 @@ class TrainOps:
             check(self, who, f"column {c}", x, dtypes=(storage.col_rings[c].dtype,), shape=(T, self.n), rule=contiguous)
         check(self, who, "done", done, sizes=(1,), shape=(T, self.n), rule=contiguous, optional=True)
         src = _ptr([None if c == done_col else x for c, x in enumerate(columns)])
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_replay_add(self._h, C.byref(d), _ptr(prev_obs), _ptr(obs), obs.stride(0), obs.stride(1), obs.stride(2),
-                                             _ptr(final_obs), _ptr(done), done_col, len(columns), src, T, self._stream()))
+        self._call("ptg_replay_add", C.byref(d), _ptr(prev_obs), _ptr(obs), obs.stride(0), obs.stride(1), obs.stride(2), _ptr(final_obs), _ptr(done), done_col,
+                   len(columns), src, T)
 
     def replay_sample(self, storage, batch_size=None, idx=None, seed=0, want_obs=True, want_next=True, want_cols=None, norm_col=-1,
                       want_idx=False, out=None):
@@ -369,14 +442,13 @@ class TrainOps:
             raise ValueError("replay_sample: norm_col names a column without an output")
         if norm_col >= 0 and storage.col_rings[norm_col].dtype != self.out_dtype:
             raise TypeError(f"replay_sample: the reward column is {storage.col_rings[norm_col].dtype}, the engine normalises {self.out_dtype}")
-        with torch.cuda.device(self.device):
-            if out is None:
+        if out is None:
+            with torch.cuda.device(self.device):
                 mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
                 o0, o1 = mk((B, F), ring_dt) if want_obs else None, mk((B, F), ring_dt) if want_next else None
                 outs = [mk((B,), x.dtype) if w else None for x, w in zip(storage.col_rings, want_cols)]
                 io = mk((B,), torch.int64) if want_idx else None
-            self._chk(self._L.ptg_replay_sample(self._h, C.byref(d), _ptr(idx), B, int(seed) & (2 ** 64 - 1), _ptr(o0), _ptr(o1), _ptr(outs),
-                                                norm_col, _ptr(io), self._stream()))
+        self._call("ptg_replay_sample", C.byref(d), _ptr(idx), B, int(seed) & (2 ** 64 - 1), _ptr(o0), _ptr(o1), _ptr(outs), norm_col, _ptr(io))
         return o0, o1, outs, io
 
     # ------------------------------------------------------------------ the action head while collecting
@@ -393,8 +465,8 @@ class TrainOps:
     def _act_outputs(self, who, kind, out, specs):
         """the output tensors of a head: out's (checked) or fresh ones; specs = [(field, wanted, dtype)] in the namedtuple's order"""
         torch = self._torch
-        if out is not None and (not isinstance(out, tuple) or len(out) != len(specs)):
-            raise ValueError(f"{who}: out must be the {kind.__name__} of an earlier call")
+        if out is not None:
+            _out_tuple(self, who, out, kind, stats=False)
         res = []
         for k, (name, wanted, dt) in enumerate(specs):
             x = None if out is None else out[k]
@@ -439,8 +511,7 @@ class TrainOps:
         head.act_dev, head.logp_dev, head.ent_dev = _ptr(res.actions), _ptr(getattr(res, "log_prob", None)), _ptr(getattr(res, "entropy", None))
         head.raw_dev = _ptr(getattr(res, "raw", None))
         head.act_kind = self._action_kind(res.actions)
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_act(self._h, C.byref(head), self._stream()))
+        self._call("ptg_act", C.byref(head))
         return res
 
     def act_categorical(self, logits, counter, seed=0, deterministic=False, out=None, want_logp=True, want_entropy=True, act_dtype=None):
@@ -517,11 +588,7 @@ class TrainOps:
     # ------------------------------------------------------------------ the loss of a minibatch and its gradients
     def policy_loss_workspace(self, batch):
         """the device scratch of policy_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
-        nbytes = self._L.ptg_policy_loss_workspace(int(batch))
-        if nbytes < 0:
-            raise ValueError(f"policy_loss_workspace: batch must be >= 1, got {batch}")
-        with self._torch.cuda.device(self.device):
-            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+        return self._loss_workspace("policy_loss", batch)
 
     def policy_loss(self, kind, head_input, values, actions, old_log_prob, advantages, returns, *, clip_range=None, clip_range_vf=None,
                     ent_coef=0.0, vf_coef=0.5, normalize_advantage=None, old_values=None, log_std=None, out=None, workspace=None):
@@ -542,9 +609,8 @@ class TrainOps:
         if kind not in ("ppo", "a2c"):
             raise ValueError(f"{who}: kind must be 'ppo' or 'a2c', got {kind!r}")
         ppo, gauss = kind == "ppo", log_std is not None
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
         if gauss:                                           # the means [B] or [B, 1]
-            x = check(self, who, "head_input (the means, with log_std)", column(head_input), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
+            x = check(self, who, "head_input (the means, with log_std)", _column(self, head_input), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
             (B,), A = x.shape, 0
         else:
             x = check(self, who, "head_input (logits; or means with log_std)", head_input, dtypes=(torch.float32, torch.float64), shape=(None, None), rule=rows)
@@ -555,7 +621,7 @@ class TrainOps:
             raise ValueError(f"{who}: an empty batch, head_input has shape {tuple(head_input.shape)}")
         dt = (x.dtype,)
         check(self, who, "log_std", log_std, dtypes=dt, numel=1, optional=True)
-        values = check(self, who, "values", column(values), dtypes=dt, shape=(B,), rule=step)
+        values = check(self, who, "values", _column(self, values), dtypes=dt, shape=(B,), rule=step)
         if clip_range_vf is not None and old_values is None:
             raise ValueError(f"{who}: clip_range_vf needs old_values")
         if ppo and old_log_prob is None:
@@ -572,22 +638,15 @@ class TrainOps:
         if normalize_advantage is None:
             normalize_advantage = ppo
         if out is not None:
-            if not isinstance(out, tuple) or len(out) != 4:
-                raise ValueError(f"{who}: out must be the PolicyLoss of an earlier call")
-            stats, g_in, g_val, g_ls = out
+            stats, g_in, g_val, g_ls = _out_tuple(self, who, out, PolicyLoss, stats=False)
             if not gauss and g_ls is not None:
                 raise ValueError(f"{who}: out.grad_log_std given, but the categorical head has no log_std")
             check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
-            g_in = check(self, who, "out.grad_input", column(g_in) if gauss else g_in, dtypes=dt, shape=x.shape, rule=step if gauss else rows, exc=ValueError)
+            g_in = check(self, who, "out.grad_input", _column(self, g_in) if gauss else g_in, dtypes=dt, shape=x.shape, rule=step if gauss else rows, exc=ValueError)
             check(self, who, "out.grad_values", g_val, dtypes=dt, shape=(B,), rule=step, exc=ValueError)
             if gauss:
                 check(self, who, "out.grad_log_std", g_ls, dtypes=dt, shape=(1,), exc=ValueError)
-        if workspace is not None:
-            check(self, who, f"workspace (policy_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
-            if workspace.numel() < self._L.ptg_policy_loss_workspace(B):
-                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_policy_loss_workspace(B)}")
-        else:
-            workspace = self.policy_loss_workspace(B)
+        workspace = self._take_workspace(who, B, workspace)
         if out is None:
             with torch.cuda.device(self.device):
                 stats = torch.empty(8, dtype=torch.float64, device=self.device)
@@ -604,18 +663,13 @@ class TrainOps:
                          ent_coef=float(ent_coef), vf_coef=float(vf_coef), stats_dev=_ptr(stats), grad_in_dev=_ptr(g_in),
                          g_s_n=max(g_in.stride(0), A, 1), grad_val_dev=_ptr(g_val), gv_s_n=max(g_val.stride(0), 1),
                          grad_log_std_dev=_ptr(g_ls if gauss else None), ws_dev=_ptr(workspace))
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_policy_loss(self._h, C.byref(d), self._stream()))
+        self._call("ptg_policy_loss", C.byref(d))
         return PolicyLoss(stats, g_in, g_val, g_ls)
 
     # ------------------------------------------------------------------ the TD loss of a replay batch and its gradients
     def td_loss_workspace(self, batch):
         """the device scratch of td_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
-        nbytes = self._L.ptg_td_loss_workspace(int(batch))
-        if nbytes < 0:
-            raise ValueError(f"td_loss_workspace: batch must be in [1, 2^31], got {batch}")
-        with self._torch.cuda.device(self.device):
-            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+        return self._loss_workspace("td_loss", batch)
 
     def td_loss(self, kind, q, next_q, rewards, dones, gamma, *, actions=None, next_log_prob=None, ent_coef=None, log_ent_coef=None,
                 want_target=False, out=None, workspace=None):
@@ -641,7 +695,6 @@ class TrainOps:
             raise ValueError(f"{who}: kind must be 'dqn', 'td3' or 'sac', got {kind!r}")
         dqn, sac = kind == "dqn", kind == "sac"
         floats = (torch.float32, torch.float64)
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
         if dqn:
             x = check(self, who, "q", q, dtypes=floats, shape=(None, None), rule=rows)
             B, A = x.shape
@@ -656,15 +709,15 @@ class TrainOps:
             if not 1 <= len(q) <= _lib.TD_MAX_CRITICS or len(next_q) != len(q):
                 raise ValueError(f"{who}: q and next_q must hold the same number of critics, 1 to {_lib.TD_MAX_CRITICS}, got {len(q)} and {len(next_q)}")
             A = 0
-            x = check(self, who, "q[0]", column(q[0]), dtypes=floats, shape=(None,), rule=step)
+            qs = _critic_columns(self, who, "q", q, floats)
+            x = qs[0]
             (B,), dt = x.shape, (x.dtype,)
-            qs = [x] + [check(self, who, f"q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step) for k, t in enumerate(q) if k > 0]
-            nqs = [check(self, who, f"next_q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step) for k, t in enumerate(next_q)]
+            nqs = _critic_columns(self, who, "next_q", next_q, dt, B)
         if B < 1:
             raise ValueError(f"{who}: an empty batch, q has shape {tuple(x.shape)}")
         K = len(qs)
-        rewards = check(self, who, "rewards", column(rewards), dtypes=floats, shape=(B,), rule=contiguous)
-        dones = check(self, who, "dones", column(dones), dtypes=floats, shape=(B,), rule=contiguous)
+        rewards = check(self, who, "rewards", _column(self, rewards), dtypes=floats, shape=(B,), rule=contiguous)
+        dones = check(self, who, "dones", _column(self, dones), dtypes=floats, shape=(B,), rule=contiguous)
         if dqn != (actions is not None):
             raise ValueError(f"{who}: actions go with kind 'dqn' and with no other")
         if sac != (next_log_prob is not None):
@@ -673,41 +726,27 @@ class TrainOps:
             raise ValueError(f"{who}: kind 'sac' takes exactly one of ent_coef and log_ent_coef, the other kinds neither")
         if not np.isfinite(float(gamma)):
             raise ValueError(f"{who}: gamma must be finite, got {gamma}")
-        actions = check(self, who, "actions", column(actions), dtypes=(torch.int32, torch.int64), shape=(B,), rule=contiguous, optional=True)
-        next_log_prob = check(self, who, "next_log_prob", column(next_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
-        alpha_dev = None
-        if log_ent_coef is not None or torch.is_tensor(ent_coef):
-            alpha_dev = check(self, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
-                              dtypes=(torch.float64,), numel=1)
-        alpha = float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+        actions = check(self, who, "actions", _column(self, actions), dtypes=(torch.int32, torch.int64), shape=(B,), rule=contiguous, optional=True)
+        next_log_prob = check(self, who, "next_log_prob", _column(self, next_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        alpha_dev, alpha = _alpha_arg(self, who, ent_coef, log_ent_coef)
         if out is not None:
-            if not isinstance(out, tuple) or len(out) != 3:
-                raise ValueError(f"{who}: out must be the TdLoss of an earlier call")
-            stats, g_q, target = out
-            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            stats, g_q, target = _out_tuple(self, who, out, TdLoss)
             if dqn:
                 gs = [check(self, who, "out.grad_q", g_q, dtypes=dt, shape=(B, A), rule=rows, exc=ValueError)]
             else:
                 if not isinstance(g_q, (list, tuple)) or len(g_q) != K:
                     raise ValueError(f"{who}: out.grad_q must be a list of {K} tensors")
-                gs = [check(self, who, f"out.grad_q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step, exc=ValueError) for k, t in enumerate(g_q)]
+                gs = _critic_columns(self, who, "out.grad_q", g_q, dt, B, exc=ValueError)
             if want_target and target is None:
                 raise ValueError(f"{who}: want_target, but out.target is None")
             check(self, who, "out.target", target, dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
-            starts = [t.data_ptr() for t in gs + qs + nqs + ([target] if target is not None else [])]
-            if len(set(starts)) != len(starts):             # the cheap half of "outputs must not overlap": one tensor given twice
-                raise ValueError(f"{who}: two of out.grad_q, out.target, q and next_q start at the same address; the outputs must not overlap each other or the inputs")
-        if workspace is not None:
-            check(self, who, f"workspace (td_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
-            if workspace.numel() < self._L.ptg_td_loss_workspace(B):
-                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_td_loss_workspace(B)}")
-        else:
-            workspace = self.td_loss_workspace(B)
+            _no_tensor_twice(who, gs + qs + nqs + ([target] if target is not None else []), "out.grad_q, out.target, q and next_q")
+        workspace = self._take_workspace(who, B, workspace)
         if out is None:
             with torch.cuda.device(self.device):
                 stats = torch.empty(8, dtype=torch.float64, device=self.device)
                 g_q = [torch.empty(tuple(t.shape), dtype=x.dtype, device=self.device) for t in ([q] if dqn else q)]
-                gs = g_q if dqn else [column(t) for t in g_q]
+                gs = g_q if dqn else [_column(self, t) for t in g_q]
                 g_q = g_q[0] if dqn else g_q
                 target = torch.empty(B, dtype=x.dtype, device=self.device) if want_target else None
         d = _lib.PtgTd(kind=_lib.TD_DQN if dqn else _lib.TD_CRITICS,
@@ -723,18 +762,13 @@ class TrainOps:
             d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), least)
             d.next_q_dev[k], d.next_s_n[k] = nqs[k].data_ptr(), max(nqs[k].stride(0), least)
             d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), least)
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_td_loss(self._h, C.byref(d), self._stream()))
+        self._call("ptg_td_loss", C.byref(d))
         return TdLoss(stats, g_q, target)
 
     # ------------------------------------------------------------------ TQC's quantile-Huber critic loss and its gradients
     def quantile_loss_workspace(self, batch):
         """the device scratch of quantile_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
-        nbytes = self._L.ptg_quantile_loss_workspace(int(batch))
-        if nbytes < 0:
-            raise ValueError(f"quantile_loss_workspace: batch must be in [1, 2^31], got {batch}")
-        with self._torch.cuda.device(self.device):
-            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+        return self._loss_workspace("quantile_loss", batch)
 
     def _quantile_views(self, who, name, x, dtypes, B=None, K=None, Q=None, exc=TypeError):
         """a [B, K, Q] tensor or a list of K [B, Q] tensors -> the K checked [B, Q] views"""
@@ -774,16 +808,15 @@ class TrainOps:
         torch = self._torch
         who = "quantile_loss"
         floats = (torch.float32, torch.float64)
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
         as_list = isinstance(quantiles, (list, tuple))
         cur = self._quantile_views(who, "quantiles", quantiles, floats)
         (B, Q), K, dt = cur[0].shape, len(cur), (cur[0].dtype,)
         if B < 1 or not 1 <= Q <= _lib.QL_MAX_QUANTILES:
             raise ValueError(f"{who}: quantiles need B >= 1 and 1 <= Q <= {_lib.QL_MAX_QUANTILES}, got B = {B}, Q = {Q}")
         nxt = self._quantile_views(who, "next_quantiles", next_quantiles, dt, B, K, Q)
-        rewards = check(self, who, "rewards", column(rewards), dtypes=floats, shape=(B,), rule=contiguous)
-        dones = check(self, who, "dones", column(dones), dtypes=floats, shape=(B,), rule=contiguous)
-        next_log_prob = check(self, who, "next_log_prob", column(next_log_prob), dtypes=dt, shape=(B,), rule=contiguous)
+        rewards = check(self, who, "rewards", _column(self, rewards), dtypes=floats, shape=(B,), rule=contiguous)
+        dones = check(self, who, "dones", _column(self, dones), dtypes=floats, shape=(B,), rule=contiguous)
+        next_log_prob = check(self, who, "next_log_prob", _column(self, next_log_prob), dtypes=dt, shape=(B,), rule=contiguous)
         drop = top_quantiles_to_drop_per_net
         if isinstance(drop, bool) or not isinstance(drop, (int, np.integer)):
             raise TypeError(f"{who}: top_quantiles_to_drop_per_net must be an int, got {type(drop).__name__}")
@@ -794,40 +827,21 @@ class TrainOps:
             raise ValueError(f"{who}: exactly one of ent_coef and log_ent_coef")
         if not np.isfinite(float(gamma)):
             raise ValueError(f"{who}: gamma must be finite, got {gamma}")
-        alpha_dev = None
-        if log_ent_coef is not None or torch.is_tensor(ent_coef):
-            alpha_dev = check(self, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
-                              dtypes=(torch.float64,), numel=1)
-        alpha = float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+        alpha_dev, alpha = _alpha_arg(self, who, ent_coef, log_ent_coef)
         if out is not None:
-            if not isinstance(out, tuple) or len(out) != 3:
-                raise ValueError(f"{who}: out must be the QuantileLoss of an earlier call")
-            stats, g_q, target = out
-            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            stats, g_q, target = _out_tuple(self, who, out, QuantileLoss)
             if isinstance(g_q, (list, tuple)) != as_list:
                 raise ValueError(f"{who}: out.grad_quantiles must be a {'list of ' + str(K) + ' tensors' if as_list else 'tensor'}, as the quantiles are")
             gs = self._quantile_views(who, "out.grad_quantiles", g_q, dt, B, K, Q, exc=ValueError)
             if want_target and target is None:
                 raise ValueError(f"{who}: want_target, but out.target is None")
             check(self, who, "out.target", target, dtypes=dt, shape=(B, M), rule=contiguous, optional=True, exc=ValueError)
-            starts = [t.data_ptr() for t in gs + cur + nxt + ([target] if target is not None else [])]
-            if len(set(starts)) != len(starts):             # the cheap half of "outputs must not overlap": one tensor given twice
-                raise ValueError(f"{who}: two of out.grad_quantiles, out.target, quantiles and next_quantiles start at the same address; the outputs must not "
-                                 "overlap each other or the inputs")
-        if workspace is not None:
-            check(self, who, f"workspace (quantile_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
-            if workspace.numel() < self._L.ptg_quantile_loss_workspace(B):
-                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_quantile_loss_workspace(B)}")
-        else:
-            workspace = self.quantile_loss_workspace(B)
+            _no_tensor_twice(who, gs + cur + nxt + ([target] if target is not None else []), "out.grad_quantiles, out.target, quantiles and next_quantiles")
+        workspace = self._take_workspace(who, B, workspace)
         if out is None:
             with torch.cuda.device(self.device):
                 stats = torch.empty(8, dtype=torch.float64, device=self.device)
-                if as_list:
-                    g_q = gs = [torch.empty((B, Q), dtype=dt[0], device=self.device) for _ in range(K)]
-                else:
-                    g_q = torch.empty((B, K, Q), dtype=dt[0], device=self.device)
-                    gs = [g_q[:, k] for k in range(K)]
+                g_q, gs = self._fresh_like_quantiles(as_list, B, K, Q, dt[0])
                 target = torch.empty((B, M), dtype=dt[0], device=self.device) if want_target else None
         d = _lib.PtgQl(flags=_lib.QL_LOG_ALPHA if log_ent_coef is not None else 0, n_critics=K, n_quantiles=Q, n_drop=int(drop),
                        q_dtype=_out_code(torch, dt[0]), rew_dtype=_out_code(torch, rewards.dtype), done_dtype=_out_code(torch, dones.dtype), batch=B,
@@ -837,18 +851,16 @@ class TrainOps:
             d.cur_dev[k], d.cur_s_n[k] = cur[k].data_ptr(), max(cur[k].stride(0), Q)
             d.next_dev[k], d.next_s_n[k] = nxt[k].data_ptr(), max(nxt[k].stride(0), Q)
             d.grad_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), Q)
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_quantile_loss(self._h, C.byref(d), self._stream()))
+        self._call("ptg_quantile_loss", C.byref(d))
         return QuantileLoss(stats, g_q, target)
 
     # ------------------------------------------------------------------ the training-time actor head: SAC / TQC rsample, TD3's target action
     def _rs_rows(self, who, mean, log_std):
         """mean and log_std [B] / [B, 1] of one float dtype, any stride >= 1 -> their [B] views and B"""
         torch = self._torch
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
-        m = check(self, who, "mean", column(mean), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
+        m = check(self, who, "mean", _column(self, mean), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
         B = m.shape[0]
-        ls = check(self, who, "log_std", column(log_std), dtypes=(m.dtype,), shape=(B,), rule=step) if log_std is not None else None
+        ls = check(self, who, "log_std", _column(self, log_std), dtypes=(m.dtype,), shape=(B,), rule=step) if log_std is not None else None
         if B < 1:
             raise ValueError(f"{who}: an empty batch, mean has shape {tuple(mean.shape)}")
         return m, ls, B
@@ -864,18 +876,15 @@ class TrainOps:
         non-finite mean or a NaN log_std gives NaN outputs and PTG_E_NONFINITE at the next sync()."""
         torch = self._torch
         who = "rsample"
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t
         m, ls, B = self._rs_rows(who, mean, log_std)
         if ls is None:
             raise TypeError(f"{who}: log_std must be a tensor, got NoneType")
         counter = self._act_counter(who, counter, deterministic)
         if out is not None:
-            if not isinstance(out, tuple) or len(out) != 3:
-                raise ValueError(f"{who}: out must be the RSample of an earlier call")
-            act, lp, noise = out
-            check(self, who, "out.actions", column(act), dtypes=(m.dtype,), shape=(B,), rule=contiguous, exc=ValueError)
-            check(self, who, "out.log_prob", column(lp), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
-            check(self, who, "out.noise", column(noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            act, lp, noise = _out_tuple(self, who, out, RSample, stats=False)
+            check(self, who, "out.actions", _column(self, act), dtypes=(m.dtype,), shape=(B,), rule=contiguous, exc=ValueError)
+            check(self, who, "out.log_prob", _column(self, lp), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "out.noise", _column(self, noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
         else:
             with torch.cuda.device(self.device):
                 act, lp = (torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device) for _ in range(2))
@@ -883,8 +892,7 @@ class TrainOps:
         d = _lib.PtgRs(kind=_lib.RS_SQUASH, flags=_lib.RS_DETERMINISTIC if deterministic else 0, q_dtype=_out_code(torch, m.dtype), batch=B,
                        mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1), log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1),
                        seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), act_dev=_ptr(act), logp_dev=_ptr(lp), noise_dev=_ptr(noise))
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_rsample(self._h, C.byref(d), self._stream()))
+        self._call("ptg_rsample", C.byref(d))
         return RSample(act, lp, noise)
 
     def rsample_backward(self, mean, log_std, noise, grad_actions, grad_log_prob, out=None):
@@ -895,32 +903,28 @@ class TrainOps:
         a non-finite input row gives NaN gradients and PTG_E_NONFINITE at the next sync()."""
         torch = self._torch
         who = "rsample_backward"
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t
         m, ls, B = self._rs_rows(who, mean, log_std)
         if ls is None:
             raise TypeError(f"{who}: log_std must be a tensor, got NoneType")
         dt = (m.dtype,)
-        noise = check(self, who, "noise", column(noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous)
-        ga = check(self, who, "grad_actions", column(grad_actions), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
-        gl = check(self, who, "grad_log_prob", column(grad_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        noise = check(self, who, "noise", _column(self, noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous)
+        ga = check(self, who, "grad_actions", _column(self, grad_actions), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        gl = check(self, who, "grad_log_prob", _column(self, grad_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
         if ga is None and gl is None:
             raise ValueError(f"{who}: grad_actions and grad_log_prob are both None")
         if out is not None:
-            if not isinstance(out, tuple) or len(out) != 2:
-                raise ValueError(f"{who}: out must be the RSampleGrad of an earlier call")
-            gm, gs = out
-            gm1 = check(self, who, "out.grad_mean", column(gm), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
-            gs1 = check(self, who, "out.grad_log_std", column(gs), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            gm, gs = _out_tuple(self, who, out, RSampleGrad, stats=False)
+            gm1 = check(self, who, "out.grad_mean", _column(self, gm), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            gs1 = check(self, who, "out.grad_log_std", _column(self, gs), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
         else:
             with torch.cuda.device(self.device):
                 gm = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
                 gs = torch.empty(tuple(log_std.shape), dtype=m.dtype, device=self.device)
-            gm1, gs1 = column(gm), column(gs)
+            gm1, gs1 = _column(self, gm), _column(self, gs)
         d = _lib.PtgRs(kind=_lib.RS_SQUASH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
                        log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1), noise_dev=_ptr(noise), grad_act_dev=_ptr(ga), grad_logp_dev=_ptr(gl),
                        grad_mean_dev=_ptr(gm1), gm_s_n=max(gm1.stride(0), 1), grad_log_std_dev=_ptr(gs1), gl_s_n=max(gs1.stride(0), 1))
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_rsample_backward(self._h, C.byref(d), self._stream()))
+        self._call("ptg_rsample_backward", C.byref(d))
         return RSampleGrad(gm, gs)
 
     def smooth_target_action(self, mean, counter, noise_std, noise_clip, clip=(-1.0, 1.0), seed=0, out=None):
@@ -930,7 +934,6 @@ class TrainOps:
         The counter advances by one on the device.  No synchronisation; a non-finite mean gives NaN and PTG_E_NONFINITE at the next sync()."""
         torch = self._torch
         who = "smooth_target_action"
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t
         m, _, B = self._rs_rows(who, mean, None)
         counter = self._act_counter(who, counter, False)
         sd, c, lo, hi = float(noise_std), float(noise_clip), float(clip[0]), float(clip[1])
@@ -938,24 +941,19 @@ class TrainOps:
             raise ValueError(f"{who}: noise_std must be finite and >= 0 and noise_clip >= 0, got {noise_std} and {noise_clip}")
         if not lo <= hi:
             raise ValueError(f"{who}: clip {clip} is not an interval")
-        check(self, who, "out", column(out), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+        check(self, who, "out", _column(self, out), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
         if out is None:
             with torch.cuda.device(self.device):
                 out = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
         d = _lib.PtgRs(kind=_lib.RS_SMOOTH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
                        seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), noise_std=sd, noise_clip=c, clip_lo=lo, clip_hi=hi, act_dev=_ptr(out))
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_rsample(self._h, C.byref(d), self._stream()))
+        self._call("ptg_rsample", C.byref(d))
         return out
 
     # ------------------------------------------------------------------ the actor and entropy-coefficient losses and their gradients
     def actor_loss_workspace(self, batch):
         """the device scratch of actor_loss for a batch of this size (a uint8 tensor; reuse it across calls of up to that size)"""
-        nbytes = self._L.ptg_actor_loss_workspace(int(batch))
-        if nbytes < 0:
-            raise ValueError(f"actor_loss_workspace: batch must be in [1, 2^31], got {batch}")
-        with self._torch.cuda.device(self.device):
-            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+        return self._loss_workspace("actor_loss", batch)
 
     def actor_loss(self, kind, q=None, log_prob=None, ent_coef=None, log_ent_coef=None, target_entropy=None, out=None, workspace=None):
         """Enqueue, on the current stream, the actor loss of SB3's SAC.train (kind "sac"), sb3_contrib's TQC.train ("tqc") or TD3.train
@@ -977,7 +975,6 @@ class TrainOps:
         if kind not in ("sac", "tqc", "td3", "ent_coef"):
             raise ValueError(f"{who}: kind must be 'sac', 'tqc', 'td3' or 'ent_coef', got {kind!r}")
         floats = (torch.float32, torch.float64)
-        column = lambda t: t[:, 0] if _dims(self, t) == 2 and t.shape[1] == 1 else t       # [B, 1] -> [B]
         only, td3 = kind == "ent_coef", kind == "td3"
         as_list = isinstance(q, (list, tuple))
         K, Q, dt, B, qs = 0, 1, floats, None, []
@@ -998,16 +995,13 @@ class TrainOps:
                 q_list = list(q)
             if not 1 <= len(q_list) <= (1 if td3 else _lib.TD_MAX_CRITICS):
                 raise ValueError(f"{who}: q must hold {'one critic' if td3 else f'1 to {_lib.TD_MAX_CRITICS} critics'}, got {len(q_list)}")
-            for k, t in enumerate(q_list):
-                qs.append(check(self, who, f"q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step))
-                if k == 0:
-                    dt, (B,) = (qs[0].dtype,), qs[0].shape
-            K = len(qs)
+            qs = _critic_columns(self, who, "q", q_list, floats)
+            dt, (B,), K = (qs[0].dtype,), qs[0].shape, len(qs)
         if td3 and not (log_prob is None and ent_coef is None and log_ent_coef is None and target_entropy is None):
             raise ValueError(f"{who}: kind 'td3' takes q alone")
         if not td3 and log_prob is None:
             raise ValueError(f"{who}: kind {kind!r} needs log_prob")
-        lp = check(self, who, "log_prob", column(log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        lp = check(self, who, "log_prob", _column(self, log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
         if only:
             B, dt = lp.shape[0], (lp.dtype,)
         if B < 1:
@@ -1021,17 +1015,10 @@ class TrainOps:
         if target_entropy is not None and not np.isfinite(float(target_entropy)):
             raise ValueError(f"{who}: target_entropy must be finite, got {target_entropy}")
         ec = target_entropy is not None
-        alpha_dev = None
-        if log_ent_coef is not None or torch.is_tensor(ent_coef):
-            alpha_dev = check(self, who, "log_ent_coef" if log_ent_coef is not None else "a tensor ent_coef", log_ent_coef if log_ent_coef is not None else ent_coef,
-                              dtypes=(torch.float64,), numel=1)
-        alpha = float(ent_coef) if ent_coef is not None and alpha_dev is None else 0.0
+        alpha_dev, alpha = _alpha_arg(self, who, ent_coef, log_ent_coef)
         g_q = gs = g_lp = g_la = None
         if out is not None:
-            if not isinstance(out, tuple) or len(out) != 4:
-                raise ValueError(f"{who}: out must be the ActorLoss of an earlier call")
-            stats, g_q, g_lp, g_la = out
-            check(self, who, "out.stats", stats, dtypes=(torch.float64,), shape=(8,), rule=contiguous, exc=ValueError)
+            stats, g_q, g_lp, g_la = _out_tuple(self, who, out, ActorLoss)
             if only:
                 if g_q is not None:
                     raise ValueError(f"{who}: out.grad_q given, but kind 'ent_coef' reads no q")
@@ -1044,48 +1031,35 @@ class TrainOps:
                 g_list = [g_q] if td3 and not as_list else g_q
                 if not isinstance(g_list, (list, tuple)) or len(g_list) != K:
                     raise ValueError(f"{who}: out.grad_q must be {'a tensor' if td3 and not as_list else f'a list of {K} tensors'}")
-                gs = [check(self, who, f"out.grad_q[{k}]", column(t), dtypes=dt, shape=(B,), rule=step, exc=ValueError) for k, t in enumerate(g_list)]
+                gs = _critic_columns(self, who, "out.grad_q", g_list, dt, B, exc=ValueError)
             if g_lp is not None and (td3 or only):
                 raise ValueError(f"{who}: out.grad_log_prob given, but kind {kind!r} has no entropy term")
             if g_la is not None and not ec:
                 raise ValueError(f"{who}: out.grad_log_ent_coef given without target_entropy")
-            check(self, who, "out.grad_log_prob", column(g_lp), dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "out.grad_log_prob", _column(self, g_lp), dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
             check(self, who, "out.grad_log_ent_coef", g_la, dtypes=(torch.float64,), shape=(1,), optional=True, exc=ValueError)
-            starts = [t.data_ptr() for t in list(gs) + qs + [x for x in (lp, g_lp) if x is not None]]
-            if len(set(starts)) != len(starts):             # the cheap half of "outputs must not overlap": one tensor given twice
-                raise ValueError(f"{who}: two of out.grad_q, out.grad_log_prob, q and log_prob start at the same address; the outputs must not overlap each "
-                                 "other or the inputs")
-        if workspace is not None:
-            check(self, who, f"workspace (actor_loss_workspace({B}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
-            if workspace.numel() < self._L.ptg_actor_loss_workspace(B):
-                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {self._L.ptg_actor_loss_workspace(B)}")
-        else:
-            workspace = self.actor_loss_workspace(B)
+            _no_tensor_twice(who, list(gs) + qs + [x for x in (lp, g_lp) if x is not None], "out.grad_q, out.grad_log_prob, q and log_prob")
+        workspace = self._take_workspace(who, B, workspace)
         if out is None:
             with torch.cuda.device(self.device):
                 mk = lambda shape, d=dt[0]: torch.empty(tuple(shape), dtype=d, device=self.device)
                 stats = mk((8,), torch.float64)
                 if kind == "tqc":
-                    if as_list:
-                        g_q = gs = [mk((B, Q)) for _ in range(K)]
-                    else:
-                        g_q = mk((B, K, Q))
-                        gs = [g_q[:, k] for k in range(K)]
+                    g_q, gs = self._fresh_like_quantiles(as_list, B, K, Q, dt[0])
                 elif not only:
                     g_list = [mk(t.shape) for t in (q if as_list else [q])]
-                    gs, g_q = [column(t) for t in g_list], (g_list if as_list else g_list[0])
+                    gs, g_q = [_column(self, t) for t in g_list], (g_list if as_list else g_list[0])
                 g_lp = mk(log_prob.shape) if not (td3 or only) else None
                 g_la = mk((1,), torch.float64) if ec else None
         flags = (0 if td3 or only else _lib.AL_ENTROPY) | (_lib.AL_LOG_ALPHA if log_ent_coef is not None else 0) | (_lib.AL_ENT_COEF if ec else 0)
         d = _lib.PtgAl(kind=_lib.AL_ALPHA_ONLY if only else (_lib.AL_MIN if kind == "sac" else _lib.AL_MEAN), flags=flags, n_critics=K, n_quantiles=Q,
                        q_dtype=_out_code(torch, dt[0]), batch=B, logp_dev=_ptr(lp), alpha_dev=_ptr(alpha_dev), alpha=alpha,
-                       target_entropy=float(target_entropy) if ec else 0.0, stats_dev=_ptr(stats), grad_logp_dev=_ptr(column(g_lp) if g_lp is not None else None),
+                       target_entropy=float(target_entropy) if ec else 0.0, stats_dev=_ptr(stats), grad_logp_dev=_ptr(_column(self, g_lp)),
                        grad_log_alpha_dev=_ptr(g_la), ws_dev=_ptr(workspace))
         for k in range(K):
             d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), Q)
             d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), Q)
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_actor_loss(self._h, C.byref(d), self._stream()))
+        self._call("ptg_actor_loss", C.byref(d))
         return ActorLoss(stats, g_q, g_lp, g_la)
 
     # ------------------------------------------------------------------ the inference forward of an MLP
@@ -1168,8 +1142,7 @@ class TrainOps:
                         out_s_n=row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
         for l in range(n):
             d.w_dev[l], d.w_s_n[l], d.b_dev[l], d.width[l] = weights[l].data_ptr(), row_stride(weights[l]), biases[l].data_ptr(), widths[l]
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_mlp_forward(self._h, C.byref(d), self._stream()))
+        self._call("ptg_mlp_forward", C.byref(d))
         hidden = None
         if keep_hidden:
             hidden, off = [], 0
@@ -1311,8 +1284,7 @@ class TrainOps:
         d.beta1, d.beta2, d.eps, d.alpha = b1, b2, float(eps), float(alpha)
         d.tau = float(tau) if tau is not None else 0.0
         d.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
-        with torch.cuda.device(self.device):
-            self._chk(self._L.ptg_optim_step(self._h, C.byref(d), self._stream()))
+        self._call("ptg_optim_step", C.byref(d))
 
     def polyak_update(self, params, targets, tau, plan=None):
         """Enqueue, on the current stream, SB3's polyak_update(params, targets, tau) for lists that no optimiser steps -- DQN's hard
@@ -1331,6 +1303,5 @@ class TrainOps:
             raise ValueError(f"{who}: the plan was built for other tensors")
         d = self._optim_desc(plan, _lib.OPTIM_POLYAK, 0)
         d.tau = float(tau)
-        with self._torch.cuda.device(self.device):
-            self._chk(self._L.ptg_optim_step(self._h, C.byref(d), self._stream()))
+        self._call("ptg_optim_step", C.byref(d))
         return plan

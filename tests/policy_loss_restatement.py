@@ -128,7 +128,7 @@ def log_prob(head_input, actions, log_std=None):
 BS = [1, 2, 63, 64, 65, 203, 257, 4097]
 AS = [2, 5, 32]
 DTYPES = [np.float32, np.float64]
-B_BIG = 70001             # 274 blocks of 256 rows: k_pl_final's 256 threads each walk two partials (blocks t and t + 256: one lap boundary),
+B_BIG = 70001             # 274 blocks of 256 rows: k_loss_final's 256 threads each walk two partials (blocks t and t + 256: one lap boundary),
 #                           and k_vn_merge's 64 lanes five moment partials each (laps at 64, 128, 192, 256 blocks)
 CLIP, CLIP_VF, ENT_COEF, VF_COEF = 0.2, 0.3, 0.01, 0.5
 

@@ -394,6 +394,15 @@ def test_a_batch_that_crosses_the_partial_boundaries():
     assert worst <= 1.0 and e_rs <= 1.0 and e_z <= 1.0
 
 
+def test_thread_0_of_the_final_pass_adds_two_partials():
+    """the same 65 793 rows (256 * 257 + 1) in float32 with one critic, the smallest K of the sweeps, and a fresh workspace: thread 0 of
+    the final kernel adds the partials of blocks 0 and 256 before the block's tree"""
+    eng = _engine()
+    worst = _check_loss(eng, at.B_BIG, 1, 1, np.float32, False, "host")
+    print(f"B={at.B_BIG}, K=1, float32: means, max error / bound {worst:.4f}")
+    assert worst <= 1.0
+
+
 def test_two_runs_give_identical_bits():
     import torch
     eng = _engine()

@@ -233,6 +233,20 @@ def test_a_batch_that_crosses_the_partial_boundaries(kind):
     assert worst <= 1.0
 
 
+@pytest.mark.parametrize("kind", ["dqn", "td3"])
+def test_thread_0_of_the_final_pass_adds_two_partials(kind):
+    """65 793 rows = 256 * 257 + 1: more than 256 block partials, so thread 0 of the final kernel adds the partials of blocks 0 and 256
+    before the block's tree; the last block holds one row.  float32, the smallest A and K of the sweeps."""
+    eng = _engine()
+    B = 256 * 257 + 1
+    if kind == "dqn":
+        worst = _check_dqn(eng, tr.dqn_case(B, tr.AS[0], np.float32), False)
+    else:
+        worst = _check_critics(eng, tr.critics_case(B, tr.KS[0], np.float32), False, "td3")
+    print(f"{kind} B={B}: means, max error / tolerance {worst:.4f}")
+    assert worst <= 1.0
+
+
 def test_two_runs_give_identical_bits():
     import torch
     eng = _engine()

@@ -1,7 +1,9 @@
-"""The training-side wrappers of the engine (vn_*, gae, minibatch, replay_*, act_*, policy_loss) without a device: what every accepted
+"""The training-side wrappers of the engine (vn_*, gae, minibatch, replay_*, act_*, policy_loss, td_loss, quantile_loss, actor_loss,
+rsample, rsample_backward, smooth_target_action) without a device: what every accepted
 call passes to the library -- each scalar, each pointer as "which tensor's data_ptr()", the order of the library calls -- pinned in one
 table, and what the Python layer refuses, on CPU tensors through the engine shells of tests/helpers.py.  The marshalling table was
-written against the wrappers while they still lived in engine.py and holds unchanged for rl_ptg_amd/train_ops.py."""
+written against the wrappers while they still lived in engine.py and holds unchanged for rl_ptg_amd/train_ops.py; the entries of
+the ops that never lived there were rendered from train_ops.py before its repeated blocks became helpers."""
 import ctypes as C
 
 import numpy as np
@@ -356,6 +358,186 @@ def case_policy_loss_ppo_i32_out_views_of_one_tensor():
     return eng, dict(logits=x, values=val, actions=act, col=col, stats=out[0], grad_input=g, grad_values=g[:, A])
 
 
+def _views(prefix, xs):
+    """the K [B, Q] views of a stacked [B, K, Q] tensor (or the K tensors of a list) under the names <prefix>0, <prefix>1, ..."""
+    xs = xs if isinstance(xs, (list, tuple)) else [xs[:, k] for k in range(xs.shape[1])]
+    return {f"{prefix}{k}": x for k, x in enumerate(xs)}
+
+
+def case_td_loss_dqn_fresh_want_target():
+    import torch
+    eng = recording_engine(N)
+    B, A = 300, 4
+    wide = torch.zeros(B, A + 2)
+    q, nq = wide[:, 1:A + 1], torch.zeros(B, A)                              # 4 Q-values, row stride 6
+    act, rew, done = torch.zeros(B, dtype=torch.int64), torch.zeros(B, 1), torch.zeros(B, dtype=torch.float64)
+    r = eng.td_loss("dqn", q, nq, rew, done, 0.97, actions=act, want_target=True)
+    assert r.stats.shape == (8,) and r.stats.dtype == torch.float64 and r.grad_q.shape == (B, A) and r.target.shape == (B,) and r.target.dtype == torch.float32
+    return eng, dict(q=q, next_q=nq, actions=act, rewards=rew, dones=done, stats=r.stats, grad_q=r.grad_q, target=r.target)
+
+
+def case_td_loss_td3_critics_out_workspace():
+    import torch
+    eng = recording_engine(N)
+    B, f64 = 5, dict(dtype=torch.float64)
+    both, nboth = torch.zeros(B, 2, **f64), torch.zeros(B, 2, **f64)          # the columns of one [B, K] tensor: stride 2
+    qs, nqs = [both[:, 0], both[:, 1]], (nboth[:, :1], nboth[:, 1:])
+    rew, done = torch.zeros(B), torch.zeros(B, 1, **f64)
+    out = (torch.zeros(8, **f64), [torch.zeros(B, **f64), torch.zeros(B, 1, **f64)], torch.zeros(B, **f64))
+    ws = torch.zeros(4096, dtype=torch.uint8)
+    r = eng.td_loss("td3", qs, nqs, rew, done, 0.99, out=out, workspace=ws)
+    assert r.stats is out[0] and r.grad_q is out[1] and r.target is out[2]
+    return eng, dict(q0=qs[0], q1=qs[1], nq0=nqs[0], nq1=nqs[1], rewards=rew, dones=done, stats=out[0], g0=out[1][0], g1=out[1][1], target=out[2],
+                     workspace=ws)
+
+
+def case_td_loss_sac_log_ent_coef():
+    import torch
+    eng = recording_engine(N)
+    B = 257
+    qs, nqs = [torch.zeros(B, 1), torch.zeros(B)], [torch.zeros(B), torch.zeros(B, 1)]
+    rew, done, lp, la = torch.zeros(B), torch.zeros(B), torch.zeros(B, 1), torch.zeros(1, dtype=torch.float64)
+    r = eng.td_loss("sac", qs, nqs, rew, done, 0.5, next_log_prob=lp, log_ent_coef=la)
+    assert [tuple(g.shape) for g in r.grad_q] == [(B, 1), (B,)] and r.target is None
+    return eng, dict(q0=qs[0], q1=qs[1], nq0=nqs[0], nq1=nqs[1], rewards=rew, dones=done, next_log_prob=lp, log_ent_coef=la, stats=r.stats,
+                     g0=r.grad_q[0], g1=r.grad_q[1])
+
+
+def case_quantile_loss_stacked_fresh():
+    import torch
+    eng = recording_engine(N)
+    B, K, Q = 9, 2, 5
+    wide = torch.zeros(B, K, Q + 1)
+    q, nq = wide[:, :, :Q], torch.zeros(B, K, Q)                             # row stride K * (Q + 1), critic stride Q + 1
+    rew, done, lp = torch.zeros(B, dtype=torch.float64), torch.zeros(B, 1), torch.zeros(B)
+    r = eng.quantile_loss(q, nq, rew, done, lp, 0.99, 2, ent_coef=0.2, want_target=True)
+    assert r.grad_quantiles.shape == (B, K, Q) and r.target.shape == (B, K * (Q - 2)) and r.stats.dtype == torch.float64
+    return eng, dict(rewards=rew, dones=done, next_log_prob=lp, stats=r.stats, target=r.target, **_views("q", q), **_views("nq", nq),
+                     **_views("g", r.grad_quantiles))
+
+
+def case_quantile_loss_list_out():
+    import torch
+    eng = recording_engine(N)
+    B, K, Q, f64 = 4, 3, 2, dict(dtype=torch.float64)
+    qs, nqs = [torch.zeros(B, Q, **f64) for _ in range(K)], [torch.zeros(B, Q + 1, **f64)[:, 1:] for _ in range(K)]
+    rew, done, lp, alpha = torch.zeros(B, 1), torch.zeros(B), torch.zeros(B, 1, **f64), torch.zeros(1, **f64)
+    out = (torch.zeros(8, **f64), [torch.zeros(B, Q, **f64) for _ in range(K)], None)
+    r = eng.quantile_loss(qs, nqs, rew, done, lp, 0.9, 0, ent_coef=alpha, out=out)
+    assert r.stats is out[0] and r.grad_quantiles is out[1] and r.target is None
+    return eng, dict(rewards=rew, dones=done, next_log_prob=lp, ent_coef=alpha, stats=out[0], **_views("q", qs), **_views("nq", nqs), **_views("g", out[1]))
+
+
+def case_actor_loss_sac_target_entropy():
+    import torch
+    eng = recording_engine(N)
+    B = 300
+    both = torch.zeros(B, 2)
+    qs, lp, la = [both[:, 0], both[:, 1:]], torch.zeros(B, 1), torch.zeros(1, dtype=torch.float64)
+    r = eng.actor_loss("sac", qs, lp, log_ent_coef=la, target_entropy=-1.0)
+    assert [tuple(g.shape) for g in r.grad_q] == [(B,), (B, 1)] and r.grad_log_prob.shape == (B, 1)
+    assert r.grad_log_ent_coef.shape == (1,) and r.grad_log_ent_coef.dtype == torch.float64
+    return eng, dict(q0=qs[0], q1=qs[1], log_prob=lp, log_ent_coef=la, stats=r.stats, g0=r.grad_q[0], g1=r.grad_q[1], grad_log_prob=r.grad_log_prob,
+                     grad_log_ent_coef=r.grad_log_ent_coef)
+
+
+def case_actor_loss_tqc_stacked():
+    import torch
+    eng = recording_engine(N)
+    B, K, Q, f64 = 6, 2, 3, dict(dtype=torch.float64)
+    q, lp = torch.zeros(B, K, Q, **f64), torch.zeros(B, **f64)
+    r = eng.actor_loss("tqc", q, lp, ent_coef=0.3)
+    assert r.grad_q.shape == (B, K, Q) and r.grad_log_prob.shape == (B,) and r.grad_log_ent_coef is None
+    return eng, dict(log_prob=lp, stats=r.stats, grad_log_prob=r.grad_log_prob, **_views("q", q), **_views("g", r.grad_q))
+
+
+def case_actor_loss_td3_bare_tensor():
+    import torch
+    eng = recording_engine(N)
+    B = 5
+    q = torch.zeros(B, 1)
+    out = (torch.zeros(8, dtype=torch.float64), torch.zeros(B, 1), None, None)
+    ws = torch.zeros(64, dtype=torch.uint8)
+    r = eng.actor_loss("td3", q, out=out, workspace=ws)
+    assert r.stats is out[0] and r.grad_q is out[1] and r.grad_log_prob is None and r.grad_log_ent_coef is None
+    return eng, dict(q=q, stats=out[0], grad_q=out[1], workspace=ws)
+
+
+def case_actor_loss_ent_coef():
+    import torch
+    eng = recording_engine(N)
+    B = 7
+    lp, la = torch.zeros(B, dtype=torch.float64), torch.zeros(1, dtype=torch.float64)
+    r = eng.actor_loss("ent_coef", log_prob=lp, log_ent_coef=la, target_entropy=-2.5)
+    assert r.grad_q is None and r.grad_log_prob is None and r.grad_log_ent_coef.shape == (1,)
+    return eng, dict(log_prob=lp, log_ent_coef=la, stats=r.stats, grad_log_ent_coef=r.grad_log_ent_coef)
+
+
+def case_rsample_column_mean_fresh():
+    import torch
+    eng = recording_engine(N)
+    B = 10                                                                   # B is not tied to the engine's env count
+    wide = torch.zeros(B, 2)
+    mean, ls, cnt = wide[:, :1], wide[:, 1], torch.zeros(1, dtype=torch.int64)      # the two columns of one actor output: stride 2
+    r = eng.rsample(mean, ls, cnt, seed=-3)
+    assert r.actions.shape == r.log_prob.shape == r.noise.shape == (B, 1) and r.noise.dtype == torch.float64 and r.actions.dtype == torch.float32
+    return eng, dict(mean=mean, log_std=ls, counter=cnt, actions=r.actions, log_prob=r.log_prob, noise=r.noise)
+
+
+def case_rsample_f64_deterministic_out():
+    import torch
+    eng = recording_engine(N)
+    B, f64 = 4, dict(dtype=torch.float64)
+    mean, ls = torch.zeros(B, **f64), torch.zeros(B, 1, **f64)
+    out = (torch.zeros(B, 1, **f64), None, torch.zeros(B, **f64))
+    r = eng.rsample(mean, ls, None, deterministic=True, out=out)
+    assert r.actions is out[0] and r.log_prob is None and r.noise is out[2]
+    return eng, dict(mean=mean, log_std=ls, actions=out[0], noise=out[2])
+
+
+def case_rsample_backward_fresh_one_gradient():
+    import torch
+    eng = recording_engine(N)
+    B = 10
+    wide = torch.zeros(B, 2)
+    mean, ls, noise, gl = wide[:, 0], wide[:, 1:], torch.zeros(B, dtype=torch.float64), torch.zeros(B, 1)
+    r = eng.rsample_backward(mean, ls, noise, None, gl)
+    assert r.grad_mean.shape == (B,) and r.grad_log_std.shape == (B, 1) and r.grad_mean.dtype == torch.float32
+    return eng, dict(mean=mean, log_std=ls, noise=noise, grad_log_prob=gl, grad_mean=r.grad_mean, grad_log_std=r.grad_log_std)
+
+
+def case_rsample_backward_f64_out_strided():
+    import torch
+    eng = recording_engine(N)
+    B, f64 = 3, dict(dtype=torch.float64)
+    mean, ls, noise, ga, gl = torch.zeros(B, 1, **f64), torch.zeros(B, **f64), torch.zeros(B, 1, **f64), torch.zeros(B, **f64), torch.zeros(B, **f64)
+    g = torch.zeros(B, 2, **f64)
+    out = (g[:, 0], g[:, 1:])
+    r = eng.rsample_backward(mean, ls, noise, ga, gl, out=out)
+    assert r.grad_mean is out[0] and r.grad_log_std is out[1]
+    return eng, dict(mean=mean, log_std=ls, noise=noise, grad_actions=ga, grad_log_prob=gl, grad_mean=out[0], grad_log_std=out[1])
+
+
+def case_smooth_target_action_fresh():
+    import torch
+    eng = recording_engine(N)
+    B = 8
+    mean, cnt = torch.zeros(B, 3)[:, 2], torch.zeros(1, dtype=torch.int64)   # stride 3
+    r = eng.smooth_target_action(mean, cnt, 0.2, 0.5, seed=2 ** 64 + 4)
+    assert r.shape == (B,) and r.dtype == torch.float32
+    return eng, dict(mean=mean, counter=cnt, out=r)
+
+
+def case_smooth_target_action_f64_column_out():
+    import torch
+    eng = recording_engine(N)
+    B, f64 = 5, dict(dtype=torch.float64)
+    mean, cnt, out = torch.zeros(B, 1, **f64), torch.zeros(1, dtype=torch.int64), torch.zeros(B, 1, **f64)
+    r = eng.smooth_target_action(mean, cnt, 0.0, 0.0, clip=(-2, 0.5), out=out)
+    assert r is out
+    return eng, dict(mean=mean, counter=cnt, out=out)
+
+
 # what the wrappers passed while they lived in engine.py (rendered by _render): 'H' the handle, the last argument the stream
 EXPECTED = {
     "act_categorical_f32_defaults": [
@@ -381,6 +563,22 @@ EXPECTED = {
     ],
     "act_gaussian_squash_per_env_f64_strided_deterministic": [
         "ptg_act('H', {kind=2, flags=3, in_dtype=1, in_dev=mean, in_s_n=3, param_dev=log_std, param_s_n=1, act_kind=1, clip_lo=-2.0, clip_hi=0.5, act_dev=actions, logp_dev=log_prob}, NULL)",
+    ],
+    "actor_loss_ent_coef": [
+        "ptg_actor_loss_workspace(7)",
+        "ptg_actor_loss('H', {kind=2, flags=6, n_quantiles=1, q_dtype=1, batch=7, logp_dev=log_prob, alpha_dev=log_ent_coef, target_entropy=-2.5, stats_dev=stats, grad_log_alpha_dev=grad_log_ent_coef}, NULL)",
+    ],
+    "actor_loss_sac_target_entropy": [
+        "ptg_actor_loss_workspace(300)",
+        "ptg_actor_loss('H', {flags=7, n_critics=2, n_quantiles=1, batch=300, q_dev=[q0, q1], q_s_n=[2, 2], logp_dev=log_prob, alpha_dev=log_ent_coef, target_entropy=-1.0, stats_dev=stats, grad_q_dev=[g0, g1], g_s_n=[1, 1], grad_logp_dev=grad_log_prob, grad_log_alpha_dev=grad_log_ent_coef}, NULL)",
+    ],
+    "actor_loss_td3_bare_tensor": [
+        "ptg_actor_loss_workspace(5)",
+        "ptg_actor_loss('H', {kind=1, n_critics=1, n_quantiles=1, batch=5, q_dev=[q], q_s_n=[1], stats_dev=stats, grad_q_dev=[grad_q], g_s_n=[1], ws_dev=workspace}, NULL)",
+    ],
+    "actor_loss_tqc_stacked": [
+        "ptg_actor_loss_workspace(6)",
+        "ptg_actor_loss('H', {kind=1, flags=1, n_critics=2, n_quantiles=3, q_dtype=1, batch=6, q_dev=[q0, q1], q_s_n=[6, 6], logp_dev=log_prob, alpha=0.3, stats_dev=stats, grad_q_dev=[g0, g1], g_s_n=[6, 6], grad_logp_dev=grad_log_prob}, NULL)",
     ],
     "gae_f32_2d_fresh": [
         "ptg_gae('H', rew, values, done, last, 20, 0, 0.99, 0.95, adv, ret, NULL)",
@@ -417,6 +615,14 @@ EXPECTED = {
     "policy_loss_workspace": [
         "ptg_policy_loss_workspace(300)",
     ],
+    "quantile_loss_list_out": [
+        "ptg_quantile_loss_workspace(4)",
+        "ptg_quantile_loss('H', {n_critics=3, n_quantiles=2, q_dtype=1, batch=4, cur_dev=[q0, q1, q2], cur_s_n=[2, 2, 2], next_dev=[nq0, nq1, nq2], next_s_n=[3, 3, 3], grad_dev=[g0, g1, g2], g_s_n=[2, 2, 2], rew_dev=rewards, done_dev=dones, next_logp_dev=next_log_prob, alpha_dev=ent_coef, gamma=0.9, stats_dev=stats}, NULL)",
+    ],
+    "quantile_loss_stacked_fresh": [
+        "ptg_quantile_loss_workspace(9)",
+        "ptg_quantile_loss('H', {n_critics=2, n_quantiles=5, n_drop=2, rew_dtype=1, batch=9, cur_dev=[q0, q1], cur_s_n=[12, 12], next_dev=[nq0, nq1], next_s_n=[10, 10], grad_dev=[g0, g1], g_s_n=[10, 10], rew_dev=rewards, done_dev=dones, next_logp_dev=next_log_prob, gamma=0.99, alpha=0.2, stats_dev=stats, y_dev=target}, NULL)",
+    ],
     "replay_add_done_col_final_obs_feature_major_rows": [
         "ptg_replay_add('H', {capacity=8, obs_dim=3, obs_bytes=8, obs_ring=obs_ring, next_ring=next_ring, n_cols=2, col_bytes=[8, 4], col_ring=[ring0, ring1], cursor_dev=cursor}, prev, obs, 18, 1, 6, final_obs, done, 1, 2, [c0], 2, NULL)",
     ],
@@ -434,6 +640,36 @@ EXPECTED = {
     ],
     "replay_sample_out_given": [
         "ptg_replay_sample('H', {capacity=8, obs_dim=3, obs_bytes=4, obs_ring=obs_ring, next_ring=next_ring, n_cols=1, col_bytes=[4], col_ring=[ring0], cursor_dev=cursor}, NULL, 4, 3, o_obs, NULL, [out0], -1, o_idx, NULL)",
+    ],
+    "rsample_backward_f64_out_strided": [
+        "ptg_rsample_backward('H', {q_dtype=1, batch=3, mean_dev=mean, mean_s_n=1, log_std_dev=log_std, log_std_s_n=1, noise_dev=noise, grad_act_dev=grad_actions, grad_logp_dev=grad_log_prob, grad_mean_dev=grad_mean, gm_s_n=2, grad_log_std_dev=grad_log_std, gl_s_n=2}, NULL)",
+    ],
+    "rsample_backward_fresh_one_gradient": [
+        "ptg_rsample_backward('H', {batch=10, mean_dev=mean, mean_s_n=2, log_std_dev=log_std, log_std_s_n=2, noise_dev=noise, grad_logp_dev=grad_log_prob, grad_mean_dev=grad_mean, gm_s_n=1, grad_log_std_dev=grad_log_std, gl_s_n=1}, NULL)",
+    ],
+    "rsample_column_mean_fresh": [
+        "ptg_rsample('H', {batch=10, mean_dev=mean, mean_s_n=2, log_std_dev=log_std, log_std_s_n=2, seed=18446744073709551613, counter_dev=counter, act_dev=actions, logp_dev=log_prob, noise_dev=noise}, NULL)",
+    ],
+    "rsample_f64_deterministic_out": [
+        "ptg_rsample('H', {flags=1, q_dtype=1, batch=4, mean_dev=mean, mean_s_n=1, log_std_dev=log_std, log_std_s_n=1, act_dev=actions, noise_dev=noise}, NULL)",
+    ],
+    "smooth_target_action_f64_column_out": [
+        "ptg_rsample('H', {kind=1, q_dtype=1, batch=5, mean_dev=mean, mean_s_n=1, counter_dev=counter, clip_lo=-2.0, clip_hi=0.5, act_dev=out}, NULL)",
+    ],
+    "smooth_target_action_fresh": [
+        "ptg_rsample('H', {kind=1, batch=8, mean_dev=mean, mean_s_n=3, seed=4, counter_dev=counter, noise_std=0.2, noise_clip=0.5, clip_lo=-1.0, clip_hi=1.0, act_dev=out}, NULL)",
+    ],
+    "td_loss_dqn_fresh_want_target": [
+        "ptg_td_loss_workspace(300)",
+        "ptg_td_loss('H', {n_actions=4, act_kind=2, done_dtype=1, batch=300, q_dev=[q], q_s_n=[6], next_q_dev=[next_q], next_s_n=[4], act_dev=actions, rew_dev=rewards, done_dev=dones, gamma=0.97, scale=1.0, stats_dev=stats, grad_q_dev=[grad_q], g_s_n=[4], y_dev=target}, NULL)",
+    ],
+    "td_loss_sac_log_ent_coef": [
+        "ptg_td_loss_workspace(257)",
+        "ptg_td_loss('H', {kind=1, flags=3, n_critics=2, batch=257, q_dev=[q0, q1], q_s_n=[1, 1], next_q_dev=[nq0, nq1], next_s_n=[1, 1], rew_dev=rewards, done_dev=dones, next_logp_dev=next_log_prob, alpha_dev=log_ent_coef, gamma=0.5, scale=0.5, stats_dev=stats, grad_q_dev=[g0, g1], g_s_n=[1, 1]}, NULL)",
+    ],
+    "td_loss_td3_critics_out_workspace": [
+        "ptg_td_loss_workspace(5)",
+        "ptg_td_loss('H', {kind=1, n_critics=2, q_dtype=1, done_dtype=1, batch=5, q_dev=[q0, q1], q_s_n=[2, 2], next_q_dev=[nq0, nq1], next_s_n=[2, 2], rew_dev=rewards, done_dev=dones, gamma=0.99, scale=1.0, stats_dev=stats, grad_q_dev=[g0, g1], g_s_n=[1, 1], y_dev=target, ws_dev=workspace}, NULL)",
     ],
     "vn_get": [
         "ptg_vn_get('H', fresh0, returns)",
