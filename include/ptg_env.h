@@ -84,7 +84,9 @@ enum { PTG_OUT_F32 = 0, PTG_OUT_F64 = 1 };                    /* element type of
  * SPLIT [N][16] (float32): the part of the SB3_FLAT row that depends on the env's own state, plus WHERE its market features are:
  *   columns 0-5 METH_STATUS one-hot, 6 T_CAT, 7 H2_in, 8 CH4_syn, 9 H2_res, 10 H2O_DE, 11 Elec_Heating, 12 sin, 13 cos,
  *   14 hour index, 15 day index -- the start of the env's 13-hour (2-day) windows in the normalised feature series of
- *   ptg_market_feature_series (index = market_set * series_length + hour or day; exact in float32 up to 2^24).
+ *   ptg_market_feature_series (index = market_set * series_length + hour or day; exact in float32 up to 2^24).  That series is
+ *   float32 whatever out_dtype is: a float64 handle's SPLIT rows hold float64 env columns, but the market columns a consumer rebuilds
+ *   from the indices carry one float32 rounding of the float64 feature (tests/test_split_oracle.py compares them at that tolerance).
  * The 26 ('raw': 17) market features of a row are a function of that index alone, so a policy's first layer can be evaluated as
  *   W_env . row[0:14] + G[hour index] (+ G_day[day index]),  G = the market columns of W applied to every window of the series
  * (rl_ptg_amd/policy_split.py): 73 instead of 169 bytes per env-step leave the env kernel, and the first layer multiplies 14

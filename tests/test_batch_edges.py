@@ -67,10 +67,7 @@ def test_batch_sizes_at_wave_and_workgroup_boundaries(layout, out_dtype):
         acts = rng.integers(0, 5, (T, n)).astype(np.int32)
         hot = _run(spec, n, layout, out_dtype, acts, "rollout")
         stp = _run(spec, n, layout, out_dtype, acts, "steps")
-        if layout == "split":                                 # the generic kernels do not write the split layout: hot rollout == hot steps
-            ref = stp
-        else:
-            ref = _run(spec, n, layout, out_dtype, acts, "generic")
+        ref = _run(spec, n, layout, out_dtype, acts, "generic")      # (split too: ObsRow::put / put_idx write it, tests/test_split_oracle.py)
         for got, name in ((hot, "rollout"), (stp, "steps")):
             for a, b, what in zip(got[:3], ref[:3], ("obs", "rew", "done")):
                 assert np.array_equal(a, b), (name, what, n, layout, out_dtype)

@@ -1,10 +1,16 @@
 """Host-side contract of PtGVecEnv.step (rl_ptg_amd/vec_env.py over ptg_step_host): what the caller may keep across steps,
 the zero-copy and the staged route, lazy eval infos, checkpointing.  Reference semantics: DummyVecEnv returns copies of its
 buffers every step (SB3 dummy_vec_env.py `_obs_from_buf`), SB3 algorithms keep `_last_obs` across exactly one step()."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import helpers as H
+
+sys.path.insert(0, os.path.join(H.ROOT, "oracle"))
+import sb3_flat_oracle as flat_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -176,18 +182,64 @@ def test_create_destroy_does_not_leak_device_memory():
     assert abs(free0 - free1) < (32 << 20), (free0, free1)
 
 
+_twin_status = {}
+
+
+def _row_twin_status(spec, n, dtype, steps):
+    """status bytes of `steps` ptg_step_host calls on a row-layout handle with the seed and the actions of the test below"""
+    import ctypes as C
+    import torch
+    from rl_ptg_amd.engine import HipEngine
+    if (n, dtype) not in _twin_status:
+        eng = HipEngine(spec.consts, spec.tables, spec.markets, n, device=0, out_dtype=dtype, obs_layout="row")
+        eng.set_episode_plan(spec.eps_ind, n, n)
+        eng.set_noise_rng(4)
+        eng.reset()
+        L, h = eng._L, eng._h
+        o_stat, total = C.c_size_t(), C.c_size_t()
+        assert L.ptg_host_layout_ex(h, None, None, C.byref(o_stat), C.byref(total)) == 0
+        blk = torch.zeros(total.value, dtype=torch.uint8, pin_memory=True)
+        act = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        fin = torch.empty(n * 35 * eng.obs.element_size(), dtype=torch.uint8, pin_memory=True)
+        nd = C.c_int(-1)
+        rng = np.random.default_rng(9)
+        out = []
+        for t in range(steps):
+            act.numpy()[:] = rng.integers(0, 5, n)
+            assert L.ptg_step_host(h, C.c_void_p(act.data_ptr()), 0, C.c_void_p(blk.data_ptr()), C.c_void_p(fin.data_ptr()), None,
+                                   C.byref(nd), eng._stream()) == 0
+            b = blk.numpy()
+            out.append(b[o_stat.value:o_stat.value + n].copy())
+            col = b[:n * 35 * eng.obs.element_size()].view(np.float64 if dtype == "float64" else np.float32).reshape(n, 35)[:, 26]
+            assert np.array_equal(out[-1].astype(np.int64), np.rint(col).astype(np.int64))
+        eng.close()
+        _twin_status[(n, dtype)] = out
+    return _twin_status[(n, dtype)]
+
+
 @pytest.mark.parametrize("n,layout,dtype", [(6, "row", "float64"), (4096, "row", "float32"), (4096, "feature", "float64"), (333, "row", "float32"),
-                                             (1001, "row", "float64")])
+                                             (1001, "row", "float64"), (333, "sb3_flat", "float32"), (6, "split", "float32"),
+                                             (1001, "split", "float64")])
 def test_host_step_phases_and_status_section(n, layout, dtype):
     """ptg_step_host_begin / _tail / _end (include/ptg_env.h) through raw ctypes, as a C caller would drive them: after `tail` the rewards,
     done flags and the contiguous METH_STATUS bytes are in the block, after `end` the observations; the three phases produce what the
     one-call ptg_step_host produces on a twin handle, and the status bytes equal the METH_STATUS column of the returned rows.  Calling
     the phases out of order is PTG_E_INVALID, not UB.  Routes (block + final rows + actions against the 256 KiB zero-copy limit):
-    zero-copy at n = 6 and n = 333 (float32 rows: 48 618 + 46 620 + 1 332 bytes), staged at n = 1001 (float64 rows) and n = 4096."""
+    zero-copy at n = 6 and n = 333 (float32 rows: 48 618 + 46 620 + 1 332 bytes; the 40-column sb3_flat rows: 55 296 + 53 280 + 1 332),
+    staged at n = 1001 (float64 rows; the 16-column split rows: 138 144 + 128 128 + 4 004 bytes > 262 144) and n = 4096.
+    One-hot layouts (sb3_flat, split: status_column / k_pack_status take their one-hot branch, on the zero-copy host loop and in the
+    staged kernel): the six METH_STATUS columns of every row are one-hot, the status bytes are their argmax, and they equal the status
+    bytes of a row-layout twin driven with the same seed and actions."""
     import ctypes as C
     import torch
     from rl_ptg_amd.engine import HipEngine
     spec = _spec()
+    onehot = layout in ("sb3_flat", "split")
+    if onehot:
+        # first of the six one-hot columns: 0 in a split row; in an sb3_flat row the widths of the keys sorted before METH_STATUS
+        widths = dict(flat_oracle.reference_keys("mod"))
+        c0 = 0 if layout == "split" else sum(w for k, w in widths.items() if k < "METH_STATUS")
+        twin_status = _row_twin_status(spec, n, dtype, 25)
     outs = []
     for phased in (True, False):
         eng = HipEngine(spec.consts, spec.tables, spec.markets, n, device=0, out_dtype=dtype, obs_layout=layout)
@@ -195,6 +247,7 @@ def test_host_step_phases_and_status_section(n, layout, dtype):
         eng.set_noise_rng(4)
         eng.reset()
         L, h = eng._L, eng._h
+        assert eng.obs_dim == {"row": 35, "feature": 35, "sb3_flat": 40, "split": 16}[layout]
         o_rew, o_done, o_stat, total = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         assert L.ptg_host_layout_ex(h, C.byref(o_rew), C.byref(o_done), C.byref(o_stat), C.byref(total)) == 0
         t3 = C.c_size_t()
@@ -225,7 +278,13 @@ def test_host_step_phases_and_status_section(n, layout, dtype):
             flat = b[:n * eng.obs_dim * np.dtype(npdt).itemsize].view(npdt)
             mat = flat.reshape(eng.obs_dim, n).T if layout == "feature" else flat.reshape(n, eng.obs_dim)
             status = b[o_stat.value:o_stat.value + n]
-            assert np.array_equal(status.astype(np.int64), np.rint(mat[:, eng.obs_dim - 9]).astype(np.int64)), t
+            if onehot:
+                hot = mat[:, c0:c0 + 6]
+                assert np.all((hot == 0) | (hot == 1)) and np.all(hot.sum(axis=1) == 1), t
+                assert np.array_equal(status.astype(np.int64), np.argmax(hot, axis=1)), t
+                assert np.array_equal(status, twin_status[t]), t
+            else:
+                assert np.array_equal(status.astype(np.int64), np.rint(mat[:, eng.obs_dim - 9]).astype(np.int64)), t
             rows.append(b[:o_stat.value + n].copy())
         assert len({int(x) for r in rows for x in np.unique(r[o_stat.value:o_stat.value + n])}) >= 3    # several METH_STATUS values occurred
         outs.append(rows)
