@@ -46,7 +46,8 @@ extern "C" {
                              *     actor head of SAC / TQC forward and backward, TD3's smoothed target action); + ptg_al, ptg_actor_loss,
                              *     ptg_actor_loss_workspace (the SAC / TQC / TD3 actor loss and the entropy-coefficient loss with their
                              *     gradients); + ptg_mlp, ptg_mlp_forward, ptg_mlp_workspace (the inference forward of the policy and target MLPs,
-                             *     one fused f32 MFMA launch per layer); no earlier declaration changed */
+                             *     one fused f32 MFMA launch per layer); + ptg_mlp_bwd, ptg_mlp_backward, ptg_mlp_backward_workspace (the backward pass
+                             *     of those MLPs, two f32 MFMA launches per layer); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -1132,7 +1133,8 @@ int ptg_actor_loss(ptg_env* env, const ptg_al* d, void* stream);
 /* ---- the inference forward of an MLP: one fused launch per layer, Linear + bias + activation on the f32 matrix cores -------------------
  * Replaces th.no_grad() calls of the nets that SB3's create_mlp builds for the reference (config/config_agent.yaml: 2 - 7 hidden layers
  * of 233 - 808 units, ReLU or Tanh): the policy while collecting and evaluating, the target actor / critics / q_net of a gradient step.
- * The backward pass, and with it the training forward under autograd, stays torch's.
+ * The backward pass is ptg_mlp_backward (below), which reads what a PTG_MLP_KEEP_HIDDEN call of this one leaves; together they are the
+ * training forward and backward.
  * The call is described by a ptg_mlp, read during the call and holding no host memory (B = batch, n = n_layers):
  *   batch         B, 1 <= B <= 2^31
  *   n_layers      n, 1 <= n <= PTG_MLP_MAX_LAYERS (the reference's deepest net is DQN's: 7 hidden layers and the output layer)
@@ -1199,6 +1201,70 @@ typedef struct ptg_mlp {
 } ptg_mlp;
 int64_t ptg_mlp_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags);
 int ptg_mlp_forward(ptg_env* env, const ptg_mlp* d, void* stream);
+
+/* ---- the backward pass of an MLP: per layer one launch for the input gradient and one for the weight and bias gradients ----------------
+ * Runs after a ptg_mlp_forward call with PTG_MLP_KEEP_HIDDEN and reads what that call left: the hidden layers in its ws_dev, the output
+ * in its out_dev.  With it a gradient step is sample -> forward -> loss -> backward -> optimiser on project kernels, with defined bits,
+ * no allocation, capturable into a hipGraph.  The call is described by a ptg_mlp_bwd, read during the call and holding no host memory:
+ *   fwd           the forward call's ptg_mlp, unchanged (same pointers, strides, widths, batch); it must carry PTG_MLP_KEEP_HIDDEN.  Its
+ *                 x_dev / x2_dev, w_dev[l], ws_dev and out_dev are read; b_dev[l] must be non-NULL but is not read
+ *   gout_dev      float32 [B][O], O = width[n - 1]: the gradient with respect to the output, element (b, j) at b * gout_s_n + j,
+ *                 gout_s_n >= O
+ *   dw_dev[l]     float32 [width[l]][in_l], element (j, k) at j * dw_s_n[l] + k, dw_s_n[l] >= in_l: the gradient of w_dev[l];
+ *   db_dev[l]     float32 [width[l]] contiguous: the gradient of b_dev[l].  dw_dev[l] and db_dev[l] are both set or both NULL; a NULL pair
+ *                 freezes that layer (no k_mlp_dw launch for it); all NULL: no parameter gradients (a critic inside an actor loss)
+ *   dx_dev        float32 [B][f1], row stride dx_s_n >= f1, or NULL;  dx2_dev float32 [B][f2], row stride dx2_s_n >= f2, or NULL (it needs
+ *                 f2 > 0): the gradient with respect to the input's pieces, each optional (SAC / TD3 / TQC's actor loss wants the
+ *                 critic's action piece alone).  Both NULL: the first layer's input-gradient launch is left out
+ *   bws_dev       caller-owned device scratch, 4-byte aligned, bws_bytes >= ptg_mlp_backward_workspace(batch, n_layers, width, flags):
+ *                 two alternating buffers of B * P(widest of ALL n widths) floats, P as in the forward.  dz of layer l (the gradient at
+ *                 its pre-activation) is [B][width[l]] with row stride P(width[l]) at byte offset (l & 1) * 4 * B * P(widest); layer l
+ *                 overwrites layer l + 2, so after the call dz of layers 0 and 1 (n >= 2) are what is left.  The last
+ *                 layer's dz is stored only when out_act != NONE; with NONE gout_dev is read in place
+ *   flags         PTG_MLP_ACCUMULATE: dw_dev / db_dev are added to, not overwritten (below)
+ * Arithmetic, which is the definition (tests/mlp_backward_restatement.py restates it).  All float32, one rounding per step, subnormals
+ * kept.  Layer l with fan-in K, width O, input x (hidden layer l - 1, or the call's one- or two-piece input), post-activation output h
+ * (hidden layer l, or out_dev); g[b][j] the gradient with respect to h[b][j] (gout for the last layer, else dx of the layer above):
+ *   dz[b][j]:  NONE g;  RELU h > 0 ? g : (h != h ? g : 0) -- a select, not a product: a NaN g under a dead unit gives 0, a NaN unit
+ *              passes g (torch's threshold_backward on the saved output);  TANH t = h * h; u = 1 - t; dz = g * u, three roundings
+ *   dx[b][k]:  acc = 0;     for j = 0 .. O - 1 ascending: acc = fmaf(dz[b][j], W[j][k], acc);   dx[b][k] = acc
+ *   dW[j][k]:  acc = init;  for b = 0 .. B - 1 ascending: acc = fmaf(dz[b][j], x[b][k], acc);   dW[j][k] = acc
+ *   db[j]:     acc = init;  for b ascending: acc = acc + dz[b][j] (= fmaf(dz[b][j], 1, acc): it rides in the dW tile as a column of ones)
+ *   init = 0, or with PTG_MLP_ACCUMULATE the value already in dW / db: a call on rows [0, B1) followed by an accumulating call on rows
+ *   [B1, B) leaves the bits of one call on [0, B) -- micro-batched gradient accumulation is exact.
+ * v_mfma_f32_16x16x4_f32 realises these chains with the accumulator as C (four ascending reduction steps per instruction).  A row's dx
+ * depends on nothing outside its own row of dz, so its bits do not depend on B, on the row's place in the batch or on the grid; dW and db
+ * depend on B's rows in their order and on nothing else.  No split-K, no atomics.  Padded reduction positions contribute fmaf(0, 0, acc),
+ * exact except -0 -> +0 (the forward's rule).  Non-finite values propagate as IEEE 754 dictates: a non-finite dz row reaches every
+ * dW[j][.] and db[j] it touches and no other row's dx.
+ * Enqueues, serially on the one stream: k_mlp_dz_out when out_act != NONE; then for l = n - 1 .. 0 k_mlp_dw (when dw_dev[l] is set) and
+ * k_mlp_dx (for l = 0 only when dx_dev or dx2_dev is set) -- at most 2 n + 1 launches.  No host synchronisation and no allocation; reads
+ * nothing of the handle but its device.  Overlap between any two buffers is NOT checked: the outputs and bws_dev must not overlap each
+ * other or anything the call reads.
+ * PTG_E_INVALID (nothing enqueued): NULL handle or descriptor; anything ptg_mlp_forward refuses in fwd; fwd without
+ * PTG_MLP_KEEP_HIDDEN; NULL gout_dev or gout_s_n below the output width; dw_dev[l] without db_dev[l] or the reverse (l < n); dw_s_n[l]
+ * below the fan-in; dx_s_n below f1; dx2_dev with f2 = 0 or dx2_s_n below f2; an unknown flag; NULL or misaligned bws_dev; bws_bytes
+ * below what ptg_mlp_backward_workspace returns.
+ * ptg_mlp_backward_workspace(batch, n_layers, widths, flags): 8 * batch * P(widest width) bytes; negative for a NULL widths or a count,
+ * width or flag the call would refuse. */
+enum { PTG_MLP_ACCUMULATE = 8 };
+typedef struct ptg_mlp_bwd {
+    ptg_mlp fwd;
+    const float* gout_dev;
+    int64_t gout_s_n;
+    float* dw_dev[PTG_MLP_MAX_LAYERS];
+    int64_t dw_s_n[PTG_MLP_MAX_LAYERS];
+    float* db_dev[PTG_MLP_MAX_LAYERS];
+    float* dx_dev;
+    int64_t dx_s_n;
+    float* dx2_dev;
+    int64_t dx2_s_n;
+    void* bws_dev;
+    int64_t bws_bytes;
+    int32_t flags, reserved;
+} ptg_mlp_bwd;
+int64_t ptg_mlp_backward_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags);
+int ptg_mlp_backward(ptg_env* env, const ptg_mlp_bwd* d, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SRC = os.path.join(CSRC, "ptg_env.hip")                # the environment: N_PARTS translation units of the parallel build
 SRC_TRAIN = os.path.join(CSRC, "ptg_train.hip")        # the training ops: one translation unit
-SRC_MLP = os.path.join(CSRC, "ptg_mlp.hip")            # the MLP forward: one translation unit
+SRC_MLP = os.path.join(CSRC, "ptg_mlp.hip")            # the MLP forward and backward: one translation unit
 HDR = os.path.join(ROOT, "include", "ptg_env.h")
 LIB_PATH = os.environ.get("PTG_LIB_PATH") or os.path.join(PKG, "lib", "libptg_env.so")      # PTG_LIB_PATH: an experiment build of the same source
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
@@ -39,6 +39,7 @@ AL_ENTROPY, AL_LOG_ALPHA, AL_ENT_COEF = 1, 2, 4
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 10, 1024
 MLP_RELU, MLP_TANH, MLP_NONE = 0, 1, 2
 MLP_KEEP_HIDDEN, MLP_NARROW, MLP_WIDE = 1, 2, 4
+MLP_ACCUMULATE = 8
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -156,6 +157,13 @@ class PtgMlp(C.Structure):                                  # ptg_mlp: one call 
                 ("width", C.c_int32 * MLP_MAX_LAYERS), ("out_dev", C.c_void_p), ("out_s_n", C.c_int64), ("ws_dev", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class PtgMlpBwd(C.Structure):                               # ptg_mlp_bwd: one call of the MLP backward
+    _fields_ = [("fwd", PtgMlp), ("gout_dev", C.c_void_p), ("gout_s_n", C.c_int64), ("dw_dev", C.c_void_p * MLP_MAX_LAYERS),
+                ("dw_s_n", C.c_int64 * MLP_MAX_LAYERS), ("db_dev", C.c_void_p * MLP_MAX_LAYERS), ("dx_dev", C.c_void_p), ("dx_s_n", C.c_int64),
+                ("dx2_dev", C.c_void_p), ("dx2_s_n", C.c_int64), ("bws_dev", C.c_void_p), ("bws_bytes", C.c_int64), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # state fields of ptg_get_state / ptg_set_state
 STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby_tid": 5, "startup_tid": 6,
                 "partial_tid": 7, "full_tid": 8, "current_action": 9, "act_ep_d": 10, "ep_ptr": 11,
@@ -166,7 +174,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
-           "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward",
+           "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward", "ptg_mlp_backward_workspace", "ptg_mlp_backward",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -305,6 +313,9 @@ def lib():
     L.ptg_mlp_workspace.argtypes = [C.c_int64, C.c_int32, i32p, C.c_int32]
     L.ptg_mlp_workspace.restype = C.c_int64
     L.ptg_mlp_forward.argtypes = [vp, C.POINTER(PtgMlp), vp]
+    L.ptg_mlp_backward_workspace.argtypes = [C.c_int64, C.c_int32, i32p, C.c_int32]
+    L.ptg_mlp_backward_workspace.restype = C.c_int64
+    L.ptg_mlp_backward.argtypes = [vp, C.POINTER(PtgMlpBwd), vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

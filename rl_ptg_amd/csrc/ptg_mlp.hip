@@ -1,5 +1,6 @@
-// ptg_mlp.hip -- the inference forward of an MLP (include/ptg_env.h, ptg_mlp_forward, states the arithmetic; tests/mlp_restatement.py
-// restates it).  One launch per layer: Linear + bias + activation fused, on gfx950's exact-float32 MFMA (v_mfma_f32_16x16x4_f32 and
+// ptg_mlp.hip -- the forward of an MLP (include/ptg_env.h, ptg_mlp_forward, states the arithmetic; tests/mlp_restatement.py
+// restates it) and, in the second half of the file, its backward pass (ptg_mlp_backward; tests/mlp_backward_restatement.py).
+// The forward: one launch per layer: Linear + bias + activation fused, on gfx950's exact-float32 MFMA (v_mfma_f32_16x16x4_f32 and
 // v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, one rounding per product).  The translation unit shares ptg_handle.h with ptg_env.hip
 // and ptg_train.hip and reads nothing of the handle but its device.
 //
@@ -297,6 +298,326 @@ int ptg_mlp_forward(ptg_env* h, const ptg_mlp* d, void* stream)
         if (int rc = launch_check(h, "k_mlp_layer")) return rc;
         kept += B * a.y_s;
         a.x = a.x2 = a.y; a.x_s = a.y_s; a.x2_s = 0; a.F1 = a.K = a.O;      // this layer's output is the next one's input
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the backward pass (include/ptg_env.h, ptg_mlp_backward, states the arithmetic) ---------------------------------
+// Two kernels per layer on v_mfma_f32_16x16x4_f32, one wave per workgroup, a 16 x 16 tile, the reduction in chunks of 32 through LDS with
+// the forward's ring of chunks in flight (four in k_mlp_dx, two in k_mlp_dw).  The lane maps are the forward's; what changes is which tensor
+// index rides on which:
+//   k_mlp_dx   D[b][k] = sum_j dz[b][j] W[j][k]:  A[l & 15][l >> 4] = dz[row0 + (l & 15)][j0 + (l >> 4)] (staged [row][j], pitch 36, as the
+//              forward's input), B[l >> 4][l & 15] = W[j0 + (l >> 4)][col0 + (l & 15)] (staged [j][k], pitch 16: the word of a read is
+//              16 (4 s + q) + r, 64 lanes on 64 banks; W's rows are read along k, 16 neighbouring floats of each of four rows per load)
+//   k_mlp_dw   D[j][k] = sum_b dz[b][j] x[b][k]:  A[l & 15][l >> 4] = dz[b0 + (l >> 4)][j0 + (l & 15)], B[l >> 4][l & 15] = x[b0 + (l >> 4)][k0 + (l & 15)]:
+//              both staged [b][.] with pitch 16, A read transposed out of LDS.  x has one column more than the fan-in, all ones: the
+//              tile column K is the bias gradient.  The accumulator starts at 0 or at the gradient already there
+// C/D register g of lane l is row 4 (l >> 4) + g, column l & 15 in both, so 16 neighbouring lanes store 16 neighbouring floats of a row.
+namespace {
+
+#ifndef PTG_MLP_DW_DEPTH
+#define PTG_MLP_DW_DEPTH 2               // an experiment build may set 4: 224 registers instead of 118, two waves per SIMD instead of four
+#endif
+constexpr int BW_TILE = 16, BW_RC = 32, BW_DEPTH = 4, BW_PITCH_T = 16;      // tile, reduction chunk, chunks in flight in k_mlp_dx, pitch of a [reduction][16] stage
+constexpr int DW_DEPTH = PTG_MLP_DW_DEPTH;                                  // chunks in flight in k_mlp_dw
+
+struct MlpDx {                           // by value in the launch
+    const float* dz; size_t dz_s;        // [B][O], the gradient at this layer's pre-activation
+    const float* w; size_t w_s;          // [O][K]
+    const float* h; size_t h_s;          // [B][K] the kept output of the layer below (ACT_BELOW != NONE)
+    float* y; size_t y_s;                // ACT_BELOW != NONE: dz of the layer below [B][K];  NONE: dx's first piece [B][F1] or NULL
+    float* y2; size_t y2_s;              // NONE: dx's second piece [B][K - F1] or NULL
+    size_t B;
+    int F1, K, O;
+};
+
+struct MlpDw {
+    const float* dz; size_t dz_s;        // [B][O]
+    const float* x; size_t x_s;          // the layer's input, first piece [B][F1]
+    const float* x2; size_t x2_s;        // second piece [B][K - F1]; one piece: F1 = K, x2 = x
+    float* dw; size_t dw_s;              // [O][K]
+    float* db;                           // [O]
+    size_t B;
+    int F1, K, O, accumulate;
+};
+
+struct MlpDzOut {
+    const float* g; size_t g_s;          // grad_out [B][O]
+    const float* h; size_t h_s;          // out [B][O]
+    float* dz; size_t dz_s;
+    size_t B;
+    int O;
+};
+
+// the activation derivative on the kept output h: RELU a select, TANH three roundings (t = h h, u = 1 - t, g u)
+template <int ACT>
+__device__ __forceinline__ float mlp_dact(float h, float g)
+{
+    if constexpr (ACT == PTG_MLP_RELU) return h > 0.0f ? g : (h != h ? g : 0.0f);
+    else if constexpr (ACT == PTG_MLP_TANH) return __fmul_rn(g, __fsub_rn(1.0f, __fmul_rn(h, h)));
+    else return g;
+}
+
+template <int ACT_BELOW>
+__global__ __launch_bounds__(64) void k_mlp_dx(const MlpDx a)
+{
+    __shared__ float zs[BW_TILE * NR_PITCH], wt[BW_RC * BW_PITCH_T];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const size_t row0 = (size_t)blockIdx.x * BW_TILE;
+    const int col0 = blockIdx.y * BW_TILE;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    constexpr int PER = BW_TILE * BW_RC / 64;                // 8 elements of dz and 8 of W per lane and chunk
+    float zr[BW_DEPTH][PER], wr[BW_DEPTH][PER];
+    const int jx = lane & 31, r2 = lane >> 5;
+    const int kw = col0 + r, kwc = min(kw, a.K - 1);
+    auto fetch = [&](int d, int j0) {                        // dz: j = j0 + jx of every second row;  W: column kw of every fourth row j
+        const int j = j0 + jx, jc = min(j, a.O - 1);
+        const bool jin = j < a.O;
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            const size_t row = row0 + r2 + 2 * i;
+            const float z = a.dz[min(row, a.B - 1) * a.dz_s + (size_t)jc];
+            zr[d][i] = jin && row < a.B ? z : 0.0f;
+            const int jw = j0 + q + 4 * i;
+            const float w = a.w[(size_t)min(jw, a.O - 1) * a.w_s + (size_t)kwc];
+            wr[d][i] = jw < a.O && kw < a.K ? w : 0.0f;
+        }
+    };
+#pragma unroll
+    for (int d = 0; d < BW_DEPTH; d++)
+        if (d * BW_RC < a.O) fetch(d, d * BW_RC);
+    for (int j0 = 0; j0 < a.O; j0 += BW_DEPTH * BW_RC) {
+#pragma unroll
+        for (int d = 0; d < BW_DEPTH; d++) {
+            const int jc = j0 + d * BW_RC;
+            if (jc >= a.O) break;                            // uniform over the workgroup
+#pragma unroll
+            for (int i = 0; i < PER; i++) {
+                zs[(r2 + 2 * i) * NR_PITCH + jx] = zr[d][i];
+                wt[(q + 4 * i) * BW_PITCH_T + r] = wr[d][i];
+            }
+            __syncthreads();
+            if (jc + BW_DEPTH * BW_RC < a.O) fetch(d, jc + BW_DEPTH * BW_RC);
+            float av[BW_RC / 4], bv[BW_RC / 4];
+#pragma unroll
+            for (int s = 0; s < BW_RC / 4; s++) {
+                av[s] = zs[r * NR_PITCH + 4 * s + q];
+                bv[s] = wt[(4 * s + q) * BW_PITCH_T + r];
+            }
+#pragma unroll
+            for (int s = 0; s < BW_RC / 4; s++)              // four ascending j per instruction
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
+            __syncthreads();
+        }
+    }
+    if (kw < a.K) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const size_t row = row0 + 4 * q + g;
+            if (row >= a.B) continue;
+            if constexpr (ACT_BELOW == PTG_MLP_NONE) {       // the first layer: dx to the caller's pieces, each optional
+                if (kw < a.F1) {
+                    if (a.y) a.y[row * a.y_s + (size_t)kw] = acc[g];
+                } else if (a.y2) a.y2[row * a.y2_s + (size_t)(kw - a.F1)] = acc[g];
+            } else {
+                a.y[row * a.y_s + (size_t)kw] = mlp_dact<ACT_BELOW>(a.h[row * a.h_s + (size_t)kw], acc[g]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
+{
+    __shared__ float zs[BW_RC * BW_PITCH_T], xs[BW_RC * BW_PITCH_T];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const int j0 = blockIdx.x * BW_TILE, k0 = blockIdx.y * BW_TILE;      // k runs to K inclusive: column K is the bias gradient
+    const int ko = k0 + r;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (a.accumulate && ko <= a.K) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int j = j0 + 4 * q + g;
+            if (j < a.O) acc[g] = ko < a.K ? a.dw[(size_t)j * a.dw_s + (size_t)ko] : a.db[j];
+        }
+    }
+    constexpr int PER = BW_TILE * BW_RC / 64;                // 8 rows per lane and chunk
+    float zr[DW_DEPTH][PER], xr[DW_DEPTH][PER];
+    const int jz = j0 + r, jzc = min(jz, a.O - 1), kc = min(ko, a.K - 1);
+    const bool one = ko == a.K;
+    const float* xp = kc < a.F1 ? a.x + (size_t)kc : a.x2 + (size_t)(kc - a.F1);
+    const size_t xps = kc < a.F1 ? a.x_s : a.x2_s;
+    auto fetch = [&](int d, size_t b0) {                     // lane: unit jz and column ko of every fourth row
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            const size_t row = b0 + q + 4 * i, rc = min(row, a.B - 1);
+            const bool rin = row < a.B;
+            const float z = a.dz[rc * a.dz_s + (size_t)jzc];
+            zr[d][i] = rin && jz < a.O ? z : 0.0f;
+            const float x = xp[rc * xps];
+            xr[d][i] = rin && ko <= a.K ? (one ? 1.0f : x) : 0.0f;
+        }
+    };
+#pragma unroll
+    for (int d = 0; d < DW_DEPTH; d++)
+        if ((size_t)(d * BW_RC) < a.B) fetch(d, (size_t)(d * BW_RC));
+    for (size_t b0 = 0; b0 < a.B; b0 += DW_DEPTH * BW_RC) {
+#pragma unroll
+        for (int d = 0; d < DW_DEPTH; d++) {
+            const size_t bc = b0 + d * BW_RC;
+            if (bc >= a.B) break;                            // uniform over the workgroup
+#pragma unroll
+            for (int i = 0; i < PER; i++) {
+                zs[(q + 4 * i) * BW_PITCH_T + r] = zr[d][i];
+                xs[(q + 4 * i) * BW_PITCH_T + r] = xr[d][i];
+            }
+            __syncthreads();
+            if (bc + DW_DEPTH * BW_RC < a.B) fetch(d, bc + DW_DEPTH * BW_RC);
+            float av[BW_RC / 4], bv[BW_RC / 4];
+#pragma unroll
+            for (int s = 0; s < BW_RC / 4; s++) {            // A transposed out of LDS: row of the stage = reduction index
+                av[s] = zs[(4 * s + q) * BW_PITCH_T + r];
+                bv[s] = xs[(4 * s + q) * BW_PITCH_T + r];
+            }
+#pragma unroll
+            for (int s = 0; s < BW_RC / 4; s++)              // four ascending b per instruction
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
+            __syncthreads();
+        }
+    }
+    if (ko <= a.K) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int j = j0 + 4 * q + g;
+            if (j >= a.O) continue;
+            if (ko < a.K) a.dw[(size_t)j * a.dw_s + (size_t)ko] = acc[g];
+            else a.db[j] = acc[g];
+        }
+    }
+}
+
+template <int ACT>
+__global__ __launch_bounds__(256) void k_mlp_dz_out(const MlpDzOut a)
+{
+    const size_t total = a.B * (size_t)a.O, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const size_t b = i / (size_t)a.O, j = i % (size_t)a.O;
+        a.dz[b * a.dz_s + j] = mlp_dact<ACT>(a.h[b * a.h_s + j], a.g[b * a.g_s + j]);
+    }
+}
+
+// what ptg_mlp_forward refuses in a descriptor, restated for the embedded one: NULL when it is well-formed
+const char* mlp_desc_fault(const ptg_mlp* d)
+{
+    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return "batch outside [1, 2^31]";
+    if (d->n_layers < 1 || d->n_layers > PTG_MLP_MAX_LAYERS) return "n_layers outside [1, PTG_MLP_MAX_LAYERS]";
+    if (d->flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) return "unknown flag in the forward's flags";
+    if ((d->flags & PTG_MLP_NARROW) && (d->flags & PTG_MLP_WIDE)) return "PTG_MLP_NARROW and PTG_MLP_WIDE exclude each other";
+    if (d->hidden_act != PTG_MLP_RELU && d->hidden_act != PTG_MLP_TANH) return "hidden_act must be PTG_MLP_RELU or PTG_MLP_TANH";
+    if (d->out_act != PTG_MLP_NONE && d->out_act != PTG_MLP_RELU && d->out_act != PTG_MLP_TANH) return "unknown out_act";
+    if (d->f1 < 1 || d->f2 < 0 || (int64_t)d->f1 + d->f2 > PTG_MLP_MAX_WIDTH) return "need f1 >= 1, f2 >= 0, f1 + f2 <= PTG_MLP_MAX_WIDTH";
+    if (!d->x_dev || d->x_s_n < d->f1) return "x_dev is null or x_s_n below f1";
+    if ((d->x2_dev != nullptr) != (d->f2 > 0)) return "x2_dev and f2 > 0 go together";
+    if (d->x2_dev && d->x2_s_n < d->f2) return "x2_s_n below f2";
+    int fan_in = d->f1 + d->f2;
+    for (int l = 0; l < d->n_layers; l++) {
+        if (d->width[l] < 1 || d->width[l] > PTG_MLP_MAX_WIDTH) return "a width outside [1, PTG_MLP_MAX_WIDTH]";
+        if (!d->w_dev[l] || !d->b_dev[l]) return "a null w_dev or b_dev";
+        if (d->w_s_n[l] < fan_in) return "a w_s_n below the fan-in";
+        fan_in = d->width[l];
+    }
+    if (!d->out_dev || (uintptr_t)d->out_dev % sizeof(float) != 0) return "out_dev is null or not aligned to 4 bytes";
+    if (d->out_s_n < d->width[d->n_layers - 1]) return "out_s_n below the output width";
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(float) != 0) return "ws_dev is null or not aligned to 4 bytes";
+    if (d->ws_bytes < ptg_mlp_workspace(d->batch, d->n_layers, d->width, d->flags)) return "ws_bytes below what ptg_mlp_workspace returns";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ptg_mlp_backward_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags)
+{
+    if (batch < 1 || batch > (int64_t)1 << 31 || n_layers < 1 || n_layers > PTG_MLP_MAX_LAYERS || !widths) return PTG_E_INVALID;
+    if (flags & ~PTG_MLP_ACCUMULATE) return PTG_E_INVALID;
+    int64_t widest = 0;
+    for (int l = 0; l < n_layers; l++) {
+        if (widths[l] < 1 || widths[l] > PTG_MLP_MAX_WIDTH) return PTG_E_INVALID;
+        widest = std::max(widest, mlp_pitch(widths[l]));
+    }
+    return 2 * batch * widest * (int64_t)sizeof(float);
+}
+
+int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: null descriptor");
+    const ptg_mlp* f = &d->fwd;
+    if (const char* why = mlp_desc_fault(f)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor: %s", why);
+    if (!(f->flags & PTG_MLP_KEEP_HIDDEN)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor must carry PTG_MLP_KEEP_HIDDEN");
+    if (d->flags & ~PTG_MLP_ACCUMULATE) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: unknown flag in %d", d->flags);
+    const int n = f->n_layers;
+    if (!d->gout_dev || d->gout_s_n < f->width[n - 1]) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: gout_dev is null or gout_s_n below the output width %d", f->width[n - 1]);
+    int fan_in = f->f1 + f->f2;
+    for (int l = 0; l < n; l++) {
+        if ((d->dw_dev[l] != nullptr) != (d->db_dev[l] != nullptr)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dw_dev[%d] and db_dev[%d] go together", l, l);
+        if (d->dw_dev[l] && d->dw_s_n[l] < fan_in) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dw_s_n[%d] below the fan-in %d", l, fan_in);
+        fan_in = f->width[l];
+    }
+    if (d->dx_dev && d->dx_s_n < f->f1) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx_s_n below f1 = %d", f->f1);
+    if (d->dx2_dev && f->f2 == 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx2_dev without a second input piece");
+    if (d->dx2_dev && d->dx2_s_n < f->f2) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx2_s_n below f2 = %d", f->f2);
+    if (!d->bws_dev || (uintptr_t)d->bws_dev % sizeof(float) != 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: bws_dev is null or not aligned to 4 bytes");
+    const int64_t need = ptg_mlp_backward_workspace(f->batch, n, f->width, d->flags);
+    if (d->bws_bytes < need) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: bws_bytes = %lld, the call needs %lld", (long long)d->bws_bytes, (long long)need);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const size_t B = (size_t)f->batch;
+    size_t widest = 0, kept[PTG_MLP_MAX_LAYERS + 1] = {0};   // kept[l]: floats of ws_dev before hidden layer l
+    for (int l = 0; l < n; l++) {
+        widest = std::max(widest, (size_t)mlp_pitch(f->width[l]));
+        kept[l + 1] = kept[l] + B * (size_t)mlp_pitch(f->width[l]);
+    }
+    auto buf = [&](int l) { return (float*)d->bws_dev + (size_t)(l & 1) * B * widest; };      // dz of layer l, row stride P(width[l])
+    const float* dz = d->gout_dev;
+    size_t dz_s = (size_t)d->gout_s_n;
+    if (f->out_act != PTG_MLP_NONE) {
+        MlpDzOut e{d->gout_dev, (size_t)d->gout_s_n, f->out_dev, (size_t)f->out_s_n, buf(n - 1), (size_t)mlp_pitch(f->width[n - 1]), B, f->width[n - 1]};
+        const size_t total = B * (size_t)e.O;
+        const unsigned blocks = (unsigned)std::min<size_t>((total - 1) / 256 + 1, 65536);
+        if (f->out_act == PTG_MLP_RELU) k_mlp_dz_out<PTG_MLP_RELU><<<blocks, 256, 0, st>>>(e);
+        else k_mlp_dz_out<PTG_MLP_TANH><<<blocks, 256, 0, st>>>(e);
+        if (int rc = launch_check(h, "k_mlp_dz_out")) return rc;
+        dz = e.dz; dz_s = e.dz_s;
+    }
+    for (int l = n - 1; l >= 0; l--) {
+        const int O = f->width[l], K = l ? f->width[l - 1] : f->f1 + f->f2;
+        const float* x = l ? (const float*)f->ws_dev + kept[l - 1] : f->x_dev;      // the layer's input: hidden layer l - 1, or the call's
+        const size_t x_s = l ? (size_t)mlp_pitch(K) : (size_t)f->x_s_n;
+        if (d->dw_dev[l]) {
+            MlpDw a{};
+            a.dz = dz; a.dz_s = dz_s; a.x = x; a.x_s = x_s; a.B = B; a.K = K; a.O = O;
+            a.x2 = !l && f->x2_dev ? f->x2_dev : x; a.x2_s = !l && f->x2_dev ? (size_t)f->x2_s_n : x_s; a.F1 = l ? K : f->f1;
+            a.dw = d->dw_dev[l]; a.dw_s = (size_t)d->dw_s_n[l]; a.db = d->db_dev[l]; a.accumulate = (d->flags & PTG_MLP_ACCUMULATE) != 0;
+            k_mlp_dw<<<dim3((unsigned)((O - 1) / BW_TILE + 1), (unsigned)(K / BW_TILE + 1)), 64, 0, st>>>(a);
+            if (int rc = launch_check(h, "k_mlp_dw")) return rc;
+        }
+        if (!l && !d->dx_dev && !d->dx2_dev) break;
+        MlpDx a{};
+        a.dz = dz; a.dz_s = dz_s; a.w = f->w_dev[l]; a.w_s = (size_t)f->w_s_n[l]; a.B = B; a.K = K; a.O = O;
+        const dim3 grid((unsigned)((B - 1) / BW_TILE + 1), (unsigned)((K - 1) / BW_TILE + 1));
+        if (l) {
+            a.h = x; a.h_s = x_s; a.y = buf(l - 1); a.y_s = x_s; a.F1 = K;
+            if (f->hidden_act == PTG_MLP_RELU) k_mlp_dx<PTG_MLP_RELU><<<grid, 64, 0, st>>>(a);
+            else k_mlp_dx<PTG_MLP_TANH><<<grid, 64, 0, st>>>(a);
+            dz = a.y; dz_s = a.y_s;
+        } else {
+            a.y = d->dx_dev; a.y_s = (size_t)d->dx_s_n; a.y2 = d->dx2_dev; a.y2_s = (size_t)d->dx2_s_n; a.F1 = f->f1;
+            k_mlp_dx<PTG_MLP_NONE><<<grid, 64, 0, st>>>(a);
+        }
+        if (int rc = launch_check(h, "k_mlp_dx")) return rc;
     }
     return 0;
 }

@@ -1,5 +1,5 @@
 """DeviceMLP: the inference forward of a torch MLP as one fused launch per layer (HipEngine.mlp_forward, include/ptg_env.h:
-ptg_mlp_forward, which states the arithmetic).
+ptg_mlp_forward, which states the arithmetic).  TrainMLP, below: the training forward and the backward pass under autograd.
 
     policy = DeviceMLP(engine, q_net, batch=engine.n)                 # an nn.Sequential of Linear / ReLU / Tanh, as SB3's create_mlp returns
     logits = policy(obs)                                              # no autograd graph, no allocation, no synchronisation
@@ -106,3 +106,107 @@ class DeviceMLP:
                                       out=None if B is None else self.out[:B], workspace=self.workspace, keep_hidden=self.keep_hidden)
         self.hidden = res.hidden
         return res.out
+
+
+class _TrainMLPFunction(torch.autograd.Function):
+    """forward: mlp_forward with keep_hidden into the module's buffers; backward: mlp_backward into the module's gradient buffers"""
+
+    @staticmethod
+    def forward(ctx, net, x, x2, *params):
+        B = x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else None
+        if B is not None and B > net.batch:
+            raise ValueError(f"TrainMLP: {B} rows, allocated for {net.batch}")
+        xd, x2d = (x.detach() if torch.is_tensor(x) else x), (x2.detach() if torch.is_tensor(x2) else x2)
+        res = net.engine.mlp_forward(xd, [p.detach() for p in params[0::2]], [p.detach() for p in params[1::2]], hidden_activation=net.hidden_activation,
+                                     out_activation=net.out_activation, x2=x2d, out=None if B is None else net.out[:B], workspace=net.workspace,
+                                     keep_hidden=True)
+        net.calls += 1
+        net.hidden = res.hidden
+        ctx.net, ctx.call, ctx.x, ctx.x2 = net, net.calls, xd, x2d
+        return res.out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        net = ctx.net
+        if ctx.call != net.calls:
+            raise RuntimeError(f"TrainMLP: backward of forward call {ctx.call}, but the latest forward is call {net.calls}: the kept activations live in the "
+                               "module's workspace and a later forward has overwritten them (run each backward before the next forward)")
+        x, x2 = ctx.x, ctx.x2
+        B, F1 = x.shape
+        needs = ctx.needs_input_grad                         # (net, x, x2, w0, b0, w1, b1, ...)
+        if grad_out.stride(1) != 1 or (B > 1 and grad_out.stride(0) < grad_out.shape[1]):
+            grad_out = grad_out.contiguous()                 # e.g. the expanded gradient of a sum
+        n = len(net.linears)
+        wanted = [needs[3 + 2 * l] or needs[4 + 2 * l] for l in range(n)]
+        gw = [net.grad_weights[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
+        gb = [net.grad_biases[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
+        gx = net.grad_input[:B, :F1] if needs[1] else None
+        gx2 = net.grad_input[:B, F1:] if x2 is not None and needs[2] else None
+        net._views = (gx, gx2)                               # held here too, so that autograd copies them into a leaf's .grad and never adopts them
+        net.engine.mlp_backward(grad_out, x, [m.weight.detach() for m in net.linears], [m.bias.detach() for m in net.linears], net.out[:B], net.workspace,
+                                hidden_activation=net.hidden_activation, out_activation=net.out_activation, x2=x2, grad_weights=gw, grad_biases=gb,
+                                grad_x=gx, grad_x2=gx2, backward_workspace=net.backward_workspace)
+        grads = []
+        for l in range(n):
+            grads += [gw[l] if gw is not None and needs[3 + 2 * l] else None, gb[l] if gb is not None and needs[4 + 2 * l] else None]
+        return (None, gx, gx2, *grads)
+
+
+class TrainMLP:
+    """The training forward and backward of a torch MLP under autograd, on the project's kernels (HipEngine.mlp_forward with keep_hidden and
+    HipEngine.mlp_backward; include/ptg_env.h states both arithmetics, DESIGN.md section 19 the design).
+
+        q_net = TrainMLP(engine, q_net_module, batch=544)
+        loss_grad = ...                                                   # e.g. engine.td_loss(...).grad_q
+        q = q_net(obs);  q.backward(loss_grad);  optimiser.step()         # .grad of every parameter from k_mlp_dw, of obs from k_mlp_dx
+        critic = TrainMLP(engine, qf, batch=256);  critic(obs, x2=actions)   # th.cat([obs, action], 1) without the cat
+
+    The parameters are held BY REFERENCE.  The output, the kept activations, both workspaces and the gradient buffers are allocated once,
+    for `batch` rows, and every call overwrites them: the output of a call is valid until the next call, and backward() must run before the
+    next forward of the same TrainMLP -- a backward whose forward is no longer the latest one raises RuntimeError (a call counter, not a
+    copy).  The tensors backward() returns to autograd are the module's own gradient buffers; autograd copies them into `.grad` (or adds
+    them to it), so `.grad` stays valid when the buffers are reused.  Parameters with requires_grad False launch no weight-gradient kernel
+    and keep `.grad` None; an input that needs no gradient gets no first-layer input-gradient launch.
+    Not supported: float64 nets, a Linear without bias, anything but Linear / ReLU / Tanh, split observation rows as input.  There is no
+    torch fall-back.
+    Cost (profiles/mlp_backward_cost.txt; DESIGN.md section 19 has the table and its one condition -- forward + backward not above the same
+    nn.Sequential's under autograd at each agent's own batch size -- which is MISSED at 5 of its 6 shapes): torch's device time of forward +
+    backward over this route's (below 1: slower than torch), TrainMLP / the two raw library calls into preallocated .grad tensors: DQN 7 x 366 at B = 544 0.75x / 0.98x, A2C
+    4 x 808 at 658 0.52x / 0.58x, PPO 2 x 358 at 203 0.89x / 1.95x, TD3's 3 x 743 critic at 257 0.70x / 0.97x, TQC's 3 x 708 critic at 290
+    0.69x / 0.95x; SAC's 6 x 233 critic at 470 1.55x / 2.24x; at B = 6 0.85x - 1.52x / 1.2x - 6.5x.  TrainMLP's own overhead
+    over the raw calls (70 - 230 us: the autograd function, two sets of argument checks, autograd's copies into .grad) is most of the
+    miss; a captured gradient step calls mlp_forward and mlp_backward directly.  What the route gives at every shape is the fixed order."""
+
+    def __init__(self, engine, modules, batch):
+        self.engine = engine
+        self.linears, self.hidden_activation, self.out_activation = parse_mlp(modules)
+        for l, m in enumerate(self.linears):
+            if not m.weight.is_contiguous() or not m.bias.is_contiguous():
+                raise ValueError(f"TrainMLP: the parameters of Linear {l} must be contiguous, got weight strides {tuple(m.weight.stride())}")
+        for l, m in enumerate(self.linears):
+            for p in (m.weight, m.bias):
+                if p.device != engine.device:
+                    raise ValueError(f"TrainMLP: Linear {l} lives on {p.device}, the engine on {engine.device}")
+        self.batch = int(batch)
+        self.widths = [m.out_features for m in self.linears]
+        self.in_features = self.linears[0].in_features
+        nbytes = engine.mlp_workspace(self.batch, self.widths, True)      # ValueError for a batch or a width out of range
+        nback = engine.mlp_backward_workspace(self.batch, self.widths)
+        dev = engine.device
+        with engine._torch.cuda.device(dev):
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.backward_workspace = torch.empty(nback, dtype=torch.uint8, device=dev)
+            self.out = torch.empty((self.batch, self.widths[-1]), dtype=torch.float32, device=dev)
+            self.grad_input = torch.empty((self.batch, self.in_features), dtype=torch.float32, device=dev)
+            self.grad_weights = [torch.empty_like(m.weight, requires_grad=False) for m in self.linears]
+            self.grad_biases = [torch.empty_like(m.bias, requires_grad=False) for m in self.linears]
+        self.hidden, self._views = None, None
+        self.calls = 0
+
+    def parameters(self):
+        return [p for m in self.linears for p in (m.weight, m.bias)]
+
+    def __call__(self, x, x2=None):
+        """x [B, F1] (and x2 [B, F2]) float32 with B <= batch -> the output [B, O] with a grad_fn: the first B rows of the preallocated
+        tensor, which the next call overwrites"""
+        return _TrainMLPFunction.apply(self, x, x2, *self.parameters())

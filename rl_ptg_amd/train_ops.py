@@ -1,6 +1,6 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the inference forward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
-(include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward); none of them steps the environment.  HipEngine inherits them.
+action heads, the policy loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the forward and backward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+(include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward and mlp_backward); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
 _action_kind; torch stays lazily imported (torch = self._torch).
@@ -1152,6 +1152,111 @@ class TrainOps:
                 off += 4 * B * p
             hidden = tuple(hidden)
         return MlpOut(out, hidden)
+
+    # ------------------------------------------------------------------ the backward pass of an MLP
+    def mlp_backward_workspace(self, batch, widths):
+        """bytes of device scratch mlp_backward needs: what ptg_mlp_backward_workspace returns (two alternating [batch, P(widest width)]
+        float32 buffers for dz), computed here so that the argument checks need no library"""
+        widths = [int(w) for w in widths]
+        if not (1 <= int(batch) <= 2 ** 31 and 1 <= len(widths) <= _lib.MLP_MAX_LAYERS and all(1 <= w <= _lib.MLP_MAX_WIDTH for w in widths)):
+            raise ValueError(f"mlp_backward_workspace: batch must be in [1, 2^31], 1 to {_lib.MLP_MAX_LAYERS} layers, widths in [1, {_lib.MLP_MAX_WIDTH}]; got {batch}, {widths}")
+        return 8 * int(batch) * max((w + 3) // 4 * 4 for w in widths)
+
+    def mlp_backward(self, grad_out, x, weights, biases, out, workspace, hidden_activation="relu", out_activation=None, x2=None, grad_weights=None,
+                     grad_biases=None, grad_x=None, grad_x2=None, backward_workspace=None, accumulate=False):
+        """Enqueue, on the current stream, the backward pass of the MLP whose forward was mlp_forward(x, weights, biases, ..., out=out,
+        workspace=workspace, keep_hidden=True) with the same arguments (include/ptg_env.h: ptg_mlp_backward, which states the arithmetic:
+        float32 fmaf chains, dx over ascending units, dW and db over ascending rows).  grad_out [B, O] float32, unit column stride, a row
+        stride >= O.  x, x2, weights, biases, out, workspace: what the forward was given and returned, unchanged since.  grad_weights /
+        grad_biases: lists of n tensors shaped like the parameters (grad_weights[l] may have a row stride above its fan-in), an entry None
+        in both freezes that layer; both None: no parameter gradients.  grad_x [B, F1] / grad_x2 [B, F2]: each optional; with neither, the
+        first layer's input gradient is not computed.  backward_workspace: contiguous uint8, >= mlp_backward_workspace(B, widths) bytes,
+        4-byte aligned, allocated when None.  accumulate: the parameter gradients are added to in place, continuing each element's chain
+        over the rows.  Nothing but backward_workspace is allocated; no synchronisation.  Returns the backward workspace (dz of layers 0
+        and 1 stay in it: include/ptg_env.h has the layout)."""
+        torch = self._torch
+        who = "mlp_backward"
+        f32 = (torch.float32,)
+        acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
+        if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)):
+            raise TypeError(f"{who}: weights and biases must be lists of tensors, got {type(weights).__name__} and {type(biases).__name__}")
+        if (grad_weights is None) != (grad_biases is None):
+            raise TypeError(f"{who}: grad_weights and grad_biases go together")
+        if grad_weights is not None and (not isinstance(grad_weights, (list, tuple)) or not isinstance(grad_biases, (list, tuple))):
+            raise TypeError(f"{who}: grad_weights and grad_biases must be lists, got {type(grad_weights).__name__} and {type(grad_biases).__name__}")
+        named = [("grad_out", grad_out), ("x", x), ("x2", x2)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases)]
+        for name, t in named:                                # TypeError first: what every value is
+            if not (t is None and name == "x2") and (not torch.is_tensor(t) or t.dtype not in f32):
+                check(self, who, name, t, dtypes=f32)
+        if hidden_activation not in ("relu", "tanh"):
+            raise ValueError(f"{who}: hidden_activation must be 'relu' or 'tanh', got {hidden_activation!r}")
+        if out_activation not in acts:
+            raise ValueError(f"{who}: out_activation must be None, 'relu' or 'tanh', got {out_activation!r}")
+        n = len(weights)
+        if not 1 <= n <= _lib.MLP_MAX_LAYERS or len(biases) != n:
+            raise ValueError(f"{who}: 1 to {_lib.MLP_MAX_LAYERS} layers with one bias each, got {n} weights and {len(biases)} biases")
+        if grad_weights is not None and (len(grad_weights) != n or len(grad_biases) != n):
+            raise ValueError(f"{who}: grad_weights and grad_biases must have {n} entries, got {len(grad_weights)} and {len(grad_biases)}")
+        check(self, who, "x", x, dtypes=f32, shape=(None, None), rule=rows)
+        B, F1 = x.shape
+        check(self, who, "x2", x2, dtypes=f32, shape=(B, None), rule=rows, optional=True)
+        F2 = 0 if x2 is None else x2.shape[1]
+        if B < 1 or F1 < 1 or (x2 is not None and F2 < 1):
+            raise ValueError(f"{who}: an empty batch or an empty input piece: x {tuple(x.shape)}" + ("" if x2 is None else f", x2 {tuple(x2.shape)}"))
+        fan_in, widths = F1 + F2, []
+        for l in range(n):
+            if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
+                raise ValueError(f"{who}: the fan-in of layer {l} is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
+            check(self, who, f"weights[{l}]", weights[l], dtypes=f32, shape=(None, fan_in), rule=rows)
+            fan_out = weights[l].shape[0]
+            check(self, who, f"biases[{l}]", biases[l], dtypes=f32, shape=(fan_out,), rule=contiguous)
+            if grad_weights is not None:
+                if (grad_weights[l] is None) != (grad_biases[l] is None):
+                    raise ValueError(f"{who}: grad_weights[{l}] and grad_biases[{l}] go together")
+                check(self, who, f"grad_weights[{l}]", grad_weights[l], dtypes=f32, shape=(fan_out, fan_in), rule=rows, optional=True, exc=ValueError)
+                check(self, who, f"grad_biases[{l}]", grad_biases[l], dtypes=f32, shape=(fan_out,), rule=contiguous, optional=True, exc=ValueError)
+            fan_in = fan_out
+            widths.append(fan_in)
+        if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
+            raise ValueError(f"{who}: the output width is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
+        check(self, who, "grad_out", grad_out, dtypes=f32, shape=(B, fan_in), rule=rows)
+        check(self, who, "out", out, dtypes=f32, shape=(B, fan_in), rule=rows, exc=ValueError)
+        need_f = self.mlp_workspace(B, widths, True)
+        check(self, who, f"workspace (mlp_workspace({B}, {widths}, True))", workspace, dtypes=(torch.uint8,), shape=(None,), rule=contiguous, exc=ValueError)
+        if workspace.numel() < need_f:
+            raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, the forward with keep_hidden needs {need_f}")
+        if workspace.data_ptr() % 4:
+            raise ValueError(f"{who}: workspace must be 4-byte aligned")
+        check(self, who, "grad_x", grad_x, dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
+        if grad_x2 is not None and x2 is None:
+            raise ValueError(f"{who}: grad_x2 without x2")
+        check(self, who, "grad_x2", grad_x2, dtypes=f32, shape=(B, F2), rule=rows, optional=True, exc=ValueError)
+        need = self.mlp_backward_workspace(B, widths)
+        if backward_workspace is not None:
+            check(self, who, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", backward_workspace, dtypes=(torch.uint8,), shape=(None,),
+                  rule=contiguous, exc=ValueError)
+            if backward_workspace.numel() < need:
+                raise ValueError(f"{who}: backward_workspace has {backward_workspace.numel()} bytes, the call needs {need}")
+            if backward_workspace.data_ptr() % 4:
+                raise ValueError(f"{who}: backward_workspace must be 4-byte aligned")
+        outs = [t for t in (list(grad_weights or []) + list(grad_biases or []) + [grad_x, grad_x2, backward_workspace]) if t is not None]
+        _no_tensor_twice(who, outs, "grad_weights, grad_biases, grad_x, grad_x2 and backward_workspace")
+        if backward_workspace is None:
+            with torch.cuda.device(self.device):
+                backward_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        row_stride = lambda t: max(t.stride(0), t.shape[1])      # a one-row tensor may report any row stride
+        d = _lib.PtgMlpBwd(gout_dev=_ptr(grad_out), gout_s_n=row_stride(grad_out), dx_dev=_ptr(grad_x), dx_s_n=0 if grad_x is None else row_stride(grad_x),
+                           dx2_dev=_ptr(grad_x2), dx2_s_n=0 if grad_x2 is None else row_stride(grad_x2), bws_dev=_ptr(backward_workspace),
+                           bws_bytes=backward_workspace.numel(), flags=_lib.MLP_ACCUMULATE if accumulate else 0)
+        d.fwd = _lib.PtgMlp(batch=B, n_layers=n, flags=_lib.MLP_KEEP_HIDDEN, hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
+                            x_dev=_ptr(x), x_s_n=row_stride(x), x2_dev=_ptr(x2), x2_s_n=0 if x2 is None else row_stride(x2), out_dev=_ptr(out),
+                            out_s_n=row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
+        for l in range(n):
+            d.fwd.w_dev[l], d.fwd.w_s_n[l], d.fwd.b_dev[l], d.fwd.width[l] = weights[l].data_ptr(), row_stride(weights[l]), biases[l].data_ptr(), widths[l]
+            if grad_weights is not None and grad_weights[l] is not None:
+                d.dw_dev[l], d.dw_s_n[l], d.db_dev[l] = grad_weights[l].data_ptr(), row_stride(grad_weights[l]), grad_biases[l].data_ptr()
+        self._call("ptg_mlp_backward", C.byref(d))
+        return backward_workspace
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):
