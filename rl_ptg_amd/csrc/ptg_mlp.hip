@@ -12,18 +12,21 @@
 // register 16 (32) neighbouring lanes store neighbouring units of one row.
 //
 // Two routes, the same bits by construction (the order rule forbids split-K, so a small batch can only be spread over the units):
-//   NARROW   one wave per workgroup, a 16-row x 16-unit tile on 16x16x4, K in chunks of 32 staged in LDS; ceil(B / 16) * ceil(O / 16)
-//            workgroups, so a 808 x 808 weight matrix is read by 51 workgroups already at B = 6
-//   WIDE     four waves per workgroup, a 128 x 128 tile on 32x32x2, each wave 2 x 2 tiles of 32 x 32 (four independent accumulators),
-//            K in chunks of 32 staged in LDS
-// Both keep a ring of chunks in flight in registers (four NARROW, two WIDE) while the matrix cores work on the current one: at the
-// reference's batch sizes a layer is a dependent chain of K / 4 MFMAs.  Loads are single dwords: odd widths (743, 233) leave weight
-// rows off 16-byte alignment and the two-piece input splits a row anywhere; a load instruction of a wave still reads 32 neighbouring
-// floats of each of two rows.
+//   NARROW   one wave per workgroup, a 16-row x 16-unit tile on 16x16x4; ceil(B / 16) * ceil(O / 16) workgroups, so a 808 x 808 weight
+//            matrix is read by 51 workgroups already at B = 6
+//   WIDE     four waves per workgroup, a 128 x 128 tile on 32x32x2, each wave 2 x 2 tiles of 32 x 32 (four independent accumulators)
+// Every MFMA kernel of the file runs its reduction through ONE pipeline, mlp_ring: chunks of 32 staged in LDS, a ring of chunks in flight
+// in registers (four NARROW, two WIDE) while the matrix cores work on the current one: at the reference's batch sizes a layer is a
+// dependent chain of K / 4 MFMAs.  A kernel plugs in its fetch (which tensor index rides on which lane), its LDS layout and its MFMAs, and
+// keeps its epilogue.  Loads are single dwords: odd widths (743, 233) leave weight rows off 16-byte alignment and the two-piece input
+// splits a row anywhere; a load instruction of a wave still reads 32 neighbouring floats of each of two rows.
 #include "ptg_handle.h"
 
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
+#include <cstdio>
+#include <type_traits>
 
 namespace {
 
@@ -73,6 +76,49 @@ __device__ __forceinline__ float mlp_act(float v)
     else return v;
 }
 
+// The pipeline over a reduction of length n (int K or O, size_t B) in chunks of RC: fetch(d, r0) loads the chunk at r0 into slot d of the
+// kernel's register ring, stage(d) writes slot d to LDS, mma() consumes the staged chunk.  DEPTH chunks are in flight; a slot is
+// refetched, DEPTH chunks ahead, as soon as it is staged.  d is static once unrolled; the break is uniform over the workgroup.  The
+// lambdas capture what they only read by value and the ring and the accumulator by reference: these loops are optimised before they are
+// inlined into the kernel, and behind reference captures the tile's invariants might alias the ring, so every prologue slot recomputed them
+// (120 to 170 instructions per slot; k_mlp_dw, whose slots are short, is the exception and says why).
+template <int DEPTH, int RC, typename N, typename Fetch, typename Stage, typename Mma>
+__device__ __forceinline__ void mlp_ring(N n, Fetch fetch, Stage stage, Mma mma)
+{
+#pragma unroll
+    for (int d = 0; d < DEPTH; d++)
+        if ((N)(d * RC) < n) fetch(d, (N)(d * RC));
+    for (N r0 = 0; r0 < n; r0 += DEPTH * RC) {
+#pragma unroll
+        for (int d = 0; d < DEPTH; d++) {
+            const N rc = r0 + d * RC;
+            if (rc >= n) break;
+            stage(d);
+            __syncthreads();
+            if (rc + DEPTH * RC < n) fetch(d, rc + DEPTH * RC);
+            mma();
+            __syncthreads();
+        }
+    }
+}
+
+// One chunk of 32 on 16x16x4, four ascending reduction indices per instruction: step s reads as[ia(s)] and bs[ib(s)].  All operands of
+// the chunk come out of LDS first, then the MFMAs run back to back: the chain is the layer's latency at small B.  A ragged last chunk
+// runs its padded steps too: both operands are 0 there, which is exact.
+template <typename IA, typename IB>
+__device__ __forceinline__ void mlp_chain16(const float* as, const float* bs, IA ia, IB ib, f32x4& acc)
+{
+    float av[NR_KC / 4], bv[NR_KC / 4];
+#pragma unroll
+    for (int s = 0; s < NR_KC / 4; s++) {
+        av[s] = as[ia(s)];
+        bv[s] = bs[ib(s)];
+    }
+#pragma unroll
+    for (int s = 0; s < NR_KC / 4; s++)
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
+}
+
 template <int ACT, int ROUTE>
 __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(const MlpLayer a)
 {
@@ -84,9 +130,9 @@ __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(co
         const float bj = col0 + r < a.O ? a.bias[col0 + r] : 0.0f;
         f32x4 acc = {bj, bj, bj, bj};
         constexpr int PER = NR_TILE * NR_KC / 64;            // 8 rows and 8 units per lane and chunk
-        float xr[NR_DEPTH][PER], wr[NR_DEPTH][PER];          // a ring of NR_DEPTH chunks in flight: the slot index is static once unrolled
+        float xr[NR_DEPTH][PER], wr[NR_DEPTH][PER];
         const int kx = lane & 31, r2 = lane >> 5;
-        auto fetch = [&](int d, int k0) {                    // lane: k = k0 + kx of every second row and unit; 0 beyond an edge
+        auto fetch = [=, &xr, &wr](int d, int k0) {          // lane: k = k0 + kx of every second row and unit; 0 beyond an edge
             const int k = k0 + kx;
             const bool kin = k < a.K;
 #pragma unroll
@@ -98,33 +144,15 @@ __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(co
                 wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
             }
         };
+        auto stage = [=, &xr, &wr](int d) {
 #pragma unroll
-        for (int d = 0; d < NR_DEPTH; d++)
-            if (d * NR_KC < a.K) fetch(d, d * NR_KC);
-        for (int k0 = 0; k0 < a.K; k0 += NR_DEPTH * NR_KC) {
-#pragma unroll
-            for (int d = 0; d < NR_DEPTH; d++) {
-                const int kc = k0 + d * NR_KC;
-                if (kc >= a.K) break;                        // uniform over the workgroup
-#pragma unroll
-                for (int i = 0; i < PER; i++) {
-                    xs[(r2 + 2 * i) * NR_PITCH + kx] = xr[d][i];
-                    ws[(r2 + 2 * i) * NR_PITCH + kx] = wr[d][i];
-                }
-                __syncthreads();
-                if (kc + NR_DEPTH * NR_KC < a.K) fetch(d, kc + NR_DEPTH * NR_KC);
-                float av[NR_KC / 4], bv[NR_KC / 4];          // all operands of the chunk out of LDS first, then the MFMAs back to back: the
-#pragma unroll                                               // chain is the layer's latency at small B.  A ragged last chunk runs its padded
-                for (int s = 0; s < NR_KC / 4; s++) {        // steps too: both operands are 0 there, which is exact
-                    av[s] = xs[r * NR_PITCH + 4 * s + q];
-                    bv[s] = ws[r * NR_PITCH + 4 * s + q];
-                }
-#pragma unroll
-                for (int s = 0; s < NR_KC / 4; s++)          // four ascending k per instruction
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
-                __syncthreads();
+            for (int i = 0; i < PER; i++) {
+                xs[(r2 + 2 * i) * NR_PITCH + kx] = xr[d][i];
+                ws[(r2 + 2 * i) * NR_PITCH + kx] = wr[d][i];
             }
-        }
+        };
+        auto at = [=](int s) { return r * NR_PITCH + 4 * s + q; };
+        mlp_ring<NR_DEPTH, NR_KC>(a.K, fetch, stage, [=, &acc] { mlp_chain16(xs, ws, at, at, acc); });
         const int u = col0 + r;
         if (u < a.O) {
 #pragma unroll
@@ -152,7 +180,7 @@ __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(co
         constexpr int PER = WD_TILE * WD_KC / 256;           // 16 rows and 16 units per thread and chunk
         float xr[WD_DEPTH][PER], wr[WD_DEPTH][PER];
         const int kx = t & 31, r8 = t >> 5;
-        auto fetch = [&](int d, int k0) {
+        auto fetch = [=, &xr, &wr](int d, int k0) {
             const int k = k0 + kx;
             const bool kin = k < a.K;
 #pragma unroll
@@ -164,35 +192,26 @@ __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(co
                 wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
             }
         };
-#pragma unroll
-        for (int d = 0; d < WD_DEPTH; d++)
-            if (d * WD_KC < a.K) fetch(d, d * WD_KC);
-        for (int k0 = 0; k0 < a.K; k0 += WD_DEPTH * WD_KC) {
-#pragma unroll
-          for (int d = 0; d < WD_DEPTH; d++) {
-            const int kc = k0 + d * WD_KC;
-            if (kc >= a.K) break;                            // uniform over the workgroup
+        auto stage = [=, &xr, &wr](int d) {
 #pragma unroll
             for (int i = 0; i < PER; i++) {
                 xs[(r8 + 8 * i) * WD_PITCH + kx] = xr[d][i];
                 ws[(r8 + 8 * i) * WD_PITCH + kx] = wr[d][i];
             }
-            __syncthreads();
-            if (kc + WD_DEPTH * WD_KC < a.K) fetch(d, kc + WD_DEPTH * WD_KC);
-            if (live) {
+        };
+        auto mma = [=, &acc] {
+            if (!live) return;
 #pragma unroll
-                for (int s = 0; s < WD_KC / 2; s++) {        // two ascending k per instruction; unrolled, so the LDS reads run ahead of the MFMAs
-                    const float a0 = xs[(wr_ * 64 + c) * WD_PITCH + 2 * s + hf], a1 = xs[(wr_ * 64 + 32 + c) * WD_PITCH + 2 * s + hf];
-                    const float b0 = ws[(wc * 64 + c) * WD_PITCH + 2 * s + hf], b1 = ws[(wc * 64 + 32 + c) * WD_PITCH + 2 * s + hf];
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-                }
+            for (int s = 0; s < WD_KC / 2; s++) {            // two ascending k per instruction; unrolled, so the LDS reads run ahead of the MFMAs
+                const float a0 = xs[(wr_ * 64 + c) * WD_PITCH + 2 * s + hf], a1 = xs[(wr_ * 64 + 32 + c) * WD_PITCH + 2 * s + hf];
+                const float b0 = ws[(wc * 64 + c) * WD_PITCH + 2 * s + hf], b1 = ws[(wc * 64 + 32 + c) * WD_PITCH + 2 * s + hf];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
             }
-            __syncthreads();
-          }
-        }
+        };
+        mlp_ring<WD_DEPTH, WD_KC>(a.K, fetch, stage, mma);
         if (live) {
 #pragma unroll
             for (int n = 0; n < 2; n++) {
@@ -210,17 +229,90 @@ __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(co
     }
 }
 
+// a runtime activation as a template argument: f(std::integral_constant<int, ACT>)
+template <typename F>
+void mlp_with_act(int act, F f)
+{
+    if (act == PTG_MLP_RELU) f(std::integral_constant<int, PTG_MLP_RELU>{});
+    else if (act == PTG_MLP_TANH) f(std::integral_constant<int, PTG_MLP_TANH>{});
+    else f(std::integral_constant<int, PTG_MLP_NONE>{});
+}
+
 template <int ROUTE>
 void launch_mlp_layer(hipStream_t st, const MlpLayer& a, int act)
 {
     const int tile = ROUTE == MLP_NARROW ? NR_TILE : WD_TILE;
     const dim3 grid((unsigned)((a.B - 1) / tile + 1), (unsigned)((a.O - 1) / tile + 1)), block(ROUTE == MLP_NARROW ? 64 : 256);      // x: up to 2^27 row tiles
-    if (act == PTG_MLP_RELU) k_mlp_layer<PTG_MLP_RELU, ROUTE><<<grid, block, 0, st>>>(a);
-    else if (act == PTG_MLP_TANH) k_mlp_layer<PTG_MLP_TANH, ROUTE><<<grid, block, 0, st>>>(a);
-    else k_mlp_layer<PTG_MLP_NONE, ROUTE><<<grid, block, 0, st>>>(a);
+    mlp_with_act(act, [&](auto A) { k_mlp_layer<decltype(A)::value, ROUTE><<<grid, block, 0, st>>>(a); });
 }
 
-inline int64_t mlp_pitch(int w) { return ((int64_t)w + 3) / 4 * 4; }
+// The layout of both workspaces (include/ptg_env.h): a hidden layer and a dz buffer are [batch][pitch(l)] floats
+struct MlpLayout {
+    int64_t batch;
+    int n;
+    const int32_t* width;
+    bool in_range() const
+    {
+        if (batch < 1 || batch > (int64_t)1 << 31 || n < 1 || n > PTG_MLP_MAX_LAYERS || !width) return false;
+        for (int l = 0; l < n; l++)
+            if (width[l] < 1 || width[l] > PTG_MLP_MAX_WIDTH) return false;
+        return true;
+    }
+    int64_t pitch(int l) const { return ((int64_t)width[l] + 3) / 4 * 4; }
+    int64_t kept(int l) const            // floats of the forward's ws_dev before hidden layer l (KEEP_HIDDEN)
+    {
+        int64_t sum = 0;
+        for (int i = 0; i < l; i++) sum += batch * pitch(i);
+        return sum;
+    }
+    int64_t alt(int l, int layers) const // floats before layer l's of the two alternating buffers, each as wide as the widest of the first `layers`
+    {
+        int64_t widest = 0;
+        for (int i = 0; i < layers; i++) widest = std::max(widest, pitch(i));
+        return (l & 1) * batch * widest;
+    }
+    int64_t forward_bytes(int flags) const { return std::max<int64_t>(16, ((flags & PTG_MLP_KEEP_HIDDEN) ? kept(n - 1) : 2 * alt(1, n - 1)) * (int64_t)sizeof(float)); }
+    int64_t backward_bytes() const { return 2 * alt(1, n) * (int64_t)sizeof(float); }
+};
+
+__attribute__((format(printf, 3, 4))) bool mlp_fault(char* why, size_t cap, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(why, cap, fmt, ap);
+    va_end(ap);
+    return true;
+}
+
+// what ptg_mlp_forward refuses in a descriptor, for it and for the backward's embedded one: false when d is well-formed, else the text in why
+bool mlp_desc_fault(const ptg_mlp* d, char* why, size_t cap)
+{
+    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return mlp_fault(why, cap, "batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (d->n_layers < 1 || d->n_layers > PTG_MLP_MAX_LAYERS) return mlp_fault(why, cap, "n_layers %d outside [1, %d]", d->n_layers, PTG_MLP_MAX_LAYERS);
+    if (d->flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) return mlp_fault(why, cap, "unknown flag in %d", d->flags);
+    if ((d->flags & PTG_MLP_NARROW) && (d->flags & PTG_MLP_WIDE)) return mlp_fault(why, cap, "PTG_MLP_NARROW and PTG_MLP_WIDE exclude each other");
+    if (d->hidden_act != PTG_MLP_RELU && d->hidden_act != PTG_MLP_TANH) return mlp_fault(why, cap, "hidden_act must be PTG_MLP_RELU or PTG_MLP_TANH");
+    if (d->out_act != PTG_MLP_NONE && d->out_act != PTG_MLP_RELU && d->out_act != PTG_MLP_TANH) return mlp_fault(why, cap, "unknown out_act %d", d->out_act);
+    if (d->f1 < 1 || d->f2 < 0 || (int64_t)d->f1 + d->f2 > PTG_MLP_MAX_WIDTH)
+        return mlp_fault(why, cap, "f1 = %d, f2 = %d: need f1 >= 1, f2 >= 0, f1 + f2 <= %d", d->f1, d->f2, PTG_MLP_MAX_WIDTH);
+    if (!d->x_dev || d->x_s_n < d->f1) return mlp_fault(why, cap, "x_dev is null or x_s_n below f1 = %d", d->f1);
+    if ((d->x2_dev != nullptr) != (d->f2 > 0)) return mlp_fault(why, cap, "x2_dev and f2 > 0 go together");
+    if (d->x2_dev && d->x2_s_n < d->f2) return mlp_fault(why, cap, "x2_s_n below f2 = %d", d->f2);
+    const int n = d->n_layers;
+    int fan_in = d->f1 + d->f2;
+    for (int l = 0; l < n; l++) {
+        if (d->width[l] < 1 || d->width[l] > PTG_MLP_MAX_WIDTH) return mlp_fault(why, cap, "width[%d] = %d outside [1, %d]", l, d->width[l], PTG_MLP_MAX_WIDTH);
+        if (!d->w_dev[l] || !d->b_dev[l]) return mlp_fault(why, cap, "null w_dev or b_dev [%d]", l);
+        if (d->w_s_n[l] < fan_in) return mlp_fault(why, cap, "w_s_n[%d] below the fan-in %d", l, fan_in);
+        fan_in = d->width[l];
+    }
+    if (!d->out_dev || (uintptr_t)d->out_dev % sizeof(float) != 0) return mlp_fault(why, cap, "out_dev is null or not aligned to 4 bytes");
+    if (d->out_s_n < d->width[n - 1]) return mlp_fault(why, cap, "out_s_n below the output width %d", d->width[n - 1]);
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(float) != 0) return mlp_fault(why, cap, "ws_dev is null or not aligned to 4 bytes");
+    const int64_t need = MlpLayout{d->batch, n, d->width}.forward_bytes(d->flags);
+    if (d->ws_bytes < need) return mlp_fault(why, cap, "ws_bytes = %lld, the call needs %lld", (long long)d->ws_bytes, (long long)need);
+    return false;
+}
 
 }  // namespace
 
@@ -228,75 +320,40 @@ extern "C" {
 
 int64_t ptg_mlp_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags)
 {
-    if (batch < 1 || batch > (int64_t)1 << 31 || n_layers < 1 || n_layers > PTG_MLP_MAX_LAYERS || !widths) return PTG_E_INVALID;
-    if (flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) return PTG_E_INVALID;
-    if ((flags & PTG_MLP_NARROW) && (flags & PTG_MLP_WIDE)) return PTG_E_INVALID;
-    int64_t sum = 0, widest = 0;
-    for (int l = 0; l < n_layers; l++) {
-        if (widths[l] < 1 || widths[l] > PTG_MLP_MAX_WIDTH) return PTG_E_INVALID;
-        if (l < n_layers - 1) {
-            sum += mlp_pitch(widths[l]);
-            widest = std::max(widest, mlp_pitch(widths[l]));
-        }
-    }
-    const int64_t floats = (flags & PTG_MLP_KEEP_HIDDEN) ? batch * sum : 2 * batch * widest;
-    return std::max<int64_t>(16, floats * (int64_t)sizeof(float));
+    const MlpLayout lay{batch, n_layers, widths};
+    if (!lay.in_range() || (flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) || ((flags & PTG_MLP_NARROW) && (flags & PTG_MLP_WIDE))) return PTG_E_INVALID;
+    return lay.forward_bytes(flags);
 }
 
 int ptg_mlp_forward(ptg_env* h, const ptg_mlp* d, void* stream)
 {
     if (!h) return PTG_E_INVALID;
     if (!d) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: null descriptor");
-    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: batch %lld outside [1, 2^31]", (long long)d->batch);
-    if (d->n_layers < 1 || d->n_layers > PTG_MLP_MAX_LAYERS) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: n_layers %d outside [1, %d]", d->n_layers, PTG_MLP_MAX_LAYERS);
-    if (d->flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: unknown flag in %d", d->flags);
-    if ((d->flags & PTG_MLP_NARROW) && (d->flags & PTG_MLP_WIDE)) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: PTG_MLP_NARROW and PTG_MLP_WIDE exclude each other");
-    if (d->hidden_act != PTG_MLP_RELU && d->hidden_act != PTG_MLP_TANH) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: hidden_act must be PTG_MLP_RELU or PTG_MLP_TANH");
-    if (d->out_act != PTG_MLP_NONE && d->out_act != PTG_MLP_RELU && d->out_act != PTG_MLP_TANH) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: unknown out_act %d", d->out_act);
-    if (d->f1 < 1 || d->f2 < 0 || (int64_t)d->f1 + d->f2 > PTG_MLP_MAX_WIDTH)
-        return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: f1 = %d, f2 = %d: need f1 >= 1, f2 >= 0, f1 + f2 <= %d", d->f1, d->f2, PTG_MLP_MAX_WIDTH);
-    if (!d->x_dev || d->x_s_n < d->f1) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: x_dev is null or x_s_n below f1 = %d", d->f1);
-    if ((d->x2_dev != nullptr) != (d->f2 > 0)) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: x2_dev and f2 > 0 go together");
-    if (d->x2_dev && d->x2_s_n < d->f2) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: x2_s_n below f2 = %d", d->f2);
-    const int n = d->n_layers;
-    int fan_in = d->f1 + d->f2;
-    for (int l = 0; l < n; l++) {
-        if (d->width[l] < 1 || d->width[l] > PTG_MLP_MAX_WIDTH) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: width[%d] = %d outside [1, %d]", l, d->width[l], PTG_MLP_MAX_WIDTH);
-        if (!d->w_dev[l] || !d->b_dev[l]) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: null w_dev or b_dev [%d]", l);
-        if (d->w_s_n[l] < fan_in) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: w_s_n[%d] below the fan-in %d", l, fan_in);
-        fan_in = d->width[l];
-    }
-    if (!d->out_dev || (uintptr_t)d->out_dev % sizeof(float) != 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: out_dev is null or not aligned to 4 bytes");
-    if (d->out_s_n < d->width[n - 1]) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: out_s_n below the output width %d", d->width[n - 1]);
-    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(float) != 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: ws_dev is null or not aligned to 4 bytes");
-    const int64_t need = ptg_mlp_workspace(d->batch, n, d->width, d->flags);
-    if (d->ws_bytes < need) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: ws_bytes = %lld, the call needs %lld", (long long)d->ws_bytes, (long long)need);
+    char why[160];
+    if (mlp_desc_fault(d, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: %s", why);
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
+    const int n = d->n_layers;
+    const MlpLayout lay{d->batch, n, d->width};
     const bool keep = (d->flags & PTG_MLP_KEEP_HIDDEN) != 0;
-    const size_t B = (size_t)d->batch;
-    size_t widest = 0;
-    for (int l = 0; l < n - 1; l++) widest = std::max(widest, (size_t)mlp_pitch(d->width[l]));
     MlpLayer a{};
-    a.B = B;
+    a.B = (size_t)d->batch;
     a.x = d->x_dev; a.x_s = (size_t)d->x_s_n; a.x2 = d->x2_dev ? d->x2_dev : d->x_dev; a.x2_s = (size_t)d->x2_s_n;
     a.F1 = d->f1; a.K = d->f1 + d->f2;
-    size_t kept = 0;                                         // floats of ws_dev before hidden layer l (KEEP_HIDDEN)
     for (int l = 0; l < n; l++) {
         const bool last = l == n - 1;
         a.w = d->w_dev[l]; a.w_s = (size_t)d->w_s_n[l]; a.bias = d->b_dev[l]; a.O = d->width[l];
         if (last) {
             a.y = d->out_dev; a.y_s = (size_t)d->out_s_n;
         } else {
-            a.y = (float*)d->ws_dev + (keep ? kept : (size_t)(l & 1) * B * widest);
-            a.y_s = (size_t)mlp_pitch(d->width[l]);
+            a.y = (float*)d->ws_dev + (keep ? lay.kept(l) : lay.alt(l, n - 1));
+            a.y_s = (size_t)lay.pitch(l);
         }
         const int act = last ? d->out_act : d->hidden_act;
         const bool wide = (d->flags & PTG_MLP_WIDE) || (!(d->flags & PTG_MLP_NARROW) && ((d->batch >= MLP_WIDE_MIN_ROWS && a.O > MLP_WIDE_MIN_UNITS) || (d->batch >= MLP_WIDE_MIN_ROWS_BROAD && a.O > MLP_BROAD_UNITS)));
         if (wide) launch_mlp_layer<MLP_WIDE>(st, a, act);
         else launch_mlp_layer<MLP_NARROW>(st, a, act);
         if (int rc = launch_check(h, "k_mlp_layer")) return rc;
-        kept += B * a.y_s;
         a.x = a.x2 = a.y; a.x_s = a.y_s; a.x2_s = 0; a.F1 = a.K = a.O;      // this layer's output is the next one's input
     }
     return 0;
@@ -305,9 +362,9 @@ int ptg_mlp_forward(ptg_env* h, const ptg_mlp* d, void* stream)
 }  // extern "C"
 
 // ---- the backward pass (include/ptg_env.h, ptg_mlp_backward, states the arithmetic) ---------------------------------
-// Two kernels per layer on v_mfma_f32_16x16x4_f32, one wave per workgroup, a 16 x 16 tile, the reduction in chunks of 32 through LDS with
-// the forward's ring of chunks in flight (four in k_mlp_dx, two in k_mlp_dw).  The lane maps are the forward's; what changes is which tensor
-// index rides on which:
+// Two kernels per layer on v_mfma_f32_16x16x4_f32, one wave per workgroup, a 16 x 16 tile, the reduction through mlp_ring and mlp_chain16
+// as in the NARROW route (four chunks in flight in k_mlp_dx, two in k_mlp_dw).  The lane maps are the forward's; what a kernel plugs in is
+// which tensor index rides on which:
 //   k_mlp_dx   D[b][k] = sum_j dz[b][j] W[j][k]:  A[l & 15][l >> 4] = dz[row0 + (l & 15)][j0 + (l >> 4)] (staged [row][j], pitch 36, as the
 //              forward's input), B[l >> 4][l & 15] = W[j0 + (l >> 4)][col0 + (l & 15)] (staged [j][k], pitch 16: the word of a read is
 //              16 (4 s + q) + r, 64 lanes on 64 banks; W's rows are read along k, 16 neighbouring floats of each of four rows per load)
@@ -321,7 +378,7 @@ namespace {
 #define PTG_MLP_DW_DEPTH 2               // an experiment build may set 4: 224 registers instead of 118, two waves per SIMD instead of four
 #endif
 constexpr int BW_TILE = 16, BW_RC = 32, BW_DEPTH = 4, BW_PITCH_T = 16;      // tile, reduction chunk, chunks in flight in k_mlp_dx, pitch of a [reduction][16] stage
-constexpr int DW_DEPTH = PTG_MLP_DW_DEPTH;                                  // chunks in flight in k_mlp_dw
+static_assert(BW_RC == NR_KC, "mlp_chain16 consumes chunks of NR_KC");
 
 struct MlpDx {                           // by value in the launch
     const float* dz; size_t dz_s;        // [B][O], the gradient at this layer's pre-activation
@@ -372,7 +429,7 @@ __global__ __launch_bounds__(64) void k_mlp_dx(const MlpDx a)
     float zr[BW_DEPTH][PER], wr[BW_DEPTH][PER];
     const int jx = lane & 31, r2 = lane >> 5;
     const int kw = col0 + r, kwc = min(kw, a.K - 1);
-    auto fetch = [&](int d, int j0) {                        // dz: j = j0 + jx of every second row;  W: column kw of every fourth row j
+    auto fetch = [=, &zr, &wr](int d, int j0) {              // dz: j = j0 + jx of every second row;  W: column kw of every fourth row j
         const int j = j0 + jx, jc = min(j, a.O - 1);
         const bool jin = j < a.O;
 #pragma unroll
@@ -385,33 +442,16 @@ __global__ __launch_bounds__(64) void k_mlp_dx(const MlpDx a)
             wr[d][i] = jw < a.O && kw < a.K ? w : 0.0f;
         }
     };
+    auto stage = [=, &zr, &wr](int d) {
 #pragma unroll
-    for (int d = 0; d < BW_DEPTH; d++)
-        if (d * BW_RC < a.O) fetch(d, d * BW_RC);
-    for (int j0 = 0; j0 < a.O; j0 += BW_DEPTH * BW_RC) {
-#pragma unroll
-        for (int d = 0; d < BW_DEPTH; d++) {
-            const int jc = j0 + d * BW_RC;
-            if (jc >= a.O) break;                            // uniform over the workgroup
-#pragma unroll
-            for (int i = 0; i < PER; i++) {
-                zs[(r2 + 2 * i) * NR_PITCH + jx] = zr[d][i];
-                wt[(q + 4 * i) * BW_PITCH_T + r] = wr[d][i];
-            }
-            __syncthreads();
-            if (jc + BW_DEPTH * BW_RC < a.O) fetch(d, jc + BW_DEPTH * BW_RC);
-            float av[BW_RC / 4], bv[BW_RC / 4];
-#pragma unroll
-            for (int s = 0; s < BW_RC / 4; s++) {
-                av[s] = zs[r * NR_PITCH + 4 * s + q];
-                bv[s] = wt[(4 * s + q) * BW_PITCH_T + r];
-            }
-#pragma unroll
-            for (int s = 0; s < BW_RC / 4; s++)              // four ascending j per instruction
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
-            __syncthreads();
+        for (int i = 0; i < PER; i++) {
+            zs[(r2 + 2 * i) * NR_PITCH + jx] = zr[d][i];
+            wt[(q + 4 * i) * BW_PITCH_T + r] = wr[d][i];
         }
-    }
+    };
+    mlp_ring<BW_DEPTH, BW_RC>(a.O, fetch, stage, [=, &acc] {
+        mlp_chain16(zs, wt, [=](int s) { return r * NR_PITCH + 4 * s + q; }, [=](int s) { return (4 * s + q) * BW_PITCH_T + r; }, acc);
+    });
     if (kw < a.K) {
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -442,12 +482,14 @@ __global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
             if (j < a.O) acc[g] = ko < a.K ? a.dw[(size_t)j * a.dw_s + (size_t)ko] : a.db[j];
         }
     }
-    constexpr int PER = BW_TILE * BW_RC / 64;                // 8 rows per lane and chunk
-    float zr[DW_DEPTH][PER], xr[DW_DEPTH][PER];
+    constexpr int DEPTH = PTG_MLP_DW_DEPTH, PER = BW_TILE * BW_RC / 64;      // chunks in flight; 8 rows per lane and chunk
+    float zr[DEPTH][PER], xr[DEPTH][PER];
     const int jz = j0 + r, jzc = min(jz, a.O - 1), kc = min(ko, a.K - 1);
     const bool one = ko == a.K;
     const float* xp = kc < a.F1 ? a.x + (size_t)kc : a.x2 + (size_t)(kc - a.F1);
     const size_t xps = kc < a.F1 ? a.x_s : a.x2_s;
+    // captures by reference, against mlp_ring's rule: by value the compiler moves the address products into the loop (72 registers
+    // instead of 120, 3 - 4 % more time at B = 257 .. 658, profiles/mlp_ring_ab.txt); its prologue is short either way
     auto fetch = [&](int d, size_t b0) {                     // lane: unit jz and column ko of every fourth row
 #pragma unroll
         for (int i = 0; i < PER; i++) {
@@ -459,33 +501,15 @@ __global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
             xr[d][i] = rin && ko <= a.K ? (one ? 1.0f : x) : 0.0f;
         }
     };
+    auto stage = [&](int d) {
 #pragma unroll
-    for (int d = 0; d < DW_DEPTH; d++)
-        if ((size_t)(d * BW_RC) < a.B) fetch(d, (size_t)(d * BW_RC));
-    for (size_t b0 = 0; b0 < a.B; b0 += DW_DEPTH * BW_RC) {
-#pragma unroll
-        for (int d = 0; d < DW_DEPTH; d++) {
-            const size_t bc = b0 + d * BW_RC;
-            if (bc >= a.B) break;                            // uniform over the workgroup
-#pragma unroll
-            for (int i = 0; i < PER; i++) {
-                zs[(q + 4 * i) * BW_PITCH_T + r] = zr[d][i];
-                xs[(q + 4 * i) * BW_PITCH_T + r] = xr[d][i];
-            }
-            __syncthreads();
-            if (bc + DW_DEPTH * BW_RC < a.B) fetch(d, bc + DW_DEPTH * BW_RC);
-            float av[BW_RC / 4], bv[BW_RC / 4];
-#pragma unroll
-            for (int s = 0; s < BW_RC / 4; s++) {            // A transposed out of LDS: row of the stage = reduction index
-                av[s] = zs[(4 * s + q) * BW_PITCH_T + r];
-                bv[s] = xs[(4 * s + q) * BW_PITCH_T + r];
-            }
-#pragma unroll
-            for (int s = 0; s < BW_RC / 4; s++)              // four ascending b per instruction
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
-            __syncthreads();
+        for (int i = 0; i < PER; i++) {
+            zs[(q + 4 * i) * BW_PITCH_T + r] = zr[d][i];
+            xs[(q + 4 * i) * BW_PITCH_T + r] = xr[d][i];
         }
-    }
+    };
+    auto at = [&](int s) { return (4 * s + q) * BW_PITCH_T + r; };      // A transposed out of LDS: row of the stage = reduction index
+    mlp_ring<DEPTH, BW_RC>(a.B, fetch, stage, [&] { mlp_chain16(zs, xs, at, at, acc); });
     if (ko <= a.K) {
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -507,47 +531,14 @@ __global__ __launch_bounds__(256) void k_mlp_dz_out(const MlpDzOut a)
     }
 }
 
-// what ptg_mlp_forward refuses in a descriptor, restated for the embedded one: NULL when it is well-formed
-const char* mlp_desc_fault(const ptg_mlp* d)
-{
-    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return "batch outside [1, 2^31]";
-    if (d->n_layers < 1 || d->n_layers > PTG_MLP_MAX_LAYERS) return "n_layers outside [1, PTG_MLP_MAX_LAYERS]";
-    if (d->flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) return "unknown flag in the forward's flags";
-    if ((d->flags & PTG_MLP_NARROW) && (d->flags & PTG_MLP_WIDE)) return "PTG_MLP_NARROW and PTG_MLP_WIDE exclude each other";
-    if (d->hidden_act != PTG_MLP_RELU && d->hidden_act != PTG_MLP_TANH) return "hidden_act must be PTG_MLP_RELU or PTG_MLP_TANH";
-    if (d->out_act != PTG_MLP_NONE && d->out_act != PTG_MLP_RELU && d->out_act != PTG_MLP_TANH) return "unknown out_act";
-    if (d->f1 < 1 || d->f2 < 0 || (int64_t)d->f1 + d->f2 > PTG_MLP_MAX_WIDTH) return "need f1 >= 1, f2 >= 0, f1 + f2 <= PTG_MLP_MAX_WIDTH";
-    if (!d->x_dev || d->x_s_n < d->f1) return "x_dev is null or x_s_n below f1";
-    if ((d->x2_dev != nullptr) != (d->f2 > 0)) return "x2_dev and f2 > 0 go together";
-    if (d->x2_dev && d->x2_s_n < d->f2) return "x2_s_n below f2";
-    int fan_in = d->f1 + d->f2;
-    for (int l = 0; l < d->n_layers; l++) {
-        if (d->width[l] < 1 || d->width[l] > PTG_MLP_MAX_WIDTH) return "a width outside [1, PTG_MLP_MAX_WIDTH]";
-        if (!d->w_dev[l] || !d->b_dev[l]) return "a null w_dev or b_dev";
-        if (d->w_s_n[l] < fan_in) return "a w_s_n below the fan-in";
-        fan_in = d->width[l];
-    }
-    if (!d->out_dev || (uintptr_t)d->out_dev % sizeof(float) != 0) return "out_dev is null or not aligned to 4 bytes";
-    if (d->out_s_n < d->width[d->n_layers - 1]) return "out_s_n below the output width";
-    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(float) != 0) return "ws_dev is null or not aligned to 4 bytes";
-    if (d->ws_bytes < ptg_mlp_workspace(d->batch, d->n_layers, d->width, d->flags)) return "ws_bytes below what ptg_mlp_workspace returns";
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" {
 
 int64_t ptg_mlp_backward_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags)
 {
-    if (batch < 1 || batch > (int64_t)1 << 31 || n_layers < 1 || n_layers > PTG_MLP_MAX_LAYERS || !widths) return PTG_E_INVALID;
-    if (flags & ~PTG_MLP_ACCUMULATE) return PTG_E_INVALID;
-    int64_t widest = 0;
-    for (int l = 0; l < n_layers; l++) {
-        if (widths[l] < 1 || widths[l] > PTG_MLP_MAX_WIDTH) return PTG_E_INVALID;
-        widest = std::max(widest, mlp_pitch(widths[l]));
-    }
-    return 2 * batch * widest * (int64_t)sizeof(float);
+    const MlpLayout lay{batch, n_layers, widths};
+    return !lay.in_range() || (flags & ~PTG_MLP_ACCUMULATE) ? PTG_E_INVALID : lay.backward_bytes();
 }
 
 int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
@@ -555,7 +546,8 @@ int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
     if (!h) return PTG_E_INVALID;
     if (!d) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: null descriptor");
     const ptg_mlp* f = &d->fwd;
-    if (const char* why = mlp_desc_fault(f)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor: %s", why);
+    char why[160];
+    if (mlp_desc_fault(f, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor: %s", why);
     if (!(f->flags & PTG_MLP_KEEP_HIDDEN)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor must carry PTG_MLP_KEEP_HIDDEN");
     if (d->flags & ~PTG_MLP_ACCUMULATE) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: unknown flag in %d", d->flags);
     const int n = f->n_layers;
@@ -570,32 +562,27 @@ int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
     if (d->dx2_dev && f->f2 == 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx2_dev without a second input piece");
     if (d->dx2_dev && d->dx2_s_n < f->f2) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx2_s_n below f2 = %d", f->f2);
     if (!d->bws_dev || (uintptr_t)d->bws_dev % sizeof(float) != 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: bws_dev is null or not aligned to 4 bytes");
-    const int64_t need = ptg_mlp_backward_workspace(f->batch, n, f->width, d->flags);
+    const MlpLayout lay{f->batch, n, f->width};
+    const int64_t need = lay.backward_bytes();
     if (d->bws_bytes < need) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: bws_bytes = %lld, the call needs %lld", (long long)d->bws_bytes, (long long)need);
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
     const size_t B = (size_t)f->batch;
-    size_t widest = 0, kept[PTG_MLP_MAX_LAYERS + 1] = {0};   // kept[l]: floats of ws_dev before hidden layer l
-    for (int l = 0; l < n; l++) {
-        widest = std::max(widest, (size_t)mlp_pitch(f->width[l]));
-        kept[l + 1] = kept[l] + B * (size_t)mlp_pitch(f->width[l]);
-    }
-    auto buf = [&](int l) { return (float*)d->bws_dev + (size_t)(l & 1) * B * widest; };      // dz of layer l, row stride P(width[l])
+    auto buf = [&](int l) { return (float*)d->bws_dev + lay.alt(l, n); };      // dz of layer l, row stride pitch(l)
     const float* dz = d->gout_dev;
     size_t dz_s = (size_t)d->gout_s_n;
     if (f->out_act != PTG_MLP_NONE) {
-        MlpDzOut e{d->gout_dev, (size_t)d->gout_s_n, f->out_dev, (size_t)f->out_s_n, buf(n - 1), (size_t)mlp_pitch(f->width[n - 1]), B, f->width[n - 1]};
+        MlpDzOut e{d->gout_dev, (size_t)d->gout_s_n, f->out_dev, (size_t)f->out_s_n, buf(n - 1), (size_t)lay.pitch(n - 1), B, f->width[n - 1]};
         const size_t total = B * (size_t)e.O;
         const unsigned blocks = (unsigned)std::min<size_t>((total - 1) / 256 + 1, 65536);
-        if (f->out_act == PTG_MLP_RELU) k_mlp_dz_out<PTG_MLP_RELU><<<blocks, 256, 0, st>>>(e);
-        else k_mlp_dz_out<PTG_MLP_TANH><<<blocks, 256, 0, st>>>(e);
+        mlp_with_act(f->out_act, [&](auto A) { k_mlp_dz_out<decltype(A)::value><<<blocks, 256, 0, st>>>(e); });
         if (int rc = launch_check(h, "k_mlp_dz_out")) return rc;
         dz = e.dz; dz_s = e.dz_s;
     }
     for (int l = n - 1; l >= 0; l--) {
         const int O = f->width[l], K = l ? f->width[l - 1] : f->f1 + f->f2;
-        const float* x = l ? (const float*)f->ws_dev + kept[l - 1] : f->x_dev;      // the layer's input: hidden layer l - 1, or the call's
-        const size_t x_s = l ? (size_t)mlp_pitch(K) : (size_t)f->x_s_n;
+        const float* x = l ? (const float*)f->ws_dev + lay.kept(l - 1) : f->x_dev;      // the layer's input: hidden layer l - 1, or the call's
+        const size_t x_s = l ? (size_t)lay.pitch(l - 1) : (size_t)f->x_s_n;
         if (d->dw_dev[l]) {
             MlpDw a{};
             a.dz = dz; a.dz_s = dz_s; a.x = x; a.x_s = x_s; a.B = B; a.K = K; a.O = O;
@@ -608,15 +595,13 @@ int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
         MlpDx a{};
         a.dz = dz; a.dz_s = dz_s; a.w = f->w_dev[l]; a.w_s = (size_t)f->w_s_n[l]; a.B = B; a.K = K; a.O = O;
         const dim3 grid((unsigned)((B - 1) / BW_TILE + 1), (unsigned)((K - 1) / BW_TILE + 1));
-        if (l) {
+        if (l) {                         // dz of the layer below, through the derivative of the hidden activation on its kept output
             a.h = x; a.h_s = x_s; a.y = buf(l - 1); a.y_s = x_s; a.F1 = K;
-            if (f->hidden_act == PTG_MLP_RELU) k_mlp_dx<PTG_MLP_RELU><<<grid, 64, 0, st>>>(a);
-            else k_mlp_dx<PTG_MLP_TANH><<<grid, 64, 0, st>>>(a);
             dz = a.y; dz_s = a.y_s;
         } else {
             a.y = d->dx_dev; a.y_s = (size_t)d->dx_s_n; a.y2 = d->dx2_dev; a.y2_s = (size_t)d->dx2_s_n; a.F1 = f->f1;
-            k_mlp_dx<PTG_MLP_NONE><<<grid, 64, 0, st>>>(a);
         }
+        mlp_with_act(l ? f->hidden_act : PTG_MLP_NONE, [&](auto A) { k_mlp_dx<decltype(A)::value><<<grid, 64, 0, st>>>(a); });
         if (int rc = launch_check(h, "k_mlp_dx")) return rc;
     }
     return 0;

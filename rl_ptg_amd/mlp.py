@@ -71,20 +71,24 @@ def parse_mlp(modules):
     return linears, (hidden.pop() if hidden else "relu"), acts[-1]
 
 
-class DeviceMLP:
+class _NetBuffers:
+    """What DeviceMLP and TrainMLP share: the parsed net, held by reference and checked to be contiguous and on the engine's device, and
+    the output and the forward's workspace for `batch` rows.  The messages carry the subclass's name."""
+
     def __init__(self, engine, modules, batch, hidden=False):
         """engine: the HipEngine whose device and library serve the calls; modules: see parse_mlp; batch: the most rows a call takes;
         hidden: keep the post-activation hidden layers of the last call in `self.hidden` (views into the workspace: what a backward
         pass would read)."""
+        who = type(self).__name__
         self.engine = engine
         self.linears, self.hidden_activation, self.out_activation = parse_mlp(modules)
         for l, m in enumerate(self.linears):
             if not m.weight.is_contiguous() or not m.bias.is_contiguous():
-                raise ValueError(f"DeviceMLP: the parameters of Linear {l} must be contiguous, got weight strides {tuple(m.weight.stride())}")
+                raise ValueError(f"{who}: the parameters of Linear {l} must be contiguous, got weight strides {tuple(m.weight.stride())}")
         for l, m in enumerate(self.linears):
             for p in (m.weight, m.bias):
                 if p.device != engine.device:
-                    raise ValueError(f"DeviceMLP: Linear {l} lives on {p.device}, the engine on {engine.device}")
+                    raise ValueError(f"{who}: Linear {l} lives on {p.device}, the engine on {engine.device}")
         self.batch = int(batch)
         self.widths = [m.out_features for m in self.linears]
         self.in_features = self.linears[0].in_features
@@ -95,12 +99,19 @@ class DeviceMLP:
             self.out = torch.empty((self.batch, self.widths[-1]), dtype=torch.float32, device=engine.device)
         self.hidden = None
 
+    def _rows(self, x):
+        """the rows of a [B, F] tensor, at most `batch`; None for what mlp_forward refuses itself"""
+        B = x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else None
+        if B is not None and B > self.batch:
+            raise ValueError(f"{type(self).__name__}: {B} rows, allocated for {self.batch}")
+        return B
+
+
+class DeviceMLP(_NetBuffers):
     def __call__(self, x, x2=None):
         """x [B, F1] (and x2 [B, F2]) float32 with B <= batch -> the output [B, O]: the first B rows of the preallocated tensor, which
         the next call overwrites.  Reads the parameters where they are now."""
-        B = x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else None
-        if B is not None and B > self.batch:
-            raise ValueError(f"DeviceMLP: {B} rows, allocated for {self.batch}")
+        B = self._rows(x)
         res = self.engine.mlp_forward(x, [m.weight.detach() for m in self.linears], [m.bias.detach() for m in self.linears],
                                       hidden_activation=self.hidden_activation, out_activation=self.out_activation, x2=x2,
                                       out=None if B is None else self.out[:B], workspace=self.workspace, keep_hidden=self.keep_hidden)
@@ -113,9 +124,7 @@ class _TrainMLPFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, x, x2, *params):
-        B = x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else None
-        if B is not None and B > net.batch:
-            raise ValueError(f"TrainMLP: {B} rows, allocated for {net.batch}")
+        B = net._rows(x)
         xd, x2d = (x.detach() if torch.is_tensor(x) else x), (x2.detach() if torch.is_tensor(x2) else x2)
         res = net.engine.mlp_forward(xd, [p.detach() for p in params[0::2]], [p.detach() for p in params[1::2]], hidden_activation=net.hidden_activation,
                                      out_activation=net.out_activation, x2=x2d, out=None if B is None else net.out[:B], workspace=net.workspace,
@@ -152,7 +161,7 @@ class _TrainMLPFunction(torch.autograd.Function):
         return (None, gx, gx2, *grads)
 
 
-class TrainMLP:
+class TrainMLP(_NetBuffers):
     """The training forward and backward of a torch MLP under autograd, on the project's kernels (HipEngine.mlp_forward with keep_hidden and
     HipEngine.mlp_backward; include/ptg_env.h states both arithmetics, DESIGN.md section 19 the design).
 
@@ -178,29 +187,15 @@ class TrainMLP:
     miss; a captured gradient step calls mlp_forward and mlp_backward directly.  What the route gives at every shape is the fixed order."""
 
     def __init__(self, engine, modules, batch):
-        self.engine = engine
-        self.linears, self.hidden_activation, self.out_activation = parse_mlp(modules)
-        for l, m in enumerate(self.linears):
-            if not m.weight.is_contiguous() or not m.bias.is_contiguous():
-                raise ValueError(f"TrainMLP: the parameters of Linear {l} must be contiguous, got weight strides {tuple(m.weight.stride())}")
-        for l, m in enumerate(self.linears):
-            for p in (m.weight, m.bias):
-                if p.device != engine.device:
-                    raise ValueError(f"TrainMLP: Linear {l} lives on {p.device}, the engine on {engine.device}")
-        self.batch = int(batch)
-        self.widths = [m.out_features for m in self.linears]
-        self.in_features = self.linears[0].in_features
-        nbytes = engine.mlp_workspace(self.batch, self.widths, True)      # ValueError for a batch or a width out of range
+        super().__init__(engine, modules, batch, hidden=True)
         nback = engine.mlp_backward_workspace(self.batch, self.widths)
         dev = engine.device
         with engine._torch.cuda.device(dev):
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             self.backward_workspace = torch.empty(nback, dtype=torch.uint8, device=dev)
-            self.out = torch.empty((self.batch, self.widths[-1]), dtype=torch.float32, device=dev)
             self.grad_input = torch.empty((self.batch, self.in_features), dtype=torch.float32, device=dev)
             self.grad_weights = [torch.empty_like(m.weight, requires_grad=False) for m in self.linears]
             self.grad_biases = [torch.empty_like(m.bias, requires_grad=False) for m in self.linears]
-        self.hidden, self._views = None, None
+        self._views = None
         self.calls = 0
 
     def parameters(self):

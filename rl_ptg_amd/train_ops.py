@@ -9,8 +9,8 @@ Every tensor argument goes through ONE checker, check(), which raises in a fixed
 tensor, a refused dtype, element size or element count), then ValueError for its shape, its strides, its device.  Nothing touches
 the library and no device memory is allocated before every check of a call has passed.  Relations between arguments (old_values
 iff clip_range_vf, done_col inside the columns ...) stay plain `if`s in the methods.  The blocks several ops share (_column,
-_critic_columns, _alpha_arg, _out_tuple, _no_tensor_twice; TrainOps._take_workspace, _fresh_like_quantiles, _call) stand once, next
-to check(), and are called at the point of the order where each op had its own copy."""
+_critic_columns, _alpha_arg, _out_tuple, _no_tensor_twice, _workspace_arg; TrainOps._take_workspace, _fresh_like_quantiles, _mlp_net,
+_call) stand once, next to check(), and are called at the point of the order where each op had its own copy."""
 import collections
 import ctypes as C
 
@@ -173,6 +173,36 @@ def _out_code(torch, dtype):
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# ------------------------------------------------------------------ what mlp_forward and mlp_backward share (TrainOps._mlp_net too)
+def _pitch(w):
+    """floats per row of a kept hidden layer and of a dz buffer: the width rounded up to 16 bytes (include/ptg_env.h)"""
+    return (w + 3) // 4 * 4
+
+
+def _row_stride(t):
+    """of a [B, A] tensor; a one-row tensor may report any row stride"""
+    return max(t.stride(0), t.shape[1])
+
+
+def _mlp_range(who, batch, widths):
+    """(batch, widths) as ints, once they lie in the range the library's *_workspace functions accept"""
+    widths = [int(w) for w in widths]
+    if not (1 <= int(batch) <= 2 ** 31 and 1 <= len(widths) <= _lib.MLP_MAX_LAYERS and all(1 <= w <= _lib.MLP_MAX_WIDTH for w in widths)):
+        raise ValueError(f"{who}: batch must be in [1, 2^31], 1 to {_lib.MLP_MAX_LAYERS} layers, widths in [1, {_lib.MLP_MAX_WIDTH}]; got {batch}, {widths}")
+    return int(batch), widths
+
+
+def _workspace_arg(eng, who, label, t, need, needs="the call needs"):
+    """a caller's MLP workspace -- label: its name, then in brackets the call that sizes it -- must be a contiguous uint8 tensor of
+    `need` bytes or more, 4-byte aligned.  (_take_workspace asks the library for the size and knows no alignment: the loss ops' own.)"""
+    name = label.split(" ")[0]
+    check(eng, who, label, t, dtypes=(eng._torch.uint8,), shape=(None,), rule=contiguous, exc=ValueError)
+    if t.numel() < need:
+        raise ValueError(f"{who}: {name} has {t.numel()} bytes, {needs} {need}")
+    if t.data_ptr() % 4:
+        raise ValueError(f"{who}: {name} must be 4-byte aligned")
 
 
 class TrainOps:
@@ -1066,116 +1096,16 @@ class TrainOps:
     def mlp_workspace(self, batch, widths, keep_hidden=False):
         """bytes of device scratch mlp_forward needs for `batch` rows of a net with these layer widths: what ptg_mlp_workspace returns
         (include/ptg_env.h documents the layout), computed here so that the argument checks need no library"""
-        widths = [int(w) for w in widths]
-        if not (1 <= int(batch) <= 2 ** 31 and 1 <= len(widths) <= _lib.MLP_MAX_LAYERS and all(1 <= w <= _lib.MLP_MAX_WIDTH for w in widths)):
-            raise ValueError(f"mlp_workspace: batch must be in [1, 2^31], 1 to {_lib.MLP_MAX_LAYERS} layers, widths in [1, {_lib.MLP_MAX_WIDTH}]; got {batch}, {widths}")
-        pitches = [(w + 3) // 4 * 4 for w in widths[:-1]]
-        floats = int(batch) * sum(pitches) if keep_hidden else 2 * int(batch) * max(pitches, default=0)
-        return max(16, 4 * floats)
+        batch, widths = _mlp_range("mlp_workspace", batch, widths)
+        pitches = [_pitch(w) for w in widths[:-1]]
+        return max(16, 4 * batch * (sum(pitches) if keep_hidden else 2 * max(pitches, default=0)))
 
-    def mlp_forward(self, x, weights, biases, hidden_activation="relu", out_activation=None, x2=None, out=None, workspace=None, keep_hidden=False,
-                    _route=None):
-        """Enqueue, on the current stream, the forward pass of an MLP without autograd: one fused launch per layer (include/ptg_env.h:
-        ptg_mlp_forward, which states the arithmetic -- per unit a float32 fmaf chain from the bias over ascending k, then the activation).
-        x [B, F1] float32 with unit column stride and a row stride >= F1 (a column slice of a wider tensor fits); x2 [B, F2] likewise, or
-        None: the net reads th.cat([x, x2], 1) without the cat.  weights[l] [out_l, in_l] float32 in torch's Linear.weight layout with
-        unit column stride, biases[l] [out_l] contiguous; in_0 = F1 + F2, in_l = out_(l-1); 1 to 10 layers, every width and the fan-in in
-        [1, 1024].  hidden_activation "relu" | "tanh" after every layer but the last, out_activation None | "relu" | "tanh" after the last.
-        out: [B, O] float32 with unit column stride and a row stride >= O, allocated when None.  workspace: a contiguous uint8 tensor
-        of at least mlp_workspace(B, widths, keep_hidden) bytes, 4-byte aligned, allocated when None.  keep_hidden: the post-activation
-        hidden layers stay in the workspace and are returned as views into it.  Returns MlpOut(out, hidden): hidden a tuple of n - 1
-        [B, width_l] views, or None.  No synchronisation and, with out= and workspace=, no allocation; a -0 result may come out as +0.
-        `_route` ("narrow" | "wide") forces one tile route in every layer: for tests and measurements, the bits do not depend on it."""
+    def _mlp_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, route=None, first=(), grad_weights=None, grad_biases=None):
+        """The checks of a net that mlp_forward and mlp_backward share, in their one order: TypeError for what every value is (`first`:
+        the (name, tensor) pairs the caller puts before x), then ValueError for the names, the counts, x, x2 and layer by layer the
+        weights, the biases and, where given, the gradients.  Returns B, F1, F2, the widths and fill(out, workspace, flags), which
+        makes the call's ptg_mlp."""
         torch = self._torch
-        who = "mlp_forward"
-        f32 = (torch.float32,)
-        acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
-        if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)):
-            raise TypeError(f"{who}: weights and biases must be lists of tensors, got {type(weights).__name__} and {type(biases).__name__}")
-        named = [("x", x), ("x2", x2)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases)]
-        for name, t in named:                                # TypeError first: what every value is
-            if not (t is None and name == "x2") and (not torch.is_tensor(t) or t.dtype not in f32):
-                check(self, who, name, t, dtypes=f32)
-        if hidden_activation not in ("relu", "tanh"):
-            raise ValueError(f"{who}: hidden_activation must be 'relu' or 'tanh', got {hidden_activation!r}")
-        if out_activation not in acts:
-            raise ValueError(f"{who}: out_activation must be None, 'relu' or 'tanh', got {out_activation!r}")
-        if _route not in (None, "narrow", "wide"):
-            raise ValueError(f"{who}: _route must be None, 'narrow' or 'wide', got {_route!r}")
-        n = len(weights)
-        if not 1 <= n <= _lib.MLP_MAX_LAYERS or len(biases) != n:
-            raise ValueError(f"{who}: 1 to {_lib.MLP_MAX_LAYERS} layers with one bias each, got {n} weights and {len(biases)} biases")
-        check(self, who, "x", x, dtypes=f32, shape=(None, None), rule=rows)
-        B, F1 = x.shape
-        check(self, who, "x2", x2, dtypes=f32, shape=(B, None), rule=rows, optional=True)
-        F2 = 0 if x2 is None else x2.shape[1]
-        if B < 1 or F1 < 1 or (x2 is not None and F2 < 1):
-            raise ValueError(f"{who}: an empty batch or an empty input piece: x {tuple(x.shape)}" + ("" if x2 is None else f", x2 {tuple(x2.shape)}"))
-        fan_in, widths = F1 + F2, []
-        for l in range(n):
-            if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
-                raise ValueError(f"{who}: the fan-in of layer {l} is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
-            check(self, who, f"weights[{l}]", weights[l], dtypes=f32, shape=(None, fan_in), rule=rows)
-            fan_in = weights[l].shape[0]
-            check(self, who, f"biases[{l}]", biases[l], dtypes=f32, shape=(fan_in,), rule=contiguous)
-            widths.append(fan_in)
-        if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
-            raise ValueError(f"{who}: the output width is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
-        check(self, who, "out", out, dtypes=f32, shape=(B, fan_in), rule=rows, optional=True, exc=ValueError)
-        need = self.mlp_workspace(B, widths, keep_hidden)
-        if workspace is not None:
-            check(self, who, f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspace, dtypes=(torch.uint8,), shape=(None,), rule=contiguous,
-                  exc=ValueError)
-            if workspace.numel() < need:
-                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, the call needs {need}")
-            if workspace.data_ptr() % 4:
-                raise ValueError(f"{who}: workspace must be 4-byte aligned")
-        with torch.cuda.device(self.device):
-            if workspace is None:
-                workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            if out is None:
-                out = torch.empty((B, fan_in), dtype=torch.float32, device=self.device)
-        row_stride = lambda t: max(t.stride(0), t.shape[1])      # a one-row tensor may report any row stride
-        flags = (_lib.MLP_KEEP_HIDDEN if keep_hidden else 0) | {None: 0, "narrow": _lib.MLP_NARROW, "wide": _lib.MLP_WIDE}[_route]
-        d = _lib.PtgMlp(batch=B, n_layers=n, flags=flags, hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
-                        x_dev=_ptr(x), x_s_n=row_stride(x), x2_dev=_ptr(x2), x2_s_n=0 if x2 is None else row_stride(x2), out_dev=_ptr(out),
-                        out_s_n=row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
-        for l in range(n):
-            d.w_dev[l], d.w_s_n[l], d.b_dev[l], d.width[l] = weights[l].data_ptr(), row_stride(weights[l]), biases[l].data_ptr(), widths[l]
-        self._call("ptg_mlp_forward", C.byref(d))
-        hidden = None
-        if keep_hidden:
-            hidden, off = [], 0
-            for w in widths[:-1]:
-                p = (w + 3) // 4 * 4
-                hidden.append(workspace[off:off + 4 * B * p].view(torch.float32).view(B, p)[:, :w])
-                off += 4 * B * p
-            hidden = tuple(hidden)
-        return MlpOut(out, hidden)
-
-    # ------------------------------------------------------------------ the backward pass of an MLP
-    def mlp_backward_workspace(self, batch, widths):
-        """bytes of device scratch mlp_backward needs: what ptg_mlp_backward_workspace returns (two alternating [batch, P(widest width)]
-        float32 buffers for dz), computed here so that the argument checks need no library"""
-        widths = [int(w) for w in widths]
-        if not (1 <= int(batch) <= 2 ** 31 and 1 <= len(widths) <= _lib.MLP_MAX_LAYERS and all(1 <= w <= _lib.MLP_MAX_WIDTH for w in widths)):
-            raise ValueError(f"mlp_backward_workspace: batch must be in [1, 2^31], 1 to {_lib.MLP_MAX_LAYERS} layers, widths in [1, {_lib.MLP_MAX_WIDTH}]; got {batch}, {widths}")
-        return 8 * int(batch) * max((w + 3) // 4 * 4 for w in widths)
-
-    def mlp_backward(self, grad_out, x, weights, biases, out, workspace, hidden_activation="relu", out_activation=None, x2=None, grad_weights=None,
-                     grad_biases=None, grad_x=None, grad_x2=None, backward_workspace=None, accumulate=False):
-        """Enqueue, on the current stream, the backward pass of the MLP whose forward was mlp_forward(x, weights, biases, ..., out=out,
-        workspace=workspace, keep_hidden=True) with the same arguments (include/ptg_env.h: ptg_mlp_backward, which states the arithmetic:
-        float32 fmaf chains, dx over ascending units, dW and db over ascending rows).  grad_out [B, O] float32, unit column stride, a row
-        stride >= O.  x, x2, weights, biases, out, workspace: what the forward was given and returned, unchanged since.  grad_weights /
-        grad_biases: lists of n tensors shaped like the parameters (grad_weights[l] may have a row stride above its fan-in), an entry None
-        in both freezes that layer; both None: no parameter gradients.  grad_x [B, F1] / grad_x2 [B, F2]: each optional; with neither, the
-        first layer's input gradient is not computed.  backward_workspace: contiguous uint8, >= mlp_backward_workspace(B, widths) bytes,
-        4-byte aligned, allocated when None.  accumulate: the parameter gradients are added to in place, continuing each element's chain
-        over the rows.  Nothing but backward_workspace is allocated; no synchronisation.  Returns the backward workspace (dz of layers 0
-        and 1 stay in it: include/ptg_env.h has the layout)."""
-        torch = self._torch
-        who = "mlp_backward"
         f32 = (torch.float32,)
         acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
         if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)):
@@ -1184,7 +1114,7 @@ class TrainOps:
             raise TypeError(f"{who}: grad_weights and grad_biases go together")
         if grad_weights is not None and (not isinstance(grad_weights, (list, tuple)) or not isinstance(grad_biases, (list, tuple))):
             raise TypeError(f"{who}: grad_weights and grad_biases must be lists, got {type(grad_weights).__name__} and {type(grad_biases).__name__}")
-        named = [("grad_out", grad_out), ("x", x), ("x2", x2)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases)]
+        named = list(first) + [("x", x), ("x2", x2)] + [(f"weights[{l}]", w) for l, w in enumerate(weights)] + [(f"biases[{l}]", b) for l, b in enumerate(biases)]
         for name, t in named:                                # TypeError first: what every value is
             if not (t is None and name == "x2") and (not torch.is_tensor(t) or t.dtype not in f32):
                 check(self, who, name, t, dtypes=f32)
@@ -1192,6 +1122,8 @@ class TrainOps:
             raise ValueError(f"{who}: hidden_activation must be 'relu' or 'tanh', got {hidden_activation!r}")
         if out_activation not in acts:
             raise ValueError(f"{who}: out_activation must be None, 'relu' or 'tanh', got {out_activation!r}")
+        if route not in (None, "narrow", "wide"):
+            raise ValueError(f"{who}: _route must be None, 'narrow' or 'wide', got {route!r}")
         n = len(weights)
         if not 1 <= n <= _lib.MLP_MAX_LAYERS or len(biases) != n:
             raise ValueError(f"{who}: 1 to {_lib.MLP_MAX_LAYERS} layers with one bias each, got {n} weights and {len(biases)} biases")
@@ -1219,42 +1151,100 @@ class TrainOps:
             widths.append(fan_in)
         if not 1 <= fan_in <= _lib.MLP_MAX_WIDTH:
             raise ValueError(f"{who}: the output width is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
-        check(self, who, "grad_out", grad_out, dtypes=f32, shape=(B, fan_in), rule=rows)
-        check(self, who, "out", out, dtypes=f32, shape=(B, fan_in), rule=rows, exc=ValueError)
-        need_f = self.mlp_workspace(B, widths, True)
-        check(self, who, f"workspace (mlp_workspace({B}, {widths}, True))", workspace, dtypes=(torch.uint8,), shape=(None,), rule=contiguous, exc=ValueError)
-        if workspace.numel() < need_f:
-            raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, the forward with keep_hidden needs {need_f}")
-        if workspace.data_ptr() % 4:
-            raise ValueError(f"{who}: workspace must be 4-byte aligned")
+
+        def fill(out, workspace, flags):
+            d = _lib.PtgMlp(batch=B, n_layers=n, flags=flags, hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
+                            x_dev=_ptr(x), x_s_n=_row_stride(x), x2_dev=_ptr(x2), x2_s_n=0 if x2 is None else _row_stride(x2), out_dev=_ptr(out),
+                            out_s_n=_row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
+            for l in range(n):
+                d.w_dev[l], d.w_s_n[l], d.b_dev[l], d.width[l] = weights[l].data_ptr(), _row_stride(weights[l]), biases[l].data_ptr(), widths[l]
+            return d
+
+        return B, F1, F2, widths, fill
+
+    def mlp_forward(self, x, weights, biases, hidden_activation="relu", out_activation=None, x2=None, out=None, workspace=None, keep_hidden=False,
+                    _route=None):
+        """Enqueue, on the current stream, the forward pass of an MLP without autograd: one fused launch per layer (include/ptg_env.h:
+        ptg_mlp_forward, which states the arithmetic -- per unit a float32 fmaf chain from the bias over ascending k, then the activation).
+        x [B, F1] float32 with unit column stride and a row stride >= F1 (a column slice of a wider tensor fits); x2 [B, F2] likewise, or
+        None: the net reads th.cat([x, x2], 1) without the cat.  weights[l] [out_l, in_l] float32 in torch's Linear.weight layout with
+        unit column stride, biases[l] [out_l] contiguous; in_0 = F1 + F2, in_l = out_(l-1); 1 to 10 layers, every width and the fan-in in
+        [1, 1024].  hidden_activation "relu" | "tanh" after every layer but the last, out_activation None | "relu" | "tanh" after the last.
+        out: [B, O] float32 with unit column stride and a row stride >= O, allocated when None.  workspace: a contiguous uint8 tensor
+        of at least mlp_workspace(B, widths, keep_hidden) bytes, 4-byte aligned, allocated when None.  keep_hidden: the post-activation
+        hidden layers stay in the workspace and are returned as views into it.  Returns MlpOut(out, hidden): hidden a tuple of n - 1
+        [B, width_l] views, or None.  No synchronisation and, with out= and workspace=, no allocation; a -0 result may come out as +0.
+        `_route` ("narrow" | "wide") forces one tile route in every layer: for tests and measurements, the bits do not depend on it."""
+        torch = self._torch
+        who = "mlp_forward"
+        B, F1, F2, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, route=_route)
+        check(self, who, "out", out, dtypes=(torch.float32,), shape=(B, widths[-1]), rule=rows, optional=True, exc=ValueError)
+        need = self.mlp_workspace(B, widths, keep_hidden)
+        if workspace is not None:
+            _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspace, need)
+        with torch.cuda.device(self.device):
+            if workspace is None:
+                workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            if out is None:
+                out = torch.empty((B, widths[-1]), dtype=torch.float32, device=self.device)
+        flags = (_lib.MLP_KEEP_HIDDEN if keep_hidden else 0) | {None: 0, "narrow": _lib.MLP_NARROW, "wide": _lib.MLP_WIDE}[_route]
+        self._call("ptg_mlp_forward", C.byref(fill(out, workspace, flags)))
+        hidden = None
+        if keep_hidden:
+            hidden, off = [], 0
+            for w in widths[:-1]:
+                p = _pitch(w)
+                hidden.append(workspace[off:off + 4 * B * p].view(torch.float32).view(B, p)[:, :w])
+                off += 4 * B * p
+            hidden = tuple(hidden)
+        return MlpOut(out, hidden)
+
+    # ------------------------------------------------------------------ the backward pass of an MLP
+    def mlp_backward_workspace(self, batch, widths):
+        """bytes of device scratch mlp_backward needs: what ptg_mlp_backward_workspace returns (two alternating [batch, P(widest width)]
+        float32 buffers for dz), computed here so that the argument checks need no library"""
+        batch, widths = _mlp_range("mlp_backward_workspace", batch, widths)
+        return 8 * batch * max(_pitch(w) for w in widths)
+
+    def mlp_backward(self, grad_out, x, weights, biases, out, workspace, hidden_activation="relu", out_activation=None, x2=None, grad_weights=None,
+                     grad_biases=None, grad_x=None, grad_x2=None, backward_workspace=None, accumulate=False):
+        """Enqueue, on the current stream, the backward pass of the MLP whose forward was mlp_forward(x, weights, biases, ..., out=out,
+        workspace=workspace, keep_hidden=True) with the same arguments (include/ptg_env.h: ptg_mlp_backward, which states the arithmetic:
+        float32 fmaf chains, dx over ascending units, dW and db over ascending rows).  grad_out [B, O] float32, unit column stride, a row
+        stride >= O.  x, x2, weights, biases, out, workspace: what the forward was given and returned, unchanged since.  grad_weights /
+        grad_biases: lists of n tensors shaped like the parameters (grad_weights[l] may have a row stride above its fan-in), an entry None
+        in both freezes that layer; both None: no parameter gradients.  grad_x [B, F1] / grad_x2 [B, F2]: each optional; with neither, the
+        first layer's input gradient is not computed.  backward_workspace: contiguous uint8, >= mlp_backward_workspace(B, widths) bytes,
+        4-byte aligned, allocated when None.  accumulate: the parameter gradients are added to in place, continuing each element's chain
+        over the rows.  Nothing but backward_workspace is allocated; no synchronisation.  Returns the backward workspace (dz of layers 0
+        and 1 stay in it: include/ptg_env.h has the layout)."""
+        torch = self._torch
+        who = "mlp_backward"
+        f32 = (torch.float32,)
+        B, F1, F2, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, first=[("grad_out", grad_out)],
+                                                grad_weights=grad_weights, grad_biases=grad_biases)
+        check(self, who, "grad_out", grad_out, dtypes=f32, shape=(B, widths[-1]), rule=rows)
+        check(self, who, "out", out, dtypes=f32, shape=(B, widths[-1]), rule=rows, exc=ValueError)
+        _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, True))", workspace, self.mlp_workspace(B, widths, True), "the forward with keep_hidden needs")
         check(self, who, "grad_x", grad_x, dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
         if grad_x2 is not None and x2 is None:
             raise ValueError(f"{who}: grad_x2 without x2")
         check(self, who, "grad_x2", grad_x2, dtypes=f32, shape=(B, F2), rule=rows, optional=True, exc=ValueError)
         need = self.mlp_backward_workspace(B, widths)
         if backward_workspace is not None:
-            check(self, who, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", backward_workspace, dtypes=(torch.uint8,), shape=(None,),
-                  rule=contiguous, exc=ValueError)
-            if backward_workspace.numel() < need:
-                raise ValueError(f"{who}: backward_workspace has {backward_workspace.numel()} bytes, the call needs {need}")
-            if backward_workspace.data_ptr() % 4:
-                raise ValueError(f"{who}: backward_workspace must be 4-byte aligned")
+            _workspace_arg(self, who, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", backward_workspace, need)
         outs = [t for t in (list(grad_weights or []) + list(grad_biases or []) + [grad_x, grad_x2, backward_workspace]) if t is not None]
         _no_tensor_twice(who, outs, "grad_weights, grad_biases, grad_x, grad_x2 and backward_workspace")
         if backward_workspace is None:
             with torch.cuda.device(self.device):
                 backward_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        row_stride = lambda t: max(t.stride(0), t.shape[1])      # a one-row tensor may report any row stride
-        d = _lib.PtgMlpBwd(gout_dev=_ptr(grad_out), gout_s_n=row_stride(grad_out), dx_dev=_ptr(grad_x), dx_s_n=0 if grad_x is None else row_stride(grad_x),
-                           dx2_dev=_ptr(grad_x2), dx2_s_n=0 if grad_x2 is None else row_stride(grad_x2), bws_dev=_ptr(backward_workspace),
+        d = _lib.PtgMlpBwd(gout_dev=_ptr(grad_out), gout_s_n=_row_stride(grad_out), dx_dev=_ptr(grad_x), dx_s_n=0 if grad_x is None else _row_stride(grad_x),
+                           dx2_dev=_ptr(grad_x2), dx2_s_n=0 if grad_x2 is None else _row_stride(grad_x2), bws_dev=_ptr(backward_workspace),
                            bws_bytes=backward_workspace.numel(), flags=_lib.MLP_ACCUMULATE if accumulate else 0)
-        d.fwd = _lib.PtgMlp(batch=B, n_layers=n, flags=_lib.MLP_KEEP_HIDDEN, hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
-                            x_dev=_ptr(x), x_s_n=row_stride(x), x2_dev=_ptr(x2), x2_s_n=0 if x2 is None else row_stride(x2), out_dev=_ptr(out),
-                            out_s_n=row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
-        for l in range(n):
-            d.fwd.w_dev[l], d.fwd.w_s_n[l], d.fwd.b_dev[l], d.fwd.width[l] = weights[l].data_ptr(), row_stride(weights[l]), biases[l].data_ptr(), widths[l]
+        d.fwd = fill(out, workspace, _lib.MLP_KEEP_HIDDEN)
+        for l in range(len(widths)):
             if grad_weights is not None and grad_weights[l] is not None:
-                d.dw_dev[l], d.dw_s_n[l], d.db_dev[l] = grad_weights[l].data_ptr(), row_stride(grad_weights[l]), grad_biases[l].data_ptr()
+                d.dw_dev[l], d.dw_s_n[l], d.db_dev[l] = grad_weights[l].data_ptr(), _row_stride(grad_weights[l]), grad_biases[l].data_ptr()
         self._call("ptg_mlp_backward", C.byref(d))
         return backward_workspace
 

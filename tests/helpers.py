@@ -296,3 +296,48 @@ class CpuTorch:
 def recording_engine(n, **attrs):
     """host_engine whose accepted calls run on CPU tensors up to the library call, which a RecordingLib keeps in eng._L.calls"""
     return host_engine(n, _h="H", _L=RecordingLib(), _torch=CpuTorch(), _stream=lambda: None, **attrs)
+
+
+def mlp_layers(fan_in, widths):
+    """zero weights and biases of a net fan_in -> widths[0] -> widths[1] ..."""
+    import torch
+    ws, bs, k = [], [], fan_in
+    for o in widths:
+        ws.append(torch.zeros(o, k))
+        bs.append(torch.zeros(o))
+        k = o
+    return ws, bs
+
+
+def faulty_mlp_nets(B=6):
+    """(exception, kwargs) for every faulty (x, x2, weights, biases, activations) that mlp_forward's argument checks are tested with
+    (tests/test_mlp_host.py); mlp_backward must refuse each in the same words (tests/test_mlp_backward_host.py).  The good net under
+    them: x [B, 40] and x2 [B, 1] into 41 -> 8 -> 8 -> 5"""
+    import torch
+    x, x2 = torch.zeros(B, 40), torch.zeros(B, 1)
+    ws, bs = mlp_layers(41, [8, 8, 5])
+    other = torch.device("meta")
+    f = lambda **kw: {**dict(x=x, weights=ws, biases=bs, x2=x2), **kw}
+    g = lambda x, net: dict(x=x, weights=net[0], biases=net[1])
+    sub = lambda xs, l, t: xs[:l] + [t] + xs[l + 1:]
+    t, v = TypeError, ValueError
+    return [
+        # what the values are
+        (t, f(x=x.numpy())), (t, f(x=x.double())), (t, f(x=None)), (t, f(x2=x2.half())),
+        (t, f(weights=ws[0])), (t, f(biases=None)), (t, f(weights=sub(ws, 1, ws[1].double()))),
+        (t, f(biases=sub(bs, 2, bs[2].long()))), (t, f(weights=sub(ws, 0, None))),
+        (t, f(x=torch.zeros(B, 2, 3), weights=sub(ws, 1, ws[1].double()))),        # TypeError before the ValueError of another argument
+        (t, f(hidden_activation="gelu", x=x.double())),
+        # the names, the counts
+        (v, f(hidden_activation="gelu")), (v, f(hidden_activation=None)), (v, f(out_activation="sigmoid")),
+        (v, f(weights=[], biases=[])), (v, f(biases=bs[:2])), (v, g(x, mlp_layers(40, [4] * 11))),
+        # shapes, strides, devices
+        (v, f(x=torch.zeros(B))), (v, f(x=torch.zeros(B, 2, 3))), (v, f(x=torch.zeros(40, B).t())),
+        (v, f(x=torch.zeros(1, 40).expand(B, 40))), (v, f(x=torch.zeros(B, 40, device=other))),
+        (v, f(x2=torch.zeros(B + 1, 1))), (v, f(x2=torch.zeros(B, 2))), (v, f(x2=None)),
+        (v, f(x=x[:0], x2=x2[:0])), (v, f(x2=torch.zeros(B, 0))), (v, f(x=torch.zeros(B, 80)[:, ::2])),
+        (v, g(torch.zeros(B, 1025), mlp_layers(1025, [4]))), (v, g(x, mlp_layers(40, [1025, 4]))), (v, g(x, mlp_layers(40, [4, 1025]))),
+        (v, f(weights=sub(ws, 1, torch.zeros(8, 9)))), (v, f(weights=sub(ws, 0, torch.zeros(41, 8).t()))),
+        (v, f(weights=sub(ws, 2, torch.zeros(5, 8, device=other)))), (v, f(biases=sub(bs, 0, torch.zeros(9)))),
+        (v, f(biases=sub(bs, 0, torch.zeros(16)[::2]))), (v, f(biases=sub(bs, 1, torch.zeros(8, 1)))),
+    ]

@@ -177,6 +177,17 @@ def test_every_pair_through_both_routes(B):
         assert mr.same_bits(outs[0], outs[1])
 
 
+RING = [1, 31, 32, 33, 64, 65, 128, 129, 160, 257]           # chunks of 32: below, at, one above and at twice the ring depths 2 and 4, with and without a ragged last chunk
+
+
+@pytest.mark.parametrize("K", RING)
+@pytest.mark.parametrize("route,rest", [("narrow", 17), ("wide", 70)])
+def test_the_ring_at_its_edges(route, rest, K):
+    """the reduction length K at the edges of the chunk ring (four chunks in flight NARROW, two WIDE); B = O = 17: two tiles, one ragged;
+    WIDE at B = O = 70: one workgroup, two live, partly filled quadrants per side.  Strided, in guard frames, hidden layer kept"""
+    _check_relu_net(_engine(), 8000 + K, rest, K, [rest, rest], keep=True, strided=True, two_piece=False, route=route)
+
+
 def test_the_widest_net():
     """1024 -> 1024 -> 5 at B = 17: the limits of fan-in and width, 64 unit tiles of the narrow route and 8 of the wide one"""
     eng = _engine()

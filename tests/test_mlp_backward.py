@@ -267,6 +267,20 @@ def test_the_widest_net():
     _same_as_ref(r, _ref(r, x, ws, gout), "1024")
 
 
+RING = [1, 31, 32, 33, 64, 65, 128, 129, 160, 257]           # chunks of 32: below, at, one above and at twice the ring depths 2 and 4, with and without a ragged last chunk
+
+
+@pytest.mark.parametrize("R", RING)
+@pytest.mark.parametrize("kernel", ["dx", "dw"])
+def test_the_ring_at_its_edges(kernel, R):
+    """the reduction length at the edges of the chunk ring: the upper layer's O in k_mlp_dx (four chunks in flight), B in k_mlp_dw (two);
+    the other dimensions 17: two tiles, one ragged.  Strided, in guard frames"""
+    B, widths = (17, [17, R]) if kernel == "dx" else (R, [17, 17])
+    x, ws, bs, gout = _case(9000 + R, B, 17, widths)
+    r = _run(_engine(), x, ws, bs, gout, strided=True)
+    _same_as_ref(r, _ref(r, x, ws, gout), (kernel, R))
+
+
 def test_a_reduction_over_several_chunks_of_rows():
     """B = 257: nine chunks of 32 rows, so the ring of four chunks in flight wraps twice and the last chunk holds one row"""
     eng = _engine()
@@ -734,13 +748,19 @@ def test_refused_descriptors_enqueue_nothing():
     bad = [F(batch=0), F(batch=2 ** 31 + 1), F(n_layers=0), F(n_layers=11), F(flags=0), F(flags=_lib.MLP_KEEP_HIDDEN | 8), F(flags=_lib.MLP_KEEP_HIDDEN | _lib.MLP_NARROW | _lib.MLP_WIDE),
            F(hidden_act=2), F(out_act=3), F(f1=0), F(f2=-1), F(x_dev=None), F(x_s_n=39), F(x2_dev=None), F(x2_s_n=0), F(w_dev=[p(w[0]), None, p(w[2])]),
            F(b_dev=[None, p(b[1]), p(b[2])]), F(w_s_n=[40, 8, 8]), F(width=[8, 0, 5]), F(width=[8, 8, 1025]), F(out_dev=None), F(out_dev=p(out, 2)), F(out_s_n=4),
-           F(ws_dev=None), F(ws_dev=p(ws, 2)), F(ws_bytes=need - 1),
-           desc(gout_dev=None), desc(gout_s_n=4), desc(dw_dev=[p(gw[0]), None, p(gw[2])]), desc(db_dev=[None, p(gb[1]), p(gb[2])]), desc(dw_s_n=[40, 8, 8]),
+           F(ws_dev=None), F(ws_dev=p(ws, 2)), F(ws_bytes=need - 1)]
+    n_fwd = len(bad)                                          # so far: faults of the embedded forward descriptor
+    bad += [desc(gout_dev=None), desc(gout_s_n=4), desc(dw_dev=[p(gw[0]), None, p(gw[2])]), desc(db_dev=[None, p(gb[1]), p(gb[2])]), desc(dw_s_n=[40, 8, 8]),
            desc(dw_s_n=[44, 7, 8]), desc(dx_s_n=39), desc(dx2_s_n=0), desc(fwd=dict(f2=0, x2_dev=None, w_s_n=[40, 8, 8])), desc(bws_dev=None), desc(bws_dev=p(bws, 2)),
            desc(bws_bytes=needb - 1), desc(bws_bytes=0), desc(flags=1), desc(flags=2), desc(flags=4), desc(flags=16), desc(flags=-1)]
     for k, d in enumerate(bad):
         assert L.ptg_mlp_backward(h, C.byref(d), stream) == _lib.E_INVALID, k
-        assert L.ptg_last_error(h).decode().startswith("ptg_mlp_backward:"), k
+        why = L.ptg_last_error(h).decode()
+        assert why.startswith("ptg_mlp_backward:"), k
+        if k < n_fwd and d.fwd.flags != 0:                   # a faulty embedded descriptor (F(flags=0) the forward accepts): one check, the forward's words
+            assert L.ptg_mlp_forward(h, C.byref(d.fwd), stream) == _lib.E_INVALID, k
+            fwd_why = L.ptg_last_error(h).decode()
+            assert fwd_why.startswith("ptg_mlp_forward: ") and why == "ptg_mlp_backward: the forward's descriptor: " + fwd_why[len("ptg_mlp_forward: "):], (k, why, fwd_why)
     assert L.ptg_mlp_backward(None, C.byref(desc()), stream) == _lib.E_INVALID and L.ptg_mlp_backward(h, None, stream) == _lib.E_INVALID
     assert torch.cuda.current_stream().query() is True        # nothing was enqueued
     torch.cuda.synchronize()

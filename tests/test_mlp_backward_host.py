@@ -248,6 +248,28 @@ def test_python_argument_checks_need_no_device():
         assert eng._L is None, k
 
 
+def test_a_faulty_net_is_refused_in_the_forwards_words():
+    """every faulty (x, x2, weights, biases, activations) of the forward's refusal list (helpers.faulty_mlp_nets, all 37 of them: none
+    had to be left out), given to mlp_backward with otherwise good arguments: the same exception class, and the same text once the
+    leading mlp_forward reads mlp_backward"""
+    import torch
+    from helpers import faulty_mlp_nets, host_engine
+    eng = host_engine(4)
+    B = 6
+    nets = faulty_mlp_nets(B)
+    assert len(nets) == 37
+    rest = dict(grad_out=torch.zeros(B, 5), out=torch.zeros(B, 5), workspace=torch.zeros(eng.mlp_workspace(B, [8, 8, 5], True), dtype=torch.uint8))
+    for k, (exc, kw) in enumerate(nets):
+        with pytest.raises(exc) as fwd:
+            eng.mlp_forward(**kw)
+        with pytest.raises(exc) as bwd:
+            eng.mlp_backward(**rest, **kw)
+        text = str(fwd.value)
+        assert type(fwd.value) is exc and type(bwd.value) is exc and text.startswith("mlp_forward: "), (k, text)
+        assert str(bwd.value) == "mlp_backward" + text[len("mlp_forward"):], (k, text, str(bwd.value))
+        assert eng._L is None, k
+
+
 def test_a_refusal_reaches_nothing_and_a_good_call_reaches_the_library_once():
     import torch
     from helpers import recording_engine

@@ -183,36 +183,17 @@ def _net(fan_in, widths):
 
 def test_python_argument_checks_need_no_device():
     import torch
-    from helpers import host_engine
+    from helpers import faulty_mlp_nets, host_engine
     eng = host_engine(4)
     B = 6
     x, x2 = torch.zeros(B, 40), torch.zeros(B, 1)
     ws, bs = _net(41, [8, 8, 5])
     other = torch.device("meta")
     f = lambda **kw: eng.mlp_forward(**{**dict(x=x, weights=ws, biases=bs, x2=x2), **kw})
-    sub = lambda xs, l, t: xs[:l] + [t] + xs[l + 1:]
     need = eng.mlp_workspace(B, [8, 8, 5])
-    refused = [
-        # what the values are
-        (TypeError, lambda: f(x=x.numpy())), (TypeError, lambda: f(x=x.double())), (TypeError, lambda: f(x=None)), (TypeError, lambda: f(x2=x2.half())),
-        (TypeError, lambda: f(weights=ws[0])), (TypeError, lambda: f(biases=None)), (TypeError, lambda: f(weights=sub(ws, 1, ws[1].double()))),
-        (TypeError, lambda: f(biases=sub(bs, 2, bs[2].long()))), (TypeError, lambda: f(weights=sub(ws, 0, None))),
-        (TypeError, lambda: f(x=torch.zeros(B, 2, 3), weights=sub(ws, 1, ws[1].double()))),        # TypeError before the ValueError of another argument
-        (TypeError, lambda: f(hidden_activation="gelu", x=x.double())),
-        # the names, the counts
-        (ValueError, lambda: f(hidden_activation="gelu")), (ValueError, lambda: f(hidden_activation=None)), (ValueError, lambda: f(out_activation="sigmoid")),
-        (ValueError, lambda: f(_route="split")), (ValueError, lambda: f(weights=[], biases=[])), (ValueError, lambda: f(biases=bs[:2])),
-        (ValueError, lambda: eng.mlp_forward(x, *_net(40, [4] * 11))),
-        # shapes, strides, devices
-        (ValueError, lambda: f(x=torch.zeros(B))), (ValueError, lambda: f(x=torch.zeros(B, 2, 3))), (ValueError, lambda: f(x=torch.zeros(40, B).t())),
-        (ValueError, lambda: f(x=torch.zeros(1, 40).expand(B, 40))), (ValueError, lambda: f(x=torch.zeros(B, 40, device=other))),
-        (ValueError, lambda: f(x2=torch.zeros(B + 1, 1))), (ValueError, lambda: f(x2=torch.zeros(B, 2))), (ValueError, lambda: f(x2=None)),
-        (ValueError, lambda: f(x=x[:0], x2=x2[:0])), (ValueError, lambda: f(x2=torch.zeros(B, 0))), (ValueError, lambda: f(x=torch.zeros(B, 80)[:, ::2])),
-        (ValueError, lambda: eng.mlp_forward(torch.zeros(B, 1025), *_net(1025, [4]))), (ValueError, lambda: eng.mlp_forward(x, *_net(40, [1025, 4]))),
-        (ValueError, lambda: eng.mlp_forward(x, *_net(40, [4, 1025]))),
-        (ValueError, lambda: f(weights=sub(ws, 1, torch.zeros(8, 9)))), (ValueError, lambda: f(weights=sub(ws, 0, torch.zeros(41, 8).t()))),
-        (ValueError, lambda: f(weights=sub(ws, 2, torch.zeros(5, 8, device=other)))), (ValueError, lambda: f(biases=sub(bs, 0, torch.zeros(9)))),
-        (ValueError, lambda: f(biases=sub(bs, 0, torch.zeros(16)[::2]))), (ValueError, lambda: f(biases=sub(bs, 1, torch.zeros(8, 1)))),
+    # what the values are, the names, the counts, shapes, strides, devices of the net: the list mlp_backward is held to as well
+    refused = [(exc, lambda kw=kw: eng.mlp_forward(**kw)) for exc, kw in faulty_mlp_nets(B)] + [
+        (ValueError, lambda: f(_route="split")),
         # out and workspace
         (ValueError, lambda: f(out=torch.zeros(B, 5).double())), (ValueError, lambda: f(out=torch.zeros(B, 4))), (ValueError, lambda: f(out=torch.zeros(B + 1, 5))),
         (ValueError, lambda: f(out=torch.zeros(5, B).t())), (ValueError, lambda: f(out=torch.zeros(B, 5, device=other))), (ValueError, lambda: f(out=[torch.zeros(B, 5)])),
@@ -220,6 +201,7 @@ def test_python_argument_checks_need_no_device():
         (ValueError, lambda: f(workspace=torch.zeros(need + 8, dtype=torch.uint8)[1:])), (ValueError, lambda: f(workspace=torch.zeros(2 * need, dtype=torch.uint8)[::2])),
         (ValueError, lambda: eng.mlp_forward(x, *_net(40, [5]), workspace=torch.zeros(15, dtype=torch.uint8))),      # one layer still takes 16 bytes
     ]
+    assert len(refused) == 49
     for k, (exc, fn) in enumerate(refused):
         with pytest.raises(exc, match="mlp_forward|mlp_workspace"):
             fn()
