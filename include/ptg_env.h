@@ -47,7 +47,8 @@ extern "C" {
                              *     ptg_actor_loss_workspace (the SAC / TQC / TD3 actor loss and the entropy-coefficient loss with their
                              *     gradients); + ptg_mlp, ptg_mlp_forward, ptg_mlp_workspace (the inference forward of the policy and target MLPs,
                              *     one fused f32 MFMA launch per layer); + ptg_mlp_bwd, ptg_mlp_backward, ptg_mlp_backward_workspace (the backward pass
-                             *     of those MLPs, two f32 MFMA launches per layer); no earlier declaration changed */
+                             *     of those MLPs, two f32 MFMA launches per layer); + PTG_MLP_GROUP_MAX, ptg_mlp_group_forward, ptg_mlp_group_backward
+                             *     (up to eight MLPs of equal depth in the launches of one); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -1265,6 +1266,35 @@ typedef struct ptg_mlp_bwd {
 } ptg_mlp_bwd;
 int64_t ptg_mlp_backward_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags);
 int ptg_mlp_backward(ptg_env* env, const ptg_mlp_bwd* d, void* stream);
+
+/* ---- a group of MLPs of equal depth in the launches of one: twin critics, critics and their targets, a policy and a value net ----------
+ * ptg_mlp_group_forward and ptg_mlp_group_backward run n_nets networks, 1 <= n_nets <= PTG_MLP_GROUP_MAX, in exactly the launches that
+ * ONE network's ptg_mlp_forward / ptg_mlp_backward enqueues: n in the forward; in the backward k_mlp_dz_out when out_act != NONE, then
+ * per layer one weight-gradient and one input-gradient launch (kernels k_mlp_layer_group, k_mlp_dz_out_group, k_mlp_dw_group,
+ * k_mlp_dx_group: the third grid dimension is the network, the first two are the largest tile counts of the group).  A weight-gradient
+ * launch of layer l is enqueued when ANY network sets dw_dev[l], the first layer's input-gradient launch when ANY network sets dx_dev
+ * or dx2_dev; the workgroups of a network that freezes the layer, or wants no dx, return at once and write nothing.
+ *   nets          an array of n_nets of the single calls' descriptors, read during the call and holding no host memory afterwards.  Each
+ *                 network has its own x_dev / x2_dev (f1 and f2 may differ), width[], w_dev / b_dev, out_dev, ws_dev, and in the backward
+ *                 its own gout_dev, dw_dev / db_dev (frozen layers per network), dx_dev / dx2_dev (each optional per network), bws_dev.
+ *                 Workspace sizes are ptg_mlp_workspace and ptg_mlp_backward_workspace, per network.
+ *   sharing       networks may share what is only read: x_dev, x2_dev, even weights.  Every out_dev, ws_dev, gradient and bws_dev of
+ *                 every network must be distinct from every other and from anything the call reads; overlap is NOT checked.
+ *   must agree    batch, n_layers, hidden_act, out_act and flags of all networks; in the backward its own flags (PTG_MLP_ACCUMULATE) too.
+ *   routes        a group always runs the 16 x 16 route: PTG_MLP_WIDE in any descriptor is refused, PTG_MLP_NARROW is accepted and means
+ *                 nothing.  A single network at a large batch (B >= 4 096 with layers wider than 512) belongs to ptg_mlp_forward and its
+ *                 128 x 128 route.
+ * Arithmetic: none of its own.  EVERY ELEMENT A GROUPED CALL WRITES IS DEFINED AS WHAT THE SINGLE CALL ON THAT NETWORK'S DESCRIPTOR WRITES
+ * -- out, the kept hidden layers, dx, dW, db and the dz left in bws_dev -- bit for bit: an element of the single ops does not depend on
+ * the grid, and the grouped kernels run the single kernels' tile code.  A shared input's gradient is NOT summed: each network writes its
+ * own dx.
+ * No host synchronisation and no allocation; capturable into a hipGraph; the weights are read when the kernels run.
+ * PTG_E_INVALID (nothing enqueued; every check runs before the first launch): NULL handle or array; n_nets outside
+ * [1, PTG_MLP_GROUP_MAX]; anything the single call refuses in a descriptor, its text behind "net <i>: "; PTG_MLP_WIDE; a disagreement
+ * in one of the fields above, which names the two networks and the field. */
+#define PTG_MLP_GROUP_MAX 8
+int ptg_mlp_group_forward(ptg_env* env, const ptg_mlp* nets, int32_t n_nets, void* stream);
+int ptg_mlp_group_backward(ptg_env* env, const ptg_mlp_bwd* nets, int32_t n_nets, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

@@ -40,6 +40,7 @@ MLP_MAX_LAYERS, MLP_MAX_WIDTH = 10, 1024
 MLP_RELU, MLP_TANH, MLP_NONE = 0, 1, 2
 MLP_KEEP_HIDDEN, MLP_NARROW, MLP_WIDE = 1, 2, 4
 MLP_ACCUMULATE = 8
+MLP_GROUP_MAX = 8
 
 _D1 = ["noise"]
 _I1 = ["eps_len_d", "sim_step", "time_step_op", "price_ahead"]
@@ -175,6 +176,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
            "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward", "ptg_mlp_backward_workspace", "ptg_mlp_backward",
+           "ptg_mlp_group_forward", "ptg_mlp_group_backward",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -316,6 +318,8 @@ def lib():
     L.ptg_mlp_backward_workspace.argtypes = [C.c_int64, C.c_int32, i32p, C.c_int32]
     L.ptg_mlp_backward_workspace.restype = C.c_int64
     L.ptg_mlp_backward.argtypes = [vp, C.POINTER(PtgMlpBwd), vp]
+    L.ptg_mlp_group_forward.argtypes = [vp, C.POINTER(PtgMlp), C.c_int32, vp]
+    L.ptg_mlp_group_backward.argtypes = [vp, C.POINTER(PtgMlpBwd), C.c_int32, vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

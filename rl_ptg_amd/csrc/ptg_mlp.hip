@@ -20,6 +20,9 @@
 // dependent chain of K / 4 MFMAs.  A kernel plugs in its fetch (which tensor index rides on which lane), its LDS layout and its MFMAs, and
 // keeps its epilogue.  Loads are single dwords: odd widths (743, 233) leave weight rows off 16-byte alignment and the two-piece input
 // splits a row anywhere; a load instruction of a wave still reads 32 neighbouring floats of each of two rows.
+// Groups (ptg_mlp_group_forward, ptg_mlp_group_backward): the 16 x 16 tile bodies of the forward and of the backward
+// are device functions with two entry points each, the single kernel and a grouped one that runs the tiles of up to PTG_MLP_GROUP_MAX
+// networks of equal depth in one launch; a network's bits are those of its own single call.
 #include "ptg_handle.h"
 
 #include <cmath>
@@ -119,48 +122,55 @@ __device__ __forceinline__ void mlp_chain16(const float* as, const float* bs, IA
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], bv[s], acc, 0, 0, 0);
 }
 
+// The NARROW tile (bx, by) of a layer: the body of k_mlp_layer<ACT, MLP_NARROW> and of k_mlp_layer_group<ACT>, which picks `a` out of its group
+template <int ACT>
+__device__ __forceinline__ void mlp_layer_tile16(const MlpLayer a, unsigned bx, unsigned by)
+{
+    __shared__ float xs[NR_TILE * NR_PITCH], ws[NR_TILE * NR_PITCH];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const size_t row0 = (size_t)bx * NR_TILE;
+    const int col0 = (int)by * NR_TILE;
+    const float bj = col0 + r < a.O ? a.bias[col0 + r] : 0.0f;
+    f32x4 acc = {bj, bj, bj, bj};
+    constexpr int PER = NR_TILE * NR_KC / 64;            // 8 rows and 8 units per lane and chunk
+    float xr[NR_DEPTH][PER], wr[NR_DEPTH][PER];
+    const int kx = lane & 31, r2 = lane >> 5;
+    auto fetch = [=, &xr, &wr](int d, int k0) {          // lane: k = k0 + kx of every second row and unit; 0 beyond an edge
+        const int k = k0 + kx;
+        const bool kin = k < a.K;
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            const int rr = r2 + 2 * i;
+            const size_t row = row0 + rr;
+            const int u = col0 + rr;
+            xr[d][i] = mlp_x(a, row, k, kin && row < a.B);
+            wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
+        }
+    };
+    auto stage = [=, &xr, &wr](int d) {
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            xs[(r2 + 2 * i) * NR_PITCH + kx] = xr[d][i];
+            ws[(r2 + 2 * i) * NR_PITCH + kx] = wr[d][i];
+        }
+    };
+    auto at = [=](int s) { return r * NR_PITCH + 4 * s + q; };
+    mlp_ring<NR_DEPTH, NR_KC>(a.K, fetch, stage, [=, &acc] { mlp_chain16(xs, ws, at, at, acc); });
+    const int u = col0 + r;
+    if (u < a.O) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const size_t row = row0 + 4 * q + g;
+            if (row < a.B) a.y[row * a.y_s + (size_t)u] = mlp_act<ACT>(acc[g]);
+        }
+    }
+}
+
 template <int ACT, int ROUTE>
 __global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(const MlpLayer a)
 {
     if constexpr (ROUTE == MLP_NARROW) {
-        __shared__ float xs[NR_TILE * NR_PITCH], ws[NR_TILE * NR_PITCH];
-        const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
-        const size_t row0 = (size_t)blockIdx.x * NR_TILE;
-        const int col0 = blockIdx.y * NR_TILE;
-        const float bj = col0 + r < a.O ? a.bias[col0 + r] : 0.0f;
-        f32x4 acc = {bj, bj, bj, bj};
-        constexpr int PER = NR_TILE * NR_KC / 64;            // 8 rows and 8 units per lane and chunk
-        float xr[NR_DEPTH][PER], wr[NR_DEPTH][PER];
-        const int kx = lane & 31, r2 = lane >> 5;
-        auto fetch = [=, &xr, &wr](int d, int k0) {          // lane: k = k0 + kx of every second row and unit; 0 beyond an edge
-            const int k = k0 + kx;
-            const bool kin = k < a.K;
-#pragma unroll
-            for (int i = 0; i < PER; i++) {
-                const int rr = r2 + 2 * i;
-                const size_t row = row0 + rr;
-                const int u = col0 + rr;
-                xr[d][i] = mlp_x(a, row, k, kin && row < a.B);
-                wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
-            }
-        };
-        auto stage = [=, &xr, &wr](int d) {
-#pragma unroll
-            for (int i = 0; i < PER; i++) {
-                xs[(r2 + 2 * i) * NR_PITCH + kx] = xr[d][i];
-                ws[(r2 + 2 * i) * NR_PITCH + kx] = wr[d][i];
-            }
-        };
-        auto at = [=](int s) { return r * NR_PITCH + 4 * s + q; };
-        mlp_ring<NR_DEPTH, NR_KC>(a.K, fetch, stage, [=, &acc] { mlp_chain16(xs, ws, at, at, acc); });
-        const int u = col0 + r;
-        if (u < a.O) {
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const size_t row = row0 + 4 * q + g;
-                if (row < a.B) a.y[row * a.y_s + (size_t)u] = mlp_act<ACT>(acc[g]);
-            }
-        }
+        mlp_layer_tile16<ACT>(a, blockIdx.x, blockIdx.y);
     } else {
         __shared__ float xs[WD_TILE * WD_PITCH], ws[WD_TILE * WD_PITCH];
         const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr_ = wave >> 1, wc = wave & 1, c = lane & 31, hf = lane >> 5;
@@ -246,6 +256,35 @@ void launch_mlp_layer(hipStream_t st, const MlpLayer& a, int act)
     mlp_with_act(act, [&](auto A) { k_mlp_layer<decltype(A)::value, ROUTE><<<grid, block, 0, st>>>(a); });
 }
 
+// ---- the grouped launches (include/ptg_env.h, ptg_mlp_group_forward) ------------------------------------------------
+// Up to PTG_MLP_GROUP_MAX networks in one launch: the by-value structs of the single kernels side by side in the kernel arguments,
+// blockIdx.z picks the network, gridDim.x / .y are the largest tile counts of the group.  The tile bodies are the single kernels': a
+// network's bits are those of its own call.  A workgroup whose tile lies outside its network, or whose network takes no part in the
+// launch, returns before any load and before the first barrier; every test for that is uniform over the workgroup.  net[blockIdx.z]
+// is read out of the kernel-argument segment with scalar loads at a computed offset: no private copy (profiles/mlp_group_resources.txt).
+template <typename T>
+struct MlpGroup {
+    T net[PTG_MLP_GROUP_MAX];
+};
+
+template <int ACT>
+__global__ __launch_bounds__(64) void k_mlp_layer_group(const MlpGroup<MlpLayer> g)
+{
+    const MlpLayer& a = g.net[blockIdx.z];
+    if ((size_t)blockIdx.x * NR_TILE >= a.B || (int)blockIdx.y * NR_TILE >= a.O) return;
+    mlp_layer_tile16<ACT>(a, blockIdx.x, blockIdx.y);
+}
+
+void launch_mlp_layer_group(hipStream_t st, const MlpGroup<MlpLayer>& g, int n_nets, int act)
+{
+    unsigned gx = 1, gy = 1;
+    for (int i = 0; i < n_nets; i++) {
+        gx = std::max(gx, (unsigned)((g.net[i].B - 1) / NR_TILE + 1));
+        gy = std::max(gy, (unsigned)((g.net[i].O - 1) / NR_TILE + 1));
+    }
+    mlp_with_act(act, [&](auto A) { k_mlp_layer_group<decltype(A)::value><<<dim3(gx, gy, (unsigned)n_nets), 64, 0, st>>>(g); });
+}
+
 // The layout of both workspaces (include/ptg_env.h): a hidden layer and a dz buffer are [batch][pitch(l)] floats
 struct MlpLayout {
     int64_t batch;
@@ -314,6 +353,53 @@ bool mlp_desc_fault(const ptg_mlp* d, char* why, size_t cap)
     return false;
 }
 
+// The launch arguments of a forward call, layer by layer: the call's input, then layer l's parameters and output, then that output as
+// the next layer's input
+MlpLayer mlp_first_input(const ptg_mlp* d)
+{
+    MlpLayer a{};
+    a.B = (size_t)d->batch;
+    a.x = d->x_dev; a.x_s = (size_t)d->x_s_n; a.x2 = d->x2_dev ? d->x2_dev : d->x_dev; a.x2_s = (size_t)d->x2_s_n;
+    a.F1 = d->f1; a.K = d->f1 + d->f2;
+    return a;
+}
+
+void mlp_set_layer(MlpLayer& a, const ptg_mlp* d, int l)
+{
+    const int n = d->n_layers;
+    const MlpLayout lay{d->batch, n, d->width};
+    a.w = d->w_dev[l]; a.w_s = (size_t)d->w_s_n[l]; a.bias = d->b_dev[l]; a.O = d->width[l];
+    if (l == n - 1) {
+        a.y = d->out_dev; a.y_s = (size_t)d->out_s_n;
+    } else {
+        a.y = (float*)d->ws_dev + ((d->flags & PTG_MLP_KEEP_HIDDEN) ? lay.kept(l) : lay.alt(l, n - 1));
+        a.y_s = (size_t)lay.pitch(l);
+    }
+}
+
+void mlp_next_input(MlpLayer& a)
+{
+    a.x = a.x2 = a.y; a.x_s = a.y_s; a.x2_s = 0; a.F1 = a.K = a.O;      // this layer's output is the next one's input
+}
+
+// what a group refuses beyond its descriptors' own faults: a route that is not the 16 x 16 one, and a disagreement with net 0 in a field
+// that the launches share.  nets: ptg_mlp, or ptg_mlp_bwd (which begins with one), `stride` bytes apart
+bool mlp_group_fault(const void* nets, size_t stride, int n_nets, char* why, size_t cap)
+{
+    auto net = [&](int i) { return (const ptg_mlp*)((const char*)nets + (size_t)i * stride); };
+    const ptg_mlp* a = net(0);
+    for (int i = 0; i < n_nets; i++) {
+        const ptg_mlp* b = net(i);
+        if (b->flags & PTG_MLP_WIDE) return mlp_fault(why, cap, "net %d: PTG_MLP_WIDE: a group runs the 16 x 16 route", i);
+        if (b->batch != a->batch) return mlp_fault(why, cap, "nets 0 and %d disagree in batch: %lld and %lld", i, (long long)a->batch, (long long)b->batch);
+        if (b->n_layers != a->n_layers) return mlp_fault(why, cap, "nets 0 and %d disagree in n_layers: %d and %d", i, a->n_layers, b->n_layers);
+        if (b->hidden_act != a->hidden_act) return mlp_fault(why, cap, "nets 0 and %d disagree in hidden_act: %d and %d", i, a->hidden_act, b->hidden_act);
+        if (b->out_act != a->out_act) return mlp_fault(why, cap, "nets 0 and %d disagree in out_act: %d and %d", i, a->out_act, b->out_act);
+        if (b->flags != a->flags) return mlp_fault(why, cap, "nets 0 and %d disagree in flags: %d and %d", i, a->flags, b->flags);
+    }
+    return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -334,27 +420,38 @@ int ptg_mlp_forward(ptg_env* h, const ptg_mlp* d, void* stream)
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
     const int n = d->n_layers;
-    const MlpLayout lay{d->batch, n, d->width};
-    const bool keep = (d->flags & PTG_MLP_KEEP_HIDDEN) != 0;
-    MlpLayer a{};
-    a.B = (size_t)d->batch;
-    a.x = d->x_dev; a.x_s = (size_t)d->x_s_n; a.x2 = d->x2_dev ? d->x2_dev : d->x_dev; a.x2_s = (size_t)d->x2_s_n;
-    a.F1 = d->f1; a.K = d->f1 + d->f2;
+    MlpLayer a = mlp_first_input(d);
     for (int l = 0; l < n; l++) {
-        const bool last = l == n - 1;
-        a.w = d->w_dev[l]; a.w_s = (size_t)d->w_s_n[l]; a.bias = d->b_dev[l]; a.O = d->width[l];
-        if (last) {
-            a.y = d->out_dev; a.y_s = (size_t)d->out_s_n;
-        } else {
-            a.y = (float*)d->ws_dev + (keep ? lay.kept(l) : lay.alt(l, n - 1));
-            a.y_s = (size_t)lay.pitch(l);
-        }
-        const int act = last ? d->out_act : d->hidden_act;
+        mlp_set_layer(a, d, l);
+        const int act = l == n - 1 ? d->out_act : d->hidden_act;
         const bool wide = (d->flags & PTG_MLP_WIDE) || (!(d->flags & PTG_MLP_NARROW) && ((d->batch >= MLP_WIDE_MIN_ROWS && a.O > MLP_WIDE_MIN_UNITS) || (d->batch >= MLP_WIDE_MIN_ROWS_BROAD && a.O > MLP_BROAD_UNITS)));
         if (wide) launch_mlp_layer<MLP_WIDE>(st, a, act);
         else launch_mlp_layer<MLP_NARROW>(st, a, act);
         if (int rc = launch_check(h, "k_mlp_layer")) return rc;
-        a.x = a.x2 = a.y; a.x_s = a.y_s; a.x2_s = 0; a.F1 = a.K = a.O;      // this layer's output is the next one's input
+        mlp_next_input(a);
+    }
+    return 0;
+}
+
+int ptg_mlp_group_forward(ptg_env* h, const ptg_mlp* nets, int32_t n_nets, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!nets) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: null descriptor array");
+    if (n_nets < 1 || n_nets > PTG_MLP_GROUP_MAX) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: n_nets %d outside [1, %d]", n_nets, PTG_MLP_GROUP_MAX);
+    char why[200];
+    for (int i = 0; i < n_nets; i++)
+        if (mlp_desc_fault(&nets[i], why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: net %d: %s", i, why);
+    if (mlp_group_fault(nets, sizeof(ptg_mlp), n_nets, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: %s", why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const int n = nets[0].n_layers;
+    MlpGroup<MlpLayer> g{};
+    for (int i = 0; i < n_nets; i++) g.net[i] = mlp_first_input(&nets[i]);
+    for (int l = 0; l < n; l++) {
+        for (int i = 0; i < n_nets; i++) mlp_set_layer(g.net[i], &nets[i], l);
+        launch_mlp_layer_group(st, g, n_nets, l == n - 1 ? nets[0].out_act : nets[0].hidden_act);
+        if (int rc = launch_check(h, "k_mlp_layer_group")) return rc;
+        for (int i = 0; i < n_nets; i++) mlp_next_input(g.net[i]);
     }
     return 0;
 }
@@ -417,13 +514,14 @@ __device__ __forceinline__ float mlp_dact(float h, float g)
     else return g;
 }
 
+// The tile bodies: each is its single kernel's whole text and the grouped kernel's, which picks `a` out of its group (forward half of the file)
 template <int ACT_BELOW>
-__global__ __launch_bounds__(64) void k_mlp_dx(const MlpDx a)
+__device__ __forceinline__ void mlp_dx_tile(const MlpDx a, unsigned bx, unsigned by)
 {
     __shared__ float zs[BW_TILE * NR_PITCH], wt[BW_RC * BW_PITCH_T];
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
-    const size_t row0 = (size_t)blockIdx.x * BW_TILE;
-    const int col0 = blockIdx.y * BW_TILE;
+    const size_t row0 = (size_t)bx * BW_TILE;
+    const int col0 = (int)by * BW_TILE;
     f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     constexpr int PER = BW_TILE * BW_RC / 64;                // 8 elements of dz and 8 of W per lane and chunk
     float zr[BW_DEPTH][PER], wr[BW_DEPTH][PER];
@@ -468,11 +566,26 @@ __global__ __launch_bounds__(64) void k_mlp_dx(const MlpDx a)
     }
 }
 
-__global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
+template <int ACT_BELOW>
+__global__ __launch_bounds__(64) void k_mlp_dx(const MlpDx a)
+{
+    mlp_dx_tile<ACT_BELOW>(a, blockIdx.x, blockIdx.y);
+}
+
+template <int ACT_BELOW>
+__global__ __launch_bounds__(64) void k_mlp_dx_group(const MlpGroup<MlpDx> g)
+{
+    const MlpDx& a = g.net[blockIdx.z];
+    if (ACT_BELOW == PTG_MLP_NONE && !a.y && !a.y2) return;      // this network wants no first-layer dx
+    if ((size_t)blockIdx.x * BW_TILE >= a.B || (int)blockIdx.y * BW_TILE >= a.K) return;
+    mlp_dx_tile<ACT_BELOW>(a, blockIdx.x, blockIdx.y);
+}
+
+__device__ __forceinline__ void mlp_dw_tile(const MlpDw a, unsigned bx, unsigned by)
 {
     __shared__ float zs[BW_RC * BW_PITCH_T], xs[BW_RC * BW_PITCH_T];
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
-    const int j0 = blockIdx.x * BW_TILE, k0 = blockIdx.y * BW_TILE;      // k runs to K inclusive: column K is the bias gradient
+    const int j0 = (int)bx * BW_TILE, k0 = (int)by * BW_TILE;      // k runs to K inclusive: column K is the bias gradient
     const int ko = k0 + r;
     f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     if (a.accumulate && ko <= a.K) {
@@ -521,14 +634,116 @@ __global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
     }
 }
 
+__global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
+{
+    mlp_dw_tile(a, blockIdx.x, blockIdx.y);
+}
+
+__global__ __launch_bounds__(64) void k_mlp_dw_group(const MlpGroup<MlpDw> g)
+{
+    const MlpDw& a = g.net[blockIdx.z];
+    if (!a.dw) return;                                       // this network freezes the layer
+    if ((int)blockIdx.x * BW_TILE >= a.O || (int)blockIdx.y * BW_TILE > a.K) return;      // column K is the bias gradient
+    mlp_dw_tile(a, blockIdx.x, blockIdx.y);
+}
+
 template <int ACT>
-__global__ __launch_bounds__(256) void k_mlp_dz_out(const MlpDzOut a)
+__device__ __forceinline__ void mlp_dz_out_rows(const MlpDzOut a)
 {
     const size_t total = a.B * (size_t)a.O, step = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
         const size_t b = i / (size_t)a.O, j = i % (size_t)a.O;
         a.dz[b * a.dz_s + j] = mlp_dact<ACT>(a.h[b * a.h_s + j], a.g[b * a.g_s + j]);
     }
+}
+
+template <int ACT>
+__global__ __launch_bounds__(256) void k_mlp_dz_out(const MlpDzOut a)
+{
+    mlp_dz_out_rows<ACT>(a);
+}
+
+template <int ACT>
+__global__ __launch_bounds__(256) void k_mlp_dz_out_group(const MlpGroup<MlpDzOut> g)      // gridDim.x: the blocks of the largest network; a block beyond a smaller one's elements loops zero times
+{
+    mlp_dz_out_rows<ACT>(g.net[blockIdx.z]);
+}
+
+// what ptg_mlp_backward refuses in a descriptor: false when d is well-formed, else the text in why
+bool mlp_bwd_fault(const ptg_mlp_bwd* d, char* why, size_t cap)
+{
+    const ptg_mlp* f = &d->fwd;
+    char fwd[160];
+    if (mlp_desc_fault(f, fwd, sizeof fwd)) return mlp_fault(why, cap, "the forward's descriptor: %s", fwd);
+    if (!(f->flags & PTG_MLP_KEEP_HIDDEN)) return mlp_fault(why, cap, "the forward's descriptor must carry PTG_MLP_KEEP_HIDDEN");
+    if (d->flags & ~PTG_MLP_ACCUMULATE) return mlp_fault(why, cap, "unknown flag in %d", d->flags);
+    const int n = f->n_layers;
+    if (!d->gout_dev || d->gout_s_n < f->width[n - 1]) return mlp_fault(why, cap, "gout_dev is null or gout_s_n below the output width %d", f->width[n - 1]);
+    int fan_in = f->f1 + f->f2;
+    for (int l = 0; l < n; l++) {
+        if ((d->dw_dev[l] != nullptr) != (d->db_dev[l] != nullptr)) return mlp_fault(why, cap, "dw_dev[%d] and db_dev[%d] go together", l, l);
+        if (d->dw_dev[l] && d->dw_s_n[l] < fan_in) return mlp_fault(why, cap, "dw_s_n[%d] below the fan-in %d", l, fan_in);
+        fan_in = f->width[l];
+    }
+    if (d->dx_dev && d->dx_s_n < f->f1) return mlp_fault(why, cap, "dx_s_n below f1 = %d", f->f1);
+    if (d->dx2_dev && f->f2 == 0) return mlp_fault(why, cap, "dx2_dev without a second input piece");
+    if (d->dx2_dev && d->dx2_s_n < f->f2) return mlp_fault(why, cap, "dx2_s_n below f2 = %d", f->f2);
+    if (!d->bws_dev || (uintptr_t)d->bws_dev % sizeof(float) != 0) return mlp_fault(why, cap, "bws_dev is null or not aligned to 4 bytes");
+    const int64_t need = MlpLayout{f->batch, n, f->width}.backward_bytes();
+    if (d->bws_bytes < need) return mlp_fault(why, cap, "bws_bytes = %lld, the call needs %lld", (long long)d->bws_bytes, (long long)need);
+    return false;
+}
+
+// The launch arguments of a backward call, walked from the last layer down: dz_out() (when out_act != NONE), then per layer dw(l) before
+// dx(l); dx(l) moves the walk's dz to the layer below
+struct MlpBwdWalk {
+    const ptg_mlp_bwd* d;
+    const float* dz;                     // the gradient at the current layer's pre-activation: grad_out, or a buffer of bws_dev
+    size_t dz_s;
+    MlpBwdWalk() : d(nullptr), dz(nullptr), dz_s(0) {}
+    explicit MlpBwdWalk(const ptg_mlp_bwd* desc) : d(desc), dz(desc->gout_dev), dz_s((size_t)desc->gout_s_n) {}
+    MlpLayout lay() const { return MlpLayout{d->fwd.batch, d->fwd.n_layers, d->fwd.width}; }
+    float* buf(int l) const { return (float*)d->bws_dev + lay().alt(l, d->fwd.n_layers); }      // dz of layer l, row stride pitch(l)
+    int fan_in(int l) const { return l ? d->fwd.width[l - 1] : d->fwd.f1 + d->fwd.f2; }
+    const float* input(int l) const { return l ? (const float*)d->fwd.ws_dev + lay().kept(l - 1) : d->fwd.x_dev; }      // the layer's input: hidden layer l - 1, or the call's
+    size_t input_s(int l) const { return l ? (size_t)lay().pitch(l - 1) : (size_t)d->fwd.x_s_n; }
+    MlpDzOut dz_out()
+    {
+        const ptg_mlp* f = &d->fwd;
+        const int n = f->n_layers;
+        const MlpDzOut e{d->gout_dev, (size_t)d->gout_s_n, f->out_dev, (size_t)f->out_s_n, buf(n - 1), (size_t)lay().pitch(n - 1), (size_t)f->batch, f->width[n - 1]};
+        dz = e.dz; dz_s = e.dz_s;
+        return e;
+    }
+    MlpDw dw(int l) const                // dw == NULL where the layer is frozen
+    {
+        const ptg_mlp* f = &d->fwd;
+        const float* x = input(l);
+        const size_t x_s = input_s(l);
+        MlpDw a{};
+        a.dz = dz; a.dz_s = dz_s; a.x = x; a.x_s = x_s; a.B = (size_t)f->batch; a.K = fan_in(l); a.O = f->width[l];
+        a.x2 = !l && f->x2_dev ? f->x2_dev : x; a.x2_s = !l && f->x2_dev ? (size_t)f->x2_s_n : x_s; a.F1 = l ? a.K : f->f1;
+        a.dw = d->dw_dev[l]; a.dw_s = (size_t)d->dw_s_n[l]; a.db = d->db_dev[l]; a.accumulate = (d->flags & PTG_MLP_ACCUMULATE) != 0;
+        return a;
+    }
+    MlpDx dx(int l)
+    {
+        const ptg_mlp* f = &d->fwd;
+        MlpDx a{};
+        a.dz = dz; a.dz_s = dz_s; a.w = f->w_dev[l]; a.w_s = (size_t)f->w_s_n[l]; a.B = (size_t)f->batch; a.K = fan_in(l); a.O = f->width[l];
+        if (l) {                         // dz of the layer below, through the derivative of the hidden activation on its kept output
+            a.h = input(l); a.h_s = input_s(l); a.y = buf(l - 1); a.y_s = a.h_s; a.F1 = a.K;
+            dz = a.y; dz_s = a.y_s;
+        } else {
+            a.y = d->dx_dev; a.y_s = (size_t)d->dx_s_n; a.y2 = d->dx2_dev; a.y2_s = (size_t)d->dx2_s_n; a.F1 = f->f1;
+        }
+        return a;
+    }
+};
+
+unsigned mlp_dz_out_blocks(const MlpDzOut& e)
+{
+    return (unsigned)std::min<size_t>((e.B * (size_t)e.O - 1) / 256 + 1, 65536);
 }
 
 }  // namespace
@@ -545,64 +760,89 @@ int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
 {
     if (!h) return PTG_E_INVALID;
     if (!d) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: null descriptor");
-    const ptg_mlp* f = &d->fwd;
-    char why[160];
-    if (mlp_desc_fault(f, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor: %s", why);
-    if (!(f->flags & PTG_MLP_KEEP_HIDDEN)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: the forward's descriptor must carry PTG_MLP_KEEP_HIDDEN");
-    if (d->flags & ~PTG_MLP_ACCUMULATE) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: unknown flag in %d", d->flags);
-    const int n = f->n_layers;
-    if (!d->gout_dev || d->gout_s_n < f->width[n - 1]) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: gout_dev is null or gout_s_n below the output width %d", f->width[n - 1]);
-    int fan_in = f->f1 + f->f2;
-    for (int l = 0; l < n; l++) {
-        if ((d->dw_dev[l] != nullptr) != (d->db_dev[l] != nullptr)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dw_dev[%d] and db_dev[%d] go together", l, l);
-        if (d->dw_dev[l] && d->dw_s_n[l] < fan_in) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dw_s_n[%d] below the fan-in %d", l, fan_in);
-        fan_in = f->width[l];
-    }
-    if (d->dx_dev && d->dx_s_n < f->f1) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx_s_n below f1 = %d", f->f1);
-    if (d->dx2_dev && f->f2 == 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx2_dev without a second input piece");
-    if (d->dx2_dev && d->dx2_s_n < f->f2) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: dx2_s_n below f2 = %d", f->f2);
-    if (!d->bws_dev || (uintptr_t)d->bws_dev % sizeof(float) != 0) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: bws_dev is null or not aligned to 4 bytes");
-    const MlpLayout lay{f->batch, n, f->width};
-    const int64_t need = lay.backward_bytes();
-    if (d->bws_bytes < need) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: bws_bytes = %lld, the call needs %lld", (long long)d->bws_bytes, (long long)need);
+    char why[240];
+    if (mlp_bwd_fault(d, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: %s", why);
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    const size_t B = (size_t)f->batch;
-    auto buf = [&](int l) { return (float*)d->bws_dev + lay.alt(l, n); };      // dz of layer l, row stride pitch(l)
-    const float* dz = d->gout_dev;
-    size_t dz_s = (size_t)d->gout_s_n;
-    if (f->out_act != PTG_MLP_NONE) {
-        MlpDzOut e{d->gout_dev, (size_t)d->gout_s_n, f->out_dev, (size_t)f->out_s_n, buf(n - 1), (size_t)lay.pitch(n - 1), B, f->width[n - 1]};
-        const size_t total = B * (size_t)e.O;
-        const unsigned blocks = (unsigned)std::min<size_t>((total - 1) / 256 + 1, 65536);
-        mlp_with_act(f->out_act, [&](auto A) { k_mlp_dz_out<decltype(A)::value><<<blocks, 256, 0, st>>>(e); });
+    const int n = d->fwd.n_layers;
+    MlpBwdWalk w{d};
+    if (d->fwd.out_act != PTG_MLP_NONE) {
+        const MlpDzOut e = w.dz_out();
+        mlp_with_act(d->fwd.out_act, [&](auto A) { k_mlp_dz_out<decltype(A)::value><<<mlp_dz_out_blocks(e), 256, 0, st>>>(e); });
         if (int rc = launch_check(h, "k_mlp_dz_out")) return rc;
-        dz = e.dz; dz_s = e.dz_s;
     }
     for (int l = n - 1; l >= 0; l--) {
-        const int O = f->width[l], K = l ? f->width[l - 1] : f->f1 + f->f2;
-        const float* x = l ? (const float*)f->ws_dev + lay.kept(l - 1) : f->x_dev;      // the layer's input: hidden layer l - 1, or the call's
-        const size_t x_s = l ? (size_t)lay.pitch(l - 1) : (size_t)f->x_s_n;
         if (d->dw_dev[l]) {
-            MlpDw a{};
-            a.dz = dz; a.dz_s = dz_s; a.x = x; a.x_s = x_s; a.B = B; a.K = K; a.O = O;
-            a.x2 = !l && f->x2_dev ? f->x2_dev : x; a.x2_s = !l && f->x2_dev ? (size_t)f->x2_s_n : x_s; a.F1 = l ? K : f->f1;
-            a.dw = d->dw_dev[l]; a.dw_s = (size_t)d->dw_s_n[l]; a.db = d->db_dev[l]; a.accumulate = (d->flags & PTG_MLP_ACCUMULATE) != 0;
-            k_mlp_dw<<<dim3((unsigned)((O - 1) / BW_TILE + 1), (unsigned)(K / BW_TILE + 1)), 64, 0, st>>>(a);
+            const MlpDw a = w.dw(l);
+            k_mlp_dw<<<dim3((unsigned)((a.O - 1) / BW_TILE + 1), (unsigned)(a.K / BW_TILE + 1)), 64, 0, st>>>(a);
             if (int rc = launch_check(h, "k_mlp_dw")) return rc;
         }
         if (!l && !d->dx_dev && !d->dx2_dev) break;
-        MlpDx a{};
-        a.dz = dz; a.dz_s = dz_s; a.w = f->w_dev[l]; a.w_s = (size_t)f->w_s_n[l]; a.B = B; a.K = K; a.O = O;
-        const dim3 grid((unsigned)((B - 1) / BW_TILE + 1), (unsigned)((K - 1) / BW_TILE + 1));
-        if (l) {                         // dz of the layer below, through the derivative of the hidden activation on its kept output
-            a.h = x; a.h_s = x_s; a.y = buf(l - 1); a.y_s = x_s; a.F1 = K;
-            dz = a.y; dz_s = a.y_s;
-        } else {
-            a.y = d->dx_dev; a.y_s = (size_t)d->dx_s_n; a.y2 = d->dx2_dev; a.y2_s = (size_t)d->dx2_s_n; a.F1 = f->f1;
-        }
-        mlp_with_act(l ? f->hidden_act : PTG_MLP_NONE, [&](auto A) { k_mlp_dx<decltype(A)::value><<<grid, 64, 0, st>>>(a); });
+        const MlpDx a = w.dx(l);
+        const dim3 grid((unsigned)((a.B - 1) / BW_TILE + 1), (unsigned)((a.K - 1) / BW_TILE + 1));
+        mlp_with_act(l ? d->fwd.hidden_act : PTG_MLP_NONE, [&](auto A) { k_mlp_dx<decltype(A)::value><<<grid, 64, 0, st>>>(a); });
         if (int rc = launch_check(h, "k_mlp_dx")) return rc;
+    }
+    return 0;
+}
+
+int ptg_mlp_group_backward(ptg_env* h, const ptg_mlp_bwd* nets, int32_t n_nets, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!nets) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: null descriptor array");
+    if (n_nets < 1 || n_nets > PTG_MLP_GROUP_MAX) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: n_nets %d outside [1, %d]", n_nets, PTG_MLP_GROUP_MAX);
+    char why[240];
+    for (int i = 0; i < n_nets; i++)
+        if (mlp_bwd_fault(&nets[i], why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: net %d: %s", i, why);
+    if (mlp_group_fault(nets, sizeof(ptg_mlp_bwd), n_nets, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: %s", why);
+    for (int i = 1; i < n_nets; i++)
+        if (nets[i].flags != nets[0].flags)
+            return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: nets 0 and %d disagree in the backward's flags: %d and %d", i, nets[0].flags, nets[i].flags);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const int n = nets[0].fwd.n_layers;
+    const unsigned G = (unsigned)n_nets;
+    MlpBwdWalk w[PTG_MLP_GROUP_MAX];
+    for (int i = 0; i < n_nets; i++) w[i] = MlpBwdWalk{&nets[i]};
+    if (nets[0].fwd.out_act != PTG_MLP_NONE) {
+        MlpGroup<MlpDzOut> g{};
+        unsigned blocks = 1;
+        for (int i = 0; i < n_nets; i++) {
+            g.net[i] = w[i].dz_out();
+            blocks = std::max(blocks, mlp_dz_out_blocks(g.net[i]));
+        }
+        mlp_with_act(nets[0].fwd.out_act, [&](auto A) { k_mlp_dz_out_group<decltype(A)::value><<<dim3(blocks, 1, G), 256, 0, st>>>(g); });
+        if (int rc = launch_check(h, "k_mlp_dz_out_group")) return rc;
+    }
+    for (int l = n - 1; l >= 0; l--) {
+        bool any_dw = false, any_dx = l > 0;
+        for (int i = 0; i < n_nets; i++) {
+            any_dw = any_dw || nets[i].dw_dev[l];
+            any_dx = any_dx || nets[i].dx_dev || nets[i].dx2_dev;
+        }
+        if (any_dw) {                    // a network that freezes the layer rides along with dw == NULL: its workgroups return at once
+            MlpGroup<MlpDw> g{};
+            unsigned gx = 1, gy = 1;
+            for (int i = 0; i < n_nets; i++) {
+                g.net[i] = w[i].dw(l);
+                if (!g.net[i].dw) continue;
+                gx = std::max(gx, (unsigned)((g.net[i].O - 1) / BW_TILE + 1));
+                gy = std::max(gy, (unsigned)(g.net[i].K / BW_TILE + 1));
+            }
+            k_mlp_dw_group<<<dim3(gx, gy, G), 64, 0, st>>>(g);
+            if (int rc = launch_check(h, "k_mlp_dw_group")) return rc;
+        }
+        if (!any_dx) break;
+        MlpGroup<MlpDx> g{};             // l = 0: a network without dx_dev and dx2_dev rides along with both NULL
+        unsigned gx = 1, gy = 1;
+        for (int i = 0; i < n_nets; i++) {
+            g.net[i] = w[i].dx(l);
+            if (!l && !g.net[i].y && !g.net[i].y2) continue;
+            gx = std::max(gx, (unsigned)((g.net[i].B - 1) / BW_TILE + 1));
+            gy = std::max(gy, (unsigned)((g.net[i].K - 1) / BW_TILE + 1));
+        }
+        mlp_with_act(l ? nets[0].fwd.hidden_act : PTG_MLP_NONE, [&](auto A) { k_mlp_dx_group<decltype(A)::value><<<dim3(gx, gy, G), 64, 0, st>>>(g); });
+        if (int rc = launch_check(h, "k_mlp_dx_group")) return rc;
     }
     return 0;
 }

@@ -1,5 +1,6 @@
 """DeviceMLP: the inference forward of a torch MLP as one fused launch per layer (HipEngine.mlp_forward, include/ptg_env.h:
 ptg_mlp_forward, which states the arithmetic).  TrainMLP, below: the training forward and the backward pass under autograd.
+DeviceMLPGroup and TrainMLPGroup, at the end: several networks of equal depth in the launches of one.
 
     policy = DeviceMLP(engine, q_net, batch=engine.n)                 # an nn.Sequential of Linear / ReLU / Tanh, as SB3's create_mlp returns
     logits = policy(obs)                                              # no autograd graph, no allocation, no synchronisation
@@ -205,3 +206,184 @@ class TrainMLP(_NetBuffers):
         """x [B, F1] (and x2 [B, F2]) float32 with B <= batch -> the output [B, O] with a grad_fn: the first B rows of the preallocated
         tensor, which the next call overwrites"""
         return _TrainMLPFunction.apply(self, x, x2, *self.parameters())
+
+
+def _group_members(who, kind, engine, nets, batch):
+    """one `kind` (DeviceMLP or TrainMLP) per entry of nets, once the group is 1 to MLP_GROUP_MAX networks of equal depth and activations"""
+    if not isinstance(nets, (list, tuple)):
+        raise TypeError(f"{who}: nets must be a list with what DeviceMLP takes for each network, got {type(nets).__name__}")
+    if not 1 <= len(nets) <= _lib.MLP_GROUP_MAX:
+        raise ValueError(f"{who}: 1 to {_lib.MLP_GROUP_MAX} networks, got {len(nets)}")
+    parsed = [parse_mlp(m) for m in nets]
+    for i, (linears, hidden, out) in enumerate(parsed):
+        if len(linears) != len(parsed[0][0]):
+            raise ValueError(f"{who}: nets 0 and {i} disagree in depth: {len(parsed[0][0])} and {len(linears)} Linear layers")
+        if len(linears) > 1 and hidden != parsed[0][1]:
+            raise ValueError(f"{who}: nets 0 and {i} disagree in the hidden activation: {parsed[0][1]} and {hidden}")
+        if out != parsed[0][2]:
+            raise ValueError(f"{who}: nets 0 and {i} disagree in the output activation: {parsed[0][2]} and {out}")
+    return [kind(engine, m, batch) for m in nets]
+
+
+def _group_inputs(who, members, x, x2):
+    """(xs, x2s, B) of a group call: x and x2 each one tensor for all networks or a list with one entry per network"""
+    G = len(members)
+    xs = list(x) if isinstance(x, (list, tuple)) else [x] * G
+    x2s = list(x2) if isinstance(x2, (list, tuple)) else [x2] * G
+    if len(xs) != G or len(x2s) != G:
+        raise ValueError(f"{who}: {G} networks, got {len(xs)} inputs x and {len(x2s)} inputs x2")
+    return xs, x2s, [m._rows(t) for m, t in zip(members, xs)]
+
+
+class DeviceMLPGroup:
+    """Up to 8 DeviceMLPs of equal depth and activations in ONE launch per layer (HipEngine.mlp_group_forward; include/ptg_env.h:
+    ptg_mlp_group_forward): the two target critics of TD3 / SAC / TQC on (next_obs, next_action), critics and
+    their targets, PPO's policy and value nets on one observation batch.  Every output is, bit for bit, what a DeviceMLP of that network
+    returns.
+
+        targets = DeviceMLPGroup(engine, [qf0_target, qf1_target], batch=256)
+        q0, q1 = targets(next_obs, x2=next_actions)                       # a tensor is shared by all networks; a list gives each its own
+
+    nets: a list of what DeviceMLP takes, one entry per network; widths and input sizes may differ, depth and activations may not
+    (ValueError, which names the two networks).  DeviceMLP's rules hold: the parameters are held BY REFERENCE, output and workspace of
+    every network are allocated once for `batch` rows, a call returns the first B rows of them and the next call overwrites them.
+    Cost (profiles/mlp_group_cost.txt; DESIGN.md section 20 has the table and its one condition -- the grouped raw call's median not above
+    the G single calls' taken in turn -- which HELD at every shape).  Device time of the forward, the G single mlp_forward calls over the
+    grouped call / the same nn.Sequentials under no_grad over DeviceMLPGroup: TD3's twin critics 3 x 743 at B = 257 1.71x / 2.04x, SAC's
+    6 x 233 at 470 1.57x / 2.92x, TQC's 3 x 708 at 290 1.70x / 1.79x, PPO's pi + vf 2 x 358 at 203 1.86x / 3.65x, A2C's pi + vf 4 x 808 at
+    658 1.21x / 0.97x (LEVEL WITH TORCH, NOT AHEAD: the single network's grid already exceeds the chip there), SAC's two critics and two
+    targets at 470 1.49x / 3.10x; at B = 6 1.66x - 1.99x / 1.93x - 3.67x.  DeviceMLPGroup costs 5 - 57 us more than the raw grouped call
+    (a second set of argument checks).  A FIRST RUN of the tool, with the grouped route first in every repetition, read the grouped
+    forward ABOVE the single calls for SAC's critics (144 against 114 us at B = 6, 155 against 126 at 470) and PPO's pi + vf (72 against
+    48 at 6, 71 against 53 at 203) while this class read 44 and 42 us for PPO in the same run: the first place in a repetition cost
+    that, not the grouped kernels; the figures above are from the run in which the first place rotates.  A grouped call makes the checks of all its networks before its first launch; on an idle stream
+    that host time (70 - 180 us) is not hidden, which was not measured."""
+
+    def __init__(self, engine, nets, batch):
+        self.engine = engine
+        self.nets = _group_members("DeviceMLPGroup", DeviceMLP, engine, nets, batch)
+        self.batch = int(batch)
+
+    def __call__(self, x, x2=None):
+        """x [B, F1] (and x2 [B, F2]) float32 shared by all networks, or lists with one tensor per network -> the tuple of the G outputs"""
+        xs, x2s, Bs = _group_inputs("DeviceMLPGroup", self.nets, x, x2)
+        m0 = self.nets[0]
+        res = self.engine.mlp_group_forward(xs, [[m.weight.detach() for m in net.linears] for net in self.nets], [[m.bias.detach() for m in net.linears] for net in self.nets],
+                                            hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
+                                            outs=[None if B is None else net.out[:B] for net, B in zip(self.nets, Bs)], workspaces=[net.workspace for net in self.nets])
+        return tuple(r.out for r in res)
+
+
+class _TrainMLPGroupFunction(torch.autograd.Function):
+    """forward: mlp_group_forward with keep_hidden into the members' buffers; backward: one mlp_group_backward over the networks whose
+    output received a gradient"""
+
+    @staticmethod
+    def forward(ctx, grp, *args):                            # args: x of every network, x2 of every network, then every network's parameters
+        G = len(grp.nets)
+        det = lambda t: t.detach() if torch.is_tensor(t) else t
+        xs, x2s, params = [det(t) for t in args[:G]], [det(t) for t in args[G:2 * G]], args[2 * G:]
+        Bs = [net._rows(t) for net, t in zip(grp.nets, xs)]
+        weights, biases, at = [], [], 0
+        for net in grp.nets:
+            n = len(net.linears)
+            weights.append([p.detach() for p in params[at:at + 2 * n:2]])
+            biases.append([p.detach() for p in params[at + 1:at + 2 * n:2]])
+            at += 2 * n
+        m0 = grp.nets[0]
+        res = grp.engine.mlp_group_forward(xs, weights, biases, hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
+                                           outs=[None if B is None else net.out[:B] for net, B in zip(grp.nets, Bs)],
+                                           workspaces=[net.workspace for net in grp.nets], keep_hidden=True)
+        grp.calls += 1
+        for net, r in zip(grp.nets, res):
+            net.hidden = r.hidden
+        ctx.grp, ctx.call, ctx.xs, ctx.x2s = grp, grp.calls, xs, x2s
+        ctx.set_materialize_grads(False)                     # an unused output's gradient arrives as None, not as zeros
+        return tuple(r.out for r in res)
+
+    @staticmethod
+    def backward(ctx, *grad_outs):
+        grp = ctx.grp
+        if ctx.call != grp.calls:
+            raise RuntimeError(f"TrainMLPGroup: backward of forward call {ctx.call}, but the latest forward is call {grp.calls}: the kept activations live in the "
+                               "group's workspaces and a later forward has overwritten them (run each backward before the next forward)")
+        G = len(grp.nets)
+        needs = ctx.needs_input_grad                         # (grp, x_0 .. x_G-1, x2_0 .. x2_G-1, w, b, w, b, ... network by network)
+        gxs, gx2s, grads = [None] * G, [None] * G, []
+        call = {k: [] for k in ("grad_outs", "xs", "x2s", "weights", "biases", "outs", "workspaces", "grad_weights", "grad_biases", "grad_xs", "grad_x2s", "bws")}
+        at = 1 + 2 * G
+        for i, net in enumerate(grp.nets):
+            n = len(net.linears)
+            mine = needs[at:at + 2 * n]
+            at += 2 * n
+            g = grad_outs[i]
+            if g is None:                                    # this network's output was not used: it is left out of the call
+                grads += [None] * (2 * n)
+                continue
+            x, x2 = ctx.xs[i], ctx.x2s[i]
+            B, F1 = x.shape
+            if g.stride(1) != 1 or (B > 1 and g.stride(0) < g.shape[1]):
+                g = g.contiguous()                           # e.g. the expanded gradient of a sum
+            wanted = [mine[2 * l] or mine[2 * l + 1] for l in range(n)]
+            gw = [net.grad_weights[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
+            gb = [net.grad_biases[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
+            gxs[i] = net.grad_input[:B, :F1] if needs[1 + i] else None
+            gx2s[i] = net.grad_input[:B, F1:] if x2 is not None and needs[1 + G + i] else None
+            for k, v in (("grad_outs", g), ("xs", x), ("x2s", x2), ("weights", [m.weight.detach() for m in net.linears]), ("biases", [m.bias.detach() for m in net.linears]),
+                         ("outs", net.out[:B]), ("workspaces", net.workspace), ("grad_weights", gw), ("grad_biases", gb), ("grad_xs", gxs[i]), ("grad_x2s", gx2s[i]),
+                         ("bws", net.backward_workspace)):
+                call[k].append(v)
+            for l in range(n):
+                grads += [gw[l] if gw is not None and mine[2 * l] else None, gb[l] if gb is not None and mine[2 * l + 1] else None]
+        grp._views = (gxs, gx2s)                             # held here too, so that autograd copies them into a leaf's .grad and never adopts them
+        if call["xs"]:
+            m0 = grp.nets[0]
+            grp.engine.mlp_group_backward(call["grad_outs"], call["xs"], call["weights"], call["biases"], call["outs"], call["workspaces"],
+                                          hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=call["x2s"], grad_weights=call["grad_weights"],
+                                          grad_biases=call["grad_biases"], grad_xs=call["grad_xs"], grad_x2s=call["grad_x2s"], backward_workspaces=call["bws"])
+        return (None, *gxs, *gx2s, *grads)
+
+
+class TrainMLPGroup:
+    """Up to 8 TrainMLPs of equal depth and activations under ONE autograd function with G outputs: the forward is one launch per layer
+    (HipEngine.mlp_group_forward with keep_hidden), the backward one mlp_group_backward -- the launches of a single network's backward --
+    over the networks whose output received a gradient (include/ptg_env.h: ptg_mlp_group_backward).  Every output
+    and every gradient is, bit for bit, what a TrainMLP of that network gives.
+
+        critics = TrainMLPGroup(engine, [qf0, qf1], batch=256)
+        q0, q1 = critics(obs, x2=actions)                                 # a tensor is shared by all networks; a list gives each its own
+        torch.autograd.backward([q0, q1], [grad_q0, grad_q1])            # ONE backward over both: .grad of every parameter of both critics
+
+    A network whose output received no gradient is left out of the backward call and its parameters keep `.grad` as it was; a network
+    whose parameters all have requires_grad False launches no weight-gradient work; an input without requires_grad gets no first-layer
+    input gradient.  Both outputs must go into ONE backward pass (torch.autograd.backward on a list, or a loss that uses all of them):
+    q0.backward() followed by q1.backward() is two passes through the function, two grouped calls.
+    AN INPUT SHARED BY SEVERAL NETWORKS is handed to the function once per network, so its `.grad` is AUTOGRAD'S OWN SUM of the networks'
+    input gradients, added in network order in float32; nothing is summed inside a kernel, and each network's dx is the single op's.
+    TrainMLP's rules hold: parameters BY REFERENCE; every buffer allocated once for `batch` rows and overwritten by every call; backward()
+    before the next forward of the same group, else RuntimeError; the gradient buffers are copied into `.grad` by autograd, never adopted.
+    parameters(): all networks' parameters in network order.
+    Cost (profiles/mlp_group_cost.txt; DESIGN.md section 20 has the table and its one condition -- the grouped raw calls' median not above
+    the G single calls' taken in turn -- which HELD at every shape).  Device time of forward + backward, the G single raw calls over the
+    grouped raw calls / the same nn.Sequentials under autograd over TrainMLPGroup (below 1: slower than torch): TD3's twin critics 3 x 743
+    at B = 257 1.29x / 0.98x, SAC's 6 x 233 at 470 1.51x / 2.26x, TQC's 3 x 708 at 290 1.48x / 1.04x, PPO's pi + vf 2 x 358 at 203
+    1.15x / 1.39x, A2C's pi + vf 4 x 808 at 658 1.07x / 0.58x (SLOWER THAN TORCH: 1556 against 906 us; the grouped raw calls are 0.65x
+    there, the wide-net loss of TrainMLP, which a group does not cure); at B = 6 1.05x - 1.56x / 1.22x - 1.81x.  TrainMLPGroup costs
+    110 - 290 us more than the raw grouped calls (the autograd function, a second set of argument checks, autograd's copies into
+    .grad); a captured gradient step calls mlp_group_forward and mlp_group_backward directly."""
+
+    def __init__(self, engine, nets, batch):
+        self.engine = engine
+        self.nets = _group_members("TrainMLPGroup", TrainMLP, engine, nets, batch)
+        self.batch = int(batch)
+        self._views = None
+        self.calls = 0
+
+    def parameters(self):
+        return [p for net in self.nets for p in net.parameters()]
+
+    def __call__(self, x, x2=None):
+        """x [B, F1] (and x2 [B, F2]) float32 shared by all networks, or lists with one tensor per network -> the tuple of the G outputs,
+        each with a grad_fn"""
+        xs, x2s, _ = _group_inputs("TrainMLPGroup", self.nets, x, x2)
+        return _TrainMLPGroupFunction.apply(self, *xs, *x2s, *self.parameters())

@@ -205,6 +205,42 @@ def _workspace_arg(eng, who, label, t, need, needs="the call needs"):
         raise ValueError(f"{who}: {name} must be 4-byte aligned")
 
 
+def _mlp_bwd_desc(fwd, n, grad_out, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate):
+    """the ptg_mlp_bwd of checked arguments around the forward's descriptor"""
+    d = _lib.PtgMlpBwd(gout_dev=_ptr(grad_out), gout_s_n=_row_stride(grad_out), dx_dev=_ptr(grad_x), dx_s_n=0 if grad_x is None else _row_stride(grad_x),
+                       dx2_dev=_ptr(grad_x2), dx2_s_n=0 if grad_x2 is None else _row_stride(grad_x2), bws_dev=_ptr(backward_workspace),
+                       bws_bytes=backward_workspace.numel(), flags=_lib.MLP_ACCUMULATE if accumulate else 0)
+    d.fwd = fwd
+    for l in range(n):
+        if grad_weights is not None and grad_weights[l] is not None:
+            d.dw_dev[l], d.dw_s_n[l], d.db_dev[l] = grad_weights[l].data_ptr(), _row_stride(grad_weights[l]), grad_biases[l].data_ptr()
+    return d
+
+
+def _per_net(who, name, xs, G, share=False, optional=False):
+    """an argument of a grouped call as a list of G entries: a list or tuple of G (ValueError for another length), with `optional` also
+    None for G times None, with `share` also one tensor for all networks; TypeError for anything else"""
+    if xs is None and optional:
+        return [None] * G
+    if isinstance(xs, (list, tuple)):
+        if len(xs) != G:
+            raise ValueError(f"{who}: {name} must have one entry per network, {G}, got {len(xs)}")
+        return list(xs)
+    if share and hasattr(xs, "data_ptr"):
+        return [xs] * G
+    raise TypeError(f"{who}: {name} must be a list with one entry per network{', or one tensor for all' if share else ''}{', or None' if optional else ''}, got {type(xs).__name__}")
+
+
+def _kept_views(torch, workspace, B, widths):
+    """the hidden layers a keep_hidden forward leaves in its workspace, as [B, width_l] views"""
+    hidden, off = [], 0
+    for w in widths[:-1]:
+        p = _pitch(w)
+        hidden.append(workspace[off:off + 4 * B * p].view(torch.float32).view(B, p)[:, :w])
+        off += 4 * B * p
+    return tuple(hidden)
+
+
 class TrainOps:
     def _call(self, name, *args):
         """one stream-ordered library call -- handle first, the current stream last -- on the engine's device, its return code checked"""
@@ -1100,14 +1136,10 @@ class TrainOps:
         pitches = [_pitch(w) for w in widths[:-1]]
         return max(16, 4 * batch * (sum(pitches) if keep_hidden else 2 * max(pitches, default=0)))
 
-    def _mlp_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, route=None, first=(), grad_weights=None, grad_biases=None):
-        """The checks of a net that mlp_forward and mlp_backward share, in their one order: TypeError for what every value is (`first`:
-        the (name, tensor) pairs the caller puts before x), then ValueError for the names, the counts, x, x2 and layer by layer the
-        weights, the biases and, where given, the gradients.  Returns B, F1, F2, the widths and fill(out, workspace, flags), which
-        makes the call's ptg_mlp."""
+    def _mlp_types(self, who, x, x2, weights, biases, first=(), grad_weights=None, grad_biases=None):
+        """the TypeError half of _mlp_net: what every value is.  A group runs it over all its networks before the other half of any."""
         torch = self._torch
         f32 = (torch.float32,)
-        acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
         if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)):
             raise TypeError(f"{who}: weights and biases must be lists of tensors, got {type(weights).__name__} and {type(biases).__name__}")
         if (grad_weights is None) != (grad_biases is None):
@@ -1118,6 +1150,18 @@ class TrainOps:
         for name, t in named:                                # TypeError first: what every value is
             if not (t is None and name == "x2") and (not torch.is_tensor(t) or t.dtype not in f32):
                 check(self, who, name, t, dtypes=f32)
+
+    def _mlp_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, route=None, first=(), grad_weights=None, grad_biases=None,
+                 typed=False):
+        """The checks of a net that mlp_forward and mlp_backward share, in their one order: TypeError for what every value is (`first`:
+        the (name, tensor) pairs the caller puts before x; typed: the caller has run _mlp_types already), then ValueError for the names,
+        the counts, x, x2 and layer by layer the weights, the biases and, where given, the gradients.  Returns B, F1, F2, the widths and
+        fill(out, workspace, flags), which makes the call's ptg_mlp."""
+        torch = self._torch
+        f32 = (torch.float32,)
+        acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
+        if not typed:
+            self._mlp_types(who, x, x2, weights, biases, first=first, grad_weights=grad_weights, grad_biases=grad_biases)
         if hidden_activation not in ("relu", "tanh"):
             raise ValueError(f"{who}: hidden_activation must be 'relu' or 'tanh', got {hidden_activation!r}")
         if out_activation not in acts:
@@ -1189,15 +1233,7 @@ class TrainOps:
                 out = torch.empty((B, widths[-1]), dtype=torch.float32, device=self.device)
         flags = (_lib.MLP_KEEP_HIDDEN if keep_hidden else 0) | {None: 0, "narrow": _lib.MLP_NARROW, "wide": _lib.MLP_WIDE}[_route]
         self._call("ptg_mlp_forward", C.byref(fill(out, workspace, flags)))
-        hidden = None
-        if keep_hidden:
-            hidden, off = [], 0
-            for w in widths[:-1]:
-                p = _pitch(w)
-                hidden.append(workspace[off:off + 4 * B * p].view(torch.float32).view(B, p)[:, :w])
-                off += 4 * B * p
-            hidden = tuple(hidden)
-        return MlpOut(out, hidden)
+        return MlpOut(out, _kept_views(torch, workspace, B, widths) if keep_hidden else None)
 
     # ------------------------------------------------------------------ the backward pass of an MLP
     def mlp_backward_workspace(self, batch, widths):
@@ -1238,15 +1274,113 @@ class TrainOps:
         if backward_workspace is None:
             with torch.cuda.device(self.device):
                 backward_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        d = _lib.PtgMlpBwd(gout_dev=_ptr(grad_out), gout_s_n=_row_stride(grad_out), dx_dev=_ptr(grad_x), dx_s_n=0 if grad_x is None else _row_stride(grad_x),
-                           dx2_dev=_ptr(grad_x2), dx2_s_n=0 if grad_x2 is None else _row_stride(grad_x2), bws_dev=_ptr(backward_workspace),
-                           bws_bytes=backward_workspace.numel(), flags=_lib.MLP_ACCUMULATE if accumulate else 0)
-        d.fwd = fill(out, workspace, _lib.MLP_KEEP_HIDDEN)
-        for l in range(len(widths)):
-            if grad_weights is not None and grad_weights[l] is not None:
-                d.dw_dev[l], d.dw_s_n[l], d.db_dev[l] = grad_weights[l].data_ptr(), _row_stride(grad_weights[l]), grad_biases[l].data_ptr()
+        d = _mlp_bwd_desc(fill(out, workspace, _lib.MLP_KEEP_HIDDEN), len(widths), grad_out, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate)
         self._call("ptg_mlp_backward", C.byref(d))
         return backward_workspace
+
+    # ------------------------------------------------------------------ MLPs of equal depth in the launches of one
+    def _mlp_group(self, who, weights, biases):
+        """G of a grouped call, from its lists of lists"""
+        if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)):
+            raise TypeError(f"{who}: weights and biases must be lists with one list of tensors per network, got {type(weights).__name__} and {type(biases).__name__}")
+        G = len(weights)
+        if not 1 <= G <= _lib.MLP_GROUP_MAX:
+            raise ValueError(f"{who}: 1 to {_lib.MLP_GROUP_MAX} networks, got {G}")
+        if len(biases) != G:
+            raise ValueError(f"{who}: biases must have one entry per network, {G}, got {len(biases)}")
+        return G
+
+    def _mlp_group_agree(self, who, nets):
+        """nets: (B, F1, F2, widths, fill) per network; batch and depth must agree with network 0's"""
+        for i, net in enumerate(nets):
+            if net[0] != nets[0][0]:
+                raise ValueError(f"{who}: nets 0 and {i} disagree in the batch: {nets[0][0]} and {net[0]} rows")
+            if len(net[3]) != len(nets[0][3]):
+                raise ValueError(f"{who}: nets 0 and {i} disagree in depth: {len(nets[0][3])} and {len(net[3])} layers")
+
+    def mlp_group_forward(self, xs, weights, biases, hidden_activation="relu", out_activation=None, x2s=None, outs=None, workspaces=None, keep_hidden=False):
+        """mlp_forward for G networks, 1 <= G <= 8, of equal depth, activations and batch in ONE launch per layer (include/ptg_env.h:
+        ptg_mlp_group_forward): twin critics, critics and their targets, a policy and a value net.  Every network's result is, bit for
+        bit, what mlp_forward gives for its arguments.  xs: a list of G tensors [B, F1_i], or one tensor that every network reads;
+        weights / biases: lists of G lists as mlp_forward takes them (widths may differ, the depth may not); x2s, outs, workspaces: None,
+        or lists of G entries in which None stands where mlp_forward allows None.  Networks may share inputs and even weights; no tensor
+        may serve two of the outs and workspaces.  The arguments are checked as mlp_forward checks them: TypeError for what the values
+        of all networks are first, then ValueError network by network, the message behind "net i:".  Returns a list of G MlpOut."""
+        torch = self._torch
+        who = "mlp_group_forward"
+        G = self._mlp_group(who, weights, biases)
+        xs, x2s = _per_net(who, "xs", xs, G, share=True), _per_net(who, "x2s", x2s, G, optional=True)
+        outs, workspaces = _per_net(who, "outs", outs, G, optional=True), _per_net(who, "workspaces", workspaces, G, optional=True)
+        for i in range(G):
+            self._mlp_types(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i])
+        nets, needs = [], []
+        for i in range(G):
+            net = self._mlp_net(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, typed=True)
+            B, widths = net[0], net[3]
+            check(self, f"{who}: net {i}", "out", outs[i], dtypes=(torch.float32,), shape=(B, widths[-1]), rule=rows, optional=True, exc=ValueError)
+            needs.append(self.mlp_workspace(B, widths, keep_hidden))
+            if workspaces[i] is not None:
+                _workspace_arg(self, f"{who}: net {i}", f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspaces[i], needs[i])
+            nets.append(net)
+        self._mlp_group_agree(who, nets)
+        _no_tensor_twice(who, [t for t in outs + workspaces if t is not None], "outs and workspaces")
+        with torch.cuda.device(self.device):
+            workspaces = [torch.empty(needs[i], dtype=torch.uint8, device=self.device) if w is None else w for i, w in enumerate(workspaces)]
+            outs = [torch.empty((nets[i][0], nets[i][3][-1]), dtype=torch.float32, device=self.device) if o is None else o for i, o in enumerate(outs)]
+        flags = _lib.MLP_KEEP_HIDDEN if keep_hidden else 0
+        descs = (_lib.PtgMlp * G)(*[nets[i][4](outs[i], workspaces[i], flags) for i in range(G)])
+        self._call("ptg_mlp_group_forward", descs, G)
+        return [MlpOut(outs[i], _kept_views(torch, workspaces[i], nets[i][0], nets[i][3]) if keep_hidden else None) for i in range(G)]
+
+    def mlp_group_backward(self, grad_outs, xs, weights, biases, outs, workspaces, hidden_activation="relu", out_activation=None, x2s=None, grad_weights=None,
+                           grad_biases=None, grad_xs=None, grad_x2s=None, backward_workspaces=None, accumulate=False):
+        """mlp_backward for the G networks of an mlp_group_forward(..., keep_hidden=True) call, in the launches of ONE network's backward
+        (include/ptg_env.h: ptg_mlp_group_backward); every network's gradients are, bit for bit, what mlp_backward gives for its
+        arguments.  grad_outs, outs, workspaces: lists of G; xs as in the forward; x2s, grad_weights, grad_biases, grad_xs, grad_x2s,
+        backward_workspaces: None or lists of G entries, each what mlp_backward takes for that network (None in grad_weights[i] and
+        grad_biases[i]: no parameter gradients for network i; a None inside them freezes that layer of that network; grad_xs[i] and
+        grad_x2s[i] each optional).  A weight-gradient launch is enqueued for a layer when any network wants it, the first layer's
+        input-gradient launch when any network wants a grad_x or grad_x2.  The gradient of an input that several networks share is NOT
+        summed: each network writes its own grad_xs[i].  No tensor may serve two of the outputs.  Checked as mlp_group_forward checks.
+        Returns the list of backward workspaces."""
+        torch = self._torch
+        who = "mlp_group_backward"
+        f32 = (torch.float32,)
+        G = self._mlp_group(who, weights, biases)
+        xs, x2s = _per_net(who, "xs", xs, G, share=True), _per_net(who, "x2s", x2s, G, optional=True)
+        grad_outs, outs, workspaces = _per_net(who, "grad_outs", grad_outs, G), _per_net(who, "outs", outs, G), _per_net(who, "workspaces", workspaces, G)
+        grad_weights, grad_biases = _per_net(who, "grad_weights", grad_weights, G, optional=True), _per_net(who, "grad_biases", grad_biases, G, optional=True)
+        grad_xs, grad_x2s = _per_net(who, "grad_xs", grad_xs, G, optional=True), _per_net(who, "grad_x2s", grad_x2s, G, optional=True)
+        bws = _per_net(who, "backward_workspaces", backward_workspaces, G, optional=True)
+        for i in range(G):
+            self._mlp_types(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], first=[("grad_out", grad_outs[i])], grad_weights=grad_weights[i],
+                            grad_biases=grad_biases[i])
+        nets, needs, written = [], [], []
+        for i in range(G):
+            wi = f"{who}: net {i}"
+            net = self._mlp_net(wi, xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, first=[("grad_out", grad_outs[i])],
+                                grad_weights=grad_weights[i], grad_biases=grad_biases[i], typed=True)
+            B, F1, F2, widths, _ = net
+            check(self, wi, "grad_out", grad_outs[i], dtypes=f32, shape=(B, widths[-1]), rule=rows)
+            check(self, wi, "out", outs[i], dtypes=f32, shape=(B, widths[-1]), rule=rows, exc=ValueError)
+            _workspace_arg(self, wi, f"workspace (mlp_workspace({B}, {widths}, True))", workspaces[i], self.mlp_workspace(B, widths, True), "the forward with keep_hidden needs")
+            check(self, wi, "grad_x", grad_xs[i], dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
+            if grad_x2s[i] is not None and x2s[i] is None:
+                raise ValueError(f"{wi}: grad_x2 without x2")
+            check(self, wi, "grad_x2", grad_x2s[i], dtypes=f32, shape=(B, F2), rule=rows, optional=True, exc=ValueError)
+            needs.append(self.mlp_backward_workspace(B, widths))
+            if bws[i] is not None:
+                _workspace_arg(self, wi, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", bws[i], needs[i])
+            written += [t for t in (list(grad_weights[i] or []) + list(grad_biases[i] or []) + [grad_xs[i], grad_x2s[i], bws[i]]) if t is not None]
+            nets.append(net)
+        self._mlp_group_agree(who, nets)
+        _no_tensor_twice(who, written, "grad_weights, grad_biases, grad_xs, grad_x2s and backward_workspaces")
+        with torch.cuda.device(self.device):
+            bws = [torch.empty(needs[i], dtype=torch.uint8, device=self.device) if w is None else w for i, w in enumerate(bws)]
+        descs = (_lib.PtgMlpBwd * G)(*[_mlp_bwd_desc(nets[i][4](outs[i], workspaces[i], _lib.MLP_KEEP_HIDDEN), len(nets[i][3]), grad_outs[i], grad_weights[i],
+                                                      grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], accumulate) for i in range(G)])
+        self._call("ptg_mlp_group_backward", descs, G)
+        return bws
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):
