@@ -22,7 +22,9 @@
 // splits a row anywhere; a load instruction of a wave still reads 32 neighbouring floats of each of two rows.
 // Groups (ptg_mlp_group_forward, ptg_mlp_group_backward): the 16 x 16 tile bodies of the forward and of the backward
 // are device functions with two entry points each, the single kernel and a grouped one that runs the tiles of up to PTG_MLP_GROUP_MAX
-// networks of equal depth in one launch; a network's bits are those of its own single call.
+// networks of equal depth in one launch; a network's bits are those of its own single call.  On the host the walk over the layers is ONE
+// per direction (mlp_forward_walk, mlp_backward_walk) behind one refusal prologue (mlp_refuse): a single entry is the walk at n = 1 with
+// the single kernels, a grouped entry the same walk with the grouped ones, and every grid comes from one function per kernel (mlp_grid).
 #include "ptg_handle.h"
 
 #include <cmath>
@@ -248,14 +250,6 @@ void mlp_with_act(int act, F f)
     else f(std::integral_constant<int, PTG_MLP_NONE>{});
 }
 
-template <int ROUTE>
-void launch_mlp_layer(hipStream_t st, const MlpLayer& a, int act)
-{
-    const int tile = ROUTE == MLP_NARROW ? NR_TILE : WD_TILE;
-    const dim3 grid((unsigned)((a.B - 1) / tile + 1), (unsigned)((a.O - 1) / tile + 1)), block(ROUTE == MLP_NARROW ? 64 : 256);      // x: up to 2^27 row tiles
-    mlp_with_act(act, [&](auto A) { k_mlp_layer<decltype(A)::value, ROUTE><<<grid, block, 0, st>>>(a); });
-}
-
 // ---- the grouped launches (include/ptg_env.h, ptg_mlp_group_forward) ------------------------------------------------
 // Up to PTG_MLP_GROUP_MAX networks in one launch: the by-value structs of the single kernels side by side in the kernel arguments,
 // blockIdx.z picks the network, gridDim.x / .y are the largest tile counts of the group.  The tile bodies are the single kernels': a
@@ -275,14 +269,23 @@ __global__ __launch_bounds__(64) void k_mlp_layer_group(const MlpGroup<MlpLayer>
     mlp_layer_tile16<ACT>(a, blockIdx.x, blockIdx.y);
 }
 
-void launch_mlp_layer_group(hipStream_t st, const MlpGroup<MlpLayer>& g, int n_nets, int act)
+// The grid of a launch: the component-wise maximum over the networks that take part, blockIdx.z the network.  own(i) is the grid network i
+// needs by itself (mlp_layer_grid, mlp_dw_grid, mlp_dx_grid, mlp_dz_out_blocks), or dim3() where it only rides along.  One network: its own grid.
+template <typename Own>
+dim3 mlp_grid(int n_nets, Own own)
 {
-    unsigned gx = 1, gy = 1;
+    dim3 grid(1, 1, (unsigned)n_nets);
     for (int i = 0; i < n_nets; i++) {
-        gx = std::max(gx, (unsigned)((g.net[i].B - 1) / NR_TILE + 1));
-        gy = std::max(gy, (unsigned)((g.net[i].O - 1) / NR_TILE + 1));
+        const dim3 e = own(i);
+        grid.x = std::max(grid.x, e.x);
+        grid.y = std::max(grid.y, e.y);
     }
-    mlp_with_act(act, [&](auto A) { k_mlp_layer_group<decltype(A)::value><<<dim3(gx, gy, (unsigned)n_nets), 64, 0, st>>>(g); });
+    return grid;
+}
+
+dim3 mlp_layer_grid(const MlpLayer& a, int tile)
+{
+    return dim3((unsigned)((a.B - 1) / tile + 1), (unsigned)((a.O - 1) / tile + 1));      // x: up to 2^27 row tiles
 }
 
 // The layout of both workspaces (include/ptg_env.h): a hidden layer and a dz buffer are [batch][pitch(l)] floats
@@ -400,6 +403,56 @@ bool mlp_group_fault(const void* nets, size_t stride, int n_nets, char* why, siz
     return false;
 }
 
+// What all four entries refuse before their first launch, in one order: the array, the count, each descriptor's own fault (`fault`:
+// mlp_desc_fault or mlp_bwd_fault; grouped: behind "net i: "), then, grouped, what the networks must agree in.  0, or the error set in h
+template <typename D, typename Fault>
+int mlp_refuse(ptg_env* h, const char* who, const D* nets, int n_nets, bool grouped, Fault fault)
+{
+    if (!nets) return set_err(h, PTG_E_INVALID, "%s: null descriptor%s", who, grouped ? " array" : "");
+    if (n_nets < 1 || n_nets > PTG_MLP_GROUP_MAX) return set_err(h, PTG_E_INVALID, "%s: n_nets %d outside [1, %d]", who, n_nets, PTG_MLP_GROUP_MAX);
+    char why[240];
+    for (int i = 0; i < n_nets; i++) {
+        if (!fault(&nets[i], why, sizeof why)) continue;
+        return grouped ? set_err(h, PTG_E_INVALID, "%s: net %d: %s", who, i, why) : set_err(h, PTG_E_INVALID, "%s: %s", who, why);
+    }
+    if (!grouped) return 0;
+    if (mlp_group_fault(nets, sizeof(D), n_nets, why, sizeof why)) return set_err(h, PTG_E_INVALID, "%s: %s", who, why);
+    if constexpr (std::is_same<D, ptg_mlp_bwd>::value)
+        for (int i = 1; i < n_nets; i++)
+            if (nets[i].flags != nets[0].flags)
+                return set_err(h, PTG_E_INVALID, "%s: nets 0 and %d disagree in the backward's flags: %d and %d", who, i, nets[0].flags, nets[i].flags);
+    return 0;
+}
+
+// THE forward: ptg_mlp_forward is this walk over one network with the single kernel (and its NARROW / WIDE choice), ptg_mlp_group_forward
+// the same walk with the grouped kernel.  `grouped` is the entry that was called, not n_nets > 1: a group of one launches the grouped kernel
+int mlp_forward_walk(ptg_env* h, const char* who, const ptg_mlp* nets, int n_nets, bool grouped, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (int rc = mlp_refuse(h, who, nets, n_nets, grouped, mlp_desc_fault)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const ptg_mlp* d = &nets[0];         // depth, activations, batch and flags: the group's
+    const int n = d->n_layers;
+    MlpGroup<MlpLayer> g{};
+    for (int i = 0; i < n_nets; i++) g.net[i] = mlp_first_input(&nets[i]);
+    for (int l = 0; l < n; l++) {
+        for (int i = 0; i < n_nets; i++) mlp_set_layer(g.net[i], &nets[i], l);
+        const MlpLayer& a = g.net[0];
+        const bool wide = !grouped && ((d->flags & PTG_MLP_WIDE) || (!(d->flags & PTG_MLP_NARROW) && ((d->batch >= MLP_WIDE_MIN_ROWS && a.O > MLP_WIDE_MIN_UNITS) || (d->batch >= MLP_WIDE_MIN_ROWS_BROAD && a.O > MLP_BROAD_UNITS))));
+        const dim3 grid = mlp_grid(n_nets, [&](int i) { return mlp_layer_grid(g.net[i], wide ? WD_TILE : NR_TILE); });
+        mlp_with_act(l == n - 1 ? d->out_act : d->hidden_act, [&](auto A) {
+            constexpr int ACT = decltype(A)::value;
+            if (grouped) k_mlp_layer_group<ACT><<<grid, 64, 0, st>>>(g);
+            else if (wide) k_mlp_layer<ACT, MLP_WIDE><<<grid, 256, 0, st>>>(a);
+            else k_mlp_layer<ACT, MLP_NARROW><<<grid, 64, 0, st>>>(a);
+        });
+        if (int rc = launch_check(h, grouped ? "k_mlp_layer_group" : "k_mlp_layer")) return rc;
+        for (int i = 0; i < n_nets; i++) mlp_next_input(g.net[i]);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -413,47 +466,12 @@ int64_t ptg_mlp_workspace(int64_t batch, int32_t n_layers, const int32_t* widths
 
 int ptg_mlp_forward(ptg_env* h, const ptg_mlp* d, void* stream)
 {
-    if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: null descriptor");
-    char why[160];
-    if (mlp_desc_fault(d, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_forward: %s", why);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const hipStream_t st = as_stream(stream);
-    const int n = d->n_layers;
-    MlpLayer a = mlp_first_input(d);
-    for (int l = 0; l < n; l++) {
-        mlp_set_layer(a, d, l);
-        const int act = l == n - 1 ? d->out_act : d->hidden_act;
-        const bool wide = (d->flags & PTG_MLP_WIDE) || (!(d->flags & PTG_MLP_NARROW) && ((d->batch >= MLP_WIDE_MIN_ROWS && a.O > MLP_WIDE_MIN_UNITS) || (d->batch >= MLP_WIDE_MIN_ROWS_BROAD && a.O > MLP_BROAD_UNITS)));
-        if (wide) launch_mlp_layer<MLP_WIDE>(st, a, act);
-        else launch_mlp_layer<MLP_NARROW>(st, a, act);
-        if (int rc = launch_check(h, "k_mlp_layer")) return rc;
-        mlp_next_input(a);
-    }
-    return 0;
+    return mlp_forward_walk(h, "ptg_mlp_forward", d, 1, false, stream);
 }
 
 int ptg_mlp_group_forward(ptg_env* h, const ptg_mlp* nets, int32_t n_nets, void* stream)
 {
-    if (!h) return PTG_E_INVALID;
-    if (!nets) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: null descriptor array");
-    if (n_nets < 1 || n_nets > PTG_MLP_GROUP_MAX) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: n_nets %d outside [1, %d]", n_nets, PTG_MLP_GROUP_MAX);
-    char why[200];
-    for (int i = 0; i < n_nets; i++)
-        if (mlp_desc_fault(&nets[i], why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: net %d: %s", i, why);
-    if (mlp_group_fault(nets, sizeof(ptg_mlp), n_nets, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_forward: %s", why);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const hipStream_t st = as_stream(stream);
-    const int n = nets[0].n_layers;
-    MlpGroup<MlpLayer> g{};
-    for (int i = 0; i < n_nets; i++) g.net[i] = mlp_first_input(&nets[i]);
-    for (int l = 0; l < n; l++) {
-        for (int i = 0; i < n_nets; i++) mlp_set_layer(g.net[i], &nets[i], l);
-        launch_mlp_layer_group(st, g, n_nets, l == n - 1 ? nets[0].out_act : nets[0].hidden_act);
-        if (int rc = launch_check(h, "k_mlp_layer_group")) return rc;
-        for (int i = 0; i < n_nets; i++) mlp_next_input(g.net[i]);
-    }
-    return 0;
+    return mlp_forward_walk(h, "ptg_mlp_group_forward", nets, n_nets, true, stream);
 }
 
 }  // extern "C"
@@ -746,6 +764,67 @@ unsigned mlp_dz_out_blocks(const MlpDzOut& e)
     return (unsigned)std::min<size_t>((e.B * (size_t)e.O - 1) / 256 + 1, 65536);
 }
 
+dim3 mlp_dw_grid(const MlpDw& a)
+{
+    return dim3((unsigned)((a.O - 1) / BW_TILE + 1), (unsigned)(a.K / BW_TILE + 1));      // K / 16 + 1, not (K - 1) / 16 + 1: column K is the bias gradient
+}
+
+dim3 mlp_dx_grid(const MlpDx& a)
+{
+    return dim3((unsigned)((a.B - 1) / BW_TILE + 1), (unsigned)((a.K - 1) / BW_TILE + 1));
+}
+
+// THE backward, as mlp_forward_walk is the forward: ptg_mlp_backward walks one network with the single kernels, ptg_mlp_group_backward
+// up to PTG_MLP_GROUP_MAX with the grouped ones.  One skip rule: dw(l) is launched when any network wants it, dx(0) when any wants dx or dx2
+int mlp_backward_walk(ptg_env* h, const char* who, const ptg_mlp_bwd* nets, int n_nets, bool grouped, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (int rc = mlp_refuse(h, who, nets, n_nets, grouped, mlp_bwd_fault)) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const ptg_mlp* f = &nets[0].fwd;     // depth and activations: the group's
+    const int n = f->n_layers;
+    MlpBwdWalk w[PTG_MLP_GROUP_MAX];
+    for (int i = 0; i < n_nets; i++) w[i] = MlpBwdWalk{&nets[i]};
+    if (f->out_act != PTG_MLP_NONE) {
+        MlpGroup<MlpDzOut> g{};
+        for (int i = 0; i < n_nets; i++) g.net[i] = w[i].dz_out();
+        const dim3 grid = mlp_grid(n_nets, [&](int i) { return dim3(mlp_dz_out_blocks(g.net[i])); });
+        mlp_with_act(f->out_act, [&](auto A) {
+            constexpr int ACT = decltype(A)::value;
+            if (grouped) k_mlp_dz_out_group<ACT><<<grid, 256, 0, st>>>(g);
+            else k_mlp_dz_out<ACT><<<grid, 256, 0, st>>>(g.net[0]);
+        });
+        if (int rc = launch_check(h, grouped ? "k_mlp_dz_out_group" : "k_mlp_dz_out")) return rc;
+    }
+    for (int l = n - 1; l >= 0; l--) {
+        bool any_dw = false, any_dx = l > 0;
+        for (int i = 0; i < n_nets; i++) {
+            any_dw = any_dw || nets[i].dw_dev[l];
+            any_dx = any_dx || nets[i].dx_dev || nets[i].dx2_dev;
+        }
+        if (any_dw) {                    // a network that freezes the layer rides along with dw == NULL: its workgroups return at once
+            MlpGroup<MlpDw> g{};
+            for (int i = 0; i < n_nets; i++) g.net[i] = w[i].dw(l);
+            const dim3 grid = mlp_grid(n_nets, [&](int i) { return g.net[i].dw ? mlp_dw_grid(g.net[i]) : dim3(); });
+            if (grouped) k_mlp_dw_group<<<grid, 64, 0, st>>>(g);
+            else k_mlp_dw<<<grid, 64, 0, st>>>(g.net[0]);
+            if (int rc = launch_check(h, grouped ? "k_mlp_dw_group" : "k_mlp_dw")) return rc;
+        }
+        if (!any_dx) break;
+        MlpGroup<MlpDx> g{};             // l = 0: a network without dx_dev and dx2_dev rides along with both NULL
+        for (int i = 0; i < n_nets; i++) g.net[i] = w[i].dx(l);
+        const dim3 grid = mlp_grid(n_nets, [&](int i) { return l || g.net[i].y || g.net[i].y2 ? mlp_dx_grid(g.net[i]) : dim3(); });
+        mlp_with_act(l ? f->hidden_act : PTG_MLP_NONE, [&](auto A) {
+            constexpr int ACT_BELOW = decltype(A)::value;
+            if (grouped) k_mlp_dx_group<ACT_BELOW><<<grid, 64, 0, st>>>(g);
+            else k_mlp_dx<ACT_BELOW><<<grid, 64, 0, st>>>(g.net[0]);
+        });
+        if (int rc = launch_check(h, grouped ? "k_mlp_dx_group" : "k_mlp_dx")) return rc;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -758,93 +837,12 @@ int64_t ptg_mlp_backward_workspace(int64_t batch, int32_t n_layers, const int32_
 
 int ptg_mlp_backward(ptg_env* h, const ptg_mlp_bwd* d, void* stream)
 {
-    if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: null descriptor");
-    char why[240];
-    if (mlp_bwd_fault(d, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_backward: %s", why);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const hipStream_t st = as_stream(stream);
-    const int n = d->fwd.n_layers;
-    MlpBwdWalk w{d};
-    if (d->fwd.out_act != PTG_MLP_NONE) {
-        const MlpDzOut e = w.dz_out();
-        mlp_with_act(d->fwd.out_act, [&](auto A) { k_mlp_dz_out<decltype(A)::value><<<mlp_dz_out_blocks(e), 256, 0, st>>>(e); });
-        if (int rc = launch_check(h, "k_mlp_dz_out")) return rc;
-    }
-    for (int l = n - 1; l >= 0; l--) {
-        if (d->dw_dev[l]) {
-            const MlpDw a = w.dw(l);
-            k_mlp_dw<<<dim3((unsigned)((a.O - 1) / BW_TILE + 1), (unsigned)(a.K / BW_TILE + 1)), 64, 0, st>>>(a);
-            if (int rc = launch_check(h, "k_mlp_dw")) return rc;
-        }
-        if (!l && !d->dx_dev && !d->dx2_dev) break;
-        const MlpDx a = w.dx(l);
-        const dim3 grid((unsigned)((a.B - 1) / BW_TILE + 1), (unsigned)((a.K - 1) / BW_TILE + 1));
-        mlp_with_act(l ? d->fwd.hidden_act : PTG_MLP_NONE, [&](auto A) { k_mlp_dx<decltype(A)::value><<<grid, 64, 0, st>>>(a); });
-        if (int rc = launch_check(h, "k_mlp_dx")) return rc;
-    }
-    return 0;
+    return mlp_backward_walk(h, "ptg_mlp_backward", d, 1, false, stream);
 }
 
 int ptg_mlp_group_backward(ptg_env* h, const ptg_mlp_bwd* nets, int32_t n_nets, void* stream)
 {
-    if (!h) return PTG_E_INVALID;
-    if (!nets) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: null descriptor array");
-    if (n_nets < 1 || n_nets > PTG_MLP_GROUP_MAX) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: n_nets %d outside [1, %d]", n_nets, PTG_MLP_GROUP_MAX);
-    char why[240];
-    for (int i = 0; i < n_nets; i++)
-        if (mlp_bwd_fault(&nets[i], why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: net %d: %s", i, why);
-    if (mlp_group_fault(nets, sizeof(ptg_mlp_bwd), n_nets, why, sizeof why)) return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: %s", why);
-    for (int i = 1; i < n_nets; i++)
-        if (nets[i].flags != nets[0].flags)
-            return set_err(h, PTG_E_INVALID, "ptg_mlp_group_backward: nets 0 and %d disagree in the backward's flags: %d and %d", i, nets[0].flags, nets[i].flags);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const hipStream_t st = as_stream(stream);
-    const int n = nets[0].fwd.n_layers;
-    const unsigned G = (unsigned)n_nets;
-    MlpBwdWalk w[PTG_MLP_GROUP_MAX];
-    for (int i = 0; i < n_nets; i++) w[i] = MlpBwdWalk{&nets[i]};
-    if (nets[0].fwd.out_act != PTG_MLP_NONE) {
-        MlpGroup<MlpDzOut> g{};
-        unsigned blocks = 1;
-        for (int i = 0; i < n_nets; i++) {
-            g.net[i] = w[i].dz_out();
-            blocks = std::max(blocks, mlp_dz_out_blocks(g.net[i]));
-        }
-        mlp_with_act(nets[0].fwd.out_act, [&](auto A) { k_mlp_dz_out_group<decltype(A)::value><<<dim3(blocks, 1, G), 256, 0, st>>>(g); });
-        if (int rc = launch_check(h, "k_mlp_dz_out_group")) return rc;
-    }
-    for (int l = n - 1; l >= 0; l--) {
-        bool any_dw = false, any_dx = l > 0;
-        for (int i = 0; i < n_nets; i++) {
-            any_dw = any_dw || nets[i].dw_dev[l];
-            any_dx = any_dx || nets[i].dx_dev || nets[i].dx2_dev;
-        }
-        if (any_dw) {                    // a network that freezes the layer rides along with dw == NULL: its workgroups return at once
-            MlpGroup<MlpDw> g{};
-            unsigned gx = 1, gy = 1;
-            for (int i = 0; i < n_nets; i++) {
-                g.net[i] = w[i].dw(l);
-                if (!g.net[i].dw) continue;
-                gx = std::max(gx, (unsigned)((g.net[i].O - 1) / BW_TILE + 1));
-                gy = std::max(gy, (unsigned)(g.net[i].K / BW_TILE + 1));
-            }
-            k_mlp_dw_group<<<dim3(gx, gy, G), 64, 0, st>>>(g);
-            if (int rc = launch_check(h, "k_mlp_dw_group")) return rc;
-        }
-        if (!any_dx) break;
-        MlpGroup<MlpDx> g{};             // l = 0: a network without dx_dev and dx2_dev rides along with both NULL
-        unsigned gx = 1, gy = 1;
-        for (int i = 0; i < n_nets; i++) {
-            g.net[i] = w[i].dx(l);
-            if (!l && !g.net[i].y && !g.net[i].y2) continue;
-            gx = std::max(gx, (unsigned)((g.net[i].B - 1) / BW_TILE + 1));
-            gy = std::max(gy, (unsigned)((g.net[i].K - 1) / BW_TILE + 1));
-        }
-        mlp_with_act(l ? nets[0].fwd.hidden_act : PTG_MLP_NONE, [&](auto A) { k_mlp_dx_group<decltype(A)::value><<<dim3(gx, gy, G), 64, 0, st>>>(g); });
-        if (int rc = launch_check(h, "k_mlp_dx_group")) return rc;
-    }
-    return 0;
+    return mlp_backward_walk(h, "ptg_mlp_group_backward", nets, n_nets, true, stream);
 }
 
 }  // extern "C"

@@ -107,17 +107,39 @@ class _NetBuffers:
             raise ValueError(f"{type(self).__name__}: {B} rows, allocated for {self.batch}")
         return B
 
+    def params(self):
+        """(weights, biases) as the ops take them: the parameters where they are now, detached"""
+        return [m.weight.detach() for m in self.linears], [m.bias.detach() for m in self.linears]
+
 
 class DeviceMLP(_NetBuffers):
     def __call__(self, x, x2=None):
         """x [B, F1] (and x2 [B, F2]) float32 with B <= batch -> the output [B, O]: the first B rows of the preallocated tensor, which
         the next call overwrites.  Reads the parameters where they are now."""
         B = self._rows(x)
-        res = self.engine.mlp_forward(x, [m.weight.detach() for m in self.linears], [m.bias.detach() for m in self.linears],
-                                      hidden_activation=self.hidden_activation, out_activation=self.out_activation, x2=x2,
+        res = self.engine.mlp_forward(x, *self.params(), hidden_activation=self.hidden_activation, out_activation=self.out_activation, x2=x2,
                                       out=None if B is None else self.out[:B], workspace=self.workspace, keep_hidden=self.keep_hidden)
         self.hidden = res.hidden
         return res.out
+
+
+def _backward_plan(net, x, x2, grad_out, need_x, need_x2, need_params):
+    """One network's share of a backward call, for both autograd functions.  net: a TrainMLP; x, x2: what its forward saved; need_x, need_x2,
+    need_params (w0, b0, w1, b1, ...): its entries of needs_input_grad.  Returns grad_out with rows the op accepts, grad_weights and grad_biases
+    (None for a layer that needs neither; both None when no layer does), grad_x and grad_x2 (views into net.grad_input, or None) and grads, the network's entries of what backward() returns."""
+    B, F1 = x.shape
+    if grad_out.stride(1) != 1 or (B > 1 and grad_out.stride(0) < grad_out.shape[1]):
+        grad_out = grad_out.contiguous()                     # e.g. the expanded gradient of a sum
+    n = len(net.linears)
+    wanted = [need_params[2 * l] or need_params[2 * l + 1] for l in range(n)]
+    gw = [net.grad_weights[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
+    gb = [net.grad_biases[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
+    gx = net.grad_input[:B, :F1] if need_x else None
+    gx2 = net.grad_input[:B, F1:] if x2 is not None and need_x2 else None
+    grads = []
+    for l in range(n):
+        grads += [gw[l] if gw is not None and need_params[2 * l] else None, gb[l] if gb is not None and need_params[2 * l + 1] else None]
+    return grad_out, gw, gb, gx, gx2, grads
 
 
 class _TrainMLPFunction(torch.autograd.Function):
@@ -142,23 +164,12 @@ class _TrainMLPFunction(torch.autograd.Function):
             raise RuntimeError(f"TrainMLP: backward of forward call {ctx.call}, but the latest forward is call {net.calls}: the kept activations live in the "
                                "module's workspace and a later forward has overwritten them (run each backward before the next forward)")
         x, x2 = ctx.x, ctx.x2
-        B, F1 = x.shape
         needs = ctx.needs_input_grad                         # (net, x, x2, w0, b0, w1, b1, ...)
-        if grad_out.stride(1) != 1 or (B > 1 and grad_out.stride(0) < grad_out.shape[1]):
-            grad_out = grad_out.contiguous()                 # e.g. the expanded gradient of a sum
-        n = len(net.linears)
-        wanted = [needs[3 + 2 * l] or needs[4 + 2 * l] for l in range(n)]
-        gw = [net.grad_weights[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
-        gb = [net.grad_biases[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
-        gx = net.grad_input[:B, :F1] if needs[1] else None
-        gx2 = net.grad_input[:B, F1:] if x2 is not None and needs[2] else None
+        grad_out, gw, gb, gx, gx2, grads = _backward_plan(net, x, x2, grad_out, needs[1], needs[2], needs[3:])
         net._views = (gx, gx2)                               # held here too, so that autograd copies them into a leaf's .grad and never adopts them
-        net.engine.mlp_backward(grad_out, x, [m.weight.detach() for m in net.linears], [m.bias.detach() for m in net.linears], net.out[:B], net.workspace,
-                                hidden_activation=net.hidden_activation, out_activation=net.out_activation, x2=x2, grad_weights=gw, grad_biases=gb,
-                                grad_x=gx, grad_x2=gx2, backward_workspace=net.backward_workspace)
-        grads = []
-        for l in range(n):
-            grads += [gw[l] if gw is not None and needs[3 + 2 * l] else None, gb[l] if gb is not None and needs[4 + 2 * l] else None]
+        net.engine.mlp_backward(grad_out, x, *net.params(), net.out[:x.shape[0]], net.workspace, hidden_activation=net.hidden_activation,
+                                out_activation=net.out_activation, x2=x2, grad_weights=gw, grad_biases=gb, grad_x=gx, grad_x2=gx2,
+                                backward_workspace=net.backward_workspace)
         return (None, gx, gx2, *grads)
 
 
@@ -268,8 +279,8 @@ class DeviceMLPGroup:
         """x [B, F1] (and x2 [B, F2]) float32 shared by all networks, or lists with one tensor per network -> the tuple of the G outputs"""
         xs, x2s, Bs = _group_inputs("DeviceMLPGroup", self.nets, x, x2)
         m0 = self.nets[0]
-        res = self.engine.mlp_group_forward(xs, [[m.weight.detach() for m in net.linears] for net in self.nets], [[m.bias.detach() for m in net.linears] for net in self.nets],
-                                            hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
+        weights, biases = zip(*[net.params() for net in self.nets])
+        res = self.engine.mlp_group_forward(xs, list(weights), list(biases), hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
                                             outs=[None if B is None else net.out[:B] for net, B in zip(self.nets, Bs)], workspaces=[net.workspace for net in self.nets])
         return tuple(r.out for r in res)
 
@@ -310,37 +321,25 @@ class _TrainMLPGroupFunction(torch.autograd.Function):
         G = len(grp.nets)
         needs = ctx.needs_input_grad                         # (grp, x_0 .. x_G-1, x2_0 .. x2_G-1, w, b, w, b, ... network by network)
         gxs, gx2s, grads = [None] * G, [None] * G, []
-        call = {k: [] for k in ("grad_outs", "xs", "x2s", "weights", "biases", "outs", "workspaces", "grad_weights", "grad_biases", "grad_xs", "grad_x2s", "bws")}
+        rows = []                                            # per network that takes part: its arguments in mlp_group_backward's order
         at = 1 + 2 * G
         for i, net in enumerate(grp.nets):
             n = len(net.linears)
             mine = needs[at:at + 2 * n]
             at += 2 * n
-            g = grad_outs[i]
-            if g is None:                                    # this network's output was not used: it is left out of the call
+            if grad_outs[i] is None:                         # this network's output was not used: it is left out of the call
                 grads += [None] * (2 * n)
                 continue
             x, x2 = ctx.xs[i], ctx.x2s[i]
-            B, F1 = x.shape
-            if g.stride(1) != 1 or (B > 1 and g.stride(0) < g.shape[1]):
-                g = g.contiguous()                           # e.g. the expanded gradient of a sum
-            wanted = [mine[2 * l] or mine[2 * l + 1] for l in range(n)]
-            gw = [net.grad_weights[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
-            gb = [net.grad_biases[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
-            gxs[i] = net.grad_input[:B, :F1] if needs[1 + i] else None
-            gx2s[i] = net.grad_input[:B, F1:] if x2 is not None and needs[1 + G + i] else None
-            for k, v in (("grad_outs", g), ("xs", x), ("x2s", x2), ("weights", [m.weight.detach() for m in net.linears]), ("biases", [m.bias.detach() for m in net.linears]),
-                         ("outs", net.out[:B]), ("workspaces", net.workspace), ("grad_weights", gw), ("grad_biases", gb), ("grad_xs", gxs[i]), ("grad_x2s", gx2s[i]),
-                         ("bws", net.backward_workspace)):
-                call[k].append(v)
-            for l in range(n):
-                grads += [gw[l] if gw is not None and mine[2 * l] else None, gb[l] if gb is not None and mine[2 * l + 1] else None]
+            g, gw, gb, gxs[i], gx2s[i], own = _backward_plan(net, x, x2, grad_outs[i], needs[1 + i], needs[1 + G + i], mine)
+            grads += own
+            rows.append((g, x, *net.params(), net.out[:x.shape[0]], net.workspace, x2, gw, gb, gxs[i], gx2s[i], net.backward_workspace))
         grp._views = (gxs, gx2s)                             # held here too, so that autograd copies them into a leaf's .grad and never adopts them
-        if call["xs"]:
+        if rows:
             m0 = grp.nets[0]
-            grp.engine.mlp_group_backward(call["grad_outs"], call["xs"], call["weights"], call["biases"], call["outs"], call["workspaces"],
-                                          hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=call["x2s"], grad_weights=call["grad_weights"],
-                                          grad_biases=call["grad_biases"], grad_xs=call["grad_xs"], grad_x2s=call["grad_x2s"], backward_workspaces=call["bws"])
+            g, xs, weights, biases, outs, works, x2s, gws, gbs, dxs, dx2s, bws = (list(col) for col in zip(*rows))
+            grp.engine.mlp_group_backward(g, xs, weights, biases, outs, works, hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
+                                          grad_weights=gws, grad_biases=gbs, grad_xs=dxs, grad_x2s=dx2s, backward_workspaces=bws)
         return (None, *gxs, *gx2s, *grads)
 
 

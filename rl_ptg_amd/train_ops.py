@@ -10,7 +10,9 @@ tensor, a refused dtype, element size or element count), then ValueError for its
 the library and no device memory is allocated before every check of a call has passed.  Relations between arguments (old_values
 iff clip_range_vf, done_col inside the columns ...) stay plain `if`s in the methods.  The blocks several ops share (_column,
 _critic_columns, _alpha_arg, _out_tuple, _no_tensor_twice, _workspace_arg; TrainOps._take_workspace, _fresh_like_quantiles, _mlp_net,
-_call) stand once, next to check(), and are called at the point of the order where each op had its own copy."""
+_call) stand once, next to check(), and are called at the point of the order where each op had its own copy.  The MLP ops go one step
+further: every check of one network stands once per direction (TrainOps._mlp_forward_net, _mlp_backward_net) and so does what follows the
+checks (_mlp_fwd_desc, _mlp_bwd_desc); mlp_forward / mlp_backward run them once, the grouped ops once per network behind "net i:"."""
 import collections
 import ctypes as C
 
@@ -175,7 +177,7 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
-# ------------------------------------------------------------------ what mlp_forward and mlp_backward share (TrainOps._mlp_net too)
+# ------------------------------------------------------------------ what the single and the grouped MLP ops share (TrainOps._mlp_net, _mlp_forward_net, _mlp_backward_net too)
 def _pitch(w):
     """floats per row of a kept hidden layer and of a dz buffer: the width rounded up to 16 bytes (include/ptg_env.h)"""
     return (w + 3) // 4 * 4
@@ -205,16 +207,22 @@ def _workspace_arg(eng, who, label, t, need, needs="the call needs"):
         raise ValueError(f"{who}: {name} must be 4-byte aligned")
 
 
-def _mlp_bwd_desc(fwd, n, grad_out, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate):
-    """the ptg_mlp_bwd of checked arguments around the forward's descriptor"""
+def _mlp_bwd_desc(eng, net, grad_out, out, workspace, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate):
+    """behind the checks of a backward call: (the ptg_mlp_bwd of network `net` (what _mlp_backward_net returned) around the forward's
+    descriptor, its backward workspace: the caller's, or a fresh one)"""
+    torch = eng._torch
+    _, widths, need, fill, _ = net
+    if backward_workspace is None:
+        with torch.cuda.device(eng.device):
+            backward_workspace = torch.empty(need, dtype=torch.uint8, device=eng.device)
     d = _lib.PtgMlpBwd(gout_dev=_ptr(grad_out), gout_s_n=_row_stride(grad_out), dx_dev=_ptr(grad_x), dx_s_n=0 if grad_x is None else _row_stride(grad_x),
                        dx2_dev=_ptr(grad_x2), dx2_s_n=0 if grad_x2 is None else _row_stride(grad_x2), bws_dev=_ptr(backward_workspace),
                        bws_bytes=backward_workspace.numel(), flags=_lib.MLP_ACCUMULATE if accumulate else 0)
-    d.fwd = fwd
-    for l in range(n):
+    d.fwd = fill(out, workspace, _lib.MLP_KEEP_HIDDEN)
+    for l in range(len(widths)):
         if grad_weights is not None and grad_weights[l] is not None:
             d.dw_dev[l], d.dw_s_n[l], d.db_dev[l] = grad_weights[l].data_ptr(), _row_stride(grad_weights[l]), grad_biases[l].data_ptr()
-    return d
+    return d, backward_workspace
 
 
 def _per_net(who, name, xs, G, share=False, optional=False):
@@ -231,14 +239,22 @@ def _per_net(who, name, xs, G, share=False, optional=False):
     raise TypeError(f"{who}: {name} must be a list with one entry per network{', or one tensor for all' if share else ''}{', or None' if optional else ''}, got {type(xs).__name__}")
 
 
-def _kept_views(torch, workspace, B, widths):
-    """the hidden layers a keep_hidden forward leaves in its workspace, as [B, width_l] views"""
+def _mlp_fwd_desc(eng, net, out, workspace, keep_hidden, flags):
+    """behind the checks of a forward call: (the ptg_mlp of network `net` (what _mlp_forward_net returned), its MlpOut, its workspace, which
+    must outlive the library call), out and workspace the caller's or fresh ones; the hidden layers a keep_hidden forward leaves in its
+    workspace are [B, width_l] views into it"""
+    torch = eng._torch
+    B, widths, need, fill = net
+    if workspace is None or out is None:
+        with torch.cuda.device(eng.device):
+            workspace = torch.empty(need, dtype=torch.uint8, device=eng.device) if workspace is None else workspace
+            out = torch.empty((B, widths[-1]), dtype=torch.float32, device=eng.device) if out is None else out
     hidden, off = [], 0
-    for w in widths[:-1]:
+    for w in widths[:-1] if keep_hidden else ():
         p = _pitch(w)
         hidden.append(workspace[off:off + 4 * B * p].view(torch.float32).view(B, p)[:, :w])
         off += 4 * B * p
-    return tuple(hidden)
+    return fill(out, workspace, flags), MlpOut(out, tuple(hidden) if keep_hidden else None), workspace
 
 
 class TrainOps:
@@ -1206,6 +1222,36 @@ class TrainOps:
 
         return B, F1, F2, widths, fill
 
+    def _mlp_forward_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, keep_hidden, route=None, typed=False):
+        """Every check of ONE network's forward, for mlp_forward (who "mlp_forward") and for mlp_group_forward (who "mlp_group_forward: net i",
+        typed): _mlp_net, then out, then the workspace.  Returns B, the widths, the workspace's bytes and _mlp_net's fill."""
+        B, _, _, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, route=route, typed=typed)
+        check(self, who, "out", out, dtypes=(self._torch.float32,), shape=(B, widths[-1]), rule=rows, optional=True, exc=ValueError)
+        need = self.mlp_workspace(B, widths, keep_hidden)
+        if workspace is not None:
+            _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspace, need)
+        return B, widths, need, fill
+
+    def _mlp_backward_net(self, who, grad_out, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, grad_weights, grad_biases, grad_x, grad_x2,
+                          backward_workspace, typed=False):
+        """Every check of ONE network's backward, for mlp_backward and for mlp_group_backward as _mlp_forward_net is for the forwards.
+        Returns B, the widths, the backward workspace's bytes, _mlp_net's fill and the tensors the network writes."""
+        f32 = (self._torch.float32,)
+        B, F1, F2, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, first=[("grad_out", grad_out)],
+                                                grad_weights=grad_weights, grad_biases=grad_biases, typed=typed)
+        check(self, who, "grad_out", grad_out, dtypes=f32, shape=(B, widths[-1]), rule=rows)
+        check(self, who, "out", out, dtypes=f32, shape=(B, widths[-1]), rule=rows, exc=ValueError)
+        _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, True))", workspace, self.mlp_workspace(B, widths, True), "the forward with keep_hidden needs")
+        check(self, who, "grad_x", grad_x, dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
+        if grad_x2 is not None and x2 is None:
+            raise ValueError(f"{who}: grad_x2 without x2")
+        check(self, who, "grad_x2", grad_x2, dtypes=f32, shape=(B, F2), rule=rows, optional=True, exc=ValueError)
+        need = self.mlp_backward_workspace(B, widths)
+        if backward_workspace is not None:
+            _workspace_arg(self, who, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", backward_workspace, need)
+        written = [t for t in (list(grad_weights or []) + list(grad_biases or []) + [grad_x, grad_x2, backward_workspace]) if t is not None]
+        return B, widths, need, fill, written
+
     def mlp_forward(self, x, weights, biases, hidden_activation="relu", out_activation=None, x2=None, out=None, workspace=None, keep_hidden=False,
                     _route=None):
         """Enqueue, on the current stream, the forward pass of an MLP without autograd: one fused launch per layer (include/ptg_env.h:
@@ -1219,21 +1265,11 @@ class TrainOps:
         hidden layers stay in the workspace and are returned as views into it.  Returns MlpOut(out, hidden): hidden a tuple of n - 1
         [B, width_l] views, or None.  No synchronisation and, with out= and workspace=, no allocation; a -0 result may come out as +0.
         `_route` ("narrow" | "wide") forces one tile route in every layer: for tests and measurements, the bits do not depend on it."""
-        torch = self._torch
-        who = "mlp_forward"
-        B, F1, F2, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, route=_route)
-        check(self, who, "out", out, dtypes=(torch.float32,), shape=(B, widths[-1]), rule=rows, optional=True, exc=ValueError)
-        need = self.mlp_workspace(B, widths, keep_hidden)
-        if workspace is not None:
-            _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspace, need)
-        with torch.cuda.device(self.device):
-            if workspace is None:
-                workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            if out is None:
-                out = torch.empty((B, widths[-1]), dtype=torch.float32, device=self.device)
+        net = self._mlp_forward_net("mlp_forward", x, x2, weights, biases, hidden_activation, out_activation, out, workspace, keep_hidden, route=_route)
         flags = (_lib.MLP_KEEP_HIDDEN if keep_hidden else 0) | {None: 0, "narrow": _lib.MLP_NARROW, "wide": _lib.MLP_WIDE}[_route]
-        self._call("ptg_mlp_forward", C.byref(fill(out, workspace, flags)))
-        return MlpOut(out, _kept_views(torch, workspace, B, widths) if keep_hidden else None)
+        d, res, workspace = _mlp_fwd_desc(self, net, out, workspace, keep_hidden, flags)
+        self._call("ptg_mlp_forward", C.byref(d))
+        return res
 
     # ------------------------------------------------------------------ the backward pass of an MLP
     def mlp_backward_workspace(self, batch, widths):
@@ -1254,27 +1290,10 @@ class TrainOps:
         4-byte aligned, allocated when None.  accumulate: the parameter gradients are added to in place, continuing each element's chain
         over the rows.  Nothing but backward_workspace is allocated; no synchronisation.  Returns the backward workspace (dz of layers 0
         and 1 stay in it: include/ptg_env.h has the layout)."""
-        torch = self._torch
-        who = "mlp_backward"
-        f32 = (torch.float32,)
-        B, F1, F2, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, first=[("grad_out", grad_out)],
-                                                grad_weights=grad_weights, grad_biases=grad_biases)
-        check(self, who, "grad_out", grad_out, dtypes=f32, shape=(B, widths[-1]), rule=rows)
-        check(self, who, "out", out, dtypes=f32, shape=(B, widths[-1]), rule=rows, exc=ValueError)
-        _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, True))", workspace, self.mlp_workspace(B, widths, True), "the forward with keep_hidden needs")
-        check(self, who, "grad_x", grad_x, dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
-        if grad_x2 is not None and x2 is None:
-            raise ValueError(f"{who}: grad_x2 without x2")
-        check(self, who, "grad_x2", grad_x2, dtypes=f32, shape=(B, F2), rule=rows, optional=True, exc=ValueError)
-        need = self.mlp_backward_workspace(B, widths)
-        if backward_workspace is not None:
-            _workspace_arg(self, who, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", backward_workspace, need)
-        outs = [t for t in (list(grad_weights or []) + list(grad_biases or []) + [grad_x, grad_x2, backward_workspace]) if t is not None]
-        _no_tensor_twice(who, outs, "grad_weights, grad_biases, grad_x, grad_x2 and backward_workspace")
-        if backward_workspace is None:
-            with torch.cuda.device(self.device):
-                backward_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        d = _mlp_bwd_desc(fill(out, workspace, _lib.MLP_KEEP_HIDDEN), len(widths), grad_out, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate)
+        net = self._mlp_backward_net("mlp_backward", grad_out, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, grad_weights, grad_biases,
+                                     grad_x, grad_x2, backward_workspace)
+        _no_tensor_twice("mlp_backward", net[4], "grad_weights, grad_biases, grad_x, grad_x2 and backward_workspace")
+        d, backward_workspace = _mlp_bwd_desc(self, net, grad_out, out, workspace, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate)
         self._call("ptg_mlp_backward", C.byref(d))
         return backward_workspace
 
@@ -1291,12 +1310,12 @@ class TrainOps:
         return G
 
     def _mlp_group_agree(self, who, nets):
-        """nets: (B, F1, F2, widths, fill) per network; batch and depth must agree with network 0's"""
+        """nets: what _mlp_forward_net or _mlp_backward_net returned per network; batch and depth must agree with network 0's"""
         for i, net in enumerate(nets):
             if net[0] != nets[0][0]:
                 raise ValueError(f"{who}: nets 0 and {i} disagree in the batch: {nets[0][0]} and {net[0]} rows")
-            if len(net[3]) != len(nets[0][3]):
-                raise ValueError(f"{who}: nets 0 and {i} disagree in depth: {len(nets[0][3])} and {len(net[3])} layers")
+            if len(net[1]) != len(nets[0][1]):
+                raise ValueError(f"{who}: nets 0 and {i} disagree in depth: {len(nets[0][1])} and {len(net[1])} layers")
 
     def mlp_group_forward(self, xs, weights, biases, hidden_activation="relu", out_activation=None, x2s=None, outs=None, workspaces=None, keep_hidden=False):
         """mlp_forward for G networks, 1 <= G <= 8, of equal depth, activations and batch in ONE launch per layer (include/ptg_env.h:
@@ -1306,31 +1325,19 @@ class TrainOps:
         or lists of G entries in which None stands where mlp_forward allows None.  Networks may share inputs and even weights; no tensor
         may serve two of the outs and workspaces.  The arguments are checked as mlp_forward checks them: TypeError for what the values
         of all networks are first, then ValueError network by network, the message behind "net i:".  Returns a list of G MlpOut."""
-        torch = self._torch
         who = "mlp_group_forward"
         G = self._mlp_group(who, weights, biases)
         xs, x2s = _per_net(who, "xs", xs, G, share=True), _per_net(who, "x2s", x2s, G, optional=True)
         outs, workspaces = _per_net(who, "outs", outs, G, optional=True), _per_net(who, "workspaces", workspaces, G, optional=True)
         for i in range(G):
             self._mlp_types(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i])
-        nets, needs = [], []
-        for i in range(G):
-            net = self._mlp_net(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, typed=True)
-            B, widths = net[0], net[3]
-            check(self, f"{who}: net {i}", "out", outs[i], dtypes=(torch.float32,), shape=(B, widths[-1]), rule=rows, optional=True, exc=ValueError)
-            needs.append(self.mlp_workspace(B, widths, keep_hidden))
-            if workspaces[i] is not None:
-                _workspace_arg(self, f"{who}: net {i}", f"workspace (mlp_workspace({B}, {widths}, {bool(keep_hidden)}))", workspaces[i], needs[i])
-            nets.append(net)
+        nets = [self._mlp_forward_net(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, outs[i], workspaces[i], keep_hidden,
+                                      typed=True) for i in range(G)]
         self._mlp_group_agree(who, nets)
         _no_tensor_twice(who, [t for t in outs + workspaces if t is not None], "outs and workspaces")
-        with torch.cuda.device(self.device):
-            workspaces = [torch.empty(needs[i], dtype=torch.uint8, device=self.device) if w is None else w for i, w in enumerate(workspaces)]
-            outs = [torch.empty((nets[i][0], nets[i][3][-1]), dtype=torch.float32, device=self.device) if o is None else o for i, o in enumerate(outs)]
-        flags = _lib.MLP_KEEP_HIDDEN if keep_hidden else 0
-        descs = (_lib.PtgMlp * G)(*[nets[i][4](outs[i], workspaces[i], flags) for i in range(G)])
-        self._call("ptg_mlp_group_forward", descs, G)
-        return [MlpOut(outs[i], _kept_views(torch, workspaces[i], nets[i][0], nets[i][3]) if keep_hidden else None) for i in range(G)]
+        made = [_mlp_fwd_desc(self, nets[i], outs[i], workspaces[i], keep_hidden, _lib.MLP_KEEP_HIDDEN if keep_hidden else 0) for i in range(G)]
+        self._call("ptg_mlp_group_forward", (_lib.PtgMlp * G)(*[m[0] for m in made]), G)      # made holds the workspaces until here
+        return [m[1] for m in made]
 
     def mlp_group_backward(self, grad_outs, xs, weights, biases, outs, workspaces, hidden_activation="relu", out_activation=None, x2s=None, grad_weights=None,
                            grad_biases=None, grad_xs=None, grad_x2s=None, backward_workspaces=None, accumulate=False):
@@ -1343,9 +1350,7 @@ class TrainOps:
         input-gradient launch when any network wants a grad_x or grad_x2.  The gradient of an input that several networks share is NOT
         summed: each network writes its own grad_xs[i].  No tensor may serve two of the outputs.  Checked as mlp_group_forward checks.
         Returns the list of backward workspaces."""
-        torch = self._torch
         who = "mlp_group_backward"
-        f32 = (torch.float32,)
         G = self._mlp_group(who, weights, biases)
         xs, x2s = _per_net(who, "xs", xs, G, share=True), _per_net(who, "x2s", x2s, G, optional=True)
         grad_outs, outs, workspaces = _per_net(who, "grad_outs", grad_outs, G), _per_net(who, "outs", outs, G), _per_net(who, "workspaces", workspaces, G)
@@ -1355,32 +1360,14 @@ class TrainOps:
         for i in range(G):
             self._mlp_types(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], first=[("grad_out", grad_outs[i])], grad_weights=grad_weights[i],
                             grad_biases=grad_biases[i])
-        nets, needs, written = [], [], []
-        for i in range(G):
-            wi = f"{who}: net {i}"
-            net = self._mlp_net(wi, xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, first=[("grad_out", grad_outs[i])],
-                                grad_weights=grad_weights[i], grad_biases=grad_biases[i], typed=True)
-            B, F1, F2, widths, _ = net
-            check(self, wi, "grad_out", grad_outs[i], dtypes=f32, shape=(B, widths[-1]), rule=rows)
-            check(self, wi, "out", outs[i], dtypes=f32, shape=(B, widths[-1]), rule=rows, exc=ValueError)
-            _workspace_arg(self, wi, f"workspace (mlp_workspace({B}, {widths}, True))", workspaces[i], self.mlp_workspace(B, widths, True), "the forward with keep_hidden needs")
-            check(self, wi, "grad_x", grad_xs[i], dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
-            if grad_x2s[i] is not None and x2s[i] is None:
-                raise ValueError(f"{wi}: grad_x2 without x2")
-            check(self, wi, "grad_x2", grad_x2s[i], dtypes=f32, shape=(B, F2), rule=rows, optional=True, exc=ValueError)
-            needs.append(self.mlp_backward_workspace(B, widths))
-            if bws[i] is not None:
-                _workspace_arg(self, wi, f"backward_workspace (mlp_backward_workspace({B}, {widths}))", bws[i], needs[i])
-            written += [t for t in (list(grad_weights[i] or []) + list(grad_biases[i] or []) + [grad_xs[i], grad_x2s[i], bws[i]]) if t is not None]
-            nets.append(net)
+        nets = [self._mlp_backward_net(f"{who}: net {i}", grad_outs[i], xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, outs[i], workspaces[i],
+                                       grad_weights[i], grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], typed=True) for i in range(G)]
         self._mlp_group_agree(who, nets)
-        _no_tensor_twice(who, written, "grad_weights, grad_biases, grad_xs, grad_x2s and backward_workspaces")
-        with torch.cuda.device(self.device):
-            bws = [torch.empty(needs[i], dtype=torch.uint8, device=self.device) if w is None else w for i, w in enumerate(bws)]
-        descs = (_lib.PtgMlpBwd * G)(*[_mlp_bwd_desc(nets[i][4](outs[i], workspaces[i], _lib.MLP_KEEP_HIDDEN), len(nets[i][3]), grad_outs[i], grad_weights[i],
-                                                      grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], accumulate) for i in range(G)])
-        self._call("ptg_mlp_group_backward", descs, G)
-        return bws
+        _no_tensor_twice(who, [t for net in nets for t in net[4]], "grad_weights, grad_biases, grad_xs, grad_x2s and backward_workspaces")
+        made = [_mlp_bwd_desc(self, nets[i], grad_outs[i], outs[i], workspaces[i], grad_weights[i], grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], accumulate)
+                for i in range(G)]
+        self._call("ptg_mlp_group_backward", (_lib.PtgMlpBwd * G)(*[d for d, _ in made]), G)
+        return [w for _, w in made]
 
     # ------------------------------------------------------------------ the optimiser step behind loss.backward()
     def optim_chunk(self):

@@ -252,6 +252,45 @@ def test_the_order_of_the_networks_changes_no_bits_and_two_runs_agree():
         _same(c[i], a[i], ("again", i))
 
 
+def test_the_skip_rules_of_the_one_walk_through_both_entries():
+    """The launches the shared walk leaves out, decided by one rule for ptg_mlp_backward and ptg_mlp_group_backward: every layer frozen with
+    grad_x and grad_x2 wanted (no dw launch at all), layer 1 frozen alone, and neither grad_x nor grad_x2 (the walk ends after dw(0)), each
+    without and with an output activation (the dz_out launch), through the single entry and as network 0 of a group of two whose other
+    network wants everything.  B = 17 and 41 (40 + 1) -> 33 -> 17 -> 5: a ragged tile in every grid dimension of every kernel, and the
+    bias column K = 16 k + 1 of dw(1) and dw(2) in a tile of its own.  What a pattern still writes has the bits of the call that wants
+    everything; a frozen layer and an unwanted dx have no tensor, and every sentinel frame, pad column and workspace tail around the
+    written ones is intact (the harness's `ok`)"""
+    eng = _engine()
+    B = 17
+    x, ws, bs, gout = tb._case(77, B, 41, [33, 17, 5])
+    net = dict(x=x, ws=ws, bs=bs, gout=gout, f1=40)
+    other = _net_case(77, B, 0, 3)                           # 40 -> 37 -> 37 -> 5: other tile counts in every launch
+    patterns = [dict(frozen=(0, 1, 2)), dict(frozen=(1,)), dict(want_dx=False, want_dx2=False)]
+
+    def written_same(got, full, p, what):
+        assert got["ok"] and full["ok"], what
+        assert mr.same_bits(got["out"], full["out"]) and all(mr.same_bits(a, b) for a, b in zip(got["hidden"], full["hidden"])), what
+        for l in range(3):
+            if l in p.get("frozen", ()):
+                assert got["dws"][l] is None and got["dbs"][l] is None, (what, l)
+            else:
+                assert mr.same_bits(got["dws"][l], full["dws"][l]) and mr.same_bits(got["dbs"][l], full["dbs"][l]), (what, l)
+        if p.get("want_dx", True):
+            assert not np.isnan(got["dx"]).any() and mr.same_bits(got["dx"], full["dx"]), what
+        else:
+            assert got["dx"] is None and not got["has_dx"] and not got["has_dx2"], what
+        assert got["dz"].keys() == full["dz"].keys() == {0, 1} and all(mr.same_bits(got["dz"][l], full["dz"][l]) for l in (0, 1)), what
+
+    for hidden_act, out_act in (("relu", None), ("tanh", "tanh")):
+        kw = dict(hidden_act=hidden_act, out_act=out_act, strided=True)
+        full, other_full = _single(eng, net, **kw), _single(eng, other, **kw)
+        for p in patterns:
+            written_same(_single(eng, dict(net, **p), **kw), full, p, ("single", out_act, p))
+            got = _run_group(eng, [dict(net, **p), other], **kw)
+            written_same(got[0], full, p, ("group", out_act, p))
+            _same(got[1], other_full, ("the other network", out_act, p))
+
+
 # ------------------------------------------------------------------------------------------------- the classes
 def _moved(eng, modules):
     """a DeviceOptimizer step and a Polyak update move the parameters IN PLACE: what the classes hold by reference must follow"""

@@ -1,8 +1,9 @@
 """ptg_mlp_group_forward / ptg_mlp_group_backward without a device: the exported symbols, the refusals the library makes on a NULL handle,
 every Python-level refusal of HipEngine.mlp_group_forward / mlp_group_backward (TypeError across all networks before the ValueError of any,
-the single op's words behind "net i:", nothing touched), the descriptor arrays an accepted call hands the library, and DeviceMLPGroup /
-TrainMLPGroup on CPU modules.  The arithmetic has no test here: a grouped call is defined as the single calls, which tests/test_mlp_group.py
+the single op's words behind "net i:", nothing touched), the descriptor arrays an accepted call hands the library, DeviceMLPGroup /
+TrainMLPGroup on CPU modules, and a group of one against the single op: the same descriptor bytes, the same refusals, the same backward plan.  The arithmetic has no test here: a grouped call is defined as the single calls, which tests/test_mlp_group.py
 compares bit for bit on the device."""
+import ctypes as C
 import os
 
 import pytest
@@ -321,3 +322,116 @@ def test_the_group_classes_parse_refuse_and_order_their_parameters():
     grp(x)
     with pytest.raises(RuntimeError, match="latest forward"):
         y[1].sum().backward()
+
+
+# ------------------------------------------------------------------------------------------------- a group of one is the single call
+def test_a_group_of_one_hands_the_library_the_single_ops_descriptor_byte_for_byte():
+    """B = 17, 41 (40 + a strided one-column x2) -> 233 -> 37 -> 5, tanh / tanh, a strided out, a weight gradient with row stride 48, layer 1
+    frozen, grad_x only, accumulate: the ptg_mlp of mlp_forward and element 0 of mlp_group_forward's array for the same tensors are the
+    same bytes, and so are the ptg_mlp_bwd of mlp_backward and of mlp_group_backward"""
+    import torch
+    from helpers import recording_engine
+    from rl_ptg_amd import _lib
+    eng = recording_engine(4)
+    B, widths = 17, [233, 37, 5]
+    wide = torch.zeros(B, 50)
+    x, x2 = wide[:, :40], wide[:, 45:46]
+    w, b = _net(41, widths)
+    out, work = torch.zeros(B, 8)[:, 1:6], _ws(eng, B, widths)
+    acts = dict(hidden_activation="tanh", out_activation="tanh")
+    eng.mlp_forward(x, w, b, x2=x2, out=out, workspace=work, keep_hidden=True, **acts)
+    eng.mlp_group_forward([x], [w], [b], x2s=[x2], outs=[out], workspaces=[work], keep_hidden=True, **acts)
+    gout = torch.zeros(B, 8)[:, 2:7]
+    gw, gb = [torch.zeros(233, 48)[:, :41], None, torch.zeros(5, 37)], [torch.zeros(233), None, torch.zeros(5)]
+    gx, bws = torch.zeros(B, 44)[:, :40], torch.zeros(eng.mlp_backward_workspace(B, widths), dtype=torch.uint8)
+    eng.mlp_backward(gout, x, w, b, out, work, x2=x2, grad_weights=gw, grad_biases=gb, grad_x=gx, backward_workspace=bws, accumulate=True, **acts)
+    eng.mlp_group_backward([gout], [x], [w], [b], [out], [work], x2s=[x2], grad_weights=[gw], grad_biases=[gb], grad_xs=[gx], backward_workspaces=[bws],
+                           accumulate=True, **acts)
+    calls = eng._L.calls
+    assert [c[0] for c in calls] == ["ptg_mlp_forward", "ptg_mlp_group_forward", "ptg_mlp_backward", "ptg_mlp_group_backward"]
+    for single, group, kind in ((calls[0], calls[1], _lib.PtgMlp), (calls[2], calls[3], _lib.PtgMlpBwd)):
+        one, (arr, G) = single[1][1]._obj, group[1][1:3]
+        assert G == 1 and len(arr) == 1 and isinstance(one, kind) and isinstance(arr[0], kind)
+        assert bytes(one) == bytes(arr[0]) and len(bytes(one)) == C.sizeof(kind)
+    d = calls[3][1][1][0]                                    # and the bytes are not empty ones
+    assert (d.fwd.x2_dev, d.fwd.x2_s_n, d.fwd.out_s_n, d.dw_s_n[0], d.dw_dev[1], d.dx_s_n, d.dx2_dev, d.flags) == (x2.data_ptr(), 50, 8, 48, None, 44, None, _lib.MLP_ACCUMULATE)
+
+
+def test_every_single_op_refusal_in_a_group_of_one_with_its_prefix():
+    """helpers.faulty_mlp_nets, all 37, as network 0 of a group of one: the single op's exception class and its words behind "net 0: ", the
+    forward's against mlp_forward's and the backward's against mlp_backward's"""
+    import torch
+    from helpers import faulty_mlp_nets, host_engine
+    eng = host_engine(4)
+    B = 6
+    nets = faulty_mlp_nets(B)
+    assert len(nets) == 37
+    rest = dict(grad_out=torch.zeros(B, 5), out=torch.zeros(B, 5), workspace=_ws(eng, B, [8, 8, 5]))
+    for k, (exc, kw) in enumerate(nets):
+        acts = {a: kw[a] for a in ("hidden_activation", "out_activation") if a in kw}
+        group = dict(xs=[kw["x"]], x2s=[kw.get("x2")], weights=[kw["weights"]], biases=[kw["biases"]], **acts)
+        with pytest.raises(exc) as single_f:
+            eng.mlp_forward(**kw)
+        with pytest.raises(exc) as single_b:
+            eng.mlp_backward(**kw, **rest)
+        with pytest.raises(exc) as fwd:
+            eng.mlp_group_forward(**group)
+        with pytest.raises(exc) as bwd:
+            eng.mlp_group_backward(grad_outs=[rest["grad_out"]], outs=[rest["out"]], workspaces=[rest["workspace"]], **group)
+        assert type(single_f.value) is exc and type(single_b.value) is exc and type(fwd.value) is exc and type(bwd.value) is exc, k
+        assert str(single_f.value).startswith("mlp_forward: ") and str(single_b.value).startswith("mlp_backward: "), k
+        assert str(fwd.value) == "mlp_group_forward: net 0: " + str(single_f.value)[len("mlp_forward: "):], (k, str(fwd.value))
+        assert str(bwd.value) == "mlp_group_backward: net 0: " + str(single_b.value)[len("mlp_backward: "):], (k, str(bwd.value))
+        assert eng._L is None, k
+
+
+def _fields(d, names):
+    """every field of a ctypes descriptor, nested structures and arrays included; a device pointer found in `names` as its name"""
+    out = {}
+    for name, _ in d._fields_:
+        v = getattr(d, name)
+        out[name] = _fields(v, names) if hasattr(v, "_fields_") else [names.get(e, e) for e in v] if hasattr(v, "__len__") else names.get(v, v)
+    return out
+
+
+@pytest.mark.parametrize("pattern", ["all parameters", "the last layer only", "the input only"])
+def test_a_train_mlp_group_of_one_hands_the_library_what_train_mlp_does(pattern):
+    """one module, 41 (40 + 1) -> 16 -> 12 -> 3, under a TrainMLP and under a TrainMLPGroup of one: the ptg_mlp_bwd of the two backward calls
+    agree in every field, each object's own buffers (out, workspaces, gradient buffers) and autograd's grad_out taken by name"""
+    import torch
+    from torch import nn
+    from helpers import recording_engine
+    torch.manual_seed(0)
+    module = nn.Sequential(nn.Linear(41, 16), nn.Tanh(), nn.Linear(16, 12), nn.Tanh(), nn.Linear(12, 3))
+    params = list(module.parameters())
+    for k, p in enumerate(params):
+        p.requires_grad_(pattern == "all parameters" or (pattern == "the last layer only" and k >= 4))
+    from rl_ptg_amd import TrainMLP, TrainMLPGroup
+    B = 6
+    x, x2 = torch.zeros(B, 40, requires_grad=pattern == "the input only"), torch.zeros(B, 1, requires_grad=pattern == "the input only")
+    seen = []
+    for grouped in (False, True):
+        eng = recording_engine(4)
+        obj = TrainMLPGroup(eng, [module], batch=8) if grouped else TrainMLP(eng, module, batch=8)
+        net = obj.nets[0] if grouped else obj
+        out = obj(x, x2=x2)[0] if grouped else obj(x, x2=x2)
+        out.sum().backward()                                 # an expanded grad_out: both make it contiguous
+        name, args = eng._L.calls[-1]
+        assert name == ("ptg_mlp_group_backward" if grouped else "ptg_mlp_backward") and len(eng._L.calls) == 2
+        d = args[1][0] if grouped else args[1]._obj
+        assert not grouped or args[2] == 1
+        names = {net.out.data_ptr(): "out", net.workspace.data_ptr(): "ws", net.backward_workspace.data_ptr(): "bws", net.grad_input.data_ptr(): "gx",
+                 net.grad_input.data_ptr() + 4 * 40: "gx2", d.gout_dev: "gout"}
+        names.update({t.data_ptr(): f"gw{l}" for l, t in enumerate(net.grad_weights)})
+        names.update({t.data_ptr(): f"gb{l}" for l, t in enumerate(net.grad_biases)})
+        seen.append(_fields(d, names))
+        for p in params:
+            p.grad = None
+        x.grad = x2.grad = None
+    single, group = seen
+    assert single == group
+    want = {"all parameters": ["gw0", "gw1", "gw2"], "the last layer only": [None, None, "gw2"], "the input only": [None, None, None]}[pattern]
+    assert single["dw_dev"][:3] == want and single["db_dev"][:3] == [None if g is None else g.replace("w", "b") for g in want]
+    assert (single["dx_dev"], single["dx2_dev"]) == (("gx", "gx2") if pattern == "the input only" else (None, None))
+    assert single["gout_dev"] == "gout" and single["gout_s_n"] == 3 and single["fwd"]["w_dev"][:3] == [m.weight.data_ptr() for m in module if isinstance(m, nn.Linear)]
+    assert single["fwd"]["out_dev"] == "out" and single["fwd"]["ws_dev"] == "ws" and single["bws_dev"] == "bws"
