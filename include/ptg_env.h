@@ -92,7 +92,9 @@ enum { PTG_OUT_F32 = 0, PTG_OUT_F64 = 1 };                    /* element type of
  * The 26 ('raw': 17) market features of a row are a function of that index alone, so a policy's first layer can be evaluated as
  *   W_env . row[0:14] + G[hour index] (+ G_day[day index]),  G = the market columns of W applied to every window of the series
  * (rl_ptg_amd/policy_split.py): 73 instead of 169 bytes per env-step leave the env kernel, and the first layer multiplies 14
- * instead of 40 inputs.  Replaces: the market sub-spaces of the Dict observation going through CombinedExtractor into the first
+ * instead of 40 inputs.  The project's own networks take the rows as they are: ptg_mlp_forward / ptg_mlp_backward and the group calls
+ * with PTG_MLP_SPLIT_INPUT rebuild the flat row inside the first layer's operand fetch, with the bits of the flat call and no table
+ * (below, and DESIGN.md section 21).  Replaces: the market sub-spaces of the Dict observation going through CombinedExtractor into the first
  * Linear of the reference's MultiInputPolicy (src/rl_config_agent.py:126-149). */
 enum { PTG_OBS_ROW_MAJOR = 0, PTG_OBS_FEATURE_MAJOR = 1, PTG_OBS_SB3_FLAT = 2, PTG_OBS_SPLIT = 3 };
 
@@ -1140,7 +1142,8 @@ int ptg_actor_loss(ptg_env* env, const ptg_al* d, void* stream);
  *   batch         B, 1 <= B <= 2^31
  *   n_layers      n, 1 <= n <= PTG_MLP_MAX_LAYERS (the reference's deepest net is DQN's: 7 hidden layers and the output layer)
  *   flags         PTG_MLP_KEEP_HIDDEN: every post-activation hidden layer stays in ws_dev (below).  PTG_MLP_NARROW / PTG_MLP_WIDE, for
- *                 tests and measurements: every layer takes that tile route instead of the host's choice; both at once are refused
+ *                 tests and measurements: every layer takes that tile route instead of the host's choice; both at once are refused.
+ *                 PTG_MLP_SPLIT_INPUT: x_dev holds PTG_OBS_SPLIT rows (below)
  *   hidden_act    PTG_MLP_RELU | PTG_MLP_TANH, applied after every layer but the last
  *   out_act       PTG_MLP_NONE | PTG_MLP_RELU | PTG_MLP_TANH, applied after the last (TD3's actor ends in tanh; a trunk called on its own
  *                 ends in its hidden activation)
@@ -1177,11 +1180,26 @@ int ptg_actor_loss(ptg_env* env, const ptg_al* d, void* stream);
  * f2 = 0 or f2 > 0 without it; a row stride below its width; an unknown activation code (NONE as hidden_act too); an unknown flag or both
  * route flags; ws_bytes below what ptg_mlp_workspace returns; an out_dev or ws_dev that is not 4-byte aligned.
  * ptg_mlp_workspace(batch, n_layers, widths, flags): bytes of scratch such a call needs, widths = the n_layers layer widths; negative for
- * a NULL widths or a count, width or flag the call would refuse. */
+ * a NULL widths or a count, width or flag the call would refuse.  PTG_MLP_SPLIT_INPUT is accepted and changes no size.
+ * PTG_MLP_SPLIT_INPUT: x_dev is [B][16] float32 PTG_OBS_SPLIT rows, x_s_n >= 16, and the first layer reads the
+ * SB3_FLAT row they stand for.  f1 must be that row's width on this handle, 2 P + 14 for 'mod' and P + 18 for 'raw' (P = price_ahead); the
+ * fan-in stays f1 + f2 and x2_dev works as before.  Column k < f1 of row b is x[b][c] for one of the 14 env columns c, or
+ * series[(int) x[b][14] + q] (a daily series of 'raw': x[b][15]) for column q of a market sub-space, in the column map of ptg_create's
+ * SB3_FLAT rows (rl_ptg_amd/policy_split.py restates it: flat_columns, env_columns) over the float32 series of ptg_market_feature_series.
+ * Those are the words an SB3_FLAT row holds, read in the same ascending k: THE RESULT OF A SPLIT CALL HAS THE BITS OF THE SAME CALL ON THE
+ * REBUILT FLAT ROWS, on either route, single or grouped, forward and backward.  The flag works on any handle, whatever its own obs_layout:
+ * the map depends on raw_modified, price_ahead and the series only.  Beyond the device the call reads the handle's series and its error
+ * words.  An index is device data and never becomes an address unchecked: the hour index is valid when it is an integer in
+ * [0, C_h - P], the day index ('raw' only; 'mod' never reads it) when it is an integer in [0, C_d - 2], C_h and C_d the counts
+ * ptg_market_feature_series reports; negative, past the end, fractional, NaN and Inf are invalid.  For an invalid index the load is
+ * clamped into the series, the row's market columns read as NaN -- so the row's outputs are NaN; every other row keeps its bits -- and the
+ * next ptg_sync (or any call that reports kernel-flagged errors) returns PTG_E_INDEX once.  Further PTG_E_INVALID: f1 not the handle's
+ * flat width; x_s_n < 16; market series shorter than one window or longer than 2^24 (indices would not be exact in float32). */
 #define PTG_MLP_MAX_LAYERS 10
 #define PTG_MLP_MAX_WIDTH 1024
 enum { PTG_MLP_RELU = 0, PTG_MLP_TANH = 1, PTG_MLP_NONE = 2 };
 enum { PTG_MLP_KEEP_HIDDEN = 1, PTG_MLP_NARROW = 2, PTG_MLP_WIDE = 4 };
+enum { PTG_MLP_SPLIT_INPUT = 16 };      /* 8 is PTG_MLP_ACCUMULATE, of ptg_mlp_bwd.flags */
 typedef struct ptg_mlp {
     int64_t batch;
     int32_t n_layers, flags;
@@ -1247,7 +1265,10 @@ int ptg_mlp_forward(ptg_env* env, const ptg_mlp* d, void* stream);
  * below the fan-in; dx_s_n below f1; dx2_dev with f2 = 0 or dx2_s_n below f2; an unknown flag; NULL or misaligned bws_dev; bws_bytes
  * below what ptg_mlp_backward_workspace returns.
  * ptg_mlp_backward_workspace(batch, n_layers, widths, flags): 8 * batch * P(widest width) bytes; negative for a NULL widths or a count,
- * width or flag the call would refuse. */
+ * width or flag the call would refuse (flags: the backward's own, so PTG_MLP_SPLIT_INPUT, a flag of fwd, is refused here).
+ * With PTG_MLP_SPLIT_INPUT in fwd.flags the weight and bias gradients of the first layer read the rebuilt flat row as the forward does
+ * (an invalid index: NaN in that row's products, PTG_E_INDEX); dx_dev must be NULL -- an observation has no gradient -- and a non-NULL
+ * one is PTG_E_INVALID; dx2_dev works as before.  The backward's own flags know no PTG_MLP_SPLIT_INPUT. */
 enum { PTG_MLP_ACCUMULATE = 8 };
 typedef struct ptg_mlp_bwd {
     ptg_mlp fwd;
@@ -1280,7 +1301,7 @@ int ptg_mlp_backward(ptg_env* env, const ptg_mlp_bwd* d, void* stream);
  *                 Workspace sizes are ptg_mlp_workspace and ptg_mlp_backward_workspace, per network.
  *   sharing       networks may share what is only read: x_dev, x2_dev, even weights.  Every out_dev, ws_dev, gradient and bws_dev of
  *                 every network must be distinct from every other and from anything the call reads; overlap is NOT checked.
- *   must agree    batch, n_layers, hidden_act, out_act and flags of all networks; in the backward its own flags (PTG_MLP_ACCUMULATE) too.
+ *   must agree    batch, n_layers, hidden_act, out_act and flags (PTG_MLP_SPLIT_INPUT among them) of all networks; in the backward its own flags (PTG_MLP_ACCUMULATE) too.
  *   routes        a group always runs the 16 x 16 route: PTG_MLP_WIDE in any descriptor is refused, PTG_MLP_NARROW is accepted and means
  *                 nothing.  A single network at a large batch (B >= 4 096 with layers wider than 512) belongs to ptg_mlp_forward and its
  *                 128 x 128 route.

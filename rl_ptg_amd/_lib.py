@@ -39,6 +39,7 @@ AL_ENTROPY, AL_LOG_ALPHA, AL_ENT_COEF = 1, 2, 4
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 10, 1024
 MLP_RELU, MLP_TANH, MLP_NONE = 0, 1, 2
 MLP_KEEP_HIDDEN, MLP_NARROW, MLP_WIDE = 1, 2, 4
+MLP_SPLIT_INPUT = 16                                      # ptg_mlp.flags: x holds split observation rows
 MLP_ACCUMULATE = 8
 MLP_GROUP_MAX = 8
 

@@ -2362,7 +2362,9 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
         return set_err(h, PTG_E_INDEX, "ptg_minibatch / ptg_replay_sample: a sample index outside [0, n_steps * n_envs) (of the replay buffer: "
                        "[0, size * n_envs), or a draw from an empty buffer) was passed (NumPy raises IndexError); "
                        "its output row and column entries were left untouched -- or ptg_policy_loss met an action outside [0, n_actions): "
-                       "that row's gradients were left untouched and the statistics are NaN");
+                       "that row's gradients were left untouched and the statistics are NaN -- or a PTG_MLP_SPLIT_INPUT call of ptg_mlp_forward / "
+                       "ptg_mlp_backward (or of their group calls) met a split row whose hour or day index is no integer inside the market series: "
+                       "that row's market columns were read as NaN");
     }
     if (__atomic_load_n(&e[5], __ATOMIC_RELAXED)) {
         __atomic_exchange_n(&e[5], 0, __ATOMIC_RELAXED);

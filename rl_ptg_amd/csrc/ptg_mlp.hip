@@ -2,7 +2,8 @@
 // restates it) and, in the second half of the file, its backward pass (ptg_mlp_backward; tests/mlp_backward_restatement.py).
 // The forward: one launch per layer: Linear + bias + activation fused, on gfx950's exact-float32 MFMA (v_mfma_f32_16x16x4_f32 and
 // v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, one rounding per product).  The translation unit shares ptg_handle.h with ptg_env.hip
-// and ptg_train.hip and reads nothing of the handle but its device.
+// and ptg_train.hip and reads nothing of the handle but its device -- and, for a PTG_MLP_SPLIT_INPUT call, its
+// config's raw_modified and price_ahead, its float32 market series and P.err.
 //
 // D = A * B + C with A = the rows of the input (A[i][k] = x[row0 + i][k]), B = the weights transposed (B[k][j] = W[col0 + j][k]) and
 // C = the bias broadcast down its column.  Lane maps (one f32 VGPR per operand per lane):
@@ -31,7 +32,9 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -71,6 +74,82 @@ __device__ __forceinline__ float mlp_w(const MlpLayer& a, int u, int k, bool ins
 {
     const float v = a.w[(size_t)min(u, a.O - 1) * a.w_s + (size_t)min(k, a.K - 1)];
     return inside ? v : 0.0f;
+}
+
+// ---- split observation rows as the first layer's input (include/ptg_env.h, PTG_MLP_SPLIT_INPUT) --------------------
+// The first piece is [B][16] split rows, and layer 0 reads the SB3_FLAT row they stand for: column k < F1 is one of the row's 14 env
+// columns, or series[(int) row[14 | 15] + q] of a market sub-space.  A lane's column is fixed over its rows, so the source is resolved
+// once per lane and chunk (mlp_split_col) and a row costs one load of the row's column and one of the series (mlp_split_x).  Both are
+// branch-free, as mlp_x is: the index is clamped into the series before it becomes an address, whatever the row holds; a lane on an env
+// column or on the second piece reads series word 0 and discards it.  An index that is no integer in [0, last] makes the row's market
+// columns NaN and raises err[4] (PTG_E_INDEX at the next ptg_sync): one store per lane behind the reduction.
+// Only the split instantiations carry an MlpSplit; the flat ones are given the empty MlpFlat and compile to what they were.
+struct MlpFlat {};
+struct MlpSplit {                        // by value in the launch: a captured call holds no host memory
+    const float* pool;                   // the handle's float32 series, one allocation (ptg_handle.h: d_pool32)
+    int off[3];                          // market sub-space m of the flat row: column k0 + q = pool[off[m] + index + q], 0 <= q < len
+    unsigned seg[3];                     // k0 | len << 16 | daily << 31 (len 0: unused); daily: the index is column 15 of a split row, the day, not column 14
+    int last_hour, last_day;             // the last valid indices
+    int* err;                            // DevParams::err
+};
+template <typename S>
+constexpr bool mlp_is_split = std::is_same<S, MlpSplit>::value;
+
+// The 14 env columns keep one order in every flat row, whatever raw_modified and price_ahead insert between them (the keys sort the same):
+// nibble e is the split column of the e-th flat column that is no market column (mlp_split_args checks it against the sorted map)
+constexpr unsigned long long MLP_SPLIT_ENV_ORDER = 0xCD654321097AB8ull;
+
+struct MlpSplitCol {                     // where a lane's column comes from
+    const float* p; size_t ps;           // row b's word: p[b * ps]: the env column, the index column or the second piece's column
+    const float* sp; int last;           // market: the series moved on by q, and the last valid index
+    unsigned nan;                        // market: the bits of a quiet NaN, else 0
+};
+
+// k inside [0, K); A: MlpLayer or MlpDw.  The sub-spaces are visited by template argument, not by a loop counter
+template <typename A, int... M>
+__device__ __forceinline__ MlpSplitCol mlp_split_col(const A& a, const MlpSplit& s, int k, std::integer_sequence<int, M...>)
+{
+    int e = k, c = 0, last = s.last_hour;                    // e: k less the market columns below it
+    const float* sp = s.pool;
+    bool market = false;
+    auto sub = [&](int off, unsigned seg) {
+        const int k0 = seg & 0xffff, len = (seg >> 16) & 0x7fff;
+        const bool daily = seg >> 31, in = k >= k0 && k < k0 + len;
+        sp = in ? s.pool + (off + k - k0) : sp;
+        last = in ? (daily ? s.last_day : s.last_hour) : last;
+        c = in ? (daily ? 15 : 14) : c;
+        market = market || in;
+        e -= k >= k0 + len ? len : 0;
+    };
+    (sub(s.off[M], s.seg[M]), ...);
+    c = market ? c : (int)(MLP_SPLIT_ENV_ORDER >> (4 * min(max(e, 0), 13))) & 15;
+    // The pieces are read BEFORE the choice between them.  Read inside its arms, the choice becomes a choice between two addresses
+    // inside the fetch's closure, and the closure, the MlpSplit with it, then stays in scratch (544 bytes in k_mlp_layer_split)
+    const float *const x = a.x, *const x2 = a.x2;
+    const size_t x_s = a.x_s, x2_s = a.x2_s;
+    const int F1 = a.F1;                 // the market sub-spaces end below it
+    const bool second = k >= F1;
+    return MlpSplitCol{second ? x2 + (size_t)(k - F1) : x + (size_t)c, second ? x2_s : x_s, sp, last, market ? 0x7fc00000u : 0u};
+}
+
+template <typename A>
+__device__ __forceinline__ MlpSplitCol mlp_split_col(const A& a, const MlpSplit& s, int k)
+{
+    return mlp_split_col(a, s, k, std::make_integer_sequence<int, 3>{});
+}
+
+// row inside [0, B).  i is an address only after the clamp; (float) i == f holds for an integer in [0, last] and for nothing else
+// (NaN, Inf, a fraction, a negative value, one past the end), last < 2^24 (mlp_desc_fault).  The verdict is kept as bits to OR into
+// the series word -- any word with them is a NaN, a word without them itself -- and not as a lane mask: a mask per row in flight, beside
+// the edge masks, is what the 128 x 128 route has no scalar registers for (63 spilled)
+__device__ __forceinline__ float mlp_split_x(const MlpSplitCol& c, size_t row, unsigned& bad)
+{
+    const float f = c.p[row * c.ps];
+    const int i = min((int)(f >= 0.0f ? fminf(f, 2.0e9f) : 0.0f), c.last);
+    const unsigned poison = (float)i == f ? 0u : c.nan;
+    bad |= poison;
+    const float v = c.sp[i];
+    return c.nan ? __uint_as_float(__float_as_uint(v) | poison) : f;
 }
 
 template <int ACT>
@@ -125,8 +204,8 @@ __device__ __forceinline__ void mlp_chain16(const float* as, const float* bs, IA
 }
 
 // The NARROW tile (bx, by) of a layer: the body of k_mlp_layer<ACT, MLP_NARROW> and of k_mlp_layer_group<ACT>, which picks `a` out of its group
-template <int ACT>
-__device__ __forceinline__ void mlp_layer_tile16(const MlpLayer a, unsigned bx, unsigned by)
+template <int ACT, typename S>
+__device__ __forceinline__ void mlp_layer_tile16(const MlpLayer a, const S s, unsigned bx, unsigned by)
 {
     __shared__ float xs[NR_TILE * NR_PITCH], ws[NR_TILE * NR_PITCH];
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
@@ -149,6 +228,25 @@ __device__ __forceinline__ void mlp_layer_tile16(const MlpLayer a, unsigned bx, 
             wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
         }
     };
+    // the split fetch: the source of column k once per chunk
+    [[maybe_unused]] unsigned bad = 0;                   // this lane met an invalid index
+    [[maybe_unused]] auto fetch_split = [=, &xr, &wr, &bad](int d, int k0) {
+        (void)xr, (void)wr, (void)bad;
+        if constexpr (mlp_is_split<S>) {      // the flat instantiations give this body nothing to compile
+            const int k = k0 + kx;
+            const bool kin = k < a.K;
+            const MlpSplitCol src = mlp_split_col(a, s, min(k, a.K - 1));
+#pragma unroll
+            for (int i = 0; i < PER; i++) {
+                const int rr = r2 + 2 * i;
+                const size_t row = row0 + rr;
+                const int u = col0 + rr;
+                const float v = mlp_split_x(src, min(row, a.B - 1), bad);
+                xr[d][i] = kin ? v : 0.0f;                   // a row beyond B repeats row B - 1 and is never stored: no mask per row (mlp_split_x)
+                wr[d][i] = mlp_w(a, u, k, kin);                 // nor per unit: a unit beyond O repeats unit O - 1 and is never stored
+            }
+        }
+    };
     auto stage = [=, &xr, &wr](int d) {
 #pragma unroll
         for (int i = 0; i < PER; i++) {
@@ -157,7 +255,12 @@ __device__ __forceinline__ void mlp_layer_tile16(const MlpLayer a, unsigned bx, 
         }
     };
     auto at = [=](int s) { return r * NR_PITCH + 4 * s + q; };
-    mlp_ring<NR_DEPTH, NR_KC>(a.K, fetch, stage, [=, &acc] { mlp_chain16(xs, ws, at, at, acc); });
+    if constexpr (mlp_is_split<S>) {
+        mlp_ring<NR_DEPTH, NR_KC>(a.K, fetch_split, stage, [=, &acc] { mlp_chain16(xs, ws, at, at, acc); });
+        if (bad) s.err[4] = 1;
+    } else {
+        mlp_ring<NR_DEPTH, NR_KC>(a.K, fetch, stage, [=, &acc] { mlp_chain16(xs, ws, at, at, acc); });
+    }
     const int u = col0 + r;
     if (u < a.O) {
 #pragma unroll
@@ -168,77 +271,112 @@ __device__ __forceinline__ void mlp_layer_tile16(const MlpLayer a, unsigned bx, 
     }
 }
 
-template <int ACT, int ROUTE>
-__global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(const MlpLayer a)
+// The WIDE tile of a layer: the body of k_mlp_layer<ACT, MLP_WIDE> and of its split twin
+template <int ACT, typename S>
+__device__ __forceinline__ void mlp_layer_tile128(const MlpLayer a, const S s)
 {
-    if constexpr (ROUTE == MLP_NARROW) {
-        mlp_layer_tile16<ACT>(a, blockIdx.x, blockIdx.y);
-    } else {
-        __shared__ float xs[WD_TILE * WD_PITCH], ws[WD_TILE * WD_PITCH];
-        const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr_ = wave >> 1, wc = wave & 1, c = lane & 31, hf = lane >> 5;
-        const size_t row0 = (size_t)blockIdx.x * WD_TILE;
-        const int col0 = blockIdx.y * WD_TILE;
-        const bool live = row0 + (size_t)(wr_ * 64) < a.B && col0 + wc * 64 < a.O;      // wave-uniform: a quadrant wholly outside computes nothing
-        f32x16 acc[2][2];
+    __shared__ float xs[WD_TILE * WD_PITCH], ws[WD_TILE * WD_PITCH];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr_ = wave >> 1, wc = wave & 1, c = lane & 31, hf = lane >> 5;
+    const size_t row0 = (size_t)blockIdx.x * WD_TILE;
+    const int col0 = blockIdx.y * WD_TILE;
+    const bool live = row0 + (size_t)(wr_ * 64) < a.B && col0 + wc * 64 < a.O;      // wave-uniform: a quadrant wholly outside computes nothing
+    f32x16 acc[2][2];
 #pragma unroll
-        for (int n = 0; n < 2; n++) {
-            const int u = col0 + wc * 64 + n * 32 + c;
-            const float bj = u < a.O ? a.bias[u] : 0.0f;
+    for (int n = 0; n < 2; n++) {
+        const int u = col0 + wc * 64 + n * 32 + c;
+        const float bj = u < a.O ? a.bias[u] : 0.0f;
 #pragma unroll
-            for (int m = 0; m < 2; m++)
+        for (int m = 0; m < 2; m++)
 #pragma unroll
-                for (int g = 0; g < 16; g++) acc[m][n][g] = bj;
+            for (int g = 0; g < 16; g++) acc[m][n][g] = bj;
+    }
+    constexpr int PER = WD_TILE * WD_KC / 256;           // 16 rows and 16 units per thread and chunk
+    float xr[WD_DEPTH][PER], wr[WD_DEPTH][PER];
+    const int kx = t & 31, r8 = t >> 5;
+    auto fetch = [=, &xr, &wr](int d, int k0) {
+        const int k = k0 + kx;
+        const bool kin = k < a.K;
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            const int rr = r8 + 8 * i;
+            const size_t row = row0 + rr;
+            const int u = col0 + rr;
+            xr[d][i] = mlp_x(a, row, k, kin && row < a.B);
+            wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
         }
-        constexpr int PER = WD_TILE * WD_KC / 256;           // 16 rows and 16 units per thread and chunk
-        float xr[WD_DEPTH][PER], wr[WD_DEPTH][PER];
-        const int kx = t & 31, r8 = t >> 5;
-        auto fetch = [=, &xr, &wr](int d, int k0) {
+    };
+    [[maybe_unused]] unsigned bad = 0;
+    [[maybe_unused]] auto fetch_split = [=, &xr, &wr, &bad](int d, int k0) {
+        (void)xr, (void)wr, (void)bad;
+        if constexpr (mlp_is_split<S>) {      // the flat instantiations give this body nothing to compile
             const int k = k0 + kx;
             const bool kin = k < a.K;
+            const MlpSplitCol src = mlp_split_col(a, s, min(k, a.K - 1));
 #pragma unroll
             for (int i = 0; i < PER; i++) {
                 const int rr = r8 + 8 * i;
                 const size_t row = row0 + rr;
                 const int u = col0 + rr;
-                xr[d][i] = mlp_x(a, row, k, kin && row < a.B);
-                wr[d][i] = mlp_w(a, u, k, kin && u < a.O);
-            }
-        };
-        auto stage = [=, &xr, &wr](int d) {
-#pragma unroll
-            for (int i = 0; i < PER; i++) {
-                xs[(r8 + 8 * i) * WD_PITCH + kx] = xr[d][i];
-                ws[(r8 + 8 * i) * WD_PITCH + kx] = wr[d][i];
-            }
-        };
-        auto mma = [=, &acc] {
-            if (!live) return;
-#pragma unroll
-            for (int s = 0; s < WD_KC / 2; s++) {            // two ascending k per instruction; unrolled, so the LDS reads run ahead of the MFMAs
-                const float a0 = xs[(wr_ * 64 + c) * WD_PITCH + 2 * s + hf], a1 = xs[(wr_ * 64 + 32 + c) * WD_PITCH + 2 * s + hf];
-                const float b0 = ws[(wc * 64 + c) * WD_PITCH + 2 * s + hf], b1 = ws[(wc * 64 + 32 + c) * WD_PITCH + 2 * s + hf];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
-        };
-        mlp_ring<WD_DEPTH, WD_KC>(a.K, fetch, stage, mma);
-        if (live) {
-#pragma unroll
-            for (int n = 0; n < 2; n++) {
-                const int u = col0 + wc * 64 + n * 32 + c;
-                if (u >= a.O) continue;
-#pragma unroll
-                for (int m = 0; m < 2; m++)
-#pragma unroll
-                    for (int g = 0; g < 16; g++) {
-                        const size_t row = row0 + (size_t)(wr_ * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * hf);
-                        if (row < a.B) a.y[row * a.y_s + (size_t)u] = mlp_act<ACT>(acc[m][n][g]);
-                    }
+                const float v = mlp_split_x(src, min(row, a.B - 1), bad);
+                xr[d][i] = kin ? v : 0.0f;                   // a row beyond B repeats row B - 1 and is never stored: no mask per row (mlp_split_x)
+                wr[d][i] = mlp_w(a, u, k, kin);                 // nor per unit: a unit beyond O repeats unit O - 1 and is never stored
             }
         }
+    };
+    auto stage = [=, &xr, &wr](int d) {
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            xs[(r8 + 8 * i) * WD_PITCH + kx] = xr[d][i];
+            ws[(r8 + 8 * i) * WD_PITCH + kx] = wr[d][i];
+        }
+    };
+    auto mma = [=, &acc] {
+        if (!live) return;
+#pragma unroll
+        for (int p = 0; p < WD_KC / 2; p++) {            // two ascending k per instruction; unrolled, so the LDS reads run ahead of the MFMAs
+            const float a0 = xs[(wr_ * 64 + c) * WD_PITCH + 2 * p + hf], a1 = xs[(wr_ * 64 + 32 + c) * WD_PITCH + 2 * p + hf];
+            const float b0 = ws[(wc * 64 + c) * WD_PITCH + 2 * p + hf], b1 = ws[(wc * 64 + 32 + c) * WD_PITCH + 2 * p + hf];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    };
+    if constexpr (mlp_is_split<S>) {
+        mlp_ring<WD_DEPTH, WD_KC>(a.K, fetch_split, stage, mma);
+        if (bad) s.err[4] = 1;
+    } else {
+        mlp_ring<WD_DEPTH, WD_KC>(a.K, fetch, stage, mma);
     }
+    if (live) {
+#pragma unroll
+        for (int n = 0; n < 2; n++) {
+            const int u = col0 + wc * 64 + n * 32 + c;
+            if (u >= a.O) continue;
+#pragma unroll
+            for (int m = 0; m < 2; m++)
+#pragma unroll
+                for (int g = 0; g < 16; g++) {
+                    const size_t row = row0 + (size_t)(wr_ * 64 + m * 32 + (g & 3) + 8 * (g >> 2) + 4 * hf);
+                    if (row < a.B) a.y[row * a.y_s + (size_t)u] = mlp_act<ACT>(acc[m][n][g]);
+                }
+        }
+    }
+}
+
+template <int ACT, int ROUTE>
+__global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer(const MlpLayer a)
+{
+    if constexpr (ROUTE == MLP_NARROW) mlp_layer_tile16<ACT>(a, MlpFlat{}, blockIdx.x, blockIdx.y);
+    else mlp_layer_tile128<ACT>(a, MlpFlat{});
+}
+
+// layer 0 of a PTG_MLP_SPLIT_INPUT call
+template <int ACT, int ROUTE>
+__global__ __launch_bounds__(ROUTE == MLP_NARROW ? 64 : 256) void k_mlp_layer_split(const MlpLayer a, const MlpSplit s)
+{
+    if constexpr (ROUTE == MLP_NARROW) mlp_layer_tile16<ACT>(a, s, blockIdx.x, blockIdx.y);
+    else mlp_layer_tile128<ACT>(a, s);
 }
 
 // a runtime activation as a template argument: f(std::integral_constant<int, ACT>)
@@ -266,7 +404,15 @@ __global__ __launch_bounds__(64) void k_mlp_layer_group(const MlpGroup<MlpLayer>
 {
     const MlpLayer& a = g.net[blockIdx.z];
     if ((size_t)blockIdx.x * NR_TILE >= a.B || (int)blockIdx.y * NR_TILE >= a.O) return;
-    mlp_layer_tile16<ACT>(a, blockIdx.x, blockIdx.y);
+    mlp_layer_tile16<ACT>(a, MlpFlat{}, blockIdx.x, blockIdx.y);
+}
+
+template <int ACT>
+__global__ __launch_bounds__(64) void k_mlp_layer_group_split(const MlpGroup<MlpLayer> g, const MlpSplit s)      // one map: the networks share the handle
+{
+    const MlpLayer& a = g.net[blockIdx.z];
+    if ((size_t)blockIdx.x * NR_TILE >= a.B || (int)blockIdx.y * NR_TILE >= a.O) return;
+    mlp_layer_tile16<ACT>(a, s, blockIdx.x, blockIdx.y);
 }
 
 // The grid of a launch: the component-wise maximum over the networks that take part, blockIdx.z the network.  own(i) is the grid network i
@@ -326,18 +472,61 @@ __attribute__((format(printf, 3, 4))) bool mlp_fault(char* why, size_t cap, cons
     return true;
 }
 
+constexpr int MLP_FWD_FLAGS = PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE | PTG_MLP_SPLIT_INPUT;
+
+// The SB3_FLAT row of handle h as a split call rebuilds it: ptg_create's column map (sub-spaces by sorted key, METH_STATUS one-hot over
+// six columns; rl_ptg_amd/policy_split.py restates it as flat_columns / env_columns) over the handle's float32 series.  Returns the row's
+// width, 2 P + 14 for 'mod' and P + 18 for 'raw' (-1: the sorted map does not have the env columns in the kernels' order); s may be null
+int mlp_split_args(const ptg_env* h, MlpSplit* s)
+{
+    struct Sub { const char* key; int width, split_col, which; };      // split_col: first column of a split row (env); which: the series (market)
+    const int P = h->cfg.price_ahead;
+    std::vector<Sub> subs;
+    if (h->cfg.raw_modified) { subs.push_back({"Pot_Reward", P, -1, 0}); subs.push_back({"Part_Full", P, -1, 1}); }
+    else { subs.push_back({"Elec_Price", P, -1, 0}); subs.push_back({"Gas_Price", 2, -1, 2}); subs.push_back({"EUA_Price", 2, -1, 3}); }
+    const char* tail[9] = {"METH_STATUS", "T_CAT", "H2_in_MolarFlow", "CH4_syn_MolarFlow", "H2_res_MolarFlow", "H2O_DE_MassFlow", "Elec_Heating", "Temp_hour_enc_sin",
+                           "Temp_hour_enc_cos"};
+    for (int q = 0; q < 9; q++) subs.push_back({tail[q], q ? 1 : 6, q ? 5 + q : 0, -1});
+    std::sort(subs.begin(), subs.end(), [](const Sub& a, const Sub& b) { return strcmp(a.key, b.key) < 0; });      // Python's sorted() of ASCII keys
+    const float* series[4] = {h->P.featA32, h->P.featB32, h->P.gas_n32, h->P.eua_n32};      // all inside d_pool32, featA32 its first word
+    int k = 0, m = 0, e = 0;
+    bool ordered = true;                 // the env columns come in MLP_SPLIT_ENV_ORDER
+    if (s) {
+        *s = MlpSplit{};
+        s->pool = h->d_pool32; s->last_hour = h->n_sets * h->P.n_hours - P; s->last_day = h->n_sets * h->P.n_days - 2; s->err = h->P.err;
+    }
+    for (const Sub& sb : subs) {
+        if (sb.which >= 0) {
+            if (s) { s->off[m] = (int)(series[sb.which] - h->d_pool32); s->seg[m] = (unsigned)k | (unsigned)sb.width << 16 | (sb.which >= 2 ? 1u << 31 : 0u); }
+            m++;
+        } else {
+            for (int j = 0; j < sb.width; j++, e++) ordered = ordered && (int)((MLP_SPLIT_ENV_ORDER >> (4 * e)) & 15) == sb.split_col + j;
+        }
+        k += sb.width;
+    }
+    return ordered && e == 14 ? k : -1;
+}
+
 // what ptg_mlp_forward refuses in a descriptor, for it and for the backward's embedded one: false when d is well-formed, else the text in why
-bool mlp_desc_fault(const ptg_mlp* d, char* why, size_t cap)
+bool mlp_desc_fault(const ptg_env* h, const ptg_mlp* d, char* why, size_t cap)
 {
     if (d->batch < 1 || d->batch > (int64_t)1 << 31) return mlp_fault(why, cap, "batch %lld outside [1, 2^31]", (long long)d->batch);
     if (d->n_layers < 1 || d->n_layers > PTG_MLP_MAX_LAYERS) return mlp_fault(why, cap, "n_layers %d outside [1, %d]", d->n_layers, PTG_MLP_MAX_LAYERS);
-    if (d->flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) return mlp_fault(why, cap, "unknown flag in %d", d->flags);
+    if (d->flags & ~MLP_FWD_FLAGS) return mlp_fault(why, cap, "unknown flag in %d", d->flags);
     if ((d->flags & PTG_MLP_NARROW) && (d->flags & PTG_MLP_WIDE)) return mlp_fault(why, cap, "PTG_MLP_NARROW and PTG_MLP_WIDE exclude each other");
     if (d->hidden_act != PTG_MLP_RELU && d->hidden_act != PTG_MLP_TANH) return mlp_fault(why, cap, "hidden_act must be PTG_MLP_RELU or PTG_MLP_TANH");
     if (d->out_act != PTG_MLP_NONE && d->out_act != PTG_MLP_RELU && d->out_act != PTG_MLP_TANH) return mlp_fault(why, cap, "unknown out_act %d", d->out_act);
     if (d->f1 < 1 || d->f2 < 0 || (int64_t)d->f1 + d->f2 > PTG_MLP_MAX_WIDTH)
         return mlp_fault(why, cap, "f1 = %d, f2 = %d: need f1 >= 1, f2 >= 0, f1 + f2 <= %d", d->f1, d->f2, PTG_MLP_MAX_WIDTH);
-    if (!d->x_dev || d->x_s_n < d->f1) return mlp_fault(why, cap, "x_dev is null or x_s_n below f1 = %d", d->f1);
+    if (d->flags & PTG_MLP_SPLIT_INPUT) {
+        const int flat = mlp_split_args(h, nullptr);
+        if (d->f1 != flat) return mlp_fault(why, cap, "PTG_MLP_SPLIT_INPUT: f1 = %d, the handle's flat row has %d columns", d->f1, flat);
+        if (!d->x_dev) return mlp_fault(why, cap, "x_dev is null");
+        if (d->x_s_n < 16) return mlp_fault(why, cap, "PTG_MLP_SPLIT_INPUT: x_s_n = %lld below the 16 columns of a split row", (long long)d->x_s_n);
+        const int64_t hours = (int64_t)h->n_sets * h->P.n_hours, days = (int64_t)h->n_sets * h->P.n_days;
+        if (hours < h->cfg.price_ahead || days < 2 || hours > (int64_t)1 << 24 || days > (int64_t)1 << 24)
+            return mlp_fault(why, cap, "PTG_MLP_SPLIT_INPUT: %lld hours and %lld days of market series: shorter than one window, or indices not exact in float32", (long long)hours, (long long)days);
+    } else if (!d->x_dev || d->x_s_n < d->f1) return mlp_fault(why, cap, "x_dev is null or x_s_n below f1 = %d", d->f1);
     if ((d->x2_dev != nullptr) != (d->f2 > 0)) return mlp_fault(why, cap, "x2_dev and f2 > 0 go together");
     if (d->x2_dev && d->x2_s_n < d->f2) return mlp_fault(why, cap, "x2_s_n below f2 = %d", d->f2);
     const int n = d->n_layers;
@@ -429,11 +618,13 @@ int mlp_refuse(ptg_env* h, const char* who, const D* nets, int n_nets, bool grou
 int mlp_forward_walk(ptg_env* h, const char* who, const ptg_mlp* nets, int n_nets, bool grouped, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (int rc = mlp_refuse(h, who, nets, n_nets, grouped, mlp_desc_fault)) return rc;
+    if (int rc = mlp_refuse(h, who, nets, n_nets, grouped, [h](const ptg_mlp* d, char* why, size_t cap) { return mlp_desc_fault(h, d, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
     const ptg_mlp* d = &nets[0];         // depth, activations, batch and flags: the group's
     const int n = d->n_layers;
+    MlpSplit s{};                        // PTG_MLP_SPLIT_INPUT: layer 0 of every network rebuilds its flat row
+    if (d->flags & PTG_MLP_SPLIT_INPUT) mlp_split_args(h, &s);
     MlpGroup<MlpLayer> g{};
     for (int i = 0; i < n_nets; i++) g.net[i] = mlp_first_input(&nets[i]);
     for (int l = 0; l < n; l++) {
@@ -443,7 +634,11 @@ int mlp_forward_walk(ptg_env* h, const char* who, const ptg_mlp* nets, int n_net
         const dim3 grid = mlp_grid(n_nets, [&](int i) { return mlp_layer_grid(g.net[i], wide ? WD_TILE : NR_TILE); });
         mlp_with_act(l == n - 1 ? d->out_act : d->hidden_act, [&](auto A) {
             constexpr int ACT = decltype(A)::value;
-            if (grouped) k_mlp_layer_group<ACT><<<grid, 64, 0, st>>>(g);
+            if (l == 0 && (d->flags & PTG_MLP_SPLIT_INPUT)) {
+                if (grouped) k_mlp_layer_group_split<ACT><<<grid, 64, 0, st>>>(g, s);
+                else if (wide) k_mlp_layer_split<ACT, MLP_WIDE><<<grid, 256, 0, st>>>(a, s);
+                else k_mlp_layer_split<ACT, MLP_NARROW><<<grid, 64, 0, st>>>(a, s);
+            } else if (grouped) k_mlp_layer_group<ACT><<<grid, 64, 0, st>>>(g);
             else if (wide) k_mlp_layer<ACT, MLP_WIDE><<<grid, 256, 0, st>>>(a);
             else k_mlp_layer<ACT, MLP_NARROW><<<grid, 64, 0, st>>>(a);
         });
@@ -460,7 +655,7 @@ extern "C" {
 int64_t ptg_mlp_workspace(int64_t batch, int32_t n_layers, const int32_t* widths, int32_t flags)
 {
     const MlpLayout lay{batch, n_layers, widths};
-    if (!lay.in_range() || (flags & ~(PTG_MLP_KEEP_HIDDEN | PTG_MLP_NARROW | PTG_MLP_WIDE)) || ((flags & PTG_MLP_NARROW) && (flags & PTG_MLP_WIDE))) return PTG_E_INVALID;
+    if (!lay.in_range() || (flags & ~MLP_FWD_FLAGS) || ((flags & PTG_MLP_NARROW) && (flags & PTG_MLP_WIDE))) return PTG_E_INVALID;      // PTG_MLP_SPLIT_INPUT changes no size
     return lay.forward_bytes(flags);
 }
 
@@ -599,7 +794,8 @@ __global__ __launch_bounds__(64) void k_mlp_dx_group(const MlpGroup<MlpDx> g)
     mlp_dx_tile<ACT_BELOW>(a, blockIdx.x, blockIdx.y);
 }
 
-__device__ __forceinline__ void mlp_dw_tile(const MlpDw a, unsigned bx, unsigned by)
+template <typename S>
+__device__ __forceinline__ void mlp_dw_tile(const MlpDw a, const S s, unsigned bx, unsigned by)
 {
     __shared__ float zs[BW_RC * BW_PITCH_T], xs[BW_RC * BW_PITCH_T];
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
@@ -619,6 +815,9 @@ __device__ __forceinline__ void mlp_dw_tile(const MlpDw a, unsigned bx, unsigned
     const bool one = ko == a.K;
     const float* xp = kc < a.F1 ? a.x + (size_t)kc : a.x2 + (size_t)(kc - a.F1);
     const size_t xps = kc < a.F1 ? a.x_s : a.x2_s;
+    [[maybe_unused]] MlpSplitCol src{};                      // split: the lane's column is one over all its rows
+    [[maybe_unused]] unsigned bad = 0;
+    if constexpr (mlp_is_split<S>) src = mlp_split_col(a, s, kc);
     // captures by reference, against mlp_ring's rule: by value the compiler moves the address products into the loop (72 registers
     // instead of 120, 3 - 4 % more time at B = 257 .. 658, profiles/mlp_ring_ab.txt); its prologue is short either way
     auto fetch = [&](int d, size_t b0) {                     // lane: unit jz and column ko of every fourth row
@@ -628,7 +827,9 @@ __device__ __forceinline__ void mlp_dw_tile(const MlpDw a, unsigned bx, unsigned
             const bool rin = row < a.B;
             const float z = a.dz[rc * a.dz_s + (size_t)jzc];
             zr[d][i] = rin && jz < a.O ? z : 0.0f;
-            const float x = xp[rc * xps];
+            float x;
+            if constexpr (mlp_is_split<S>) x = mlp_split_x(src, rc, bad);
+            else x = xp[rc * xps];
             xr[d][i] = rin && ko <= a.K ? (one ? 1.0f : x) : 0.0f;
         }
     };
@@ -641,6 +842,8 @@ __device__ __forceinline__ void mlp_dw_tile(const MlpDw a, unsigned bx, unsigned
     };
     auto at = [&](int s) { return (4 * s + q) * BW_PITCH_T + r; };      // A transposed out of LDS: row of the stage = reduction index
     mlp_ring<DEPTH, BW_RC>(a.B, fetch, stage, [&] { mlp_chain16(zs, xs, at, at, acc); });
+    if constexpr (mlp_is_split<S>)
+        if (bad) s.err[4] = 1;
     if (ko <= a.K) {
 #pragma unroll
         for (int g = 0; g < 4; g++) {
@@ -654,7 +857,13 @@ __device__ __forceinline__ void mlp_dw_tile(const MlpDw a, unsigned bx, unsigned
 
 __global__ __launch_bounds__(64) void k_mlp_dw(const MlpDw a)
 {
-    mlp_dw_tile(a, blockIdx.x, blockIdx.y);
+    mlp_dw_tile(a, MlpFlat{}, blockIdx.x, blockIdx.y);
+}
+
+// layer 0 of a PTG_MLP_SPLIT_INPUT call: x is the split rows, the operand the flat row they stand for
+__global__ __launch_bounds__(64) void k_mlp_dw_split(const MlpDw a, const MlpSplit s)
+{
+    mlp_dw_tile(a, s, blockIdx.x, blockIdx.y);
 }
 
 __global__ __launch_bounds__(64) void k_mlp_dw_group(const MlpGroup<MlpDw> g)
@@ -662,7 +871,15 @@ __global__ __launch_bounds__(64) void k_mlp_dw_group(const MlpGroup<MlpDw> g)
     const MlpDw& a = g.net[blockIdx.z];
     if (!a.dw) return;                                       // this network freezes the layer
     if ((int)blockIdx.x * BW_TILE >= a.O || (int)blockIdx.y * BW_TILE > a.K) return;      // column K is the bias gradient
-    mlp_dw_tile(a, blockIdx.x, blockIdx.y);
+    mlp_dw_tile(a, MlpFlat{}, blockIdx.x, blockIdx.y);
+}
+
+__global__ __launch_bounds__(64) void k_mlp_dw_group_split(const MlpGroup<MlpDw> g, const MlpSplit s)
+{
+    const MlpDw& a = g.net[blockIdx.z];
+    if (!a.dw) return;
+    if ((int)blockIdx.x * BW_TILE >= a.O || (int)blockIdx.y * BW_TILE > a.K) return;
+    mlp_dw_tile(a, s, blockIdx.x, blockIdx.y);
 }
 
 template <int ACT>
@@ -688,11 +905,11 @@ __global__ __launch_bounds__(256) void k_mlp_dz_out_group(const MlpGroup<MlpDzOu
 }
 
 // what ptg_mlp_backward refuses in a descriptor: false when d is well-formed, else the text in why
-bool mlp_bwd_fault(const ptg_mlp_bwd* d, char* why, size_t cap)
+bool mlp_bwd_fault(const ptg_env* h, const ptg_mlp_bwd* d, char* why, size_t cap)
 {
     const ptg_mlp* f = &d->fwd;
-    char fwd[160];
-    if (mlp_desc_fault(f, fwd, sizeof fwd)) return mlp_fault(why, cap, "the forward's descriptor: %s", fwd);
+    char fwd[200];
+    if (mlp_desc_fault(h, f, fwd, sizeof fwd)) return mlp_fault(why, cap, "the forward's descriptor: %s", fwd);
     if (!(f->flags & PTG_MLP_KEEP_HIDDEN)) return mlp_fault(why, cap, "the forward's descriptor must carry PTG_MLP_KEEP_HIDDEN");
     if (d->flags & ~PTG_MLP_ACCUMULATE) return mlp_fault(why, cap, "unknown flag in %d", d->flags);
     const int n = f->n_layers;
@@ -703,6 +920,7 @@ bool mlp_bwd_fault(const ptg_mlp_bwd* d, char* why, size_t cap)
         if (d->dw_dev[l] && d->dw_s_n[l] < fan_in) return mlp_fault(why, cap, "dw_s_n[%d] below the fan-in %d", l, fan_in);
         fan_in = f->width[l];
     }
+    if (d->dx_dev && (f->flags & PTG_MLP_SPLIT_INPUT)) return mlp_fault(why, cap, "dx_dev with PTG_MLP_SPLIT_INPUT: an observation has no gradient");
     if (d->dx_dev && d->dx_s_n < f->f1) return mlp_fault(why, cap, "dx_s_n below f1 = %d", f->f1);
     if (d->dx2_dev && f->f2 == 0) return mlp_fault(why, cap, "dx2_dev without a second input piece");
     if (d->dx2_dev && d->dx2_s_n < f->f2) return mlp_fault(why, cap, "dx2_s_n below f2 = %d", f->f2);
@@ -779,11 +997,13 @@ dim3 mlp_dx_grid(const MlpDx& a)
 int mlp_backward_walk(ptg_env* h, const char* who, const ptg_mlp_bwd* nets, int n_nets, bool grouped, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (int rc = mlp_refuse(h, who, nets, n_nets, grouped, mlp_bwd_fault)) return rc;
+    if (int rc = mlp_refuse(h, who, nets, n_nets, grouped, [h](const ptg_mlp_bwd* d, char* why, size_t cap) { return mlp_bwd_fault(h, d, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
     const ptg_mlp* f = &nets[0].fwd;     // depth and activations: the group's
     const int n = f->n_layers;
+    MlpSplit s{};
+    if (f->flags & PTG_MLP_SPLIT_INPUT) mlp_split_args(h, &s);
     MlpBwdWalk w[PTG_MLP_GROUP_MAX];
     for (int i = 0; i < n_nets; i++) w[i] = MlpBwdWalk{&nets[i]};
     if (f->out_act != PTG_MLP_NONE) {
@@ -807,7 +1027,10 @@ int mlp_backward_walk(ptg_env* h, const char* who, const ptg_mlp_bwd* nets, int 
             MlpGroup<MlpDw> g{};
             for (int i = 0; i < n_nets; i++) g.net[i] = w[i].dw(l);
             const dim3 grid = mlp_grid(n_nets, [&](int i) { return g.net[i].dw ? mlp_dw_grid(g.net[i]) : dim3(); });
-            if (grouped) k_mlp_dw_group<<<grid, 64, 0, st>>>(g);
+            if (l == 0 && (f->flags & PTG_MLP_SPLIT_INPUT)) {
+                if (grouped) k_mlp_dw_group_split<<<grid, 64, 0, st>>>(g, s);
+                else k_mlp_dw_split<<<grid, 64, 0, st>>>(g.net[0], s);
+            } else if (grouped) k_mlp_dw_group<<<grid, 64, 0, st>>>(g);
             else k_mlp_dw<<<grid, 64, 0, st>>>(g.net[0]);
             if (int rc = launch_check(h, grouped ? "k_mlp_dw_group" : "k_mlp_dw")) return rc;
         }

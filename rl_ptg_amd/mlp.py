@@ -11,8 +11,15 @@ The parameters are held BY REFERENCE, never copied: what DeviceOptimizer.step() 
 and the next replay of a captured call, reads.  Output and workspace are allocated once, for `batch` rows; a call with fewer rows
 returns the first rows of the output tensor, and every call overwrites it.
 
-Not supported: obs_layout="split" rows (policy_split.FirstLayerSplit) as input -- feed row-major observations; float64 nets; a Linear
-without bias; anything but Linear / ReLU / Tanh in the sequence.  There is no torch fall-back.
+obs="split" (all four classes): x is the [B, 16] rows of an engine with obs_layout="split", and the first Linear -- built for the flat
+row, 2 P + 14 ('raw': P + 18) input columns plus those of x2 -- reads the flat row they stand for, rebuilt from the engine's market
+series while it loads (include/ptg_env.h: PTG_MLP_SPLIT_INPUT).  Outputs and gradients have the bits of the
+obs="flat" call on policy_split.flat_rows_from_split(x); nothing is rebuilt after a weight update.
+
+    policy = DeviceMLP(engine, q_net, batch=engine.n, obs="split");  logits = policy(engine.obs)
+
+Not supported: float64 nets (a float64 engine's split rows too); a Linear without bias; anything but Linear / ReLU / Tanh in the
+sequence.  There is no torch fall-back.
 
 Cost (profiles/mlp_cost.txt; DESIGN.md section 18 has the table and its one condition, which is MISSED at 7 of its 12 shapes).  Device time
 against the same nn.Sequential under torch.no_grad(): faster for the deep, narrow nets at the reference's batch sizes (DQN's 7 x 366 at B = 6
@@ -76,11 +83,14 @@ class _NetBuffers:
     """What DeviceMLP and TrainMLP share: the parsed net, held by reference and checked to be contiguous and on the engine's device, and
     the output and the forward's workspace for `batch` rows.  The messages carry the subclass's name."""
 
-    def __init__(self, engine, modules, batch, hidden=False):
+    def __init__(self, engine, modules, batch, hidden=False, obs="flat"):
         """engine: the HipEngine whose device and library serve the calls; modules: see parse_mlp; batch: the most rows a call takes;
         hidden: keep the post-activation hidden layers of the last call in `self.hidden` (views into the workspace: what a backward
-        pass would read)."""
+        pass would read); obs: "flat", or "split" for split observation rows as x (the module's docstring)."""
         who = type(self).__name__
+        if obs not in ("flat", "split"):
+            raise ValueError(f"{who}: obs must be 'flat' or 'split', got {obs!r}")
+        self.split = obs == "split"
         self.engine = engine
         self.linears, self.hidden_activation, self.out_activation = parse_mlp(modules)
         for l, m in enumerate(self.linears):
@@ -118,23 +128,23 @@ class DeviceMLP(_NetBuffers):
         the next call overwrites.  Reads the parameters where they are now."""
         B = self._rows(x)
         res = self.engine.mlp_forward(x, *self.params(), hidden_activation=self.hidden_activation, out_activation=self.out_activation, x2=x2,
-                                      out=None if B is None else self.out[:B], workspace=self.workspace, keep_hidden=self.keep_hidden)
+                                      out=None if B is None else self.out[:B], workspace=self.workspace, keep_hidden=self.keep_hidden, split=self.split)
         self.hidden = res.hidden
         return res.out
 
 
 def _backward_plan(net, x, x2, grad_out, need_x, need_x2, need_params):
     """One network's share of a backward call, for both autograd functions.  net: a TrainMLP; x, x2: what its forward saved; need_x, need_x2,
-    need_params (w0, b0, w1, b1, ...): its entries of needs_input_grad.  Returns grad_out with rows the op accepts, grad_weights and grad_biases
+    need_params (w0, b0, w1, b1, ...): its entries of needs_input_grad.  A split net has no grad_x, and its grad_input holds the x2 part alone.  Returns grad_out with rows the op accepts, grad_weights and grad_biases
     (None for a layer that needs neither; both None when no layer does), grad_x and grad_x2 (views into net.grad_input, or None) and grads, the network's entries of what backward() returns."""
-    B, F1 = x.shape
+    B, F1 = x.shape[0], (0 if net.split else x.shape[1])
     if grad_out.stride(1) != 1 or (B > 1 and grad_out.stride(0) < grad_out.shape[1]):
         grad_out = grad_out.contiguous()                     # e.g. the expanded gradient of a sum
     n = len(net.linears)
     wanted = [need_params[2 * l] or need_params[2 * l + 1] for l in range(n)]
     gw = [net.grad_weights[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
     gb = [net.grad_biases[l] if wanted[l] else None for l in range(n)] if any(wanted) else None
-    gx = net.grad_input[:B, :F1] if need_x else None
+    gx = net.grad_input[:B, :F1] if need_x and not net.split else None
     gx2 = net.grad_input[:B, F1:] if x2 is not None and need_x2 else None
     grads = []
     for l in range(n):
@@ -151,7 +161,7 @@ class _TrainMLPFunction(torch.autograd.Function):
         xd, x2d = (x.detach() if torch.is_tensor(x) else x), (x2.detach() if torch.is_tensor(x2) else x2)
         res = net.engine.mlp_forward(xd, [p.detach() for p in params[0::2]], [p.detach() for p in params[1::2]], hidden_activation=net.hidden_activation,
                                      out_activation=net.out_activation, x2=x2d, out=None if B is None else net.out[:B], workspace=net.workspace,
-                                     keep_hidden=True)
+                                     keep_hidden=True, split=net.split)
         net.calls += 1
         net.hidden = res.hidden
         ctx.net, ctx.call, ctx.x, ctx.x2 = net, net.calls, xd, x2d
@@ -169,7 +179,7 @@ class _TrainMLPFunction(torch.autograd.Function):
         net._views = (gx, gx2)                               # held here too, so that autograd copies them into a leaf's .grad and never adopts them
         net.engine.mlp_backward(grad_out, x, *net.params(), net.out[:x.shape[0]], net.workspace, hidden_activation=net.hidden_activation,
                                 out_activation=net.out_activation, x2=x2, grad_weights=gw, grad_biases=gb, grad_x=gx, grad_x2=gx2,
-                                backward_workspace=net.backward_workspace)
+                                backward_workspace=net.backward_workspace, split=net.split)
         return (None, gx, gx2, *grads)
 
 
@@ -188,8 +198,9 @@ class TrainMLP(_NetBuffers):
     copy).  The tensors backward() returns to autograd are the module's own gradient buffers; autograd copies them into `.grad` (or adds
     them to it), so `.grad` stays valid when the buffers are reused.  Parameters with requires_grad False launch no weight-gradient kernel
     and keep `.grad` None; an input that needs no gradient gets no first-layer input-gradient launch.
-    Not supported: float64 nets, a Linear without bias, anything but Linear / ReLU / Tanh, split observation rows as input.  There is no
-    torch fall-back.
+    obs="split": x is split observation rows (the module's docstring); their gradient is None, whatever x.requires_grad says, and
+    grad_input holds the x2 part alone.
+    Not supported: float64 nets, a Linear without bias, anything but Linear / ReLU / Tanh.  There is no torch fall-back.
     Cost (profiles/mlp_backward_cost.txt; DESIGN.md section 19 has the table and its one condition -- forward + backward not above the same
     nn.Sequential's under autograd at each agent's own batch size -- which is MISSED at 5 of its 6 shapes): torch's device time of forward +
     backward over this route's (below 1: slower than torch), TrainMLP / the two raw library calls into preallocated .grad tensors: DQN 7 x 366 at B = 544 0.75x / 0.98x, A2C
@@ -198,13 +209,18 @@ class TrainMLP(_NetBuffers):
     over the raw calls (70 - 230 us: the autograd function, two sets of argument checks, autograd's copies into .grad) is most of the
     miss; a captured gradient step calls mlp_forward and mlp_backward directly.  What the route gives at every shape is the fixed order."""
 
-    def __init__(self, engine, modules, batch):
-        super().__init__(engine, modules, batch, hidden=True)
+    def __init__(self, engine, modules, batch, obs="flat"):
+        super().__init__(engine, modules, batch, hidden=True, obs=obs)
+        if self.split:
+            from .policy_split import flat_columns
+            flat = flat_columns("mod" if engine.consts["raw_modified"] else "raw", int(engine.consts["price_ahead"]))[1]
+            if self.in_features < flat:
+                raise ValueError(f"TrainMLP: the first Linear takes {self.in_features} features, the flat observation alone has {flat}")
         nback = engine.mlp_backward_workspace(self.batch, self.widths)
         dev = engine.device
         with engine._torch.cuda.device(dev):
             self.backward_workspace = torch.empty(nback, dtype=torch.uint8, device=dev)
-            self.grad_input = torch.empty((self.batch, self.in_features), dtype=torch.float32, device=dev)
+            self.grad_input = torch.empty((self.batch, self.in_features - (flat if self.split else 0)), dtype=torch.float32, device=dev)
             self.grad_weights = [torch.empty_like(m.weight, requires_grad=False) for m in self.linears]
             self.grad_biases = [torch.empty_like(m.bias, requires_grad=False) for m in self.linears]
         self._views = None
@@ -219,7 +235,7 @@ class TrainMLP(_NetBuffers):
         return _TrainMLPFunction.apply(self, x, x2, *self.parameters())
 
 
-def _group_members(who, kind, engine, nets, batch):
+def _group_members(who, kind, engine, nets, batch, obs="flat"):
     """one `kind` (DeviceMLP or TrainMLP) per entry of nets, once the group is 1 to MLP_GROUP_MAX networks of equal depth and activations"""
     if not isinstance(nets, (list, tuple)):
         raise TypeError(f"{who}: nets must be a list with what DeviceMLP takes for each network, got {type(nets).__name__}")
@@ -233,7 +249,7 @@ def _group_members(who, kind, engine, nets, batch):
             raise ValueError(f"{who}: nets 0 and {i} disagree in the hidden activation: {parsed[0][1]} and {hidden}")
         if out != parsed[0][2]:
             raise ValueError(f"{who}: nets 0 and {i} disagree in the output activation: {parsed[0][2]} and {out}")
-    return [kind(engine, m, batch) for m in nets]
+    return [kind(engine, m, batch, obs=obs) for m in nets]
 
 
 def _group_inputs(who, members, x, x2):
@@ -270,9 +286,10 @@ class DeviceMLPGroup:
     that, not the grouped kernels; the figures above are from the run in which the first place rotates.  A grouped call makes the checks of all its networks before its first launch; on an idle stream
     that host time (70 - 180 us) is not hidden, which was not measured."""
 
-    def __init__(self, engine, nets, batch):
+    def __init__(self, engine, nets, batch, obs="flat"):
+        """obs: "flat", or "split" for split observation rows as every network's x (the module's docstring)"""
         self.engine = engine
-        self.nets = _group_members("DeviceMLPGroup", DeviceMLP, engine, nets, batch)
+        self.nets = _group_members("DeviceMLPGroup", DeviceMLP, engine, nets, batch, obs)
         self.batch = int(batch)
 
     def __call__(self, x, x2=None):
@@ -281,7 +298,8 @@ class DeviceMLPGroup:
         m0 = self.nets[0]
         weights, biases = zip(*[net.params() for net in self.nets])
         res = self.engine.mlp_group_forward(xs, list(weights), list(biases), hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
-                                            outs=[None if B is None else net.out[:B] for net, B in zip(self.nets, Bs)], workspaces=[net.workspace for net in self.nets])
+                                            outs=[None if B is None else net.out[:B] for net, B in zip(self.nets, Bs)], workspaces=[net.workspace for net in self.nets],
+                                            split=m0.split)
         return tuple(r.out for r in res)
 
 
@@ -304,7 +322,7 @@ class _TrainMLPGroupFunction(torch.autograd.Function):
         m0 = grp.nets[0]
         res = grp.engine.mlp_group_forward(xs, weights, biases, hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
                                            outs=[None if B is None else net.out[:B] for net, B in zip(grp.nets, Bs)],
-                                           workspaces=[net.workspace for net in grp.nets], keep_hidden=True)
+                                           workspaces=[net.workspace for net in grp.nets], keep_hidden=True, split=m0.split)
         grp.calls += 1
         for net, r in zip(grp.nets, res):
             net.hidden = r.hidden
@@ -339,7 +357,7 @@ class _TrainMLPGroupFunction(torch.autograd.Function):
             m0 = grp.nets[0]
             g, xs, weights, biases, outs, works, x2s, gws, gbs, dxs, dx2s, bws = (list(col) for col in zip(*rows))
             grp.engine.mlp_group_backward(g, xs, weights, biases, outs, works, hidden_activation=m0.hidden_activation, out_activation=m0.out_activation, x2s=x2s,
-                                          grad_weights=gws, grad_biases=gbs, grad_xs=dxs, grad_x2s=dx2s, backward_workspaces=bws)
+                                          grad_weights=gws, grad_biases=gbs, grad_xs=dxs, grad_x2s=dx2s, backward_workspaces=bws, split=m0.split)
         return (None, *gxs, *gx2s, *grads)
 
 
@@ -371,9 +389,10 @@ class TrainMLPGroup:
     110 - 290 us more than the raw grouped calls (the autograd function, a second set of argument checks, autograd's copies into
     .grad); a captured gradient step calls mlp_group_forward and mlp_group_backward directly."""
 
-    def __init__(self, engine, nets, batch):
+    def __init__(self, engine, nets, batch, obs="flat"):
+        """obs: "flat", or "split" for split observation rows as every network's x (TrainMLP's rules: no gradient of x)"""
         self.engine = engine
-        self.nets = _group_members("TrainMLPGroup", TrainMLP, engine, nets, batch)
+        self.nets = _group_members("TrainMLPGroup", TrainMLP, engine, nets, batch, obs)
         self.batch = int(batch)
         self._views = None
         self.calls = 0

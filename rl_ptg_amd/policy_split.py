@@ -76,7 +76,10 @@ class FirstLayerSplit:
     """y = W x + b of a first layer with weight W [H, 40 | 31] (flat column order; 2 P + 14 | P + 18 columns at price_ahead P),
     evaluated from split rows.
 
-    prepare(W, b) builds the projection tables (call after every weight update); __call__(rows) -> [..., H]."""
+    prepare(W, b) builds the projection tables (call after every weight update); __call__(rows) -> [..., H].
+
+    The project's own networks need none of this: DeviceMLP, TrainMLP and their groups with obs="split" (rl_ptg_amd/mlp.py; HipEngine.
+    mlp_forward(..., split=True)) read split rows directly, with the bits of the flat call, a backward pass and no table to rebuild."""
 
     def __init__(self, series, raw_modified="mod", device=None, price_ahead=13):
         import torch

@@ -3,7 +3,7 @@ action heads, the policy loss, the TD losses, TQC's quantile loss, the training-
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward and mlp_backward); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
-_action_kind; torch stays lazily imported (torch = self._torch).
+_action_kind, and for split=True of the MLP ops self.consts (raw_modified, price_ahead); torch stays lazily imported (torch = self._torch).
 
 Every tensor argument goes through ONE checker, check(), which raises in a fixed order: TypeError for what the value is (not a
 tensor, a refused dtype, element size or element count), then ValueError for its shape, its strides, its device.  Nothing touches
@@ -1168,11 +1168,13 @@ class TrainOps:
                 check(self, who, name, t, dtypes=f32)
 
     def _mlp_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, route=None, first=(), grad_weights=None, grad_biases=None,
-                 typed=False):
+                 typed=False, split=False):
         """The checks of a net that mlp_forward and mlp_backward share, in their one order: TypeError for what every value is (`first`:
         the (name, tensor) pairs the caller puts before x; typed: the caller has run _mlp_types already), then ValueError for the names,
-        the counts, x, x2 and layer by layer the weights, the biases and, where given, the gradients.  Returns B, F1, F2, the widths and
-        fill(out, workspace, flags), which makes the call's ptg_mlp."""
+        the counts, x, x2 and layer by layer the weights, the biases and, where given, the gradients.  split: x is [B, 16] split
+        observation rows and F1 the width of the flat row they stand for on this engine (policy_split.flat_columns), which the first
+        weight's fan-in must match.  Returns B, F1, F2, the widths and fill(out, workspace, flags), which makes the call's ptg_mlp
+        (split: with MLP_SPLIT_INPUT among its flags)."""
         torch = self._torch
         f32 = (torch.float32,)
         acts = {"relu": _lib.MLP_RELU, "tanh": _lib.MLP_TANH, None: _lib.MLP_NONE}
@@ -1189,8 +1191,11 @@ class TrainOps:
             raise ValueError(f"{who}: 1 to {_lib.MLP_MAX_LAYERS} layers with one bias each, got {n} weights and {len(biases)} biases")
         if grad_weights is not None and (len(grad_weights) != n or len(grad_biases) != n):
             raise ValueError(f"{who}: grad_weights and grad_biases must have {n} entries, got {len(grad_weights)} and {len(grad_biases)}")
-        check(self, who, "x", x, dtypes=f32, shape=(None, None), rule=rows)
+        check(self, who, "x", x, dtypes=f32, shape=(None, 16 if split else None), rule=rows)
         B, F1 = x.shape
+        if split:
+            from .policy_split import flat_columns
+            F1 = flat_columns("mod" if self.consts["raw_modified"] else "raw", int(self.consts["price_ahead"]))[1]
         check(self, who, "x2", x2, dtypes=f32, shape=(B, None), rule=rows, optional=True)
         F2 = 0 if x2 is None else x2.shape[1]
         if B < 1 or F1 < 1 or (x2 is not None and F2 < 1):
@@ -1213,7 +1218,7 @@ class TrainOps:
             raise ValueError(f"{who}: the output width is {fan_in}, outside [1, {_lib.MLP_MAX_WIDTH}]")
 
         def fill(out, workspace, flags):
-            d = _lib.PtgMlp(batch=B, n_layers=n, flags=flags, hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
+            d = _lib.PtgMlp(batch=B, n_layers=n, flags=flags | (_lib.MLP_SPLIT_INPUT if split else 0), hidden_act=acts[hidden_activation], out_act=acts[out_activation], f1=F1, f2=F2,
                             x_dev=_ptr(x), x_s_n=_row_stride(x), x2_dev=_ptr(x2), x2_s_n=0 if x2 is None else _row_stride(x2), out_dev=_ptr(out),
                             out_s_n=_row_stride(out), ws_dev=_ptr(workspace), ws_bytes=workspace.numel())
             for l in range(n):
@@ -1222,10 +1227,11 @@ class TrainOps:
 
         return B, F1, F2, widths, fill
 
-    def _mlp_forward_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, keep_hidden, route=None, typed=False):
+    def _mlp_forward_net(self, who, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, keep_hidden, route=None, typed=False,
+                         split=False):
         """Every check of ONE network's forward, for mlp_forward (who "mlp_forward") and for mlp_group_forward (who "mlp_group_forward: net i",
         typed): _mlp_net, then out, then the workspace.  Returns B, the widths, the workspace's bytes and _mlp_net's fill."""
-        B, _, _, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, route=route, typed=typed)
+        B, _, _, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, route=route, typed=typed, split=split)
         check(self, who, "out", out, dtypes=(self._torch.float32,), shape=(B, widths[-1]), rule=rows, optional=True, exc=ValueError)
         need = self.mlp_workspace(B, widths, keep_hidden)
         if workspace is not None:
@@ -1233,15 +1239,17 @@ class TrainOps:
         return B, widths, need, fill
 
     def _mlp_backward_net(self, who, grad_out, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, grad_weights, grad_biases, grad_x, grad_x2,
-                          backward_workspace, typed=False):
+                          backward_workspace, typed=False, split=False):
         """Every check of ONE network's backward, for mlp_backward and for mlp_group_backward as _mlp_forward_net is for the forwards.
         Returns B, the widths, the backward workspace's bytes, _mlp_net's fill and the tensors the network writes."""
         f32 = (self._torch.float32,)
         B, F1, F2, widths, fill = self._mlp_net(who, x, x2, weights, biases, hidden_activation, out_activation, first=[("grad_out", grad_out)],
-                                                grad_weights=grad_weights, grad_biases=grad_biases, typed=typed)
+                                                grad_weights=grad_weights, grad_biases=grad_biases, typed=typed, split=split)
         check(self, who, "grad_out", grad_out, dtypes=f32, shape=(B, widths[-1]), rule=rows)
         check(self, who, "out", out, dtypes=f32, shape=(B, widths[-1]), rule=rows, exc=ValueError)
         _workspace_arg(self, who, f"workspace (mlp_workspace({B}, {widths}, True))", workspace, self.mlp_workspace(B, widths, True), "the forward with keep_hidden needs")
+        if split and grad_x is not None:
+            raise ValueError(f"{who}: grad_x with split=True: an observation has no gradient")
         check(self, who, "grad_x", grad_x, dtypes=f32, shape=(B, F1), rule=rows, optional=True, exc=ValueError)
         if grad_x2 is not None and x2 is None:
             raise ValueError(f"{who}: grad_x2 without x2")
@@ -1253,7 +1261,7 @@ class TrainOps:
         return B, widths, need, fill, written
 
     def mlp_forward(self, x, weights, biases, hidden_activation="relu", out_activation=None, x2=None, out=None, workspace=None, keep_hidden=False,
-                    _route=None):
+                    _route=None, split=False):
         """Enqueue, on the current stream, the forward pass of an MLP without autograd: one fused launch per layer (include/ptg_env.h:
         ptg_mlp_forward, which states the arithmetic -- per unit a float32 fmaf chain from the bias over ascending k, then the activation).
         x [B, F1] float32 with unit column stride and a row stride >= F1 (a column slice of a wider tensor fits); x2 [B, F2] likewise, or
@@ -1264,8 +1272,14 @@ class TrainOps:
         of at least mlp_workspace(B, widths, keep_hidden) bytes, 4-byte aligned, allocated when None.  keep_hidden: the post-activation
         hidden layers stay in the workspace and are returned as views into it.  Returns MlpOut(out, hidden): hidden a tuple of n - 1
         [B, width_l] views, or None.  No synchronisation and, with out= and workspace=, no allocation; a -0 result may come out as +0.
-        `_route` ("narrow" | "wide") forces one tile route in every layer: for tests and measurements, the bits do not depend on it."""
-        net = self._mlp_forward_net("mlp_forward", x, x2, weights, biases, hidden_activation, out_activation, out, workspace, keep_hidden, route=_route)
+        `_route` ("narrow" | "wide") forces one tile route in every layer: for tests and measurements, the bits do not depend on it.
+        split: x is [B, 16] split observation rows (obs_layout="split"; row stride >= 16) and the first layer reads the flat row they
+        stand for, rebuilt from the engine's market series while it loads (include/ptg_env.h: PTG_MLP_SPLIT_INPUT; DESIGN.md section
+        21): weights[0] has the flat row's width (policy_split.flat_columns of the engine's raw_modified and price_ahead) plus F2 input
+        columns, and the result has the bits of the same call on policy_split.flat_rows_from_split(x).  A row whose hour or day index
+        is no integer inside the series gives NaN outputs, and the next sync() raises PTG_E_INDEX."""
+        net = self._mlp_forward_net("mlp_forward", x, x2, weights, biases, hidden_activation, out_activation, out, workspace, keep_hidden, route=_route,
+                                    split=split)
         flags = (_lib.MLP_KEEP_HIDDEN if keep_hidden else 0) | {None: 0, "narrow": _lib.MLP_NARROW, "wide": _lib.MLP_WIDE}[_route]
         d, res, workspace = _mlp_fwd_desc(self, net, out, workspace, keep_hidden, flags)
         self._call("ptg_mlp_forward", C.byref(d))
@@ -1279,7 +1293,7 @@ class TrainOps:
         return 8 * batch * max(_pitch(w) for w in widths)
 
     def mlp_backward(self, grad_out, x, weights, biases, out, workspace, hidden_activation="relu", out_activation=None, x2=None, grad_weights=None,
-                     grad_biases=None, grad_x=None, grad_x2=None, backward_workspace=None, accumulate=False):
+                     grad_biases=None, grad_x=None, grad_x2=None, backward_workspace=None, accumulate=False, split=False):
         """Enqueue, on the current stream, the backward pass of the MLP whose forward was mlp_forward(x, weights, biases, ..., out=out,
         workspace=workspace, keep_hidden=True) with the same arguments (include/ptg_env.h: ptg_mlp_backward, which states the arithmetic:
         float32 fmaf chains, dx over ascending units, dW and db over ascending rows).  grad_out [B, O] float32, unit column stride, a row
@@ -1289,9 +1303,10 @@ class TrainOps:
         first layer's input gradient is not computed.  backward_workspace: contiguous uint8, >= mlp_backward_workspace(B, widths) bytes,
         4-byte aligned, allocated when None.  accumulate: the parameter gradients are added to in place, continuing each element's chain
         over the rows.  Nothing but backward_workspace is allocated; no synchronisation.  Returns the backward workspace (dz of layers 0
-        and 1 stay in it: include/ptg_env.h has the layout)."""
+        and 1 stay in it: include/ptg_env.h has the layout).  split: as in the forward, which must have had it too; the first layer's
+        weight and bias gradients read the rebuilt flat row, and grad_x must be None: an observation has no gradient."""
         net = self._mlp_backward_net("mlp_backward", grad_out, x, x2, weights, biases, hidden_activation, out_activation, out, workspace, grad_weights, grad_biases,
-                                     grad_x, grad_x2, backward_workspace)
+                                     grad_x, grad_x2, backward_workspace, split=split)
         _no_tensor_twice("mlp_backward", net[4], "grad_weights, grad_biases, grad_x, grad_x2 and backward_workspace")
         d, backward_workspace = _mlp_bwd_desc(self, net, grad_out, out, workspace, grad_weights, grad_biases, grad_x, grad_x2, backward_workspace, accumulate)
         self._call("ptg_mlp_backward", C.byref(d))
@@ -1317,14 +1332,16 @@ class TrainOps:
             if len(net[1]) != len(nets[0][1]):
                 raise ValueError(f"{who}: nets 0 and {i} disagree in depth: {len(nets[0][1])} and {len(net[1])} layers")
 
-    def mlp_group_forward(self, xs, weights, biases, hidden_activation="relu", out_activation=None, x2s=None, outs=None, workspaces=None, keep_hidden=False):
+    def mlp_group_forward(self, xs, weights, biases, hidden_activation="relu", out_activation=None, x2s=None, outs=None, workspaces=None, keep_hidden=False,
+                          split=False):
         """mlp_forward for G networks, 1 <= G <= 8, of equal depth, activations and batch in ONE launch per layer (include/ptg_env.h:
         ptg_mlp_group_forward): twin critics, critics and their targets, a policy and a value net.  Every network's result is, bit for
         bit, what mlp_forward gives for its arguments.  xs: a list of G tensors [B, F1_i], or one tensor that every network reads;
         weights / biases: lists of G lists as mlp_forward takes them (widths may differ, the depth may not); x2s, outs, workspaces: None,
         or lists of G entries in which None stands where mlp_forward allows None.  Networks may share inputs and even weights; no tensor
         may serve two of the outs and workspaces.  The arguments are checked as mlp_forward checks them: TypeError for what the values
-        of all networks are first, then ValueError network by network, the message behind "net i:".  Returns a list of G MlpOut."""
+        of all networks are first, then ValueError network by network, the message behind "net i:".  split: every network's x holds
+        split observation rows, as in mlp_forward.  Returns a list of G MlpOut."""
         who = "mlp_group_forward"
         G = self._mlp_group(who, weights, biases)
         xs, x2s = _per_net(who, "xs", xs, G, share=True), _per_net(who, "x2s", x2s, G, optional=True)
@@ -1332,7 +1349,7 @@ class TrainOps:
         for i in range(G):
             self._mlp_types(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i])
         nets = [self._mlp_forward_net(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, outs[i], workspaces[i], keep_hidden,
-                                      typed=True) for i in range(G)]
+                                      typed=True, split=split) for i in range(G)]
         self._mlp_group_agree(who, nets)
         _no_tensor_twice(who, [t for t in outs + workspaces if t is not None], "outs and workspaces")
         made = [_mlp_fwd_desc(self, nets[i], outs[i], workspaces[i], keep_hidden, _lib.MLP_KEEP_HIDDEN if keep_hidden else 0) for i in range(G)]
@@ -1340,7 +1357,7 @@ class TrainOps:
         return [m[1] for m in made]
 
     def mlp_group_backward(self, grad_outs, xs, weights, biases, outs, workspaces, hidden_activation="relu", out_activation=None, x2s=None, grad_weights=None,
-                           grad_biases=None, grad_xs=None, grad_x2s=None, backward_workspaces=None, accumulate=False):
+                           grad_biases=None, grad_xs=None, grad_x2s=None, backward_workspaces=None, accumulate=False, split=False):
         """mlp_backward for the G networks of an mlp_group_forward(..., keep_hidden=True) call, in the launches of ONE network's backward
         (include/ptg_env.h: ptg_mlp_group_backward); every network's gradients are, bit for bit, what mlp_backward gives for its
         arguments.  grad_outs, outs, workspaces: lists of G; xs as in the forward; x2s, grad_weights, grad_biases, grad_xs, grad_x2s,
@@ -1349,6 +1366,7 @@ class TrainOps:
         grad_x2s[i] each optional).  A weight-gradient launch is enqueued for a layer when any network wants it, the first layer's
         input-gradient launch when any network wants a grad_x or grad_x2.  The gradient of an input that several networks share is NOT
         summed: each network writes its own grad_xs[i].  No tensor may serve two of the outputs.  Checked as mlp_group_forward checks.
+        split: as in mlp_backward, for every network: every grad_xs[i] must be None.
         Returns the list of backward workspaces."""
         who = "mlp_group_backward"
         G = self._mlp_group(who, weights, biases)
@@ -1361,7 +1379,7 @@ class TrainOps:
             self._mlp_types(f"{who}: net {i}", xs[i], x2s[i], weights[i], biases[i], first=[("grad_out", grad_outs[i])], grad_weights=grad_weights[i],
                             grad_biases=grad_biases[i])
         nets = [self._mlp_backward_net(f"{who}: net {i}", grad_outs[i], xs[i], x2s[i], weights[i], biases[i], hidden_activation, out_activation, outs[i], workspaces[i],
-                                       grad_weights[i], grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], typed=True) for i in range(G)]
+                                       grad_weights[i], grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], typed=True, split=split) for i in range(G)]
         self._mlp_group_agree(who, nets)
         _no_tensor_twice(who, [t for net in nets for t in net[4]], "grad_weights, grad_biases, grad_xs, grad_x2s and backward_workspaces")
         made = [_mlp_bwd_desc(self, nets[i], grad_outs[i], outs[i], workspaces[i], grad_weights[i], grad_biases[i], grad_xs[i], grad_x2s[i], bws[i], accumulate)

@@ -1,11 +1,13 @@
 """What the SB3-facing observation hand-off buys end to end: a collect loop  obs -> policy -> action -> env step  with a
 policy of the shape the reference trains (SB3 "MultiInputPolicy": CombinedExtractor's 40 columns -> 64 -> 64 -> 5 logits, tanh; random
-weights, greedy actions), five ways:
+weights, greedy actions), six ways:
   flat    PTG_OBS_SB3_FLAT rows stay on the device: torch MLP on the [N, 40] tensor the kernel wrote, ptg_step on the action tensor it produced
   graph   the flat loop captured once (policy forward + ptg_step) and replayed as one hipGraph per step (ptg_note_replays afterwards)
   mlp     the graph loop with rl_ptg_amd.DeviceMLP (ptg_mlp_forward: one fused launch per layer) + act_categorical(deterministic=True) in place of
           torch's three Linears, two tanh kernels and the argmax
   split   PTG_OBS_SPLIT rows (16 columns) + policy_split.FirstLayerSplit for the first layer
+  split_mlp   the mlp loop on a PTG_OBS_SPLIT engine: DeviceMLP(obs="split") reads the 16-column rows and rebuilds the flat row inside its
+          first layer's operand fetch (PTG_MLP_SPLIT_INPUT); same graph, same head
   host    the drop-in route of the reference's loop: PtGVecEnv.step(numpy actions) -> dict of NumPy arrays -> flattened on the host ->
           torch.as_tensor(...).cuda() -> policy -> actions.cpu().numpy()   (what SB3's collect_rollouts does around a VecEnv)
 Not product code; the policy is the caller's.  python tools/policy_loop.py [envs] [steps]"""
@@ -119,6 +121,30 @@ def step_split(o):
     return eng.step(a, want_final=False)[0]
 dt = timed(step_split, obs)
 print(f"split  (device-resident, [N, 16] rows + G_hour):   {dt * 1e6:8.1f} us per vector step = {n / dt:.3e} env-steps/s", flush=True)
+eng.close()
+
+# --- the mlp loop on split rows: the env kernel writes 16 columns, the first layer's fetch rebuilds the other 26 from the series
+eng = engine("split")
+obs_static = eng.reset()
+policy = DeviceMLP(eng, torch.nn.Sequential(l1, torch.nn.Tanh(), l2, torch.nn.Tanh(), l3), batch=n, obs="split")
+head = eng.act_categorical(policy(obs_static), None, deterministic=True, want_logp=False, want_entropy=False)
+def body_split_mlp():
+    eng.act_categorical(policy(obs_static), None, deterministic=True, want_logp=False, want_entropy=False, out=head)
+    eng.step(head.actions, want_final=False)
+for _ in range(3):
+    body_split_mlp()
+side = torch.cuda.Stream()
+side.wait_stream(torch.cuda.current_stream())
+g3 = torch.cuda.CUDAGraph()
+with torch.cuda.stream(side):
+    with torch.cuda.graph(g3, stream=side):
+        body_split_mlp()
+torch.cuda.current_stream().wait_stream(side)
+dt = timed(lambda o: g3.replay(), None)
+eng.note_replays(50 + K - 1)
+eng.sync()                                                   # raises if a replay met an invalid index
+assert eng.steps_to_episode_end() == int(spec.consts["eps_sim_steps"]) - 5 - (3 + 50 + K)
+print(f"split_mlp (graph loop, [N, 16] rows, DeviceMLP(obs=split)): {dt * 1e6:6.1f} us per vector step = {n / dt:.3e} env-steps/s", flush=True)
 eng.close()
 
 # --- the VecEnv route (NumPy dict observations over PCIe, as SB3's loop sees them)
