@@ -48,7 +48,8 @@ extern "C" {
                              *     gradients); + ptg_mlp, ptg_mlp_forward, ptg_mlp_workspace (the inference forward of the policy and target MLPs,
                              *     one fused f32 MFMA launch per layer); + ptg_mlp_bwd, ptg_mlp_backward, ptg_mlp_backward_workspace (the backward pass
                              *     of those MLPs, two f32 MFMA launches per layer); + PTG_MLP_GROUP_MAX, ptg_mlp_group_forward, ptg_mlp_group_backward
-                             *     (up to eight MLPs of equal depth in the launches of one); no earlier declaration changed */
+                             *     (up to eight MLPs of equal depth in the launches of one); + ptg_rollout_buffer, ptg_rollout_buffer_begin, ptg_rollout_buffer_add
+                             *     (the on-policy algorithms' collect storage with its cursor on the device); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -60,7 +61,7 @@ enum {
     PTG_E_HIP = -2,            /* a HIP runtime call failed (no device, out of memory, ...) */
     PTG_E_ACTION = -3,         /* a discrete action outside [-5, 4] reached a kernel (reference: IndexError, :347) */
     PTG_E_RANGE = -4,          /* a price index left the series (reference: IndexError, :446-447) */
-    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss / ptg_td_loss an action outside [0, A) */
+    PTG_E_INDEX = -5,          /* ptg_minibatch / ptg_replay_sample met a sample index out of range (NumPy: IndexError); ptg_policy_loss / ptg_td_loss an action outside [0, A); ptg_rollout_buffer_add a full buffer */
     PTG_E_NONFINITE = -6       /* ptg_act met a row it cannot act on: NaN / +Inf input, all -Inf logits, NaN parameter, epsilon outside [0, 1];
                                 * ptg_policy_loss / ptg_td_loss / ptg_quantile_loss / ptg_actor_loss a row it has no finite loss for;
                                 * ptg_rsample / ptg_rsample_backward a non-finite mean, log_std, noise or incoming gradient */
@@ -506,6 +507,63 @@ int ptg_replay_add(ptg_env* env, const ptg_replay* rb, const void* prev_obs_dev,
                    int64_t n_steps, void* stream);
 int ptg_replay_sample(ptg_env* env, const ptg_replay* rb, const int64_t* idx_dev, int64_t batch, uint64_t seed, void* obs_out_dev,
                       void* next_obs_out_dev, void* const* cols_out_host, int norm_col, int64_t* idx_out_dev, void* stream);
+
+/* ---- the rollout buffer of the on-policy algorithms on the device ----------------------------------------------------
+ * Replaces: stable_baselines3.common.buffers.RolloutBuffer.reset / add (SB3 2.0.0a13), into which the reference's PPO (its default,
+ * rl_alg : PPO) and A2C collect: every action is chosen from the observation before it, so the collect step is network -> ptg_act ->
+ * ptg_step, captured into a hipGraph once and replayed.  A replayed graph has fixed addresses; with these two calls the step's results
+ * go to the next row all the same, because the row number lives on the device.  ptg_gae and ptg_minibatch read what they leave.
+ * Storage is the caller's (the library allocates nothing) and is described by a ptg_rollout_buffer, read during the call:
+ *   n_steps            T >= 1 steps per window
+ *   obs_rows           T + 1 observation blocks of obs_dim features, obs_bytes (4 | 8) per element, each laid out exactly like the
+ *                      block ptg_step writes (below), row r starting r * row_pitch elements behind row 0
+ *   col_rows[c]        n_cols <= PTG_MB_MAX_COLS contiguous [T][N] arrays of col_bytes[c] (1 | 2 | 4 | 8) bytes per element: rewards,
+ *                      done flags (uint8, ptg_step's own array, which ptg_gae takes), actions, values, log-probs ...  No column has a
+ *                      meaning to the kernel.
+ *   cursor_dev         uint64[2] on the device: {rows added in this window, completion ticket}.  The second word is reserved: begin zeroes it,
+ *                      add leaves it (a one-launch measurement build counts its workgroups in it).
+ * Row layout.  Row 0 holds the observation the window's first action is chosen from.  After the window obs_rows[0 .. T) are SB3's
+ * `observations` (what ptg_minibatch gathers from) and obs_rows[T] is `new_obs` (what last_values is computed from and what the next
+ * window begins with); SB3's episode_starts[t + 1] is the done column's row t.  No copy of the previous observation is kept anywhere.
+ *   ptg_rollout_buffer_begin(env, rb, obs_dev, obs_s_n, obs_s_f, row_pitch, stream)
+ *                      copies the block obs_dev into row 0 and sets both cursor words to 0 (RolloutBuffer.reset).
+ *   ptg_rollout_buffer_add(env, rb, obs_dev, obs_s_n, obs_s_f, row_pitch, n_cols, cols_host, col_stride_host, stream)
+ *                      with t = cursor[0] read on the device: obs_dev, the block ptg_step just wrote, goes to row t + 1; entry e of
+ *                      column source c goes to col_rows[c][t][e], byte for byte, read at cols_host[c] + e * col_stride_host[c]
+ *                      elements (stride >= 1: the value column out[:, A] of a joint network output is read in place); then
+ *                      cursor[0] = t + 1.  cols_host / col_stride_host [n_cols] are host arrays of device pointers / element strides.
+ * No transposing.  Feature f of env e is element e * obs_s_n + f * obs_s_f of the source block AND of the buffer row: a row has the
+ * source's layout.  Row-major, SB3_FLAT and SPLIT blocks, (obs_s_n, obs_s_f) = (F, 1), and feature-major blocks without a pitch,
+ * (1, N), are one contiguous run of N * F elements, row_pitch = N * F; a feature-major block with plane pitch p (ptg_set_feature_pitch),
+ * (1, p), is F runs of N elements, row_pitch = F * p, and the p - N pad elements of a plane are neither read nor written.
+ * ptg_minibatch reads both forms with obs_s_t = row_pitch.  Elements move as 16-byte pieces when the block is one contiguous run of a
+ * whole number of them and obs_dev, obs_rows and row_pitch * obs_bytes are multiples of 16, else one by one.
+ * Full buffer.  ptg_rollout_buffer_add with t >= n_steps never forms an address: nothing is written, the cursor stays, and the next
+ * ptg_sync (or any call that reports kernel-flagged errors) returns PTG_E_INDEX once (SB3 raises IndexError in the same place).
+ * Cursor.  Every workgroup of add's copy kernel reads cursor[0] before anything else; a trailing one-thread kernel advances it in
+ * stream order (or flags the full buffer), as ptg_replay_add does.  A one-launch form -- the workgroup that draws the last of one
+ * ticket per workgroup on cursor[1] advances the cursor -- was measured beside it inside a captured collect step and is not in the
+ * library.  There is no spin-wait, no cooperative launch and no atomic; the stored bytes do not depend on the grid.
+ * Both calls enqueue kernels only (begin one, add two): no host synchronisation, no allocation, pointers by value in the launch, so a captured add holds
+ * no host memory and every replay stores at the next row.  Neither touches env state, the finished-episode ring or the ptg_vn_*
+ * statistics.  Overlap of the sources with the buffer, of buffer rows with each other (a row_pitch below a block's extent) and of the
+ * columns is NOT checked.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, obs_rows, cursor, obs_dev or column (of the descriptor or of cols_host,
+ * or NULL arrays with n_cols > 0); n_steps < 1; obs_dim outside [1, 2^20]; obs_bytes other than 4 | 8; a negative stride or pitch;
+ * n_cols other than the descriptor's or outside [0, 8]; a column element size other than 1 | 2 | 4 | 8; a column stride < 1. */
+typedef struct ptg_rollout_buffer {
+    int64_t n_steps;
+    int32_t obs_dim, obs_bytes;
+    void* obs_rows;
+    int32_t n_cols;
+    int32_t col_bytes[PTG_MB_MAX_COLS];
+    void* col_rows[PTG_MB_MAX_COLS];
+    uint64_t* cursor_dev;
+} ptg_rollout_buffer;
+int ptg_rollout_buffer_begin(ptg_env* env, const ptg_rollout_buffer* rb, const void* obs_dev, int64_t obs_s_n, int64_t obs_s_f,
+                             int64_t row_pitch, void* stream);
+int ptg_rollout_buffer_add(ptg_env* env, const ptg_rollout_buffer* rb, const void* obs_dev, int64_t obs_s_n, int64_t obs_s_f, int64_t row_pitch,
+                           int n_cols, const void* const* cols_host, const int64_t* col_stride_host, void* stream);
 
 /* ---- the action head: policy outputs to actions, log-probs and entropy in one launch --------------------------------
  * Replaces what the reference's algorithms (src/rl_config_agent.py:80-222) run between the network's output and env.step while

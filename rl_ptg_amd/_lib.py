@@ -84,6 +84,11 @@ class PtgReplay(C.Structure):                               # ptg_replay: caller
                 ("col_ring", C.c_void_p * MB_MAX_COLS), ("cursor_dev", C.c_void_p)]
 
 
+class PtgRolloutBuffer(C.Structure):                        # ptg_rollout_buffer: caller-owned on-policy collect storage
+    _fields_ = [("n_steps", C.c_int64), ("obs_dim", C.c_int32), ("obs_bytes", C.c_int32), ("obs_rows", C.c_void_p), ("n_cols", C.c_int32),
+                ("col_bytes", C.c_int32 * MB_MAX_COLS), ("col_rows", C.c_void_p * MB_MAX_COLS), ("cursor_dev", C.c_void_p)]
+
+
 class PtgHead(C.Structure):                                 # ptg_head: one call of the action head
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("n_actions", C.c_int32), ("in_dtype", C.c_int32), ("in_dev", C.c_void_p),
                 ("in_s_n", C.c_int64), ("param_dev", C.c_void_p), ("param_s_n", C.c_int32), ("act_kind", C.c_int32),
@@ -174,7 +179,7 @@ STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby
 EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_obs_dim", "ptg_last_error",
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
-           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
+           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_rollout_buffer_begin", "ptg_rollout_buffer_add", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
            "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward", "ptg_mlp_backward_workspace", "ptg_mlp_backward",
            "ptg_mlp_group_forward", "ptg_mlp_group_backward",
@@ -294,6 +299,8 @@ def lib():
                                 C.c_int, C.POINTER(vp), i32p, C.POINTER(vp), vp]
     L.ptg_replay_add.argtypes = [vp, C.POINTER(PtgReplay), vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int64, vp]
     L.ptg_replay_sample.argtypes = [vp, C.POINTER(PtgReplay), vp, C.c_int64, C.c_uint64, vp, vp, C.POINTER(vp), C.c_int, vp, vp]
+    L.ptg_rollout_buffer_begin.argtypes = [vp, C.POINTER(PtgRolloutBuffer), vp, C.c_int64, C.c_int64, C.c_int64, vp]
+    L.ptg_rollout_buffer_add.argtypes = [vp, C.POINTER(PtgRolloutBuffer), vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), vp]
     L.ptg_act.argtypes = [vp, C.POINTER(PtgHead), vp]
     L.ptg_policy_loss_workspace.argtypes = [C.c_int64]
     L.ptg_policy_loss_workspace.restype = C.c_int64

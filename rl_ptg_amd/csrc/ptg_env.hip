@@ -2282,7 +2282,7 @@ namespace { thread_local std::string g_create_err; }
 
 int set_err(ptg_env* h, int code, const char* fmt, ...)
 {
-    char buf[512];
+    char buf[1024];                                         // the PTG_E_INDEX text of ptg_sync names five callers
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
@@ -2364,7 +2364,8 @@ int check_error_flags(ptg_env* h)          // after the stream has been synchron
                        "its output row and column entries were left untouched -- or ptg_policy_loss met an action outside [0, n_actions): "
                        "that row's gradients were left untouched and the statistics are NaN -- or a PTG_MLP_SPLIT_INPUT call of ptg_mlp_forward / "
                        "ptg_mlp_backward (or of their group calls) met a split row whose hour or day index is no integer inside the market series: "
-                       "that row's market columns were read as NaN");
+                       "that row's market columns were read as NaN -- or ptg_rollout_buffer_add was called on a full buffer (n_steps rows since "
+                       "ptg_rollout_buffer_begin; SB3 raises IndexError): nothing was stored and the cursor stayed");
     }
     if (__atomic_load_n(&e[5], __ATOMIC_RELAXED)) {
         __atomic_exchange_n(&e[5], 0, __ATOMIC_RELAXED);

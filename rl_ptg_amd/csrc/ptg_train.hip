@@ -488,6 +488,116 @@ k_rb_sample(const long long* __restrict__ idx, size_t B, unsigned long long seed
     if (out1) mb_stream_rows<V>(ring1, sizeof(V), P, off, rows, lane, out1 + b0 * row_bytes);
 }
 
+// ================================================================================== rollout buffer of the on-policy algorithms
+// stable-baselines3 2.0.0a13, common/buffers.py RolloutBuffer.reset / add, which the reference's PPO and A2C collect into.  The
+// caller owns the storage (ptg_rollout_buffer, include/ptg_env.h): T + 1 observation blocks in the engine's own layout, up to
+// PTG_MB_MAX_COLS columns [T][N] and a device cursor {rows added in this window, completion ticket}.  k_ro_add copies the block
+// ptg_step just wrote to row cursor[0] + 1 and one entry per env and column to row cursor[0] of the columns; every workgroup reads
+// cursor[0] before anything else, and k_ro_bump advances it in stream order behind the copy, as k_rb_bump does for the replay buffer.
+// A full buffer (cursor[0] >= T) forms no address: k_ro_bump raises err[4] (PTG_E_INDEX) and leaves the cursor.  The same kernel with
+// begin = 1 copies into row 0 and zeroes both cursor words.
+// Two one-launch forms were measured beside it and lost; they compile only into a measurement build,
+// -DPTG_RO_FORM=1 | 2 (tools/rollout_buffer_cost.py), never into the library that ships: the workgroup that draws the last ticket (one
+// atomicAdd per workgroup on cursor[1]) zeroes the ticket and advances the cursor, behind a __threadfence (1) or without one (2).
+// A block keeps the source's layout (no transpose): unit u of a block lies at the same byte offset in the source and in the row.
+// One contiguous run (row-major, sb3_flat, split, feature-major without a pitch): unit u at u * sizeof(V), V a 16-byte piece when the
+// run is a whole number of them and every base is aligned, else an element.  Strided (feature-major with a pitch): element
+// u = o * inner + i at o * s_outer + i * s_inner, the lanes along the unit-stride axis; pad columns are neither read nor written.
+// A workgroup takes 256 * RO_U consecutive units, lane l the units l, l + 256, ...: every load and store instruction of a wave is one
+// contiguous segment, and RO_U loads are in flight before the first store.  Lane e < N of the launch moves env e's column entries
+// (consecutive lanes, consecutive entries of every column ring).  The data path holds no atomic.
+constexpr int RO_U = 4;                  // units in flight per lane: 640 workgroups, not 2 560, at 65 536 envs x 40 float32
+#ifndef PTG_RO_FORM
+#define PTG_RO_FORM 0                    // 0: k_ro_bump behind the copy (ships); 1, 2: the ticket forms of a measurement build
+#endif
+
+struct RoAdd {                           // by value in the launch: a captured call holds no host memory
+    const char* obs;                     // the source block
+    char* rows;                          // buffer row 0
+    unsigned long long* cursor;          // {rows added, ticket (counted in by a measurement build only; else 0)}
+    int* err;
+    size_t row_bytes;                    // between buffer rows
+    size_t T, N, units, inner;           // inner == units: one contiguous run
+    size_t s_outer, s_inner;             // bytes
+    const char* col_src[PTG_MB_MAX_COLS];
+    char* col_dst[PTG_MB_MAX_COLS];
+    size_t col_stride[PTG_MB_MAX_COLS];  // of the source, bytes
+    int col_bytes[PTG_MB_MAX_COLS];
+    int n_cols;
+};
+
+template <typename V>
+__global__ void __launch_bounds__(256)
+k_ro_add(RoAdd a, int begin)
+{
+    const unsigned long long t = begin ? 0ull : a.cursor[0];
+    const bool full = !begin && t >= a.T;
+    if (!full) {
+        char* const dst = a.rows + (size_t)(begin ? 0ull : t + 1) * a.row_bytes;
+        const size_t u0 = (size_t)blockIdx.x * (256 * RO_U) + threadIdx.x;
+        V v[RO_U];
+        size_t off[RO_U];
+        bool ok[RO_U];
+#pragma unroll
+        for (int j = 0; j < RO_U; j++) {
+            const size_t u = u0 + (size_t)j * 256;
+            ok[j] = u < a.units;
+            off[j] = u * sizeof(V);
+            if (a.inner != a.units) {                        // launch-uniform
+                if (a.units <= 0xFFFFFFFFull) { const unsigned o = (unsigned)u / (unsigned)a.inner; off[j] = o * a.s_outer + ((unsigned)u - o * (unsigned)a.inner) * a.s_inner; }
+                else { const size_t o = u / a.inner; off[j] = o * a.s_outer + (u - o * a.inner) * a.s_inner; }
+            }
+            v[j] = V();
+            if (ok[j]) v[j] = *(const V*)(a.obs + off[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < RO_U; j++)
+            if (ok[j]) *(V*)(dst + off[j]) = v[j];
+        const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+        if (!begin && e < a.N)
+            for (int c = 0; c < a.n_cols; c++) {             // wave-uniform trip count and switch
+                const char* s = a.col_src[c] + e * a.col_stride[c];
+                char* d = a.col_dst[c] + ((size_t)t * a.N + e) * (size_t)a.col_bytes[c];
+                switch (a.col_bytes[c]) {
+                    case 1: *(uint8_t*)d = *(const uint8_t*)s; break;
+                    case 2: *(uint16_t*)d = *(const uint16_t*)s; break;
+                    case 4: *(uint32_t*)d = *(const uint32_t*)s; break;
+                    default: *(uint64_t*)d = *(const uint64_t*)s; break;
+                }
+            }
+    }
+    if (begin) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { a.cursor[0] = 0; a.cursor[1] = 0; }
+        return;
+    }
+#if PTG_RO_FORM != 0
+    // Measurement build.  The cursor must not move before every workgroup has read it.  It cannot: a workgroup's loads of cursor[0]
+    // have returned before its stores are issued (their addresses, and the branch on `full`, depend on t), the stores stand before
+    // the barrier in program order, and the draw stands behind it -- so every draw follows its workgroup's read, and the one write
+    // of cursor[0] follows the draw that returned gridDim.x - 1, i.e. all draws.  The draw is a relaxed atomic and the two stores
+    // behind it are plain: nothing in this launch reads what they publish, and the end of the kernel publishes them to the next.
+    // Form 1 adds the agent-scope release the first design asked for; it orders nothing that anyone waits for.
+#if PTG_RO_FORM == 1
+    __threadfence();
+#endif
+    __syncthreads();
+    if (threadIdx.x == 0 && atomicAdd(&a.cursor[1], 1ull) == (unsigned long long)gridDim.x - 1) {
+        a.cursor[1] = 0;
+        if (full) a.err[4] = 1;
+        else a.cursor[0] = t + 1;
+    }
+#endif
+}
+
+#if PTG_RO_FORM == 0
+// DeviceReplayBuffer's form: the copy kernel, then this one in stream order.
+__global__ void k_ro_bump(unsigned long long* cursor, unsigned long long T, int* err)
+{
+    if (cursor[0] >= T) err[4] = 1;
+    else cursor[0] += 1;
+}
+#endif
+
 // ================================================================================== the action head
 // What runs between the network's output and env.step while collecting (include/ptg_env.h, ptg_act, states the lines; the tests
 // restate them in NumPy): SB3's CategoricalDistribution sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads of
@@ -1987,6 +2097,78 @@ int ptg_replay_sample(ptg_env* h, const ptg_replay* rb, const int64_t* idx_dev, 
     else hipLaunchKernelGGL(k_rb_sample<uint32_t>, grid, block, 0, st, idx, B, (unsigned long long)seed, cur, S, N, row_bytes, (unsigned)rb->obs_dim, r0, r1, o0, o1, cols, norm, idx_out, h->P.err);
     if (!idx_dev) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)rb->cursor_dev + 1, 1ull);
     return launch_check(h, "k_rb_sample");
+}
+
+// ---- RolloutBuffer.reset / add on the device, over the caller's rows --------------------------------------------------
+// begin (cols_host unused) and add share every check and the launch; `who` names the entry point in the refusal
+static int rollout_buffer_store(ptg_env* h, const char* who, bool begin, const ptg_rollout_buffer* rb, const void* obs_dev, int64_t obs_s_n,
+                                int64_t obs_s_f, int64_t row_pitch, int n_cols, const void* const* cols_host, const int64_t* col_stride_host, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!rb) return set_err(h, PTG_E_INVALID, "%s: null descriptor", who);
+    if (!rb->obs_rows || !rb->cursor_dev) return set_err(h, PTG_E_INVALID, "%s: null obs_rows or cursor in the descriptor", who);
+    if (rb->n_steps < 1) return set_err(h, PTG_E_INVALID, "%s: n_steps < 1", who);
+    if (rb->obs_dim < 1 || rb->obs_dim > (1 << 20) || (rb->obs_bytes != 4 && rb->obs_bytes != 8))
+        return set_err(h, PTG_E_INVALID, "%s: obs_dim outside [1, 2^20] or obs_bytes other than 4 | 8", who);
+    if (rb->n_cols < 0 || rb->n_cols > PTG_MB_MAX_COLS) return set_err(h, PTG_E_INVALID, "%s: n_cols outside [0, 8]", who);
+    for (int c = 0; c < rb->n_cols; c++) {
+        const int s = rb->col_bytes[c];
+        if (!rb->col_rows[c]) return set_err(h, PTG_E_INVALID, "%s: column %d of the descriptor is null", who, c);
+        if (s != 1 && s != 2 && s != 4 && s != 8) return set_err(h, PTG_E_INVALID, "%s: column %d has %d-byte elements (1, 2, 4 or 8)", who, c, s);
+    }
+    if (!obs_dev) return set_err(h, PTG_E_INVALID, "%s: null observations", who);
+    if (obs_s_n < 0 || obs_s_f < 0 || row_pitch < 0) return set_err(h, PTG_E_INVALID, "%s: negative stride or pitch", who);
+    RoAdd a{};
+    if (!begin) {
+        if (n_cols != rb->n_cols || (n_cols > 0 && (!cols_host || !col_stride_host)))
+            return set_err(h, PTG_E_INVALID, "%s: n_cols differs from the descriptor's, or null column arrays", who);
+        for (int c = 0; c < n_cols; c++) {
+            if (!cols_host[c]) return set_err(h, PTG_E_INVALID, "%s: column %d is null", who, c);
+            if (col_stride_host[c] < 1) return set_err(h, PTG_E_INVALID, "%s: column %d has stride %lld (>= 1)", who, c, (long long)col_stride_host[c]);
+            a.col_src[c] = (const char*)cols_host[c]; a.col_dst[c] = (char*)rb->col_rows[c]; a.col_bytes[c] = rb->col_bytes[c];
+            a.col_stride[c] = (size_t)col_stride_host[c] * (size_t)rb->col_bytes[c];
+        }
+        a.n_cols = n_cols;
+    }
+    const size_t sz = (size_t)rb->obs_bytes, N = (size_t)h->n, F = (size_t)rb->obs_dim, s_n = (size_t)obs_s_n, s_f = (size_t)obs_s_f;
+    a.obs = (const char*)obs_dev; a.rows = (char*)rb->obs_rows; a.cursor = (unsigned long long*)rb->cursor_dev; a.err = h->P.err;
+    a.row_bytes = (size_t)row_pitch * sz; a.T = (size_t)rb->n_steps; a.N = N;
+    // one contiguous run of N * F elements: [N][F] rows back to back, or [F][N] planes back to back
+    const bool run = ((F == 1 || s_f == 1) && (N == 1 || s_n == F)) || ((N == 1 || s_n == 1) && (F == 1 || s_f == N));
+    bool wide = false;
+    if (run) {
+        const auto al = [](const void* q) { return (uintptr_t)q % 16 == 0; };
+        wide = (N * F * sz) % 16 == 0 && a.row_bytes % 16 == 0 && al(a.obs) && al(a.rows);
+        a.units = a.inner = wide ? N * F * sz / 16 : N * F;
+    } else {
+        a.units = N * F;
+        if (s_n == 1) { a.inner = N; a.s_inner = sz; a.s_outer = s_f * sz; }          // planes at a pitch: the lanes along the envs
+        else { a.inner = F; a.s_inner = s_f * sz; a.s_outer = s_n * sz; }
+    }
+    const size_t per = 256 * RO_U, blocks = std::max((a.units + per - 1) / per, begin ? (size_t)1 : (N + 255) / 256);
+    if (blocks > 0x7FFFFFFFull) return set_err(h, PTG_E_INVALID, "%s: the block is too large for one launch", who);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (wide) hipLaunchKernelGGL(k_ro_add<uint4>, grid, block, 0, st, a, (int)begin);
+    else if (sz == 8) hipLaunchKernelGGL(k_ro_add<uint64_t>, grid, block, 0, st, a, (int)begin);
+    else hipLaunchKernelGGL(k_ro_add<uint32_t>, grid, block, 0, st, a, (int)begin);
+#if PTG_RO_FORM == 0
+    if (!begin) hipLaunchKernelGGL(k_ro_bump, dim3(1), dim3(1), 0, st, a.cursor, (unsigned long long)a.T, a.err);
+#endif
+    return launch_check(h, "k_ro_add");
+}
+
+int ptg_rollout_buffer_begin(ptg_env* h, const ptg_rollout_buffer* rb, const void* obs_dev, int64_t obs_s_n, int64_t obs_s_f, int64_t row_pitch,
+                             void* stream)
+{
+    return rollout_buffer_store(h, "ptg_rollout_buffer_begin", true, rb, obs_dev, obs_s_n, obs_s_f, row_pitch, 0, nullptr, nullptr, stream);
+}
+
+int ptg_rollout_buffer_add(ptg_env* h, const ptg_rollout_buffer* rb, const void* obs_dev, int64_t obs_s_n, int64_t obs_s_f, int64_t row_pitch,
+                           int n_cols, const void* const* cols_host, const int64_t* col_stride_host, void* stream)
+{
+    return rollout_buffer_store(h, "ptg_rollout_buffer_add", false, rb, obs_dev, obs_s_n, obs_s_f, row_pitch, n_cols, cols_host, col_stride_host, stream);
 }
 
 // ---- the action head: policy outputs -> actions, log-probs, entropy ----------------------------------------------------

@@ -533,6 +533,54 @@ class TrainOps:
         self._call("ptg_replay_sample", C.byref(d), _ptr(idx), B, int(seed) & (2 ** 64 - 1), _ptr(o0), _ptr(o1), _ptr(outs), norm_col, _ptr(io))
         return o0, o1, outs, io
 
+    # ------------------------------------------------------------------ RolloutBuffer.reset / add on the device
+    def _rollout_desc(self, st, who, obs):
+        """the ptg_rollout_buffer descriptor of a storage object (rl_ptg_amd.rollout_buffer.RolloutStorage: obs_rows [T + 1, ...] as
+        alloc_obs(T + 1) makes them, col_rows [T, N] each, cursor uint64-as-int64 [2]) and the (obs_s_n, obs_s_f, row_pitch) of its
+        blocks; its tensors and obs, one block of the same layout, checked"""
+        torch = self._torch
+        rows, cols, cur = st.obs_rows, list(st.col_rows), st.cursor
+        fm = self.feature_major
+        check(self, who, "obs_rows", rows, sizes=(4, 8), shape=(None, None, self.n) if fm else (None, self.n, None), rule=self._check_obs)
+        T, F = rows.shape[0] - 1, rows.shape[1] if fm else rows.shape[2]
+        if T < 1 or F < 1:
+            raise ValueError(f"{who}: obs_rows must hold T + 1 >= 2 blocks of F >= 1 features, got shape {tuple(rows.shape)}")
+        if len(cols) > _lib.MB_MAX_COLS:
+            raise ValueError(f"{who}: at most {_lib.MB_MAX_COLS} columns, got {len(cols)}")
+        for c, x in enumerate(cols):
+            check(self, who, f"col_rows {c}", x, sizes=(1, 2, 4, 8), shape=(T, self.n), rule=contiguous)
+        check(self, who, "cursor", cur, dtypes=(torch.int64,), numel=2, shape=(2,), rule=contiguous)
+        check(self, who, "obs", obs, dtypes=(rows.dtype,), shape=tuple(rows.shape[1:]), rule=self._check_obs)
+        d = _lib.PtgRolloutBuffer()
+        d.n_steps, d.obs_dim, d.obs_bytes, d.obs_rows, d.n_cols, d.cursor_dev = T, F, rows.element_size(), _ptr(rows), len(cols), _ptr(cur)
+        for c, x in enumerate(cols):
+            d.col_bytes[c], d.col_rows[c] = x.element_size(), x.data_ptr()
+        return d, ((1, self.pitch, F * self.pitch) if fm else (F, 1, self.n * F))
+
+    def rollout_buffer_begin(self, storage, obs):
+        """Enqueue, on the current stream, SB3's RolloutBuffer.reset (include/ptg_env.h: ptg_rollout_buffer_begin): obs, an
+        observation block in the engine's layout ([N, F], or [F, N] feature-major with the engine's pitch), goes to row 0 of
+        storage.obs_rows and both cursor words become 0.  No synchronisation."""
+        d, lay = self._rollout_desc(storage, "rollout_buffer_begin", obs)
+        self._call("ptg_rollout_buffer_begin", C.byref(d), _ptr(obs), *lay)
+
+    def rollout_buffer_add(self, storage, obs, columns=()):
+        """Enqueue, on the current stream, SB3's RolloutBuffer.add for one vector step (include/ptg_env.h: ptg_rollout_buffer_add):
+        with t = cursor[0] read on the device, obs -- the block step() just wrote -- goes to row t + 1 of storage.obs_rows and
+        columns[c], an [N] tensor of col_rows[c]'s dtype with any stride >= 1 (a column of a wider network output is read in place),
+        to col_rows[c][t]; then the cursor advances on the device, so a captured call stores at the next row on every replay.  No
+        synchronisation; a call on a full buffer stores nothing and makes the next sync() raise PtgError with code PTG_E_INDEX.
+        Sources must not overlap the storage (not checked)."""
+        who = "rollout_buffer_add"
+        d, lay = self._rollout_desc(storage, who, obs)
+        columns = list(columns)
+        if len(columns) != len(storage.col_rows):
+            raise ValueError(f"{who}: {len(storage.col_rows)} columns in the storage but {len(columns)} given")
+        for c, x in enumerate(columns):
+            check(self, who, f"column {c}", x, dtypes=(storage.col_rows[c].dtype,), shape=(self.n,), rule=step)
+        stride = (C.c_int64 * max(len(columns), 1))(*[x.stride(0) if self.n > 1 else 1 for x in columns])     # one env: its only stride is free
+        self._call("ptg_rollout_buffer_add", C.byref(d), _ptr(obs), *lay, len(columns), _ptr(columns), stride)
+
     # ------------------------------------------------------------------ the action head while collecting
     def new_draw_counter(self):
         """The zeroed device counter of the action heads' draws: uint64 [1], held as an int64 tensor.  A stochastic act_* call advances
