@@ -49,7 +49,9 @@ extern "C" {
                              *     one fused f32 MFMA launch per layer); + ptg_mlp_bwd, ptg_mlp_backward, ptg_mlp_backward_workspace (the backward pass
                              *     of those MLPs, two f32 MFMA launches per layer); + PTG_MLP_GROUP_MAX, ptg_mlp_group_forward, ptg_mlp_group_backward
                              *     (up to eight MLPs of equal depth in the launches of one); + ptg_rollout_buffer, ptg_rollout_buffer_begin, ptg_rollout_buffer_add
-                             *     (the on-policy algorithms' collect storage with its cursor on the device); no earlier declaration changed */
+                             *     (the on-policy algorithms' collect storage with its cursor on the device); + ptg_sde_noise, ptg_sde_head, ptg_sde_loss, ptg_sde_resample,
+                             *     ptg_sde_act, ptg_sde_policy_loss, ptg_sde_policy_loss_workspace (gSDE: the state-dependent exploration head while
+                             *     collecting and its PPO / A2C loss); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -573,7 +575,7 @@ int ptg_rollout_buffer_add(ptg_env* env, const ptg_rollout_buffer* rb, const voi
  *   PTG_HEAD_GAUSSIAN     TD3 clip(mu + N(0, sigma_exp), -1, 1); SAC / TQC tanh(mu + sigma z) (PTG_HEAD_SQUASH); A2C / PPO with
  *                         action_type "continuous": DiagGaussianDistribution, clipped to the Box for the env and stored unclipped
  * -- six to ten element-wise launches in torch.  The env's Box is one-dimensional, so the Gaussian head has D = 1: one mean and one
- * action per env.  Out of scope: the networks, gSDE (evaluate_actions at training time is ptg_policy_loss, below).
+ * action per env.  Out of scope: the networks (evaluate_actions at training time is ptg_policy_loss, below).  gSDE (use_sde) has ops of its own: ptg_sde_resample / ptg_sde_act, behind ptg_policy_loss.
  * The head is described by a ptg_head, read during the call:
  *   kind          PTG_HEAD_CATEGORICAL | PTG_HEAD_EPS_GREEDY | PTG_HEAD_GAUSSIAN
  *   flags         PTG_HEAD_DETERMINISTIC: the mode; nothing is drawn, counter_dev is neither read nor advanced (and may be NULL).
@@ -648,7 +650,7 @@ int ptg_act(ptg_env* env, const ptg_head* head, void* stream);
  * network's outputs is a closed form of quantities the forward pass holds, so one pass emits the loss, the statistics SB3 logs,
  * d loss / d logits (or means), d loss / d values and d loss / d log_std; the caller's backward starts from those
  * (rl_ptg_amd/loss.py wraps the call in a torch.autograd.Function).  Out of scope: the networks, target_kl's early stop (the
- * caller reads stats[4]), gSDE, the squashed and off-policy losses, a per-env log_std.  The optimiser and max_grad_norm follow the
+ * caller reads stats[4]), the squashed and off-policy losses, a per-env log_std.  The gSDE head's loss is ptg_sde_policy_loss, below.  The optimiser and max_grad_norm follow the
  * backward pass as ptg_optim_step, below.
  * The call is described by a ptg_loss, read during the call (B = batch, A = n_actions):
  *   kind          PTG_LOSS_PPO | PTG_LOSS_A2C
@@ -746,6 +748,134 @@ typedef struct ptg_loss {
 } ptg_loss;
 int64_t ptg_policy_loss_workspace(int64_t batch);
 int ptg_policy_loss(ptg_env* env, const ptg_loss* d, void* stream);
+
+/* ---- gSDE: the state-dependent exploration head while collecting, and its PPO / A2C loss ------------------------------------
+ * Replaces what SB3 2.0.0a13 runs for the reference's agent switch `gSDE : True` (config/config_agent.yaml; src/rl_config_agent.py
+ * passes it as use_sde) in A2C and PPO: common/distributions.py::StateDependentNoiseDistribution with its on-policy defaults
+ * full_std=True, use_expln=False, squash_output=False, learn_features=False, epsilon = 1e-6 -- sample_weights, proba_distribution,
+ * sample, log_prob, entropy, mode -- and evaluate_actions plus the loss lines of PPO.train / A2C.train on that distribution: about a
+ * dozen element-wise launches, an mm and a bmm per collect step in torch.  The env's Box is one-dimensional, so D = 1: log_std is
+ * [L, 1], an exploration matrix is one [L] row per env.  L = latent_dim is the width of the policy's last hidden layer,
+ * 1 <= L <= PTG_MLP_MAX_WIDTH (1024); the latent rows are what a PTG_MLP_KEEP_HIDDEN forward leaves in its workspace, whose rows are
+ * padded to 16 bytes, so every [.][L] array here has a row stride >= L.
+ * Out of scope: SAC / TQC with gSDE (squashing, clip_mean, learn_features=True, reset_noise per gradient step); use_expln;
+ * full_std=False; D > 1; fusing the head into the network's last layer.  sde_sample_freq is the caller's schedule of ptg_sde_resample.
+ * Arithmetic, all three ops: float64 whatever in_dtype is, every operation rounded once (no fused multiply-add), results rounded once
+ * on the store; exp, log, sqrt, cos are the double-precision library functions.  s_k = exp((double)log_std[k]); h_k a latent entry.
+ * Sums over k run in an order given by L alone: unit k belongs to lane k mod 64, a lane adds its terms ascending in k from 0.0, the 64
+ * lane sums meet in ptg_policy_loss's shuffle tree (offsets 32, 16, ..., 1).
+ *
+ * ptg_sde_resample (sample_weights) fills the exploration matrix E_dev [N][L] in in_dtype, element (e, k) at e * e_s_n + k, N the
+ * handle's n_envs.  With c = *counter_dev (uint64 [1], read on the device), element (e, k) takes the words (w0, w1) of
+ * ptg_replay_sample's chain with the key (seed, c, (global env offset + e) * 1024 + k) -- the key depends neither on L nor on the
+ * shard -- z is ptg_act's Gaussian draw from (w0, w1), and E[e][k] = s_k * z.  log_std_dev is [L] contiguous in in_dtype, read when
+ * the kernel runs.  A trailing one-thread kernel does *counter_dev += 1, so a replayed graph draws afresh.  A NaN or +Inf log_std[k]
+ * makes column k NaN and the next ptg_sync returns PTG_E_NONFINITE once.  Two launches.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, log_std_dev, counter_dev or e_dev; an in_dtype other than the two;
+ * latent_dim outside [1, 1024]; e_s_n < latent_dim. */
+typedef struct ptg_sde_noise {
+    int32_t in_dtype, latent_dim;
+    const void* log_std_dev;
+    uint64_t seed;
+    uint64_t* counter_dev;
+    void* e_dev;
+    int64_t e_s_n;
+} ptg_sde_noise;
+int ptg_sde_resample(ptg_env* env, const ptg_sde_noise* d, void* stream);
+
+/* ptg_sde_act (proba_distribution, sample / mode, log_prob, entropy) is the collecting head, one launch:
+ *   flags         PTG_HEAD_DETERMINISTIC: the mode; noise = 0, e_dev is neither read nor required
+ *   mean_dev      [N] in in_dtype, element e at e * mean_s_n, mean_s_n >= 1
+ *   latent_dev    [N][L], element (e, k) at e * latent_s_n + k, latent_s_n >= L;  e_dev likewise with e_s_n;  log_std_dev [L] contiguous
+ *   act_dev       [N] float32 (act_kind PTG_ACT_F32): what ptg_step takes;  raw_dev, logp_dev, ent_dev [N] in in_dtype, nullable
+ * Per env:  noise = sum_k h_k * E_k;  V = (sum_k (h_k * h_k) * (s_k * s_k)) + 1e-6;  sd = sqrt(V);  lsd = log(sd);  g = mu + noise;
+ * raw = g;  action = clip(g, clip_lo, clip_hi) rounded to float32 (ptg_act's clip);  logp = ((-(noise * noise)) / (2 * V)) - lsd -
+ * 0.9189385332046727;  entropy = 1.4189385332046727 + lsd.
+ * Bad rows: a row whose mean or any latent entry is not finite, and every row when any log_std is NaN or +Inf, gets action 0 and NaN
+ * in raw / logp / ent; the other rows are computed as usual and the next ptg_sync returns PTG_E_NONFINITE once.
+ * Reads nothing of the handle but its n_envs and device.  Enqueues one kernel: no host synchronisation, no allocation.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, mean_dev, latent_dev, log_std_dev or act_dev; NULL e_dev unless
+ * deterministic; an unknown flag; an in_dtype other than the two; latent_dim outside [1, 1024]; an act_kind other than PTG_ACT_F32;
+ * mean_s_n < 1; latent_s_n < latent_dim; e_s_n < latent_dim (unless deterministic); clip_lo > clip_hi or a NaN bound. */
+typedef struct ptg_sde_head {
+    int32_t flags, in_dtype;
+    int32_t latent_dim, act_kind;
+    const void* mean_dev;
+    int64_t mean_s_n;
+    const void* latent_dev;
+    int64_t latent_s_n;
+    const void* e_dev;
+    int64_t e_s_n;
+    const void* log_std_dev;
+    double clip_lo, clip_hi;
+    void* act_dev;
+    void* raw_dev;
+    void* logp_dev;
+    void* ent_dev;
+} ptg_sde_head;
+int ptg_sde_act(ptg_env* env, const ptg_sde_head* d, void* stream);
+
+/* ptg_sde_policy_loss is ptg_policy_loss for this head.  kind, flags, batch, in_dtype, val_dev / val_s_n, old_logp_dev, adv_dev,
+ * ret_dev, old_val_dev, the four host doubles, stats_dev [8], grad_in_dev / g_s_n (d loss / d means), grad_val_dev / gv_s_n mean
+ * exactly what they mean in ptg_loss, and the advantage, PPO / A2C, value and "means" lines are ptg_policy_loss's (one device text
+ * serves both).  mean_dev / mean_s_n are ptg_loss's Gaussian in_dev / in_s_n.  New:
+ *   latent_dev    [B][L], element (i, k) at i * latent_s_n + k, latent_s_n >= L
+ *   log_std_dev   [L] contiguous in in_dtype, read when the kernels run
+ *   act_dev       [B] contiguous in in_dtype: the stored raw samples
+ *   grad_log_std_dev   [L] contiguous in in_dtype, required
+ *   grad_latent_dev    [B][L] with row stride gl_s_n >= L, nullable (SB3's on-policy learn_features=False: NULL)
+ *   ws_dev        caller-owned device scratch, 8-byte aligned, at least ptg_sde_policy_loss_workspace(batch, latent_dim) bytes
+ * Row i:  V, sd, lsd as in ptg_sde_act;  d = a - mu;  lp = ((-(d * d)) / (2 * V)) - lsd - 0.9189385332046727;  H = 1.4189385332046727 + lsd.
+ * Gradients, g the surrogate's derivative of ptg_policy_loss:
+ *   d loss / d mu = ((-g) * (d / V)) / B
+ *   c_i = (((-g) * (((d * d) / V) - 1)) - c_e) / (2 * V)               (B times the loss's derivative with respect to V_i)
+ *   d loss / d log_std[k] = ((2 * (s_k * s_k)) * sum_i c_i * (h_ik * h_ik)) / B
+ *   d loss / d h_ik = ((c_i * (2 * h_ik)) * (s_k * s_k)) / B
+ * Batch sums run in an order given by (B, L) alone, with no floating-point atomics -- the same inputs give the same bits on every
+ * run.  With R = ceil(B / 4096) rows per wave, block b of 4 waves owns rows [4 R b, 4 R (b + 1)); wave w walks rows 4 R b + w,
+ * 4 R b + w + 4, ... ascending; sum_i c_i * h_ik^2 is added per wave in that order from 0.0, then the block's waves in wave order,
+ * then the blocks ascending.  The five means: per wave in the same row order, then ptg_policy_loss's steps 2 and 3 over these blocks.
+ * Bad rows follow ptg_policy_loss's rules (NaN gradients, NaN stats[0..5], PTG_E_NONFINITE at the next ptg_sync); besides, a
+ * non-finite latent entry or a non-finite V makes its row bad, and a NaN or +Inf log_std makes every row bad.  A bad row makes
+ * every entry of grad_log_std NaN.
+ * Enqueues kernels only -- s_k^2 into the workspace, the rows, the means, the log_std gradient, and two more in front for the moments
+ * under PTG_LOSS_NORM_ADV -- no host synchronisation, no allocation.  Reads nothing of the handle but its device.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, mean_dev, val_dev, latent_dev, log_std_dev, act_dev, adv_dev, ret_dev,
+ * stats_dev, grad_in_dev, grad_val_dev, grad_log_std_dev or ws_dev (or a ws_dev that is not 8-byte aligned); NULL old_logp_dev for
+ * PPO; an unknown kind or flag; batch outside [1, 2^31]; an in_dtype other than the two; latent_dim outside [1, 1024]; mean_s_n,
+ * g_s_n, val_s_n or gv_s_n below 1; latent_s_n, or gl_s_n with grad_latent_dev, below latent_dim; PTG_LOSS_CLIP_VF without
+ * old_val_dev; a NaN or negative clip_range (PPO) or clip_range_vf (with PTG_LOSS_CLIP_VF).
+ * ptg_sde_policy_loss_workspace(batch, latent_dim): bytes of scratch; with m = ceil(B / 256) and n = ceil(B / (4 R)) blocks it is
+ * 8 * (4 + 3 m + L + n * (8 + L)); negative for a batch outside [1, 2^31] or a latent_dim outside [1, 1024]. */
+typedef struct ptg_sde_loss {
+    int32_t kind, flags;
+    int32_t in_dtype, latent_dim;
+    int64_t batch;
+    const void* mean_dev;
+    int64_t mean_s_n;
+    const void* val_dev;
+    int64_t val_s_n;
+    const void* latent_dev;
+    int64_t latent_s_n;
+    const void* log_std_dev;
+    const void* act_dev;
+    const void* old_logp_dev;
+    const void* adv_dev;
+    const void* ret_dev;
+    const void* old_val_dev;
+    double clip_range, clip_range_vf, ent_coef, vf_coef;
+    double* stats_dev;
+    void* grad_in_dev;
+    int64_t g_s_n;
+    void* grad_val_dev;
+    int64_t gv_s_n;
+    void* grad_log_std_dev;
+    void* grad_latent_dev;
+    int64_t gl_s_n;
+    void* ws_dev;
+} ptg_sde_loss;
+int64_t ptg_sde_policy_loss_workspace(int64_t batch, int32_t latent_dim);
+int ptg_sde_policy_loss(ptg_env* env, const ptg_sde_loss* d, void* stream);
 
 /* ---- the optimiser step: grad-norm clip, Adam / RMSprop, Polyak and zero_grad for all tensors of an optimiser --------------------
  * Replaces what the reference's agents (src/rl_config_agent.py; SB3 2.0.0a13 on torch) run behind loss.backward() on every minibatch:

@@ -105,6 +105,28 @@ class PtgLoss(C.Structure):                                 # ptg_loss: one call
                 ("grad_val_dev", C.c_void_p), ("gv_s_n", C.c_int64), ("grad_log_std_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
 
 
+class PtgSdeNoise(C.Structure):                             # ptg_sde_noise: one refill of gSDE's exploration matrix
+    _fields_ = [("in_dtype", C.c_int32), ("latent_dim", C.c_int32), ("log_std_dev", C.c_void_p), ("seed", C.c_uint64), ("counter_dev", C.c_void_p),
+                ("e_dev", C.c_void_p), ("e_s_n", C.c_int64)]
+
+
+class PtgSdeHead(C.Structure):                              # ptg_sde_head: one call of gSDE's collecting head
+    _fields_ = [("flags", C.c_int32), ("in_dtype", C.c_int32), ("latent_dim", C.c_int32), ("act_kind", C.c_int32), ("mean_dev", C.c_void_p),
+                ("mean_s_n", C.c_int64), ("latent_dev", C.c_void_p), ("latent_s_n", C.c_int64), ("e_dev", C.c_void_p), ("e_s_n", C.c_int64),
+                ("log_std_dev", C.c_void_p), ("clip_lo", C.c_double), ("clip_hi", C.c_double), ("act_dev", C.c_void_p), ("raw_dev", C.c_void_p),
+                ("logp_dev", C.c_void_p), ("ent_dev", C.c_void_p)]
+
+
+class PtgSdeLoss(C.Structure):                              # ptg_sde_loss: one call of the policy loss on gSDE's head
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("in_dtype", C.c_int32), ("latent_dim", C.c_int32), ("batch", C.c_int64),
+                ("mean_dev", C.c_void_p), ("mean_s_n", C.c_int64), ("val_dev", C.c_void_p), ("val_s_n", C.c_int64), ("latent_dev", C.c_void_p),
+                ("latent_s_n", C.c_int64), ("log_std_dev", C.c_void_p), ("act_dev", C.c_void_p), ("old_logp_dev", C.c_void_p), ("adv_dev", C.c_void_p),
+                ("ret_dev", C.c_void_p), ("old_val_dev", C.c_void_p), ("clip_range", C.c_double), ("clip_range_vf", C.c_double),
+                ("ent_coef", C.c_double), ("vf_coef", C.c_double), ("stats_dev", C.c_void_p), ("grad_in_dev", C.c_void_p), ("g_s_n", C.c_int64),
+                ("grad_val_dev", C.c_void_p), ("gv_s_n", C.c_int64), ("grad_log_std_dev", C.c_void_p), ("grad_latent_dev", C.c_void_p),
+                ("gl_s_n", C.c_int64), ("ws_dev", C.c_void_p)]
+
+
 class PtgOptimTensor(C.Structure):                          # ptg_optim_tensor: one record of the optimiser's tensor table
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p), ("target", C.c_void_p),
                 ("numel", C.c_int64)]
@@ -180,6 +202,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_rollout_buffer_begin", "ptg_rollout_buffer_add", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
+           "ptg_sde_resample", "ptg_sde_act", "ptg_sde_policy_loss_workspace", "ptg_sde_policy_loss",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
            "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward", "ptg_mlp_backward_workspace", "ptg_mlp_backward",
            "ptg_mlp_group_forward", "ptg_mlp_group_backward",
@@ -305,6 +328,11 @@ def lib():
     L.ptg_policy_loss_workspace.argtypes = [C.c_int64]
     L.ptg_policy_loss_workspace.restype = C.c_int64
     L.ptg_policy_loss.argtypes = [vp, C.POINTER(PtgLoss), vp]
+    L.ptg_sde_resample.argtypes = [vp, C.POINTER(PtgSdeNoise), vp]
+    L.ptg_sde_act.argtypes = [vp, C.POINTER(PtgSdeHead), vp]
+    L.ptg_sde_policy_loss_workspace.argtypes = [C.c_int64, C.c_int32]
+    L.ptg_sde_policy_loss_workspace.restype = C.c_int64
+    L.ptg_sde_policy_loss.argtypes = [vp, C.POINTER(PtgSdeLoss), vp]
     L.ptg_optim_chunk.argtypes = []
     L.ptg_optim_workspace.argtypes = [C.c_int64]
     L.ptg_optim_workspace.restype = C.c_int64

@@ -9,6 +9,7 @@
 //   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
 //   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
 //   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
+//   k_sde_*           gSDE (SB3's StateDependentNoiseDistribution, on-policy): the exploration matrix, the collecting head, the PPO / A2C loss.
 //   k_optim_*         clip_grad_norm_, torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad over all tensors of an optimiser.
 //   k_td_*            the TD loss of DQN / the TD3 and SAC critics on a replay batch, its statistics and the gradients w.r.t. the Q-values.
 //   k_ql_*            TQC's quantile-Huber critic loss on a replay batch, its statistics and the gradients w.r.t. the current quantiles.
@@ -431,6 +432,14 @@ __device__ __forceinline__ unsigned long long rb_draw_word(unsigned long long se
     return ((unsigned long long)w0 << 32) | w1;
 }
 
+// the Gaussian draw of a word pair (include/ptg_env.h, ptg_act): Box-Muller's cosine branch on u1 in (0, 1], u2 in [0, 1)
+__device__ __forceinline__ double rb_draw_normal(unsigned long long w)
+{
+    const unsigned w0 = (unsigned)(w >> 32), w1 = (unsigned)w;
+    const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = (double)w1 * 2.3283064365386963e-10;      // 2^-32
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
 struct RbNorm {                          // SB3's _normalize_reward at sample time: column `col` through k_vn_norm's expression
     int col;                             // -1: none
     const double* stats;                 // the handle's {mean, var, count}
@@ -651,11 +660,7 @@ k_act(ActArgs a)
             a.err[5] = 1;
             return;
         }
-        double z = 0.0;
-        if (!det) {
-            const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = (double)w1 * 2.3283064365386963e-10;      // 2^-32
-            z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-        }
+        const double z = det ? 0.0 : rb_draw_normal(((unsigned long long)w0 << 32) | w1);
         const double g = mu + exp(ls) * z;
         double lp = ((-(z * z) / 2.0) - ls) - 0.9189385332046727;
         double x = g;
@@ -784,6 +789,65 @@ __device__ __forceinline__ void pl_block_moments(const LossArgs& a, size_t i, bo
     for (int k = 0; k < PL_WAVES; k++) chan_merge(c, m, M, sh[k * 3 + 0], sh[k * 3 + 1], sh[k * 3 + 2]);
 }
 
+// What a row of either policy loss (this one and the gSDE one below) reads besides its head's own input, and the header's lines that
+// do not depend on the head: they stand here once.
+struct PlIn { double v, adv, ret, old, ov; };        // value, advantage, return, old log-prob (PPO), old value (PTG_LOSS_CLIP_VF)
+
+template <typename IN>
+__device__ __forceinline__ bool pl_load(const LossArgs& a, size_t i, PlIn& x)      // true: one of the five is not finite
+{
+    x.v = (double)((const IN*)a.val)[i * a.v_s];
+    x.adv = (double)((const IN*)a.adv)[i]; x.ret = (double)((const IN*)a.ret)[i];
+    x.old = a.kind == PTG_LOSS_PPO ? (double)((const IN*)a.old_lp)[i] : 0.0;
+    x.ov = (a.flags & PTG_LOSS_CLIP_VF) ? (double)((const IN*)a.old_val)[i] : 0.0;
+    return !pl_finite(x.v) || !pl_finite(x.adv) || !pl_finite(x.ret) || !pl_finite(x.old) || !pl_finite(x.ov);
+}
+
+// PPO's log-ratio and ratio of a row with log-probability lp (A2C: 0 and 1); true: the ratio overflows (Ah * r would be Inf, or NaN where Ah is 0)
+__device__ __forceinline__ bool pl_ratio(const LossArgs& a, const PlIn& x, double lp, double& d, double& r)
+{
+    d = 0.0; r = 1.0;
+    if (a.kind != PTG_LOSS_PPO) return false;
+    d = lp - x.old;
+    r = exp(d);
+    return !pl_finite(r);
+}
+
+// the advantage, PPO / A2C and value lines of a good row: fills surr, q, kl and cf of t, returns the surrogate's derivative g and
+// through gv d loss / d value
+__device__ __forceinline__ double pl_lines(const LossArgs& a, const PlIn& x, double lp, double d, double r, bool norm, double mean, double den,
+                                           PlRow& t, double& gv)
+{
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double ah = norm ? (x.adv - mean) / den : x.adv;
+    double g;
+    if (a.kind == PTG_LOSS_PPO) {
+        const double lo = 1.0 - a.eps, hi = 1.0 + a.eps;
+        const double c = r < lo ? lo : (r > hi ? hi : r);
+        const double t1 = ah * r, t2 = ah * c;
+        t.surr = (t1 != t1 || t2 != t2) ? nan : (t2 < t1 ? t2 : t1);
+        g = (t1 < t2 || (r >= lo && r <= hi)) ? t1 : 0.0;
+        t.kl = (r - 1.0) - d;
+        t.cf = fabs(r - 1.0) > a.eps ? 1.0 : 0.0;
+    } else {
+        t.surr = ah * lp;
+        g = ah;
+    }
+    double vh = x.v;
+    bool pass = true;
+    if (a.flags & PTG_LOSS_CLIP_VF) {
+        const double dv = x.v - x.ov;
+        const double cl = dv < -a.eps_v ? -a.eps_v : (dv > a.eps_v ? a.eps_v : dv);
+        vh = x.ov + cl;
+        pass = dv >= -a.eps_v && dv <= a.eps_v;
+    }
+    const double dq = x.ret - vh;
+    t.q = dq * dq;
+    const double h = pass ? 2.0 * (vh - x.ret) : 0.0;
+    gv = (a.vf_coef * h) / (double)a.B;
+    return g;
+}
+
 // One row: its gradients are stored, its terms returned.  mean / den: the advantage moments in use (den = std + 1e-8).
 template <typename IN>
 __device__ __forceinline__ PlRow pl_row(const LossArgs& a, size_t i, bool norm, double mean, double den)
@@ -791,18 +855,15 @@ __device__ __forceinline__ PlRow pl_row(const LossArgs& a, size_t i, bool norm, 
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
     const PlRow poison{nan, nan, nan, nan, nan, nan};
     const double Bd = (double)a.B;
-    const bool ppo = a.kind == PTG_LOSS_PPO, clipv = (a.flags & PTG_LOSS_CLIP_VF) != 0, cat = a.head == PTG_HEAD_CATEGORICAL;
+    const bool cat = a.head == PTG_HEAD_CATEGORICAL;
     const int A = a.A;
     long long act = 0;
     if (cat) {
         act = a.act_kind == PTG_ACT_I64 ? ((const long long*)a.act)[i] : (long long)((const int*)a.act)[i];
         if (act < 0 || act >= (long long)A) { a.err[4] = 1; return poison; }      // never an address; the row's gradients stay as they were
     }
-    const double v = (double)((const IN*)a.val)[i * a.v_s];
-    const double adv = (double)((const IN*)a.adv)[i], ret = (double)((const IN*)a.ret)[i];
-    const double old = ppo ? (double)((const IN*)a.old_lp)[i] : 0.0;
-    const double ov = clipv ? (double)((const IN*)a.old_val)[i] : 0.0;
-    bool bad = !pl_finite(v) || !pl_finite(adv) || !pl_finite(ret) || !pl_finite(old) || !pl_finite(ov);
+    PlIn x;
+    bool bad = pl_load<IN>(a, i, x);
     IN* const g_row = (IN*)a.g_in + i * a.g_s;
     const IN* __restrict__ row = (const IN*)a.in + i * a.s_n;
     double lp = 0.0, H = 0.0, m = 0.0, s = 1.0, log_s = 0.0, z = 0.0, sigma = 1.0;
@@ -830,20 +891,16 @@ __device__ __forceinline__ PlRow pl_row(const LossArgs& a, size_t i, bool norm, 
             H = -ent;
         }
     } else {
-        const double mu = (double)row[0], ls = (double)((const IN*)a.log_std)[0], x = (double)((const IN*)a.act)[i];
+        const double mu = (double)row[0], ls = (double)((const IN*)a.log_std)[0], smp = (double)((const IN*)a.act)[i];
         bad = bad || !pl_finite(mu) || !(ls <= PL_DBL_MAX);   // NaN or Inf mean; NaN or +Inf log_std
         sigma = exp(ls);
-        z = (x - mu) / sigma;
+        z = (smp - mu) / sigma;
         lp = ((-(z * z) / 2.0) - ls) - 0.9189385332046727;
         H = 1.4189385332046727 + ls;
     }
     bad = bad || !pl_finite(lp);                             // an action of probability 0 (a -Inf logit, a zero sigma), a non-finite sample
-    double d = 0.0, r = 1.0;
-    if (ppo) {
-        d = lp - old;
-        r = exp(d);
-        bad = bad || !pl_finite(r);                          // a ratio that overflows: Ah * r would be Inf, or NaN where Ah is 0
-    }
+    double d, r;
+    bad = pl_ratio(a, x, lp, d, r) || bad;
     IN* const g_v = (IN*)a.g_val + i * a.gv_s;
     if (bad) {
         if (cat) { for (int j = 0; j < A; j++) g_row[j] = (IN)nan; } else g_row[0] = (IN)nan;
@@ -851,33 +908,10 @@ __device__ __forceinline__ PlRow pl_row(const LossArgs& a, size_t i, bool norm, 
         a.err[5] = 1;
         return poison;
     }
-    const double ah = norm ? (adv - mean) / den : adv;
     PlRow t{0.0, 0.0, H, 0.0, 0.0, 0.0};
-    double g;
-    if (ppo) {
-        const double lo = 1.0 - a.eps, hi = 1.0 + a.eps;
-        const double c = r < lo ? lo : (r > hi ? hi : r);
-        const double t1 = ah * r, t2 = ah * c;
-        t.surr = (t1 != t1 || t2 != t2) ? nan : (t2 < t1 ? t2 : t1);
-        g = (t1 < t2 || (r >= lo && r <= hi)) ? t1 : 0.0;
-        t.kl = (r - 1.0) - d;
-        t.cf = fabs(r - 1.0) > a.eps ? 1.0 : 0.0;
-    } else {
-        t.surr = ah * lp;
-        g = ah;
-    }
-    double vh = v;
-    bool pass = true;
-    if (clipv) {
-        const double dv = v - ov;
-        const double cl = dv < -a.eps_v ? -a.eps_v : (dv > a.eps_v ? a.eps_v : dv);
-        vh = ov + cl;
-        pass = dv >= -a.eps_v && dv <= a.eps_v;
-    }
-    const double dq = ret - vh;
-    t.q = dq * dq;
-    const double h = pass ? 2.0 * (vh - ret) : 0.0;
-    g_v[0] = (IN)((a.vf_coef * h) / Bd);
+    double gv;
+    const double g = pl_lines(a, x, lp, d, r, norm, mean, den, t, gv);
+    g_v[0] = (IN)gv;
     if (cat) {
         for (int j = 0; j < A; j++) {
             const double d = (double)row[j] - m;
@@ -1006,6 +1040,252 @@ struct PlFinal {                         // mean and sd once more from the merge
     {
         const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
         pl_finish<IN>(a, v, norm ? a.ws[1] : 0.0, norm ? sqrt(a.ws[2] / ((double)a.B - 1.0)) : 1.0);
+    }
+};
+
+// ================================================================================== gSDE: the state-dependent exploration head and its loss
+// SB3's StateDependentNoiseDistribution with its on-policy defaults (include/ptg_env.h, ptg_sde_*, states the lines;
+// tests/sde_restatement.py restates them in NumPy).  The work is per (row, latent unit), so a row is a WAVE here, not a lane: lane l
+// owns the units k = l, l + 64, ... < L <= 1024, at most SDE_MAX_J = 16 of them, which it keeps in registers between the row's
+// reductions and its gradient pass -- the loops over j are unrolled to NJ = 4 | 8 | 16 (the kernels' template axis), so no register
+// array is indexed dynamically.  A row's loads are 64 consecutive elements per j.  Row sums: the lane's own terms ascending in j from
+// 0.0, then pl_wave_sum.  s_k * s_k never costs an exp per (row, k): the head's workgroup computes it once into LDS and walks its
+// rows, the loss reads it as float64 [L] from the workspace, where a leading kernel left it.
+constexpr int SDE_MAX_J = PTG_MLP_MAX_WIDTH / 64, SDE_WAVES = 4, SDE_BLOCK = 64 * SDE_WAVES;
+constexpr int SDE_MAX_BLOCKS = 1024;     // of the head and of the loss's row kernel: beyond that a wave walks more rows
+
+// rows a wave of the row kernels walks: 1 up to 4 096 rows, so that a small batch spreads over the CUs
+__host__ __device__ __forceinline__ size_t sde_rows_per_wave(size_t rows) { return (rows - 1) / ((size_t)SDE_WAVES * SDE_MAX_BLOCKS) + 1; }
+
+struct SdeNoiseArgs {                    // by value in the launch
+    const void* log_std;
+    void* E; size_t e_s;                 // elements
+    const unsigned long long* counter;
+    unsigned long long seed;
+    long long env_offset;
+    size_t N, rows_per_block;
+    int L;
+    int* err;
+};
+
+// E[e][k] = exp(log_std[k]) * z(seed, c, (global env) * 1024 + k): one wave per 64 columns and run of rows, so that a lane takes
+// its column's exp once and its stores are 64 consecutive elements
+template <typename IN>
+__global__ void __launch_bounds__(64)
+k_sde_resample(SdeNoiseArgs a)
+{
+    const int k = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (k >= a.L) return;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double ls = (double)((const IN*)a.log_std)[k];
+    const bool bad = !(ls <= PL_DBL_MAX);                    // NaN or +Inf
+    if (bad) a.err[5] = 1;
+    const double s = exp(ls);
+    const unsigned long long c = a.counter[0];
+    const size_t e0 = (size_t)blockIdx.y * a.rows_per_block;
+    const size_t e1 = e0 + a.rows_per_block < a.N ? e0 + a.rows_per_block : a.N;
+    IN* const E = (IN*)a.E;
+    for (size_t e = e0; e < e1; e++) {
+        const unsigned long long key = (unsigned long long)(a.env_offset + (long long)e) * (unsigned long long)PTG_MLP_MAX_WIDTH + (unsigned long long)k;
+        const double z = rb_draw_normal(rb_draw_word(a.seed, c, key));
+        E[e * a.e_s + (size_t)k] = (IN)(bad ? nan : s * z);
+    }
+}
+
+struct SdeActArgs {                      // by value in the launch
+    const void* mean; size_t m_s;        // elements
+    const void* lat; size_t lat_s;
+    const void* E; size_t e_s;           // null when deterministic
+    const void* log_std;
+    void *act, *raw, *logp, *ent;
+    double lo, hi;
+    size_t N, rows_per_wave;
+    int L;
+    int* err;
+};
+
+template <typename IN, int NJ>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_act(SdeActArgs a)
+{
+    __shared__ double sh_s2[PTG_MLP_MAX_WIDTH];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, L = a.L;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    int ls_bad = 0;
+    for (int k = threadIdx.x; k < L; k += SDE_BLOCK) {
+        const double ls = (double)((const IN*)a.log_std)[k];
+        ls_bad |= !(ls <= PL_DBL_MAX);                       // NaN or +Inf: every row is bad
+        const double s = exp(ls);
+        sh_s2[k] = s * s;
+    }
+    ls_bad = __syncthreads_or(ls_bad);
+    double s2[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; j++) s2[j] = lane + 64 * j < L ? sh_s2[lane + 64 * j] : 0.0;
+    const IN* const lat = (const IN*)a.lat; const IN* const E = (const IN*)a.E;
+    IN* const raw_o = (IN*)a.raw; IN* const logp_o = (IN*)a.logp; IN* const ent_o = (IN*)a.ent;
+    const size_t base = (size_t)blockIdx.x * (a.rows_per_wave * SDE_WAVES);
+    for (size_t t = 0; t < a.rows_per_wave; t++) {
+        const size_t e = base + t * SDE_WAVES + (size_t)w;
+        if (e >= a.N) break;                                 // wave-uniform: the ragged end
+        double vp = 0.0, np = 0.0;
+        bool h_bad = false;
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int k = lane + 64 * j;
+            if (k < L) {
+                const double h = (double)lat[e * a.lat_s + (size_t)k];
+                h_bad = h_bad || !pl_finite(h);
+                vp += (h * h) * s2[j];
+                if (E) np += h * (double)E[e * a.e_s + (size_t)k];
+            }
+        }
+        const double V = pl_wave_sum(vp) + 1e-6;
+        const double noise = E ? pl_wave_sum(np) : 0.0;
+        const bool bad_lat = __ballot(h_bad) != 0ull;
+        const double mu = (double)((const IN*)a.mean)[e * a.m_s];
+        const bool bad = ls_bad || bad_lat || !pl_finite(mu);
+        const double lsd = log(sqrt(V));
+        const double g = mu + noise;
+        const double x = g < a.lo ? a.lo : (g > a.hi ? a.hi : g);
+        if (lane == 0) {                                     // the row's scalars are the same on every lane; one of them stores
+            ((float*)a.act)[e] = bad ? 0.0f : (float)x;
+            if (raw_o) raw_o[e] = (IN)(bad ? nan : g);
+            if (logp_o) logp_o[e] = (IN)(bad ? nan : (((-(noise * noise)) / (2.0 * V)) - lsd) - 0.9189385332046727);
+            if (ent_o) ent_o[e] = (IN)(bad ? nan : 1.4189385332046727 + lsd);
+            if (bad) a.err[5] = 1;
+        }
+    }
+}
+
+// The loss.  The row kernel reads the latent once: a wave walks its rows ascending (rows base + w, base + w + 4, ...), adds c_i * h_ik^2
+// to its columns' partials in registers, the block's four waves meet in LDS in wave order and the block leaves one [L] partial, which
+// k_sde_cols adds over the blocks ascending.  The five means go the way of every loss here (loss_tail, k_loss_final): a wave's sums
+// sit on its lane 0 with zeroes beside them, so pl_block_sum's tree returns them unchanged.  The block count is given by B alone.
+struct SdeLossArgs {                     // by value in the launch
+    LossArgs l;                          // mean as `in`, the stored samples as `act`, log_std [L]; head, A, act_kind are not read
+    const void* lat; size_t lat_s;       // elements
+    void* g_lat; size_t gl_s;            // null: no latent gradient
+    const double* s2;                    // float64 [L] in the workspace
+    double *row_part, *col_part;         // [nblk][PL_PITCH], [nblk][L]
+    size_t rows_per_wave;
+    int L, nblk;                         // blocks of the row kernel (l.nblk: of the moments)
+};
+
+// the workspace, in doubles: [0..2] merged moments, [4 ..) moment partials [l.nblk][3], s2 [L], row partials [nblk][PL_PITCH], column partials [nblk][L]
+__host__ __device__ __forceinline__ double* sde_s2(const LossArgs& l) { return l.ws + 4 + (size_t)l.nblk * 3; }
+
+template <typename IN>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_s2(const void* log_std, int L, double* s2)
+{
+    const int k = (int)blockIdx.x * SDE_BLOCK + (int)threadIdx.x;
+    if (k >= L) return;
+    const double ls = (double)((const IN*)log_std)[k];
+    const double s = exp(ls);
+    s2[k] = !(ls <= PL_DBL_MAX) ? __longlong_as_double(0x7FF8000000000000ll) : s * s;       // NaN or +Inf: V, and with it every row, is not finite
+}
+
+template <typename IN, int NJ>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_rows(SdeLossArgs a)
+{
+    __shared__ double sh[PL_WAVES * PL_PITCH];
+    __shared__ double sh_col[PTG_MLP_MAX_WIDTH];
+    static_assert(SDE_WAVES == PL_WAVES && SDE_BLOCK == PL_BLOCK, "loss_tail serves a block of PL_WAVES waves");
+    const LossArgs& l = a.l;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, L = a.L;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double Bd = (double)l.B;
+    const bool norm = (l.flags & PTG_LOSS_NORM_ADV) != 0 && l.B > 1;
+    const double mean = norm ? l.ws[1] : 0.0, sd = norm ? sqrt(l.ws[2] / (Bd - 1.0)) : 1.0;
+    double s2[NJ], acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; j++) { s2[j] = lane + 64 * j < L ? a.s2[lane + 64 * j] : 0.0; acc[j] = 0.0; }
+    const IN* const lat = (const IN*)a.lat;
+    IN* const g_lat = (IN*)a.g_lat;
+    PlRow sum{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const size_t base = (size_t)blockIdx.x * (a.rows_per_wave * SDE_WAVES);
+    for (size_t t = 0; t < a.rows_per_wave; t++) {
+        const size_t i = base + t * SDE_WAVES + (size_t)w;
+        if (i >= l.B) break;                                 // wave-uniform: the ragged end
+        double h[NJ], hh[NJ], vp = 0.0;
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int k = lane + 64 * j;
+            h[j] = k < L ? (double)lat[i * a.lat_s + (size_t)k] : 0.0;
+            hh[j] = h[j] * h[j];
+            vp += hh[j] * s2[j];
+        }
+        const double V = pl_wave_sum(vp) + 1e-6;             // a non-finite latent entry or s2 makes it non-finite, whatever meets it
+        // the row's scalars, the same on every lane
+        PlIn x;
+        bool bad = pl_load<IN>(l, i, x);
+        const double mu = (double)((const IN*)l.in)[i * l.s_n], smp = (double)((const IN*)l.act)[i];
+        bad = bad || !pl_finite(mu) || !pl_finite(V);
+        const double lsd = log(sqrt(V));
+        const double dm = smp - mu;
+        const double lp = (((-(dm * dm)) / (2.0 * V)) - lsd) - 0.9189385332046727;
+        bad = bad || !pl_finite(lp);                         // a non-finite sample
+        double d, r;
+        bad = pl_ratio(l, x, lp, d, r) || bad;
+        PlRow tr{nan, nan, nan, nan, nan, 0.0};
+        double g_mu = nan, gv = nan, ci = nan;
+        if (!bad) {
+            tr = PlRow{0.0, 0.0, 1.4189385332046727 + lsd, 0.0, 0.0, 0.0};
+            const double g = pl_lines(l, x, lp, d, r, norm, mean, sd + 1e-8, tr, gv);
+            g_mu = ((-g) * (dm / V)) / Bd;
+            ci = (((-g) * (((dm * dm) / V) - 1.0)) - l.ent_coef) / (2.0 * V);
+        }
+        sum.surr += tr.surr; sum.q += tr.q; sum.H += tr.H; sum.kl += tr.kl; sum.cf += tr.cf;
+        if (lane == 0) {
+            ((IN*)l.g_in)[i * l.g_s] = (IN)g_mu;
+            ((IN*)l.g_val)[i * l.gv_s] = (IN)gv;
+            if (bad) l.err[5] = 1;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int k = lane + 64 * j;
+            acc[j] += ci * hh[j];
+            if (g_lat && k < L) g_lat[i * a.gl_s + (size_t)k] = (IN)(((ci * (2.0 * h[j])) * s2[j]) / Bd);
+        }
+    }
+    // the block's column partial: the waves in wave order
+    for (int q = 0; q < SDE_WAVES; q++) {
+        if (w == q) {
+#pragma unroll
+            for (int j = 0; j < NJ; j++) {
+                const int k = lane + 64 * j;
+                if (k < L) sh_col[k] = q == 0 ? acc[j] : sh_col[k] + acc[j];
+            }
+        }
+        __syncthreads();
+    }
+    for (int k = threadIdx.x; k < L; k += SDE_BLOCK) a.col_part[(size_t)blockIdx.x * (size_t)L + (size_t)k] = sh_col[k];
+    const bool first = lane == 0;
+    double v[PL_TERMS] = {first ? sum.surr : 0.0, first ? sum.q : 0.0, first ? sum.H : 0.0, first ? sum.kl : 0.0, first ? sum.cf : 0.0, 0.0};
+    loss_tail<false>(v, sh, a.row_part, [](const double*) {});
+}
+
+// d loss / d log_std[k] from the blocks' column partials, ascending
+template <typename IN>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_cols(SdeLossArgs a, void* g_ls)
+{
+    const int k = (int)blockIdx.x * SDE_BLOCK + (int)threadIdx.x;
+    if (k >= a.L) return;
+    double s = a.col_part[k];
+    for (int b = 1; b < a.nblk; b++) s += a.col_part[(size_t)b * (size_t)a.L + (size_t)k];
+    ((IN*)g_ls)[k] = (IN)(((2.0 * a.s2[k]) * s) / (double)a.l.B);
+}
+
+template <typename IN>
+struct SdeFinal {                        // the eight statistics; the log_std gradient is k_sde_cols'
+    __device__ void operator()(const SdeLossArgs& a, const double* v) const
+    {
+        LossArgs l = a.l;
+        l.g_ls = nullptr;
+        PlFinal<IN>()(l, v);
     }
 };
 
@@ -1569,10 +1849,7 @@ k_rs_fwd(RsArgs a)
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
     double z = 0.0;
     if (a.counter) {
-        const unsigned long long w = rb_draw_word(a.seed, a.counter[0], (unsigned long long)b);
-        const unsigned w0 = (unsigned)(w >> 32), w1 = (unsigned)w;
-        const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = (double)w1 * 2.3283064365386963e-10;      // 2^-32
-        z = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+        z = rb_draw_normal(rb_draw_word(a.seed, a.counter[0], (unsigned long long)b));
     }
     if (a.noise) a.noise[b] = z;
     const double mu = (double)((const IN*)a.mean)[b * a.m_s];
@@ -1799,6 +2076,35 @@ void launch_loss(hipStream_t st, const A& a, const double* part, void (*one)(A),
     }
     hipLaunchKernelGGL(many, grid, block, 0, st, a);
     hipLaunchKernelGGL((k_loss_final<A, FIN>), dim3(1), block, 0, st, a, part);
+}
+
+// the gSDE row kernels' NJ: the smallest of 4 | 8 | 16 that holds a lane's ceil(L / 64) units
+static int sde_nj(int L) { const int nj = (L + 63) / 64; return nj <= 4 ? 4 : (nj <= 8 ? 8 : SDE_MAX_J); }
+static int64_t sde_loss_blocks(int64_t batch) { return loss_blocks(batch, (int)sde_rows_per_wave((size_t)batch) * SDE_WAVES); }
+
+template <typename IN>
+void launch_sde_act(hipStream_t st, dim3 grid, const SdeActArgs& a)
+{
+    const dim3 block(SDE_BLOCK);
+    switch (sde_nj(a.L)) {
+    case 4: hipLaunchKernelGGL((k_sde_act<IN, 4>), grid, block, 0, st, a); break;
+    case 8: hipLaunchKernelGGL((k_sde_act<IN, 8>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_sde_act<IN, SDE_MAX_J>), grid, block, 0, st, a);
+    }
+}
+
+// the rows, then the five means over the blocks' partials and the log_std gradient over their column partials
+template <typename IN>
+void launch_sde_loss(hipStream_t st, const SdeLossArgs& a, void* g_ls)
+{
+    const dim3 grid((unsigned)a.nblk), block(SDE_BLOCK);
+    switch (sde_nj(a.L)) {
+    case 4: hipLaunchKernelGGL((k_sde_rows<IN, 4>), grid, block, 0, st, a); break;
+    case 8: hipLaunchKernelGGL((k_sde_rows<IN, 8>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_sde_rows<IN, SDE_MAX_J>), grid, block, 0, st, a);
+    }
+    hipLaunchKernelGGL((k_loss_final<SdeLossArgs, SdeFinal<IN>>), dim3(1), dim3(PL_BLOCK), 0, st, a, (const double*)a.row_part);
+    hipLaunchKernelGGL(k_sde_cols<IN>, dim3((unsigned)((a.L - 1) / SDE_BLOCK + 1)), block, 0, st, a, g_ls);
 }
 
 // what ptg_rsample and ptg_rsample_backward refuse alike; the text of the first fault, or null
@@ -2273,6 +2579,118 @@ int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
     if (f64) launch_loss<PlFinal<double>>(st, a, pl_partials(a), k_pl_rows<double, true>, k_pl_rows<double, false>);
     else launch_loss<PlFinal<float>>(st, a, pl_partials(a), k_pl_rows<float, true>, k_pl_rows<float, false>);
     return launch_check(h, "k_pl_rows");
+}
+
+// ---- gSDE: the exploration matrix, the collecting head, the PPO / A2C loss ----------------------------------------------
+static bool sde_dtype_ok(int dt) { return dt == PTG_OUT_F32 || dt == PTG_OUT_F64; }
+static bool sde_width_ok(int L) { return L >= 1 && L <= PTG_MLP_MAX_WIDTH; }
+
+int ptg_sde_resample(ptg_env* h, const ptg_sde_noise* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: null descriptor");
+    if (!sde_dtype_ok(d->in_dtype)) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!sde_width_ok(d->latent_dim)) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: latent_dim %d outside [1, %d]", d->latent_dim, PTG_MLP_MAX_WIDTH);
+    if (!d->log_std_dev || !d->counter_dev || !d->e_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: null log_std_dev, counter_dev or e_dev");
+    if (d->e_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: e_s_n < latent_dim");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    SdeNoiseArgs a{};
+    a.log_std = d->log_std_dev; a.E = d->e_dev; a.e_s = (size_t)d->e_s_n; a.counter = (const unsigned long long*)d->counter_dev;
+    a.seed = (unsigned long long)d->seed; a.env_offset = h->P.env_offset; a.N = (size_t)h->n; a.L = d->latent_dim; a.err = h->P.err;
+    a.rows_per_block = (a.N - 1) / SDE_MAX_BLOCKS + 1;
+    const dim3 grid((unsigned)((a.L + 63) / 64), (unsigned)((a.N - 1) / a.rows_per_block + 1)), block(64);
+    if (d->in_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_sde_resample<double>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_sde_resample<float>, grid, block, 0, st, a);
+    hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)d->counter_dev, 1ull);
+    return launch_check(h, "k_sde_resample");
+}
+
+int ptg_sde_act(ptg_env* h, const ptg_sde_head* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_sde_act: null descriptor");
+    if (d->flags & ~PTG_HEAD_DETERMINISTIC) return set_err(h, PTG_E_INVALID, "ptg_sde_act: unknown flag in %d", d->flags);
+    const bool det = (d->flags & PTG_HEAD_DETERMINISTIC) != 0;
+    if (!sde_dtype_ok(d->in_dtype)) return set_err(h, PTG_E_INVALID, "ptg_sde_act: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!sde_width_ok(d->latent_dim)) return set_err(h, PTG_E_INVALID, "ptg_sde_act: latent_dim %d outside [1, %d]", d->latent_dim, PTG_MLP_MAX_WIDTH);
+    if (d->act_kind != PTG_ACT_F32) return set_err(h, PTG_E_INVALID, "ptg_sde_act: the head writes PTG_ACT_F32 actions");
+    if (!d->mean_dev || !d->latent_dev || !d->log_std_dev || !d->act_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_act: null mean_dev, latent_dev, log_std_dev or act_dev");
+    if (!det && !d->e_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_act: a stochastic head needs e_dev");
+    if (d->mean_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_sde_act: mean_s_n < 1");
+    if (d->latent_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "ptg_sde_act: latent_s_n < latent_dim");
+    if (!det && d->e_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "ptg_sde_act: e_s_n < latent_dim");
+    if (!(d->clip_lo <= d->clip_hi)) return set_err(h, PTG_E_INVALID, "ptg_sde_act: clip_lo > clip_hi (or a NaN bound)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    SdeActArgs a{};
+    a.mean = d->mean_dev; a.m_s = (size_t)d->mean_s_n; a.lat = d->latent_dev; a.lat_s = (size_t)d->latent_s_n;
+    a.E = det ? nullptr : d->e_dev; a.e_s = det ? 0 : (size_t)d->e_s_n; a.log_std = d->log_std_dev;
+    a.act = d->act_dev; a.raw = d->raw_dev; a.logp = d->logp_dev; a.ent = d->ent_dev;
+    a.lo = d->clip_lo; a.hi = d->clip_hi; a.N = (size_t)h->n; a.L = d->latent_dim; a.err = h->P.err;
+    a.rows_per_wave = sde_rows_per_wave(a.N);
+    const dim3 grid((unsigned)((a.N - 1) / (a.rows_per_wave * SDE_WAVES) + 1));
+    if (d->in_dtype == PTG_OUT_F64) launch_sde_act<double>(as_stream(stream), grid, a);
+    else launch_sde_act<float>(as_stream(stream), grid, a);
+    return launch_check(h, "k_sde_act");
+}
+
+int64_t ptg_sde_policy_loss_workspace(int64_t batch, int32_t latent_dim)
+{
+    if (batch < 1 || batch > (int64_t)1 << 31 || !sde_width_ok(latent_dim)) return PTG_E_INVALID;
+    const int64_t nmb = loss_blocks(batch, PL_BLOCK), nblk = sde_loss_blocks(batch);
+    return (4 + nmb * 3 + latent_dim + nblk * latent_dim) * (int64_t)sizeof(double) + loss_partials_bytes(nblk);
+}
+
+int ptg_sde_policy_loss(ptg_env* h, const ptg_sde_loss* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (!d) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: null descriptor");
+    if (d->kind != PTG_LOSS_PPO && d->kind != PTG_LOSS_A2C) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: unknown kind %d", d->kind);
+    if (d->flags & ~(PTG_LOSS_NORM_ADV | PTG_LOSS_CLIP_VF)) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: unknown flag in %d", d->flags);
+    const bool ppo = d->kind == PTG_LOSS_PPO, clipv = (d->flags & PTG_LOSS_CLIP_VF) != 0;
+    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (!sde_dtype_ok(d->in_dtype)) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!sde_width_ok(d->latent_dim)) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: latent_dim %d outside [1, %d]", d->latent_dim, PTG_MLP_MAX_WIDTH);
+    if (!d->mean_dev || !d->val_dev || !d->latent_dev || !d->log_std_dev || !d->act_dev || !d->adv_dev || !d->ret_dev)
+        return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: null means, values, latent, log_std, actions, advantages or returns");
+    if (ppo && !d->old_logp_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: PPO needs old_logp_dev");
+    if (!d->stats_dev || !d->grad_in_dev || !d->grad_val_dev || !d->grad_log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: null stats_dev, grad_in_dev, grad_val_dev or grad_log_std_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: ws_dev is null or not aligned to 8 bytes");
+    if (clipv && !d->old_val_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: PTG_LOSS_CLIP_VF needs old_val_dev");
+    if (d->mean_s_n < 1 || d->g_s_n < 1 || d->val_s_n < 1 || d->gv_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: mean_s_n, g_s_n, val_s_n or gv_s_n < 1");
+    if (d->latent_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: latent_s_n < latent_dim");
+    if (d->grad_latent_dev && d->gl_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: gl_s_n < latent_dim");
+    if (ppo && !(d->clip_range >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: clip_range is negative or NaN");
+    if (clipv && !(d->clip_range_vf >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_sde_policy_loss: clip_range_vf is negative or NaN");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    SdeLossArgs a{};
+    LossArgs& l = a.l;
+    l.in = d->mean_dev; l.s_n = (size_t)d->mean_s_n; l.val = d->val_dev; l.v_s = (size_t)d->val_s_n;
+    l.act = d->act_dev; l.old_lp = d->old_logp_dev; l.adv = d->adv_dev; l.ret = d->ret_dev; l.old_val = d->old_val_dev; l.log_std = d->log_std_dev;
+    l.g_in = d->grad_in_dev; l.g_s = (size_t)d->g_s_n; l.g_val = d->grad_val_dev; l.gv_s = (size_t)d->gv_s_n; l.g_ls = d->grad_log_std_dev;
+    l.stats = d->stats_dev; l.ws = (double*)d->ws_dev;
+    l.eps = d->clip_range; l.eps_v = d->clip_range_vf; l.ent_coef = d->ent_coef; l.vf_coef = d->vf_coef;
+    l.B = (size_t)d->batch; l.kind = d->kind; l.head = PTG_HEAD_GAUSSIAN; l.flags = d->flags;
+    l.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
+    l.err = h->P.err;
+    a.lat = d->latent_dev; a.lat_s = (size_t)d->latent_s_n; a.g_lat = d->grad_latent_dev; a.gl_s = (size_t)d->gl_s_n;
+    a.L = d->latent_dim; a.nblk = (int)sde_loss_blocks(d->batch); a.rows_per_wave = sde_rows_per_wave(l.B);
+    double* const s2 = sde_s2(l);
+    a.s2 = s2; a.row_part = s2 + a.L; a.col_part = a.row_part + (size_t)a.nblk * PL_PITCH;
+    const bool f64 = d->in_dtype == PTG_OUT_F64, norm = (d->flags & PTG_LOSS_NORM_ADV) != 0 && d->batch > 1;
+    const dim3 block(SDE_BLOCK), cols((unsigned)((a.L - 1) / SDE_BLOCK + 1));
+    if (f64) hipLaunchKernelGGL(k_sde_s2<double>, cols, block, 0, st, d->log_std_dev, a.L, s2);
+    else hipLaunchKernelGGL(k_sde_s2<float>, cols, block, 0, st, d->log_std_dev, a.L, s2);
+    if (norm) {
+        const dim3 grid((unsigned)l.nblk);
+        if (f64) hipLaunchKernelGGL(k_pl_moments<double>, grid, dim3(PL_BLOCK), 0, st, l);
+        else hipLaunchKernelGGL(k_pl_moments<float>, grid, dim3(PL_BLOCK), 0, st, l);
+        hipLaunchKernelGGL(k_vn_merge, dim3(1), dim3(64), 0, st, (const double*)(l.ws + 4), l.nblk, l.ws);
+    }
+    if (f64) launch_sde_loss<double>(st, a, d->grad_log_std_dev);
+    else launch_sde_loss<float>(st, a, d->grad_log_std_dev);
+    return launch_check(h, "k_sde_rows");
 }
 
 // ---- the optimiser step: grad-norm clip, Adam / RMSprop, Polyak and zero_grad for all tensors of an optimiser -----------

@@ -1,4 +1,5 @@
 """ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd;
+ppo_sde_loss / a2c_sde_loss: the same for a policy with gSDE (HipEngine.sde_policy_loss, ptg_sde_policy_loss);
 dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise, and tqc_critic_loss: TQC's
 quantile-Huber critic loss (HipEngine.quantile_loss, ptg_quantile_loss); squashed_rsample (HipEngine.rsample / rsample_backward,
 ptg_rsample) and sac_actor_loss / tqc_actor_loss / td3_actor_loss / ent_coef_loss (HipEngine.actor_loss, ptg_actor_loss): the actor
@@ -60,6 +61,48 @@ def a2c_loss(engine, head_input, values, actions, advantages, returns, *, ent_co
     """SB3's A2C.train loss of its one batch -> (loss, stats) as ppo_loss gives them (approx_kl and clip_fraction are 0)."""
     kw = dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, out=out, workspace=workspace)
     return _call("a2c", engine, head_input, values, actions, None, advantages, returns, None, log_std, kw)
+
+
+# ------------------------------------------------------------------------------------------------- the on-policy losses with gSDE
+#     out = net(obs)                                            # TrainMLP: [B, 2], the mean and a value column
+#     latent = net.hidden[-1]                                   # [B, L]: data, as under SB3's learn_features=False
+#     loss, stats = ppo_sde_loss(engine, out[:, 0], out[:, 1], latent, log_std, actions, old_log_prob, advantages, returns, clip_range=0.2)
+#     loss.backward()                                           # fills the network's gradients and log_std.grad
+# The gradient reaches the latent only when it requires grad (learn_features=True); then the kernel writes d loss / d latent too.
+class _SdePolicyLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, engine, kind, mean, values, latent, log_std, actions, old_log_prob, advantages, returns, old_values, kw):
+        res = engine.sde_policy_loss(kind, mean.detach(), values.detach(), latent.detach(), log_std.detach(), actions, old_log_prob, advantages, returns,
+                                     old_values=old_values, want_grad_latent=latent.requires_grad, **kw)
+        ctx.res = res
+        ctx.shapes = (mean.shape, values.shape, latent.shape, log_std.shape)
+        ctx.mark_non_differentiable(res.stats)
+        return res.stats[0].to(mean.dtype, copy=True), res.stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        res, (s_mu, s_val, s_lat, s_ls) = ctx.res, ctx.shapes
+        g_lat = None if res.grad_latent is None else (res.grad_latent * grad_loss).reshape(s_lat)
+        return (None, None, (res.grad_input * grad_loss).reshape(s_mu), (res.grad_values * grad_loss).reshape(s_val), g_lat,
+                (res.grad_log_std * grad_loss).reshape(s_ls), None, None, None, None, None, None)
+
+
+def ppo_sde_loss(engine, mean, values, latent, log_std, actions, old_log_prob, advantages, returns, *, clip_range, clip_range_vf=None, ent_coef=0.0,
+                 vf_coef=0.5, normalize_advantage=True, old_values=None, out=None, workspace=None):
+    """ppo_loss for a policy with gSDE (SB3's use_sde=True): SB3's PPO.train loss of one minibatch on StateDependentNoiseDistribution
+    -> (loss, stats) as ppo_loss gives them.  mean [B] / [B, 1], values [B], latent [B, L] the policy's last hidden layer, log_std the
+    [L] / [L, 1] parameter, actions the stored raw samples.  Gradients go to mean, values and log_std, and to latent when it requires
+    grad.  Arguments as HipEngine.sde_policy_loss."""
+    kw = dict(clip_range=clip_range, clip_range_vf=clip_range_vf, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage,
+              out=out, workspace=workspace)
+    return _SdePolicyLossFn.apply(engine, "ppo", mean, values, latent, log_std, actions, old_log_prob, advantages, returns, old_values, kw)
+
+
+def a2c_sde_loss(engine, mean, values, latent, log_std, actions, advantages, returns, *, ent_coef=0.0, vf_coef=0.5, normalize_advantage=False, out=None,
+                 workspace=None):
+    """a2c_loss for a policy with gSDE -> (loss, stats) as ppo_sde_loss gives them (approx_kl and clip_fraction are 0)."""
+    kw = dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, out=out, workspace=workspace)
+    return _SdePolicyLossFn.apply(engine, "a2c", mean, values, latent, log_std, actions, None, advantages, returns, None, kw)
 
 
 # ------------------------------------------------------------------------------------------------- the off-policy losses

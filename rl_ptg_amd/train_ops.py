@@ -1,5 +1,5 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the forward and backward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+action heads, the policy loss, gSDE's matrix, head and loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the forward and backward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward and mlp_backward); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
@@ -26,6 +26,10 @@ EpsGreedyAct = collections.namedtuple("EpsGreedyAct", "actions")
 GaussianAct = collections.namedtuple("GaussianAct", "actions raw log_prob entropy")
 # what policy_loss returns: stats float64 [8], the gradients w.r.t. the head's input, the values and (Gaussian head) log_std
 PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values grad_log_std")
+# what sde_act returns (GaussianAct's fields) and what sde_policy_loss returns: PolicyLoss's fields with grad_log_std [L], then the
+# gradient w.r.t. the latent [B, L] (None when not asked for)
+SdeAct = collections.namedtuple("SdeAct", "actions raw log_prob entropy")
+SdePolicyLoss = collections.namedtuple("SdePolicyLoss", "stats grad_input grad_values grad_log_std grad_latent")
 # what td_loss returns: stats float64 [8], the gradients w.r.t. the current Q-values (DQN: one tensor [B, A]; critics: a list of K tensors
 # shaped like q[k]) and the TD target [B] (None when not asked for)
 TdLoss = collections.namedtuple("TdLoss", "stats grad_q target")
@@ -58,6 +62,11 @@ def contiguous(x):
 def rows(x):
     """[B, A] logits, possibly a column slice of a wider tensor"""
     return None if x.stride(1) == 1 and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1]) else "unit column stride and a row stride >= A"
+
+
+def wide_rows(x):
+    """[B, L] latent rows or an exploration matrix, possibly the padded hidden layer of an MLP workspace"""
+    return None if (x.shape[1] <= 1 or x.stride(1) == 1) and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1]) else "unit column stride and a row stride >= L"
 
 
 def step(x):
@@ -795,6 +804,156 @@ class TrainOps:
                          grad_log_std_dev=_ptr(g_ls if gauss else None), ws_dev=_ptr(workspace))
         self._call("ptg_policy_loss", C.byref(d))
         return PolicyLoss(stats, g_in, g_val, g_ls)
+
+    # ------------------------------------------------------------------ gSDE: the exploration matrix, the collecting head, its loss
+    def _sde_log_std(self, who, log_std, dtypes, L=None):
+        """log_std [L] or [L, 1] contiguous (SB3's parameter with the env's one action dimension) -> (the checked tensor, L)"""
+        if _dims(self, log_std) == 2 and log_std.shape[1] == 1:
+            log_std = log_std[:, 0]
+        check(self, who, "log_std", log_std, dtypes=dtypes, shape=(L,), rule=contiguous)
+        if not 1 <= log_std.shape[0] <= _lib.MLP_MAX_WIDTH:
+            raise ValueError(f"{who}: log_std must have 1 to {_lib.MLP_MAX_WIDTH} entries, got shape {tuple(log_std.shape)}")
+        return log_std, log_std.shape[0]
+
+    def sde_resample(self, log_std, counter, noise, seed=0):
+        """Enqueue SB3's StateDependentNoiseDistribution.sample_weights on the current stream (include/ptg_env.h: ptg_sde_resample):
+        noise [N, L] (log_std's dtype, unit column stride, row stride >= L) is filled with exp(log_std[k]) * z, z the draw of
+        (seed, *counter, (global env offset + e) * 1024 + k); counter: new_draw_counter(), advanced by one on the device.  log_std [L]
+        or [L, 1], float32 or float64, read when the kernel runs.  Returns noise.  A NaN or +Inf log_std entry makes its column NaN and
+        the next sync() raise PtgError with code PTG_E_NONFINITE."""
+        torch = self._torch
+        who = "sde_resample"
+        log_std, L = self._sde_log_std(who, log_std, (torch.float32, torch.float64))
+        check(self, who, "counter (new_draw_counter())", counter, dtypes=(torch.int64,), numel=1, shape=(1,))
+        check(self, who, "noise", noise, dtypes=(log_std.dtype,), shape=(self.n, L), rule=wide_rows, exc=ValueError)
+        d = _lib.PtgSdeNoise(in_dtype=_out_code(torch, log_std.dtype), latent_dim=L, log_std_dev=_ptr(log_std), seed=int(seed) & (2 ** 64 - 1),
+                             counter_dev=_ptr(counter), e_dev=_ptr(noise), e_s_n=_row_stride(noise))
+        self._call("ptg_sde_resample", C.byref(d))
+        return noise
+
+    def sde_act_outputs(self, dtype):
+        """fresh outputs of sde_act for its out=: what a captured collect step writes on every replay"""
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            return SdeAct(torch.zeros(self.n, dtype=torch.float32, device=self.device), *[torch.zeros(self.n, dtype=dtype, device=self.device) for _ in range(3)])
+
+    def sde_act(self, mean, latent, log_std, noise, clip=(-1.0, 1.0), deterministic=False, out=None, want_raw=True, want_logp=True, want_entropy=True):
+        """gSDE's collecting head in one launch (include/ptg_env.h: ptg_sde_act): g = mean + latent . noise row by row, the variance
+        (latent^2) . exp(log_std)^2 + 1e-6; deterministic: g = mean and noise may be None.  mean [N] / [N, 1] (any stride >= 1),
+        latent [N, L] and noise [N, L] (unit column stride, row stride >= L: the kept hidden layer of an MLP forward is taken in place),
+        log_std [L] / [L, 1], all of ONE dtype, float32 or float64.  Returns SdeAct(actions float32 [N] clipped for step(), raw = g (what
+        an on-policy buffer stores), log_prob, entropy).  A non-finite mean or latent entry, or a NaN / +Inf log_std, gives action 0,
+        NaN outputs and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "sde_act"
+        _, s_n = self._act_input(who, mean, "mean", False)
+        m1 = mean[:, 0] if mean.dim() == 2 else mean
+        dt = (mean.dtype,)
+        log_std, L = self._sde_log_std(who, log_std, dt)
+        check(self, who, "latent", latent, dtypes=dt, shape=(self.n, L), rule=wide_rows)
+        if noise is None and not deterministic:
+            raise ValueError(f"{who}: a stochastic head needs the exploration matrix (sde_resample)")
+        check(self, who, "noise", noise, dtypes=dt, shape=(self.n, L), rule=wide_rows, optional=True)
+        lo, hi = float(clip[0]), float(clip[1])
+        if not lo <= hi:
+            raise ValueError(f"{who}: clip {clip} is not an interval")
+        res = self._act_outputs(who, SdeAct, out, [("actions", True, torch.float32), ("raw", want_raw, mean.dtype), ("log_prob", want_logp, mean.dtype),
+                                                   ("entropy", want_entropy, mean.dtype)])
+        stochastic = not deterministic
+        d = _lib.PtgSdeHead(flags=_lib.HEAD_DETERMINISTIC if deterministic else 0, in_dtype=_out_code(torch, mean.dtype), latent_dim=L,
+                            act_kind=_lib.ACT_F32, mean_dev=_ptr(m1), mean_s_n=s_n, latent_dev=_ptr(latent), latent_s_n=_row_stride(latent),
+                            e_dev=_ptr(noise if stochastic else None), e_s_n=_row_stride(noise) if stochastic else 0, log_std_dev=_ptr(log_std),
+                            clip_lo=lo, clip_hi=hi, act_dev=_ptr(res.actions), raw_dev=_ptr(res.raw), logp_dev=_ptr(res.log_prob), ent_dev=_ptr(res.entropy))
+        self._call("ptg_sde_act", C.byref(d))
+        return res
+
+    @staticmethod
+    def sde_policy_loss_workspace_bytes(batch, latent_dim):
+        """ptg_sde_policy_loss_workspace restated: 8 * (4 + 3 m + L + n * (8 + L)) with m blocks of 256 rows for the advantage moments
+        and n blocks of 4 * ceil(B / 4096) rows for the row kernel; -1 outside the ranges the library accepts"""
+        B, L = int(batch), int(latent_dim)
+        if not (1 <= B <= 2 ** 31 and 1 <= L <= _lib.MLP_MAX_WIDTH):
+            return -1
+        per = 4 * ((B - 1) // 4096 + 1)
+        return 8 * (4 + 3 * ((B - 1) // 256 + 1) + L + ((B - 1) // per + 1) * (8 + L))
+
+    def sde_policy_loss_workspace(self, batch, latent_dim):
+        """the device scratch of sde_policy_loss for a batch of this size and latent width (a uint8 tensor)"""
+        nbytes = self._L.ptg_sde_policy_loss_workspace(int(batch), int(latent_dim))
+        if nbytes < 0:
+            raise ValueError(f"sde_policy_loss_workspace: batch must be in [1, 2^31] and latent_dim in [1, {_lib.MLP_MAX_WIDTH}], got {batch}, {latent_dim}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def sde_policy_loss(self, kind, mean, values, latent, log_std, actions, old_log_prob, advantages, returns, *, clip_range=None, clip_range_vf=None,
+                        ent_coef=0.0, vf_coef=0.5, normalize_advantage=None, old_values=None, want_grad_latent=False, out=None, workspace=None):
+        """policy_loss for gSDE's head (include/ptg_env.h: ptg_sde_policy_loss): SB3's evaluate_actions on
+        StateDependentNoiseDistribution and the loss lines of PPO.train ("ppo") / A2C.train ("a2c") with their gradients.  mean [B] /
+        [B, 1] and values [B] (any stride >= 1), latent [B, L] (unit column stride, row stride >= L), log_std [L] / [L, 1], actions [B]
+        the stored raw samples; the other arguments as policy_loss takes them; every float tensor of ONE dtype.  Returns
+        SdePolicyLoss(stats float64 [8] as policy_loss gives them, grad_input = d loss / d mean shaped like mean, grad_values [B],
+        grad_log_std [L], grad_latent [B, L] with want_grad_latent (SB3's learn_features=True) else None).  out: an earlier result,
+        reused by a captured call (its grad_latent decides whether that gradient is written); workspace:
+        sde_policy_loss_workspace(B, L) or larger.  No synchronisation; a bad row makes the next sync() raise PtgError."""
+        torch = self._torch
+        who = "sde_policy_loss"
+        if kind not in ("ppo", "a2c"):
+            raise ValueError(f"{who}: kind must be 'ppo' or 'a2c', got {kind!r}")
+        ppo = kind == "ppo"
+        x = check(self, who, "mean", _column(self, mean), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
+        (B,) = x.shape
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch, mean has shape {tuple(mean.shape)}")
+        dt = (x.dtype,)
+        log_std, L = self._sde_log_std(who, log_std, dt)
+        check(self, who, "latent", latent, dtypes=dt, shape=(B, L), rule=wide_rows)
+        values = check(self, who, "values", _column(self, values), dtypes=dt, shape=(B,), rule=step)
+        if clip_range_vf is not None and old_values is None:
+            raise ValueError(f"{who}: clip_range_vf needs old_values")
+        if ppo and old_log_prob is None:
+            raise ValueError(f"{who}: PPO needs old_log_prob")
+        cols = [("actions (the raw samples)", actions), ("advantages", advantages), ("returns", returns)] + ([("old_log_prob", old_log_prob)] if ppo else [])
+        for name, c in cols + ([("old_values", old_values)] if clip_range_vf is not None else []):
+            check(self, who, name, c, dtypes=dt, shape=(B,), rule=contiguous)
+        if ppo:
+            if clip_range is None or not float(clip_range) >= 0.0:
+                raise ValueError(f"{who}: PPO needs a clip_range >= 0, got {clip_range}")
+        if clip_range_vf is not None and not float(clip_range_vf) >= 0.0:
+            raise ValueError(f"{who}: clip_range_vf must be >= 0 (or None), got {clip_range_vf}")
+        if normalize_advantage is None:
+            normalize_advantage = ppo
+        if out is not None:
+            stats, g_in, g_val, g_ls, g_lat = _out_tuple(self, who, out, SdePolicyLoss)
+            g_in = check(self, who, "out.grad_input", _column(self, g_in), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            check(self, who, "out.grad_values", g_val, dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            check(self, who, "out.grad_log_std", g_ls, dtypes=dt, shape=(L,), rule=contiguous, exc=ValueError)
+            check(self, who, "out.grad_latent", g_lat, dtypes=dt, shape=(B, L), rule=wide_rows, optional=True, exc=ValueError)
+        if workspace is not None:
+            need = self.sde_policy_loss_workspace_bytes(B, L)
+            check(self, who, f"workspace (sde_policy_loss_workspace({B}, {L}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
+            if workspace.numel() < need:
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} at latent width {L} needs {need}")
+        else:
+            workspace = self.sde_policy_loss_workspace(B, L)
+        if out is None:
+            with torch.cuda.device(self.device):
+                stats = torch.empty(8, dtype=torch.float64, device=self.device)
+                g_in = torch.empty(B, dtype=x.dtype, device=self.device)
+                g_val = torch.empty(B, dtype=x.dtype, device=self.device)
+                g_ls = torch.empty(L, dtype=x.dtype, device=self.device)
+                g_lat = torch.empty((B, L), dtype=x.dtype, device=self.device) if want_grad_latent else None
+        d = _lib.PtgSdeLoss(kind=_lib.LOSS_PPO if ppo else _lib.LOSS_A2C,
+                            flags=(_lib.LOSS_NORM_ADV if normalize_advantage else 0) | (_lib.LOSS_CLIP_VF if clip_range_vf is not None else 0),
+                            in_dtype=_out_code(torch, x.dtype), latent_dim=L, batch=B, mean_dev=_ptr(x), mean_s_n=max(x.stride(0), 1),
+                            val_dev=_ptr(values), val_s_n=max(values.stride(0), 1), latent_dev=_ptr(latent), latent_s_n=_row_stride(latent),
+                            log_std_dev=_ptr(log_std), act_dev=_ptr(actions), old_logp_dev=_ptr(old_log_prob if ppo else None), adv_dev=_ptr(advantages),
+                            ret_dev=_ptr(returns), old_val_dev=_ptr(old_values if clip_range_vf is not None else None),
+                            clip_range=float(clip_range) if ppo else 0.0, clip_range_vf=float(clip_range_vf) if clip_range_vf is not None else 0.0,
+                            ent_coef=float(ent_coef), vf_coef=float(vf_coef), stats_dev=_ptr(stats), grad_in_dev=_ptr(g_in), g_s_n=max(g_in.stride(0), 1),
+                            grad_val_dev=_ptr(g_val), gv_s_n=max(g_val.stride(0), 1), grad_log_std_dev=_ptr(g_ls), grad_latent_dev=_ptr(g_lat),
+                            gl_s_n=0 if g_lat is None else _row_stride(g_lat), ws_dev=_ptr(workspace))
+        self._call("ptg_sde_policy_loss", C.byref(d))
+        return SdePolicyLoss(stats, g_in, g_val, g_ls, g_lat)
 
     # ------------------------------------------------------------------ the TD loss of a replay batch and its gradients
     def td_loss_workspace(self, batch):
