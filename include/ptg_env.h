@@ -51,7 +51,9 @@ extern "C" {
                              *     (up to eight MLPs of equal depth in the launches of one); + ptg_rollout_buffer, ptg_rollout_buffer_begin, ptg_rollout_buffer_add
                              *     (the on-policy algorithms' collect storage with its cursor on the device); + ptg_sde_noise, ptg_sde_head, ptg_sde_loss, ptg_sde_resample,
                              *     ptg_sde_act, ptg_sde_policy_loss, ptg_sde_policy_loss_workspace (gSDE: the state-dependent exploration head while
-                             *     collecting and its PPO / A2C loss); no earlier declaration changed */
+                             *     collecting and its PPO / A2C loss); + ptg_sde_rs, ptg_sde_resample_rows, ptg_sde_rsample,
+                             *     ptg_sde_rsample_backward, ptg_sde_rsample_backward_workspace (gSDE for SAC / TQC: the squashed head, its reparametrised sample and the
+                             *     backward); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -758,8 +760,9 @@ int ptg_policy_loss(ptg_env* env, const ptg_loss* d, void* stream);
  * [L, 1], an exploration matrix is one [L] row per env.  L = latent_dim is the width of the policy's last hidden layer,
  * 1 <= L <= PTG_MLP_MAX_WIDTH (1024); the latent rows are what a PTG_MLP_KEEP_HIDDEN forward leaves in its workspace, whose rows are
  * padded to 16 bytes, so every [.][L] array here has a row stride >= L.
- * Out of scope: SAC / TQC with gSDE (squashing, clip_mean, learn_features=True, reset_noise per gradient step); use_expln;
- * full_std=False; D > 1; fusing the head into the network's last layer.  sde_sample_freq is the caller's schedule of ptg_sde_resample.
+ * Out of scope: use_expln; full_std=False; D > 1; fusing the head into the network's last layer.  sde_sample_freq is the caller's
+ * schedule of ptg_sde_resample.  SAC / TQC with gSDE (squashing, clip_mean, learn_features=True, reset_noise per gradient step) has
+ * ops of its own: ptg_sde_resample_rows / ptg_sde_rsample / ptg_sde_rsample_backward, behind ptg_sde_policy_loss.
  * Arithmetic, all three ops: float64 whatever in_dtype is, every operation rounded once (no fused multiply-add), results rounded once
  * on the store; exp, log, sqrt, cos are the double-precision library functions.  s_k = exp((double)log_std[k]); h_k a latent entry.
  * Sums over k run in an order given by L alone: unit k belongs to lane k mod 64, a lane adds its terms ascending in k from 0.0, the 64
@@ -876,6 +879,114 @@ typedef struct ptg_sde_loss {
 } ptg_sde_loss;
 int64_t ptg_sde_policy_loss_workspace(int64_t batch, int32_t latent_dim);
 int ptg_sde_policy_loss(ptg_env* env, const ptg_sde_loss* d, void* stream);
+
+/* ---- gSDE for SAC and TQC: the squashed head, its reparametrised sample and the backward --------------------------------------
+ * Replaces what SB3 2.0.0a13 runs for `gSDE : True` under SAC and TQC: sac/policies.py::Actor with use_sde builds
+ * StateDependentNoiseDistribution(1, full_std=True, use_expln=False, learn_features=True, squash_output=True); log_std is [L, 1],
+ * initialised at -3 and NOT clamped; mu = Sequential(Linear(L, 1), Hardtanh(-clip_mean, clip_mean)), clip_mean = 2.0; the latent is
+ * the trunk's output, behind its activation.  Actor.action_log_prob (proba_distribution, sample, tanh, log_prob with the
+ * log(1 - a^2 + 1e-6) correction) runs two or three times on every gradient step, and autograd walks back over it into the mean,
+ * into the latent (through the variance and through the noise) and into log_std (through the variance and through the resampled
+ * matrix itself, which is weights_dist.rsample()).  SAC.train / TQC.train call actor.reset_noise() (batch_size = 1) once per gradient
+ * step: ONE [L] row serves the whole batch, the actor's pass over the observations and the target's pass over the next
+ * observations alike.  While collecting, reset_noise(n_envs) gives one row per env; no log-prob, no gradient.
+ * D = 1, 1 <= L <= 1024, strides and the arithmetic rules (float64, one rounding per operation, the order of the sums over k) as
+ * stated above for the on-policy ops; tanh is the double-precision library function.  s_k = exp((double)log_std[k]), h_ik a latent entry.
+ * Out of scope: use_expln; full_std=False; D > 1; sde_sample_freq as anything but the caller's schedule of the resample calls.
+ *
+ * ptg_sde_resample_rows is the training matrix: `rows` >= 1 rows of [L] at e_dev with the row stride e_s_n, E[r][k] = s_k * z, z
+ * ptg_act's Gaussian draw from the words of ptg_replay_sample's chain keyed (seed, c, r * 1024 + k), c = *counter_dev -- NO global
+ * env offset and no reading of n_envs: a row is a batch row, as in ptg_rsample.  Everything else (the descriptor, the trailing
+ * one-thread kernel that does *counter_dev += 1, a NaN or +Inf log_std[k] making column k NaN and PTG_E_NONFINITE at the next
+ * ptg_sync, two launches) is ptg_sde_resample's.  At global env offset 0 the first n_envs rows' keys are ptg_sde_resample's, so a
+ * caller that holds both matrices keeps the streams apart: rl_ptg_amd.SquashedSdeNoise gives the training row a counter of its own
+ * and the seed (seed XOR 0x9E3779B97F4A7C15).
+ * PTG_E_INVALID (nothing enqueued): ptg_sde_resample's list, and rows outside [1, 2^31].
+ *
+ * ptg_sde_rsample is the forward, one launch; ptg_sde_rsample_backward the backward.  Both read a ptg_sde_rs, B = batch:
+ *   flags         PTG_SDE_RS_DETERMINISTIC: noise = 0, e_dev is neither read nor required.  PTG_SDE_RS_SHARED_E: e_dev is ONE [L]
+ *                 row for all B rows (training; e_s_n is not read); without it e_dev is [B][L], element (i, k) at i * e_s_n + k
+ *                 (collecting: B is the matrix's row count)
+ *   in_dtype      PTG_OUT_F32 | PTG_OUT_F64: of mean, latent, E, log_std, act, logp and of every gradient tensor
+ *   batch         B >= 1, a 64-bit count that is not tied to the handle's n_envs; at most 2^31
+ *   mean_dev      [B], element i at i * mean_s_n >= 1: the UNCLIPPED output of Linear(L, 1)
+ *   latent_dev    [B][L], element (i, k) at i * latent_s_n + k, latent_s_n >= L;   log_std_dev [L] contiguous
+ *   clip_mean     c, a host double: > 0 applies the Hardtanh, +Inf switches it off; <= 0 or NaN is refused
+ *   act_dev       [B] contiguous in in_dtype: a = tanh(g)
+ *   step_act_dev  float32 [B] contiguous, nullable: a rounded to float32, what ptg_step takes when in_dtype is float64 (0 on a bad row)
+ *   logp_dev      [B] contiguous in in_dtype, nullable
+ *   saved_dev     float64 [B][2] contiguous, 8-byte aligned: (noise, V) of row i at 2 i and 2 i + 1; nullable in the forward, which
+ *                 writes it; the backward reads and requires it
+ *   grad_act_dev, grad_logp_dev   backward inputs, [B] contiguous in in_dtype: d loss / d act and d loss / d logp; each nullable (= 0), not both
+ *   grad_mean_dev [B], element i at i * gm_s_n >= 1, required: the gradient with respect to the unclipped mean
+ *   grad_latent_dev   [B][L] with the row stride gl_s_n >= L, nullable
+ *   grad_log_std_dev  [L] contiguous in in_dtype, nullable; refused without PTG_SDE_RS_SHARED_E (a collecting matrix has no backward)
+ *   ws_dev        backward only: caller-owned device scratch, 8-byte aligned, at least ptg_sde_rsample_backward_workspace(batch,
+ *                 latent_dim) bytes
+ * Forward, row i, mu = mean[i], E_k the shared row's or row i's entry:
+ *   m = mu < -c ? -c : (mu > c ? c : mu)
+ *   V = (sum_k (h_ik * h_ik) * (s_k * s_k)) + 1e-6;   noise = sum_k h_ik * E_k  (deterministic: 0);   sd = sqrt(V);   lsd = log(sd)
+ *   g = m + noise;   a = tanh(g);   act = a
+ *   logp = ((((-(noise * noise)) / (2 * V)) - lsd) - 0.9189385332046727) - log((1 - a * a) + 1e-6)
+ * With PTG_SDE_RS_SHARED_E the forward gives the bits of the per-row call on B copies of the row.
+ * Backward, row i: ga = grad_act[i], gl = grad_logp[i] (0 when NULL); (noise, V) = saved[i]; m, g, a recomputed as above;
+ *   d = 1 - a * a;   q = ((2 * a) * d) / (d + 1e-6);   t = ga * d + gl * q
+ *   grad_mean = (-c < mu && mu < c) ? t : 0                 (torch's Hardtanh backward: exclusive at both ends)
+ *   n = t - gl * (noise / V);   cV = (gl * (((noise * noise) / V) - 1)) / (2 * V)
+ *   grad_latent[i][k] = (n * E_k) + ((cV * (2 * h_ik)) * (s_k * s_k))          (deterministic: E_k = 0)
+ *   grad_log_std[k] = sum_i h_ik * grad_latent[i][k]        (the variance path 2 s_k^2 sum_i cV h_ik^2 and the matrix path
+ *                     E_k sum_i n h_ik in one sum; computed whether or not grad_latent_dev is stored)
+ * The batch sum runs in ptg_sde_policy_loss's order, given by (B, L) alone, with no floating-point atomics: R = ceil(B / 4096) rows
+ * per wave, block b of 4 waves owns rows [4 R b, 4 R (b + 1)); wave w adds rows 4 R b + w, 4 R b + w + 4, ... ascending from 0.0, then
+ * the block's waves in wave order, then the blocks ascending.
+ * Known differences from SB3.  (1) SB3's log_prob(actions) recovers g as atanh(clamp(tanh(g), +-(1 - eps))), eps float32's; this op
+ * uses g itself -- identical in exact arithmetic while the clamp is inactive; where the clamp saturates, SB3's gradient through the
+ * action is zero and this one is not.  (2) Everything is float64, where SB3 computes in float32 and draws with torch's generator
+ * (ptg_rsample's note).
+ * Bad rows: a row whose mean, any latent entry, V or noise (backward: a saved value or an incoming gradient) is not finite, and every
+ * row when any log_std is NaN or +Inf.  A bad row gets NaN in act, logp, grad_mean and its grad_latent row, 0 in step_act, and makes
+ * every entry of grad_log_std NaN; the other rows keep their bits; the next ptg_sync returns PTG_E_NONFINITE once.  An exactly
+ * saturated row (a = +-1, d = 0) is legal: q = 0 and logp is finite.
+ * Enqueues kernels only -- the forward one (a wave per row, s_k * s_k once per workgroup in LDS), the backward s_k * s_k into the
+ * workspace, the rows, and with grad_log_std_dev the sum over the blocks' column partials -- no host synchronisation, no allocation;
+ * capturable.  Reads nothing of the handle but its device.
+ * PTG_E_INVALID (nothing enqueued): NULL handle, descriptor, mean_dev, latent_dev or log_std_dev; NULL e_dev unless deterministic; an
+ * unknown flag; an in_dtype other than the two; latent_dim outside [1, 1024]; batch outside [1, 2^31]; mean_s_n < 1; latent_s_n <
+ * latent_dim; e_s_n < latent_dim (stochastic, without PTG_SDE_RS_SHARED_E); a clip_mean that is <= 0 or NaN; a saved_dev that is not
+ * 8-byte aligned; forward: NULL act_dev; backward: NULL saved_dev, grad_mean_dev or ws_dev (or a ws_dev that is not 8-byte aligned),
+ * both incoming gradients NULL, gm_s_n < 1, gl_s_n < latent_dim with grad_latent_dev, grad_log_std_dev without PTG_SDE_RS_SHARED_E.
+ * ptg_sde_rsample_backward_workspace(batch, latent_dim): bytes of scratch; with n = ceil(B / (4 R)) blocks it is 8 * L * (1 + n);
+ * negative for a batch outside [1, 2^31] or a latent_dim outside [1, 1024]. */
+enum { PTG_SDE_RS_DETERMINISTIC = 1, PTG_SDE_RS_SHARED_E = 2 };
+typedef struct ptg_sde_rs {
+    int32_t flags, in_dtype;
+    int32_t latent_dim, reserved;
+    int64_t batch;
+    const void* mean_dev;
+    int64_t mean_s_n;
+    const void* latent_dev;
+    int64_t latent_s_n;
+    const void* e_dev;
+    int64_t e_s_n;
+    const void* log_std_dev;
+    double clip_mean;
+    void* act_dev;
+    float* step_act_dev;
+    void* logp_dev;
+    double* saved_dev;
+    const void* grad_act_dev;
+    const void* grad_logp_dev;
+    void* grad_mean_dev;
+    int64_t gm_s_n;
+    void* grad_latent_dev;
+    int64_t gl_s_n;
+    void* grad_log_std_dev;
+    void* ws_dev;
+} ptg_sde_rs;
+int ptg_sde_resample_rows(ptg_env* env, const ptg_sde_noise* d, int64_t rows, void* stream);
+int ptg_sde_rsample(ptg_env* env, const ptg_sde_rs* d, void* stream);
+int64_t ptg_sde_rsample_backward_workspace(int64_t batch, int32_t latent_dim);
+int ptg_sde_rsample_backward(ptg_env* env, const ptg_sde_rs* d, void* stream);
 
 /* ---- the optimiser step: grad-norm clip, Adam / RMSprop, Polyak and zero_grad for all tensors of an optimiser --------------------
  * Replaces what the reference's agents (src/rl_config_agent.py; SB3 2.0.0a13 on torch) run behind loss.backward() on every minibatch:

@@ -34,6 +34,7 @@ QL_LOG_ALPHA = 1
 QL_MAX_QUANTILES = 64
 RS_SQUASH, RS_SMOOTH = 0, 1
 RS_DETERMINISTIC = 1
+SDE_RS_DETERMINISTIC, SDE_RS_SHARED_E = 1, 2
 AL_MIN, AL_MEAN, AL_ALPHA_ONLY = 0, 1, 2
 AL_ENTROPY, AL_LOG_ALPHA, AL_ENT_COEF = 1, 2, 4
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 10, 1024
@@ -127,6 +128,15 @@ class PtgSdeLoss(C.Structure):                              # ptg_sde_loss: one 
                 ("gl_s_n", C.c_int64), ("ws_dev", C.c_void_p)]
 
 
+class PtgSdeRs(C.Structure):                                # ptg_sde_rs: one call of gSDE's squashed head for SAC / TQC, forward or backward
+    _fields_ = [("flags", C.c_int32), ("in_dtype", C.c_int32), ("latent_dim", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int64),
+                ("mean_dev", C.c_void_p), ("mean_s_n", C.c_int64), ("latent_dev", C.c_void_p), ("latent_s_n", C.c_int64), ("e_dev", C.c_void_p),
+                ("e_s_n", C.c_int64), ("log_std_dev", C.c_void_p), ("clip_mean", C.c_double), ("act_dev", C.c_void_p), ("step_act_dev", C.c_void_p),
+                ("logp_dev", C.c_void_p), ("saved_dev", C.c_void_p), ("grad_act_dev", C.c_void_p), ("grad_logp_dev", C.c_void_p),
+                ("grad_mean_dev", C.c_void_p), ("gm_s_n", C.c_int64), ("grad_latent_dev", C.c_void_p), ("gl_s_n", C.c_int64),
+                ("grad_log_std_dev", C.c_void_p), ("ws_dev", C.c_void_p)]
+
+
 class PtgOptimTensor(C.Structure):                          # ptg_optim_tensor: one record of the optimiser's tensor table
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p), ("target", C.c_void_p),
                 ("numel", C.c_int64)]
@@ -203,6 +213,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
            "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_rollout_buffer_begin", "ptg_rollout_buffer_add", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_sde_resample", "ptg_sde_act", "ptg_sde_policy_loss_workspace", "ptg_sde_policy_loss",
+           "ptg_sde_resample_rows", "ptg_sde_rsample", "ptg_sde_rsample_backward_workspace", "ptg_sde_rsample_backward",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
            "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward", "ptg_mlp_backward_workspace", "ptg_mlp_backward",
            "ptg_mlp_group_forward", "ptg_mlp_group_backward",
@@ -333,6 +344,11 @@ def lib():
     L.ptg_sde_policy_loss_workspace.argtypes = [C.c_int64, C.c_int32]
     L.ptg_sde_policy_loss_workspace.restype = C.c_int64
     L.ptg_sde_policy_loss.argtypes = [vp, C.POINTER(PtgSdeLoss), vp]
+    L.ptg_sde_resample_rows.argtypes = [vp, C.POINTER(PtgSdeNoise), C.c_int64, vp]
+    L.ptg_sde_rsample.argtypes = [vp, C.POINTER(PtgSdeRs), vp]
+    L.ptg_sde_rsample_backward_workspace.argtypes = [C.c_int64, C.c_int32]
+    L.ptg_sde_rsample_backward_workspace.restype = C.c_int64
+    L.ptg_sde_rsample_backward.argtypes = [vp, C.POINTER(PtgSdeRs), vp]
     L.ptg_optim_chunk.argtypes = []
     L.ptg_optim_workspace.argtypes = [C.c_int64]
     L.ptg_optim_workspace.restype = C.c_int64

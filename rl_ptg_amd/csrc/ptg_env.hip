@@ -3149,7 +3149,10 @@ int ptg_step_host_begin(ptg_env* h, const void* actions_host, int action_kind, v
     }
     if (!zc) {
         if (!h->hs_act) HIP_TRY(h, hipMalloc(&h->hs_act, (size_t)h->n * 8));
-        if (!h->hs_out) HIP_TRY(h, hipMalloc(&h->hs_out, total));
+        if (!h->hs_out) {                                    // zeroed once: the padding between the block's sections is copied out with them
+            HIP_TRY(h, hipMalloc(&h->hs_out, total));
+            HIP_TRY(h, hipMemsetAsync(h->hs_out, 0, total, st));
+        }
         if (!h->hs_final) HIP_TRY(h, hipMalloc(&h->hs_final, final_bytes));
         if (info_host && !h->hs_info) HIP_TRY(h, hipMalloc((void**)&h->hs_info, info_bytes));
         if (!h->ev_tail) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));

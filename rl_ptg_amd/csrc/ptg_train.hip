@@ -9,7 +9,7 @@
 //   k_rb_*            SB3's ReplayBuffer.add / sample over caller-owned rings on the device (the off-policy algorithms).
 //   k_act             the action head while collecting: SB3's Categorical sample / log_prob / entropy, DQN's epsilon-greedy, the Gaussian heads.
 //   k_pl_*            the PPO / A2C loss of a minibatch, SB3's logged statistics and the gradients w.r.t. the network's outputs in one pass.
-//   k_sde_*           gSDE (SB3's StateDependentNoiseDistribution, on-policy): the exploration matrix, the collecting head, the PPO / A2C loss.
+//   k_sde_*           gSDE (SB3's StateDependentNoiseDistribution): the exploration matrix, the collecting head, the PPO / A2C loss; k_sde_rs_*: SAC / TQC's squashed head and its backward.
 //   k_optim_*         clip_grad_norm_, torch.optim.Adam / RMSprop, SB3's polyak_update and zero_grad over all tensors of an optimiser.
 //   k_td_*            the TD loss of DQN / the TD3 and SAC critics on a replay batch, its statistics and the gradients w.r.t. the Q-values.
 //   k_ql_*            TQC's quantile-Huber critic loss on a replay batch, its statistics and the gradients w.r.t. the current quantiles.
@@ -1175,6 +1175,32 @@ struct SdeLossArgs {                     // by value in the launch
 // the workspace, in doubles: [0..2] merged moments, [4 ..) moment partials [l.nblk][3], s2 [L], row partials [nblk][PL_PITCH], column partials [nblk][L]
 __host__ __device__ __forceinline__ double* sde_s2(const LossArgs& l) { return l.ws + 4 + (size_t)l.nblk * 3; }
 
+// The column-partial tail of a row kernel (the loss's and the squashed head's backward): a lane holds its units' sums over the rows its
+// wave walked; the block's waves meet in LDS in wave order and the block leaves one [L] partial.  sde_col_sum adds column k's
+// partials over the blocks ascending.
+template <int NJ>
+__device__ __forceinline__ void sde_col_tail(const double (&acc)[NJ], double* sh_col, double* col_part, int L, int lane, int w)
+{
+    for (int q = 0; q < SDE_WAVES; q++) {
+        if (w == q) {
+#pragma unroll
+            for (int j = 0; j < NJ; j++) {
+                const int k = lane + 64 * j;
+                if (k < L) sh_col[k] = q == 0 ? acc[j] : sh_col[k] + acc[j];
+            }
+        }
+        __syncthreads();
+    }
+    for (int k = threadIdx.x; k < L; k += SDE_BLOCK) col_part[(size_t)blockIdx.x * (size_t)L + (size_t)k] = sh_col[k];
+}
+
+__device__ __forceinline__ double sde_col_sum(const double* col_part, int nblk, int L, int k)
+{
+    double s = col_part[k];
+    for (int b = 1; b < nblk; b++) s += col_part[(size_t)b * (size_t)L + (size_t)k];
+    return s;
+}
+
 template <typename IN>
 __global__ void __launch_bounds__(SDE_BLOCK)
 k_sde_s2(const void* log_std, int L, double* s2)
@@ -1250,18 +1276,7 @@ k_sde_rows(SdeLossArgs a)
             if (g_lat && k < L) g_lat[i * a.gl_s + (size_t)k] = (IN)(((ci * (2.0 * h[j])) * s2[j]) / Bd);
         }
     }
-    // the block's column partial: the waves in wave order
-    for (int q = 0; q < SDE_WAVES; q++) {
-        if (w == q) {
-#pragma unroll
-            for (int j = 0; j < NJ; j++) {
-                const int k = lane + 64 * j;
-                if (k < L) sh_col[k] = q == 0 ? acc[j] : sh_col[k] + acc[j];
-            }
-        }
-        __syncthreads();
-    }
-    for (int k = threadIdx.x; k < L; k += SDE_BLOCK) a.col_part[(size_t)blockIdx.x * (size_t)L + (size_t)k] = sh_col[k];
+    sde_col_tail<NJ>(acc, sh_col, a.col_part, L, lane, w);
     const bool first = lane == 0;
     double v[PL_TERMS] = {first ? sum.surr : 0.0, first ? sum.q : 0.0, first ? sum.H : 0.0, first ? sum.kl : 0.0, first ? sum.cf : 0.0, 0.0};
     loss_tail<false>(v, sh, a.row_part, [](const double*) {});
@@ -1274,8 +1289,7 @@ k_sde_cols(SdeLossArgs a, void* g_ls)
 {
     const int k = (int)blockIdx.x * SDE_BLOCK + (int)threadIdx.x;
     if (k >= a.L) return;
-    double s = a.col_part[k];
-    for (int b = 1; b < a.nblk; b++) s += a.col_part[(size_t)b * (size_t)a.L + (size_t)k];
+    const double s = sde_col_sum(a.col_part, a.nblk, a.L, k);
     ((IN*)g_ls)[k] = (IN)(((2.0 * a.s2[k]) * s) / (double)a.l.B);
 }
 
@@ -1288,6 +1302,162 @@ struct SdeFinal {                        // the eight statistics; the log_std gr
         PlFinal<IN>()(l, v);
     }
 };
+
+// ---- gSDE for SAC / TQC: the squashed head's reparametrised sample and its backward (include/ptg_env.h, ptg_sde_rsample, states the
+// lines; tests/sde_squash_restatement.py restates them).  The forward is k_sde_act's shape: a wave per row, s_k * s_k once per
+// workgroup in LDS -- the target's pass and the collecting head have no workspace, and at a replay batch a leading launch would cost
+// more than the workgroup's L exps.  With one shared row the lane keeps its E entries in registers across its rows.  The backward
+// has a workspace for its column partials anyway, so k_sde_s2 leaves s_k * s_k there as it does for the loss, and the row kernel needs
+// no reduction over k at all: (noise, V) come from the forward, every line of a row is a lane's own but the bad-latent ballot.
+struct SdeRsArgs {                       // by value in the launch
+    const void* mean; size_t m_s;        // elements
+    const void* lat; size_t lat_s;
+    const void* E; size_t e_s;           // null when deterministic
+    const void* log_std;                 // forward
+    const double* s2;                    // backward: float64 [L] in the workspace
+    void *act, *logp;
+    float* step_act;
+    double* saved;                       // [B][2]: noise, V
+    const void *g_act, *g_logp;
+    void* g_mean; size_t gm_s;
+    void* g_lat; size_t gl_s;
+    double* col_part;                    // [nblk][L]; null: no log_std gradient
+    double c;                            // clip_mean
+    size_t B, rows_per_wave;
+    int L, nblk, shared;
+    int* err;
+};
+
+__device__ __forceinline__ double sde_hardtanh(double mu, double c) { return mu < -c ? -c : (mu > c ? c : mu); }      // a NaN falls through
+
+template <typename IN, int NJ>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_rs_fwd(SdeRsArgs a)
+{
+    __shared__ double sh_s2[PTG_MLP_MAX_WIDTH];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, L = a.L;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    int ls_bad = 0;
+    for (int k = threadIdx.x; k < L; k += SDE_BLOCK) {
+        const double ls = (double)((const IN*)a.log_std)[k];
+        ls_bad |= !(ls <= PL_DBL_MAX);                       // NaN or +Inf: every row is bad
+        const double s = exp(ls);
+        sh_s2[k] = s * s;
+    }
+    ls_bad = __syncthreads_or(ls_bad);
+    const IN* const lat = (const IN*)a.lat; const IN* const E = (const IN*)a.E;
+    const bool shared = a.shared != 0;
+    double s2[NJ], es[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int k = lane + 64 * j;
+        s2[j] = k < L ? sh_s2[k] : 0.0;
+        es[j] = (shared && k < L) ? (double)E[k] : 0.0;
+    }
+    IN* const act_o = (IN*)a.act; IN* const logp_o = (IN*)a.logp;
+    const size_t base = (size_t)blockIdx.x * (a.rows_per_wave * SDE_WAVES);
+    for (size_t t = 0; t < a.rows_per_wave; t++) {
+        const size_t i = base + t * SDE_WAVES + (size_t)w;
+        if (i >= a.B) break;                                 // wave-uniform: the ragged end
+        double vp = 0.0, np = 0.0;
+        bool h_bad = false;
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int k = lane + 64 * j;
+            if (k < L) {
+                const double h = (double)lat[i * a.lat_s + (size_t)k];
+                h_bad = h_bad || !pl_finite(h);
+                vp += (h * h) * s2[j];
+                if (E) np += h * (shared ? es[j] : (double)E[i * a.e_s + (size_t)k]);
+            }
+        }
+        const double V = pl_wave_sum(vp) + 1e-6;
+        const double noise = E ? pl_wave_sum(np) : 0.0;
+        const bool bad_lat = __ballot(h_bad) != 0ull;
+        const double mu = (double)((const IN*)a.mean)[i * a.m_s];
+        const bool bad = ls_bad || bad_lat || !pl_finite(mu) || !pl_finite(V) || !pl_finite(noise);
+        const double m = sde_hardtanh(mu, a.c);
+        const double lsd = log(sqrt(V));
+        const double g = m + noise;
+        const double x = tanh(g);
+        if (lane == 0) {                                     // the row's scalars are the same on every lane; one of them stores
+            act_o[i] = (IN)(bad ? nan : x);
+            if (a.step_act) a.step_act[i] = bad ? 0.0f : (float)x;
+            if (logp_o) logp_o[i] = (IN)(bad ? nan : ((((-(noise * noise)) / (2.0 * V)) - lsd) - 0.9189385332046727) - log((1.0 - x * x) + 1e-6));
+            if (a.saved) { a.saved[2 * i] = noise; a.saved[2 * i + 1] = V; }
+            if (bad) a.err[5] = 1;
+        }
+    }
+}
+
+template <typename IN, int NJ>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_rs_bwd(SdeRsArgs a)
+{
+    __shared__ double sh_col[PTG_MLP_MAX_WIDTH];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, L = a.L;
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const IN* const lat = (const IN*)a.lat; const IN* const E = (const IN*)a.E;
+    IN* const g_lat = (IN*)a.g_lat;
+    const bool shared = a.shared != 0;
+    double s2[NJ], es[NJ], acc[NJ];
+    bool s_bad = false;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int k = lane + 64 * j;
+        s2[j] = k < L ? a.s2[k] : 0.0;
+        s_bad = s_bad || s2[j] != s2[j];                     // k_sde_s2's NaN: a NaN or +Inf log_std, every row is bad
+        es[j] = (shared && k < L) ? (double)E[k] : 0.0;
+        acc[j] = 0.0;
+    }
+    const bool ls_bad = __ballot(s_bad) != 0ull;
+    const size_t base = (size_t)blockIdx.x * (a.rows_per_wave * SDE_WAVES);
+    for (size_t t = 0; t < a.rows_per_wave; t++) {
+        const size_t i = base + t * SDE_WAVES + (size_t)w;
+        if (i >= a.B) break;                                 // wave-uniform: the ragged end
+        // the row's scalars, the same on every lane
+        const double mu = (double)((const IN*)a.mean)[i * a.m_s], noise = a.saved[2 * i], V = a.saved[2 * i + 1];
+        const double ga = a.g_act ? (double)((const IN*)a.g_act)[i] : 0.0, gl = a.g_logp ? (double)((const IN*)a.g_logp)[i] : 0.0;
+        double h[NJ];
+        bool h_bad = false;
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int k = lane + 64 * j;
+            h[j] = k < L ? (double)lat[i * a.lat_s + (size_t)k] : 0.0;
+            h_bad = h_bad || !pl_finite(h[j]);
+        }
+        const bool bad = ls_bad || __ballot(h_bad) != 0ull || !pl_finite(mu) || !pl_finite(noise) || !pl_finite(V) || !pl_finite(ga) || !pl_finite(gl);
+        const double x = tanh(sde_hardtanh(mu, a.c) + noise);
+        const double d = 1.0 - x * x;
+        const double q = ((2.0 * x) * d) / (d + 1e-6);
+        const double tt = ga * d + gl * q;
+        const double n = bad ? nan : tt - gl * (noise / V);
+        const double cV = bad ? nan : (gl * (((noise * noise) / V) - 1.0)) / (2.0 * V);
+        if (lane == 0) {
+            ((IN*)a.g_mean)[i * a.gm_s] = (IN)(bad ? nan : ((-a.c < mu && mu < a.c) ? tt : 0.0));
+            if (bad) a.err[5] = 1;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int k = lane + 64 * j;
+            const double e = E ? (shared ? es[j] : (k < L ? (double)E[i * a.e_s + (size_t)k] : 0.0)) : 0.0;
+            const double gh = (n * e) + ((cV * (2.0 * h[j])) * s2[j]);
+            acc[j] += h[j] * gh;
+            if (g_lat && k < L) g_lat[i * a.gl_s + (size_t)k] = (IN)gh;
+        }
+    }
+    if (a.col_part) sde_col_tail<NJ>(acc, sh_col, a.col_part, L, lane, w);
+}
+
+// d loss / d log_std[k] of the squashed head from the blocks' column partials, ascending
+template <typename IN>
+__global__ void __launch_bounds__(SDE_BLOCK)
+k_sde_rs_cols(const double* col_part, int nblk, int L, void* g_ls)
+{
+    const int k = (int)blockIdx.x * SDE_BLOCK + (int)threadIdx.x;
+    if (k >= L) return;
+    ((IN*)g_ls)[k] = (IN)sde_col_sum(col_part, nblk, L, k);
+}
 
 // ================================================================================== the optimiser step
 // What runs behind loss.backward() (include/ptg_env.h, ptg_optim_step, states the lines; tests/optim_restatement.py restates them in
@@ -2107,6 +2277,25 @@ void launch_sde_loss(hipStream_t st, const SdeLossArgs& a, void* g_ls)
     hipLaunchKernelGGL(k_sde_cols<IN>, dim3((unsigned)((a.L - 1) / SDE_BLOCK + 1)), block, 0, st, a, g_ls);
 }
 
+template <typename IN>
+void launch_sde_rs(hipStream_t st, const SdeRsArgs& a, bool backward)
+{
+    const dim3 grid((unsigned)a.nblk), block(SDE_BLOCK);
+    if (!backward) {
+        switch (sde_nj(a.L)) {
+        case 4: hipLaunchKernelGGL((k_sde_rs_fwd<IN, 4>), grid, block, 0, st, a); break;
+        case 8: hipLaunchKernelGGL((k_sde_rs_fwd<IN, 8>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((k_sde_rs_fwd<IN, SDE_MAX_J>), grid, block, 0, st, a);
+        }
+        return;
+    }
+    switch (sde_nj(a.L)) {
+    case 4: hipLaunchKernelGGL((k_sde_rs_bwd<IN, 4>), grid, block, 0, st, a); break;
+    case 8: hipLaunchKernelGGL((k_sde_rs_bwd<IN, 8>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_sde_rs_bwd<IN, SDE_MAX_J>), grid, block, 0, st, a);
+    }
+}
+
 // what ptg_rsample and ptg_rsample_backward refuse alike; the text of the first fault, or null
 const char* rs_desc_error(const ptg_rs* d, bool backward)
 {
@@ -2585,25 +2774,32 @@ int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
 static bool sde_dtype_ok(int dt) { return dt == PTG_OUT_F32 || dt == PTG_OUT_F64; }
 static bool sde_width_ok(int L) { return L >= 1 && L <= PTG_MLP_MAX_WIDTH; }
 
-int ptg_sde_resample(ptg_env* h, const ptg_sde_noise* d, void* stream)
+// ptg_sde_resample and ptg_sde_resample_rows: `rows` rows whose keys start at the global row `offset`
+static int sde_resample(ptg_env* h, const char* who, const ptg_sde_noise* d, long long offset, int64_t rows, void* stream)
 {
-    if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: null descriptor");
-    if (!sde_dtype_ok(d->in_dtype)) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
-    if (!sde_width_ok(d->latent_dim)) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: latent_dim %d outside [1, %d]", d->latent_dim, PTG_MLP_MAX_WIDTH);
-    if (!d->log_std_dev || !d->counter_dev || !d->e_dev) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: null log_std_dev, counter_dev or e_dev");
-    if (d->e_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "ptg_sde_resample: e_s_n < latent_dim");
+    if (!d) return set_err(h, PTG_E_INVALID, "%s: null descriptor", who);
+    if (!sde_dtype_ok(d->in_dtype)) return set_err(h, PTG_E_INVALID, "%s: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64", who);
+    if (!sde_width_ok(d->latent_dim)) return set_err(h, PTG_E_INVALID, "%s: latent_dim %d outside [1, %d]", who, d->latent_dim, PTG_MLP_MAX_WIDTH);
+    if (!d->log_std_dev || !d->counter_dev || !d->e_dev) return set_err(h, PTG_E_INVALID, "%s: null log_std_dev, counter_dev or e_dev", who);
+    if (d->e_s_n < d->latent_dim) return set_err(h, PTG_E_INVALID, "%s: e_s_n < latent_dim", who);
+    if (rows < 1 || rows > (int64_t)1 << 31) return set_err(h, PTG_E_INVALID, "%s: rows %lld outside [1, 2^31]", who, (long long)rows);
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
     SdeNoiseArgs a{};
     a.log_std = d->log_std_dev; a.E = d->e_dev; a.e_s = (size_t)d->e_s_n; a.counter = (const unsigned long long*)d->counter_dev;
-    a.seed = (unsigned long long)d->seed; a.env_offset = h->P.env_offset; a.N = (size_t)h->n; a.L = d->latent_dim; a.err = h->P.err;
+    a.seed = (unsigned long long)d->seed; a.env_offset = offset; a.N = (size_t)rows; a.L = d->latent_dim; a.err = h->P.err;
     a.rows_per_block = (a.N - 1) / SDE_MAX_BLOCKS + 1;
     const dim3 grid((unsigned)((a.L + 63) / 64), (unsigned)((a.N - 1) / a.rows_per_block + 1)), block(64);
     if (d->in_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_sde_resample<double>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(k_sde_resample<float>, grid, block, 0, st, a);
     hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)d->counter_dev, 1ull);
     return launch_check(h, "k_sde_resample");
+}
+
+int ptg_sde_resample(ptg_env* h, const ptg_sde_noise* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    return sde_resample(h, "ptg_sde_resample", d, h->P.env_offset, h->n, stream);        // a row is an env
 }
 
 int ptg_sde_act(ptg_env* h, const ptg_sde_head* d, void* stream)
@@ -2691,6 +2887,92 @@ int ptg_sde_policy_loss(ptg_env* h, const ptg_sde_loss* d, void* stream)
     if (f64) launch_sde_loss<double>(st, a, d->grad_log_std_dev);
     else launch_sde_loss<float>(st, a, d->grad_log_std_dev);
     return launch_check(h, "k_sde_rows");
+}
+
+// ---- gSDE for SAC / TQC: the training matrix, the squashed head's reparametrised sample, its backward ------------------------------
+int ptg_sde_resample_rows(ptg_env* h, const ptg_sde_noise* d, int64_t rows, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    return sde_resample(h, "ptg_sde_resample_rows", d, 0, rows, stream);                 // a row is a batch row: no env offset
+}
+
+// what ptg_sde_rsample and ptg_sde_rsample_backward refuse alike, then each its own; the text of the first fault, or null
+static const char* sde_rs_error(const ptg_sde_rs* d, bool backward)
+{
+    if (!d) return "null descriptor";
+    if (d->flags & ~(PTG_SDE_RS_DETERMINISTIC | PTG_SDE_RS_SHARED_E)) return "unknown flag";
+    const bool det = (d->flags & PTG_SDE_RS_DETERMINISTIC) != 0, shared = (d->flags & PTG_SDE_RS_SHARED_E) != 0;
+    if (!sde_dtype_ok(d->in_dtype)) return "in_dtype must be PTG_OUT_F32 or PTG_OUT_F64";
+    if (!sde_width_ok(d->latent_dim)) return "latent_dim outside [1, 1024]";
+    if (d->batch < 1 || d->batch > (int64_t)1 << 31) return "batch outside [1, 2^31]";
+    if (!d->mean_dev || !d->latent_dev || !d->log_std_dev) return "null mean_dev, latent_dev or log_std_dev";
+    if (!det && !d->e_dev) return "a stochastic call needs e_dev";
+    if (d->mean_s_n < 1) return "mean_s_n < 1";
+    if (d->latent_s_n < d->latent_dim) return "latent_s_n < latent_dim";
+    if (!det && !shared && d->e_s_n < d->latent_dim) return "e_s_n < latent_dim";
+    if (!(d->clip_mean > 0.0)) return "clip_mean is <= 0 or NaN";
+    if ((uintptr_t)d->saved_dev % sizeof(double) != 0) return "saved_dev is not aligned to 8 bytes";
+    if (!backward) return d->act_dev ? nullptr : "null act_dev";
+    if (!d->saved_dev || !d->grad_mean_dev) return "null saved_dev or grad_mean_dev";
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return "ws_dev is null or not aligned to 8 bytes";
+    if (!d->grad_act_dev && !d->grad_logp_dev) return "grad_act_dev and grad_logp_dev are both null";
+    if (d->gm_s_n < 1) return "gm_s_n < 1";
+    if (d->grad_latent_dev && d->gl_s_n < d->latent_dim) return "gl_s_n < latent_dim";
+    if (d->grad_log_std_dev && !shared) return "grad_log_std_dev without PTG_SDE_RS_SHARED_E";
+    return nullptr;
+}
+
+static void sde_rs_args(ptg_env* h, const ptg_sde_rs* d, SdeRsArgs& a)
+{
+    const bool det = (d->flags & PTG_SDE_RS_DETERMINISTIC) != 0;
+    a.mean = d->mean_dev; a.m_s = (size_t)d->mean_s_n; a.lat = d->latent_dev; a.lat_s = (size_t)d->latent_s_n;
+    a.E = det ? nullptr : d->e_dev; a.shared = !det && (d->flags & PTG_SDE_RS_SHARED_E) != 0; a.e_s = (det || a.shared) ? 0 : (size_t)d->e_s_n;
+    a.log_std = d->log_std_dev; a.act = d->act_dev; a.logp = d->logp_dev; a.step_act = d->step_act_dev; a.saved = d->saved_dev;
+    a.g_act = d->grad_act_dev; a.g_logp = d->grad_logp_dev; a.g_mean = d->grad_mean_dev; a.gm_s = (size_t)d->gm_s_n;
+    a.g_lat = d->grad_latent_dev; a.gl_s = (size_t)d->gl_s_n;
+    a.c = d->clip_mean; a.B = (size_t)d->batch; a.rows_per_wave = sde_rows_per_wave(a.B); a.L = d->latent_dim;
+    a.nblk = (int)sde_loss_blocks(d->batch); a.err = h->P.err;
+}
+
+int ptg_sde_rsample(ptg_env* h, const ptg_sde_rs* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (const char* why = sde_rs_error(d, false)) return set_err(h, PTG_E_INVALID, "ptg_sde_rsample: %s", why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    SdeRsArgs a{};
+    sde_rs_args(h, d, a);
+    if (d->in_dtype == PTG_OUT_F64) launch_sde_rs<double>(as_stream(stream), a, false);
+    else launch_sde_rs<float>(as_stream(stream), a, false);
+    return launch_check(h, "k_sde_rs_fwd");
+}
+
+int64_t ptg_sde_rsample_backward_workspace(int64_t batch, int32_t latent_dim)
+{
+    if (batch < 1 || batch > (int64_t)1 << 31 || !sde_width_ok(latent_dim)) return PTG_E_INVALID;
+    return (int64_t)latent_dim * (1 + sde_loss_blocks(batch)) * (int64_t)sizeof(double);
+}
+
+int ptg_sde_rsample_backward(ptg_env* h, const ptg_sde_rs* d, void* stream)
+{
+    if (!h) return PTG_E_INVALID;
+    if (const char* why = sde_rs_error(d, true)) return set_err(h, PTG_E_INVALID, "ptg_sde_rsample_backward: %s", why);
+    HIP_TRY(h, hipSetDevice(h->device));
+    const hipStream_t st = as_stream(stream);
+    SdeRsArgs a{};
+    sde_rs_args(h, d, a);
+    double* const s2 = (double*)d->ws_dev;
+    a.s2 = s2; a.col_part = d->grad_log_std_dev ? s2 + a.L : nullptr;
+    const bool f64 = d->in_dtype == PTG_OUT_F64;
+    const dim3 block(SDE_BLOCK), cols((unsigned)((a.L - 1) / SDE_BLOCK + 1));
+    if (f64) hipLaunchKernelGGL(k_sde_s2<double>, cols, block, 0, st, d->log_std_dev, a.L, s2);
+    else hipLaunchKernelGGL(k_sde_s2<float>, cols, block, 0, st, d->log_std_dev, a.L, s2);
+    if (f64) launch_sde_rs<double>(st, a, true);
+    else launch_sde_rs<float>(st, a, true);
+    if (a.col_part) {
+        if (f64) hipLaunchKernelGGL(k_sde_rs_cols<double>, cols, block, 0, st, (const double*)a.col_part, a.nblk, a.L, d->grad_log_std_dev);
+        else hipLaunchKernelGGL(k_sde_rs_cols<float>, cols, block, 0, st, (const double*)a.col_part, a.nblk, a.L, d->grad_log_std_dev);
+    }
+    return launch_check(h, "k_sde_rs_bwd");
 }
 
 // ---- the optimiser step: grad-norm clip, Adam / RMSprop, Polyak and zero_grad for all tensors of an optimiser -----------

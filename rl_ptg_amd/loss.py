@@ -1,5 +1,6 @@
 """ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd;
-ppo_sde_loss / a2c_sde_loss: the same for a policy with gSDE (HipEngine.sde_policy_loss, ptg_sde_policy_loss);
+ppo_sde_loss / a2c_sde_loss: the same for a policy with gSDE (HipEngine.sde_policy_loss, ptg_sde_policy_loss); sde_squashed_rsample: SAC's
+and TQC's actor head with gSDE (HipEngine.sde_rsample / sde_rsample_backward, ptg_sde_rsample);
 dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise, and tqc_critic_loss: TQC's
 quantile-Huber critic loss (HipEngine.quantile_loss, ptg_quantile_loss); squashed_rsample (HipEngine.rsample / rsample_backward,
 ptg_rsample) and sac_actor_loss / tqc_actor_loss / td3_actor_loss / ent_coef_loss (HipEngine.actor_loss, ptg_actor_loss): the actor
@@ -103,6 +104,48 @@ def a2c_sde_loss(engine, mean, values, latent, log_std, actions, advantages, ret
     """a2c_loss for a policy with gSDE -> (loss, stats) as ppo_sde_loss gives them (approx_kl and clip_fraction are 0)."""
     kw = dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, out=out, workspace=workspace)
     return _SdePolicyLossFn.apply(engine, "a2c", mean, values, latent, log_std, actions, None, advantages, returns, None, kw)
+
+
+# ------------------------------------------------------------------------------------------------- SAC / TQC with gSDE
+#     noise.reset_train_noise(log_std)                          # SquashedSdeNoise: once per gradient step, as SB3's actor.reset_noise()
+#     with torch.no_grad():
+#         next_actions, next_log_prob = sde_squashed_rsample(noise, mu(trunk(next_obs)), trunk_out, log_std)       # the same row
+#     latent = trunk(obs)                                       # TrainMLP, its hidden activation as out_activation
+#     actions, log_prob = sde_squashed_rsample(noise, mu(latent), latent, log_std)
+#     loss, stats = sac_actor_loss(engine, critics(obs, actions), log_prob, ent_coef=alpha); loss.backward()
+# The backward is a kernel (HipEngine.sde_rsample_backward): it fills the gradients of the mean, of the latent (learn_features=True)
+# and of log_std, the last through the variance AND through the resampled row E = exp(log_std) * z, which SB3 draws with rsample().
+class _SdeRSampleFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, noise, mean, latent, log_std, deterministic):
+        eng = noise.engine
+        keep = any(ctx.needs_input_grad[1:4])                # False under torch.no_grad(): nothing is kept
+        row = None if deterministic else noise.train_row
+        res = eng.sde_rsample(mean.detach(), latent.detach(), log_std.detach(), row, clip_mean=noise.clip_mean, deterministic=deterministic, want_saved=keep)
+        if keep:
+            ctx.save_for_backward(mean.detach(), latent.detach(), log_std.detach())
+            ctx.eng, ctx.row, ctx.saved, ctx.clip_mean, ctx.deterministic = eng, None if row is None else row.clone(), res.saved, noise.clip_mean, deterministic
+            ctx.want = (ctx.needs_input_grad[2], ctx.needs_input_grad[3] and not deterministic)
+        return res.actions.reshape(mean.shape), res.log_prob.reshape(mean.shape)
+
+    @staticmethod
+    def backward(ctx, grad_actions, grad_log_prob):
+        mean, latent, log_std = ctx.saved_tensors
+        ga = None if grad_actions is None else grad_actions.contiguous()
+        gl = None if grad_log_prob is None else grad_log_prob.contiguous()
+        g = ctx.eng.sde_rsample_backward(mean, latent, log_std, ctx.row, ctx.saved, ga, gl, clip_mean=ctx.clip_mean, deterministic=ctx.deterministic,
+                                         want_grad_latent=ctx.want[0], want_grad_log_std=ctx.want[1])
+        g_ls = None if g.grad_log_std is None else g.grad_log_std.reshape(log_std.shape)
+        return None, g.grad_mean.reshape(mean.shape), g.grad_latent, g_ls, None
+
+
+def sde_squashed_rsample(noise, mean, latent, log_std, deterministic=False):
+    """SB3's Actor.action_log_prob of SAC / TQC with use_sde on a replay batch -> (actions, log_prob), shaped like mean, with a
+    grad_fn: noise a SquashedSdeNoise whose reset_train_noise() drew this gradient step's row, mean [B] / [B, 1] the mu layer's
+    UNCLIPPED output, latent [B, L] the trunk's output, log_std the [L] / [L, 1] parameter.  The forward is HipEngine.sde_rsample, the
+    backward HipEngine.sde_rsample_backward on the saved (noise, V) pairs and a copy of the row.  Under torch.no_grad() (the next
+    observations, for the critic target) nothing is kept."""
+    return _SdeRSampleFn.apply(noise, mean, latent, log_std, deterministic)
 
 
 # ------------------------------------------------------------------------------------------------- the off-policy losses

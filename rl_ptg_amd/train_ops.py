@@ -1,5 +1,5 @@
 """TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
-action heads, the policy loss, gSDE's matrix, head and loss, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the forward and backward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
+action heads, the policy loss, gSDE's matrix, head and loss, gSDE's squashed head for SAC / TQC with its backward, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the forward and backward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward and mlp_backward); none of them steps the environment.  HipEngine inherits them.
 
 The mixin reads self._torch, _L, _h, n, device, out_dtype, obs_dim, feature_major, pitch and calls self._chk, _stream, _check_obs,
@@ -30,6 +30,11 @@ PolicyLoss = collections.namedtuple("PolicyLoss", "stats grad_input grad_values 
 # gradient w.r.t. the latent [B, L] (None when not asked for)
 SdeAct = collections.namedtuple("SdeAct", "actions raw log_prob entropy")
 SdePolicyLoss = collections.namedtuple("SdePolicyLoss", "stats grad_input grad_values grad_log_std grad_latent")
+# what sde_rsample returns: actions and log_prob [B] in the inputs' dtype, step_actions float32 [B] (what step() takes), saved float64
+# [B, 2] (noise, V: what sde_rsample_backward reads); sde_rsample_backward: the gradients w.r.t. the unclipped mean [B], the latent
+# [B, L] and log_std [L].  Fields not asked for are None.
+SdeRSample = collections.namedtuple("SdeRSample", "actions step_actions log_prob saved")
+SdeRSampleGrad = collections.namedtuple("SdeRSampleGrad", "grad_mean grad_latent grad_log_std")
 # what td_loss returns: stats float64 [8], the gradients w.r.t. the current Q-values (DQN: one tensor [B, A]; critics: a list of K tensors
 # shaped like q[k]) and the TD target [B] (None when not asked for)
 TdLoss = collections.namedtuple("TdLoss", "stats grad_q target")
@@ -954,6 +959,148 @@ class TrainOps:
                             gl_s_n=0 if g_lat is None else _row_stride(g_lat), ws_dev=_ptr(workspace))
         self._call("ptg_sde_policy_loss", C.byref(d))
         return SdePolicyLoss(stats, g_in, g_val, g_ls, g_lat)
+
+    # ------------------------------------------------------------------ gSDE for SAC / TQC: the training matrix, the squashed head, its backward
+    def sde_resample_rows(self, log_std, counter, noise, seed=0):
+        """sde_resample for a matrix of batch rows (include/ptg_env.h: ptg_sde_resample_rows): noise [rows, L] or one row [L] is filled
+        with exp(log_std[k]) * z, z the draw of (seed, *counter, r * 1024 + k) -- no global env offset, rows not tied to n_envs.  SAC /
+        TQC with gSDE draw ONE row per gradient step.  The counter advances by one on the device.  Returns noise."""
+        torch = self._torch
+        who = "sde_resample_rows"
+        log_std, L = self._sde_log_std(who, log_std, (torch.float32, torch.float64))
+        check(self, who, "counter (new_draw_counter())", counter, dtypes=(torch.int64,), numel=1, shape=(1,))
+        m = noise[None, :] if _dims(self, noise) == 1 else noise
+        check(self, who, "noise", m, dtypes=(log_std.dtype,), shape=(None, L), rule=wide_rows, exc=ValueError)
+        if m.shape[0] < 1:
+            raise ValueError(f"{who}: noise has no rows, shape {tuple(noise.shape)}")
+        d = _lib.PtgSdeNoise(in_dtype=_out_code(torch, log_std.dtype), latent_dim=L, log_std_dev=_ptr(log_std), seed=int(seed) & (2 ** 64 - 1),
+                             counter_dev=_ptr(counter), e_dev=_ptr(m), e_s_n=_row_stride(m))
+        self._call("ptg_sde_resample_rows", C.byref(d), m.shape[0])
+        return noise
+
+    def _sde_rs_inputs(self, who, mean, latent, log_std, noise, clip_mean, deterministic):
+        """the checked inputs the forward and the backward share -> (mean [B], B, L, log_std [L], the flags, clip_mean)"""
+        torch = self._torch
+        m = check(self, who, "mean", _column(self, mean), dtypes=(torch.float32, torch.float64), shape=(None,), rule=step)
+        B = m.shape[0]
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch, mean has shape {tuple(mean.shape)}")
+        dt = (m.dtype,)
+        log_std, L = self._sde_log_std(who, log_std, dt)
+        check(self, who, "latent", latent, dtypes=dt, shape=(B, L), rule=wide_rows)
+        flags = _lib.SDE_RS_DETERMINISTIC if deterministic else 0
+        if not deterministic:
+            if noise is None:
+                raise ValueError(f"{who}: a stochastic call needs the exploration matrix (sde_resample / sde_resample_rows)")
+            if _dims(self, noise) == 1:
+                check(self, who, "noise (one shared row)", noise, dtypes=dt, shape=(L,), rule=contiguous)
+                flags |= _lib.SDE_RS_SHARED_E
+            else:
+                check(self, who, "noise", noise, dtypes=dt, shape=(B, L), rule=wide_rows)
+        c = float(clip_mean)
+        if not c > 0.0:
+            raise ValueError(f"{who}: clip_mean must be > 0 (float('inf'): no clipping), got {clip_mean}")
+        return m, B, L, log_std, flags, c
+
+    def sde_rsample(self, mean, latent, log_std, noise, clip_mean=2.0, deterministic=False, out=None, want_step_actions=False, want_logp=True,
+                    want_saved=True):
+        """gSDE's squashed head as SAC / TQC use it, in one launch (include/ptg_env.h: ptg_sde_rsample): a = tanh(hardtanh(mean,
+        +-clip_mean) + latent . E) and log pi(a) with SB3's tanh correction, the variance (latent^2) . exp(log_std)^2 + 1e-6.  mean [B]
+        / [B, 1] (any stride >= 1): the UNCLIPPED output of the mu layer; latent [B, L] (unit column stride, row stride >= L); log_std
+        [L] / [L, 1], not clamped; noise: ONE row [L] shared by the batch (training: sde_resample_rows) or a matrix [B, L] (collecting:
+        sde_resample), None when deterministic; all of ONE dtype, float32 or float64.  B is not tied to n_envs.  Returns
+        SdeRSample(actions, step_actions float32 or None, log_prob or None, saved float64 [B, 2] or None: what sde_rsample_backward
+        reads).  out: an earlier result, reused by a captured call (its None fields are not written).  No synchronisation; a non-finite
+        row or a NaN / +Inf log_std gives NaN outputs and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "sde_rsample"
+        m, B, L, log_std, flags, c = self._sde_rs_inputs(who, mean, latent, log_std, noise, clip_mean, deterministic)
+        specs = [("actions", True, m.dtype), ("step_actions", want_step_actions, torch.float32), ("log_prob", want_logp, m.dtype)]
+        if out is not None:
+            act, sact, lp, saved = _out_tuple(self, who, out, SdeRSample, stats=False)
+            if act is None:
+                raise ValueError(f"{who}: out.actions is missing")
+            for (name, _, dt), x in zip(specs, (act, sact, lp)):
+                check(self, who, f"out.{name}", _column(self, x), dtypes=(dt,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+            check(self, who, "out.saved", saved, dtypes=(torch.float64,), shape=(B, 2), rule=contiguous, optional=True, exc=ValueError)
+        else:
+            with torch.cuda.device(self.device):
+                act, sact, lp = (torch.empty(B, dtype=dt, device=self.device) if wanted else None for _, wanted, dt in specs)
+                saved = torch.empty((B, 2), dtype=torch.float64, device=self.device) if want_saved else None
+        stochastic = not deterministic
+        shared = bool(flags & _lib.SDE_RS_SHARED_E)
+        d = _lib.PtgSdeRs(flags=flags, in_dtype=_out_code(torch, m.dtype), latent_dim=L, batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
+                          latent_dev=_ptr(latent), latent_s_n=_row_stride(latent), e_dev=_ptr(noise if stochastic else None),
+                          e_s_n=_row_stride(noise) if stochastic and not shared else 0, log_std_dev=_ptr(log_std), clip_mean=c, act_dev=_ptr(act),
+                          step_act_dev=_ptr(sact), logp_dev=_ptr(lp), saved_dev=_ptr(saved))
+        self._call("ptg_sde_rsample", C.byref(d))
+        return SdeRSample(act, sact, lp, saved)
+
+    @staticmethod
+    def sde_rsample_backward_workspace_bytes(batch, latent_dim):
+        """ptg_sde_rsample_backward_workspace restated: 8 * L * (1 + n) with n blocks of 4 * ceil(B / 4096) rows; -1 outside the ranges
+        the library accepts"""
+        B, L = int(batch), int(latent_dim)
+        if not (1 <= B <= 2 ** 31 and 1 <= L <= _lib.MLP_MAX_WIDTH):
+            return -1
+        per = 4 * ((B - 1) // 4096 + 1)
+        return 8 * L * (1 + (B - 1) // per + 1)
+
+    def sde_rsample_backward_workspace(self, batch, latent_dim):
+        """the device scratch of sde_rsample_backward for a batch of this size and latent width (a uint8 tensor)"""
+        nbytes = self._L.ptg_sde_rsample_backward_workspace(int(batch), int(latent_dim))
+        if nbytes < 0:
+            raise ValueError(f"sde_rsample_backward_workspace: batch must be in [1, 2^31] and latent_dim in [1, {_lib.MLP_MAX_WIDTH}], got {batch}, {latent_dim}")
+        with self._torch.cuda.device(self.device):
+            return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
+
+    def sde_rsample_backward(self, mean, latent, log_std, noise, saved, grad_actions, grad_log_prob, clip_mean=2.0, deterministic=False,
+                             want_grad_latent=True, want_grad_log_std=True, out=None, workspace=None):
+        """The backward of sde_rsample (include/ptg_env.h: ptg_sde_rsample_backward): from the same mean, latent, log_std and noise, the
+        (noise, V) pairs the forward saved and the incoming gradients d L / d actions and d L / d log_prob ([B] or [B, 1], contiguous;
+        either may be None = 0, not both), the gradients with respect to the unclipped mean (0 outside the open interval
+        +-clip_mean), the latent [B, L] (through the variance and through the noise) and log_std [L] (through the variance and through
+        the matrix row E = exp(log_std) * z itself; only with one shared row).  Returns SdeRSampleGrad(grad_mean [B], grad_latent or
+        None, grad_log_std or None); out: such a tuple; workspace: sde_rsample_backward_workspace(B, L) or larger.  No synchronisation;
+        a bad row gives NaN gradients, a NaN grad_log_std and PTG_E_NONFINITE at the next sync()."""
+        torch = self._torch
+        who = "sde_rsample_backward"
+        m, B, L, log_std, flags, c = self._sde_rs_inputs(who, mean, latent, log_std, noise, clip_mean, deterministic)
+        dt = (m.dtype,)
+        shared = bool(flags & _lib.SDE_RS_SHARED_E)
+        check(self, who, "saved", saved, dtypes=(torch.float64,), shape=(B, 2), rule=contiguous)
+        ga = check(self, who, "grad_actions", _column(self, grad_actions), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        gl = check(self, who, "grad_log_prob", _column(self, grad_log_prob), dtypes=dt, shape=(B,), rule=contiguous, optional=True)
+        if ga is None and gl is None:
+            raise ValueError(f"{who}: grad_actions and grad_log_prob are both None")
+        if out is not None:
+            gm, g_lat, g_ls = _out_tuple(self, who, out, SdeRSampleGrad, stats=False)
+            gm = check(self, who, "out.grad_mean", _column(self, gm), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            check(self, who, "out.grad_latent", g_lat, dtypes=dt, shape=(B, L), rule=wide_rows, optional=True, exc=ValueError)
+            check(self, who, "out.grad_log_std", g_ls, dtypes=dt, shape=(L,), rule=contiguous, optional=True, exc=ValueError)
+            want_grad_log_std = g_ls is not None
+        if want_grad_log_std and not shared:
+            raise ValueError(f"{who}: the log_std gradient needs one shared noise row [L]; a collecting matrix (or no noise) has no such backward")
+        need = self.sde_rsample_backward_workspace_bytes(B, L)
+        if workspace is not None:
+            check(self, who, f"workspace (sde_rsample_backward_workspace({B}, {L}))", workspace, dtypes=(torch.uint8,), rule=contiguous, exc=ValueError)
+            if workspace.numel() < need:
+                raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} at latent width {L} needs {need}")
+        else:
+            workspace = self.sde_rsample_backward_workspace(B, L)
+        if out is None:
+            with torch.cuda.device(self.device):
+                gm = torch.empty(B, dtype=m.dtype, device=self.device)
+                g_lat = torch.empty((B, L), dtype=m.dtype, device=self.device) if want_grad_latent else None
+                g_ls = torch.empty(L, dtype=m.dtype, device=self.device) if want_grad_log_std else None
+        stochastic = not deterministic
+        d = _lib.PtgSdeRs(flags=flags, in_dtype=_out_code(torch, m.dtype), latent_dim=L, batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
+                          latent_dev=_ptr(latent), latent_s_n=_row_stride(latent), e_dev=_ptr(noise if stochastic else None),
+                          e_s_n=_row_stride(noise) if stochastic and not shared else 0, log_std_dev=_ptr(log_std), clip_mean=c, saved_dev=_ptr(saved),
+                          grad_act_dev=_ptr(ga), grad_logp_dev=_ptr(gl), grad_mean_dev=_ptr(gm), gm_s_n=max(gm.stride(0), 1),
+                          grad_latent_dev=_ptr(g_lat), gl_s_n=0 if g_lat is None else _row_stride(g_lat), grad_log_std_dev=_ptr(g_ls), ws_dev=_ptr(workspace))
+        self._call("ptg_sde_rsample_backward", C.byref(d))
+        return SdeRSampleGrad(gm, g_lat, g_ls)
 
     # ------------------------------------------------------------------ the TD loss of a replay batch and its gradients
     def td_loss_workspace(self, batch):
