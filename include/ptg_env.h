@@ -53,7 +53,8 @@ extern "C" {
                              *     ptg_sde_act, ptg_sde_policy_loss, ptg_sde_policy_loss_workspace (gSDE: the state-dependent exploration head while
                              *     collecting and its PPO / A2C loss); + ptg_sde_rs, ptg_sde_resample_rows, ptg_sde_rsample,
                              *     ptg_sde_rsample_backward, ptg_sde_rsample_backward_workspace (gSDE for SAC / TQC: the squashed head, its reparametrised sample and the
-                             *     backward); no earlier declaration changed */
+                             *     backward); + ptg_minibatch_drawn, ptg_minibatch_end_epoch (ptg_minibatch with its indices drawn on the device from an
+                             *     epoch cursor, so a PPO / A2C gradient step replays); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -439,6 +440,59 @@ int ptg_gae(ptg_env* env, const void* rew_dev, const void* val_dev, const uint8_
 int ptg_minibatch(ptg_env* env, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps,
                   const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev,
                   int n_cols, const void* const* cols_host, const int* col_bytes_host, void* const* cols_out_host, void* stream);
+
+/* ---- the same gather with its indices drawn on the device: a PPO / A2C gradient step that replays -------------------
+ * ptg_minibatch needs a permutation in memory and a different slice of it per batch, so a captured gather replays only after the
+ * host has rewritten its idx buffer.  ptg_minibatch_drawn takes no indices: row l of batch j of epoch c is
+ *   idx[l] = perm_c(j * batch + l),      (c, j) = cursor_dev[0], cursor_dev[1] read on the device (the launch may be a replay),
+ * where perm_c is a keyed bijection of [0, TN), TN = n_steps * n_envs, computed per row; no permutation exists in memory.  The value
+ * is SB3's swap_and_flatten index i = e * n_steps + t, exactly as ptg_minibatch reads it, and from the index on the two calls are
+ * one kernel: same strides, columns, byte-for-byte copy.  A trailing one-thread kernel advances the cursor in stream order, so one
+ * captured graph of gather -> networks -> loss -> backward -> optimiser replays through every minibatch of every epoch.
+ *
+ * perm_c, in integer arithmetic only (tests/minibatch_drawn_restatement.py restates these lines in Python integers), with
+ * h = lowbias32 and (w0, w1) the two words of ptg_replay_sample's keying above:
+ *   n = max(2, bit_length(TN - 1));  a = n / 2 (the low half's bits);  b = n - a (the high half's);  mask_a = 2^a - 1, mask_b = 2^b - 1
+ *   k_r = w0 of (seed, c, r) -- the chain above with the epoch c in the batch counter's place and the round r in the row's --
+ *         for r = 0 .. R - 1, R = PTG_MB_PERM_ROUNDS = 6
+ *   F(x): lo = x & mask_a; hi = (x >> a) & mask_b;
+ *         for r = 0 .. R - 1:  r even: hi ^= h(lo ^ k_r) & mask_b;   r odd: lo ^= h(hi ^ k_r) & mask_a;
+ *         F(x) = hi << a | lo                       (a Feistel network: every round is its own inverse, F a bijection of [0, 2^n))
+ *   perm_c(i) = the first of F(i), F(F(i)), ... that is below TN        (cycle-walking: i itself lies on that cycle, so the walk
+ *         ends and perm_c is a bijection of [0, TN); 2^n < 2 TN for TN > 2, so a walk is two applications on average; the longest
+ *         seen on the host was 17, at TN = 4097 over 40 epochs.  Only a wave's 16 index lanes walk.)
+ * R: the position-octile x value-octile counts over 400 epochs (a chi-square of 49 degrees of freedom, 99.9 % quantile 85.4;
+ * tests/test_minibatch_drawn_host.py) read, in the mean of 16 seeds at TN = 1218, 2796 for R = 2, 50.4 for R = 4 (every one below
+ * the bound), 43.0 for R = 6 and 43.4 for NumPy's own permutations: R = 4 passes the bound and is still told from uniform by this
+ * statistic, R = 6 is not, so 6 it is: four more hashes on 16 lanes of a wave.
+ * NOT a uniform draw from the TN! orders: 6 x 32 key bits per (seed, epoch) reach at most 2^192 of them, and at TN <= 6 whole
+ * classes of orders are over- or under-represented whatever R is.  What is claimed, and tested, is a bijection whose
+ * position-to-value statistics are indistinguishable from uniform at training sizes (TN = 203 and up).  SB3's NumPy stream is not
+ * reproduced, as it was not by ptg_minibatch, which takes any permutation.
+ *
+ *   cursor_dev         uint64[2] on the device, zero at creation: {epochs finished, batches drawn in this epoch}.  Behind the gather:
+ *                      j += 1; if (j >= TN / batch) { j = 0; epochs += 1; }.  Checkpoint and restore it as two integers.
+ *   seed               with the epoch, the permutation's key
+ *   idx_out_dev        (nullable) int64 [batch]: the indices used
+ *   everything else    as in ptg_minibatch
+ * A drawn index is below TN by construction.  A POSITION j * batch + l at or past TN -- a cursor restored past its epoch, or a
+ * batch size changed in the middle of one -- is never walked (no cycle through it is known to return below TN): its row, column
+ * entries and idx_out entry are left untouched and the next ptg_sync returns PTG_E_INDEX once; the cursor kernel then starts the
+ * next epoch.
+ * ptg_minibatch_end_epoch ends an epoch that was cut short (SB3's PPO leaves its epoch loop on target_kl): if (j != 0) { j = 0;
+ * epochs += 1; } -- a fresh epoch is left alone -- as one one-thread kernel.
+ * Both enqueue kernels only -- ptg_minibatch_drawn two, ptg_minibatch_end_epoch one: no host synchronisation, no allocation, no
+ * host memory in the launch; env state, the finished-episode ring and the ptg_vn_* statistics are untouched.
+ * PTG_E_INVALID (nothing enqueued): everything ptg_minibatch refuses but its indices; a NULL cursor_dev; n_steps * n_envs not a
+ * multiple of batch (a ragged last batch cannot feed a graph of fixed shape and stays with ptg_minibatch; the reference's PPO has
+ * n_steps = 21 * batch_size and A2C's batch is everything); n_steps * n_envs above PTG_MB_DRAWN_MAX_ROWS = 2^48, the bound up to
+ * which the restatement and the kernel are checked (the arithmetic itself holds for any n <= 64). */
+#define PTG_MB_PERM_ROUNDS 6
+#define PTG_MB_DRAWN_MAX_ROWS ((uint64_t)1 << 48)
+int ptg_minibatch_drawn(ptg_env* env, uint64_t* cursor_dev, uint64_t seed, int64_t* idx_out_dev, int64_t batch, int n_steps,
+                        const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev,
+                        int n_cols, const void* const* cols_host, const int* col_bytes_host, void* const* cols_out_host, void* stream);
+int ptg_minibatch_end_epoch(ptg_env* env, uint64_t* cursor_dev, void* stream);
 
 /* ---- the replay buffer of the off-policy algorithms on the device ---------------------------------------------------
  * Replaces: stable_baselines3.common.buffers.ReplayBuffer / DictReplayBuffer .add, .sample and ._get_samples (SB3 2.0.0a13,

@@ -20,6 +20,8 @@ ACT_I32, ACT_F32, ACT_I64 = 0, 1, 2
 OUT_F32, OUT_F64 = 0, 1
 E_INVALID, E_HIP, E_ACTION, E_RANGE, E_INDEX, E_NONFINITE = -1, -2, -3, -4, -5, -6
 MB_MAX_COLS = 8
+MB_PERM_ROUNDS = 6                       # PTG_MB_PERM_ROUNDS
+MB_DRAWN_MAX_ROWS = 1 << 48              # PTG_MB_DRAWN_MAX_ROWS
 OBS_ROW_MAJOR, OBS_FEATURE_MAJOR, OBS_SB3_FLAT, OBS_SPLIT = 0, 1, 2, 3
 HEAD_CATEGORICAL, HEAD_EPS_GREEDY, HEAD_GAUSSIAN = 0, 1, 2
 HEAD_DETERMINISTIC, HEAD_SQUASH = 1, 2
@@ -211,7 +213,7 @@ STATE_FIELDS = {"meth_state": 0, "i": 1, "j": 2, "k": 3, "hot_cold": 4, "standby
 EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_obs_dim", "ptg_last_error",
            "ptg_set_market_assignment", "ptg_set_episode_plan", "ptg_set_noise_tape", "ptg_set_noise_rng", "ptg_set_global_env_offset", "ptg_set_feature_pitch", "ptg_fill_noise_tape",
            "ptg_get_noise_tape", "ptg_reset", "ptg_step", "ptg_rollout", "ptg_rollout_info", "ptg_rollout_launches", "ptg_step_host", "ptg_host_layout", "ptg_host_layout_ex", "ptg_step_host_begin", "ptg_step_host_tail", "ptg_step_host_end", "ptg_step_host_finish", "ptg_host_buffers_changed", "ptg_profile", "ptg_profile_read", "ptg_profile_read_ex", "ptg_finished_dropped", "ptg_steps_to_episode_end", "ptg_note_replays", "ptg_set_replay_proof", "ptg_sync", "ptg_get_state", "ptg_set_state",
-           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_replay_add", "ptg_replay_sample", "ptg_rollout_buffer_begin", "ptg_rollout_buffer_add", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
+           "ptg_finished_episodes", "ptg_finished_episodes_dev", "ptg_episode_stats_dev", "ptg_vn_init", "ptg_vn_batch_moments", "ptg_vn_apply", "ptg_vn_clear_done", "ptg_vn_get", "ptg_vn_set", "ptg_gae", "ptg_minibatch", "ptg_minibatch_drawn", "ptg_minibatch_end_epoch", "ptg_replay_add", "ptg_replay_sample", "ptg_rollout_buffer_begin", "ptg_rollout_buffer_add", "ptg_act", "ptg_policy_loss_workspace", "ptg_policy_loss",
            "ptg_sde_resample", "ptg_sde_act", "ptg_sde_policy_loss_workspace", "ptg_sde_policy_loss",
            "ptg_sde_resample_rows", "ptg_sde_rsample", "ptg_sde_rsample_backward_workspace", "ptg_sde_rsample_backward",
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
@@ -331,6 +333,9 @@ def lib():
     L.ptg_gae.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
     L.ptg_minibatch.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp,
                                 C.c_int, C.POINTER(vp), i32p, C.POINTER(vp), vp]
+    L.ptg_minibatch_drawn.argtypes = [vp, vp, C.c_uint64, vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, vp,
+                                      C.c_int, C.POINTER(vp), i32p, C.POINTER(vp), vp]
+    L.ptg_minibatch_end_epoch.argtypes = [vp, vp, vp]
     L.ptg_replay_add.argtypes = [vp, C.POINTER(PtgReplay), vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.c_int64, vp]
     L.ptg_replay_sample.argtypes = [vp, C.POINTER(PtgReplay), vp, C.c_int64, C.c_uint64, vp, vp, C.POINTER(vp), C.c_int, vp, vp]
     L.ptg_rollout_buffer_begin.argtypes = [vp, C.POINTER(PtgRolloutBuffer), vp, C.c_int64, C.c_int64, C.c_int64, vp]

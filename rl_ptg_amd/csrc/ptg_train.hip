@@ -19,6 +19,7 @@
 #include "ptg_handle.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -290,18 +291,76 @@ __device__ __forceinline__ void mb_stream_rows(const char* __restrict__ src, siz
     }
 }
 
+// The two 32-bit words of row b of the c-th device-drawn batch under `seed` (include/ptg_env.h states the same lines; the tests
+// restate them in integer arithmetic): a chain of lowbias32 over the six 32-bit halves of (seed, c, b), then two finalisers.
+__device__ __forceinline__ unsigned long long rb_draw_word(unsigned long long seed, unsigned long long c, unsigned long long b)
+{
+    unsigned k = lowbias32((unsigned)seed ^ 0x9E3779B9u);
+    k = lowbias32(k + (unsigned)(seed >> 32));
+    k = lowbias32(k ^ (unsigned)c);
+    k = lowbias32(k + (unsigned)(c >> 32));
+    k = lowbias32(k ^ (unsigned)b);
+    k = lowbias32(k + (unsigned)(b >> 32));
+    const unsigned w0 = lowbias32(k ^ 0x85EBCA6Bu), w1 = lowbias32(k ^ 0xC2B2AE35u);
+    return ((unsigned long long)w0 << 32) | w1;
+}
+
+// The index source "drawn" of k_minibatch (include/ptg_env.h, ptg_minibatch_drawn, states the same lines; tests/
+// minibatch_drawn_restatement.py restates them in Python integers): no permutation exists in memory, row b of batch j of epoch c
+// is perm_c(j * B + b), a keyed bijection of [0, TN) -- PTG_MB_PERM_ROUNDS Feistel rounds over the a low and b high bits of the
+// position, applied until the result is below TN.  2^(a + b) < 2 TN for TN > 2, so a walk is two applications on average.
+struct MbDraw {                          // by value in the launch
+    const unsigned long long* cursor;    // {epochs finished, batches drawn in this epoch}, read here: the launch may be a replay
+    unsigned long long seed;
+    long long* idx_out;                  // nullable: the indices used, [B]
+    unsigned a, b;                       // bits of the low and of the high half
+};
+struct MbDrawn {};                       // k_minibatch's index type I for that source: idx is not read
+
+__device__ __forceinline__ unsigned long long mb_perm_rounds(unsigned long long x, const unsigned (&key)[PTG_MB_PERM_ROUNDS], unsigned a,
+                                                             unsigned mask_a, unsigned mask_b)
+{
+    unsigned lo = (unsigned)x & mask_a, hi = (unsigned)(x >> a) & mask_b;
+#pragma unroll
+    for (int r = 0; r < PTG_MB_PERM_ROUNDS; r += 2) {
+        hi ^= lowbias32(lo ^ key[r]) & mask_b;
+        lo ^= lowbias32(hi ^ key[r + 1]) & mask_a;
+    }
+    return ((unsigned long long)hi << a) | lo;
+}
+
 template <typename V, typename I>
 __global__ void __launch_bounds__(64 * MB_WAVES)
-k_minibatch(const I* __restrict__ idx, size_t B, unsigned T, size_t N, size_t TN, const char* __restrict__ obs, size_t s_t, size_t s_n,
-            size_t unit_stride, unsigned P, char* __restrict__ obs_out, MbCols cols, int* err)
+k_minibatch(const I* __restrict__ idx, MbDraw draw, size_t B, unsigned T, size_t N, size_t TN, const char* __restrict__ obs, size_t s_t,
+            size_t s_n, size_t unit_stride, unsigned P, char* __restrict__ obs_out, MbCols cols, int* err)
 {
+    constexpr bool DRAWN = std::is_same<I, MbDrawn>::value;
     const unsigned lane = threadIdx.x & 63u;
     const size_t b0 = ((size_t)blockIdx.x * MB_WAVES + (threadIdx.x >> 6)) * MB_ROWS;
     if (b0 >= B) return;                                     // wave-uniform
     const unsigned rows = (unsigned)min((size_t)MB_ROWS, B - b0);
     size_t off = (size_t)MB_BAD << 32;                       // byte offset of this lane's source row in the observation buffer
+    [[maybe_unused]] unsigned key[PTG_MB_PERM_ROUNDS];
+    if constexpr (DRAWN) {                                   // lane r makes round key r; every lane of the wave is still here
+        const unsigned mine = (unsigned)(rb_draw_word(draw.seed, draw.cursor[0], lane % PTG_MB_PERM_ROUNDS) >> 32);
+#pragma unroll
+        for (int r = 0; r < PTG_MB_PERM_ROUNDS; r++) key[r] = __shfl(mine, r);
+    }
     if (lane < rows) {
-        const long long v = (long long)idx[b0 + lane];
+        long long v;
+        if constexpr (DRAWN) {
+            // the position in the epoch's order; one at or past TN (a cursor set past its epoch, or a batch size changed within one)
+            // lies on no cycle that is known to return below TN, so it is never walked: rejected like an index out of range
+            const unsigned long long pos = draw.cursor[1] * B + b0 + lane;
+            const unsigned mask_a = (1u << draw.a) - 1u, mask_b = (1u << draw.b) - 1u;              // host: a <= b <= 24
+            unsigned long long x = pos;
+            if (pos < TN)
+                do x = mb_perm_rounds(x, key, draw.a, mask_a, mask_b); while (x >= TN);     // ends: pos itself lies on x's cycle
+            v = (long long)x;
+            if (draw.idx_out && pos < TN) draw.idx_out[b0 + lane] = v;
+        } else {
+            v = (long long)idx[b0 + lane];
+        }
         if ((unsigned long long)v < (unsigned long long)TN) {
             size_t e, t;
             if (TN <= 0xFFFFFFFFull) { const unsigned u = (unsigned)v; e = u / T; t = u - (unsigned)e * T; }   // the common case: 32-bit division
@@ -315,6 +374,21 @@ k_minibatch(const I* __restrict__ idx, size_t B, unsigned T, size_t N, size_t TN
         }
     }
     if (obs) mb_stream_rows<V>(obs, unit_stride, P, off, rows, lane, obs_out + b0 * P * sizeof(V));
+}
+
+// One thread, in stream order behind a drawn gather (as k_rb_bump is behind k_rb_sample): the next batch, and behind the epoch's last
+// one -- `batches` = TN / B -- the next epoch.  finish: ptg_minibatch_end_epoch, an epoch cut short ends; a fresh one is left alone.
+__global__ void k_mb_cursor(unsigned long long* cursor, unsigned long long batches, int finish)
+{
+    unsigned long long j = cursor[1];
+    if (finish) {
+        if (j == 0) return;
+    } else if (++j < batches) {
+        cursor[1] = j;
+        return;
+    }
+    cursor[0] += 1;
+    cursor[1] = 0;
 }
 
 // ================================================================================== replay buffer of the off-policy algorithms
@@ -417,20 +491,6 @@ k_rb_add_tr(RbAdd a)
 }
 
 __global__ void k_rb_bump(unsigned long long* word, unsigned long long by) { *word += by; }
-
-// The two 32-bit words of row b of the c-th device-drawn batch under `seed` (include/ptg_env.h states the same lines; the tests
-// restate them in integer arithmetic): a chain of lowbias32 over the six 32-bit halves of (seed, c, b), then two finalisers.
-__device__ __forceinline__ unsigned long long rb_draw_word(unsigned long long seed, unsigned long long c, unsigned long long b)
-{
-    unsigned k = lowbias32((unsigned)seed ^ 0x9E3779B9u);
-    k = lowbias32(k + (unsigned)(seed >> 32));
-    k = lowbias32(k ^ (unsigned)c);
-    k = lowbias32(k + (unsigned)(c >> 32));
-    k = lowbias32(k ^ (unsigned)b);
-    k = lowbias32(k + (unsigned)(b >> 32));
-    const unsigned w0 = lowbias32(k ^ 0x85EBCA6Bu), w1 = lowbias32(k ^ 0xC2B2AE35u);
-    return ((unsigned long long)w0 << 32) | w1;
-}
 
 // the Gaussian draw of a word pair (include/ptg_env.h, ptg_act): Box-Muller's cosine branch on u1 in (0, 1], u2 in [0, 1)
 __device__ __forceinline__ double rb_draw_normal(unsigned long long w)
@@ -2210,16 +2270,19 @@ struct AlFinal {
 };
 
 // ================================================================================================= host side
-// ptg_minibatch's launch: the unit type V (16-byte piece or element) and the index type are the kernel's two template axes
+// the gathers' launch: the unit type V (16-byte piece or element) and the index source -- the caller's int32 / int64 indices, or with
+// idx null the drawn ones -- are the kernel's two template axes
 template <typename V>
-void launch_minibatch(hipStream_t st, const void* idx, int idx_bytes, size_t B, unsigned T, size_t N, const char* obs, size_t s_t,
-                             size_t s_n, size_t unit_stride, unsigned P, char* obs_out, const MbCols& cols, int* err)
+void launch_minibatch(hipStream_t st, const void* idx, int idx_bytes, const MbDraw& draw, size_t B, unsigned T, size_t N, const char* obs,
+                             size_t s_t, size_t s_n, size_t unit_stride, unsigned P, char* obs_out, const MbCols& cols, int* err)
 {
     const dim3 grid((unsigned)((B + MB_ROWS * MB_WAVES - 1) / (MB_ROWS * MB_WAVES))), block(64 * MB_WAVES);
-    if (idx_bytes == 8)
-        hipLaunchKernelGGL((k_minibatch<V, long long>), grid, block, 0, st, (const long long*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+    if (!idx)
+        hipLaunchKernelGGL((k_minibatch<V, MbDrawn>), grid, block, 0, st, (const MbDrawn*)nullptr, draw, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+    else if (idx_bytes == 8)
+        hipLaunchKernelGGL((k_minibatch<V, long long>), grid, block, 0, st, (const long long*)idx, draw, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
     else
-        hipLaunchKernelGGL((k_minibatch<V, int>), grid, block, 0, st, (const int*)idx, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
+        hipLaunchKernelGGL((k_minibatch<V, int>), grid, block, 0, st, (const int*)idx, draw, B, T, N, N * T, obs, s_t, s_n, unit_stride, P, obs_out, cols, err);
 }
 
 // the blocks of a loss's batch at `per` rows a block (PL_BLOCK; the quantile loss: PL_WAVES), and the bytes of that many partials
@@ -2453,41 +2516,78 @@ int ptg_gae(ptg_env* h, const void* rew_dev, const void* val_dev, const uint8_t*
 }
 
 // ---- RolloutBuffer.get's _get_samples on the device: one minibatch per launch ---------------------------------------
-int ptg_minibatch(ptg_env* h, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps, const void* obs_dev, int64_t obs_s_t,
-                  int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev, int n_cols, const void* const* cols_host,
-                  const int* col_bytes_host, void* const* cols_out_host, void* stream)
+// ptg_minibatch (the caller's indices) and ptg_minibatch_drawn (`drawn`, idx_dev null: the indices drawn on the device, the cursor
+// advanced behind the gather) share every check and the launch; `who` names the entry point in the refusal
+static int minibatch_gather(ptg_env* h, const char* who, bool drawn, const void* idx_dev, int idx_bytes, uint64_t* cursor_dev, uint64_t seed,
+                            int64_t* idx_out_dev, int64_t batch, int n_steps, const void* obs_dev, int64_t obs_s_t, int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes,
+                            void* obs_out_dev, int n_cols, const void* const* cols_host, const int* col_bytes_host, void* const* cols_out_host, void* stream)
 {
-    if (!h || !idx_dev || batch < 1 || n_steps < 1) return set_err(h, PTG_E_INVALID, "ptg_minibatch: bad argument");
-    if (idx_bytes != 4 && idx_bytes != 8) return set_err(h, PTG_E_INVALID, "ptg_minibatch: indices must be int32 or int64");
-    if (batch > (int64_t)0x7FFFFFFF * (MB_ROWS * MB_WAVES)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: batch too large for one launch");
-    if ((obs_dev == nullptr) != (obs_out_dev == nullptr)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: observations and their output go together");
+    if (!h || (!drawn && !idx_dev) || batch < 1 || n_steps < 1) return set_err(h, PTG_E_INVALID, "%s: bad argument", who);
+    if (!drawn && idx_bytes != 4 && idx_bytes != 8) return set_err(h, PTG_E_INVALID, "%s: indices must be int32 or int64", who);
+    if (batch > (int64_t)0x7FFFFFFF * (MB_ROWS * MB_WAVES)) return set_err(h, PTG_E_INVALID, "%s: batch too large for one launch", who);
+    if ((obs_dev == nullptr) != (obs_out_dev == nullptr)) return set_err(h, PTG_E_INVALID, "%s: observations and their output go together", who);
     if (obs_dev && (obs_dim < 1 || obs_dim > (1 << 20) || (obs_bytes != 4 && obs_bytes != 8) || obs_s_t < 0 || obs_s_n < 0 || obs_s_f < 0))
-        return set_err(h, PTG_E_INVALID, "ptg_minibatch: bad observation shape (obs_dim in [1, 2^20], 4- or 8-byte elements, strides >= 0)");
-    if (n_cols < 0 || n_cols > PTG_MB_MAX_COLS) return set_err(h, PTG_E_INVALID, "ptg_minibatch: at most %d columns", PTG_MB_MAX_COLS);
-    if (n_cols > 0 && (!cols_host || !col_bytes_host || !cols_out_host)) return set_err(h, PTG_E_INVALID, "ptg_minibatch: null column arrays");
-    if (!obs_dev && n_cols == 0) return set_err(h, PTG_E_INVALID, "ptg_minibatch: nothing to gather");
+        return set_err(h, PTG_E_INVALID, "%s: bad observation shape (obs_dim in [1, 2^20], 4- or 8-byte elements, strides >= 0)", who);
+    if (n_cols < 0 || n_cols > PTG_MB_MAX_COLS) return set_err(h, PTG_E_INVALID, "%s: at most %d columns", who, PTG_MB_MAX_COLS);
+    if (n_cols > 0 && (!cols_host || !col_bytes_host || !cols_out_host)) return set_err(h, PTG_E_INVALID, "%s: null column arrays", who);
+    if (!obs_dev && n_cols == 0) return set_err(h, PTG_E_INVALID, "%s: nothing to gather", who);
     MbCols cols{};
     cols.n = n_cols;
     for (int c = 0; c < n_cols; c++) {
         const int s = col_bytes_host[c];
-        if (!cols_host[c] || !cols_out_host[c]) return set_err(h, PTG_E_INVALID, "ptg_minibatch: column %d or its output is null", c);
-        if (s != 1 && s != 2 && s != 4 && s != 8) return set_err(h, PTG_E_INVALID, "ptg_minibatch: column %d has %d-byte elements (1, 2, 4 or 8)", c, s);
+        if (!cols_host[c] || !cols_out_host[c]) return set_err(h, PTG_E_INVALID, "%s: column %d or its output is null", who, c);
+        if (s != 1 && s != 2 && s != 4 && s != 8) return set_err(h, PTG_E_INVALID, "%s: column %d has %d-byte elements (1, 2, 4 or 8)", who, c, s);
         cols.src[c] = cols_host[c]; cols.dst[c] = cols_out_host[c]; cols.bytes[c] = s;
+    }
+    const size_t B = (size_t)batch, N = (size_t)h->n, sz = (size_t)obs_bytes;
+    const unsigned T = (unsigned)n_steps;
+    MbDraw draw{};
+    if (drawn) {
+        const uint64_t TN = (uint64_t)N * T;
+        if (!cursor_dev) return set_err(h, PTG_E_INVALID, "%s: null cursor", who);
+        if (TN % B != 0) return set_err(h, PTG_E_INVALID, "%s: a batch of %lld rows does not divide the %llu rows of the rollout", who, (long long)batch, (unsigned long long)TN);
+        if (TN > PTG_MB_DRAWN_MAX_ROWS) return set_err(h, PTG_E_INVALID, "%s: more than 2^48 rows", who);
+        unsigned n = 2;                                      // max(2, bit_length(TN - 1))
+        while (n < 64 && ((TN - 1) >> n) != 0) n++;
+        draw = MbDraw{(const unsigned long long*)cursor_dev, (unsigned long long)seed, (long long*)idx_out_dev, n / 2, n - n / 2};
     }
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    const size_t B = (size_t)batch, N = (size_t)h->n, sz = (size_t)obs_bytes;
-    const unsigned T = (unsigned)n_steps;
     const char* obs = (const char*)obs_dev;
     char* out = (char*)obs_out_dev;
     const size_t row_bytes = obs_dev ? (size_t)obs_dim * sz : 0, s_t = (size_t)obs_s_t * sz, s_n = (size_t)obs_s_n * sz;
     // 16-byte pieces when a row is contiguous, a whole number of them, and every row starts on one -- in the buffer and in the output
     const bool wide = obs_dev && obs_s_f == 1 && row_bytes % 16 == 0 && s_t % 16 == 0 && s_n % 16 == 0 &&
                       (uintptr_t)obs % 16 == 0 && (uintptr_t)out % 16 == 0;
-    if (wide) launch_minibatch<uint4>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, 16, (unsigned)(row_bytes / 16), out, cols, h->P.err);
-    else if (obs_bytes == 8) launch_minibatch<uint64_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 8, (unsigned)obs_dim, out, cols, h->P.err);
-    else launch_minibatch<uint32_t>(st, idx_dev, idx_bytes, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 4, obs_dev ? (unsigned)obs_dim : 1u, out, cols, h->P.err);
+    if (wide) launch_minibatch<uint4>(st, idx_dev, idx_bytes, draw, B, T, N, obs, s_t, s_n, 16, (unsigned)(row_bytes / 16), out, cols, h->P.err);
+    else if (obs_bytes == 8) launch_minibatch<uint64_t>(st, idx_dev, idx_bytes, draw, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 8, (unsigned)obs_dim, out, cols, h->P.err);
+    else launch_minibatch<uint32_t>(st, idx_dev, idx_bytes, draw, B, T, N, obs, s_t, s_n, (size_t)obs_s_f * 4, obs_dev ? (unsigned)obs_dim : 1u, out, cols, h->P.err);
+    if (drawn) hipLaunchKernelGGL(k_mb_cursor, dim3(1), dim3(1), 0, st, (unsigned long long*)cursor_dev, (unsigned long long)((uint64_t)N * T / B), 0);
     return launch_check(h, "k_minibatch");
+}
+
+int ptg_minibatch(ptg_env* h, const void* idx_dev, int idx_bytes, int64_t batch, int n_steps, const void* obs_dev, int64_t obs_s_t,
+                  int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev, int n_cols, const void* const* cols_host,
+                  const int* col_bytes_host, void* const* cols_out_host, void* stream)
+{
+    return minibatch_gather(h, "ptg_minibatch", false, idx_dev, idx_bytes, nullptr, 0, nullptr, batch, n_steps, obs_dev, obs_s_t, obs_s_n, obs_s_f, obs_dim,
+                            obs_bytes, obs_out_dev, n_cols, cols_host, col_bytes_host, cols_out_host, stream);
+}
+
+int ptg_minibatch_drawn(ptg_env* h, uint64_t* cursor_dev, uint64_t seed, int64_t* idx_out_dev, int64_t batch, int n_steps, const void* obs_dev,
+                        int64_t obs_s_t, int64_t obs_s_n, int64_t obs_s_f, int obs_dim, int obs_bytes, void* obs_out_dev, int n_cols,
+                        const void* const* cols_host, const int* col_bytes_host, void* const* cols_out_host, void* stream)
+{
+    return minibatch_gather(h, "ptg_minibatch_drawn", true, nullptr, 0, cursor_dev, seed, idx_out_dev, batch, n_steps, obs_dev, obs_s_t, obs_s_n, obs_s_f,
+                            obs_dim, obs_bytes, obs_out_dev, n_cols, cols_host, col_bytes_host, cols_out_host, stream);
+}
+
+int ptg_minibatch_end_epoch(ptg_env* h, uint64_t* cursor_dev, void* stream)
+{
+    if (!h || !cursor_dev) return set_err(h, PTG_E_INVALID, "ptg_minibatch_end_epoch: null handle or cursor");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_mb_cursor, dim3(1), dim3(1), 0, as_stream(stream), (unsigned long long*)cursor_dev, 0ull, 1);
+    return launch_check(h, "k_mb_cursor");
 }
 
 // ---- ReplayBuffer.add / sample on the device, over the caller's rings ------------------------------------------------

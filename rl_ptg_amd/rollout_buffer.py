@@ -5,6 +5,9 @@ add() enqueue kernels of csrc/ptg_train.hip (ptg_rollout_buffer_begin: one; ptg_
 kernel behind it; include/ptg_env.h) on the current stream, without synchronisation, so a collect step -- DeviceMLP -> act_* ->
 HipEngine.step() -> add() -- can be captured into one graph and replayed: the row number lives on the device (cursor), like the step count of the hot kernels, so every replay stores
 at the next row.  compute_returns_and_advantage() and get() are HipEngine.gae / vn_normalize / minibatches over the same storage.
+next_batch() is HipEngine.minibatch_drawn over it: the minibatch is named by a second device cursor {epochs finished, batches drawn
+in this epoch} and its indices are computed in the gather, so a captured gradient step -- next_batch -> networks -> loss -> backward
+-> optimiser -- replays through every minibatch of every epoch.
 
 Row layout: obs_rows[0] is the observation the window's first action is chosen from (begin() puts it there), add() number t writes
 obs_rows[t + 1] and row t of every column.  After T adds obs_rows[:T] are SB3's `observations`, obs_rows[T] is `new_obs` -- what
@@ -17,8 +20,8 @@ RolloutBufferSamples = collections.namedtuple("RolloutBufferSamples", ["observat
 
 
 class DeviceRolloutBuffer:
-    def __init__(self, engine, n_steps, columns=None):
-        """n_steps vector steps of engine.n envs per window.  columns: name -> torch dtype of the per-step columns beside the
+    def __init__(self, engine, n_steps, columns=None, seed=0):
+        """n_steps vector steps of engine.n envs per window; seed keys the minibatch orders that next_batch() draws.  columns: name -> torch dtype of the per-step columns beside the
         observations; "actions" is required (default: actions int64 for a discrete engine, float32 for a continuous one, values
         float32, log_probs float32), "rewards" (the engine's out_dtype) and "dones" (uint8, step()'s own flags, which gae takes) are
         always kept; at most 8 in all.  compute_returns_and_advantage() needs a float32 or float64 "values" column -- advantages and
@@ -42,6 +45,7 @@ class DeviceRolloutBuffer:
             raise ValueError(f"DeviceRolloutBuffer: at most {_lib.MB_MAX_COLS} columns with 'rewards' and 'dones', got {len(cols)}")
         self.columns = cols
         self.names = list(cols)
+        self.seed = int(seed)
         T, N = self.n_steps, engine.n
         with torch.cuda.device(engine.device):
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=engine.device)
@@ -49,6 +53,7 @@ class DeviceRolloutBuffer:
             self.advantages = self.returns = None
             if "values" in cols:
                 self.advantages, self.returns = z((T, N), cols["values"]), z((T, N), cols["values"])
+            self.epoch = engine.new_epoch_cursor()
 
     # views with SB3's names
     observations = property(lambda self: self.storage.obs_rows[:self.n_steps])
@@ -71,7 +76,8 @@ class DeviceRolloutBuffer:
 
     def begin(self, obs=None):
         """SB3's reset(): obs (default engine.obs, what reset() or the last step() left) becomes row 0, the observation the window's
-        first action is chosen from, and the cursor returns to 0.  Enqueues on the current stream; nothing is copied to the host."""
+        first action is chosen from, and the cursor returns to 0.  Enqueues on the current stream; nothing is copied to the host.
+        The epoch cursor of next_batch() is left alone, so successive windows draw under successive epoch numbers."""
         self.engine.rollout_buffer_begin(self.storage, self.engine.obs if obs is None else obs)
 
     def add(self, obs, rewards, dones, **columns):
@@ -101,17 +107,61 @@ class DeviceRolloutBuffer:
         eng.gae(rew, self.values, self.dones, last_values, gamma, gae_lambda, adv=self.advantages, ret=self.returns)
         return self.advantages, self.returns
 
-    def get(self, batch_size=None, perm=None):
+    def _batch_columns(self):
+        return [self.actions, self.values, self.log_probs, self.advantages, self.returns]
+
+    def next_batch(self, batch_size=None, out=None):
+        """The next minibatch of the current epoch as RolloutBufferSamples, through HipEngine.minibatch_drawn: its indices are computed
+        on the device from (seed, epoch cursor) and the cursor advances behind the gather -- past the epoch's last batch to the next
+        epoch.  batch_size must divide T * N; None: one batch of everything (A2C).  out: the RolloutBufferSamples of an earlier
+        call, written again -- then nothing is allocated and the call may be captured into a graph and replayed, every replay
+        giving the next batch.  Does not synchronise and does not check that the window is full."""
+        self._need("next_batch", "values", "log_probs")
+        B = self.n_steps * self.n_envs if batch_size is None else batch_size
+        if out is not None and (not isinstance(out, tuple) or len(out) != len(RolloutBufferSamples._fields)):
+            raise ValueError("DeviceRolloutBuffer.next_batch: out must be the RolloutBufferSamples of an earlier call")
+        obs, outs, _ = self.engine.minibatch_drawn(self.epoch, B, obs=self.observations, columns=self._batch_columns(), seed=self.seed,
+                                                   obs_out=None if out is None else out[0], columns_out=None if out is None else list(out[1:]))
+        return RolloutBufferSamples(obs, *outs)
+
+    def end_epoch(self):
+        """End an epoch that was cut short (PPO's target_kl): the next next_batch() is batch 0 of the next epoch; after a whole epoch,
+        or before the first batch, nothing changes.  Enqueues one kernel; does not synchronise."""
+        self.engine.minibatch_end_epoch(self.epoch)
+
+    def epoch_cursor(self):
+        """(epochs finished, batches drawn in this epoch); synchronises"""
+        c, j = self.epoch.cpu().tolist()
+        return int(c), int(j)
+
+    def set_epoch_cursor(self, epochs, batches):
+        """restore epoch_cursor() from a checkpoint; the batch size that goes with `batches` is the caller's to keep"""
+        epochs, batches = int(epochs), int(batches)
+        if epochs < 0 or batches < 0:
+            raise ValueError(f"DeviceRolloutBuffer.set_epoch_cursor: ({epochs}, {batches}) must not be negative")
+        self.epoch.copy_(self._torch.tensor([epochs, batches], dtype=self._torch.int64))
+
+    def get(self, batch_size=None, perm=None, drawn=False):
         """SB3's get(): yields RolloutBufferSamples(observations [B, F], actions, old_values, old_log_prob, advantages, returns [B]
         each) through HipEngine.minibatches over a permutation of T * N (perm, or a fresh torch.randperm on the device); batch_size
-        None: one batch of everything (A2C).  Does not synchronise and does not check that the window is full."""
+        None: one batch of everything (A2C).  drawn=True: no permutation is made; the T * N / batch_size batches of one epoch come
+        from next_batch() with fresh outputs each, from the epoch cursor on (batch_size must divide T * N).  Does not synchronise and does not check that the window is full."""
         self._need("get", "values", "log_probs")
         torch = self._torch
+        if drawn:
+            if perm is not None:
+                raise ValueError("DeviceRolloutBuffer.get: perm and drawn=True exclude each other")
+            total = self.n_steps * self.n_envs
+            B = total if batch_size is None else int(batch_size)
+            if B < 1 or total % B:
+                raise ValueError(f"DeviceRolloutBuffer.get: drawn=True needs a batch_size that divides {total}, got {batch_size}")
+            for _ in range(total // B):
+                yield self.next_batch(B)
+            return
         if perm is None:
             with torch.cuda.device(self.engine.device):
                 perm = torch.randperm(self.n_steps * self.n_envs, device=self.engine.device)
-        cols = [self.actions, self.values, self.log_probs, self.advantages, self.returns]
-        for obs, outs in self.engine.minibatches(perm, batch_size, obs=self.observations, columns=cols):
+        for obs, outs in self.engine.minibatches(perm, batch_size, obs=self.observations, columns=self._batch_columns()):
             yield RolloutBufferSamples(obs, *outs)
 
     def cursor(self):

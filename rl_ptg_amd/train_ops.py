@@ -1,4 +1,4 @@
-"""TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers, the replay buffer, the
+"""TrainOps: the training-side operations of the engine -- reward normalisation (vn_*), GAE, minibatch gathers (indices given or drawn on the device), the replay buffer, the
 action heads, the policy loss, gSDE's matrix, head and loss, gSDE's squashed head for SAC / TQC with its backward, the TD losses, TQC's quantile loss, the training-time actor head, the actor losses, the forward and backward of the MLPs and the optimiser step.  Each method checks its tensors, marshals pointers and strides and makes one library call
 (include/ptg_env.h states the arithmetic, csrc/ptg_train.hip holds the kernels, csrc/ptg_mlp.hip those of mlp_forward and mlp_backward); none of them steps the environment.  HipEngine inherits them.
 
@@ -9,7 +9,7 @@ Every tensor argument goes through ONE checker, check(), which raises in a fixed
 tensor, a refused dtype, element size or element count), then ValueError for its shape, its strides, its device.  Nothing touches
 the library and no device memory is allocated before every check of a call has passed.  Relations between arguments (old_values
 iff clip_range_vf, done_col inside the columns ...) stay plain `if`s in the methods.  The blocks several ops share (_column,
-_critic_columns, _alpha_arg, _out_tuple, _no_tensor_twice, _workspace_arg; TrainOps._take_workspace, _fresh_like_quantiles, _mlp_net,
+_critic_columns, _alpha_arg, _out_tuple, _no_tensor_twice, _workspace_arg; TrainOps._take_workspace, _fresh_like_quantiles, _gather_args, _mlp_net,
 _call) stand once, next to check(), and are called at the point of the order where each op had its own copy.  The MLP ops go one step
 further: every check of one network stands once per direction (TrainOps._mlp_forward_net, _mlp_backward_net) and so does what follows the
 checks (_mlp_fwd_desc, _mlp_bwd_desc); mlp_forward / mlp_backward run them once, the grouped ops once per network behind "net i:"."""
@@ -383,15 +383,22 @@ class TrainOps:
         [column outputs [B]]), allocated when not given; row b is source row (idx[b] % T, idx[b] // T), byte for byte.  Outputs must
         not overlap inputs (not checked).  No synchronisation; an index out of range leaves its row untouched and makes the next
         sync() raise PtgError with code PTG_E_INDEX."""
-        torch = self._torch
-        who = "minibatch"
-        columns = list(columns)
-        check(self, who, "idx", idx, dtypes=(torch.int32, torch.int64), shape=(None,), rule=contiguous)
-        if obs is None and not columns:
-            raise ValueError("minibatch: neither observations nor columns given")
-        if len(columns) > _lib.MB_MAX_COLS:
-            raise ValueError(f"minibatch: at most {_lib.MB_MAX_COLS} columns, got {len(columns)}")
+        check(self, "minibatch", "idx", idx, dtypes=(self._torch.int32, self._torch.int64), shape=(None,), rule=contiguous)
         B = idx.shape[0]
+        T, tail, obs_out, outs = self._gather_args("minibatch", B, obs, columns, obs_out, columns_out)
+        self._call("ptg_minibatch", _ptr(idx), idx.element_size(), B, T, *tail)
+        return obs_out, outs
+
+    def _gather_args(self, who, B, obs, columns, obs_out, columns_out, rows_rule=None):
+        """what minibatch and minibatch_drawn check and pass alike: (T, the library call's arguments from obs_dev on, obs_out, the
+        column outputs), the outputs allocated when not given; rows_rule(T): the caller's own refusals once T is known, before
+        anything is allocated"""
+        torch = self._torch
+        columns = list(columns)
+        if obs is None and not columns:
+            raise ValueError(f"{who}: neither observations nor columns given")
+        if len(columns) > _lib.MB_MAX_COLS:
+            raise ValueError(f"{who}: at most {_lib.MB_MAX_COLS} columns, got {len(columns)}")
         T, F, s_t, s_n, s_f = None, 0, 0, 0, 0
         if obs is not None:                                 # a [T, ...] buffer of alloc_obs(T)
             check(self, who, "obs", obs, sizes=(4, 8), shape=(None, self.obs_dim, self.n) if self.feature_major else (None, self.n, self.obs_dim),
@@ -401,22 +408,65 @@ class TrainOps:
         for c, x in enumerate(columns):                     # without observations the first column sets T
             T = check(self, who, f"column {c}", x, sizes=(1, 2, 4, 8), shape=(T, self.n), rule=contiguous).shape[0]
         if columns_out is not None and len(columns_out) != len(columns):
-            raise ValueError(f"minibatch: {len(columns)} columns but {len(columns_out)} column outputs")
+            raise ValueError(f"{who}: {len(columns)} columns but {len(columns_out)} column outputs")
         if obs is None and obs_out is not None:
-            raise ValueError("minibatch: obs_out given without obs")
+            raise ValueError(f"{who}: obs_out given without obs")
         if obs is not None:
             check(self, who, "obs_out", obs_out, dtypes=(obs.dtype,), shape=(B, F), rule=contiguous, optional=True, exc=ValueError)
         for c, (x, o) in enumerate(zip(columns, columns_out or ())):
             check(self, who, f"output of column {c}", o, dtypes=(x.dtype,), shape=(B,), rule=contiguous, exc=ValueError)
+        if rows_rule is not None:
+            rows_rule(T)
         with torch.cuda.device(self.device):
             if obs is not None and obs_out is None:
                 obs_out = torch.empty((B, F), dtype=obs.dtype, device=self.device)
             outs = [torch.empty((B,), dtype=x.dtype, device=self.device) for x in columns] if columns_out is None else list(columns_out)
         k = len(columns)
         size = (C.c_int32 * max(k, 1))(*[x.element_size() for x in columns])
-        self._call("ptg_minibatch", _ptr(idx), idx.element_size(), B, T, _ptr(obs), s_t, s_n, s_f, F, obs.element_size() if obs is not None else 0,
-                   _ptr(obs_out), k, _ptr(columns), size, _ptr(outs))
-        return obs_out, outs
+        tail = (_ptr(obs), s_t, s_n, s_f, F, obs.element_size() if obs is not None else 0, _ptr(obs_out), k, _ptr(columns), size, _ptr(outs))
+        return T, tail, obs_out, outs
+
+    def new_epoch_cursor(self):
+        """The zeroed device cursor of the drawn minibatches: uint64 [2] {epochs finished, batches drawn in this epoch}, held as an
+        int64 tensor.  minibatch_drawn advances it on the device, so a replayed graph draws the next batch."""
+        return self._torch.zeros(2, dtype=self._torch.int64, device=self.device)
+
+    def _epoch_cursor(self, who, cursor):
+        return check(self, who, "cursor (new_epoch_cursor())", cursor, dtypes=(self._torch.int64,), numel=2, shape=(2,), rule=contiguous)
+
+    def minibatch_drawn(self, cursor, batch_size, obs=None, columns=(), seed=0, obs_out=None, columns_out=None, idx_out=None):
+        """minibatch() without a permutation in memory (include/ptg_env.h: ptg_minibatch_drawn, which states the arithmetic): the
+        indices of batch cursor[1] of epoch cursor[0] are computed in the gather itself from a keyed bijection of [0, T * N) under
+        (seed, epoch), and the cursor advances on the device behind it -- so ONE captured call replays through every minibatch of
+        every epoch.  batch_size must divide T * N (A2C: all of it); a ragged last batch stays with minibatch().  obs, columns,
+        obs_out, columns_out as in minibatch(); idx_out: int64 [B], receives the indices used.  Returns (obs_out, [column outputs],
+        idx_out).  No synchronisation; with every output given, no allocation.  Not SB3's NumPy stream and not a uniform draw from
+        all (T * N)! orders: a bijection whose position-to-value statistics pass for uniform at training sizes.
+        Cost (profiles/minibatch_drawn_cost.txt): called eagerly it is two launches and 2.5 - 4.2 us MORE device time
+        than minibatch() on a ready idx (parity had been expected and was missed at 3 of 4 shapes); what it buys is the replay -- an
+        epoch of PPO gradient steps at the reference's shape took 4.0 ms as 21 replays against 16.9 ms for the eager loop over get()."""
+        who = "minibatch_drawn"
+        self._epoch_cursor(who, cursor)
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"{who}: batch_size must be >= 1, got {batch_size}")
+        check(self, who, "idx_out", idx_out, dtypes=(self._torch.int64,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
+
+        def rows_rule(T):
+            if (T * self.n) % B:
+                raise ValueError(f"{who}: batch_size {B} does not divide the {T} x {self.n} rows of the rollout; a ragged last batch stays with minibatch()")
+            if T * self.n > _lib.MB_DRAWN_MAX_ROWS:
+                raise ValueError(f"{who}: {T} x {self.n} rows, more than 2^48")
+
+        T, tail, obs_out, outs = self._gather_args(who, B, obs, columns, obs_out, columns_out, rows_rule)
+        self._call("ptg_minibatch_drawn", _ptr(cursor), int(seed) & (2 ** 64 - 1), _ptr(idx_out), B, T, *tail)
+        return obs_out, outs, idx_out
+
+    def minibatch_end_epoch(self, cursor):
+        """End an epoch that was cut short (SB3's PPO leaves its epoch loop on target_kl): the next minibatch_drawn is batch 0 of the
+        next epoch.  A cursor on a fresh epoch is left alone.  One one-thread kernel on the current stream; no synchronisation."""
+        self._epoch_cursor("minibatch_end_epoch", cursor)
+        self._call("ptg_minibatch_end_epoch", _ptr(cursor))
 
     def minibatches(self, perm, batch_size, obs=None, columns=()):
         """SB3's RolloutBuffer.get loop: yields minibatch(perm[start : start + batch_size], obs, columns) for start = 0, batch_size,
