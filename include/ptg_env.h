@@ -54,7 +54,8 @@ extern "C" {
                              *     collecting and its PPO / A2C loss); + ptg_sde_rs, ptg_sde_resample_rows, ptg_sde_rsample,
                              *     ptg_sde_rsample_backward, ptg_sde_rsample_backward_workspace (gSDE for SAC / TQC: the squashed head, its reparametrised sample and the
                              *     backward); + ptg_minibatch_drawn, ptg_minibatch_end_epoch (ptg_minibatch with its indices drawn on the device from an
-                             *     epoch cursor, so a PPO / A2C gradient step replays); no earlier declaration changed */
+                             *     epoch cursor, so a PPO / A2C gradient step replays); + PTG_TRAIN_GROUP_MAX, ptg_policy_loss_group, ptg_optim_step_group (the loss
+                             *     and the optimiser step of up to eight independent PPO / A2C agents in the launches of one); no earlier declaration changed */
 #define PTG_N_TABLES 17
 #define PTG_N_COLS 7
 #define PTG_N_INFO 24
@@ -1669,6 +1670,49 @@ int ptg_mlp_backward(ptg_env* env, const ptg_mlp_bwd* d, void* stream);
 #define PTG_MLP_GROUP_MAX 8
 int ptg_mlp_group_forward(ptg_env* env, const ptg_mlp* nets, int32_t n_nets, void* stream);
 int ptg_mlp_group_backward(ptg_env* env, const ptg_mlp_bwd* nets, int32_t n_nets, void* stream);
+
+/* ---- the PPO / A2C loss and the optimiser step of up to eight independent agents in the launches of one: seeds, sweeps ------------------
+ * ptg_policy_loss_group and ptg_optim_step_group run n_members descriptors, 1 <= n_members <= PTG_TRAIN_GROUP_MAX, of the single calls
+ * (ptg_loss, ptg_optim, unchanged) in exactly the launches that ONE ptg_policy_loss / ptg_optim_step enqueues.  The descriptors are read
+ * during the call and travel by value in the launch arguments -- eight ptg_loss members take 8 x 208 = 1 664 bytes, eight ptg_optim
+ * members 8 x 136 = 1 088 bytes of the 4 096 bytes of kernel arguments a launch may have -- so a captured call holds no host memory.
+ * ptg_policy_loss_group:
+ *   must agree    kind, head, flags, n_actions, in_dtype, act_kind and batch of all members.
+ *   its own       every pointer and stride; clip_range, clip_range_vf, ent_coef, vf_coef; stats_dev, ws_dev (ptg_policy_loss_workspace(batch)
+ *                 bytes each), the gradient outputs and log_std_dev.
+ *   launches      those of the single call for that batch and those flags: one for batch <= 256 (k_pl_rows); beyond that the rows and
+ *                 the final merge (k_pl_rows, k_loss_final), with two more in front for the advantage moments under PTG_LOSS_NORM_ADV
+ *                 (k_pl_moments, k_pl_merge_group) -- the single call's kernels instantiated over the group's arguments.  The member is
+ *                 a grid dimension.
+ *   arithmetic    none of its own: a grouped kernel is the single kernel's text on the member its block index names, every member's sums run in the single
+ *                 call's order, which depends on batch alone, and nothing is reduced across members.  MEMBER i's stats, grad_in, grad_val
+ *                 AND grad_log_std ARE DEFINED AS WHAT ptg_policy_loss(&members[i]) WRITES, bit for bit.
+ * ptg_optim_step_group:
+ *   must agree    kind, flags and dtype of all members.
+ *   its own       the two tables, n_tensors, n_chunks; state_dev, lr_dev (NULL or not, per member), norm_dev, ws_dev
+ *                 (ptg_optim_workspace(n_chunks) bytes of that member); lr, beta1, beta2, eps, alpha, tau, max_norm.
+ *   launches      three (k_optim_norm, k_optim_head, k_optim_update, instantiated over the group's arguments), two without
+ *                 PTG_OPTIM_CLIP, one for PTG_OPTIM_POLYAK, whatever n_members is.  The norm pass and the update run on a grid of (the largest n_chunks of the
+ *                 group) x n_members workgroups: a workgroup owns one chunk of one member, and the surplus workgroups of a member with
+ *                 fewer chunks leave at once.  The head kernel runs one workgroup per member.
+ *   arithmetic    none of its own.  Each member keeps its own total norm and clip coefficient, its own step count and running products and
+ *                 its own partials in its own ws_dev, added in the order of its own tables: MEMBER i's PARAMETERS, STATES, TARGETS,
+ *                 GRADIENTS (PTG_OPTIM_ZERO_GRAD), state_dev AND norm_dev AFTER THE CALL ARE DEFINED AS THOSE AFTER
+ *                 ptg_optim_step(&members[i]), bit for bit.
+ * Members may share what is only read (an observation batch's columns, lr_dev).  Every output and scratch buffer of every member must be
+ * distinct from every other member's and from anything the call reads; two members with EQUAL stats_dev, ws_dev, grad_in_dev or
+ * grad_val_dev (the loss), state_dev, norm_dev or ws_dev (the optimiser) are refused, overlap beyond equal base pointers is NOT checked.
+ * The two error words of the handle are shared: a bad row or span in member i, or a non-finite norm in member i, raises the word as the
+ * single call does (the next ptg_sync returns PTG_E_INDEX or PTG_E_NONFINITE once) and changes nothing in any other member's outputs.
+ * No host synchronisation and no allocation; capturable into a hipGraph.
+ * PTG_E_INVALID (nothing enqueued, every output untouched; every check runs before the first launch): NULL handle or members;
+ * n_members outside [1, PTG_TRAIN_GROUP_MAX]; anything the single call refuses in a descriptor, the single call's text behind
+ * "member <i>: " (one checker serves both entries); a disagreement in one of the fields above, which names the field and the two
+ * members; two members that share one of the output or scratch pointers above.
+ * Not grouped: the gSDE, TD, quantile and actor losses; the minibatch gathers; members of different batch. */
+#define PTG_TRAIN_GROUP_MAX 8
+int ptg_policy_loss_group(ptg_env* env, const ptg_loss* members, int32_t n_members, void* stream);
+int ptg_optim_step_group(ptg_env* env, const ptg_optim* members, int32_t n_members, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

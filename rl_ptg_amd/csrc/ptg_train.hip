@@ -18,7 +18,10 @@
 // Built with -ffp-contract=off: the float64 expressions keep the reference's operand order.
 #include "ptg_handle.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <type_traits>
 
 namespace {
@@ -93,10 +96,10 @@ k_vn_moments(const OUT* __restrict__ rew, const uint8_t* __restrict__ done, int 
     if (live) returns[e] = ret;
 }
 
-__global__ void __launch_bounds__(64)
-k_vn_merge(const double* __restrict__ partials, int nW, double* __restrict__ moments)
+// one wave merges the nW partials of step t into moments[3 t ..]: k_vn_merge's body, and k_pl_merge_group's per member (t = 0)
+__device__ __forceinline__ void vn_merge_step(const double* __restrict__ partials, int nW, double* __restrict__ moments, int t)
 {
-    const int t = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     double c = 0.0, m = 0.0, M = 0.0;
     for (int w = lane; w < nW; w += 64) {
         const double* p = partials + ((size_t)t * nW + w) * 3;
@@ -111,6 +114,12 @@ k_vn_merge(const double* __restrict__ partials, int nW, double* __restrict__ mom
         else { chan_merge(ca, ma, Ma, cb, mb, Mb); c = ca; m = ma; M = Ma; }
     }
     if (lane == 0) { moments[t * 3 + 0] = c; moments[t * 3 + 1] = m; moments[t * 3 + 2] = M; }
+}
+
+__global__ void __launch_bounds__(64)
+k_vn_merge(const double* __restrict__ partials, int nW, double* __restrict__ moments)
+{
+    vn_merge_step(partials, nW, moments, blockIdx.x);
 }
 
 // RunningMeanStd.update_from_moments over the T steps of a launch; den[t] = sqrt(var + epsilon) AFTER the update of step t
@@ -1039,10 +1048,30 @@ __device__ __forceinline__ void loss_tail(double* v, double* sh, double* part, F
 
 // the last launch of a loss of more than one block, one block: step 3 of the order above, then FIN()(a, v) -- the loss's *_finish --
 // on thread 0.  A: the loss's launch arguments (their nblk is read), part: where the row kernel left its partials.
-template <typename A, typename FIN>
+// ---- grouped launches (include/ptg_env.h, ptg_policy_loss_group and ptg_optim_step_group) ----------------------
+// Up to PTG_TRAIN_GROUP_MAX calls in the launches of one: the single kernels' by-value arguments side by side in the kernel arguments
+// (eight LossArgs: 1 664 bytes, eight OptArgs: 1 088 bytes, of the 4 096 a launch takes), the member a grid dimension.  A kernel
+// that serves both is ONE text with the argument type as its last template parameter, ARGS: the call's own arguments (the default:
+// the single call's instantiation, whose code is what it was before the parameter existed, profiles/train_group_resources.txt) or a
+// TrainGroup of them, of which train_member picks the block's.  m[i] is read out of the kernel-argument segment at a computed offset,
+// no private copy.  Nothing is reduced across members and a member's sums run in the order its own call gives them: a member's bits
+// are those of its own call.
+template <typename T>
+struct TrainGroup {
+    T m[PTG_TRAIN_GROUP_MAX];
+};
+template <typename A>
+__device__ __forceinline__ const A& train_member(const A& a, unsigned) { return a; }
+template <typename A>
+__device__ __forceinline__ const A& train_member(const TrainGroup<A>& g, unsigned i) { return g.m[i]; }
+
+// ARGS = TrainGroup<A>: one block per member, and the partials are where FIN::partials(a) says (`part` is not read)
+template <typename A, typename FIN, typename ARGS = A>
 __global__ void __launch_bounds__(PL_BLOCK)
-k_loss_final(A a, const double* part)
+k_loss_final(ARGS args, const double* part)
 {
+    const A& a = train_member(args, blockIdx.x);
+    if constexpr (!std::is_same<ARGS, A>::value) part = FIN::partials(a);
     __shared__ double sh[PL_WAVES * PL_PITCH];
     double v[PL_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int b = threadIdx.x; b < a.nblk; b += PL_BLOCK) {
@@ -1056,10 +1085,12 @@ k_loss_final(A a, const double* part)
 // where the policy loss keeps its row partials: behind the merged moments and the moment partials
 __host__ __device__ __forceinline__ double* pl_partials(const LossArgs& a) { return a.ws + 4 + (size_t)a.nblk * 3; }
 
-template <typename IN>
+// blockIdx.x is the block within the batch, blockIdx.y (grouped) the member; the members agree in batch, so no block is surplus
+template <typename IN, typename ARGS = LossArgs>
 __global__ void __launch_bounds__(PL_BLOCK)
-k_pl_moments(LossArgs a)
+k_pl_moments(ARGS args)
 {
+    const LossArgs& a = train_member(args, blockIdx.y);
     __shared__ double sh[PL_WAVES * 3];
     const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
     double c, m, M;
@@ -1072,10 +1103,11 @@ k_pl_moments(LossArgs a)
 
 // ONE: the whole batch is this block (B <= PL_BLOCK): moments, rows and statistics in one launch.  Otherwise the moments come
 // merged from the workspace and the block leaves its partial sums there for k_loss_final.
-template <typename IN, bool ONE>
+template <typename IN, bool ONE, typename ARGS = LossArgs>
 __global__ void __launch_bounds__(PL_BLOCK)
-k_pl_rows(LossArgs a)
+k_pl_rows(ARGS args)
 {
+    const LossArgs& a = train_member(args, blockIdx.y);
     __shared__ double sh[PL_WAVES * PL_PITCH];
     const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
     const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
@@ -1096,12 +1128,23 @@ k_pl_rows(LossArgs a)
 
 template <typename IN>
 struct PlFinal {                         // mean and sd once more from the merged moments, as k_pl_rows<IN, false> has them
+    __device__ static const double* partials(const LossArgs& a) { return pl_partials(a); }
     __device__ void operator()(const LossArgs& a, const double* v) const
     {
         const bool norm = (a.flags & PTG_LOSS_NORM_ADV) != 0 && a.B > 1;
         pl_finish<IN>(a, v, norm ? a.ws[1] : 0.0, norm ? sqrt(a.ws[2] / ((double)a.B - 1.0)) : 1.0);
     }
 };
+
+static_assert(sizeof(TrainGroup<LossArgs>) == 8 * 208 && sizeof(TrainGroup<LossArgs>) + sizeof(const double*) <= 4096, "the launch takes 4 096 bytes of kernel arguments");
+
+// k_vn_merge's merge with the member as the block index: one wave per member merges its moment partials into its ws[0..2]
+__global__ void __launch_bounds__(64)
+k_pl_merge_group(const TrainGroup<LossArgs> g)
+{
+    const LossArgs& a = g.m[blockIdx.x];
+    vn_merge_step(a.ws + 4, a.nblk, a.ws, 0);
+}
 
 // ================================================================================== gSDE: the state-dependent exploration head and its loss
 // SB3's StateDependentNoiseDistribution with its on-policy defaults (include/ptg_env.h, ptg_sde_*, states the lines;
@@ -1615,10 +1658,17 @@ __device__ __forceinline__ double opt_block_sum(double v, double* sh)
     return s;
 }
 
-template <typename T>
+static_assert(sizeof(TrainGroup<OptArgs>) == 8 * 136 && sizeof(TrainGroup<OptArgs>) <= 4096, "the launch takes 4 096 bytes of kernel arguments");
+
+// Grouped (ARGS = TrainGroup<OptArgs>, above k_loss_final): the norm pass and the update run on a grid of (the largest chunk count of
+// the group, members); a workgroup owns chunk blockIdx.x of member blockIdx.y, and where that member has fewer chunks it returns
+// before any load and before the first barrier -- a test uniform over the workgroup.  The head kernel runs one workgroup per member.
+template <typename T, typename ARGS = OptArgs>
 __global__ void __launch_bounds__(OPT_BLOCK)
-k_optim_norm(OptArgs a)
+k_optim_norm(ARGS args)
 {
+    const OptArgs& a = train_member(args, blockIdx.y);
+    if (!std::is_same<ARGS, OptArgs>::value && blockIdx.x >= a.n_chunks) return;
     __shared__ double sh[OPT_WAVES];
     ptg_optim_tensor t; size_t e0; int n;
     const bool ok = opt_chunk(a, t, e0, n);                  // block-uniform
@@ -1633,9 +1683,11 @@ k_optim_norm(OptArgs a)
     if (threadIdx.x == 0) a.ws[OPT_WS_HEAD + blockIdx.x] = s;
 }
 
+template <typename ARGS = OptArgs>
 __global__ void __launch_bounds__(OPT_BLOCK)
-k_optim_head(OptArgs a)
+k_optim_head(ARGS args)
 {
+    const OptArgs& a = train_member(args, blockIdx.x);
     __shared__ double sh[OPT_WAVES];
     const bool clip = (a.flags & PTG_OPTIM_CLIP) != 0;
     double s = 0.0;
@@ -1665,10 +1717,12 @@ k_optim_head(OptArgs a)
     }
 }
 
-template <typename T>
+template <typename T, typename ARGS = OptArgs>
 __global__ void __launch_bounds__(OPT_BLOCK)
-k_optim_update(OptArgs a)
+k_optim_update(ARGS args)
 {
+    const OptArgs& a = train_member(args, blockIdx.y);
+    if (!std::is_same<ARGS, OptArgs>::value && blockIdx.x >= a.n_chunks) return;
     ptg_optim_tensor t; size_t e0; int n;
     if (!opt_chunk(a, t, e0, n) || n == 0) return;
     const bool polyak = a.kind == PTG_OPTIM_POLYAK, adam = a.kind == PTG_OPTIM_ADAM;
@@ -2388,6 +2442,158 @@ const char* rs_desc_error(const ptg_rs* d, bool backward)
     return nullptr;
 }
 
+// ---- what ptg_policy_loss / ptg_optim_step and their grouped entries share: one descriptor check, one set of launch arguments ------
+// a fault's text into `why`; true, so that a checker can `return train_fault(...)`
+__attribute__((format(printf, 3, 4))) bool train_fault(char* why, size_t cap, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(why, cap, fmt, ap);
+    va_end(ap);
+    return true;
+}
+
+// what a ptg_loss is refused for, in the single call's order; true with the text in `why`
+bool loss_desc_fault(const ptg_loss* d, char* why, size_t cap)
+{
+    if (d->kind != PTG_LOSS_PPO && d->kind != PTG_LOSS_A2C) return train_fault(why, cap, "unknown kind %d", d->kind);
+    if (d->head != PTG_HEAD_CATEGORICAL && d->head != PTG_HEAD_GAUSSIAN) return train_fault(why, cap, "head %d is neither categorical nor Gaussian", d->head);
+    if (d->flags & ~(PTG_LOSS_NORM_ADV | PTG_LOSS_CLIP_VF)) return train_fault(why, cap, "unknown flag in %d", d->flags);
+    const bool ppo = d->kind == PTG_LOSS_PPO, gauss = d->head == PTG_HEAD_GAUSSIAN, clipv = (d->flags & PTG_LOSS_CLIP_VF) != 0;
+    if (ptg_policy_loss_workspace(d->batch) < 0) return train_fault(why, cap, "batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (d->in_dtype != PTG_OUT_F32 && d->in_dtype != PTG_OUT_F64) return train_fault(why, cap, "in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->in_dev || !d->val_dev || !d->act_dev || !d->adv_dev || !d->ret_dev) return train_fault(why, cap, "null input, values, actions, advantages or returns");
+    if (ppo && !d->old_logp_dev) return train_fault(why, cap, "PPO needs old_logp_dev");
+    if (!d->stats_dev || !d->grad_in_dev || !d->grad_val_dev) return train_fault(why, cap, "null stats_dev, grad_in_dev or grad_val_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return train_fault(why, cap, "ws_dev is null or not aligned to 8 bytes");
+    if (clipv && !d->old_val_dev) return train_fault(why, cap, "PTG_LOSS_CLIP_VF needs old_val_dev");
+    if (d->val_s_n < 1 || d->gv_s_n < 1) return train_fault(why, cap, "val_s_n or gv_s_n < 1");
+    if (gauss) {
+        if (d->in_s_n < 1 || d->g_s_n < 1) return train_fault(why, cap, "in_s_n or g_s_n < 1");
+        if (!d->log_std_dev) return train_fault(why, cap, "the Gaussian head needs log_std_dev");
+    } else {
+        if (d->n_actions < 2 || d->n_actions > 32) return train_fault(why, cap, "n_actions outside [2, 32]");
+        if (d->in_s_n < d->n_actions || d->g_s_n < d->n_actions) return train_fault(why, cap, "in_s_n or g_s_n < n_actions");
+        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return train_fault(why, cap, "the categorical head takes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (d->grad_log_std_dev) return train_fault(why, cap, "grad_log_std_dev is the Gaussian head's");
+    }
+    if (ppo && !(d->clip_range >= 0.0)) return train_fault(why, cap, "clip_range is negative or NaN");
+    if (clipv && !(d->clip_range_vf >= 0.0)) return train_fault(why, cap, "clip_range_vf is negative or NaN");
+    return false;
+}
+
+LossArgs loss_args(ptg_env* h, const ptg_loss* d)
+{
+    LossArgs a{};
+    a.in = d->in_dev; a.s_n = (size_t)d->in_s_n; a.val = d->val_dev; a.v_s = (size_t)d->val_s_n;
+    a.act = d->act_dev; a.old_lp = d->old_logp_dev; a.adv = d->adv_dev; a.ret = d->ret_dev; a.old_val = d->old_val_dev; a.log_std = d->log_std_dev;
+    a.g_in = d->grad_in_dev; a.g_s = (size_t)d->g_s_n; a.g_val = d->grad_val_dev; a.gv_s = (size_t)d->gv_s_n; a.g_ls = d->grad_log_std_dev;
+    a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.eps = d->clip_range; a.eps_v = d->clip_range_vf; a.ent_coef = d->ent_coef; a.vf_coef = d->vf_coef;
+    a.B = (size_t)d->batch; a.A = d->n_actions; a.kind = d->kind; a.head = d->head; a.flags = d->flags; a.act_kind = d->act_kind;
+    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
+    a.err = h->P.err;
+    return a;
+}
+
+// what a ptg_optim is refused for, in the single call's order; true with the text in `why`
+bool optim_desc_fault(const ptg_optim* d, char* why, size_t cap)
+{
+    const int kind = d->kind, flags = d->flags;
+    if (kind != PTG_OPTIM_ADAM && kind != PTG_OPTIM_RMSPROP && kind != PTG_OPTIM_POLYAK) return train_fault(why, cap, "unknown kind %d", kind);
+    if (flags & ~(PTG_OPTIM_CLIP | PTG_OPTIM_TARGETS | PTG_OPTIM_ZERO_GRAD)) return train_fault(why, cap, "unknown flag in %d", flags);
+    const bool polyak = kind == PTG_OPTIM_POLYAK, clip = (flags & PTG_OPTIM_CLIP) != 0, targets = polyak || (flags & PTG_OPTIM_TARGETS) != 0;
+    if (polyak && (flags & (PTG_OPTIM_CLIP | PTG_OPTIM_ZERO_GRAD))) return train_fault(why, cap, "PTG_OPTIM_POLYAK reads no gradient: no PTG_OPTIM_CLIP, no PTG_OPTIM_ZERO_GRAD");
+    if (d->dtype != PTG_OUT_F32 && d->dtype != PTG_OUT_F64) return train_fault(why, cap, "dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (d->n_tensors < 1) return train_fault(why, cap, "n_tensors < 1");
+    if (ptg_optim_workspace(d->n_chunks) < 0) return train_fault(why, cap, "n_chunks %lld outside [1, 2^31)", (long long)d->n_chunks);
+    if (!d->tensors_dev || !d->chunks_dev) return train_fault(why, cap, "null tensor or chunk table");
+    if ((uintptr_t)d->tensors_dev % 8 != 0 || (uintptr_t)d->chunks_dev % 8 != 0) return train_fault(why, cap, "a table is not aligned to 8 bytes");
+    if (targets && !(d->tau >= 0.0 && d->tau <= 1.0)) return train_fault(why, cap, "tau outside [0, 1] (or NaN)");
+    if (!polyak) {
+        if (!d->state_dev) return train_fault(why, cap, "null state_dev");
+        if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return train_fault(why, cap, "ws_dev is null or not aligned to 8 bytes");
+        if (!d->lr_dev && !(d->lr >= 0.0 && std::isfinite(d->lr))) return train_fault(why, cap, "lr is negative or not finite (and lr_dev is null)");
+        if (!(d->eps >= 0.0) || !std::isfinite(d->eps)) return train_fault(why, cap, "eps is negative or not finite");
+        if (kind == PTG_OPTIM_ADAM && (!(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0)))
+            return train_fault(why, cap, "a beta outside [0, 1)");
+        if (kind == PTG_OPTIM_RMSPROP && !(d->alpha >= 0.0 && std::isfinite(d->alpha))) return train_fault(why, cap, "alpha is negative or not finite");
+        if (clip && !d->norm_dev) return train_fault(why, cap, "PTG_OPTIM_CLIP needs norm_dev");
+        if (clip && !(d->max_norm >= 0.0)) return train_fault(why, cap, "max_norm is negative or NaN");
+    }
+    return false;
+}
+
+OptArgs optim_args(ptg_env* h, const ptg_optim* d)
+{
+    OptArgs a{};
+    a.tensors = (const ptg_optim_tensor*)d->tensors_dev; a.chunks = (const ptg_optim_span*)d->chunks_dev;
+    a.ws = (double*)d->ws_dev; a.state = d->state_dev; a.lr_dev = d->lr_dev; a.norm = d->norm_dev;
+    a.lr = d->lr; a.b1 = d->beta1; a.b2 = d->beta2; a.eps = d->eps; a.alpha = d->alpha; a.tau = d->tau; a.max_norm = d->max_norm;
+    a.n_tensors = (long long)d->n_tensors; a.n_chunks = (unsigned)d->n_chunks; a.kind = d->kind; a.flags = d->flags; a.err = h->P.err;
+    return a;
+}
+
+// What a single and a grouped entry refuse before the first launch, in one order: the array, the count, each descriptor's own fault
+// (grouped: behind "member i: "), then, grouped, `agree` -- a disagreement with member 0, or an output that two members share.  0, or
+// the error set in h
+template <typename D, typename Fault, typename Agree>
+int train_refuse(ptg_env* h, const char* who, const D* members, int n_members, bool grouped, Fault fault, Agree agree)
+{
+    if (!members) return set_err(h, PTG_E_INVALID, "%s: null descriptor%s", who, grouped ? " array" : "");
+    if (n_members < 1 || n_members > PTG_TRAIN_GROUP_MAX) return set_err(h, PTG_E_INVALID, "%s: n_members %d outside [1, %d]", who, n_members, PTG_TRAIN_GROUP_MAX);
+    char why[240];
+    for (int i = 0; i < n_members; i++) {
+        if (!fault(&members[i], why, sizeof why)) continue;
+        return grouped ? set_err(h, PTG_E_INVALID, "%s: member %d: %s", who, i, why) : set_err(h, PTG_E_INVALID, "%s: %s", who, why);
+    }
+    if (grouped && agree(why, sizeof why)) return set_err(h, PTG_E_INVALID, "%s: %s", who, why);
+    return 0;
+}
+
+// two members that name one output or scratch buffer: the half of "outputs must not overlap" that the host can see
+bool train_shared(const void* p, const void* q, const char* field, int i, int j, char* why, size_t cap)
+{
+    return p && p == q ? train_fault(why, cap, "members %d and %d share %s", i, j, field) : false;
+}
+
+#define TRAIN_AGREE(field, fmt, cast)                                                                                                                    \
+    if (b.field != a.field) return train_fault(why, cap, "members 0 and %d disagree in " #field ": " fmt " and " fmt, i, (cast)a.field, (cast)b.field)
+#define TRAIN_DISTINCT(field)                                                                                                                            \
+    if (train_shared(m[i].field, m[j].field, #field, j, i, why, cap)) return true
+
+bool loss_group_fault(const ptg_loss* m, int n, char* why, size_t cap)
+{
+    const ptg_loss& a = m[0];
+    for (int i = 1; i < n; i++) {
+        const ptg_loss& b = m[i];
+        TRAIN_AGREE(kind, "%d", int); TRAIN_AGREE(head, "%d", int); TRAIN_AGREE(flags, "%d", int); TRAIN_AGREE(n_actions, "%d", int);
+        TRAIN_AGREE(in_dtype, "%d", int); TRAIN_AGREE(act_kind, "%d", int); TRAIN_AGREE(batch, "%lld", long long);
+    }
+    for (int i = 1; i < n; i++)
+        for (int j = 0; j < i; j++) {
+            TRAIN_DISTINCT(stats_dev); TRAIN_DISTINCT(ws_dev); TRAIN_DISTINCT(grad_in_dev); TRAIN_DISTINCT(grad_val_dev);
+        }
+    return false;
+}
+
+bool optim_group_fault(const ptg_optim* m, int n, char* why, size_t cap)
+{
+    const ptg_optim& a = m[0];
+    for (int i = 1; i < n; i++) {
+        const ptg_optim& b = m[i];
+        TRAIN_AGREE(kind, "%d", int); TRAIN_AGREE(flags, "%d", int); TRAIN_AGREE(dtype, "%d", int);
+    }
+    if (a.kind == PTG_OPTIM_POLYAK) return false;             // it reads no state, norm or scratch
+    for (int i = 1; i < n; i++)
+        for (int j = 0; j < i; j++) {
+            TRAIN_DISTINCT(state_dev); TRAIN_DISTINCT(norm_dev); TRAIN_DISTINCT(ws_dev);
+        }
+    return false;
+}
+#undef TRAIN_AGREE
+#undef TRAIN_DISTINCT
+
 }  // namespace
 
 extern "C" {
@@ -2820,54 +3026,54 @@ int64_t ptg_policy_loss_workspace(int64_t batch)
     return (4 + nblk * 3) * (int64_t)sizeof(double) + loss_partials_bytes(nblk);
 }
 
-int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream)
+// THE policy loss: ptg_policy_loss is this walk over one descriptor with the single kernels, ptg_policy_loss_group the same walk with
+// the grouped ones.  `grouped` is the entry that was called, not n_members > 1: a group of one launches the grouped kernels
+static int policy_loss_walk(ptg_env* h, const char* who, const ptg_loss* members, int n_members, bool grouped, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null descriptor");
-    if (d->kind != PTG_LOSS_PPO && d->kind != PTG_LOSS_A2C) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: unknown kind %d", d->kind);
-    if (d->head != PTG_HEAD_CATEGORICAL && d->head != PTG_HEAD_GAUSSIAN) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: head %d is neither categorical nor Gaussian", d->head);
-    if (d->flags & ~(PTG_LOSS_NORM_ADV | PTG_LOSS_CLIP_VF)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: unknown flag in %d", d->flags);
-    const bool ppo = d->kind == PTG_LOSS_PPO, gauss = d->head == PTG_HEAD_GAUSSIAN, clipv = (d->flags & PTG_LOSS_CLIP_VF) != 0;
-    if (ptg_policy_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
-    if (d->in_dtype != PTG_OUT_F32 && d->in_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
-    if (!d->in_dev || !d->val_dev || !d->act_dev || !d->adv_dev || !d->ret_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null input, values, actions, advantages or returns");
-    if (ppo && !d->old_logp_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: PPO needs old_logp_dev");
-    if (!d->stats_dev || !d->grad_in_dev || !d->grad_val_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: null stats_dev, grad_in_dev or grad_val_dev");
-    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: ws_dev is null or not aligned to 8 bytes");
-    if (clipv && !d->old_val_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: PTG_LOSS_CLIP_VF needs old_val_dev");
-    if (d->val_s_n < 1 || d->gv_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: val_s_n or gv_s_n < 1");
-    if (gauss) {
-        if (d->in_s_n < 1 || d->g_s_n < 1) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_s_n or g_s_n < 1");
-        if (!d->log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: the Gaussian head needs log_std_dev");
-    } else {
-        if (d->n_actions < 2 || d->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: n_actions outside [2, 32]");
-        if (d->in_s_n < d->n_actions || d->g_s_n < d->n_actions) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: in_s_n or g_s_n < n_actions");
-        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: the categorical head takes PTG_ACT_I32 or PTG_ACT_I64 actions");
-        if (d->grad_log_std_dev) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: grad_log_std_dev is the Gaussian head's");
-    }
-    if (ppo && !(d->clip_range >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: clip_range is negative or NaN");
-    if (clipv && !(d->clip_range_vf >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_policy_loss: clip_range_vf is negative or NaN");
+    if (int rc = train_refuse(h, who, members, n_members, grouped, loss_desc_fault,
+                              [&](char* why, size_t cap) { return loss_group_fault(members, n_members, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    LossArgs a{};
-    a.in = d->in_dev; a.s_n = (size_t)d->in_s_n; a.val = d->val_dev; a.v_s = (size_t)d->val_s_n;
-    a.act = d->act_dev; a.old_lp = d->old_logp_dev; a.adv = d->adv_dev; a.ret = d->ret_dev; a.old_val = d->old_val_dev; a.log_std = d->log_std_dev;
-    a.g_in = d->grad_in_dev; a.g_s = (size_t)d->g_s_n; a.g_val = d->grad_val_dev; a.gv_s = (size_t)d->gv_s_n; a.g_ls = d->grad_log_std_dev;
-    a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
-    a.eps = d->clip_range; a.eps_v = d->clip_range_vf; a.ent_coef = d->ent_coef; a.vf_coef = d->vf_coef;
-    a.B = (size_t)d->batch; a.A = d->n_actions; a.kind = d->kind; a.head = d->head; a.flags = d->flags; a.act_kind = d->act_kind;
-    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
-    a.err = h->P.err;
+    const ptg_loss* d = &members[0];     // batch, dtype and flags: the group's
+    TrainGroup<LossArgs> g{};
+    for (int i = 0; i < n_members; i++) g.m[i] = loss_args(h, &members[i]);
+    const LossArgs& a = g.m[0];
     const bool f64 = d->in_dtype == PTG_OUT_F64, norm = (d->flags & PTG_LOSS_NORM_ADV) != 0 && d->batch > 1;
-    if (a.nblk > 1 && norm) {                                // PPO's minibatch is one block, which takes its moments itself
-        const dim3 grid((unsigned)a.nblk), block(PL_BLOCK);
-        if (f64) hipLaunchKernelGGL(k_pl_moments<double>, grid, block, 0, st, a);
-        else hipLaunchKernelGGL(k_pl_moments<float>, grid, block, 0, st, a);
-        hipLaunchKernelGGL(k_vn_merge, dim3(1), dim3(64), 0, st, (const double*)(a.ws + 4), a.nblk, a.ws);
+    const dim3 block(PL_BLOCK), rows((unsigned)a.nblk, (unsigned)n_members), per_member((unsigned)n_members);
+    if (!grouped) {
+        if (a.nblk > 1 && norm) {                            // PPO's minibatch is one block, which takes its moments itself
+            const dim3 grid((unsigned)a.nblk);
+            if (f64) hipLaunchKernelGGL(k_pl_moments<double>, grid, block, 0, st, a);
+            else hipLaunchKernelGGL(k_pl_moments<float>, grid, block, 0, st, a);
+            hipLaunchKernelGGL(k_vn_merge, dim3(1), dim3(64), 0, st, (const double*)(a.ws + 4), a.nblk, a.ws);
+        }
+        if (f64) launch_loss<PlFinal<double>>(st, a, pl_partials(a), k_pl_rows<double, true>, k_pl_rows<double, false>);
+        else launch_loss<PlFinal<float>>(st, a, pl_partials(a), k_pl_rows<float, true>, k_pl_rows<float, false>);
+        return launch_check(h, "k_pl_rows");
     }
-    if (f64) launch_loss<PlFinal<double>>(st, a, pl_partials(a), k_pl_rows<double, true>, k_pl_rows<double, false>);
-    else launch_loss<PlFinal<float>>(st, a, pl_partials(a), k_pl_rows<float, true>, k_pl_rows<float, false>);
-    return launch_check(h, "k_pl_rows");
+    if (a.nblk > 1 && norm) {
+        if (f64) hipLaunchKernelGGL((k_pl_moments<double, TrainGroup<LossArgs>>), rows, block, 0, st, g);
+        else hipLaunchKernelGGL((k_pl_moments<float, TrainGroup<LossArgs>>), rows, block, 0, st, g);
+        hipLaunchKernelGGL(k_pl_merge_group, per_member, dim3(64), 0, st, g);
+    }
+    if (a.nblk == 1) {
+        if (f64) hipLaunchKernelGGL((k_pl_rows<double, true, TrainGroup<LossArgs>>), rows, block, 0, st, g);
+        else hipLaunchKernelGGL((k_pl_rows<float, true, TrainGroup<LossArgs>>), rows, block, 0, st, g);
+    } else {
+        if (f64) hipLaunchKernelGGL((k_pl_rows<double, false, TrainGroup<LossArgs>>), rows, block, 0, st, g);
+        else hipLaunchKernelGGL((k_pl_rows<float, false, TrainGroup<LossArgs>>), rows, block, 0, st, g);
+        if (f64) hipLaunchKernelGGL((k_loss_final<LossArgs, PlFinal<double>, TrainGroup<LossArgs>>), per_member, block, 0, st, g, (const double*)nullptr);
+        else hipLaunchKernelGGL((k_loss_final<LossArgs, PlFinal<float>, TrainGroup<LossArgs>>), per_member, block, 0, st, g, (const double*)nullptr);
+    }
+    return launch_check(h, "k_pl_rows (grouped)");
+}
+
+int ptg_policy_loss(ptg_env* h, const ptg_loss* d, void* stream) { return policy_loss_walk(h, "ptg_policy_loss", d, 1, false, stream); }
+
+int ptg_policy_loss_group(ptg_env* h, const ptg_loss* members, int32_t n_members, void* stream)
+{
+    return policy_loss_walk(h, "ptg_policy_loss_group", members, n_members, true, stream);
 }
 
 // ---- gSDE: the exploration matrix, the collecting head, the PPO / A2C loss ----------------------------------------------
@@ -3084,51 +3290,56 @@ int64_t ptg_optim_workspace(int64_t n_chunks)
     return (OPT_WS_HEAD + n_chunks) * (int64_t)sizeof(double);
 }
 
-int ptg_optim_step(ptg_env* h, const ptg_optim* d, void* stream)
+// THE optimiser step: ptg_optim_step is this walk over one descriptor with the single kernels, ptg_optim_step_group the same walk with
+// the grouped ones on a grid of (the largest chunk count, members)
+static int optim_step_walk(ptg_env* h, const char* who, const ptg_optim* members, int n_members, bool grouped, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_optim_step: null descriptor");
-    const int kind = d->kind, flags = d->flags;
-    if (kind != PTG_OPTIM_ADAM && kind != PTG_OPTIM_RMSPROP && kind != PTG_OPTIM_POLYAK) return set_err(h, PTG_E_INVALID, "ptg_optim_step: unknown kind %d", kind);
-    if (flags & ~(PTG_OPTIM_CLIP | PTG_OPTIM_TARGETS | PTG_OPTIM_ZERO_GRAD)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: unknown flag in %d", flags);
-    const bool polyak = kind == PTG_OPTIM_POLYAK, clip = (flags & PTG_OPTIM_CLIP) != 0, targets = polyak || (flags & PTG_OPTIM_TARGETS) != 0;
-    if (polyak && (flags & (PTG_OPTIM_CLIP | PTG_OPTIM_ZERO_GRAD))) return set_err(h, PTG_E_INVALID, "ptg_optim_step: PTG_OPTIM_POLYAK reads no gradient: no PTG_OPTIM_CLIP, no PTG_OPTIM_ZERO_GRAD");
-    if (d->dtype != PTG_OUT_F32 && d->dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_optim_step: dtype must be PTG_OUT_F32 or PTG_OUT_F64");
-    if (d->n_tensors < 1) return set_err(h, PTG_E_INVALID, "ptg_optim_step: n_tensors < 1");
-    if (ptg_optim_workspace(d->n_chunks) < 0) return set_err(h, PTG_E_INVALID, "ptg_optim_step: n_chunks %lld outside [1, 2^31)", (long long)d->n_chunks);
-    if (!d->tensors_dev || !d->chunks_dev) return set_err(h, PTG_E_INVALID, "ptg_optim_step: null tensor or chunk table");
-    if ((uintptr_t)d->tensors_dev % 8 != 0 || (uintptr_t)d->chunks_dev % 8 != 0) return set_err(h, PTG_E_INVALID, "ptg_optim_step: a table is not aligned to 8 bytes");
-    if (targets && !(d->tau >= 0.0 && d->tau <= 1.0)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: tau outside [0, 1] (or NaN)");
-    if (!polyak) {
-        if (!d->state_dev) return set_err(h, PTG_E_INVALID, "ptg_optim_step: null state_dev");
-        if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_optim_step: ws_dev is null or not aligned to 8 bytes");
-        if (!d->lr_dev && !(d->lr >= 0.0 && std::isfinite(d->lr))) return set_err(h, PTG_E_INVALID, "ptg_optim_step: lr is negative or not finite (and lr_dev is null)");
-        if (!(d->eps >= 0.0) || !std::isfinite(d->eps)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: eps is negative or not finite");
-        if (kind == PTG_OPTIM_ADAM && (!(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0)))
-            return set_err(h, PTG_E_INVALID, "ptg_optim_step: a beta outside [0, 1)");
-        if (kind == PTG_OPTIM_RMSPROP && !(d->alpha >= 0.0 && std::isfinite(d->alpha))) return set_err(h, PTG_E_INVALID, "ptg_optim_step: alpha is negative or not finite");
-        if (clip && !d->norm_dev) return set_err(h, PTG_E_INVALID, "ptg_optim_step: PTG_OPTIM_CLIP needs norm_dev");
-        if (clip && !(d->max_norm >= 0.0)) return set_err(h, PTG_E_INVALID, "ptg_optim_step: max_norm is negative or NaN");
-    }
+    if (int rc = train_refuse(h, who, members, n_members, grouped, optim_desc_fault,
+                              [&](char* why, size_t cap) { return optim_group_fault(members, n_members, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    OptArgs a{};
-    a.tensors = (const ptg_optim_tensor*)d->tensors_dev; a.chunks = (const ptg_optim_span*)d->chunks_dev;
-    a.ws = (double*)d->ws_dev; a.state = d->state_dev; a.lr_dev = d->lr_dev; a.norm = d->norm_dev;
-    a.lr = d->lr; a.b1 = d->beta1; a.b2 = d->beta2; a.eps = d->eps; a.alpha = d->alpha; a.tau = d->tau; a.max_norm = d->max_norm;
-    a.n_tensors = (long long)d->n_tensors; a.n_chunks = (unsigned)d->n_chunks; a.kind = kind; a.flags = flags; a.err = h->P.err;
-    const bool f64 = d->dtype == PTG_OUT_F64;
-    const dim3 grid((unsigned)d->n_chunks), block(OPT_BLOCK);
+    const ptg_optim* d = &members[0];    // kind, flags and dtype: the group's
+    const bool polyak = d->kind == PTG_OPTIM_POLYAK, clip = (d->flags & PTG_OPTIM_CLIP) != 0, f64 = d->dtype == PTG_OUT_F64;
+    TrainGroup<OptArgs> g{};
+    unsigned most = 1;
+    for (int i = 0; i < n_members; i++) {
+        g.m[i] = optim_args(h, &members[i]);
+        most = std::max(most, g.m[i].n_chunks);
+    }
+    const OptArgs& a = g.m[0];
+    const dim3 block(OPT_BLOCK);
+    if (!grouped) {
+        const dim3 grid(a.n_chunks);
+        if (!polyak) {
+            if (clip) {
+                if (f64) hipLaunchKernelGGL(k_optim_norm<double>, grid, block, 0, st, a);
+                else hipLaunchKernelGGL(k_optim_norm<float>, grid, block, 0, st, a);
+            }
+            hipLaunchKernelGGL(k_optim_head<>, dim3(1), block, 0, st, a);
+        }
+        if (f64) hipLaunchKernelGGL(k_optim_update<double>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_optim_update<float>, grid, block, 0, st, a);
+        return launch_check(h, "k_optim_update");
+    }
+    const dim3 grid(most, (unsigned)n_members);
     if (!polyak) {
         if (clip) {
-            if (f64) hipLaunchKernelGGL(k_optim_norm<double>, grid, block, 0, st, a);
-            else hipLaunchKernelGGL(k_optim_norm<float>, grid, block, 0, st, a);
+            if (f64) hipLaunchKernelGGL((k_optim_norm<double, TrainGroup<OptArgs>>), grid, block, 0, st, g);
+            else hipLaunchKernelGGL((k_optim_norm<float, TrainGroup<OptArgs>>), grid, block, 0, st, g);
         }
-        hipLaunchKernelGGL(k_optim_head, dim3(1), block, 0, st, a);
+        hipLaunchKernelGGL(k_optim_head<TrainGroup<OptArgs>>, dim3((unsigned)n_members), block, 0, st, g);
     }
-    if (f64) hipLaunchKernelGGL(k_optim_update<double>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_optim_update<float>, grid, block, 0, st, a);
-    return launch_check(h, "k_optim_update");
+    if (f64) hipLaunchKernelGGL((k_optim_update<double, TrainGroup<OptArgs>>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((k_optim_update<float, TrainGroup<OptArgs>>), grid, block, 0, st, g);
+    return launch_check(h, "k_optim_update (grouped)");
+}
+
+int ptg_optim_step(ptg_env* h, const ptg_optim* d, void* stream) { return optim_step_walk(h, "ptg_optim_step", d, 1, false, stream); }
+
+int ptg_optim_step_group(ptg_env* h, const ptg_optim* members, int32_t n_members, void* stream)
+{
+    return optim_step_walk(h, "ptg_optim_step_group", members, n_members, true, stream);
 }
 
 // ---- the TD losses: DQN's and the TD3 / SAC critics', the statistics and the gradients w.r.t. the current Q-values ---------

@@ -11,6 +11,7 @@ train_or_eval {0 train, 1 eval}.  `markets` is a list (one per business scenario
 with el, pot_rew, part_full, gas, eua (1-D float64), scenario, rew_l_b, rew_u_b, r_0.
 """
 import ctypes as C
+import gc
 
 import numpy as np
 
@@ -41,6 +42,10 @@ class HipEngine(TrainOps):
         self._L = _lib.lib()                      # raises if the extension is missing
         if not torch.cuda.is_available():
             raise RuntimeError("HipEngine needs a ROCm GPU (torch.cuda.is_available() is False); rl_ptg_amd has no CPU path")
+        # one full collection before the handle and its buffers are allocated: device tensors that only dead reference cycles still
+        # hold (an exception's traceback, an autograd graph) go back to torch's allocator now, not at whatever later moment the
+        # collector's counters pick -- which could be inside a stretch of stream-ordered calls that must not touch the allocator
+        gc.collect()
         self.n = int(n_envs)
         self._fin_buf = None
         self.device = torch.device("cuda", int(device))

@@ -1,4 +1,6 @@
 """ppo_loss / a2c_loss: the fused policy loss (HipEngine.policy_loss, include/ptg_env.h: ptg_policy_loss) behind torch autograd;
+ppo_loss_group / a2c_loss_group: the losses of up to eight independent agents in the launches of one (HipEngine.policy_loss_group,
+ptg_policy_loss_group) under ONE autograd function;
 ppo_sde_loss / a2c_sde_loss: the same for a policy with gSDE (HipEngine.sde_policy_loss, ptg_sde_policy_loss); sde_squashed_rsample: SAC's
 and TQC's actor head with gSDE (HipEngine.sde_rsample / sde_rsample_backward, ptg_sde_rsample);
 dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise, and tqc_critic_loss: TQC's
@@ -62,6 +64,93 @@ def a2c_loss(engine, head_input, values, actions, advantages, returns, *, ent_co
     """SB3's A2C.train loss of its one batch -> (loss, stats) as ppo_loss gives them (approx_kl and clip_fraction are 0)."""
     kw = dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, out=out, workspace=workspace)
     return _call("a2c", engine, head_input, values, actions, None, advantages, returns, None, log_std, kw)
+
+
+# ------------------------------------------------------------------------------------------------- G agents' losses in one's launches
+#     outs = nets(obs_batches)                                  # TrainMLPGroup: policy and value net of every agent
+#     losses, stats = ppo_loss_group(engine, [dict(head_input=outs[2 * i], values=outs[2 * i + 1], actions=..., old_log_prob=...,
+#                                                  advantages=..., returns=...) for i in range(G)], clip_range=[0.2, 0.1, ...])
+#     torch.autograd.backward(losses)                           # ONE pass: every agent's gradients go to its own networks
+class _PolicyLossGroupFn(torch.autograd.Function):
+    """forward: one policy_loss_group over the members; backward: each member's gradients, scaled by its loss's incoming gradient, to
+    its head_input, values and log_std; a loss that received no gradient hands None to its networks"""
+
+    @staticmethod
+    def forward(ctx, engine, kind, members, *diff):          # diff: head_input, values, log_std (or None) of every member
+        calls, shapes = [], []
+        for i, m in enumerate(members):
+            hi, val, ls = diff[3 * i:3 * i + 3]
+            kw = dict(m, head_input=hi.detach(), values=val.detach(), log_std=None if ls is None else ls.detach())
+            if kw.get("out") is None:                        # fresh gradients are zeroed, as _PolicyLossFn's are
+                dev, dt = hi.device, hi.dtype
+                kw["out"] = (torch.empty(8, dtype=torch.float64, device=dev), torch.zeros(hi.shape, dtype=dt, device=dev),
+                             torch.zeros(val.shape[0], dtype=dt, device=dev), None if ls is None else torch.zeros(1, dtype=dt, device=dev))
+            calls.append(kw)
+            shapes.append((hi.shape, val.shape, None if ls is None else ls.shape))
+        res = engine.policy_loss_group(kind, calls)
+        ctx.res, ctx.shapes = res, shapes
+        stats = [r.stats for r in res]
+        ctx.mark_non_differentiable(*stats)
+        ctx.set_materialize_grads(False)                     # an unused loss's gradient arrives as None, not as a zero
+        return (*[r.stats[0].to(d.dtype, copy=True) for r, d in zip(res, diff[::3])], *stats)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        out = []
+        for r, (s_in, s_val, s_ls), g in zip(ctx.res, ctx.shapes, grads):
+            if g is None:
+                out += [None, None, None]
+                continue
+            out += [(r.grad_input * g).reshape(s_in), (r.grad_values * g).reshape(s_val), None if s_ls is None else (r.grad_log_std * g).reshape(s_ls)]
+        return (None, None, None, *out)
+
+
+_GROUP_TENSORS = ("head_input", "values", "actions", "old_log_prob", "advantages", "returns", "old_values", "log_std", "out", "workspace")
+
+
+def _group_call(who, kind, engine, members, scalars):
+    if not isinstance(members, (list, tuple)) or not members or not all(isinstance(m, dict) for m in members):
+        raise TypeError(f"{who}: members must be a non-empty list of dicts (head_input, values, actions, advantages, returns, ...), got {type(members).__name__}")
+    G = len(members)
+    calls = []
+    for i, m in enumerate(members):
+        unknown = [k for k in m if k not in _GROUP_TENSORS]
+        if unknown:
+            raise TypeError(f"{who}: member {i} names {unknown}; a member holds the tensors {_GROUP_TENSORS}, the scalars are keyword arguments")
+        missing = [k for k in ("head_input", "values") if not torch.is_tensor(m.get(k))]
+        if missing:
+            raise TypeError(f"{who}: member {i} needs the tensors {missing}")
+        kw = dict(m)
+        for name, v in scalars.items():                      # one value for all, or a list with one per member
+            if isinstance(v, (list, tuple)):
+                if len(v) != G:
+                    raise ValueError(f"{who}: {name} must have one entry per member, {G}, or be one value for all; got {len(v)}")
+                v = v[i]
+            kw[name] = v
+        if kind == "a2c":
+            kw["old_log_prob"] = None
+        calls.append(kw)
+    diff = [t for m in calls for t in (m.get("head_input"), m.get("values"), m.get("log_std"))]
+    out = _PolicyLossGroupFn.apply(engine, kind, calls, *diff)
+    return list(out[:G]), list(out[G:])
+
+
+def ppo_loss_group(engine, members, *, clip_range, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True):
+    """ppo_loss for G independent agents' minibatches of one batch size, 1 <= G <= 8, in the launches of ONE ppo_loss
+    (HipEngine.policy_loss_group) -> (losses, stats): two lists of G, member i's what ppo_loss gives for its
+    arguments, bit for bit.  members: a list of dicts of ppo_loss's tensors by name (head_input, values, actions, old_log_prob,
+    advantages, returns; old_values, log_std, out, workspace).  clip_range, clip_range_vf, ent_coef, vf_coef: one value for all, or a
+    list with one per member (clip_range_vf: given for all or for none); normalize_advantage: one value.  The G losses belong in ONE
+    backward pass -- torch.autograd.backward(losses) -- which hands each member's gradients to its own networks; a loss left out of it
+    leaves its networks' gradients alone.
+    Cost (profiles/train_group_cost.txt; DESIGN.md section 26, whose one condition held at every shape): see DeviceOptimizerGroup's docstring."""
+    scalars = dict(clip_range=clip_range, clip_range_vf=clip_range_vf, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage)
+    return _group_call("ppo_loss_group", "ppo", engine, members, scalars)
+
+
+def a2c_loss_group(engine, members, *, ent_coef=0.0, vf_coef=0.5, normalize_advantage=False):
+    """a2c_loss for G independent agents -> (losses, stats) as ppo_loss_group gives them (no old_log_prob, no clipping)."""
+    return _group_call("a2c_loss_group", "a2c", engine, members, dict(ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage))
 
 
 # ------------------------------------------------------------------------------------------------- the on-policy losses with gSDE

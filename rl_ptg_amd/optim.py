@@ -8,7 +8,10 @@
 
 Differences from torch.optim, all stated in the header: every parameter of the optimiser must have a gradient when step() runs (torch
 skips a parameter whose .grad is None; here that raises ValueError); the gradients are not rewritten by the clipping; all tensors share
-one dtype, float32 or float64, and are contiguous; no weight decay, amsgrad, momentum or centering.  There is no torch fall-back."""
+one dtype, float32 or float64, and are contiguous; no weight decay, amsgrad, momentum or centering.  There is no torch fall-back.
+
+DeviceOptimizerGroup: the steps of up to eight DeviceOptimizers -- independent agents -- as ONE library call (HipEngine.optim_step_group,
+ptg_optim_step_group)."""
 import torch
 
 from .train_ops import OptimPlan  # noqa: F401  (re-exported: what DeviceOptimizer.plan is)
@@ -148,3 +151,80 @@ class DeviceOptimizer:
                 xs[i].copy_(state[k][name])
         b1, b2 = self.betas if self.kind == "adam" else (1.0, 1.0)
         self.plan.state.copy_(torch.tensor([t, b1 ** t, b2 ** t, 0.0], dtype=torch.float64))
+
+
+class DeviceOptimizerGroup:
+    """Up to 8 DeviceOptimizers of one kind and flag set -- the optimisers of independent agents: seeds, a sweep over lr -- whose step()
+    is ONE grouped library call (HipEngine.optim_step_group; include/ptg_env.h: ptg_optim_step_group): three
+    launches, two without clipping, whatever the number of agents.  Every member's parameters, moments, targets, zeroed gradients, step
+    count and grad norm after a step are, bit for bit, what its own DeviceOptimizer.step() gives.
+
+        opts = [DeviceOptimizer(engine, agent.parameters(), lr=lr_i, eps=1e-5, max_grad_norm=0.5, zero_grad=True) for agent, lr_i in ...]
+        group = DeviceOptimizerGroup(engine, opts)
+        losses, stats = ppo_loss_group(engine, members, clip_range=0.2)
+        torch.autograd.backward(losses)
+        group.step()                                          # every agent's clip + Adam + zero_grad
+
+    The members must agree in kind, in clipping or not (max_grad_norm None or not), in having targets or not and in zero_grad, and all
+    parameters of all members in dtype (ValueError, which names the two members); lr (a float or a device tensor, per member), betas,
+    eps, alpha, max_grad_norm and tau are each member's own, read from it at every step.  A member stays usable alone (its own step()
+    takes the same next step), and checkpoints stay the members' own state_dict / load_state_dict.  As in DeviceOptimizer.step, a .grad
+    that moved in a member rebuilds that member's plan; under stream capture that raises, with the member named.
+    Cost (profiles/train_group_cost.txt; DESIGN.md section 26 has the table and its one condition -- at every shape the grouped route's
+    median not above the G single calls', or the G single-agent graphs', taken in turn -- which HELD at every shape).  The G single calls
+    over the grouped call, raw calls, HIP events behind a device-side delay: optim_step over PPO's 0.29 M parameters per member (Adam, clip,
+    zero-grad) G = 2 / 4 / 6 / 8 1.54x / 2.54x / 3.43x / 3.71x (25.9 against 96.1 us at eight members), over A2C's 4 x 808 nets (RMSprop,
+    clip) G = 2 / 6 1.27x / 1.64x; policy_loss at PPO's B = 203 G = 2 / 4 / 6 / 8 1.66x / 1.41x / 1.38x / 1.34x and at A2C's B = 3 948
+    G = 2 / 6 1.76x / 1.87x -- from G = 4 on those loss figures hold the device waiting for the host's argument checks (in
+    both routes), not one launch's device time.  A whole captured gradient step of four PPO agents (per-agent next_batch, one
+    TrainMLPGroup of eight nets, ppo_loss_group, one backward, this class): 371 us per step of all four against 755 us for the four
+    single-agent graphs replayed in turn, 2.03x; the four graphs on four streams read 876 us, the four gathers 9 % of the grouped replay.
+    One run in one process.  Not measured: float64, the Gaussian head, G processes, the host cost of the grouped calls on an idle stream."""
+
+    def __init__(self, engine, optimizers):
+        optimizers = list(optimizers)
+        if not optimizers:
+            raise ValueError("DeviceOptimizerGroup: an empty list of optimizers")
+        if len(optimizers) > 8:
+            raise ValueError(f"DeviceOptimizerGroup: 1 to 8 optimizers, got {len(optimizers)}")
+        for i, o in enumerate(optimizers):
+            if not isinstance(o, DeviceOptimizer):
+                raise TypeError(f"DeviceOptimizerGroup: optimizers[{i}] must be a DeviceOptimizer, got {type(o).__name__}")
+        o0 = optimizers[0]
+        for i, o in enumerate(optimizers):
+            for name, a, b in (("kind", o0.kind, o.kind), ("clipping (max_grad_norm None or not)", o0.max_grad_norm is not None, o.max_grad_norm is not None),
+                               ("having targets", o0.targets is not None, o.targets is not None), ("zero_grad", o0.zero_grad_flag, o.zero_grad_flag),
+                               ("the parameters' dtype", o0.params[0].dtype, o.params[0].dtype)):
+                if a != b:
+                    raise ValueError(f"DeviceOptimizerGroup: optimizers 0 and {i} disagree in {name}: {a} and {b}")
+            if o.engine is not engine:
+                raise ValueError(f"DeviceOptimizerGroup: optimizers[{i}] belongs to another engine")
+        if len({id(o) for o in optimizers}) != len(optimizers):
+            raise ValueError("DeviceOptimizerGroup: an optimizer is given twice")
+        self.engine, self.optimizers = engine, optimizers
+
+    def step(self):
+        """One step of every parameter of every member on the current stream; returns nothing.  Each member's .grad pointers are compared
+        with its plan's, as DeviceOptimizer.step does: a member whose .grad moved has its plan rebuilt (its moments and step count are
+        taken over) -- under stream capture that raises, with the member named."""
+        for i, o in enumerate(self.optimizers):
+            grads = o._grads()
+            if o.plan is None or [None if g is None else g.data_ptr() for g in grads] != o.plan.grad_ptrs:
+                if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError(f"DeviceOptimizerGroup.step: member {i}: a .grad moved (or no step was taken yet) -- the tables cannot be rebuilt under "
+                                       "stream capture; take one eager step first and keep the gradients in place (zero_grad=True, or set_to_none=False)")
+                o._retired = o.plan
+                o._build(state=o.plan)
+        os_ = self.optimizers
+        self.engine.optim_step_group([o.plan for o in os_], [o.lr for o in os_], betas=[o.betas for o in os_], eps=[o.eps for o in os_],
+                                     alpha=[o.alpha for o in os_], max_grad_norm=[o.max_grad_norm for o in os_], tau=[o.tau for o in os_],
+                                     zero_grad=os_[0].zero_grad_flag)
+
+    def zero_grad(self, set_to_none=False):
+        for o in self.optimizers:
+            o.zero_grad(set_to_none=set_to_none)
+
+    @property
+    def grad_norms(self):
+        """the members' grad_norm: a list of float64 device scalars [1] (None without clipping or before the first step)"""
+        return [o.grad_norm for o in self.optimizers]

@@ -52,6 +52,11 @@ ActorLoss = collections.namedtuple("ActorLoss", "stats grad_q grad_log_prob grad
 MlpOut = collections.namedtuple("MlpOut", "out hidden")
 
 
+# what a member dict of policy_loss_group must and may name: policy_loss's arguments
+_LOSS_MEMBER_NEEDS = ("head_input", "values", "actions", "old_log_prob", "advantages", "returns")
+_LOSS_MEMBER_TAKES = _LOSS_MEMBER_NEEDS + ("clip_range", "clip_range_vf", "ent_coef", "vf_coef", "normalize_advantage", "old_values", "log_std", "out", "workspace")
+
+
 class OptimPlan:
     """What optim_plan makes of an optimiser's tensor lists: the checked tensors (kept alive here: the device tables hold their
     addresses), the state tensors, the two device tables, the float64 device scalars and the scratch of ptg_optim_step."""
@@ -285,15 +290,17 @@ class TrainOps:
         with self._torch.cuda.device(self.device):
             return self._torch.empty(nbytes, dtype=self._torch.uint8, device=self.device)
 
-    def _take_workspace(self, op, B, workspace):
+    def _take_workspace(self, op, B, workspace, who=None, fresh=True):
         """the workspace= of the loss `op`: the caller's, once it is a contiguous uint8 tensor of ptg_<op>_workspace(B) bytes or more,
-        else a fresh one"""
+        else a fresh one.  who: the caller's name where it is not the op's (a grouped call's "... member i"); fresh=False: only the
+        check, None comes back as None"""
+        who = who or op
         if workspace is None:
-            return self._loss_workspace(op, B)
-        check(self, op, f"workspace ({op}_workspace({B}))", workspace, dtypes=(self._torch.uint8,), rule=contiguous, exc=ValueError)
+            return self._loss_workspace(op, B) if fresh else None
+        check(self, who, f"workspace ({op}_workspace({B}))", workspace, dtypes=(self._torch.uint8,), rule=contiguous, exc=ValueError)
         size = getattr(self._L, f"ptg_{op}_workspace")
         if workspace.numel() < size(B):
-            raise ValueError(f"{op}: workspace has {workspace.numel()} bytes, a batch of {B} needs {size(B)}")
+            raise ValueError(f"{who}: workspace has {workspace.numel()} bytes, a batch of {B} needs {size(B)}")
         return workspace
 
     def _fresh_like_quantiles(self, as_list, B, K, Q, dtype):
@@ -798,8 +805,19 @@ class TrainOps:
         (or any such tuple: grad_input and grad_values may be views of one [B, A + 1] tensor), reused by a captured call; workspace:
         policy_loss_workspace(B) or larger, allocated when missing.  Fresh gradients are torch.empty: a row refused for its action
         keeps what was there.  No synchronisation; a bad row makes the next sync() raise PtgError (PTG_E_INDEX / PTG_E_NONFINITE)."""
+        d, res, _ = self._policy_loss_member("policy_loss", kind, head_input, values, actions, old_log_prob, advantages, returns, clip_range=clip_range,
+                                             clip_range_vf=clip_range_vf, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage,
+                                             old_values=old_values, log_std=log_std, out=out, workspace=workspace)[1]()
+        self._call("ptg_policy_loss", C.byref(d))
+        return res
+
+    def _policy_loss_member(self, who, kind, head_input, values, actions, old_log_prob, advantages, returns, *, clip_range=None, clip_range_vf=None,
+                            ent_coef=0.0, vf_coef=0.5, normalize_advantage=None, old_values=None, log_std=None, out=None, workspace=None):
+        """Every check of ONE policy-loss call, in policy_loss's order, for policy_loss and for each member of policy_loss_group (who:
+        "policy_loss", or "policy_loss_group: member i").  Allocates nothing and does not touch the library.  Returns (what a group
+        must agree in, as (name, value) pairs; make; the outputs and workspace the caller gave), where make() allocates what was not
+        given and returns (the PtgLoss, the PolicyLoss, the workspace, which must outlive the library call)."""
         torch = self._torch
-        who = "policy_loss"
         if kind not in ("ppo", "a2c"):
             raise ValueError(f"{who}: kind must be 'ppo' or 'a2c', got {kind!r}")
         ppo, gauss = kind == "ppo", log_std is not None
@@ -840,13 +858,33 @@ class TrainOps:
             check(self, who, "out.grad_values", g_val, dtypes=dt, shape=(B,), rule=step, exc=ValueError)
             if gauss:
                 check(self, who, "out.grad_log_std", g_ls, dtypes=dt, shape=(1,), exc=ValueError)
-        workspace = self._take_workspace(who, B, workspace)
+        self._take_workspace("policy_loss", B, workspace, who=who, fresh=False)
+        agree = (("kind", kind), ("the head", "gaussian" if gauss else "categorical"), ("normalize_advantage", bool(normalize_advantage)),
+                 ("clip_range_vf given or not", clip_range_vf is not None), ("the number of actions", A), ("the dtype", x.dtype),
+                 ("the actions' dtype", actions.dtype), ("the batch", B))
+        given = ([] if out is None else [stats, g_in, g_val]) + ([] if workspace is None else [workspace])
+
+        def make():
+            return self._policy_loss_desc(kind, x, values, actions, old_log_prob, advantages, returns, clip_range, clip_range_vf, ent_coef, vf_coef, normalize_advantage,
+                                          old_values, log_std, None if out is None else (stats, g_in, g_val, g_ls), workspace)
+        return agree, make, given
+
+    def _policy_loss_desc(self, kind, x, values, actions, old_log_prob, advantages, returns, clip_range, clip_range_vf, ent_coef, vf_coef, normalize_advantage,
+                          old_values, log_std, out, workspace):
+        """behind the checks of _policy_loss_member: (the PtgLoss, the PolicyLoss, the workspace), outputs and workspace the caller's or fresh"""
+        torch = self._torch
+        ppo, gauss = kind == "ppo", log_std is not None
+        B, A = x.shape[0], 0 if gauss else x.shape[1]
+        if workspace is None:
+            workspace = self._loss_workspace("policy_loss", B)
         if out is None:
             with torch.cuda.device(self.device):
                 stats = torch.empty(8, dtype=torch.float64, device=self.device)
                 g_in = torch.empty(tuple(x.shape), dtype=x.dtype, device=self.device)
                 g_val = torch.empty(B, dtype=x.dtype, device=self.device)
                 g_ls = torch.empty(1, dtype=x.dtype, device=self.device) if gauss else None
+        else:
+            stats, g_in, g_val, g_ls = out
         d = _lib.PtgLoss(kind=_lib.LOSS_PPO if ppo else _lib.LOSS_A2C, head=_lib.HEAD_GAUSSIAN if gauss else _lib.HEAD_CATEGORICAL,
                          flags=(_lib.LOSS_NORM_ADV if normalize_advantage else 0) | (_lib.LOSS_CLIP_VF if clip_range_vf is not None else 0),
                          n_actions=A, in_dtype=_out_code(torch, x.dtype), act_kind=_lib.ACT_I64 if actions.dtype == torch.int64 else _lib.ACT_I32,
@@ -857,8 +895,43 @@ class TrainOps:
                          ent_coef=float(ent_coef), vf_coef=float(vf_coef), stats_dev=_ptr(stats), grad_in_dev=_ptr(g_in),
                          g_s_n=max(g_in.stride(0), A, 1), grad_val_dev=_ptr(g_val), gv_s_n=max(g_val.stride(0), 1),
                          grad_log_std_dev=_ptr(g_ls if gauss else None), ws_dev=_ptr(workspace))
-        self._call("ptg_policy_loss", C.byref(d))
-        return PolicyLoss(stats, g_in, g_val, g_ls)
+        return d, PolicyLoss(stats, g_in, g_val, g_ls), workspace
+
+    def policy_loss_group(self, kind, members, *, clip_range=None, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, normalize_advantage=None):
+        """policy_loss for G independent minibatches of ONE batch size, 1 <= G <= 8, in exactly the launches of one policy_loss call
+        (include/ptg_env.h: ptg_policy_loss_group): the agents of a seed sweep.  Every member's result is, bit
+        for bit, what policy_loss gives for its arguments.  members: a list of G dicts of policy_loss's arguments by name (head_input,
+        values, actions, old_log_prob, advantages, returns, and any of clip_range, clip_range_vf, ent_coef, vf_coef, old_values, log_std,
+        out, workspace); the keyword arguments here are the defaults of the members that do not name them.  The members must agree in
+        kind, head, normalize_advantage, whether clip_range_vf is given, A, the dtypes and B (ValueError, which names the two members);
+        every scalar may differ.  No tensor may serve two members as an output or workspace.  Checked as policy_loss checks, member by
+        member, the message behind "member i:"; the library is not touched and nothing is allocated before every check has passed, and
+        nothing at all when every member brings out= and workspace=.  Returns the list of G PolicyLoss.
+        Cost (profiles/train_group_cost.txt; DESIGN.md section 26, whose one condition held at every shape): see DeviceOptimizerGroup's docstring."""
+        who = "policy_loss_group"
+        if not isinstance(members, (list, tuple)) or not all(isinstance(m, dict) for m in members):
+            raise TypeError(f"{who}: members must be a list of dicts of policy_loss's arguments, got {type(members).__name__}")
+        G = len(members)
+        if not 1 <= G <= _lib.TRAIN_GROUP_MAX:
+            raise ValueError(f"{who}: 1 to {_lib.TRAIN_GROUP_MAX} members, got {G}")
+        shared = dict(clip_range=clip_range, clip_range_vf=clip_range_vf, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage)
+        checked = []
+        for i, m in enumerate(members):
+            kw = dict(shared, **m)
+            if kind == "a2c":
+                kw.setdefault("old_log_prob", None)
+            missing, unknown = [k for k in _LOSS_MEMBER_NEEDS if k not in kw], [k for k in kw if k not in _LOSS_MEMBER_TAKES]
+            if missing or unknown:
+                raise TypeError(f"{who}: member {i}: a member names policy_loss's arguments; missing {missing}, unknown {unknown}")
+            checked.append(self._policy_loss_member(f"{who}: member {i}", kind, **kw))
+        for i, (agree, _, _) in enumerate(checked):
+            for (name, a), (_, b) in zip(checked[0][0], agree):
+                if a != b:
+                    raise ValueError(f"{who}: members 0 and {i} disagree in {name}: {a} and {b}")
+        _no_tensor_twice(who, [t for _, _, given in checked for t in given], "the members' outputs and workspaces")
+        made = [make() for _, make, _ in checked]
+        self._call("ptg_policy_loss_group", (_lib.PtgLoss * G)(*[m[0] for m in made]), G)      # made holds the workspaces until here
+        return [m[1] for m in made]
 
     # ------------------------------------------------------------------ gSDE: the exploration matrix, the collecting head, its loss
     def _sde_log_std(self, who, log_std, dtypes, L=None):
@@ -1884,8 +1957,11 @@ class TrainOps:
         the kernel runs.  Three launches (two without clipping) whatever the number of tensors, no synchronisation, no allocation:
         the call may be captured and replayed, and every replay takes the next step t + 1.  plan.norm holds the total norm afterwards.
         A non-finite total norm (without clipping: gradient element) makes the next sync() raise PtgError with code PTG_E_NONFINITE."""
+        self._call("ptg_optim_step", C.byref(self._optim_step_member("optim_step", plan, lr, betas, eps, alpha, max_grad_norm, tau, zero_grad)))
+
+    def _optim_step_member(self, who, plan, lr, betas, eps, alpha, max_grad_norm, tau, zero_grad):
+        """every check of ONE optim_step call, in its order, for optim_step and for each member of optim_step_group -> its PtgOptim"""
         torch = self._torch
-        who = "optim_step"
         if not isinstance(plan, OptimPlan):
             raise TypeError(f"{who}: plan must be an OptimPlan (optim_plan()), got {type(plan).__name__}")
         if torch.is_tensor(lr):
@@ -1922,7 +1998,44 @@ class TrainOps:
         d.beta1, d.beta2, d.eps, d.alpha = b1, b2, float(eps), float(alpha)
         d.tau = float(tau) if tau is not None else 0.0
         d.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
-        self._call("ptg_optim_step", C.byref(d))
+        return d
+
+    def optim_step_group(self, plans, lrs, betas=(0.9, 0.999), eps=1e-8, alpha=0.99, max_grad_norm=None, tau=None, zero_grad=False):
+        """optim_step for G plans of ONE kind and dtype, 1 <= G <= 8, in exactly the launches of one optim_step call -- three, two without
+        clipping, whatever G is (include/ptg_env.h: ptg_optim_step_group).  Every member's parameters, states,
+        targets, zeroed gradients, step count and plan.norm are, bit for bit, what optim_step gives for its arguments.  plans: a list
+        of G OptimPlans; lrs, betas, eps, alpha, max_grad_norm, tau: each a list with one entry per member, or one value for all (lrs:
+        floats and float64 device tensors may be mixed; betas: a pair for all, or a list of G pairs).  The members must agree in the
+        plan's kind and dtype, in clipping or not (max_grad_norm None or not), in having targets or not, and in zero_grad (ValueError,
+        which names the two members); no plan may be given twice.  Checked as optim_step checks, member by member, the message behind
+        "member i:".  No synchronisation, no allocation: the call may be captured and replayed.
+        Cost (profiles/train_group_cost.txt; DESIGN.md section 26, whose one condition held at every shape): see DeviceOptimizerGroup's docstring."""
+        who = "optim_step_group"
+        if not isinstance(plans, (list, tuple)):
+            raise TypeError(f"{who}: plans must be a list of OptimPlans, got {type(plans).__name__}")
+        G = len(plans)
+        if not 1 <= G <= _lib.TRAIN_GROUP_MAX:
+            raise ValueError(f"{who}: 1 to {_lib.TRAIN_GROUP_MAX} members, got {G}")
+
+        def per(name, x, one=lambda v: not isinstance(v, (list, tuple))):
+            if one(x):
+                return [x] * G
+            if len(x) != G:
+                raise ValueError(f"{who}: {name} must have one entry per member, {G}, or be one value for all; got {len(x)}")
+            return list(x)
+        lrs, eps, alpha, mgn, tau = per("lrs", lrs), per("eps", eps), per("alpha", alpha), per("max_grad_norm", max_grad_norm), per("tau", tau)
+        betas = per("betas", betas, one=lambda v: len(v) == 2 and not isinstance(v[0], (list, tuple)))
+        descs = [self._optim_step_member(f"{who}: member {i}", plans[i], lrs[i], betas[i], eps[i], alpha[i], mgn[i], tau[i], zero_grad) for i in range(G)]
+        for i in range(1, G):
+            for name, a, b in (("the plan's kind", plans[0].kind, plans[i].kind), ("the dtype", plans[0].dtype, plans[i].dtype),
+                               ("clipping (max_grad_norm None or not)", mgn[0] is not None, mgn[i] is not None),
+                               ("having targets", plans[0].targets is not None, plans[i].targets is not None)):
+                if a != b:
+                    raise ValueError(f"{who}: members 0 and {i} disagree in {name}: {a} and {b}")
+        if len({id(p) for p in plans}) != G:
+            raise ValueError(f"{who}: a plan is given twice; every member steps its own parameters")
+        _no_tensor_twice(who, [t for p in plans for t in (p.state, p.norm, p.workspace)], "the plans' state, norm and workspace")
+        self._call("ptg_optim_step_group", (_lib.PtgOptim * G)(*descs), G)
 
     def polyak_update(self, params, targets, tau, plan=None):
         """Enqueue, on the current stream, SB3's polyak_update(params, targets, tau) for lists that no optimiser steps -- DQN's hard
