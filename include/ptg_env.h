@@ -1709,10 +1709,51 @@ int ptg_mlp_group_backward(ptg_env* env, const ptg_mlp_bwd* nets, int32_t n_nets
  * n_members outside [1, PTG_TRAIN_GROUP_MAX]; anything the single call refuses in a descriptor, the single call's text behind
  * "member <i>: " (one checker serves both entries); a disagreement in one of the fields above, which names the field and the two
  * members; two members that share one of the output or scratch pointers above.
- * Not grouped: the gSDE, TD, quantile and actor losses; the minibatch gathers; members of different batch. */
+ * Not grouped: the gSDE and quantile losses; the minibatch gathers; members of different batch.  The TD and actor
+ * losses and the training-time actor head have grouped entries of their own, below. */
 #define PTG_TRAIN_GROUP_MAX 8
 int ptg_policy_loss_group(ptg_env* env, const ptg_loss* members, int32_t n_members, void* stream);
 int ptg_optim_step_group(ptg_env* env, const ptg_optim* members, int32_t n_members, void* stream);
+
+/* ---- the off-policy losses and the actor head of up to eight independent agents in the launches of one ---------
+ * ptg_td_loss_group, ptg_actor_loss_group, ptg_rsample_group and ptg_rsample_backward_group run n_members descriptors, 1 <= n_members <=
+ * PTG_TRAIN_GROUP_MAX, of the single calls (ptg_td, ptg_al, ptg_rs, unchanged) in exactly the launches that ONE single call enqueues,
+ * whatever n_members is.  The descriptors are read during the call and travel by value in the launch arguments -- eight members take
+ * 8 x 328 = 2 624 (td), 8 x 232 = 1 856 (actor loss) and 8 x 176 = 1 408 bytes (rsample) of the 4 096 a launch may have -- so a captured
+ * call holds no host memory.  The member is a grid dimension; a grouped kernel is the single kernel's text on the member its block index
+ * names, every member's sums run in the single call's order, which depends on batch alone, and nothing is reduced across members:
+ * WHAT MEMBER i's OUTPUTS HOLD AFTER A GROUPED CALL IS DEFINED AS WHAT THE SINGLE CALL ON &members[i] WRITES, bit for bit.
+ * ptg_td_loss_group:
+ *   must agree    kind, flags, n_actions, n_critics, q_dtype, rew_dtype, done_dtype, act_kind and batch.
+ *   its own       every pointer and stride; gamma, alpha, alpha_dev (NULL or not, where the flags allow either), scale; y_dev (NULL or not).
+ *   distinct      stats_dev, ws_dev, y_dev, and every grad_q_dev entry against every entry of every other member.
+ *   launches      one for batch <= 256 (k_td_rows), else the rows and the final merge (k_td_rows, k_loss_final: one workgroup a member).
+ * ptg_actor_loss_group:
+ *   must agree    kind, flags, n_critics, n_quantiles, q_dtype and batch.
+ *   its own       every pointer and stride; alpha, alpha_dev, target_entropy; grad_logp_dev and grad_log_alpha_dev (NULL or not).
+ *   distinct      stats_dev, ws_dev, every grad_q_dev entry, grad_logp_dev, grad_log_alpha_dev.
+ *   launches      one for batch <= 256 (k_al_rows), else the rows and the final merge.
+ * ptg_rsample_group / ptg_rsample_backward_group:
+ *   must agree    kind, flags, q_dtype and batch.
+ *   its own       every pointer and stride; seed and counter_dev; noise_std, noise_clip, clip_lo, clip_hi.
+ *   distinct      forward: act_dev, logp_dev, noise_dev and -- unless deterministic -- counter_dev: the grouped forward reads every
+ *                 counter before any of them is advanced, which n_members calls in turn on one counter would not; backward: the two
+ *                 gradient outputs.
+ *   launches      forward: k_rs_fwd and one launch that advances every member's counter by one (one thread a member), or k_rs_fwd alone
+ *                 when deterministic; backward: one.
+ * Members may share what is only read.  Two members with EQUAL base pointers in one of the `distinct` fields are refused; overlap beyond
+ * equal base pointers is NOT checked.  The error words of the handle are shared: a bad row in member i raises the word as the single
+ * call does (the next ptg_sync returns PTG_E_INDEX or PTG_E_NONFINITE once) and changes nothing in any other member's outputs.
+ * No host synchronisation and no allocation; capturable into a hipGraph.
+ * PTG_E_INVALID (nothing enqueued, every output untouched; every check runs before the first launch): NULL handle or members;
+ * n_members outside [1, PTG_TRAIN_GROUP_MAX]; anything the single call refuses in a descriptor, the single call's text behind
+ * "member <i>: " (one checker serves both entries); a disagreement in one of the fields above, which names the field and the two
+ * members; two members that share one of the pointers above.
+ * Not grouped: ptg_quantile_loss, the gSDE ops, the replay buffer's add and sample, members of different batch. */
+int ptg_td_loss_group(ptg_env* env, const ptg_td* members, int32_t n_members, void* stream);
+int ptg_actor_loss_group(ptg_env* env, const ptg_al* members, int32_t n_members, void* stream);
+int ptg_rsample_group(ptg_env* env, const ptg_rs* members, int32_t n_members, void* stream);
+int ptg_rsample_backward_group(ptg_env* env, const ptg_rs* members, int32_t n_members, void* stream);
 
 /* The pre-normalised float32 market feature series the kernels read, as [n_sets][series length]: which = 0 Pot_Reward ('raw':
  * Elec_Price) hourly, 1 Part_Full hourly ('mod' only), 2 Gas_Price daily, 3 EUA_Price daily.  out_host NULL: only *count.

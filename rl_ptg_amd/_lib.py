@@ -220,6 +220,7 @@ EXPORTS = ["ptg_abi_version", "ptg_create", "ptg_destroy", "ptg_num_envs", "ptg_
            "ptg_optim_chunk", "ptg_optim_workspace", "ptg_optim_step", "ptg_td_loss_workspace", "ptg_td_loss", "ptg_quantile_loss_workspace", "ptg_quantile_loss",
            "ptg_rsample", "ptg_rsample_backward", "ptg_actor_loss_workspace", "ptg_actor_loss", "ptg_mlp_workspace", "ptg_mlp_forward", "ptg_mlp_backward_workspace", "ptg_mlp_backward",
            "ptg_mlp_group_forward", "ptg_mlp_group_backward", "ptg_policy_loss_group", "ptg_optim_step_group",
+           "ptg_td_loss_group", "ptg_actor_loss_group", "ptg_rsample_group", "ptg_rsample_backward_group",
            "ptg_market_feature_series", "ptg_debug_get_index_lut", "ptg_debug_window_record", "ptg_debug_table_plan"]
 
 
@@ -380,6 +381,10 @@ def lib():
     L.ptg_mlp_group_backward.argtypes = [vp, C.POINTER(PtgMlpBwd), C.c_int32, vp]
     L.ptg_policy_loss_group.argtypes = [vp, C.POINTER(PtgLoss), C.c_int32, vp]
     L.ptg_optim_step_group.argtypes = [vp, C.POINTER(PtgOptim), C.c_int32, vp]
+    L.ptg_td_loss_group.argtypes = [vp, C.POINTER(PtgTd), C.c_int32, vp]
+    L.ptg_actor_loss_group.argtypes = [vp, C.POINTER(PtgAl), C.c_int32, vp]
+    L.ptg_rsample_group.argtypes = [vp, C.POINTER(PtgRs), C.c_int32, vp]
+    L.ptg_rsample_backward_group.argtypes = [vp, C.POINTER(PtgRs), C.c_int32, vp]
     L.ptg_market_feature_series.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
     L.ptg_debug_get_index_lut.argtypes = [vp, dp, i32p, C.POINTER(C.c_int)]
     L.ptg_debug_window_record.argtypes = [vp, C.c_int, C.c_int, dp]

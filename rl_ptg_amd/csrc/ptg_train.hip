@@ -1905,10 +1905,12 @@ __device__ __forceinline__ void td_finish(const TdArgs& a, const double* sum, do
 
 // ONE: the whole batch is this block (B <= PL_BLOCK): rows and statistics in one launch.  Otherwise the block leaves its partial sums
 // in the workspace for k_loss_final.
-template <typename IN, bool DQN, bool ONE>
+// blockIdx.x is the block within the batch, blockIdx.y (ARGS = TrainGroup<TdArgs>, ptg_td_loss_group) the member
+template <typename IN, bool DQN, bool ONE, typename ARGS = TdArgs>
 __global__ void __launch_bounds__(PL_BLOCK)
-k_td_rows(TdArgs a)
+k_td_rows(ARGS args)
 {
+    const TdArgs& a = train_member(args, blockIdx.y);
     __shared__ double sh[PL_WAVES * PL_PITCH];
     const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
     const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
@@ -1920,8 +1922,11 @@ k_td_rows(TdArgs a)
 }
 
 struct TdFinal {
+    __device__ static const double* partials(const TdArgs& a) { return a.ws; }
     __device__ void operator()(const TdArgs& a, const double* v) const { td_finish(a, v, td_alpha(a)); }
 };
+
+static_assert(sizeof(TrainGroup<TdArgs>) == 8 * 328 && sizeof(TrainGroup<TdArgs>) + sizeof(const double*) <= 4096, "the launch takes 4 096 bytes of kernel arguments");
 
 // ================================================================================== the quantile-Huber loss of TQC's critics
 // sb3_contrib's TQC.train critic lines and quantile_huber_loss(sum_over_quantiles=False) (include/ptg_env.h, ptg_quantile_loss, states
@@ -2124,10 +2129,14 @@ struct RsArgs {                          // by value in the launch: a captured c
 
 __device__ __forceinline__ double rs_clamp_log_std(double l) { return l < -20.0 ? -20.0 : (l > 2.0 ? 2.0 : l); }      // a NaN falls through
 
-template <typename IN>
+static_assert(sizeof(TrainGroup<RsArgs>) == 8 * 176 && sizeof(TrainGroup<RsArgs>) <= 4096, "the launch takes 4 096 bytes of kernel arguments");
+
+// blockIdx.x is the block within the batch, blockIdx.y (ARGS = TrainGroup<RsArgs>, ptg_rsample_group) the member
+template <typename IN, typename ARGS = RsArgs>
 __global__ void __launch_bounds__(ACT_BLOCK)
-k_rs_fwd(RsArgs a)
+k_rs_fwd(ARGS args)
 {
+    const RsArgs& a = train_member(args, blockIdx.y);
     const size_t b = (size_t)blockIdx.x * ACT_BLOCK + threadIdx.x;
     if (b >= a.B) return;                                    // the ragged last wave
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
@@ -2160,10 +2169,19 @@ k_rs_fwd(RsArgs a)
     if (logp_o) logp_o[b] = (IN)((((-(z * z) / 2.0) - ls) - 0.9189385332046727) - log((1.0 - x * x) + 1e-6));
 }
 
-template <typename IN>
-__global__ void __launch_bounds__(ACT_BLOCK)
-k_rs_bwd(RsArgs a)
+// k_rb_bump's step for the grouped forward: one thread per member (the block index), each on its own counter word -- the members'
+// counters are distinct and, the flags agreeing, none is null when this is launched
+__global__ void k_rs_bump_group(const TrainGroup<RsArgs> g)
 {
+    unsigned long long* const word = const_cast<unsigned long long*>(g.m[blockIdx.x].counter);
+    *word += 1ull;
+}
+
+template <typename IN, typename ARGS = RsArgs>
+__global__ void __launch_bounds__(ACT_BLOCK)
+k_rs_bwd(ARGS args)
+{
+    const RsArgs& a = train_member(args, blockIdx.y);
     const size_t b = (size_t)blockIdx.x * ACT_BLOCK + threadIdx.x;
     if (b >= a.B) return;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
@@ -2246,10 +2264,12 @@ __device__ __forceinline__ void al_finish(const AlArgs& a, const double* sum, do
 
 // ONE: the whole batch is this block (B <= PL_BLOCK): rows and statistics in one launch.  Otherwise the block leaves its partial sums
 // in the workspace for k_loss_final.
-template <typename IN, bool ONE>
+// blockIdx.x is the block within the batch, blockIdx.y (ARGS = TrainGroup<AlArgs>, ptg_actor_loss_group) the member
+template <typename IN, bool ONE, typename ARGS = AlArgs>
 __global__ void __launch_bounds__(PL_BLOCK)
-k_al_rows(AlArgs a)
+k_al_rows(ARGS args)
 {
+    const AlArgs& a = train_member(args, blockIdx.y);
     __shared__ double sh[PL_WAVES * PL_PITCH];
     const size_t i = (size_t)blockIdx.x * PL_BLOCK + threadIdx.x;
     const bool live = i < a.B;                               // the ragged last wave: no row, zero terms, but it takes part in the trees
@@ -2315,6 +2335,7 @@ k_al_rows(AlArgs a)
 }
 
 struct AlFinal {
+    __device__ static const double* partials(const AlArgs& a) { return a.ws; }
     __device__ void operator()(const AlArgs& a, const double* v) const
     {
         bool ok;
@@ -2322,6 +2343,8 @@ struct AlFinal {
         al_finish(a, v, alpha);
     }
 };
+
+static_assert(sizeof(TrainGroup<AlArgs>) == 8 * 232 && sizeof(TrainGroup<AlArgs>) + sizeof(const double*) <= 4096, "the launch takes 4 096 bytes of kernel arguments");
 
 // ================================================================================================= host side
 // the gathers' launch: the unit type V (16-byte piece or element) and the index source -- the caller's int32 / int64 indices, or with
@@ -2363,6 +2386,20 @@ void launch_loss(hipStream_t st, const A& a, const double* part, void (*one)(A),
     }
     hipLaunchKernelGGL(many, grid, block, 0, st, a);
     hipLaunchKernelGGL((k_loss_final<A, FIN>), dim3(1), block, 0, st, a, part);
+}
+
+// the grouped launches of a loss whose row kernel keeps nothing but its partials in the workspace: launch_loss's, the member as the
+// grid's y (rows) or x (the final merge, which finds each member's partials through FIN::partials)
+template <typename FIN, typename A>
+void launch_loss_group(hipStream_t st, const TrainGroup<A>& g, int n_members, void (*one)(TrainGroup<A>), void (*many)(TrainGroup<A>))
+{
+    const dim3 rows((unsigned)g.m[0].nblk, (unsigned)n_members), block(PL_BLOCK);
+    if (g.m[0].nblk == 1) {
+        hipLaunchKernelGGL(one, rows, block, 0, st, g);
+        return;
+    }
+    hipLaunchKernelGGL(many, rows, block, 0, st, g);
+    hipLaunchKernelGGL((k_loss_final<A, FIN, TrainGroup<A>>), dim3((unsigned)n_members), block, 0, st, g, (const double*)nullptr);
 }
 
 // the gSDE row kernels' NJ: the smallest of 4 | 8 | 16 that holds a lane's ceil(L / 64) units
@@ -2588,6 +2625,186 @@ bool optim_group_fault(const ptg_optim* m, int n, char* why, size_t cap)
     for (int i = 1; i < n; i++)
         for (int j = 0; j < i; j++) {
             TRAIN_DISTINCT(state_dev); TRAIN_DISTINCT(norm_dev); TRAIN_DISTINCT(ws_dev);
+        }
+    return false;
+}
+
+// ---- what ptg_td_loss / ptg_actor_loss / ptg_rsample(_backward) and their grouped entries share -------------
+// what a ptg_td is refused for, in the single call's order; true with the text in `why`
+bool td_desc_fault(const ptg_td* d, char* why, size_t cap)
+{
+    if (d->kind != PTG_TD_DQN && d->kind != PTG_TD_CRITICS) return train_fault(why, cap, "unknown kind %d", d->kind);
+    if (d->flags & ~(PTG_TD_ENTROPY | PTG_TD_LOG_ALPHA)) return train_fault(why, cap, "unknown flag in %d", d->flags);
+    const bool dqn = d->kind == PTG_TD_DQN, ent = (d->flags & PTG_TD_ENTROPY) != 0, log_alpha = (d->flags & PTG_TD_LOG_ALPHA) != 0;
+    const auto dtype_ok = [](int c) { return c == PTG_OUT_F32 || c == PTG_OUT_F64; };
+    if (ptg_td_loss_workspace(d->batch) < 0) return train_fault(why, cap, "batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (!dtype_ok(d->q_dtype) || !dtype_ok(d->rew_dtype) || !dtype_ok(d->done_dtype))
+        return train_fault(why, cap, "q_dtype, rew_dtype and done_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->rew_dev || !d->done_dev || !d->stats_dev) return train_fault(why, cap, "null rew_dev, done_dev or stats_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return train_fault(why, cap, "ws_dev is null or not aligned to 8 bytes");
+    if (dqn && ent) return train_fault(why, cap, "PTG_TD_ENTROPY applies to the critics only");
+    if (log_alpha && !ent) return train_fault(why, cap, "PTG_TD_LOG_ALPHA needs PTG_TD_ENTROPY");
+    if (ent && !d->next_logp_dev) return train_fault(why, cap, "PTG_TD_ENTROPY needs next_logp_dev");
+    if (log_alpha && !d->alpha_dev) return train_fault(why, cap, "PTG_TD_LOG_ALPHA needs alpha_dev");
+    int K = 1;
+    int64_t min_stride = 1;
+    if (dqn) {
+        if (d->n_actions < 2 || d->n_actions > 32) return train_fault(why, cap, "n_actions outside [2, 32]");
+        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return train_fault(why, cap, "DQN takes PTG_ACT_I32 or PTG_ACT_I64 actions");
+        if (!d->act_dev) return train_fault(why, cap, "DQN needs act_dev");
+        min_stride = d->n_actions;
+    } else {
+        if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return train_fault(why, cap, "n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
+        K = d->n_critics;
+    }
+    for (int k = 0; k < K; k++) {
+        if (!d->q_dev[k] || !d->next_q_dev[k] || !d->grad_q_dev[k]) return train_fault(why, cap, "null q_dev, next_q_dev or grad_q_dev [%d]", k);
+        if (d->q_s_n[k] < min_stride || d->next_s_n[k] < min_stride || d->g_s_n[k] < min_stride)
+            return train_fault(why, cap, "q_s_n, next_s_n or g_s_n [%d] below %lld", k, (long long)min_stride);
+    }
+    return false;
+}
+
+// the critics a checked ptg_td / ptg_al names: DQN's one Q network, none for the entropy-coefficient loss alone
+int td_critics(const ptg_td* d) { return d->kind == PTG_TD_DQN ? 1 : d->n_critics; }
+int al_critics(const ptg_al* d) { return d->kind == PTG_AL_ALPHA_ONLY ? 0 : d->n_critics; }
+
+TdArgs td_args(ptg_env* h, const ptg_td* d)
+{
+    const bool ent = (d->flags & PTG_TD_ENTROPY) != 0;
+    const int K = td_critics(d);
+    TdArgs a{};
+    for (int k = 0; k < K; k++) {
+        a.q[k] = d->q_dev[k]; a.q_s[k] = (size_t)d->q_s_n[k];
+        a.nq[k] = d->next_q_dev[k]; a.nq_s[k] = (size_t)d->next_s_n[k];
+        a.g[k] = d->grad_q_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    }
+    a.act = d->act_dev; a.rew = d->rew_dev; a.done = d->done_dev; a.lp = ent ? d->next_logp_dev : nullptr;
+    a.alpha_dev = ent ? d->alpha_dev : nullptr;
+    a.y = d->y_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.gamma = d->gamma; a.alpha = d->alpha; a.scale = d->scale;
+    a.B = (size_t)d->batch; a.A = d->n_actions; a.K = K; a.kind = d->kind; a.flags = d->flags; a.act_kind = d->act_kind;
+    a.rew_f64 = d->rew_dtype == PTG_OUT_F64; a.done_f64 = d->done_dtype == PTG_OUT_F64;
+    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
+    a.err = h->P.err;
+    return a;
+}
+
+// what a ptg_al is refused for, in the single call's order; true with the text in `why`
+bool al_desc_fault(const ptg_al* d, char* why, size_t cap)
+{
+    if (d->kind != PTG_AL_MIN && d->kind != PTG_AL_MEAN && d->kind != PTG_AL_ALPHA_ONLY) return train_fault(why, cap, "unknown kind %d", d->kind);
+    if (d->flags & ~(PTG_AL_ENTROPY | PTG_AL_LOG_ALPHA | PTG_AL_ENT_COEF)) return train_fault(why, cap, "unknown flag in %d", d->flags);
+    const bool only = d->kind == PTG_AL_ALPHA_ONLY, ent = (d->flags & PTG_AL_ENTROPY) != 0, log_alpha = (d->flags & PTG_AL_LOG_ALPHA) != 0,
+               ec = (d->flags & PTG_AL_ENT_COEF) != 0;
+    if (ptg_actor_loss_workspace(d->batch) < 0) return train_fault(why, cap, "batch %lld outside [1, 2^31]", (long long)d->batch);
+    if (d->q_dtype != PTG_OUT_F32 && d->q_dtype != PTG_OUT_F64) return train_fault(why, cap, "q_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
+    if (!d->stats_dev) return train_fault(why, cap, "null stats_dev");
+    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return train_fault(why, cap, "ws_dev is null or not aligned to 8 bytes");
+    if (only && (ent || !ec)) return train_fault(why, cap, "PTG_AL_ALPHA_ONLY takes PTG_AL_ENT_COEF and no PTG_AL_ENTROPY");
+    if (ec && !log_alpha) return train_fault(why, cap, "PTG_AL_ENT_COEF needs PTG_AL_LOG_ALPHA");
+    if (log_alpha && !ent && !ec) return train_fault(why, cap, "PTG_AL_LOG_ALPHA needs PTG_AL_ENTROPY or PTG_AL_ENT_COEF");
+    if (log_alpha && !d->alpha_dev) return train_fault(why, cap, "PTG_AL_LOG_ALPHA needs alpha_dev");
+    if ((ent || ec) && !d->logp_dev) return train_fault(why, cap, "PTG_AL_ENTROPY and PTG_AL_ENT_COEF need logp_dev");
+    if (ec && !std::isfinite(d->target_entropy)) return train_fault(why, cap, "PTG_AL_ENT_COEF needs a finite target_entropy");
+    if (d->grad_logp_dev && !ent) return train_fault(why, cap, "grad_logp_dev goes with PTG_AL_ENTROPY");
+    if (d->grad_log_alpha_dev && (!ec || (uintptr_t)d->grad_log_alpha_dev % sizeof(double) != 0))
+        return train_fault(why, cap, "grad_log_alpha_dev goes with PTG_AL_ENT_COEF and is aligned to 8 bytes");
+    if (!only) {
+        if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return train_fault(why, cap, "n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
+        int Q = 1;
+        if (d->kind == PTG_AL_MEAN) {
+            if (d->n_quantiles < 1 || d->n_quantiles > PTG_QL_MAX_QUANTILES) return train_fault(why, cap, "n_quantiles outside [1, %d]", PTG_QL_MAX_QUANTILES);
+            Q = d->n_quantiles;
+        }
+        for (int k = 0; k < d->n_critics; k++) {
+            if (!d->q_dev[k] || !d->grad_q_dev[k]) return train_fault(why, cap, "null q_dev or grad_q_dev [%d]", k);
+            if (d->q_s_n[k] < Q || d->g_s_n[k] < Q) return train_fault(why, cap, "q_s_n or g_s_n [%d] below %d", k, Q);
+        }
+    }
+    return false;
+}
+
+AlArgs al_args(ptg_env* h, const ptg_al* d)
+{
+    const bool ent = (d->flags & PTG_AL_ENTROPY) != 0, ec = (d->flags & PTG_AL_ENT_COEF) != 0;
+    const int K = al_critics(d);
+    AlArgs a{};
+    for (int k = 0; k < K; k++) {
+        a.q[k] = d->q_dev[k]; a.q_s[k] = (size_t)d->q_s_n[k];
+        a.g[k] = d->grad_q_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    }
+    a.lp = (ent || ec) ? d->logp_dev : nullptr; a.alpha_dev = (ent || ec) ? d->alpha_dev : nullptr;
+    a.g_lp = d->grad_logp_dev; a.g_la = d->grad_log_alpha_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
+    a.alpha = d->alpha; a.H_t = ec ? d->target_entropy : 0.0;
+    a.B = (size_t)d->batch; a.K = K; a.Q = d->kind == PTG_AL_MEAN ? d->n_quantiles : 1; a.kind = d->kind; a.flags = d->flags;
+    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
+    a.err = h->P.err;
+    return a;
+}
+
+// any grad_q_dev of member i against any of member j: the K gradient outputs of a member are K buffers
+template <typename D>
+bool train_shared_grads(const D* m, int K, int i, int j, char* why, size_t cap)
+{
+    for (int k = 0; k < K; k++)
+        for (int l = 0; l < K; l++)
+            if (train_shared(m[i].grad_q_dev[k], m[j].grad_q_dev[l], "grad_q_dev", j, i, why, cap)) return true;
+    return false;
+}
+
+bool td_group_fault(const ptg_td* m, int n, char* why, size_t cap)
+{
+    const ptg_td& a = m[0];
+    for (int i = 1; i < n; i++) {
+        const ptg_td& b = m[i];
+        TRAIN_AGREE(kind, "%d", int); TRAIN_AGREE(flags, "%d", int); TRAIN_AGREE(n_actions, "%d", int); TRAIN_AGREE(n_critics, "%d", int);
+        TRAIN_AGREE(q_dtype, "%d", int); TRAIN_AGREE(rew_dtype, "%d", int); TRAIN_AGREE(done_dtype, "%d", int); TRAIN_AGREE(act_kind, "%d", int);
+        TRAIN_AGREE(batch, "%lld", long long);
+    }
+    for (int i = 1; i < n; i++)
+        for (int j = 0; j < i; j++) {
+            TRAIN_DISTINCT(stats_dev); TRAIN_DISTINCT(ws_dev); TRAIN_DISTINCT(y_dev);
+            if (train_shared_grads(m, td_critics(&a), i, j, why, cap)) return true;
+        }
+    return false;
+}
+
+bool al_group_fault(const ptg_al* m, int n, char* why, size_t cap)
+{
+    const ptg_al& a = m[0];
+    for (int i = 1; i < n; i++) {
+        const ptg_al& b = m[i];
+        TRAIN_AGREE(kind, "%d", int); TRAIN_AGREE(flags, "%d", int); TRAIN_AGREE(n_critics, "%d", int); TRAIN_AGREE(n_quantiles, "%d", int);
+        TRAIN_AGREE(q_dtype, "%d", int); TRAIN_AGREE(batch, "%lld", long long);
+    }
+    for (int i = 1; i < n; i++)
+        for (int j = 0; j < i; j++) {
+            TRAIN_DISTINCT(stats_dev); TRAIN_DISTINCT(ws_dev);
+            if (train_shared_grads(m, al_critics(&a), i, j, why, cap)) return true;
+            TRAIN_DISTINCT(grad_logp_dev); TRAIN_DISTINCT(grad_log_alpha_dev);
+        }
+    return false;
+}
+
+// a shared counter_dev is refused too: the grouped forward reads every counter before any bump, G calls in turn would not
+bool rs_group_fault(const ptg_rs* m, int n, bool backward, char* why, size_t cap)
+{
+    const ptg_rs& a = m[0];
+    for (int i = 1; i < n; i++) {
+        const ptg_rs& b = m[i];
+        TRAIN_AGREE(kind, "%d", int); TRAIN_AGREE(flags, "%d", int); TRAIN_AGREE(q_dtype, "%d", int); TRAIN_AGREE(batch, "%lld", long long);
+    }
+    for (int i = 1; i < n; i++)
+        for (int j = 0; j < i; j++) {
+            if (backward) {
+                TRAIN_DISTINCT(grad_mean_dev); TRAIN_DISTINCT(grad_log_std_dev);
+                if (train_shared(m[i].grad_mean_dev, m[j].grad_log_std_dev, "grad_mean_dev and grad_log_std_dev", j, i, why, cap)) return true;
+                if (train_shared(m[i].grad_log_std_dev, m[j].grad_mean_dev, "grad_mean_dev and grad_log_std_dev", j, i, why, cap)) return true;
+            } else {
+                TRAIN_DISTINCT(act_dev); TRAIN_DISTINCT(logp_dev); TRAIN_DISTINCT(noise_dev);
+                if (!(a.flags & PTG_RS_DETERMINISTIC)) TRAIN_DISTINCT(counter_dev);
+            }
         }
     return false;
 }
@@ -3345,61 +3562,40 @@ int ptg_optim_step_group(ptg_env* h, const ptg_optim* members, int32_t n_members
 // ---- the TD losses: DQN's and the TD3 / SAC critics', the statistics and the gradients w.r.t. the current Q-values ---------
 int64_t ptg_td_loss_workspace(int64_t batch) { return loss_workspace(batch, PL_BLOCK); }
 
-int ptg_td_loss(ptg_env* h, const ptg_td* d, void* stream)
+// THE TD loss: ptg_td_loss is this walk over one descriptor with the single kernels, ptg_td_loss_group the same walk with the grouped
+// ones.  `grouped` is the entry that was called, not n_members > 1: a group of one launches the grouped kernels
+static int td_loss_walk(ptg_env* h, const char* who, const ptg_td* members, int n_members, bool grouped, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_td_loss: null descriptor");
-    if (d->kind != PTG_TD_DQN && d->kind != PTG_TD_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_td_loss: unknown kind %d", d->kind);
-    if (d->flags & ~(PTG_TD_ENTROPY | PTG_TD_LOG_ALPHA)) return set_err(h, PTG_E_INVALID, "ptg_td_loss: unknown flag in %d", d->flags);
-    const bool dqn = d->kind == PTG_TD_DQN, ent = (d->flags & PTG_TD_ENTROPY) != 0, log_alpha = (d->flags & PTG_TD_LOG_ALPHA) != 0;
-    const auto dtype_ok = [](int c) { return c == PTG_OUT_F32 || c == PTG_OUT_F64; };
-    if (ptg_td_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_td_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
-    if (!dtype_ok(d->q_dtype) || !dtype_ok(d->rew_dtype) || !dtype_ok(d->done_dtype))
-        return set_err(h, PTG_E_INVALID, "ptg_td_loss: q_dtype, rew_dtype and done_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
-    if (!d->rew_dev || !d->done_dev || !d->stats_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: null rew_dev, done_dev or stats_dev");
-    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_td_loss: ws_dev is null or not aligned to 8 bytes");
-    if (dqn && ent) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_ENTROPY applies to the critics only");
-    if (log_alpha && !ent) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_LOG_ALPHA needs PTG_TD_ENTROPY");
-    if (ent && !d->next_logp_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_ENTROPY needs next_logp_dev");
-    if (log_alpha && !d->alpha_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: PTG_TD_LOG_ALPHA needs alpha_dev");
-    int K = 1;
-    int64_t min_stride = 1;
-    if (dqn) {
-        if (d->n_actions < 2 || d->n_actions > 32) return set_err(h, PTG_E_INVALID, "ptg_td_loss: n_actions outside [2, 32]");
-        if (d->act_kind != PTG_ACT_I32 && d->act_kind != PTG_ACT_I64) return set_err(h, PTG_E_INVALID, "ptg_td_loss: DQN takes PTG_ACT_I32 or PTG_ACT_I64 actions");
-        if (!d->act_dev) return set_err(h, PTG_E_INVALID, "ptg_td_loss: DQN needs act_dev");
-        min_stride = d->n_actions;
-    } else {
-        if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_td_loss: n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
-        K = d->n_critics;
-    }
-    for (int k = 0; k < K; k++) {
-        if (!d->q_dev[k] || !d->next_q_dev[k] || !d->grad_q_dev[k]) return set_err(h, PTG_E_INVALID, "ptg_td_loss: null q_dev, next_q_dev or grad_q_dev [%d]", k);
-        if (d->q_s_n[k] < min_stride || d->next_s_n[k] < min_stride || d->g_s_n[k] < min_stride)
-            return set_err(h, PTG_E_INVALID, "ptg_td_loss: q_s_n, next_s_n or g_s_n [%d] below %lld", k, (long long)min_stride);
-    }
+    if (int rc = train_refuse(h, who, members, n_members, grouped, td_desc_fault,
+                              [&](char* why, size_t cap) { return td_group_fault(members, n_members, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    TdArgs a{};
-    for (int k = 0; k < K; k++) {
-        a.q[k] = d->q_dev[k]; a.q_s[k] = (size_t)d->q_s_n[k];
-        a.nq[k] = d->next_q_dev[k]; a.nq_s[k] = (size_t)d->next_s_n[k];
-        a.g[k] = d->grad_q_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    const ptg_td* d = &members[0];       // kind, dtype and batch: the group's
+    TrainGroup<TdArgs> g{};
+    for (int i = 0; i < n_members; i++) g.m[i] = td_args(h, &members[i]);
+    const TdArgs& a = g.m[0];
+    const bool f64 = d->q_dtype == PTG_OUT_F64, dqn = d->kind == PTG_TD_DQN;      // the Q dtype and the kind are the row kernel's template axes
+    if (!grouped) {
+        if (f64 && dqn) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<double, true, true>, k_td_rows<double, true, false>);
+        else if (f64) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<double, false, true>, k_td_rows<double, false, false>);
+        else if (dqn) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<float, true, true>, k_td_rows<float, true, false>);
+        else launch_loss<TdFinal>(st, a, a.ws, k_td_rows<float, false, true>, k_td_rows<float, false, false>);
+        return launch_check(h, "k_td_rows");
     }
-    a.act = d->act_dev; a.rew = d->rew_dev; a.done = d->done_dev; a.lp = ent ? d->next_logp_dev : nullptr;
-    a.alpha_dev = ent ? d->alpha_dev : nullptr;
-    a.y = d->y_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
-    a.gamma = d->gamma; a.alpha = d->alpha; a.scale = d->scale;
-    a.B = (size_t)d->batch; a.A = d->n_actions; a.K = K; a.kind = d->kind; a.flags = d->flags; a.act_kind = d->act_kind;
-    a.rew_f64 = d->rew_dtype == PTG_OUT_F64; a.done_f64 = d->done_dtype == PTG_OUT_F64;
-    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
-    a.err = h->P.err;
-    const bool f64 = d->q_dtype == PTG_OUT_F64;               // the Q dtype and the kind are the row kernel's template axes
-    if (f64 && dqn) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<double, true, true>, k_td_rows<double, true, false>);
-    else if (f64) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<double, false, true>, k_td_rows<double, false, false>);
-    else if (dqn) launch_loss<TdFinal>(st, a, a.ws, k_td_rows<float, true, true>, k_td_rows<float, true, false>);
-    else launch_loss<TdFinal>(st, a, a.ws, k_td_rows<float, false, true>, k_td_rows<float, false, false>);
-    return launch_check(h, "k_td_rows");
+    using G = TrainGroup<TdArgs>;
+    if (f64 && dqn) launch_loss_group<TdFinal>(st, g, n_members, k_td_rows<double, true, true, G>, k_td_rows<double, true, false, G>);
+    else if (f64) launch_loss_group<TdFinal>(st, g, n_members, k_td_rows<double, false, true, G>, k_td_rows<double, false, false, G>);
+    else if (dqn) launch_loss_group<TdFinal>(st, g, n_members, k_td_rows<float, true, true, G>, k_td_rows<float, true, false, G>);
+    else launch_loss_group<TdFinal>(st, g, n_members, k_td_rows<float, false, true, G>, k_td_rows<float, false, false, G>);
+    return launch_check(h, "k_td_rows (grouped)");
+}
+
+int ptg_td_loss(ptg_env* h, const ptg_td* d, void* stream) { return td_loss_walk(h, "ptg_td_loss", d, 1, false, stream); }
+
+int ptg_td_loss_group(ptg_env* h, const ptg_td* members, int32_t n_members, void* stream)
+{
+    return td_loss_walk(h, "ptg_td_loss_group", members, n_members, true, stream);
 }
 
 // ---- the quantile-Huber loss of TQC's critics, the statistics and the gradients w.r.t. the current quantiles -------------------------
@@ -3449,8 +3645,9 @@ int ptg_quantile_loss(ptg_env* h, const ptg_ql* d, void* stream)
 }
 
 // ---- the training-time actor head: reparametrised squashed-Gaussian sample with its log-prob, its backward, TD3's smoothed target action ----
-static void rs_args(ptg_env* h, const ptg_rs* d, RsArgs& a)
+static RsArgs rs_args(ptg_env* h, const ptg_rs* d)
 {
+    RsArgs a{};
     a.mean = d->mean_dev; a.m_s = (size_t)d->mean_s_n; a.ls = d->log_std_dev; a.ls_s = (size_t)d->log_std_s_n;
     a.act = d->act_dev; a.logp = d->logp_dev; a.noise = d->noise_dev;
     a.g_act = d->grad_act_dev; a.g_logp = d->grad_logp_dev;
@@ -3458,92 +3655,96 @@ static void rs_args(ptg_env* h, const ptg_rs* d, RsArgs& a)
     a.counter = (d->flags & PTG_RS_DETERMINISTIC) ? nullptr : (const unsigned long long*)d->counter_dev; a.seed = (unsigned long long)d->seed;
     a.sigma_t = d->noise_std; a.c = d->noise_clip; a.lo = d->clip_lo; a.hi = d->clip_hi;
     a.B = (size_t)d->batch; a.kind = d->kind; a.err = h->P.err;
+    return a;
 }
 
-int ptg_rsample(ptg_env* h, const ptg_rs* d, void* stream)
+// THE actor head: ptg_rsample and ptg_rsample_backward are this walk over one descriptor with the single kernels, their grouped entries
+// the same walk with the grouped ones on a grid of (blocks of the batch, members).  `grouped` is the entry that was called
+static int rsample_walk(ptg_env* h, const char* who, const ptg_rs* members, int n_members, bool grouped, bool backward, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_rsample: null descriptor");
-    if (const char* why = rs_desc_error(d, false)) return set_err(h, PTG_E_INVALID, "ptg_rsample: %s", why);
+    if (int rc = train_refuse(h, who, members, n_members, grouped,
+                              [&](const ptg_rs* d, char* why, size_t cap) { const char* e = rs_desc_error(d, backward); return e ? train_fault(why, cap, "%s", e) : false; },
+                              [&](char* why, size_t cap) { return rs_group_fault(members, n_members, backward, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    RsArgs a{};
-    rs_args(h, d, a);
-    const dim3 grid((unsigned)((a.B + ACT_BLOCK - 1) / ACT_BLOCK)), block(ACT_BLOCK);
-    if (d->q_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_rs_fwd<double>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_rs_fwd<float>, grid, block, 0, st, a);
-    if (a.counter) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)d->counter_dev, 1ull);
-    return launch_check(h, "k_rs_fwd");
+    const ptg_rs* d = &members[0];       // dtype, flags and batch: the group's
+    TrainGroup<RsArgs> g{};
+    for (int i = 0; i < n_members; i++) g.m[i] = rs_args(h, &members[i]);
+    const RsArgs& a = g.m[0];
+    const bool f64 = d->q_dtype == PTG_OUT_F64;
+    const unsigned nblk = (unsigned)((a.B + ACT_BLOCK - 1) / ACT_BLOCK);
+    const dim3 block(ACT_BLOCK);
+    if (!grouped) {
+        const dim3 grid(nblk);
+        if (backward) {
+            if (f64) hipLaunchKernelGGL(k_rs_bwd<double>, grid, block, 0, st, a);
+            else hipLaunchKernelGGL(k_rs_bwd<float>, grid, block, 0, st, a);
+            return launch_check(h, "k_rs_bwd");
+        }
+        if (f64) hipLaunchKernelGGL(k_rs_fwd<double>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_rs_fwd<float>, grid, block, 0, st, a);
+        if (a.counter) hipLaunchKernelGGL(k_rb_bump, dim3(1), dim3(1), 0, st, (unsigned long long*)d->counter_dev, 1ull);
+        return launch_check(h, "k_rs_fwd");
+    }
+    const dim3 grid(nblk, (unsigned)n_members);
+    if (backward) {
+        if (f64) hipLaunchKernelGGL((k_rs_bwd<double, TrainGroup<RsArgs>>), grid, block, 0, st, g);
+        else hipLaunchKernelGGL((k_rs_bwd<float, TrainGroup<RsArgs>>), grid, block, 0, st, g);
+        return launch_check(h, "k_rs_bwd (grouped)");
+    }
+    if (f64) hipLaunchKernelGGL((k_rs_fwd<double, TrainGroup<RsArgs>>), grid, block, 0, st, g);
+    else hipLaunchKernelGGL((k_rs_fwd<float, TrainGroup<RsArgs>>), grid, block, 0, st, g);
+    if (a.counter) hipLaunchKernelGGL(k_rs_bump_group, dim3((unsigned)n_members), dim3(1), 0, st, g);      // the flags agree: every member has its counter
+    return launch_check(h, "k_rs_fwd (grouped)");
 }
 
-int ptg_rsample_backward(ptg_env* h, const ptg_rs* d, void* stream)
+int ptg_rsample(ptg_env* h, const ptg_rs* d, void* stream) { return rsample_walk(h, "ptg_rsample", d, 1, false, false, stream); }
+
+int ptg_rsample_backward(ptg_env* h, const ptg_rs* d, void* stream) { return rsample_walk(h, "ptg_rsample_backward", d, 1, false, true, stream); }
+
+int ptg_rsample_group(ptg_env* h, const ptg_rs* members, int32_t n_members, void* stream)
 {
-    if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_rsample_backward: null descriptor");
-    if (const char* why = rs_desc_error(d, true)) return set_err(h, PTG_E_INVALID, "ptg_rsample_backward: %s", why);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const hipStream_t st = as_stream(stream);
-    RsArgs a{};
-    rs_args(h, d, a);
-    const dim3 grid((unsigned)((a.B + ACT_BLOCK - 1) / ACT_BLOCK)), block(ACT_BLOCK);
-    if (d->q_dtype == PTG_OUT_F64) hipLaunchKernelGGL(k_rs_bwd<double>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_rs_bwd<float>, grid, block, 0, st, a);
-    return launch_check(h, "k_rs_bwd");
+    return rsample_walk(h, "ptg_rsample_group", members, n_members, true, false, stream);
+}
+
+int ptg_rsample_backward_group(ptg_env* h, const ptg_rs* members, int32_t n_members, void* stream)
+{
+    return rsample_walk(h, "ptg_rsample_backward_group", members, n_members, true, true, stream);
 }
 
 // ---- the actor and entropy-coefficient losses of SAC / TQC / TD3, the statistics and the gradients -----------------------------------
 int64_t ptg_actor_loss_workspace(int64_t batch) { return loss_workspace(batch, PL_BLOCK); }
 
-int ptg_actor_loss(ptg_env* h, const ptg_al* d, void* stream)
+// THE actor loss: ptg_actor_loss is this walk over one descriptor with the single kernels, ptg_actor_loss_group the same walk with the
+// grouped ones.  `grouped` is the entry that was called
+static int actor_loss_walk(ptg_env* h, const char* who, const ptg_al* members, int n_members, bool grouped, void* stream)
 {
     if (!h) return PTG_E_INVALID;
-    if (!d) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: null descriptor");
-    if (d->kind != PTG_AL_MIN && d->kind != PTG_AL_MEAN && d->kind != PTG_AL_ALPHA_ONLY) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: unknown kind %d", d->kind);
-    if (d->flags & ~(PTG_AL_ENTROPY | PTG_AL_LOG_ALPHA | PTG_AL_ENT_COEF)) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: unknown flag in %d", d->flags);
-    const bool only = d->kind == PTG_AL_ALPHA_ONLY, ent = (d->flags & PTG_AL_ENTROPY) != 0, log_alpha = (d->flags & PTG_AL_LOG_ALPHA) != 0,
-               ec = (d->flags & PTG_AL_ENT_COEF) != 0;
-    if (ptg_actor_loss_workspace(d->batch) < 0) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: batch %lld outside [1, 2^31]", (long long)d->batch);
-    if (d->q_dtype != PTG_OUT_F32 && d->q_dtype != PTG_OUT_F64) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: q_dtype must be PTG_OUT_F32 or PTG_OUT_F64");
-    if (!d->stats_dev) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: null stats_dev");
-    if (!d->ws_dev || (uintptr_t)d->ws_dev % sizeof(double) != 0) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: ws_dev is null or not aligned to 8 bytes");
-    if (only && (ent || !ec)) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ALPHA_ONLY takes PTG_AL_ENT_COEF and no PTG_AL_ENTROPY");
-    if (ec && !log_alpha) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ENT_COEF needs PTG_AL_LOG_ALPHA");
-    if (log_alpha && !ent && !ec) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_LOG_ALPHA needs PTG_AL_ENTROPY or PTG_AL_ENT_COEF");
-    if (log_alpha && !d->alpha_dev) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_LOG_ALPHA needs alpha_dev");
-    if ((ent || ec) && !d->logp_dev) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ENTROPY and PTG_AL_ENT_COEF need logp_dev");
-    if (ec && !std::isfinite(d->target_entropy)) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: PTG_AL_ENT_COEF needs a finite target_entropy");
-    if (d->grad_logp_dev && !ent) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: grad_logp_dev goes with PTG_AL_ENTROPY");
-    if (d->grad_log_alpha_dev && (!ec || (uintptr_t)d->grad_log_alpha_dev % sizeof(double) != 0))
-        return set_err(h, PTG_E_INVALID, "ptg_actor_loss: grad_log_alpha_dev goes with PTG_AL_ENT_COEF and is aligned to 8 bytes");
-    int K = 0, Q = 1;
-    if (!only) {
-        if (d->n_critics < 1 || d->n_critics > PTG_TD_MAX_CRITICS) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: n_critics outside [1, %d]", PTG_TD_MAX_CRITICS);
-        K = d->n_critics;
-        if (d->kind == PTG_AL_MEAN) {
-            if (d->n_quantiles < 1 || d->n_quantiles > PTG_QL_MAX_QUANTILES) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: n_quantiles outside [1, %d]", PTG_QL_MAX_QUANTILES);
-            Q = d->n_quantiles;
-        }
-        for (int k = 0; k < K; k++) {
-            if (!d->q_dev[k] || !d->grad_q_dev[k]) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: null q_dev or grad_q_dev [%d]", k);
-            if (d->q_s_n[k] < Q || d->g_s_n[k] < Q) return set_err(h, PTG_E_INVALID, "ptg_actor_loss: q_s_n or g_s_n [%d] below %d", k, Q);
-        }
-    }
+    if (int rc = train_refuse(h, who, members, n_members, grouped, al_desc_fault,
+                              [&](char* why, size_t cap) { return al_group_fault(members, n_members, why, cap); })) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const hipStream_t st = as_stream(stream);
-    AlArgs a{};
-    for (int k = 0; k < K; k++) {
-        a.q[k] = d->q_dev[k]; a.q_s[k] = (size_t)d->q_s_n[k];
-        a.g[k] = d->grad_q_dev[k]; a.g_s[k] = (size_t)d->g_s_n[k];
+    TrainGroup<AlArgs> g{};
+    for (int i = 0; i < n_members; i++) g.m[i] = al_args(h, &members[i]);
+    const AlArgs& a = g.m[0];
+    const bool f64 = members[0].q_dtype == PTG_OUT_F64;      // the group's
+    if (!grouped) {
+        if (f64) launch_loss<AlFinal>(st, a, a.ws, k_al_rows<double, true>, k_al_rows<double, false>);
+        else launch_loss<AlFinal>(st, a, a.ws, k_al_rows<float, true>, k_al_rows<float, false>);
+        return launch_check(h, "k_al_rows");
     }
-    a.lp = (ent || ec) ? d->logp_dev : nullptr; a.alpha_dev = (ent || ec) ? d->alpha_dev : nullptr;
-    a.g_lp = d->grad_logp_dev; a.g_la = d->grad_log_alpha_dev; a.stats = d->stats_dev; a.ws = (double*)d->ws_dev;
-    a.alpha = d->alpha; a.H_t = ec ? d->target_entropy : 0.0;
-    a.B = (size_t)d->batch; a.K = K; a.Q = Q; a.kind = d->kind; a.flags = d->flags;
-    a.nblk = (int)loss_blocks(d->batch, PL_BLOCK);
-    a.err = h->P.err;
-    if (d->q_dtype == PTG_OUT_F64) launch_loss<AlFinal>(st, a, a.ws, k_al_rows<double, true>, k_al_rows<double, false>);
-    else launch_loss<AlFinal>(st, a, a.ws, k_al_rows<float, true>, k_al_rows<float, false>);
-    return launch_check(h, "k_al_rows");
+    using G = TrainGroup<AlArgs>;
+    if (f64) launch_loss_group<AlFinal>(st, g, n_members, k_al_rows<double, true, G>, k_al_rows<double, false, G>);
+    else launch_loss_group<AlFinal>(st, g, n_members, k_al_rows<float, true, G>, k_al_rows<float, false, G>);
+    return launch_check(h, "k_al_rows (grouped)");
+}
+
+int ptg_actor_loss(ptg_env* h, const ptg_al* d, void* stream) { return actor_loss_walk(h, "ptg_actor_loss", d, 1, false, stream); }
+
+int ptg_actor_loss_group(ptg_env* h, const ptg_al* members, int32_t n_members, void* stream)
+{
+    return actor_loss_walk(h, "ptg_actor_loss_group", members, n_members, true, stream);
 }
 
 }  // extern "C"

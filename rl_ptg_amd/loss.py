@@ -6,7 +6,9 @@ and TQC's actor head with gSDE (HipEngine.sde_rsample / sde_rsample_backward, pt
 dqn_loss / td3_critic_loss / sac_critic_loss: the fused TD losses (HipEngine.td_loss, ptg_td_loss) likewise, and tqc_critic_loss: TQC's
 quantile-Huber critic loss (HipEngine.quantile_loss, ptg_quantile_loss); squashed_rsample (HipEngine.rsample / rsample_backward,
 ptg_rsample) and sac_actor_loss / tqc_actor_loss / td3_actor_loss / ent_coef_loss (HipEngine.actor_loss, ptg_actor_loss): the actor
-half of an off-policy step -- see the end of the file.
+half of an off-policy step; dqn_loss_group / td3_critic_loss_group / sac_critic_loss_group, squashed_rsample_group, sac_actor_loss_group /
+tqc_actor_loss_group / td3_actor_loss_group and ent_coef_loss_group: those of up to eight independent agents in the launches of one
+(HipEngine.td_loss_group, rsample_group / rsample_backward_group, actor_loss_group) -- see the end of the file.
 
     out = net(obs)                                            # [B, A + 1]: logits and a value column
     loss, stats = ppo_loss(engine, out[:, :A], out[:, A], actions, old_log_prob, advantages, returns, clip_range=0.2)
@@ -420,3 +422,237 @@ def ent_coef_loss(engine, log_prob, log_ent_coef, *, target_entropy, out=None, w
     the alpha optimiser's step for both."""
     kw = dict(target_entropy=target_entropy, out=out, workspace=workspace)
     return _ActorLossFn.apply(engine, "ent_coef", False, 0, kw, log_prob.detach(), log_ent_coef)
+
+
+# ------------------------------------------------------------------------------------------------- G agents' off-policy steps in one's launches
+#     qs = critics(cur_in)                                      # TrainMLPGroup: the K critics of every agent, agent by agent
+#     losses, stats = sac_critic_loss_group(engine, [dict(q=qs[K * i:K * i + K], next_q=..., rewards=..., dones=..., next_log_prob=...,
+#                                                         ent_coef=alpha_i) for i in range(G)], gamma=[0.96, 0.97, ...])
+#     torch.autograd.backward(losses)                           # ONE pass: every agent's gradients go to its own critics
+# Each *_group function is ONE autograd function over the members (HipEngine.td_loss_group / rsample_group / rsample_backward_group /
+# actor_loss_group; DESIGN.md section 27): member i's loss, statistics and gradients are, bit for bit, what the single function gives
+# for its arguments.  A member dict holds the single function's tensors by name (and out, workspace); its scalars are keyword
+# arguments, one value for all or a list with one per member.  A loss left out of the backward pass leaves its networks alone.
+def _group_members(who, members, takes, needs, scalars):
+    """the members as a list of call dicts: every name known, the needed tensors there, the scalars spread (a list: one per member)"""
+    if not isinstance(members, (list, tuple)) or not members or not all(isinstance(m, dict) for m in members):
+        raise TypeError(f"{who}: members must be a non-empty list of dicts {needs}, got {type(members).__name__}")
+    G = len(members)
+    calls = []
+    for i, m in enumerate(members):
+        unknown = [k for k in m if k not in takes]
+        if unknown:
+            raise TypeError(f"{who}: member {i} names {unknown}; a member holds {takes}, the scalars are keyword arguments")
+        missing = [k for k in needs if m.get(k) is None]
+        if missing:
+            raise TypeError(f"{who}: member {i} needs {missing}")
+        kw = dict(m)
+        for name, v in scalars.items():
+            if isinstance(v, list):
+                if len(v) != G:
+                    raise ValueError(f"{who}: {name} must have one entry per member, {G}, or be one value for all; got {len(v)}")
+                v = v[i]
+            if v is not None and kw.get(name) is None:
+                kw[name] = v
+        calls.append(kw)
+    return calls
+
+
+def _det_all(x):
+    return [_det(t) for t in x] if isinstance(x, (list, tuple)) else _det(x)
+
+
+class _TdLossGroupFn(torch.autograd.Function):
+    """forward: one td_loss_group over the members; backward: each member's gradients, scaled by its loss's incoming gradient, to its
+    current Q tensors; a loss that received no gradient hands None to its networks"""
+
+    @staticmethod
+    def forward(ctx, engine, kind, members, n_q, *q):        # q: the current Q tensors of every member, n_q[i] of member i
+        dqn = kind == "dqn"
+        calls, at = [], 0
+        for m, n in zip(members, n_q):
+            mine, at = q[at:at + n], at + n
+            kw = dict(m)
+            if kw.get("out") is None:                        # fresh gradients are zeroed, as _TdLossFn's are
+                dev, dt = mine[0].device, mine[0].dtype
+                grads = [torch.zeros(t.shape, dtype=dt, device=dev) for t in mine]
+                kw["out"] = (torch.empty(8, dtype=torch.float64, device=dev), grads[0] if dqn else grads, None)
+            qd = [t.detach() for t in mine]
+            calls.append(dict(kw, q=qd[0] if dqn else qd))
+        res = engine.td_loss_group(kind, calls)
+        ctx.grads = [[r.grad_q] if dqn else list(r.grad_q) for r in res]
+        ctx.shapes = [t.shape for t in q]
+        stats = [r.stats for r in res]
+        ctx.mark_non_differentiable(*stats)
+        ctx.set_materialize_grads(False)                     # an unused loss's gradient arrives as None, not as a zero
+        return (*[r.stats[0].to(gs[0].dtype, copy=True) for r, gs in zip(res, ctx.grads)], *stats)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        out, shapes = [], iter(ctx.shapes)
+        for gs, g in zip(ctx.grads, grads):
+            out += [None if g is None else (x * g).reshape(s) for x, s in zip(gs, shapes)]
+        return (None, None, None, None, *out)
+
+
+def _td_group(who, kind, engine, members, needs, scalars):
+    calls = _group_members(who, members, needs + ("out", "workspace", "ent_coef", "log_ent_coef")[:4 if kind == "sac" else 2], needs, scalars)
+    q = [[m.pop("q")] if kind == "dqn" else list(m.pop("q")) for m in calls]
+    calls = [{k: _det_all(v) if k != "out" else v for k, v in m.items()} for m in calls]
+    out = _TdLossGroupFn.apply(engine, kind, calls, [len(x) for x in q], *[t for x in q for t in x])
+    return list(out[:len(calls)]), list(out[len(calls):])
+
+
+def dqn_loss_group(engine, members, *, gamma):
+    """dqn_loss for G independent agents' replay batches of one batch size, 1 <= G <= 8, in the launches of ONE dqn_loss -> (losses,
+    stats): two lists of G.  members: dicts of q, next_q, actions, rewards, dones (out, workspace); gamma: one value or a list."""
+    return _td_group("dqn_loss_group", "dqn", engine, members, ("q", "next_q", "actions", "rewards", "dones"), dict(gamma=gamma))
+
+
+def td3_critic_loss_group(engine, members, *, gamma):
+    """td3_critic_loss for G independent agents -> (losses, stats).  members: dicts of q, next_q (lists of K critic outputs), rewards,
+    dones (out, workspace); gamma: one value or a list."""
+    return _td_group("td3_critic_loss_group", "td3", engine, members, ("q", "next_q", "rewards", "dones"), dict(gamma=gamma))
+
+
+def sac_critic_loss_group(engine, members, *, gamma, ent_coef=None):
+    """sac_critic_loss for G independent agents -> (losses, stats).  members: dicts of q, next_q (lists of K critic outputs), rewards,
+    dones, next_log_prob and one of ent_coef (a float or a float64 device tensor of 1 element) and log_ent_coef (out, workspace); all
+    members bring log_ent_coef or none does.  gamma, ent_coef: one value or a list with one per member."""
+    return _td_group("sac_critic_loss_group", "sac", engine, members, ("q", "next_q", "rewards", "dones", "next_log_prob"), dict(gamma=gamma, ent_coef=ent_coef))
+
+
+class _RSampleGroupFn(torch.autograd.Function):
+    """forward: one rsample_group; backward: one rsample_backward_group over the members whose outputs received a gradient"""
+
+    @staticmethod
+    def forward(ctx, engine, members, deterministic, *diff):     # diff: mean, log_std of every member
+        calls = [dict(m, mean=diff[2 * i].detach(), log_std=diff[2 * i + 1].detach()) for i, m in enumerate(members)]
+        res = engine.rsample_group(calls, deterministic=deterministic)
+        if any(r.noise is None for r in res):
+            raise ValueError("squashed_rsample_group: out.noise is None, but the backward reads it")
+        ctx.engine, ctx.noise = engine, [r.noise for r in res]
+        ctx.save_for_backward(*diff)
+        ctx.set_materialize_grads(False)
+        return tuple(t for r in res for t in (r.actions, r.log_prob))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        diff = ctx.saved_tensors
+        live, calls = [], []
+        for i, noise in enumerate(ctx.noise):
+            ga, gl = grads[2 * i], grads[2 * i + 1]
+            if ga is None and gl is None:
+                continue
+            live.append(i)
+            calls.append(dict(mean=diff[2 * i].detach(), log_std=diff[2 * i + 1].detach(), noise=noise, grad_actions=None if ga is None else ga.contiguous(),
+                              grad_log_prob=None if gl is None else gl.contiguous()))
+        out = [None] * len(diff)
+        if calls:
+            for i, g in zip(live, ctx.engine.rsample_backward_group(calls)):
+                out[2 * i], out[2 * i + 1] = g.grad_mean, g.grad_log_std
+        return (None, None, None, *out)
+
+
+def squashed_rsample_group(engine, members, *, seed=0, deterministic=False):
+    """squashed_rsample for G independent actors' outputs of one batch size, 1 <= G <= 8, in the launches of ONE squashed_rsample -> a
+    list of G (actions, log_prob) pairs, each differentiable in its member's mean and log_std.  members: dicts of mean, log_std, counter
+    (out); every member its own counter.  seed: one value or a list with one per member.  The backward is one
+    HipEngine.rsample_backward_group call over the members whose outputs received a gradient."""
+    calls = _group_members("squashed_rsample_group", members, ("mean", "log_std", "counter", "out"), ("mean", "log_std"), dict(seed=seed))
+    diff = [t for m in calls for t in (m.pop("mean"), m.pop("log_std"))]
+    out = _RSampleGroupFn.apply(engine, calls, deterministic, *diff)
+    return [(out[2 * i], out[2 * i + 1]) for i in range(len(calls))]
+
+
+class _ActorLossGroupFn(torch.autograd.Function):
+    """forward: one actor_loss_group over the members; backward: each member's gradients, scaled by its loss's incoming gradient"""
+
+    @staticmethod
+    def forward(ctx, engine, kind, members, layout, *diff):  # layout[i] = (as_list, n_q, tensors of member i in diff); diff as _ActorLossFn's, member by member
+        calls, at = [], 0
+        for m, (as_list, n_q, n) in zip(members, layout):
+            d, at = [t.detach() for t in diff[at:at + n]], at + n
+            if kind == "ent_coef":
+                calls.append(dict(m, log_prob=d[0], log_ent_coef=d[1]))
+            elif kind == "td3":
+                calls.append(dict(m, q=d[0]))
+            else:
+                calls.append(dict(m, q=d[:n_q] if as_list else d[0], log_prob=d[n_q]))
+        res = engine.actor_loss_group(kind, calls)
+        ctx.grads = []
+        for r, (as_list, n_q, n) in zip(res, layout):
+            if kind == "ent_coef":
+                ctx.grads.append([None, r.grad_log_ent_coef])
+            elif kind == "td3":
+                ctx.grads.append([r.grad_q])
+            else:
+                ctx.grads.append((list(r.grad_q) if as_list else [r.grad_q]) + [r.grad_log_prob])
+        ctx.shapes = [t.shape for t in diff]
+        stats = [r.stats for r in res]
+        ctx.mark_non_differentiable(*stats)
+        ctx.set_materialize_grads(False)
+        if kind == "ent_coef":
+            return (*[r.stats[1].clone() for r in res], *stats)
+        firsts, at = [], 0
+        for _, _, n in layout:
+            firsts.append(diff[at].dtype)
+            at += n
+        return (*[r.stats[0].to(dt, copy=True) for r, dt in zip(res, firsts)], *stats)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        out, shapes = [], iter(ctx.shapes)
+        for gs, g in zip(ctx.grads, grads):
+            for x in gs:
+                s = next(shapes)
+                out.append(None if g is None or x is None else (x * g).reshape(s))
+        return (None, None, None, None, *out)
+
+
+def _actor_group(who, kind, engine, members, needs, scalars, q_name):
+    takes = needs + ("out", "workspace") + (("ent_coef", "log_ent_coef") if kind in ("sac", "tqc") else ())
+    calls = _group_members(who, members, takes, needs, scalars)
+    layout, diff = [], []
+    for m in calls:
+        if kind == "ent_coef":
+            mine, as_list, n_q = [m.pop("log_prob").detach(), m.pop("log_ent_coef")], False, 0
+        elif kind == "td3":
+            mine, as_list, n_q = [m.pop(q_name)], False, 1
+        else:
+            q = m.pop(q_name)
+            as_list = isinstance(q, (list, tuple))
+            qs = list(q) if as_list else [q]
+            mine, n_q = qs + [m.pop("log_prob")], len(qs)
+        for k in ("ent_coef", "log_ent_coef"):
+            if k in m:
+                m[k] = _det(m[k])
+        layout.append((as_list, n_q, len(mine)))
+        diff += mine
+    out = _ActorLossGroupFn.apply(engine, kind, calls, layout, *diff)
+    return list(out[:len(calls)]), list(out[len(calls):])
+
+
+def sac_actor_loss_group(engine, members, *, ent_coef=None):
+    """sac_actor_loss for G independent agents of one batch size, 1 <= G <= 8, in the launches of ONE sac_actor_loss -> (losses, stats).
+    members: dicts of q (the list of K critic outputs on (obs, actions_pi)), log_prob and one of ent_coef and log_ent_coef (out,
+    workspace); ent_coef: one value or a list with one per member."""
+    return _actor_group("sac_actor_loss_group", "sac", engine, members, ("q", "log_prob"), dict(ent_coef=ent_coef), "q")
+
+
+def tqc_actor_loss_group(engine, members, *, ent_coef=None):
+    """tqc_actor_loss for G independent agents -> (losses, stats).  members: dicts of quantiles (a [B, K, Q] tensor or a list of K
+    [B, Q] tensors, all members alike), log_prob and one of ent_coef and log_ent_coef (out, workspace)."""
+    return _actor_group("tqc_actor_loss_group", "tqc", engine, members, ("quantiles", "log_prob"), dict(ent_coef=ent_coef), "quantiles")
+
+
+def td3_actor_loss_group(engine, members):
+    """td3_actor_loss for G independent agents -> (losses, stats).  members: dicts of q1 [B] / [B, 1] (out, workspace)."""
+    return _actor_group("td3_actor_loss_group", "td3", engine, members, ("q1",), {}, "q1")
+
+
+def ent_coef_loss_group(engine, members, *, target_entropy):
+    """ent_coef_loss for G independent agents -> (losses, stats): each loss a 0-dim float64 tensor differentiable in its member's
+    log_ent_coef alone; stats[i][4:5] is member i's alpha on the device.  members: dicts of log_prob, log_ent_coef (out, workspace);
+    target_entropy: one value or a list with one per member."""
+    return _actor_group("ent_coef_loss_group", "ent_coef", engine, members, ("log_prob", "log_ent_coef"), dict(target_entropy=target_entropy), None)

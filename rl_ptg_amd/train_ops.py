@@ -1248,8 +1248,18 @@ class TrainOps:
         allocated when missing.  Fresh gradients are torch.empty: a row refused for its action keeps what was there.  Outputs must
         not overlap each other or the inputs: a tensor given twice is refused, any other overlap is not checked.  No
         synchronisation; a bad row makes the next sync() raise PtgError (PTG_E_INDEX / PTG_E_NONFINITE)."""
+        d, res, _ = self._td_loss_member("td_loss", kind, q, next_q, rewards, dones, gamma, actions=actions, next_log_prob=next_log_prob, ent_coef=ent_coef,
+                                         log_ent_coef=log_ent_coef, want_target=want_target, out=out, workspace=workspace)[1]()
+        self._call("ptg_td_loss", C.byref(d))
+        return res
+
+    def _td_loss_member(self, who, kind, q, next_q, rewards, dones, gamma, *, actions=None, next_log_prob=None, ent_coef=None, log_ent_coef=None,
+                        want_target=False, out=None, workspace=None):
+        """Every check of ONE TD-loss call, in td_loss's order, for td_loss and for each member of td_loss_group (who: "td_loss", or
+        "td_loss_group: member i").  Allocates nothing and does not touch the library.  Returns (what a group must agree in, as (name,
+        value) pairs; make; the outputs and workspace the caller gave), where make() allocates what was not given and returns (the
+        PtgTd, the TdLoss, the workspace, which must outlive the library call)."""
         torch = self._torch
-        who = "td_loss"
         if kind not in ("dqn", "td3", "sac"):
             raise ValueError(f"{who}: kind must be 'dqn', 'td3' or 'sac', got {kind!r}")
         dqn, sac = kind == "dqn", kind == "sac"
@@ -1300,29 +1310,83 @@ class TrainOps:
                 raise ValueError(f"{who}: want_target, but out.target is None")
             check(self, who, "out.target", target, dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
             _no_tensor_twice(who, gs + qs + nqs + ([target] if target is not None else []), "out.grad_q, out.target, q and next_q")
-        workspace = self._take_workspace(who, B, workspace)
-        if out is None:
-            with torch.cuda.device(self.device):
-                stats = torch.empty(8, dtype=torch.float64, device=self.device)
-                g_q = [torch.empty(tuple(t.shape), dtype=x.dtype, device=self.device) for t in ([q] if dqn else q)]
-                gs = g_q if dqn else [_column(self, t) for t in g_q]
-                g_q = g_q[0] if dqn else g_q
-                target = torch.empty(B, dtype=x.dtype, device=self.device) if want_target else None
-        d = _lib.PtgTd(kind=_lib.TD_DQN if dqn else _lib.TD_CRITICS,
-                       flags=(_lib.TD_ENTROPY if sac else 0) | (_lib.TD_LOG_ALPHA if log_ent_coef is not None else 0),
-                       n_actions=A, n_critics=0 if dqn else K, q_dtype=_out_code(torch, x.dtype),
-                       act_kind=_lib.ACT_I64 if dqn and actions.dtype == torch.int64 else _lib.ACT_I32,
-                       rew_dtype=_out_code(torch, rewards.dtype), done_dtype=_out_code(torch, dones.dtype), batch=B,
-                       act_dev=_ptr(actions), rew_dev=_ptr(rewards), done_dev=_ptr(dones), next_logp_dev=_ptr(next_log_prob),
-                       alpha_dev=_ptr(alpha_dev), gamma=float(gamma), alpha=alpha, scale=0.5 if sac else 1.0,
-                       stats_dev=_ptr(stats), y_dev=_ptr(target), ws_dev=_ptr(workspace))
-        least = max(A, 1)
-        for k in range(K):
-            d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), least)
-            d.next_q_dev[k], d.next_s_n[k] = nqs[k].data_ptr(), max(nqs[k].stride(0), least)
-            d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), least)
-        self._call("ptg_td_loss", C.byref(d))
-        return TdLoss(stats, g_q, target)
+        self._take_workspace("td_loss", B, workspace, who=who, fresh=False)
+        agree = (("kind", kind), ("the number of actions", A), ("the number of critics", K), ("the dtype", x.dtype), ("the rewards' dtype", rewards.dtype),
+                 ("the dones' dtype", dones.dtype), ("the actions' dtype", actions.dtype if dqn else None), ("log_ent_coef given or not", log_ent_coef is not None),
+                 ("the batch", B))
+        theirs = None if out is None else (stats, g_q, gs, target)
+        given = ([] if out is None else [stats] + list(gs) + ([target] if target is not None else [])) + ([] if workspace is None else [workspace])
+
+        def make():
+            ws = self._loss_workspace("td_loss", B) if workspace is None else workspace
+            if theirs is None:
+                with torch.cuda.device(self.device):
+                    stats = torch.empty(8, dtype=torch.float64, device=self.device)
+                    g_q = [torch.empty(tuple(t.shape), dtype=x.dtype, device=self.device) for t in ([q] if dqn else q)]
+                    gs = g_q if dqn else [_column(self, t) for t in g_q]
+                    g_q = g_q[0] if dqn else g_q
+                    target = torch.empty(B, dtype=x.dtype, device=self.device) if want_target else None
+            else:
+                stats, g_q, gs, target = theirs
+            d = _lib.PtgTd(kind=_lib.TD_DQN if dqn else _lib.TD_CRITICS,
+                           flags=(_lib.TD_ENTROPY if sac else 0) | (_lib.TD_LOG_ALPHA if log_ent_coef is not None else 0),
+                           n_actions=A, n_critics=0 if dqn else K, q_dtype=_out_code(torch, x.dtype),
+                           act_kind=_lib.ACT_I64 if dqn and actions.dtype == torch.int64 else _lib.ACT_I32,
+                           rew_dtype=_out_code(torch, rewards.dtype), done_dtype=_out_code(torch, dones.dtype), batch=B,
+                           act_dev=_ptr(actions), rew_dev=_ptr(rewards), done_dev=_ptr(dones), next_logp_dev=_ptr(next_log_prob),
+                           alpha_dev=_ptr(alpha_dev), gamma=float(gamma), alpha=alpha, scale=0.5 if sac else 1.0,
+                           stats_dev=_ptr(stats), y_dev=_ptr(target), ws_dev=_ptr(ws))
+            least = max(A, 1)
+            for k in range(K):
+                d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), least)
+                d.next_q_dev[k], d.next_s_n[k] = nqs[k].data_ptr(), max(nqs[k].stride(0), least)
+                d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), least)
+            return d, TdLoss(stats, g_q, target), ws
+        return agree, make, given
+
+    def td_loss_group(self, kind, members, *, gamma=None, ent_coef=None, want_target=False):
+        """td_loss for G independent replay batches of ONE batch size, 1 <= G <= 8, in exactly the launches of one td_loss call
+        (include/ptg_env.h: ptg_td_loss_group): the agents of a seed sweep.  Every member's result is, bit for bit,
+        what td_loss gives for its arguments.  members: a list of G dicts of td_loss's arguments by name (q, next_q, rewards, dones, and
+        any of gamma, actions, next_log_prob, ent_coef, log_ent_coef, want_target, out, workspace); gamma, ent_coef and want_target here
+        are one value for the members that do not name them, or a list with one entry per member.  The members must agree in kind, A, K,
+        the dtypes, whether log_ent_coef is given, and B (ValueError, which names the two members); every scalar may differ, and one
+        member may bring a float ent_coef where another brings a device tensor.  No tensor may serve two members as an output or
+        workspace.  Checked as td_loss checks, member by member, the message behind "member i:"; the library is not touched and nothing is
+        allocated before every check has passed, and nothing at all when every member brings out= and workspace=.  Returns the list of G
+        TdLoss.  Cost: profiles/offpolicy_group_cost.txt; DESIGN.md section 27."""
+        made = self._train_group("td_loss_group", "td_loss", members, ("q", "next_q", "rewards", "dones", "gamma"),
+                                 ("actions", "next_log_prob", "ent_coef", "log_ent_coef", "want_target", "out", "workspace"),
+                                 dict(gamma=gamma, ent_coef=ent_coef, want_target=want_target), lambda who, kw: self._td_loss_member(who, kind, **kw))
+        self._call("ptg_td_loss_group", (_lib.PtgTd * len(made))(*[m[0] for m in made]), len(made))      # made holds the workspaces until here
+        return [m[1] for m in made]
+
+    def _train_group(self, who, single, members, needs, takes, shared, member):
+        """What the grouped off-policy ops share: the members' container and count, the keyword defaults (one value, or a list with one
+        per member; None: no default), every member through the single op's check function member(who_i, kwargs) in order, the
+        agreement, no output or workspace twice -- then, and only then, every member's make().  Returns the list of what make() gave."""
+        if not isinstance(members, (list, tuple)) or not all(isinstance(m, dict) for m in members):
+            raise TypeError(f"{who}: members must be a list of dicts of {single}'s arguments, got {type(members).__name__}")
+        G = len(members)
+        if not 1 <= G <= _lib.TRAIN_GROUP_MAX:
+            raise ValueError(f"{who}: 1 to {_lib.TRAIN_GROUP_MAX} members, got {G}")
+        for name, v in shared.items():
+            if isinstance(v, list) and len(v) != G:
+                raise ValueError(f"{who}: {name} must have one entry per member, {G}, or be one value for all; got {len(v)}")
+        checked = []
+        for i, m in enumerate(members):
+            kw = {name: (v[i] if isinstance(v, list) else v) for name, v in shared.items() if v is not None}
+            kw.update(m)
+            missing, unknown = [k for k in needs if k not in kw], [k for k in kw if k not in needs and k not in takes]
+            if missing or unknown:
+                raise TypeError(f"{who}: member {i}: a member names {single}'s arguments; missing {missing}, unknown {unknown}")
+            checked.append(member(f"{who}: member {i}", kw))
+        for i, (agree, _, _) in enumerate(checked):
+            for (name, a), (_, b) in zip(checked[0][0], agree):
+                if a != b:
+                    raise ValueError(f"{who}: members 0 and {i} disagree in {name}: {a} and {b}")
+        _no_tensor_twice(who, [t for _, _, given in checked for t in given], "the members' outputs, counters and workspaces")
+        return [make() for _, make, _ in checked]
 
     # ------------------------------------------------------------------ TQC's quantile-Huber critic loss and its gradients
     def quantile_loss_workspace(self, batch):
@@ -1433,8 +1497,15 @@ class TrainOps:
         Returns RSample(actions, log_prob in the inputs' dtype and shaped like mean, noise float64: z, which rsample_backward reads).
         out: an earlier result, reused by a captured call; its log_prob and noise may be None (not written).  No synchronisation; a
         non-finite mean or a NaN log_std gives NaN outputs and PTG_E_NONFINITE at the next sync()."""
+        d, res = self._rsample_member("rsample", mean, log_std, counter, seed=seed, deterministic=deterministic, out=out)[1]()
+        self._call("ptg_rsample", C.byref(d))
+        return res
+
+    def _rsample_member(self, who, mean, log_std, counter, seed=0, deterministic=False, out=None):
+        """Every check of ONE rsample call, in rsample's order, for rsample and for each member of rsample_group.  Allocates nothing and does
+        not touch the library.  Returns (what a group must agree in; make; the outputs the caller gave and the counter a stochastic call
+        advances), where make() allocates what was not given and returns (the PtgRs, the RSample)."""
         torch = self._torch
-        who = "rsample"
         m, ls, B = self._rs_rows(who, mean, log_std)
         if ls is None:
             raise TypeError(f"{who}: log_std must be a tensor, got NoneType")
@@ -1444,15 +1515,34 @@ class TrainOps:
             check(self, who, "out.actions", _column(self, act), dtypes=(m.dtype,), shape=(B,), rule=contiguous, exc=ValueError)
             check(self, who, "out.log_prob", _column(self, lp), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
             check(self, who, "out.noise", _column(self, noise), dtypes=(torch.float64,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
-        else:
-            with torch.cuda.device(self.device):
-                act, lp = (torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device) for _ in range(2))
-                noise = torch.empty(tuple(mean.shape), dtype=torch.float64, device=self.device)
-        d = _lib.PtgRs(kind=_lib.RS_SQUASH, flags=_lib.RS_DETERMINISTIC if deterministic else 0, q_dtype=_out_code(torch, m.dtype), batch=B,
-                       mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1), log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1),
-                       seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), act_dev=_ptr(act), logp_dev=_ptr(lp), noise_dev=_ptr(noise))
-        self._call("ptg_rsample", C.byref(d))
-        return RSample(act, lp, noise)
+        agree = (("the dtype", m.dtype), ("deterministic", bool(deterministic)), ("the batch", B))
+        given = ([] if out is None else [t for t in out if t is not None]) + ([] if deterministic or counter is None else [counter])
+
+        def make():
+            if out is None:
+                with torch.cuda.device(self.device):
+                    act, lp = (torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device) for _ in range(2))
+                    noise = torch.empty(tuple(mean.shape), dtype=torch.float64, device=self.device)
+            else:
+                act, lp, noise = out
+            d = _lib.PtgRs(kind=_lib.RS_SQUASH, flags=_lib.RS_DETERMINISTIC if deterministic else 0, q_dtype=_out_code(torch, m.dtype), batch=B,
+                           mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1), log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1),
+                           seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), act_dev=_ptr(act), logp_dev=_ptr(lp), noise_dev=_ptr(noise))
+            return d, RSample(act, lp, noise)
+        return agree, make, given
+
+    def rsample_group(self, members, *, seed=0, deterministic=False):
+        """rsample for G independent actors' outputs of ONE batch size, 1 <= G <= 8, in exactly the launches of one rsample call
+        (include/ptg_env.h: ptg_rsample_group).  Every member's actions, log-probs and noise are, bit for bit, what
+        rsample gives for its arguments, and every member's counter advances by one.  members: a list of G dicts of rsample's arguments
+        by name (mean, log_std, counter, and any of seed, out); seed is one value for the members that do not name it, or a list with
+        one per member; deterministic is the group's.  The members must agree in the dtype and B; no tensor may serve two members as an
+        output, and no counter two members: the grouped call reads every counter before any is advanced.  Checked as rsample checks, member
+        by member, the message behind "member i:".  Returns the list of G RSample."""
+        made = self._train_group("rsample_group", "rsample", members, ("mean", "log_std", "counter"), ("seed", "out"), dict(seed=seed),
+                                 lambda who, kw: self._rsample_member(who, deterministic=deterministic, **kw))
+        self._call("ptg_rsample_group", (_lib.PtgRs * len(made))(*[m[0] for m in made]), len(made))
+        return [m[1] for m in made]
 
     def rsample_backward(self, mean, log_std, noise, grad_actions, grad_log_prob, out=None):
         """Enqueue, on the current stream, the backward of rsample (include/ptg_env.h: ptg_rsample_backward): from the same mean and log_std,
@@ -1460,8 +1550,14 @@ class TrainOps:
         dtype; either may be None = 0, not both), the gradients with respect to mean and to the unclamped log_std (0 outside the clamp).
         Returns RSampleGrad(grad_mean, grad_log_std), shaped like mean and log_std; out: such a pair, any stride >= 1.  No synchronisation;
         a non-finite input row gives NaN gradients and PTG_E_NONFINITE at the next sync()."""
+        d, res = self._rsample_backward_member("rsample_backward", mean, log_std, noise, grad_actions, grad_log_prob, out=out)[1]()
+        self._call("ptg_rsample_backward", C.byref(d))
+        return res
+
+    def _rsample_backward_member(self, who, mean, log_std, noise, grad_actions, grad_log_prob, out=None):
+        """Every check of ONE rsample_backward call, in its order, for rsample_backward and for each member of rsample_backward_group;
+        returns (agree, make, given) as _rsample_member does, make() giving (the PtgRs, the RSampleGrad)"""
         torch = self._torch
-        who = "rsample_backward"
         m, ls, B = self._rs_rows(who, mean, log_std)
         if ls is None:
             raise TypeError(f"{who}: log_std must be a tensor, got NoneType")
@@ -1473,26 +1569,48 @@ class TrainOps:
             raise ValueError(f"{who}: grad_actions and grad_log_prob are both None")
         if out is not None:
             gm, gs = _out_tuple(self, who, out, RSampleGrad, stats=False)
-            gm1 = check(self, who, "out.grad_mean", _column(self, gm), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
-            gs1 = check(self, who, "out.grad_log_std", _column(self, gs), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
-        else:
-            with torch.cuda.device(self.device):
-                gm = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
-                gs = torch.empty(tuple(log_std.shape), dtype=m.dtype, device=self.device)
+            check(self, who, "out.grad_mean", _column(self, gm), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+            check(self, who, "out.grad_log_std", _column(self, gs), dtypes=dt, shape=(B,), rule=step, exc=ValueError)
+        agree = (("the dtype", m.dtype), ("the batch", B))
+        given = [] if out is None else list(out)
+
+        def make():
+            if out is None:
+                with torch.cuda.device(self.device):
+                    gm = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
+                    gs = torch.empty(tuple(log_std.shape), dtype=m.dtype, device=self.device)
+            else:
+                gm, gs = out
             gm1, gs1 = _column(self, gm), _column(self, gs)
-        d = _lib.PtgRs(kind=_lib.RS_SQUASH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
-                       log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1), noise_dev=_ptr(noise), grad_act_dev=_ptr(ga), grad_logp_dev=_ptr(gl),
-                       grad_mean_dev=_ptr(gm1), gm_s_n=max(gm1.stride(0), 1), grad_log_std_dev=_ptr(gs1), gl_s_n=max(gs1.stride(0), 1))
-        self._call("ptg_rsample_backward", C.byref(d))
-        return RSampleGrad(gm, gs)
+            d = _lib.PtgRs(kind=_lib.RS_SQUASH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
+                           log_std_dev=_ptr(ls), log_std_s_n=max(ls.stride(0), 1), noise_dev=_ptr(noise), grad_act_dev=_ptr(ga), grad_logp_dev=_ptr(gl),
+                           grad_mean_dev=_ptr(gm1), gm_s_n=max(gm1.stride(0), 1), grad_log_std_dev=_ptr(gs1), gl_s_n=max(gs1.stride(0), 1))
+            return d, RSampleGrad(gm, gs)
+        return agree, make, given
+
+    def rsample_backward_group(self, members):
+        """rsample_backward for G members of ONE batch size and dtype, 1 <= G <= 8, in one launch (include/ptg_env.h:
+        ptg_rsample_backward_group): every member's two gradients are, bit for bit, what rsample_backward gives for
+        its arguments.  members: a list of G dicts of rsample_backward's arguments by name (mean, log_std, noise, grad_actions,
+        grad_log_prob -- either may be None, member by member -- and out).  Returns the list of G RSampleGrad."""
+        made = self._train_group("rsample_backward_group", "rsample_backward", members, ("mean", "log_std", "noise", "grad_actions", "grad_log_prob"), ("out",), {},
+                                 lambda who, kw: self._rsample_backward_member(who, **kw))
+        self._call("ptg_rsample_backward_group", (_lib.PtgRs * len(made))(*[m[0] for m in made]), len(made))
+        return [m[1] for m in made]
 
     def smooth_target_action(self, mean, counter, noise_std, noise_clip, clip=(-1.0, 1.0), seed=0, out=None):
         """Enqueue, on the current stream, TD3.train's target-policy smoothing (include/ptg_env.h: ptg_rsample, PTG_RS_SMOOTH):
         clip(mean + clip(noise_std * z, -noise_clip, noise_clip), clip[0], clip[1]) with rsample's draw.  mean = actor_target(next_obs),
         [B] or [B, 1], float32 / float64, any stride >= 1.  Returns the actions, shaped like mean (out: such a tensor, contiguous).
         The counter advances by one on the device.  No synchronisation; a non-finite mean gives NaN and PTG_E_NONFINITE at the next sync()."""
+        d, res = self._smooth_member("smooth_target_action", mean, counter, noise_std, noise_clip, clip=clip, seed=seed, out=out)[1]()
+        self._call("ptg_rsample", C.byref(d))
+        return res
+
+    def _smooth_member(self, who, mean, counter, noise_std, noise_clip, clip=(-1.0, 1.0), seed=0, out=None):
+        """Every check of ONE smooth_target_action call, in its order, for it and for each member of smooth_target_action_group; returns
+        (agree, make, given) as _rsample_member does, make() giving (the PtgRs, the actions)"""
         torch = self._torch
-        who = "smooth_target_action"
         m, _, B = self._rs_rows(who, mean, None)
         counter = self._act_counter(who, counter, False)
         sd, c, lo, hi = float(noise_std), float(noise_clip), float(clip[0]), float(clip[1])
@@ -1501,13 +1619,30 @@ class TrainOps:
         if not lo <= hi:
             raise ValueError(f"{who}: clip {clip} is not an interval")
         check(self, who, "out", _column(self, out), dtypes=(m.dtype,), shape=(B,), rule=contiguous, optional=True, exc=ValueError)
-        if out is None:
-            with torch.cuda.device(self.device):
-                out = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
-        d = _lib.PtgRs(kind=_lib.RS_SMOOTH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
-                       seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), noise_std=sd, noise_clip=c, clip_lo=lo, clip_hi=hi, act_dev=_ptr(out))
-        self._call("ptg_rsample", C.byref(d))
-        return out
+        agree = (("the dtype", m.dtype), ("the batch", B))
+        given = ([] if out is None else [out]) + [counter]
+
+        def make():
+            act = out
+            if act is None:
+                with torch.cuda.device(self.device):
+                    act = torch.empty(tuple(mean.shape), dtype=m.dtype, device=self.device)
+            d = _lib.PtgRs(kind=_lib.RS_SMOOTH, q_dtype=_out_code(torch, m.dtype), batch=B, mean_dev=_ptr(m), mean_s_n=max(m.stride(0), 1),
+                           seed=int(seed) & (2 ** 64 - 1), counter_dev=_ptr(counter), noise_std=sd, noise_clip=c, clip_lo=lo, clip_hi=hi, act_dev=_ptr(act))
+            return d, act
+        return agree, make, given
+
+    def smooth_target_action_group(self, members, *, noise_std=None, noise_clip=None, clip=(-1.0, 1.0), seed=0):
+        """smooth_target_action for G target actors' outputs of ONE batch size and dtype, 1 <= G <= 8, in the two launches of one call
+        (include/ptg_env.h: ptg_rsample_group with PTG_RS_SMOOTH); every member's actions are, bit for bit, what
+        smooth_target_action gives for its arguments, and every member's counter advances by one.  members: a list of G dicts (mean,
+        counter, and any of noise_std, noise_clip, clip, seed, out); noise_std, noise_clip, clip (a tuple) and seed here are one value
+        for the members that do not name them, or a list with one per member.  No counter may serve two members.  Returns the list of G
+        action tensors."""
+        made = self._train_group("smooth_target_action_group", "smooth_target_action", members, ("mean", "counter", "noise_std", "noise_clip"), ("clip", "seed", "out"),
+                                 dict(noise_std=noise_std, noise_clip=noise_clip, clip=clip, seed=seed), lambda who, kw: self._smooth_member(who, **kw))
+        self._call("ptg_rsample_group", (_lib.PtgRs * len(made))(*[m[0] for m in made]), len(made))
+        return [m[1] for m in made]
 
     # ------------------------------------------------------------------ the actor and entropy-coefficient losses and their gradients
     def actor_loss_workspace(self, batch):
@@ -1529,8 +1664,15 @@ class TrainOps:
         grad_log_ent_coef float64 [1] (None without target_entropy)).  out: an earlier result, reused by a captured call (its
         grad_log_prob and grad_log_ent_coef may be None: not written); workspace: actor_loss_workspace(B) or larger.  No synchronisation;
         a non-finite row makes the next sync() raise PtgError (PTG_E_NONFINITE)."""
+        d, res, _ = self._actor_loss_member("actor_loss", kind, q=q, log_prob=log_prob, ent_coef=ent_coef, log_ent_coef=log_ent_coef, target_entropy=target_entropy,
+                                            out=out, workspace=workspace)[1]()
+        self._call("ptg_actor_loss", C.byref(d))
+        return res
+
+    def _actor_loss_member(self, who, kind, q=None, log_prob=None, ent_coef=None, log_ent_coef=None, target_entropy=None, out=None, workspace=None):
+        """Every check of ONE actor-loss call, in actor_loss's order, for actor_loss and for each member of actor_loss_group; returns
+        (agree, make, given) as _td_loss_member does, make() giving (the PtgAl, the ActorLoss, the workspace)"""
         torch = self._torch
-        who = "actor_loss"
         if kind not in ("sac", "tqc", "td3", "ent_coef"):
             raise ValueError(f"{who}: kind must be 'sac', 'tqc', 'td3' or 'ent_coef', got {kind!r}")
         floats = (torch.float32, torch.float64)
@@ -1598,28 +1740,52 @@ class TrainOps:
             check(self, who, "out.grad_log_prob", _column(self, g_lp), dtypes=dt, shape=(B,), rule=contiguous, optional=True, exc=ValueError)
             check(self, who, "out.grad_log_ent_coef", g_la, dtypes=(torch.float64,), shape=(1,), optional=True, exc=ValueError)
             _no_tensor_twice(who, list(gs) + qs + [x for x in (lp, g_lp) if x is not None], "out.grad_q, out.grad_log_prob, q and log_prob")
-        workspace = self._take_workspace(who, B, workspace)
-        if out is None:
-            with torch.cuda.device(self.device):
-                mk = lambda shape, d=dt[0]: torch.empty(tuple(shape), dtype=d, device=self.device)
-                stats = mk((8,), torch.float64)
-                if kind == "tqc":
-                    g_q, gs = self._fresh_like_quantiles(as_list, B, K, Q, dt[0])
-                elif not only:
-                    g_list = [mk(t.shape) for t in (q if as_list else [q])]
-                    gs, g_q = [_column(self, t) for t in g_list], (g_list if as_list else g_list[0])
-                g_lp = mk(log_prob.shape) if not (td3 or only) else None
-                g_la = mk((1,), torch.float64) if ec else None
-        flags = (0 if td3 or only else _lib.AL_ENTROPY) | (_lib.AL_LOG_ALPHA if log_ent_coef is not None else 0) | (_lib.AL_ENT_COEF if ec else 0)
-        d = _lib.PtgAl(kind=_lib.AL_ALPHA_ONLY if only else (_lib.AL_MIN if kind == "sac" else _lib.AL_MEAN), flags=flags, n_critics=K, n_quantiles=Q,
-                       q_dtype=_out_code(torch, dt[0]), batch=B, logp_dev=_ptr(lp), alpha_dev=_ptr(alpha_dev), alpha=alpha,
-                       target_entropy=float(target_entropy) if ec else 0.0, stats_dev=_ptr(stats), grad_logp_dev=_ptr(_column(self, g_lp)),
-                       grad_log_alpha_dev=_ptr(g_la), ws_dev=_ptr(workspace))
-        for k in range(K):
-            d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), Q)
-            d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), Q)
-        self._call("ptg_actor_loss", C.byref(d))
-        return ActorLoss(stats, g_q, g_lp, g_la)
+        self._take_workspace("actor_loss", B, workspace, who=who, fresh=False)
+        agree = (("kind", kind), ("the number of critics", K), ("the number of quantiles", Q), ("the dtype", dt[0]), ("log_ent_coef given or not", log_ent_coef is not None),
+                 ("target_entropy given or not", ec), ("the batch", B))
+        theirs = None if out is None else (stats, g_q, gs, g_lp, g_la)
+        given = ([] if out is None else [stats] + list(gs) + [t for t in (g_lp, g_la) if t is not None]) + ([] if workspace is None else [workspace])
+
+        def make():
+            ws = self._loss_workspace("actor_loss", B) if workspace is None else workspace
+            g_q = gs = None
+            if theirs is None:
+                with torch.cuda.device(self.device):
+                    mk = lambda shape, d=dt[0]: torch.empty(tuple(shape), dtype=d, device=self.device)
+                    stats = mk((8,), torch.float64)
+                    if kind == "tqc":
+                        g_q, gs = self._fresh_like_quantiles(as_list, B, K, Q, dt[0])
+                    elif not only:
+                        g_list = [mk(t.shape) for t in (q if as_list else [q])]
+                        gs, g_q = [_column(self, t) for t in g_list], (g_list if as_list else g_list[0])
+                    g_lp = mk(log_prob.shape) if not (td3 or only) else None
+                    g_la = mk((1,), torch.float64) if ec else None
+            else:
+                stats, g_q, gs, g_lp, g_la = theirs
+            flags = (0 if td3 or only else _lib.AL_ENTROPY) | (_lib.AL_LOG_ALPHA if log_ent_coef is not None else 0) | (_lib.AL_ENT_COEF if ec else 0)
+            d = _lib.PtgAl(kind=_lib.AL_ALPHA_ONLY if only else (_lib.AL_MIN if kind == "sac" else _lib.AL_MEAN), flags=flags, n_critics=K, n_quantiles=Q,
+                           q_dtype=_out_code(torch, dt[0]), batch=B, logp_dev=_ptr(lp), alpha_dev=_ptr(alpha_dev), alpha=alpha,
+                           target_entropy=float(target_entropy) if ec else 0.0, stats_dev=_ptr(stats), grad_logp_dev=_ptr(_column(self, g_lp)),
+                           grad_log_alpha_dev=_ptr(g_la), ws_dev=_ptr(ws))
+            for k in range(K):
+                d.q_dev[k], d.q_s_n[k] = qs[k].data_ptr(), max(qs[k].stride(0), Q)
+                d.grad_q_dev[k], d.g_s_n[k] = gs[k].data_ptr(), max(gs[k].stride(0), Q)
+            return d, ActorLoss(stats, g_q, g_lp, g_la), ws
+        return agree, make, given
+
+    def actor_loss_group(self, kind, members, *, ent_coef=None, target_entropy=None):
+        """actor_loss for G independent agents' batches of ONE batch size, 1 <= G <= 8, in exactly the launches of one actor_loss call
+        (include/ptg_env.h: ptg_actor_loss_group).  Every member's result is, bit for bit, what actor_loss gives
+        for its arguments.  members: a list of G dicts of actor_loss's arguments by name (any of q, log_prob, ent_coef, log_ent_coef,
+        target_entropy, out, workspace, as the kind asks); ent_coef and target_entropy here are one value for the members that do not name
+        them, or a list with one per member.  The members must agree in kind, K, Q, the dtype, whether log_ent_coef and target_entropy are
+        given, and B; every scalar may differ.  No tensor may serve two members as an output or workspace.  Checked as actor_loss checks,
+        member by member, the message behind "member i:"; nothing is allocated and the library is not touched before every check has
+        passed.  Returns the list of G ActorLoss."""
+        made = self._train_group("actor_loss_group", "actor_loss", members, (), ("q", "log_prob", "ent_coef", "log_ent_coef", "target_entropy", "out", "workspace"),
+                                 dict(ent_coef=ent_coef, target_entropy=target_entropy), lambda who, kw: self._actor_loss_member(who, kind, **kw))
+        self._call("ptg_actor_loss_group", (_lib.PtgAl * len(made))(*[m[0] for m in made]), len(made))      # made holds the workspaces until here
+        return [m[1] for m in made]
 
     # ------------------------------------------------------------------ the inference forward of an MLP
     def mlp_workspace(self, batch, widths, keep_hidden=False):
